@@ -7,12 +7,19 @@ launches it under torch.distributed.run (one rank per GPU, RCCL).  A "step" is o
 one batch of synthetic actions that is already resident in HBM.  W untimed steps, then EXACTLY K timed
 steps bracketed by barrier + synchronize, MAX over ranks, one JSON line from rank 0.
 
+A plain run does only what the headline needs: set-up, a fixed untimed pre-roll, the W warm-up steps, the K timed steps and the
+line (`ms_per_step` = milliseconds of one timed step, wall clock).  `--dump-outputs DIR` writes what the last timed step returned
+(obs, reward, done, truncated, found_targets) as DIR/<name>.npy; the inputs are seeded and the pre-roll is a fixed number of steps, so
+the same arguments give the same arrays on every run.  Every other measurement (launch shapes, sub-legs, 2 M-drone fleets, fleet
+sweep, copy ceiling, NumPy surface, policy-in-the-loop legs, CPU baseline, the sharded leg) runs only with `--full`.
+
 Workload = BASELINE.json configs[2]: 32 768 drones per GPU on the 8-gate race track
 (`Waypoints.reaching()`), norm_rew off, positional observation; actions U(-1,1)^4 float32 from a seeded
 generator (the bang-bang regime that exercises the auto-reset path constantly).
 The path shards embarrassingly (no data-path collective): weak scaling, 32 768 drones per rank.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (`roofline` in every run, its `kernel_only`, `single_step_*`, `hover_*` and `hbm_bound_*` fields and
+the other objects with `--full`):
   roofline     -- HBM roofline of the kernel the timed region launches.  ALGORITHMIC bytes over the average
                   launch duration measured with HIP events on the launch stream over the timed region; peak 8 TB/s
                   (MI355X_MICROARCH.md).  Per drone a single-step launch (dn_step) moves 288 B (+432 B with the obs
@@ -43,7 +50,12 @@ ALGO_BYTES_IO_PER_STEP = 78            # of which per step whatever the launch s
 ALGO_BYTES_STATE = 210                 # and once per LAUNCH: state R+W 104 + bookkeeping R+W 106 (registers hold it between fused steps)
 ALGO_BYTES_NORMALISER = 432            # per-drone NormalizeObservation statistics, 27 float64 R+W (once per launch)
 HBM_PEAK_GBPS = 8000.0                 # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-PREROLL_SECONDS = 0.5                  # untimed fused stepping before the warm-up: the GPU clock needs ~50 ms of load to settle
+# untimed fused stepping before the warm-up: the GPU clock needs ~50 ms of load to settle.  A fixed count, so that the timed region
+# starts from the same fleet state on every run: what 0.5 s of stepping was at 32 768 drones (76 x 4096 vector steps), and no more
+# drone-steps than that on larger fleets.  A timed region of one short launch (--steps 20) depends on that state by a few per cent.
+PREROLL_VECTOR_STEPS = 76 * 4096
+PREROLL_DRONE_STEPS = PREROLL_VECTOR_STEPS * 32768
+DUMP_MAX_BYTES = 64 * 10 ** 6          # --dump-outputs: at most this much in all, files included (a fixed sample of drones beyond it)
 
 
 def algo_bytes_per_launch(n, steps_per_launch, norm):
@@ -142,6 +154,26 @@ def fast_path_hit_rate(torch, acts):
     return float(sat.view(a_, m // 64, 64, 4).all(dim=2).float().mean().item())
 
 
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """Write `arrays` (NumPy, drone-major: row i belongs to drone i) as path/<name>.npy, integers and booleans as float32 (exact for the
+    values the step returns).  If they exceed max_bytes together, the same fixed, seeded sample of rows is written from every array and
+    its drone indices go to path/drone_index.npy (float64).  Returns the names written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)) for k, a in
+              ((k, np.asarray(v)) for k, v in arrays.items())}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // n for a in arrays.values())
+    budget = max_bytes - 256 * (len(arrays) + 1)          # room for the .npy headers (128 bytes each for these shapes)
+    if n * row_bytes > budget:
+        rows = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+        arrays = dict({k: a[idx] for k, a in arrays.items()}, drone_index=idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -169,7 +201,7 @@ def parse():
     ap.add_argument("--no-ppo-rollout", action="store_true", help="skip the policy-in-the-loop rollout measurement")
     ap.add_argument("--ppo-sharded", dest="ppo_sharded", action="store_true", default=None,
                     help="BASELINE configs[3]: also time the policy-in-the-loop rollout on every rank with the per-rollout RCCL "
-                         "all-gather of advantages/returns.  On by default whenever WORLD_SIZE > 1 (the one collective the design "
+                         "all-gather of advantages/returns.  On by default with --full whenever WORLD_SIZE > 1 (the one collective the design "
                          "has must be seen by the scaling run); a watchdog ends the process with a non-zero code if it hangs")
     ap.add_argument("--no-ppo-sharded", dest="ppo_sharded", action="store_false")
     ap.add_argument("--sharded-timeout", type=float, default=240.0, help="seconds the sharded leg may take before the watchdog exits(3)")
@@ -178,7 +210,17 @@ def parse():
                          "no NumPy-surface legs; timings of such a run mean nothing, only the counters do")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group even for one rank (exercises the N > 1 code path on a 1-GPU box)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other measurement: launch shapes, the other normaliser setting, hover band, 2 M-drone "
+                         "fleets, copy ceiling, fleet sweep, NumPy surface, policy-in-the-loop legs, CPU baseline (the --no-* options "
+                         "still drop single legs), and the sharded leg when WORLD_SIZE > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, done, truncated, found_targets; float32) as DIR/<name>.npy, "
+                         f"at most {DUMP_MAX_BYTES // 10 ** 6} MB (a fixed sample of drones beyond it); DIR/rank<r>/ on each rank when WORLD_SIZE > 1")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(track, num_envs, max_steps, seconds, normalize_obs=True):
@@ -621,11 +663,12 @@ def main():
     # untimed pre-roll, independent of --warmup: the clock of an idle GPU takes ~50 ms of load to settle, and the
     # driver's default (--steps 20 --warmup 5) is a 40 us timed region
     t_pre = time.perf_counter()
-    pre_steps = 0
-    while time.perf_counter() - t_pre < (0.0 if args.profile_lite else PREROLL_SECONDS):
-        run_many(64 * A)
+    chunk = 64 * A
+    pre_steps = 0 if args.profile_lite else -(-min(PREROLL_VECTOR_STEPS, PREROLL_DRONE_STEPS // n) // chunk) * chunk
+    for _ in range(pre_steps // chunk):
+        run_many(chunk)
         torch.cuda.synchronize(dev)
-        pre_steps += 64 * A
+    pre_seconds = time.perf_counter() - t_pre
     run(W)
     torch.cuda.synchronize(dev)
     barrier()
@@ -653,6 +696,15 @@ def main():
     if os.environ.get("DN_BENCH_DEBUG"):
         print(f"timed region: rec0 {(ta - t0) * 1e6:.1f} run {(tb - ta) * 1e6:.1f} rec1 {(tc - tb) * 1e6:.1f} sync {(td - tc) * 1e6:.1f} us", file=sys.stderr)
     gpu_ms = e0.elapsed_time(e1)                          # HIP events on the launch stream, timed region only
+    if args.dump_outputs:
+        # the last timed step's outputs, before anything below launches again into the same buffers: in every mode step t of the
+        # region wrote slot t % A of the step-major [A, n, ...] buffers
+        j = (K - 1) % A
+        dump_outputs(os.path.join(args.dump_outputs, f"rank{rank}") if world > 1 else args.dump_outputs,
+                     {"obs": o["obs"][j].cpu().numpy(), "reward": o["reward"][j].cpu().numpy(), "done": o["done"][j].cpu().numpy(),
+                      "truncated": o["trunc"][j].cpu().numpy(), "found_targets": o["found"][j].cpu().numpy()},
+                     max_bytes=DUMP_MAX_BYTES // world)
+
     def kernel_only(handle, fn, k):
         """The same k-step launch with its own dispatch's begin / end stamps (dn_set_launch_events -> hipExtLaunchKernelGGL): the kernel's
         duration as rocprofv3 --kernel-trace reports it (marker events also see the ~1 us between a marker and the kernel).  Median of 5."""
@@ -668,7 +720,7 @@ def main():
         return sorted(reps_)[len(reps_) // 2]
 
     kernel_only_us = None
-    if args.mode == "many" and K <= A and not args.profile_lite:      # (not in the counter passes: these launches take another dispatch path)
+    if args.full and args.mode == "many" and K <= A and not args.profile_lite:      # (not in the counter passes: another dispatch path)
         kernel_only_us = kernel_only(h, run, K)                       # OUTSIDE the region the wall clock brackets
     if dist is not None:
         tw = torch.tensor([wall, gpu_ms], dtype=torch.float64, device=dev)
@@ -699,8 +751,8 @@ def main():
     # hipGraph (GPU timeline only), "many" = the fused K-step kernel
     k_single = (8192 if not args.profile_lite else 2 * A) // A * A if A <= 8192 else A
     k_many = max(A, (32768 if not args.profile_lite else 4 * A) // A * A)
-    others = {}
-    for m_ in ("many", "single", "graph"):
+    others, single_step = {}, {}
+    for m_ in (("many", "single", "graph") if args.full else ()):
         if world > 1 and m_ == "graph":
             continue
         fn = {"many": run_many, "single": run_single, "graph": run_graph}[m_]
@@ -708,15 +760,16 @@ def main():
         wv = env.kernel_waves(fused=m_ == "many")
         d = leg(m_, fn, k_single if m_ != "many" else k_many, spl, args.normalize_obs, wv)
         others[m_] = d
-    single_step = dict(others["graph"] if "graph" in others else others["single"])
-    single_step["launched_from"] = "hipGraph replay of dn_step launches" if "graph" in others else "python loop of dn_step calls"
-    single_step["python_loop_us_per_vector_step"] = others["single"]["us_per_vector_step"]
+    if others:
+        single_step = dict(others["graph"] if "graph" in others else others["single"])
+        single_step["launched_from"] = "hipGraph replay of dn_step launches" if "graph" in others else "python loop of dn_step calls"
+        single_step["python_loop_us_per_vector_step"] = others["single"]["us_per_vector_step"]
 
     # the same workload with the normaliser switched the OTHER way (the headline has it on, as the reference does,
     # PBDroneSimulator.py:181; the sub-leg shows what the bare step costs)
     other_norm = not args.normalize_obs
     norm_leg = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             env_n = pkg.DroneVecEnv(track, n, max_steps=max_steps, normalize_obs=other_norm, compute_dtype=args.compute_dtype,
                                     env_id_offset=rank * n, device=dev)
@@ -754,7 +807,7 @@ def main():
     # evaluations; here every wave evaluates the float32 chain and episodes are long (no reset pass on most tile-steps) -- the regime a
     # trained policy lives in, timed so that the fast path cannot be read as tuning to the benchmark.
     hover_leg = None
-    if world == 1 and not args.profile_lite and args.mode == "many":
+    if world == 1 and args.full and not args.profile_lite and args.mode == "many":
         try:
             other_kind = "hover" if args.actions == "uniform" else "uniform"
             env_h = pkg.DroneVecEnv(track, n, max_steps=max_steps, normalize_obs=args.normalize_obs, compute_dtype=args.compute_dtype,
@@ -797,7 +850,7 @@ def main():
 
     # a measured stream-copy ceiling of THIS box beside the nominal 8 TB/s (a device-to-device copy of 1 GiB: read + write)
     copy_ceiling = None
-    if world == 1 and not args.profile_lite:
+    if world == 1 and args.full and not args.profile_lite:
         try:
             src = torch.empty(1 << 28, dtype=torch.float32, device=dev).fill_(1.0)
             dst = torch.empty_like(src)
@@ -874,7 +927,7 @@ def main():
         return d
 
     large = large_norm = None
-    if world == 1 and not args.profile_lite:
+    if world == 1 and args.full and not args.profile_lite:
         for norm_l in (True, False):
             try:
                 d_l = hbm_bound_leg(norm_l)
@@ -888,7 +941,7 @@ def main():
     # the fused launch on larger single-GPU fleets (BASELINE configs[3] / [4] hold 131 072 / 262 144 drones in all: on one GPU they are one fleet,
     # sharded they are the headline's 32 768 per GPU): dn_create's own shape pick per size, 64-step launches replayed from one hipGraph
     fleet_sweep = None
-    if world == 1 and not args.profile_lite and args.mode == "many":
+    if world == 1 and args.full and not args.profile_lite and args.mode == "many":
         fleet_sweep = {"what": "us per vector step of the fused launch (64 steps per launch, 20 launches replayed from one hipGraph, best of 3) at larger "
                                "fleets on ONE GPU, the shape dn_create picks at each size; workload as in the headline", "sizes": {}}
         for n_f in (65536, 131072, 262144):
@@ -912,7 +965,7 @@ def main():
 
     # the SB3 NumPy surface (PCIe-inclusive: H2D actions, D2H obs/reward/done/found, N info dicts built in Python);
     # host bound, reported for the record only
-    if world == 1 and not args.profile_lite:
+    if world == 1 and args.full and not args.profile_lite:
         import numpy as np
         a_np = acts[0].cpu().numpy()
         for mode_, fresh_ in (("full", True), ("sparse", True), ("sparse", False)):
@@ -967,7 +1020,7 @@ def main():
             "kernel_only_source": "dn_set_launch_events on 5 launches right after the timed region (median); rocprofv3 twin: profiles/r06_a_bench32k_k20.txt",
             "single_step_us": single_step.get("us_per_vector_step"), "single_step_frac": single_step.get("frac"),
             "single_step_source": "single_step leg of this line (dn_step launches replayed from a hipGraph, 288 + 432 B per drone)",
-            "fast_path_hit_rate": round(fast_path_hit_rate(torch, acts), 4),
+            "fast_path_hit_rate": round(fast_path_hit_rate(torch, acts), 4) if args.full else None,
             "hover_us_per_step": hover_leg["kernel_only_us_per_vector_step"] if hv_ok else None,
             "hover_frac": hover_leg["kernel_only_frac"] if hv_ok else None,
             "hover_fast_path_hit_rate": hover_leg["fast_path_hit_rate"] if hv_ok else None,
@@ -1001,8 +1054,9 @@ def main():
                        "ground_contact": ("on" if env.ground_contact else
                                           "resolved off by DN_GROUND_CONTACT_AUTO: on this track every point low enough to touch the floor is "
                                           "already outside the corridor of every segment, so the contact term of PBDroneEnv.py:699 cannot fire"),
-                       "preroll": {"seconds": PREROLL_SECONDS, "vector_steps": pre_steps,
-                                   "what": "untimed fused stepping before --warmup so that the timed region runs at a settled clock"}},
+                       "preroll": {"seconds": round(pre_seconds, 3), "vector_steps": pre_steps,
+                                   "what": "untimed fused stepping before --warmup so that the timed region runs at a settled clock; a fixed "
+                                           "number of steps, so that it starts from the same fleet state on every run"}},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": tsrc,
                          "traffic_frac": (round(traffic / (launch_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5) if traffic else None),
@@ -1033,17 +1087,20 @@ def main():
                                                "normaliser_off": {k_: large.get(k_) for k_ in ("us_per_vector_step", "achieved_GBps", "frac", "frac_of_copy_ceiling", "traffic_ratio")},
                                                "copy_ceiling_GBps": (copy_ceiling or {}).get("GBps")}
                                               if isinstance(large_norm, dict) and isinstance(large, dict) and "frac" in large_norm and "frac" in large else None)},
-            "single_step": single_step,
-            "hover_band": hover_leg,
-            ("normalize_obs_on" if other_norm else "normalize_obs_off"): norm_leg,
-            "hbm_bound_fleet_norm": large_norm,
-            "hbm_bound_fleet": large,
-            "hbm_copy_ceiling": copy_ceiling,
-            "other_launch_shapes": others,
-            "fleet_sweep": fleet_sweep,
         }
+        if args.full:
+            line.update({
+                "single_step": single_step,
+                "hover_band": hover_leg,
+                ("normalize_obs_on" if other_norm else "normalize_obs_off"): norm_leg,
+                "hbm_bound_fleet_norm": large_norm,
+                "hbm_bound_fleet": large,
+                "hbm_copy_ceiling": copy_ceiling,
+                "other_launch_shapes": others,
+                "fleet_sweep": fleet_sweep,
+            })
         # the two side legs must never cost the headline line: a failure is reported in place of the numbers
-        if world == 1 and not args.no_ppo_rollout:
+        if world == 1 and args.full and not args.no_ppo_rollout:
             try:
                 line["ppo_rollout"] = ppo_rollout(pkg, track, n, max_steps, dev, rank)
             except Exception as exc:  # noqa: BLE001
@@ -1052,16 +1109,16 @@ def main():
                 line["sac_collect"] = sac_collect(pkg, track, n, max_steps, dev, rank)
             except Exception as exc:  # noqa: BLE001
                 line["sac_collect"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(track, n, max_steps, args.cpu_baseline_seconds, args.normalize_obs)
             except Exception as exc:  # noqa: BLE001
                 line["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
     # BASELINE configs[3]: the one collective of the design (RCCL all-gather of advantages / returns per rollout), timed on every rank
-    # whenever WORLD_SIZE > 1.  It runs AFTER the headline line is assembled: an exception is reported inside the line, and if the
-    # collective hangs a watchdog thread ends THIS process with a non-zero code (never a re-exec) -- rank 0 printing the headline it
-    # already holds first, so that a scaling run does not lose its measurement to the optional leg.
-    want_sharded = (world > 1) if args.ppo_sharded is None else args.ppo_sharded
+    # whenever WORLD_SIZE > 1 with --full (or when --ppo-sharded asks for it).  It runs AFTER the headline line is assembled: an exception
+    # is reported inside the line, and if the collective hangs a watchdog thread ends THIS process with a non-zero code (never a re-exec)
+    # -- rank 0 printing the headline it already holds first, so that a scaling run does not lose its measurement to the optional leg.
+    want_sharded = (world > 1 and args.full) if args.ppo_sharded is None else args.ppo_sharded
     if want_sharded and dist is not None:
         import threading
 

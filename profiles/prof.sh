@@ -18,10 +18,10 @@ pass() {   # pass <name> <rocprofv3 arguments...>: a failed pass is recorded in 
     local name=$1; shift
     if ! "$@" > "$OUT/bench_$name.log" 2>&1; then FAILED="$FAILED $name"; fi
 }
-pass stats rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o stats -- python3 "$ROOT/bench.py" --no-cpu-baseline "$@"
+pass stats rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o stats -- python3 "$ROOT/bench.py" --full --no-cpu-baseline "$@"
 if [ "${DN_PROF_PMC:-1}" = "1" ]; then
-    pass fetch rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-ppo-rollout --profile-lite "$@"
-    pass write rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/write" -o write -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-ppo-rollout --profile-lite "$@"
+    pass fetch rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-ppo-rollout --profile-lite "$@"
+    pass write rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/write" -o write -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-ppo-rollout --profile-lite "$@"
 fi
 cd "$ROOT"
 python3 profiles/summarize.py "$OUT" > "$ROOT/gpurun_out/prof_$TAG.txt"

@@ -15,7 +15,7 @@ for n in sizes:
     row = {}
     for w in ("1", "2", "3"):
         env = dict(os.environ, DN_WAVES=w)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--num-envs", str(n), "--steps",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--num-envs", str(n), "--steps",
                               str(steps), "--warmup", str(max(ab, steps // 8 // ab * ab)), "--action-batches", str(ab), "--no-ppo-rollout"],
                              capture_output=True, text=True, env=env)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
