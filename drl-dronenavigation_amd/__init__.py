@@ -9,9 +9,11 @@ Importing this package needs the compiled library (there is no CPU fallback); bu
 from . import _capi, build, tracks  # noqa: F401
 from ._capi import DroneNavError, DroneNavLibraryError  # noqa: F401
 from .tracks import Track  # noqa: F401
+from .dynamics import DynamicsRandomization  # noqa: F401
 
 __all__ = ["DroneVecEnv", "Track", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
-           "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor"]
+           "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor",
+           "DynamicsRandomization"]
 
 
 def __getattr__(name):

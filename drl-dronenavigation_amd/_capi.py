@@ -66,6 +66,11 @@ class DnStats(C.Structure):
                 ("sum_ep_len", C.c_int64), ("sum_found_targets", C.c_int64), ("sum_ep_return", C.c_double)]
 
 
+class DnDynamicsConfig(C.Structure):
+    _fields_ = [("mass", C.c_float * 2), ("inertia", C.c_float * 2), ("kf", C.c_float * 2), ("km", C.c_float * 2),
+                ("resample", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every entry point declared in include/dronenav.h: name -> (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 PROTOTYPES = {
@@ -105,6 +110,10 @@ PROTOTYPES = {
     "dn_gae": (_I32, [_VP] * 5 + [_I64, _I64, C.c_double, C.c_double, _VP, _VP, _I32, _VP]),
     "dn_set_launch_events": (_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
+    "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),
+    "dn_set_dynamics": (_I32, [_VP, _VP, _VP]),
+    "dn_get_dynamics": (_I32, [_VP, _VP, _VP]),
+    "dn_get_dynamics_config": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),
 }
 
 _lib = None

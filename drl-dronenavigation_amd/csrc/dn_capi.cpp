@@ -92,6 +92,8 @@ struct dn_env {
     int waves_fused = 2;        // kernel shape of dn_step_many (k > 1), see dn_launch_step_many
     int waves_single = 1;       // kernel shape of dn_step (k == 1)
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // dn_set_launch_events: attached to the next step kernel's dispatch, then cleared
+    DnDyn dyn = {};             // dn_enable_dynamics: dyn.dyn is an allocation of its own (not in the arena: dn_state_bytes is unchanged)
+    dn_dynamics_config dyn_cfg = {};
 };
 
 thread_local hipEvent_t dn_tl_ev_start = nullptr, dn_tl_ev_stop = nullptr;
@@ -542,9 +544,11 @@ int32_t dn_destroy(dn_env *env)
 {
     if (!env) return DN_OK;
     hipError_t he = hipSuccess;
-    if (env->arena) {
-        (void)hipSetDevice(env->cfg.device_id);
-        he = hipFree(env->arena);
+    if (env->arena || env->dyn.dyn) (void)hipSetDevice(env->cfg.device_id);
+    if (env->arena) he = hipFree(env->arena);
+    if (env->dyn.dyn) {
+        const hipError_t hd = hipFree(env->dyn.dyn);
+        if (he == hipSuccess) he = hd;
     }
     delete env;
     if (he != hipSuccess) return fail(DN_ERR_HIP, "hipFree failed: %s", hipGetErrorString(he));
@@ -580,7 +584,7 @@ int32_t dn_reset(dn_env *env, float *obs, void *stream)
 {
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     if (!obs) return fail(DN_ERR_INVALID_ARGUMENT, "obs is NULL");
-    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream));
+    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn));
     return DN_OK;
 }
 
@@ -600,7 +604,7 @@ int32_t dn_step(dn_env *env, const float *actions, float *obs, float *reward, ui
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream));
+    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn));
     return DN_OK;
 }
 
@@ -618,6 +622,8 @@ int32_t dn_step_sampled(dn_env *env, const float *mean, const float *log_std, ui
     if (env->cfg.clip_rew || env->cfg.norm_rew || env->cfg.physics != 0 || env->cfg.action_type != 0 || env->cfg.random_spawn || env->cfg.zero_damping)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled is built for the configuration without reward wrappers / extra physics terms / RPM actions / random spawn / zero damping; "
                                              "use dn_policy_sample + dn_step there");
+    if (env->dyn.dyn)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_policy_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -644,6 +650,8 @@ int32_t dn_step_squashed(dn_env *env, const float *mu_log_std, uint64_t seed, in
     if (env->cfg.clip_rew || env->cfg.norm_rew || env->cfg.physics != 0 || env->cfg.action_type != 0 || env->cfg.random_spawn || env->cfg.zero_damping)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed is built for the configuration without reward wrappers / extra physics terms / RPM actions / random spawn / zero damping; "
                                              "use dn_squashed_sample + dn_step there");
+    if (env->dyn.dyn)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the randomised dynamics (dn_enable_dynamics); use dn_squashed_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -669,6 +677,8 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
     if (num_nets < 1 || num_nets > 2) return fail(DN_ERR_INVALID_ARGUMENT, "num_nets must be 1 (actor) or 2 (actor, critic)");
     if (obs_dim < 1 || obs_dim > 16) return fail(DN_ERR_INVALID_ARGUMENT, "obs_dim must be in 1..16 (got %d)", obs_dim);
     if (((uintptr_t)actions_out & 15u) || ((uintptr_t)obs & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "actions_out and obs must be 16-byte aligned");
+    if (env->dyn.dyn)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_mlp_forward + dn_policy_sample + dn_step");
     const dn_config &c = env->cfg;
     for (int k = 0; k < num_nets; ++k) {
         const dn_mlp_net &n = nets[k];
@@ -727,6 +737,8 @@ int32_t dn_eval_kinematics(dn_env *env, const double *kinematics, float *obs, fl
     if (c.act_noise_sigma > 0.0f || c.obs_noise_sigma > 0.0f || c.clip_rew || c.norm_rew || c.physics != 0 || c.action_type != 0 || c.random_spawn)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics is built for the reference configuration (no noise, no reward wrappers, "
                                              "Physics.PYB, ActionType.THRUST, fixed spawn)");
+    if (env->dyn.dyn)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given nominal-body transition: refused with the randomised dynamics (dn_enable_dynamics)");
     DnStepIO io;
     memset(&io, 0, sizeof io);
     io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated; io.found_targets = found_targets;
@@ -759,7 +771,7 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
     DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream));
+    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn));
     return DN_OK;
 }
 
@@ -976,6 +988,62 @@ int32_t dn_reset_stats(dn_env *env, void *stream)
 }
 
 int32_t dn_get_kernel_waves(const dn_env *env, int32_t fused) { return env ? (fused ? env->waves_fused : env->waves_single) : 0; }
+
+int32_t dn_enable_dynamics(dn_env *env, const dn_dynamics_config *cfg)
+{
+    if (!env || !cfg) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    const float *rng[4] = {cfg->mass, cfg->inertia, cfg->kf, cfg->km};
+    const char *names[4] = {"mass", "inertia", "kf", "km"};
+    for (int j = 0; j < 4; ++j) {
+        const float lo = rng[j][0], hi = rng[j][1];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo > 0.0f) || !(lo <= hi))
+            return fail(DN_ERR_INVALID_ARGUMENT, "dynamics range %s = [%g, %g]: need finite 0 < lo <= hi", names[j], (double)lo, (double)hi);
+    }
+    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    DN_HIP(hipSetDevice(env->cfg.device_id));
+    if (!env->dyn.dyn) {                    // first call: the per-drone scales, all 1 (the nominal body) until a reset draws or dn_set_dynamics writes
+        const long long n = env->cfg.num_envs;
+        float4 *d = nullptr;
+        const hipError_t he = hipMalloc(&d, (size_t)n * sizeof(float4));
+        if (he != hipSuccess)
+            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the dynamics scales failed: %s", (size_t)n * sizeof(float4), hipGetErrorString(he));
+        if (dn_launch_fill4(d, make_float4(1.0f, 1.0f, 1.0f, 1.0f), n, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(d);
+            return fail(DN_ERR_HIP, "initialising the dynamics scales failed");
+        }
+        env->dyn.dyn = d;
+    }
+    for (int j = 0; j < 4; ++j) { env->dyn.lo[j] = rng[j][0]; env->dyn.hi[j] = rng[j][1]; }
+    env->dyn.resample = cfg->resample;
+    env->dyn_cfg = *cfg;
+    env->waves_fused = env->waves_single = 1;     // the scales live in the one-wave option kernels only (as the random spawn does)
+    return DN_OK;
+}
+
+int32_t dn_set_dynamics(dn_env *env, const float *scales, void *stream)
+{
+    if (!env || !scales) return fail(DN_ERR_INVALID_ARGUMENT, "env and scales are required");
+    if (!env->dyn.dyn) return fail(DN_ERR_BAD_STATE, "dynamics randomisation is not enabled (dn_enable_dynamics)");
+    DN_HIP(hipMemcpyAsync(env->dyn.dyn, scales, (size_t)env->cfg.num_envs * sizeof(float4), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_get_dynamics(dn_env *env, float *scales, void *stream)
+{
+    if (!env || !scales) return fail(DN_ERR_INVALID_ARGUMENT, "env and scales are required");
+    if (!env->dyn.dyn) return fail(DN_ERR_BAD_STATE, "dynamics randomisation is not enabled (dn_enable_dynamics)");
+    DN_HIP(hipMemcpyAsync(scales, env->dyn.dyn, (size_t)env->cfg.num_envs * sizeof(float4), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_get_dynamics_config(const dn_env *env, dn_dynamics_config *out)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    if (!env->dyn.dyn) return 0;
+    *out = env->dyn_cfg;
+    return 1;
+}
 
 int32_t dn_get_step_count(const dn_env *env, uint64_t *out)
 {

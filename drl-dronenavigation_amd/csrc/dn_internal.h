@@ -116,6 +116,17 @@ struct DnParams {
     DnConsts<float> c32;
 };
 
+// Per-drone dynamics randomisation (dn_enable_dynamics): the scale factors of the simulated body and how they are drawn.  Not a field of
+// DnParams: DnParams is the first argument of every step kernel, and growing it would move every later kernel argument (a different
+// instruction stream for every kernel).  It is the last argument of the kernels that read it: the one-wave step kernels instantiated with
+// the scales (dn_step_many_1w_kernel<..., DYN = true>) and the reset kernel.
+struct DnDyn {
+    float4 *dyn;            // [N] s_m, s_I, s_kf, s_km; nullptr = dynamics not enabled (the nominal cf2x body)
+    float lo[4], hi[4];     // scale ranges of the draws, in the order of the float4
+    int resample;           // 1: draw at every episode start (dn_reset, auto-reset); 0: keep what dn_set_dynamics wrote
+    int pad_;
+};
+
 // dn_set_launch_events (ABI 8): the step kernel of the next dn_step / dn_step_many launch is dispatched with these two hipEvents attached to
 // its own dispatch packet (hipExtLaunchKernelGGL) -- they time the kernel itself, like a profiler's kernel trace, where a pair of
 // hipEventRecord around the call would also time the host's launch path and add two marker packets to the stream.  One shot: the
@@ -128,9 +139,10 @@ extern thread_local hipEvent_t dn_tl_ev_start, dn_tl_ev_stop;
     } while (0)
 
 int dn_norm_exact_compiled_in();      // 1 in libdronenav_exact.so (-DDN_NORM_EXACT=1: the normaliser's float64 output stage), else 0
-hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);
+hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream,
+                               const DnDyn *dy = nullptr);    // dy->dyn != nullptr: the one-wave kernel with the scales, whatever `waves` says
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);   // dn_kernels_mw.hip
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream);
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy = nullptr);
 hipError_t dn_launch_eval_kinematics(const DnParams &p, const DnStepIO &io, const double *kin, bool f32, hipStream_t stream);
 hipError_t dn_launch_gae(const float *rewards, const float *values, const uint8_t *dones,
                          const float *last_values, const uint8_t *last_dones, long long T, long long N,

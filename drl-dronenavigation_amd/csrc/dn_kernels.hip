@@ -1230,7 +1230,7 @@ DN_DEV LinPre<R> physics_linear_pre(const float4 G2, const R damp = K<R>::LIN_DA
 }
 template <typename R>
 DN_DEV Lin<R> physics_linear_post(const float4 G0, const float4 G2, const AttCol<R> col, const LinPre<R> &l, const R fz, const R dax, const R day,
-                                  const R daz, const bool extra)
+                                  const R daz, const bool extra, const R inv_m = K<R>::INV_M)     // inv_m: 1 / (M s_m) of a randomised body
 {
     Lin<R> o;
     R px = G0.x, py = G0.y, pz = G0.z;
@@ -1238,7 +1238,7 @@ DN_DEV Lin<R> physics_linear_post(const float4 G0, const float4 G2, const AttCol
     const R dt = K<R>::DT;
     const R r02 = col.r02, r12 = col.r12, r22 = col.r22;
     // linear: a = R[:,2] fz/M - (0,0,G) - v (c + c|v|)
-    const R fm = fz * K<R>::INV_M;
+    const R fm = fz * inv_m;
     R awx = F(r02, fm, -l.vkx), awy = F(r12, fm, -l.vky), awz = F(-vz, l.kl, F(r22, fm, -K<R>::G));
     if (extra) { awx += dax; awy += day; awz += daz; }
     vx = F(awx, dt, vx); vy = F(awy, dt, vy); vz = F(awz, dt, vz);       // applyDeltaVeeMultiDof
@@ -1252,15 +1252,15 @@ DN_DEV Lin<R> physics_linear_post(const float4 G0, const float4 G2, const AttCol
 }
 template <typename R>
 DN_DEV Lin<R> physics_linear_col(const float4 G0, const float4 G2, const AttCol<R> col, const R fz, const R dax, const R day, const R daz,
-                                 const bool extra, const R damp = K<R>::LIN_DAMP)
+                                 const bool extra, const R damp = K<R>::LIN_DAMP, const R inv_m = K<R>::INV_M)
 {
-    return physics_linear_post<R>(G0, G2, col, physics_linear_pre<R>(G2, damp), fz, dax, day, daz, extra);
+    return physics_linear_post<R>(G0, G2, col, physics_linear_pre<R>(G2, damp), fz, dax, day, daz, extra, inv_m);
 }
 template <typename R>
 DN_DEV Lin<R> physics_linear(const float4 G0, const float4 G1, const float4 G2, const R fz, const R dax, const R day, const R daz,
-                             const bool extra, const R damp = K<R>::LIN_DAMP)
+                             const bool extra, const R damp = K<R>::LIN_DAMP, const R inv_m = K<R>::INV_M)
 {
-    return physics_linear_col<R>(G0, G2, attitude_column<R>(G1), fz, dax, day, daz, extra, damp);
+    return physics_linear_col<R>(G0, G2, attitude_column<R>(G1), fz, dax, day, daz, extra, damp, inv_m);
 }
 template <typename R> struct Ang {
     R qx, qy, qz, qw;      // new attitude (unit quaternion)
@@ -1276,16 +1276,20 @@ template <typename R> struct AngPre {
 };
 // ... on quaternion terms the caller already holds: a wave that owns the attitude across the steps of a fused launch forms quat_terms of
 // the NEW attitude once, at the end of a step (for the thrust direction it mails to the linear half), and starts the next step from them.
+// ixx, iyy, izz: the diagonal inertia (I s_I of a randomised body)
 template <typename R>
-DN_DEV AngPre<R> physics_angular_pre_terms(const float4 G1, const float4 G3, const QuatTerms<R> &t, const R damp = K<R>::ANG_DAMP);
+DN_DEV AngPre<R> physics_angular_pre_terms(const float4 G1, const float4 G3, const QuatTerms<R> &t, const R damp = K<R>::ANG_DAMP,
+                                           const R ixx = K<R>::IXX, const R iyy = K<R>::IYY, const R izz = K<R>::IZZ);
 template <typename R>
-DN_DEV AngPre<R> physics_angular_pre(const float4 G1, const float4 G3, const R damp = K<R>::ANG_DAMP)
+DN_DEV AngPre<R> physics_angular_pre(const float4 G1, const float4 G3, const R damp = K<R>::ANG_DAMP, const R ixx = K<R>::IXX,
+                                     const R iyy = K<R>::IYY, const R izz = K<R>::IZZ)
 {
     const R qx = G1.x, qy = G1.y, qz = G1.z, qw = G1.w;
-    return physics_angular_pre_terms<R>(G1, G3, quat_terms<R>(qx, qy, qz, qw), damp);
+    return physics_angular_pre_terms<R>(G1, G3, quat_terms<R>(qx, qy, qz, qw), damp, ixx, iyy, izz);
 }
 template <typename R>
-DN_DEV AngPre<R> physics_angular_pre_terms(const float4 G1, const float4 G3, const QuatTerms<R> &t, const R damp)
+DN_DEV AngPre<R> physics_angular_pre_terms(const float4 G1, const float4 G3, const QuatTerms<R> &t, const R damp, const R ixx, const R iyy,
+                                           const R izz)
 {
     AngPre<R> a;
     const R qx = G1.x, qy = G1.y, qz = G1.z, qw = G1.w;
@@ -1296,20 +1300,21 @@ DN_DEV AngPre<R> physics_angular_pre_terms(const float4 G1, const float4 G3, con
     // angular, in the body frame: I dw = tau - w x (I w) - I w (c + c|w|)
     const R wbx = F(a.r20, wz, F(a.r10, wy, a.r00 * wx)), wby = F(a.r21, wz, F(a.r11, wy, a.r01 * wx)), wbz = F(a.r22, wz, F(a.r12, wy, a.r02 * wx));
     a.ka = F(damp, (R)__builtin_amdgcn_sqrtf((float)F(wz, wz, F(wy, wy, wx * wx))), damp);
-    a.Iwx = K<R>::IXX * wbx; a.Iwy = K<R>::IYY * wby; a.Iwz = K<R>::IZZ * wbz;
+    a.Iwx = ixx * wbx; a.Iwy = iyy * wby; a.Iwz = izz * wbz;
     a.gx = F(wby, a.Iwz, -(wbz * a.Iwy)); a.gy = F(wbz, a.Iwx, -(wbx * a.Iwz)); a.gz = F(wbx, a.Iwy, -(wby * a.Iwx));
     a.qx = qx; a.qy = qy; a.qz = qz; a.qw = qw; a.wx = wx; a.wy = wy; a.wz = wz;
     return a;
 }
 template <typename R>
-DN_DEV Ang<R> physics_angular_post(const AngPre<R> &a, const R tx, const R ty, const R ztq)
+DN_DEV Ang<R> physics_angular_post(const AngPre<R> &a, const R tx, const R ty, const R ztq, const R inv_ixx = K<R>::INV_IXX,
+                                   const R inv_iyy = K<R>::INV_IYY, const R inv_izz = K<R>::INV_IZZ)
 {
     Ang<R> o;
     const R qx = a.qx, qy = a.qy, qz = a.qz, qw = a.qw;
     R wx = a.wx, wy = a.wy, wz = a.wz;
     const R dt = K<R>::DT;
-    const R dbx = F(-a.Iwx, a.ka, tx - a.gx) * K<R>::INV_IXX, dby = F(-a.Iwy, a.ka, ty - a.gy) * K<R>::INV_IYY,
-            dbz = F(-a.Iwz, a.ka, ztq - a.gz) * K<R>::INV_IZZ;
+    const R dbx = F(-a.Iwx, a.ka, tx - a.gx) * inv_ixx, dby = F(-a.Iwy, a.ka, ty - a.gy) * inv_iyy,
+            dbz = F(-a.Iwz, a.ka, ztq - a.gz) * inv_izz;
     const R dwx = F(a.r02, dbz, F(a.r01, dby, a.r00 * dbx)), dwy = F(a.r12, dbz, F(a.r11, dby, a.r10 * dbx)), dwz = F(a.r22, dbz, F(a.r21, dby, a.r20 * dbx));
     wx = F(dwx, dt, wx); wy = F(dwy, dt, wy); wz = F(dwz, dt, wz);       // applyDeltaVeeMultiDof
     const R mv = K<R>::MAX_COORD_VEL;
@@ -1337,14 +1342,55 @@ DN_DEV Ang<R> physics_angular_post(const AngPre<R> &a, const R tx, const R ty, c
     return o;
 }
 template <typename R>
-DN_DEV Ang<R> physics_angular(const float4 G1, const float4 G3, const R tx, const R ty, const R ztq, const R damp = K<R>::ANG_DAMP)
+DN_DEV Ang<R> physics_angular(const float4 G1, const float4 G3, const R tx, const R ty, const R ztq, const R damp = K<R>::ANG_DAMP,
+                              const R ixx = K<R>::IXX, const R iyy = K<R>::IYY, const R izz = K<R>::IZZ, const R inv_ixx = K<R>::INV_IXX,
+                              const R inv_iyy = K<R>::INV_IYY, const R inv_izz = K<R>::INV_IZZ)
 {
-    return physics_angular_post<R>(physics_angular_pre<R>(G1, G3, damp), tx, ty, ztq);
+    return physics_angular_post<R>(physics_angular_pre<R>(G1, G3, damp, ixx, iyy, izz), tx, ty, ztq, inv_ixx, inv_iyy, inv_izz);
 }
 
-template <typename R, typename TH = Thrust, bool XOPT = false>
+// ---- per-drone dynamics randomisation (dn_enable_dynamics) --------------------------------------------------------------
+// The simulated body's mass, inertia, thrust and torque coefficients as multiples of the cf2x constants.  The action chain, the
+// hover rpm and the PID loop keep modelling the NOMINAL drone (a flight stack knows only that one): the scales act on the body.
+// Every scale enters as a product with a per-drone factor (or constant / s), formed once per launch and again after a redraw,
+// so scales of 1 reproduce the nominal bits and power-of-two scales leave every acceleration unchanged.
+template <typename R> struct DynK {
+    R inv_m;                        // 1 / (M s_m)   = INV_M / s_m
+    R ixx, iyy, izz;                // I s_I
+    R inv_ixx, inv_iyy, inv_izz;    // 1 / (I s_I)   = INV_I / s_I
+    R kf, km;                       // s_kf, s_km
+};
+template <typename R> DN_DEV DynK<R> dyn_terms(const float4 s)
+{
+    DynK<R> d;
+    const R sm = s.x, si = s.y;
+    d.inv_m = K<R>::INV_M / sm;
+    d.ixx = K<R>::IXX * si; d.iyy = K<R>::IYY * si; d.izz = K<R>::IZZ * si;
+    d.inv_ixx = K<R>::INV_IXX / si; d.inv_iyy = K<R>::INV_IYY / si; d.inv_izz = K<R>::INV_IZZ / si;
+    d.kf = s.z; d.km = s.w;
+    return d;
+}
+// One Philox4x32-10 call keyed (seed; global drone id, the vector step the episode starts on, stream 13): scale j = lo + (hi - lo) u_j,
+// u_j = (r_j + 0.5) / 2^32, in float64, stored as float32.  Keyed like spawn_point: sharding does not move a draw, a graph replay draws afresh.
+DN_DEV float4 dyn_draw(const DnDyn &dy, const unsigned long long seed, const unsigned long long gid, const unsigned long long step)
+{
+    unsigned r[4];
+    philox4x32((unsigned)gid, (unsigned)(gid >> 32), (unsigned)step, 13u | ((unsigned)(step >> 32) << 8), (unsigned)seed,
+               (unsigned)(seed >> 32), r);
+    float s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double u = ((double)r[j] + 0.5) * (1.0 / 4294967296.0);
+        const double lo = dy.lo[j], hi = dy.hi[j];
+        s[j] = (float)(lo + (hi - lo) * u);
+    }
+    return make_float4(s[0], s[1], s[2], s[3]);
+}
+
+// DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
+template <typename R, typename TH = Thrust, bool XOPT = false, bool DYN = false>
 DN_DEV Flight<R> physics_phase(const TH &th, const float4 G0, const float4 G1, const float4 G2, const float4 G3,
-                               const int max_steps, const Extras *x = nullptr)
+                               const int max_steps, const Extras *x = nullptr, const DynK<R> *dk = nullptr)
 {
     Flight<R> fl;
     flight_entry<R>(fl, G0, G2, G3, max_steps);
@@ -1385,19 +1431,32 @@ DN_DEV Flight<R> physics_phase(const TH &th, const float4 G0, const float4 G1, c
             const R kxy = R(-DRAG_XY) * sum, kz = R(-DRAG_Z) * sum;
             const R ux = kxy * vx, uy = kxy * vy, uz = kz * vz;
             const R bx = r00 * ux + r01 * uy + r02 * uz, by = r10 * ux + r11 * uy + r12 * uz, bz = r20 * ux + r21 * uy + r22 * uz;
-            dax = (r00 * bx + r01 * by + r02 * bz) * K<R>::INV_M;
-            day = (r10 * bx + r11 * by + r12 * bz) * K<R>::INV_M;
-            daz = (r20 * bx + r21 * by + r22 * bz) * K<R>::INV_M;
+            R inv_m = K<R>::INV_M;
+            if constexpr (DYN) inv_m = dk->inv_m;               // the drag force accelerates this drone's mass
+            dax = (r00 * bx + r01 * by + r02 * bz) * inv_m;
+            day = (r10 * bx + r11 * by + r12 * bz) * inv_m;
+            daz = (r20 * bx + r21 * by + r22 * bz) * inv_m;
+        }
+        if constexpr (DYN) {    // KF scales every rotor force after the chain, the PID / RPM forms and the ground effect
+            F0 *= dk->kf; F1 *= dk->kf; F2 *= dk->kf; F3 *= dk->kf;
         }
     }
     fz = (F0 + F1) + (F2 + F3);
     tx = K<R>::ARM * ((F2 + F3) - (F0 + F1));
     ty = K<R>::ARM * ((F1 + F2) - (F0 + F3));
     ztq = (R)th.zt;
+    if constexpr (DYN) ztq *= dk->km;
     }
     const R damp = XOPT ? (R)x->damp : K<R>::LIN_DAMP;        // the option kernels take it at run time (dn_config.zero_damping)
-    const Lin<R> lin = physics_linear<R>(G0, G1, G2, fz, dax, day, daz, XOPT, damp);
-    const Ang<R> ang = physics_angular<R>(G1, G3, tx, ty, ztq, damp);
+    Lin<R> lin;
+    Ang<R> ang;
+    if constexpr (DYN) {
+        lin = physics_linear<R>(G0, G1, G2, fz, dax, day, daz, XOPT, damp, dk->inv_m);
+        ang = physics_angular<R>(G1, G3, tx, ty, ztq, damp, dk->ixx, dk->iyy, dk->izz, dk->inv_ixx, dk->inv_iyy, dk->inv_izz);
+    } else {
+        lin = physics_linear<R>(G0, G1, G2, fz, dax, day, daz, XOPT, damp);
+        ang = physics_angular<R>(G1, G3, tx, ty, ztq, damp);
+    }
     fl.px = lin.px; fl.py = lin.py; fl.pz = lin.pz;
     fl.qx = ang.qx; fl.qy = ang.qy; fl.qz = ang.qz; fl.qw = ang.qw;
     fl.vx = (float)lin.vx; fl.vy = (float)lin.vy; fl.vz = (float)lin.vz;
@@ -1985,9 +2044,10 @@ DN_DEV BlockState block_state(const DnState &st, long long tile_base)
 }
 
 // thrust + physics of one step; the XOPT kernels take the float64 carriers and the optional force terms (N4)
-template <typename R, bool NOISE, bool XOPT>
+template <typename R, bool NOISE, bool XOPT, bool DYN = false>
 DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long long sc, const float4 A, const float4 G0, const float4 G1,
-                     const float4 G2, const float4 G3, const float4 G7, float4 &rpm_now, double *pid_st = nullptr)
+                     const float4 G2, const float4 G3, const float4 G7, float4 &rpm_now, double *pid_st = nullptr,
+                     const DynK<R> *dk = nullptr)
 {
     if (XOPT) {
         Extras x;
@@ -1996,7 +2056,7 @@ DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long lo
         cx.G0 = G0; cx.G1 = G1; cx.G2 = G2; cx.st = pid_st;
         const ThrustX th = thrust_phase_x<NOISE>(p, gid, sc, A, x, pid_st ? &cx : nullptr);
         rpm_now = make_float4((float)x.rpm[0], (float)x.rpm[1], (float)x.rpm[2], (float)x.rpm[3]);
-        return physics_phase<R, ThrustX, true>(th, G0, G1, G2, G3, p.max_steps, &x);
+        return physics_phase<R, ThrustX, true, DYN>(th, G0, G1, G2, G3, p.max_steps, &x, dk);
     }
     const Thrust th = thrust_phase<NOISE>(p, gid, sc, A);
     return physics_phase<R>(th, G0, G1, G2, G3, p.max_steps);
@@ -2065,8 +2125,12 @@ DN_DEV float4 sample_action(const DnStepIO &io, const unsigned long long gid, co
 // -----------------------------------------------------------------------------------------------------
 // ONE = true is the single-step launch (dn_step): k_steps is the constant 1, and the kernel gets its own name in
 // profiles (dn_step_many_*_kernel<..., true> = one control step per launch, <..., false> = k_arg steps per launch).
-template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false>
-__global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg)
+// DYN (with XOPT): the per-drone body scales of dn_enable_dynamics, passed as the last argument.  Without them that argument is an empty
+// struct, which leaves the offsets of the kernel's other arguments -- and with them every instruction of the kernel -- as they were.
+template <bool DYN> struct DynArg : DnDyn {};
+template <> struct DynArg<false> {};
+template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false>
+__global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg, const DynArg<DYN> dy)
 {
     const int k_steps = ONE ? 1 : k_arg;
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
@@ -2090,6 +2154,9 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     float4 G0 = b.g0[li], G1 = b.g1[li], G2 = b.g2[li], G3 = b.g3[li], G4 = b.g4[li], G5 = b.g5[li];
     float4 G7 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (XOPT && p.drag) G7 = b.g7[li];
+    // dn_enable_dynamics: this drone's body scales, held with their derived terms in registers across the launch (1.0 = the nominal body)
+    float4 S = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    if constexpr (DYN) S = dy.dyn[i];
     stage_table<R>(p, s_tab);
     block_lds_barrier();
     const long long n = p.n, words = (p.n + 63) / 64;
@@ -2103,6 +2170,8 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     if (NORM) load_rms_walk(p, tile_base, li, rms);
     RewNorm rn = {0.0, 0.0, 1.0, 1e-4};
     if (XOPT && p.norm_rew) load_rewnorm(p, i, rn);
+    DynK<R> dk = dyn_terms<R>(S);                       // DYN only (dead code otherwise)
+    bool redrawn = false;
     double pid_st[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (XOPT && p.pid_mode) {
 #pragma unroll
@@ -2116,10 +2185,18 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         const unsigned long long sc = sc0 + (unsigned long long)t;
         float4 rpm_now;
         const GateRow<R> row_e = load_gate_row<R>(s_tab, unpack_meta(G3.w).idx);
-        Flight<R> fl = fly<R, NOISE, XOPT>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr);
+        Flight<R> fl = fly<R, NOISE, XOPT, DYN>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr, DYN ? &dk : nullptr);
         const float4 G0e = G0, G3e = G3;
         const Verdict<R> v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc);
         if (XOPT && p.drag) G7 = (v.terminated || fl.truncated) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : rpm_now;   // BaseAviary.py:442,545
+        if constexpr (DYN) {
+            if (dy.resample) {       // the body reloaded by the auto-reset (rules_commit) is a new draw, flown from the next step on
+                const bool done = v.terminated || fl.truncated;
+                if (__ballot(done) != 0ull) {           // wave-uniform: most wave-steps skip this
+                    if (done) { S = dyn_draw(dy, p.seed, gid, sc); dk = dyn_terms<R>(S); redrawn = true; }
+                }
+            }
+        }
         attitude_phase<R>(fl);
         Observed<R> ob = observe_phase<R, NORM, NOISE>(p, c, s_tab, fl, G4, G5, gid, sc, rms);
         report_phase<R, NORM, NOISE, XOPT, 0, XOPT>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn);
@@ -2136,6 +2213,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     if (active) {
         b.g0[li] = G0; b.g1[li] = G1; b.g2[li] = G2; b.g3[li] = G3; b.g4[li] = G4; b.g5[li] = G5;
         if (XOPT && p.drag) b.g7[li] = G7;
+        if constexpr (DYN) { if (redrawn) dy.dyn[i] = S; }
     }
 }
 
@@ -3679,7 +3757,7 @@ __global__ __launch_bounds__(3 * DN_BLOCK) void dn_step_pqx_kernel(const DnParam
 // VecEnv.reset(): every drone goes through Monitor.reset / NormalizeObservation.reset / PBDroneEnv.reset.
 // =====================================================================================================
 template <typename R>
-__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs)
+__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy)
 {
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -3728,6 +3806,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
         b.g5[li] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(0));
         b.g6[li] = make_float4((float)cpx, (float)cpy, (float)cpz, 0.0f);
         if (p.drag) b.g7[li] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);      // last_clipped_action, BaseAviary.py:545
+        if (dy.dyn && dy.resample) dy.dyn[i] = dyn_draw(dy, p.seed, gid, p.st.stats[blockIdx.x].step_count);   // this episode's body
     }
     store_obs_tile(s_tile, obs + tile_base * DN_OBS_DIM, rows, lane, o);
 }
@@ -4005,7 +4084,7 @@ hipError_t dn_launch_filld(double *dst, double v, long long n, hipStream_t strea
         if (two_wave)                                                                                                   \
             DN_KLAUNCH((dn_step_many_2w_kernel<R, NORM, NOISE, ONE, XOPT>), dim3(grid), dim3(2 * DN_BLOCK), 0, stream, p, io, k); \
         else                                                                                                            \
-            DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, ONE, XOPT>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k);     \
+            DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, ONE, XOPT>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, DynArg<false>{}); \
     } while (0)
 #define DN_LAUNCH2(R, NORM, NOISE, ONE)                                                                                 \
     do {                                                                                                                \
@@ -4088,9 +4167,29 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 }
 #endif
 #elif DN_TU == 1
-hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream)
+hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnDyn *dy)
 {
     const bool norm = p.normalize_obs != 0;
+    if (dy && dy->dyn) {                    // dn_enable_dynamics: the one-wave option kernel with the body scales, whatever the configuration
+        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the scales (the C ABI refuses them first)
+        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
+        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
+        const DynArg<true> dya = {*dy};
+#define DN_LD(R, NORM, NOISE)                                                                                                       \
+        do {                                                                                                                        \
+            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, dya); \
+            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, dya);   \
+        } while (0)
+        if (f32) {
+            if (norm) { if (noise) DN_LD(float, true, true); else DN_LD(float, true, false); }
+            else { if (noise) DN_LD(float, false, true); else DN_LD(float, false, false); }
+        } else {
+            if (norm) { if (noise) DN_LD(double, true, true); else DN_LD(double, true, false); }
+            else { if (noise) DN_LD(double, false, true); else DN_LD(double, false, false); }
+        }
+#undef DN_LD
+        return hipGetLastError();
+    }
     if (io.mean && waves == 3) {            // dn_step_sampled on three waves
         const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
         const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
@@ -4108,7 +4207,7 @@ hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, boo
     if (io.mean) {                          // dn_step_sampled: one-wave single-step kernels with the sampler compiled in
         const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
         const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-#define DN_LS(R, NORM, NOISE) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, false, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1)
+#define DN_LS(R, NORM, NOISE) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, false, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, DynArg<false>{})
         if (f32) {
             if (norm) { if (noise) DN_LS(float, true, true); else DN_LS(float, true, false); }
             else { if (noise) DN_LS(float, false, true); else DN_LS(float, false, false); }
@@ -4158,11 +4257,12 @@ hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, boo
 #undef DN_LAUNCH3
 
 #if DN_TU == 1
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream)
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy)
 {
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs);
+    const DnDyn dyn = dy ? *dy : DnDyn{};
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn);
     return hipGetLastError();
 }
 

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from .dynamics import DynamicsRandomization
 from .spaces import Box
 from .tracks import Track
 
@@ -169,7 +170,9 @@ class DroneVecEnv(_VecEnvBase):
                  include_distance=True, normalize_actions=True, normalize_obs=True, ground_contact=None,
                  compute_dtype="float64", act_noise_sigma=0.0, obs_noise_sigma=0.0, seed=0, env_id_offset=0,
                  device=None, info_mode="sparse", clip_rew=False, norm_rew=False, physics="pyb", act="thrust", random_spawn=False,
-                 zero_damping=False, fresh_arrays=True):
+                 zero_damping=False, fresh_arrays=True, dynamics=None):
+        if dynamics is not None and not isinstance(dynamics, DynamicsRandomization):
+            raise TypeError("dynamics must be a drl_dronenavigation_amd.DynamicsRandomization (or None)")
         if track is not None:
             if not isinstance(track, Track):
                 raise TypeError("track must be a drl_dronenavigation_amd.tracks.Track")
@@ -209,6 +212,14 @@ class DroneVecEnv(_VecEnvBase):
         _capi.check(self._lib.dn_create(C.byref(self.cfg), C.byref(self._handle)))
         _capi.check(self._lib.dn_get_config(self._handle, C.byref(self.cfg)))     # the resolved configuration (ground_contact 0 / 1)
         self.ground_contact = bool(self.cfg.ground_contact)
+        self.dynamics = dynamics
+        if dynamics is not None:               # before the first reset: dn_reset draws the first episode's bodies
+            rc = self._lib.dn_enable_dynamics(self._handle, C.byref(dynamics.to_c()))
+            if rc != _capi.DN_OK:
+                err = _capi.DroneNavError(rc, self._lib.dn_last_error().decode("utf-8", "replace"))
+                self._lib.dn_destroy(self._handle)
+                self._handle = C.c_void_p()
+                raise err
 
         n = int(num_envs)
         self.num_envs = n
@@ -593,6 +604,46 @@ class DroneVecEnv(_VecEnvBase):
     def set_state(self, states):
         arr = _numpy_to_states(states, self.num_envs)
         _capi.check(self._lib.dn_set_state(self._handle, C.cast(arr, C.c_void_p), self.num_envs))
+
+    # ------------------------------------------------------------------ dynamics randomisation (dn_enable_dynamics)
+    def get_dynamics(self):
+        """Every drone's body scales as a float32 tensor [N, 4] on the env's device: s_m, s_I, s_kf, s_km.  With get_state() this is
+        a checkpoint of a randomised fleet (dn_env_state does not carry the scales)."""
+        self._require_dynamics()
+        out = torch.empty((self.num_envs, 4), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.dn_get_dynamics(self._handle, out.data_ptr(), self._stream()))
+        return out
+
+    def set_dynamics(self, scales):
+        """Writes every drone's body scales (float32 [N, 4] on the env's device; every value positive and finite).  With
+        resample=False they hold until the next set_dynamics; with resample=True until the drone's next episode start."""
+        self._require_dynamics()
+        if not isinstance(scales, torch.Tensor):
+            raise TypeError("scales must be a torch.Tensor")
+        if scales.dtype != torch.float32:
+            raise TypeError(f"scales must be float32, got {scales.dtype}")
+        if scales.device != self.device:
+            raise ValueError(f"scales must live on {self.device}, got {scales.device}")
+        if tuple(scales.shape) != (self.num_envs, 4):
+            raise ValueError(f"scales must have shape ({self.num_envs}, 4), got {tuple(scales.shape)}")
+        s = scales.contiguous()
+        if not bool(((s > 0) & torch.isfinite(s)).all()):      # one device-side reduction, one scalar back
+            raise ValueError("every scale must be positive and finite")
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.dn_set_dynamics(self._handle, s.data_ptr(), self._stream()))
+
+    def dynamics_config(self):
+        """The DynamicsRandomization in force (dn_get_dynamics_config), or None when the feature is off."""
+        c = _capi.DnDynamicsConfig()
+        rc = self._lib.dn_get_dynamics_config(self._handle, C.byref(c))
+        if rc < 0:
+            _capi.check(rc)
+        return DynamicsRandomization.from_c(c) if rc == 1 else None
+
+    def _require_dynamics(self):
+        if self.dynamics is None:
+            raise RuntimeError("dynamics randomisation is not enabled: construct the env with dynamics=DynamicsRandomization(...)")
 
     def stats(self):
         s = _capi.DnStats()

@@ -101,7 +101,8 @@ typedef struct dn_config {
 } dn_config;
 
 /* One drone's persistent state, host-side AoS view used by dn_get_state/dn_set_state (tests,
- * checkpointing).  Field names follow the reference's attributes. */
+ * checkpointing).  Field names follow the reference's attributes.  It does not carry the body scales of
+ * dn_enable_dynamics: a checkpoint of a randomised fleet is dn_get_state + dn_get_dynamics (restore: dn_set_state + dn_set_dynamics). */
 typedef struct dn_env_state {
     float pos[3], quat[4], vel[3], ang_v[3];    /* Bullet base state, BaseAviary.py:596-598 (quat = x,y,z,w) */
     float prev_vel[3], prev_ang_v[3];           /* PBDroneEnv.prev_vel / prev_ang_v */
@@ -386,8 +387,39 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
  * (Sol/Utilities/Profiler.py:5-16), at the granularity this path has: one launch.  Used by bench.py's roofline figure. */
 int32_t dn_set_launch_events(dn_env *env, void *start_event, void *stop_event);
 
-/* Bytes of HBM the persistent state of `num_envs` drones occupies (capacity planning). */
+/* Bytes of HBM the persistent state of `num_envs` drones occupies (capacity planning).  The body scales of dn_enable_dynamics are a
+ * separate allocation of 16 bytes per drone and are not included. */
 int64_t dn_state_bytes(int64_t num_envs, int32_t normalize_obs);
+
+/* Per-drone dynamics randomisation (sim-to-real).  Each drone carries four float32 scale factors relative to the nominal cf2x body:
+ *   s_m   mass: linear acceleration = R F / (M s_m) - g (gravity stays g); the drag force of Physics.PYB_DRAG also accelerates M s_m
+ *   s_I   inertia: diag(Ixx, Iyy, Izz) s_I in I w, the gyroscopic term and I^-1 (Bullet's damping form unchanged)
+ *   s_kf  thrust coefficient: every rotor force after the action chain, ground effect included (it is KF rpm^2 coeff)
+ *   s_km  torque coefficient: the yaw torque after the chain
+ * The action chain (rescale_action -> cmd2pwm -> pwm2rpm), HOVER_RPM of ActionType.RPM and the DSLPIDControl loop stay NOMINAL: they model
+ * the drone a flight stack knows, only the simulated body differs.  Scales of 1 reproduce the nominal arithmetic bit for bit.
+ * resample = 1: every episode start (dn_reset and every in-kernel auto-reset) draws new scales, each lo + (hi - lo) u in float64 stored as
+ * float32, u = (r + 0.5) / 2^32, the four words r from ONE Philox4x32-10 call keyed (seed; global drone id, the vector-step counter of
+ * the step the episode starts on, stream 13) -- sharding does not move the draws, and a hipGraph replay keeps drawing fresh ones.  New
+ * scales act from the first physics step of the new episode; the reset observation does not depend on them.  resample = 0: the scales
+ * are what dn_set_dynamics last wrote (1 after the first dn_enable_dynamics).
+ * The scales live in the one-wave option kernels: enabling forces dn_get_kernel_waves(env, 0 / 1) == 1.  dn_step_sampled,
+ * dn_step_squashed, dn_mlp_step_sampled and dn_eval_kinematics refuse an env with dynamics enabled (DN_ERR_INVALID_ARGUMENT): use
+ * dn_policy_sample / dn_squashed_sample + dn_step. */
+typedef struct dn_dynamics_config {
+    float mass[2], inertia[2], kf[2], km[2];   /* scale ranges [lo, hi]: 0 < lo <= hi, finite */
+    int32_t resample;                          /* 1: draw at every episode start; 0: keep dn_set_dynamics' values */
+    int32_t reserved;                          /* must be 0 */
+} dn_dynamics_config;
+/* Validates the ranges and enables the feature.  The first call allocates 16 bytes per drone (outside dn_state_bytes) and sets every
+ * scale to 1; a later call changes the ranges and `resample` and keeps the current scales.  Synchronises the device. */
+int32_t dn_enable_dynamics(dn_env *env, const dn_dynamics_config *cfg);
+/* Device [N][4] float32 rows (s_m, s_I, s_kf, s_km), copied on `stream`; DN_ERR_BAD_STATE if dynamics are not enabled.  dn_set_dynamics
+ * does not validate the values (the caller's device buffer is not read on the host): every scale must be positive and finite. */
+int32_t dn_set_dynamics(dn_env *env, const float *scales, void *stream);
+int32_t dn_get_dynamics(dn_env *env, float *scales, void *stream);
+/* 1: dynamics enabled, *out = the configuration last given to dn_enable_dynamics; 0: not enabled (*out untouched); < 0: error. */
+int32_t dn_get_dynamics_config(const dn_env *env, dn_dynamics_config *out);
 
 #ifdef __cplusplus
 }
