@@ -10,10 +10,11 @@ from . import _capi, build, tracks  # noqa: F401
 from ._capi import DroneNavError, DroneNavLibraryError  # noqa: F401
 from .tracks import Track  # noqa: F401
 from .dynamics import DynamicsRandomization  # noqa: F401
+from .wind import WindDisturbance  # noqa: F401
 
 __all__ = ["DroneVecEnv", "Track", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
            "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor",
-           "DynamicsRandomization"]
+           "DynamicsRandomization", "WindDisturbance"]
 
 
 def __getattr__(name):

@@ -71,6 +71,11 @@ class DnDynamicsConfig(C.Structure):
                 ("resample", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DnWindConfig(C.Structure):
+    _fields_ = [("speed", C.c_float * 2), ("azimuth", C.c_float * 2), ("vertical", C.c_float * 2), ("gust_sigma", C.c_float * 2),
+                ("gust_tau", C.c_float), ("coeff", C.c_float * 2), ("resample", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every entry point declared in include/dronenav.h: name -> (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 PROTOTYPES = {
@@ -114,6 +119,10 @@ PROTOTYPES = {
     "dn_set_dynamics": (_I32, [_VP, _VP, _VP]),
     "dn_get_dynamics": (_I32, [_VP, _VP, _VP]),
     "dn_get_dynamics_config": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),
+    "dn_enable_wind": (_I32, [_VP, C.POINTER(DnWindConfig)]),
+    "dn_set_wind": (_I32, [_VP, _VP, _VP, _VP]),
+    "dn_get_wind": (_I32, [_VP, _VP, _VP, _VP]),
+    "dn_get_wind_config": (_I32, [_VP, C.POINTER(DnWindConfig)]),
 }
 
 _lib = None

@@ -94,6 +94,8 @@ struct dn_env {
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // dn_set_launch_events: attached to the next step kernel's dispatch, then cleared
     DnDyn dyn = {};             // dn_enable_dynamics: dyn.dyn is an allocation of its own (not in the arena: dn_state_bytes is unchanged)
     dn_dynamics_config dyn_cfg = {};
+    DnWind wind = {};           // dn_enable_wind: wind.mean / wind.gust are one allocation of its own (2 float4 per drone, outside the arena)
+    dn_wind_config wind_cfg = {};
 };
 
 thread_local hipEvent_t dn_tl_ev_start = nullptr, dn_tl_ev_stop = nullptr;
@@ -544,11 +546,15 @@ int32_t dn_destroy(dn_env *env)
 {
     if (!env) return DN_OK;
     hipError_t he = hipSuccess;
-    if (env->arena || env->dyn.dyn) (void)hipSetDevice(env->cfg.device_id);
+    if (env->arena || env->dyn.dyn || env->wind.mean) (void)hipSetDevice(env->cfg.device_id);
     if (env->arena) he = hipFree(env->arena);
     if (env->dyn.dyn) {
         const hipError_t hd = hipFree(env->dyn.dyn);
         if (he == hipSuccess) he = hd;
+    }
+    if (env->wind.mean) {
+        const hipError_t hw = hipFree(env->wind.mean);
+        if (he == hipSuccess) he = hw;
     }
     delete env;
     if (he != hipSuccess) return fail(DN_ERR_HIP, "hipFree failed: %s", hipGetErrorString(he));
@@ -584,7 +590,7 @@ int32_t dn_reset(dn_env *env, float *obs, void *stream)
 {
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     if (!obs) return fail(DN_ERR_INVALID_ARGUMENT, "obs is NULL");
-    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn));
+    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn, &env->wind));
     return DN_OK;
 }
 
@@ -604,7 +610,7 @@ int32_t dn_step(dn_env *env, const float *actions, float *obs, float *reward, ui
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn));
+    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn, &env->wind));
     return DN_OK;
 }
 
@@ -624,6 +630,8 @@ int32_t dn_step_sampled(dn_env *env, const float *mean, const float *log_std, ui
                                              "use dn_policy_sample + dn_step there");
     if (env->dyn.dyn)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_policy_sample + dn_step there");
+    if (env->wind.mean)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the wind (dn_enable_wind); use dn_policy_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -652,6 +660,8 @@ int32_t dn_step_squashed(dn_env *env, const float *mu_log_std, uint64_t seed, in
                                              "use dn_squashed_sample + dn_step there");
     if (env->dyn.dyn)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the randomised dynamics (dn_enable_dynamics); use dn_squashed_sample + dn_step there");
+    if (env->wind.mean)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the wind (dn_enable_wind); use dn_squashed_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -679,6 +689,8 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
     if (((uintptr_t)actions_out & 15u) || ((uintptr_t)obs & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "actions_out and obs must be 16-byte aligned");
     if (env->dyn.dyn)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_mlp_forward + dn_policy_sample + dn_step");
+    if (env->wind.mean)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the wind (dn_enable_wind); use dn_mlp_forward + dn_policy_sample + dn_step");
     const dn_config &c = env->cfg;
     for (int k = 0; k < num_nets; ++k) {
         const dn_mlp_net &n = nets[k];
@@ -739,6 +751,8 @@ int32_t dn_eval_kinematics(dn_env *env, const double *kinematics, float *obs, fl
                                              "Physics.PYB, ActionType.THRUST, fixed spawn)");
     if (env->dyn.dyn)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given nominal-body transition: refused with the randomised dynamics (dn_enable_dynamics)");
+    if (env->wind.mean)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given still-air transition: refused with the wind (dn_enable_wind)");
     DnStepIO io;
     memset(&io, 0, sizeof io);
     io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated; io.found_targets = found_targets;
@@ -771,7 +785,7 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
     DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn));
+    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn, &env->wind));
     return DN_OK;
 }
 
@@ -1042,6 +1056,86 @@ int32_t dn_get_dynamics_config(const dn_env *env, dn_dynamics_config *out)
     if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
     if (!env->dyn.dyn) return 0;
     *out = env->dyn_cfg;
+    return 1;
+}
+
+int32_t dn_enable_wind(dn_env *env, const dn_wind_config *cfg)
+{
+    if (!env || !cfg) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    const float *rng[3] = {cfg->speed, cfg->azimuth, cfg->vertical};
+    const char *names[3] = {"speed", "azimuth", "vertical"};
+    for (int j = 0; j < 3; ++j) {
+        const float lo = rng[j][0], hi = rng[j][1];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo <= hi))
+            return fail(DN_ERR_INVALID_ARGUMENT, "wind range %s = [%g, %g]: need finite lo <= hi", names[j], (double)lo, (double)hi);
+    }
+    if (!(cfg->speed[0] >= 0.0f)) return fail(DN_ERR_INVALID_ARGUMENT, "wind speed lo = %g: need >= 0", (double)cfg->speed[0]);
+    for (int j = 0; j < 2; ++j) {
+        if (!std::isfinite(cfg->gust_sigma[j]) || !(cfg->gust_sigma[j] >= 0.0f))
+            return fail(DN_ERR_INVALID_ARGUMENT, "gust_sigma[%d] = %g: need finite >= 0", j, (double)cfg->gust_sigma[j]);
+        if (!std::isfinite(cfg->coeff[j]) || !(cfg->coeff[j] >= 0.0f))
+            return fail(DN_ERR_INVALID_ARGUMENT, "coeff[%d] = %g: need finite >= 0", j, (double)cfg->coeff[j]);
+    }
+    if (!std::isfinite(cfg->gust_tau) || !(cfg->gust_tau > 0.0f))
+        return fail(DN_ERR_INVALID_ARGUMENT, "gust_tau = %g: need finite > 0", (double)cfg->gust_tau);
+    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    DN_HIP(hipSetDevice(env->cfg.device_id));
+    if (!env->wind.mean) {                  // first call: wbar and g of every drone, 0 (still air) until an episode start draws or dn_set_wind writes
+        const long long n = env->cfg.num_envs;
+        float4 *d = nullptr;
+        const hipError_t he = hipMalloc(&d, (size_t)(2 * n) * sizeof(float4));
+        if (he != hipSuccess)
+            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the wind failed: %s", (size_t)(2 * n) * sizeof(float4), hipGetErrorString(he));
+        if (dn_launch_fill4(d, make_float4(0.0f, 0.0f, 0.0f, 0.0f), 2 * n, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(d);
+            return fail(DN_ERR_HIP, "initialising the wind failed");
+        }
+        env->wind.mean = d;
+        env->wind.gust = d + n;
+    }
+    DnWind &w = env->wind;
+    for (int j = 0; j < 2; ++j) {
+        w.speed[j] = cfg->speed[j]; w.azimuth[j] = cfg->azimuth[j]; w.vertical[j] = cfg->vertical[j];
+        w.sigma[j] = cfg->gust_sigma[j]; w.k[j] = cfg->coeff[j];
+    }
+    const double dt = 1.0 / 240.0;                              // the control step (PYB_FREQ = CTRL_FREQ = 240)
+    w.a = std::exp(-dt / (double)cfg->gust_tau);
+    const double root = std::sqrt(1.0 - w.a * w.a);
+    w.b[0] = (double)cfg->gust_sigma[0] * root;
+    w.b[1] = (double)cfg->gust_sigma[1] * root;
+    w.resample = cfg->resample;
+    w.gust_on = cfg->gust_sigma[0] > 0.0f || cfg->gust_sigma[1] > 0.0f;
+    env->wind_cfg = *cfg;
+    env->waves_fused = env->waves_single = 1;     // the wind lives in the one-wave option kernels only
+    return DN_OK;
+}
+
+int32_t dn_set_wind(dn_env *env, const float *mean, const float *gust, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    if (!env->wind.mean) return fail(DN_ERR_BAD_STATE, "wind is not enabled (dn_enable_wind)");
+    const size_t bytes = (size_t)env->cfg.num_envs * sizeof(float4);
+    if (mean) DN_HIP(hipMemcpyAsync(env->wind.mean, mean, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (gust) DN_HIP(hipMemcpyAsync(env->wind.gust, gust, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_get_wind(dn_env *env, float *mean, float *gust, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    if (!env->wind.mean) return fail(DN_ERR_BAD_STATE, "wind is not enabled (dn_enable_wind)");
+    const size_t bytes = (size_t)env->cfg.num_envs * sizeof(float4);
+    if (mean) DN_HIP(hipMemcpyAsync(mean, env->wind.mean, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (gust) DN_HIP(hipMemcpyAsync(gust, env->wind.gust, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_get_wind_config(const dn_env *env, dn_wind_config *out)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    if (!env->wind.mean) return 0;
+    *out = env->wind_cfg;
     return 1;
 }
 

@@ -127,6 +127,21 @@ struct DnDyn {
     int pad_;
 };
 
+// Per-drone wind (dn_enable_wind): a steady part wbar drawn per episode and an Ornstein-Uhlenbeck gust g, both world frame, m/s.  Not a
+// field of DnParams for the same reason as DnDyn; it travels with DnDyn in the last argument of the one-wave step kernels instantiated with
+// the wind (dn_step_many_1w_kernel<..., DYN = true, WIND = true>) and as the last argument of the reset kernel.
+struct DnWind {
+    float4 *mean;           // [N] wbar (x, y, z, 0); nullptr = wind not enabled
+    float4 *gust;           // [N] g (x, y, z, 0): mean + N of the same allocation
+    double a;               // exp(-dt / tau): the gust's one-step autocorrelation (float64 on the host, cast to R in the kernel)
+    double b[2];            // sigma sqrt(1 - a^2), (xy, z)
+    float speed[2], azimuth[2], vertical[2];    // ranges of the steady draw [lo, hi]
+    float sigma[2];         // stationary gust standard deviation (xy, z)
+    float k[2];             // force per unit wind speed (k_xy, k_z), N s / m
+    int resample;           // 1: draw wbar at every episode start; 0: keep what dn_set_wind wrote
+    int gust_on;            // sigma != (0, 0): launch-uniform; 0 = no draws, g held between episode starts and 0 from each
+};
+
 // dn_set_launch_events (ABI 8): the step kernel of the next dn_step / dn_step_many launch is dispatched with these two hipEvents attached to
 // its own dispatch packet (hipExtLaunchKernelGGL) -- they time the kernel itself, like a profiler's kernel trace, where a pair of
 // hipEventRecord around the call would also time the host's launch path and add two marker packets to the stream.  One shot: the
@@ -140,9 +155,10 @@ extern thread_local hipEvent_t dn_tl_ev_start, dn_tl_ev_stop;
 
 int dn_norm_exact_compiled_in();      // 1 in libdronenav_exact.so (-DDN_NORM_EXACT=1: the normaliser's float64 output stage), else 0
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream,
-                               const DnDyn *dy = nullptr);    // dy->dyn != nullptr: the one-wave kernel with the scales, whatever `waves` says
+                               const DnDyn *dy = nullptr,     // dy->dyn != nullptr: the one-wave kernel with the scales, whatever `waves` says
+                               const DnWind *wd = nullptr);   // wd->mean != nullptr: the one-wave kernel with the wind (and dy's scales, if any)
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);   // dn_kernels_mw.hip
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy = nullptr);
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy = nullptr, const DnWind *wd = nullptr);
 hipError_t dn_launch_eval_kinematics(const DnParams &p, const DnStepIO &io, const double *kin, bool f32, hipStream_t stream);
 hipError_t dn_launch_gae(const float *rewards, const float *values, const uint8_t *dones,
                          const float *last_values, const uint8_t *last_dones, long long T, long long N,

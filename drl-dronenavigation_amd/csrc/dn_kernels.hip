@@ -1387,11 +1387,65 @@ DN_DEV float4 dyn_draw(const DnDyn &dy, const unsigned long long seed, const uns
     return make_float4(s[0], s[1], s[2], s[3]);
 }
 
-// DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
-template <typename R, typename TH = Thrust, bool XOPT = false, bool DYN = false>
-DN_DEV Flight<R> physics_phase(const TH &th, const float4 G0, const float4 G1, const float4 G2, const float4 G3,
-                               const int max_steps, const Extras *x = nullptr, const DynK<R> *dk = nullptr)
+// ---- per-drone wind (dn_enable_wind) ------------------------------------------------------------------------------------
+// w = wbar + g (world frame, m/s) pushes the body with F_w = (k_xy w_x, k_xy w_y, k_z w_z) at the centre of mass: F_w / (M s_m) joins the
+// extra accelerations of the option kernels.  wbar and g are float32 state held in registers across a fused launch, so K steps in one
+// launch are K single-step launches bit for bit.  Every draw is keyed like dyn_draw (seed; global drone id, vector step, stream):
+// 14 the steady part at an episode start, 15 the gust's step, 16 the gust at an episode start.
+template <typename R> struct WindF {
+    R x, y, z;              // F_w, N
+};
+template <typename R> DN_DEV WindF<R> wind_force(const DnWind &w, const float4 WB, const float4 WG)
 {
+    WindF<R> f;
+    const R kxy = (R)w.k[0], kz = (R)w.k[1];
+    f.x = kxy * ((R)WB.x + (R)WG.x);
+    f.y = kxy * ((R)WB.y + (R)WG.y);
+    f.z = kz * ((R)WB.z + (R)WG.z);
+    return f;
+}
+// The steady wind of an episode: ONE Philox4x32-10 call on stream 14, u_j = (r_j + 0.5) / 2^32; in float64 s = speed_lo + (speed_hi -
+// speed_lo) u0, theta = az_lo + (az_hi - az_lo) u1, v = vert_lo + (vert_hi - vert_lo) u2; wbar = (s cos theta, s sin theta, v) stored
+// as float32 (r_3 unused).  An episode start only: the libm cos / sin are not on the per-step path.
+DN_DEV float4 wind_mean_draw(const DnWind &w, const unsigned long long seed, const unsigned long long gid, const unsigned long long step)
+{
+    unsigned r[4];
+    philox4x32((unsigned)gid, (unsigned)(gid >> 32), (unsigned)step, 14u | ((unsigned)(step >> 32) << 8), (unsigned)seed,
+               (unsigned)(seed >> 32), r);
+    double u[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) u[j] = ((double)r[j] + 0.5) * (1.0 / 4294967296.0);
+    const double s = (double)w.speed[0] + ((double)w.speed[1] - (double)w.speed[0]) * u[0];
+    const double th = (double)w.azimuth[0] + ((double)w.azimuth[1] - (double)w.azimuth[0]) * u[1];
+    const double v = (double)w.vertical[0] + ((double)w.vertical[1] - (double)w.vertical[0]) * u[2];
+    return make_float4((float)(s * cos(th)), (float)(s * sin(th)), (float)v, 0.0f);
+}
+// The gust at an episode start, a draw from the stationary law: sigma * (the first three values of the exact noise4 on stream 16)
+DN_DEV float4 wind_gust_draw(const DnWind &w, const unsigned long long seed, const unsigned long long gid, const unsigned long long step)
+{
+    float z[4];
+    noise4<true>(seed, gid, step, 16u, z);
+    return make_float4(w.sigma[0] * z[0], w.sigma[0] * z[1], w.sigma[1] * z[2], 0.0f);
+}
+// One step of the Ornstein-Uhlenbeck gust after the physics of vector step `step`: g <- float32(a g + b xi), evaluated in R, xi = the first
+// three values of the exact noise4 on stream 15 (the draws that feed the dynamics use the float64 Box-Muller form)
+template <typename R>
+DN_DEV float4 wind_gust_step(const DnWind &w, const float4 g, const unsigned long long seed, const unsigned long long gid,
+                             const unsigned long long step)
+{
+    float z[4];
+    noise4<true>(seed, gid, step, 15u, z);
+    const R a = (R)w.a, bxy = (R)w.b[0], bz = (R)w.b[1];
+    return make_float4((float)(a * (R)g.x + bxy * (R)z[0]), (float)(a * (R)g.y + bxy * (R)z[1]), (float)(a * (R)g.z + bz * (R)z[2]), 0.0f);
+}
+
+// DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
+// WIND (with DYN): the wind force *wf over the mass of *dk joins the extra accelerations
+template <typename R, typename TH = Thrust, bool XOPT = false, bool DYN = false, bool WIND = false>
+DN_DEV Flight<R> physics_phase(const TH &th, const float4 G0, const float4 G1, const float4 G2, const float4 G3,
+                               const int max_steps, const Extras *x = nullptr, const DynK<R> *dk = nullptr, const WindF<R> *wf = nullptr)
+{
+    static_assert(!WIND || (DYN && XOPT), "the wind rides on the option kernels with the body terms");
     Flight<R> fl;
     flight_entry<R>(fl, G0, G2, G3, max_steps);
     // rotor thrusts along body z at the prop offsets (+,-) (-,-) (-,+) (+,+) * 0.028 (cf2x.urdf:42,54,66,78)
@@ -1436,6 +1490,11 @@ DN_DEV Flight<R> physics_phase(const TH &th, const float4 G0, const float4 G1, c
             dax = (r00 * bx + r01 * by + r02 * bz) * inv_m;
             day = (r10 * bx + r11 * by + r12 * bz) * inv_m;
             daz = (r20 * bx + r21 * by + r22 * bz) * inv_m;
+        }
+        if constexpr (WIND) {   // F_w / (M s_m); Bullet's damping and the drag above keep the ground velocity
+            dax += wf->x * dk->inv_m;
+            day += wf->y * dk->inv_m;
+            daz += wf->z * dk->inv_m;
         }
         if constexpr (DYN) {    // KF scales every rotor force after the chain, the PID / RPM forms and the ground effect
             F0 *= dk->kf; F1 *= dk->kf; F2 *= dk->kf; F3 *= dk->kf;
@@ -2044,10 +2103,10 @@ DN_DEV BlockState block_state(const DnState &st, long long tile_base)
 }
 
 // thrust + physics of one step; the XOPT kernels take the float64 carriers and the optional force terms (N4)
-template <typename R, bool NOISE, bool XOPT, bool DYN = false>
+template <typename R, bool NOISE, bool XOPT, bool DYN = false, bool WIND = false>
 DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long long sc, const float4 A, const float4 G0, const float4 G1,
                      const float4 G2, const float4 G3, const float4 G7, float4 &rpm_now, double *pid_st = nullptr,
-                     const DynK<R> *dk = nullptr)
+                     const DynK<R> *dk = nullptr, const WindF<R> *wf = nullptr)
 {
     if (XOPT) {
         Extras x;
@@ -2056,7 +2115,7 @@ DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long lo
         cx.G0 = G0; cx.G1 = G1; cx.G2 = G2; cx.st = pid_st;
         const ThrustX th = thrust_phase_x<NOISE>(p, gid, sc, A, x, pid_st ? &cx : nullptr);
         rpm_now = make_float4((float)x.rpm[0], (float)x.rpm[1], (float)x.rpm[2], (float)x.rpm[3]);
-        return physics_phase<R, ThrustX, true, DYN>(th, G0, G1, G2, G3, p.max_steps, &x, dk);
+        return physics_phase<R, ThrustX, true, DYN, WIND>(th, G0, G1, G2, G3, p.max_steps, &x, dk, wf);
     }
     const Thrust th = thrust_phase<NOISE>(p, gid, sc, A);
     return physics_phase<R>(th, G0, G1, G2, G3, p.max_steps);
@@ -2127,10 +2186,18 @@ DN_DEV float4 sample_action(const DnStepIO &io, const unsigned long long gid, co
 // profiles (dn_step_many_*_kernel<..., true> = one control step per launch, <..., false> = k_arg steps per launch).
 // DYN (with XOPT): the per-drone body scales of dn_enable_dynamics, passed as the last argument.  Without them that argument is an empty
 // struct, which leaves the offsets of the kernel's other arguments -- and with them every instruction of the kernel -- as they were.
+// WIND (with DYN and XOPT): the argument also carries dn_enable_wind's state (WindArg); its scale pointer is null when dynamics are off,
+// and the body is then the nominal one (scales of 1).
 template <bool DYN> struct DynArg : DnDyn {};
 template <> struct DynArg<false> {};
-template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false>
-__global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg, const DynArg<DYN> dy)
+struct WindArg : DnDyn {
+    DnWind w;
+};
+template <bool DYN, bool WIND> struct StepArg { using type = DynArg<DYN>; };
+template <> struct StepArg<true, true> { using type = WindArg; };
+template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false>
+__global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg,
+                                                                   const typename StepArg<DYN, WIND>::type dy)
 {
     const int k_steps = ONE ? 1 : k_arg;
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
@@ -2156,7 +2223,12 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     if (XOPT && p.drag) G7 = b.g7[li];
     // dn_enable_dynamics: this drone's body scales, held with their derived terms in registers across the launch (1.0 = the nominal body)
     float4 S = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-    if constexpr (DYN) S = dy.dyn[i];
+    if constexpr (WIND) { if (dy.dyn) S = dy.dyn[i]; }
+    else if constexpr (DYN) S = dy.dyn[i];
+    // dn_enable_wind: this drone's steady wind and gust, held in registers across the launch
+    float4 WB = make_float4(0.0f, 0.0f, 0.0f, 0.0f), WG = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (WIND) { WB = dy.w.mean[i]; WG = dy.w.gust[i]; }
+    bool wind_new = false;                              // an episode started inside the launch: new wbar (resample) and g
     stage_table<R>(p, s_tab);
     block_lds_barrier();
     const long long n = p.n, words = (p.n + 63) / 64;
@@ -2185,7 +2257,10 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         const unsigned long long sc = sc0 + (unsigned long long)t;
         float4 rpm_now;
         const GateRow<R> row_e = load_gate_row<R>(s_tab, unpack_meta(G3.w).idx);
-        Flight<R> fl = fly<R, NOISE, XOPT, DYN>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr, DYN ? &dk : nullptr);
+        WindF<R> wf;
+        if constexpr (WIND) wf = wind_force<R>(dy.w, WB, WG);
+        Flight<R> fl = fly<R, NOISE, XOPT, DYN, WIND>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr, DYN ? &dk : nullptr,
+                                                      WIND ? &wf : nullptr);
         const float4 G0e = G0, G3e = G3;
         const Verdict<R> v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc);
         if (XOPT && p.drag) G7 = (v.terminated || fl.truncated) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : rpm_now;   // BaseAviary.py:442,545
@@ -2194,6 +2269,17 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
                 const bool done = v.terminated || fl.truncated;
                 if (__ballot(done) != 0ull) {           // wave-uniform: most wave-steps skip this
                     if (done) { S = dyn_draw(dy, p.seed, gid, sc); dk = dyn_terms<R>(S); redrawn = true; }
+                }
+            }
+        }
+        if constexpr (WIND) {
+            const bool done = v.terminated || fl.truncated;
+            if (dy.w.gust_on) WG = wind_gust_step<R>(dy.w, WG, p.seed, gid, sc);      // launch-uniform; sigma = 0: no draws
+            if (__ballot(done) != 0ull) {               // wave-uniform: the episode starts of this step take the stationary draw instead
+                if (done) {
+                    if (dy.w.resample) WB = wind_mean_draw(dy.w, p.seed, gid, sc);
+                    WG = dy.w.gust_on ? wind_gust_draw(dy.w, p.seed, gid, sc) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    wind_new = true;
                 }
             }
         }
@@ -2214,6 +2300,10 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         b.g0[li] = G0; b.g1[li] = G1; b.g2[li] = G2; b.g3[li] = G3; b.g4[li] = G4; b.g5[li] = G5;
         if (XOPT && p.drag) b.g7[li] = G7;
         if constexpr (DYN) { if (redrawn) dy.dyn[i] = S; }
+        if constexpr (WIND) {
+            if (dy.w.gust_on || wind_new) dy.w.gust[i] = WG;
+            if (wind_new && dy.w.resample) dy.w.mean[i] = WB;
+        }
     }
 }
 
@@ -3757,7 +3847,7 @@ __global__ __launch_bounds__(3 * DN_BLOCK) void dn_step_pqx_kernel(const DnParam
 // VecEnv.reset(): every drone goes through Monitor.reset / NormalizeObservation.reset / PBDroneEnv.reset.
 // =====================================================================================================
 template <typename R>
-__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy)
+__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd)
 {
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -3807,6 +3897,11 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
         b.g6[li] = make_float4((float)cpx, (float)cpy, (float)cpz, 0.0f);
         if (p.drag) b.g7[li] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);      // last_clipped_action, BaseAviary.py:545
         if (dy.dyn && dy.resample) dy.dyn[i] = dyn_draw(dy, p.seed, gid, p.st.stats[blockIdx.x].step_count);   // this episode's body
+        if (wd.mean) {                                                                                            // ... and its wind
+            const unsigned long long sc = p.st.stats[blockIdx.x].step_count;
+            if (wd.resample) wd.mean[i] = wind_mean_draw(wd, p.seed, gid, sc);
+            wd.gust[i] = wd.gust_on ? wind_gust_draw(wd, p.seed, gid, sc) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
     }
     store_obs_tile(s_tile, obs + tile_base * DN_OBS_DIM, rows, lane, o);
 }
@@ -4167,9 +4262,32 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 }
 #endif
 #elif DN_TU == 1
-hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnDyn *dy)
+hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnDyn *dy,
+                               const DnWind *wd)
 {
     const bool norm = p.normalize_obs != 0;
+    if (wd && wd->mean) {                   // dn_enable_wind: the one-wave option kernel with the wind and the body terms (scales of 1 without dynamics)
+        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the wind (the C ABI refuses them first)
+        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
+        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
+        WindArg wa;
+        static_cast<DnDyn &>(wa) = dy ? *dy : DnDyn{};
+        wa.w = *wd;
+#define DN_LW(R, NORM, NOISE)                                                                                                       \
+        do {                                                                                                                        \
+            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, wa); \
+            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, wa);   \
+        } while (0)
+        if (f32) {
+            if (norm) { if (noise) DN_LW(float, true, true); else DN_LW(float, true, false); }
+            else { if (noise) DN_LW(float, false, true); else DN_LW(float, false, false); }
+        } else {
+            if (norm) { if (noise) DN_LW(double, true, true); else DN_LW(double, true, false); }
+            else { if (noise) DN_LW(double, false, true); else DN_LW(double, false, false); }
+        }
+#undef DN_LW
+        return hipGetLastError();
+    }
     if (dy && dy->dyn) {                    // dn_enable_dynamics: the one-wave option kernel with the body scales, whatever the configuration
         if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the scales (the C ABI refuses them first)
         const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
@@ -4257,12 +4375,13 @@ hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, boo
 #undef DN_LAUNCH3
 
 #if DN_TU == 1
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy)
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy, const DnWind *wd)
 {
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
     const DnDyn dyn = dy ? *dy : DnDyn{};
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn);
+    const DnWind wnd = wd ? *wd : DnWind{};
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd);
     return hipGetLastError();
 }
 

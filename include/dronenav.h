@@ -102,7 +102,8 @@ typedef struct dn_config {
 
 /* One drone's persistent state, host-side AoS view used by dn_get_state/dn_set_state (tests,
  * checkpointing).  Field names follow the reference's attributes.  It does not carry the body scales of
- * dn_enable_dynamics: a checkpoint of a randomised fleet is dn_get_state + dn_get_dynamics (restore: dn_set_state + dn_set_dynamics). */
+ * dn_enable_dynamics: a checkpoint of a randomised fleet is dn_get_state + dn_get_dynamics (restore: dn_set_state + dn_set_dynamics),
+ * nor the wind of dn_enable_wind (+ dn_get_wind / dn_set_wind). */
 typedef struct dn_env_state {
     float pos[3], quat[4], vel[3], ang_v[3];    /* Bullet base state, BaseAviary.py:596-598 (quat = x,y,z,w) */
     float prev_vel[3], prev_ang_v[3];           /* PBDroneEnv.prev_vel / prev_ang_v */
@@ -388,7 +389,7 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
 int32_t dn_set_launch_events(dn_env *env, void *start_event, void *stop_event);
 
 /* Bytes of HBM the persistent state of `num_envs` drones occupies (capacity planning).  The body scales of dn_enable_dynamics are a
- * separate allocation of 16 bytes per drone and are not included. */
+ * separate allocation of 16 bytes per drone and are not included, nor is the wind of dn_enable_wind (32 bytes per drone). */
 int64_t dn_state_bytes(int64_t num_envs, int32_t normalize_obs);
 
 /* Per-drone dynamics randomisation (sim-to-real).  Each drone carries four float32 scale factors relative to the nominal cf2x body:
@@ -420,6 +421,47 @@ int32_t dn_set_dynamics(dn_env *env, const float *scales, void *stream);
 int32_t dn_get_dynamics(dn_env *env, float *scales, void *stream);
 /* 1: dynamics enabled, *out = the configuration last given to dn_enable_dynamics; 0: not enabled (*out untouched); < 0: error. */
 int32_t dn_get_dynamics_config(const dn_env *env, dn_dynamics_config *out);
+
+/* Per-drone wind (sim-to-real external disturbance).  Each drone carries a steady wind wbar and a gust g (float32 x 3, world frame, m/s)
+ * that push it with F_w = (k_xy w_x, k_xy w_y, k_z w_z) N, w = wbar + g, at the centre of mass (no torque): F_w / (M s_m) joins the
+ * linear acceleration in every physics mode (s_m = the mass scale of dn_enable_dynamics, 1 without).  Bullet's damping and the
+ * PYB_DRAG / ground-effect terms keep using the ground velocity.  The defaults of coeff are the cf2x rotor-drag coefficients at hover,
+ * k = DRAG_COEFF 4 HOVER_RPM 2 pi / 60 = (5.5626e-3, 6.2490e-3) N s / m: a 5 m/s wind is about 1.03 m/s^2 on the nominal body.
+ *   steady:  resample = 1: every episode start (dn_reset and every in-kernel auto-reset) draws, from ONE Philox4x32-10 call keyed
+ *            (seed; global drone id, the vector step the episode starts on, stream 14) with u_j = (r_j + 0.5) / 2^32, in float64:
+ *            s = speed lo + (hi - lo) u0, theta = azimuth lo + (hi - lo) u1 (the direction the air moves toward), v = vertical lo +
+ *            (hi - lo) u2, and stores wbar = (s cos theta, s sin theta, v) as float32.  resample = 0: wbar is what dn_set_wind last wrote.
+ *   gust:    an Ornstein-Uhlenbeck process with correlation time tau and stationary standard deviation sigma = (sigma_xy, sigma_xy,
+ *            sigma_z).  a = exp(-dt / tau), dt = 1/240, b = sigma sqrt(1 - a^2) (float64 on the host).  After the physics of vector
+ *            step sc: g <- float32(a g + b xi), xi = the first three normal draws of (seed; drone id, sc, stream 15) (Box-Muller in
+ *            float64, as the action noise).  An episode start at sc, whatever resample is, sets g = float32(sigma xi'), xi' from stream 16:
+ *            a draw from the stationary law, taken instead of the update.  sigma = (0, 0) switches the process off: no draws, g keeps
+ *            its value and becomes 0 at the drone's next episode start.
+ * New values act from the first physics step of the new episode; the reset observation does not depend on them.  wbar and g are float32
+ * state: a fused launch of K steps equals K single steps bit for bit.  A checkpoint is dn_get_state + dn_get_wind + dn_get_step_count.
+ * The wind lives in the one-wave option kernels: enabling forces dn_get_kernel_waves(env, 0 / 1) == 1.  dn_step_sampled,
+ * dn_step_squashed, dn_mlp_step_sampled and dn_eval_kinematics refuse an env with wind enabled (DN_ERR_INVALID_ARGUMENT). */
+typedef struct dn_wind_config {
+    float speed[2];       /* horizontal steady speed [lo, hi], m/s: 0 <= lo <= hi, finite */
+    float azimuth[2];     /* direction the air moves toward, radians [lo, hi]: finite, lo <= hi */
+    float vertical[2];    /* vertical steady component [lo, hi], m/s: finite, lo <= hi */
+    float gust_sigma[2];  /* stationary gust standard deviation (xy, z), m/s: finite, >= 0 */
+    float gust_tau;       /* gust correlation time, s: finite, > 0 */
+    float coeff[2];       /* (k_xy, k_z), N s / m: finite, >= 0 */
+    int32_t resample;     /* 1: draw wbar at every episode start; 0: keep dn_set_wind's */
+    int32_t reserved;     /* must be 0 */
+} dn_wind_config;
+/* Validates the configuration and enables the feature.  The first call allocates 32 bytes per drone (outside dn_state_bytes) and sets
+ * wbar = g = 0 (still air until each drone's next episode start, unless dn_set_wind writes them); a later call changes the
+ * configuration and keeps the current values.  Synchronises the device. */
+int32_t dn_enable_wind(dn_env *env, const dn_wind_config *cfg);
+/* Device [N][4] float32 rows (x, y, z, 0) of wbar (`mean`) and g (`gust`), copied on `stream`; NULL = leave (set) / skip (get).
+ * DN_ERR_BAD_STATE if wind is not enabled.  dn_set_wind does not validate the values (the caller's device buffers are not read on the
+ * host): every value must be finite. */
+int32_t dn_set_wind(dn_env *env, const float *mean, const float *gust, void *stream);
+int32_t dn_get_wind(dn_env *env, float *mean, float *gust, void *stream);
+/* 1: wind enabled, *out = the configuration last given to dn_enable_wind; 0: not enabled (*out untouched); < 0: error. */
+int32_t dn_get_wind_config(const dn_env *env, dn_wind_config *out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,540 @@
+"""Per-drone wind (include/dronenav.h dn_enable_wind) on the HIP path: zero wind is still air bit for bit, the steady force against the
+independent integrator of tests/rigid_body_ref.py and a closed form, the Philox draws and the gust recursion against their definitions
+(and the gust's statistics), launch shape, episode starts, sharding, the refusals of the sampling-fused entry points, and checkpointing
+through get_state + get_wind + step_count."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+from scipy import stats
+from scipy.spatial.transform import Rotation
+
+import rigid_body_ref as RB
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+WIDE = [-1e4, -1e4, -1e4, 1e4, 1e4, 1e4]
+DEV = "cuda:0"
+STATE_KEYS = ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev", "idx", "steps", "just_found", "ep_ret",
+              "ep_len", "rms_mean", "rms_var", "rms_count", "last_rpm", "ep_ret_lo")
+ZERO = dict(speed=(0.0, 0.0), azimuth=(0.0, 0.0), vertical=(0.0, 0.0), gust_sigma=(0.0, 0.0))
+GUSTY = dict(speed=(0.5, 6.0), azimuth=(-math.pi, math.pi), vertical=(-0.5, 0.5), gust_sigma=(0.8, 0.3), gust_tau=0.25)
+DT = 1.0 / 240.0
+
+
+def _pkg():
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
+    import drl_dronenavigation_amd as pkg
+    return pkg
+
+
+def _mixed(rng, n):
+    bang = rng.uniform(-1, 1, (n, 4))
+    hover = 0.0922 + 0.003 * rng.standard_normal((n, 4))
+    return np.where((np.arange(n) % 2 == 0)[:, None], bang, hover).astype(np.float32)
+
+
+def _acts(rng, n, K):
+    return torch.from_numpy(np.stack([_mixed(rng, n) for _ in range(K)])).to(DEV)
+
+
+def _philox(gid, step, stream, seed):
+    from oracle import oracle as O
+    out = (C.c_uint32 * 4)()
+    O.lib().orc_philox4x32(gid & 0xFFFFFFFF, gid >> 32, step & 0xFFFFFFFF, stream | ((step >> 32) << 8), seed & 0xFFFFFFFF, seed >> 32, out)
+    return np.array(list(out), dtype=np.float64)
+
+
+def _noise(seed, gid0, n, step, stream):
+    """orc_noise4 of drones gid0 .. gid0 + n - 1: [n, 4] float32 (Box-Muller on the C library's log / sqrt / cos / sin)."""
+    from oracle import oracle as O
+    out = np.zeros((n, 4), np.float32)
+    O.lib().orc_noise4_many(seed, gid0, n, step, stream, out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+def _mean_draw(w, gid, step, seed):
+    """The documented steady draw: one Philox4x32-10 call on (seed; gid, step, stream 14), float64, stored as float32."""
+    u = (_philox(gid, step, 14, seed)[:3] + 0.5) / 4294967296.0
+    f = lambda r: (float(np.float32(r[0])), float(np.float32(r[1])))
+    (s0, s1), (a0, a1), (v0, v1) = f(w.speed), f(w.azimuth), f(w.vertical)
+    s, th, v = s0 + (s1 - s0) * u[0], a0 + (a1 - a0) * u[1], v0 + (v1 - v0) * u[2]
+    return np.array([s * math.cos(th), s * math.sin(th), v, 0.0], dtype=np.float32)
+
+
+def _ulps(a, b):
+    """Distance in float32 ulps (same-sign values; 0 and -0 are 0 apart)."""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    ia, ib = a.view(np.int32).astype(np.int64), b.view(np.int32).astype(np.int64)
+    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia)
+    ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
+    return np.abs(ia - ib)
+
+
+def _sigma3(w):
+    return np.array([w.gust_sigma[0], w.gust_sigma[0], w.gust_sigma[1], 0.0], np.float32)
+
+
+def _same_state(a, b):
+    for k in STATE_KEYS:
+        assert np.ascontiguousarray(a[k]).tobytes() == np.ascontiguousarray(b[k]).tobytes(), k
+
+
+def _same_wind(a, b):
+    for x, y in zip(a.get_wind(), b.get_wind()):
+        assert torch.equal(x, y)
+
+
+def _run_pair(envs, rng, n, launches=3, K=20):
+    """Reset, one dn_step and `launches` fused launches of K steps on every env with the same actions: the outputs, bit for bit."""
+    outs = [e.reset_tensor().clone() for e in envs]
+    for o in outs[1:]:
+        assert torch.equal(outs[0], o)
+    a = torch.from_numpy(_mixed(rng, n)).to(DEV)
+    res = [tuple(x.clone() for x in e.step_tensor(a)[:3]) for e in envs]
+    for r in res[1:]:
+        for x, y in zip(res[0], r):
+            assert torch.equal(x, y)
+    n_done = 0
+    for _ in range(launches):
+        acts = _acts(rng, n, K)
+        rs = [{k: v.clone() for k, v in e.rollout_tensor(acts, want_terminal=True).items()} for e in envs]
+        for r in rs[1:]:
+            for k in rs[0]:
+                assert torch.equal(rs[0][k], r[k]), k
+        n_done += int(rs[0]["done"].sum())
+    sts = [e.get_state() for e in envs]
+    for s in sts[1:]:
+        _same_state(sts[0], s)
+    return n_done
+
+
+def _bullet_env(pkg, n, wind, **kw):
+    """A free body far from every target and wall: no episode ends, actions are the four rotor thrusts."""
+    opts = dict(target_points=np.array([[5e3, 5e3, 5e3]]), initial_xyzs=np.array([[0.0, 0.0, 1.0]]), aviary_dim=WIDE,
+                circle=False, cylinder=False, ground_contact=False, normalize_actions=False, normalize_obs=False,
+                threshold=0.0, max_steps=1 << 20, device=DEV, wind=wind)
+    opts.update(kw)
+    return pkg.DroneVecEnv(None, n, **opts)
+
+
+# ---- 1. identity --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("norm", [True, False])
+@pytest.mark.parametrize("f32", [False, True])
+def test_zero_wind_is_still_air_bit_for_bit(norm, f32, monkeypatch):
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    monkeypatch.delenv("DN_WAVES", raising=False)       # the wind-off env runs dn_create's own pick
+    n = 2048
+    kw = dict(max_steps=15, seed=11, device=DEV, normalize_obs=norm, compute_dtype="float32" if f32 else "float64")
+    track = tracks.reaching()
+    windy = pkg.DroneVecEnv(track, n, wind=pkg.WindDisturbance(**ZERO), **kw)
+    plain = pkg.DroneVecEnv(track, n, **kw)
+    assert windy.kernel_waves(fused=True) == windy.kernel_waves(fused=False) == 1
+    assert _run_pair([windy, plain], np.random.default_rng(3), n) > n     # episodes ended and restarted inside the fused launches
+    for x in windy.get_wind():
+        assert not bool(x.any())
+    windy.close()
+    plain.close()
+
+
+def test_zero_wind_with_dynamics_is_dynamics_alone_bit_for_bit():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    n = 2048
+    d = pkg.DynamicsRandomization(mass=(0.8, 1.2), inertia=(0.7, 1.3), kf=(0.9, 1.1), km=(0.8, 1.2))
+    kw = dict(max_steps=15, seed=13, device=DEV, normalize_obs=True, dynamics=d)
+    track = tracks.reaching()
+    windy = pkg.DroneVecEnv(track, n, wind=pkg.WindDisturbance(**ZERO), **kw)
+    plain = pkg.DroneVecEnv(track, n, **kw)
+    assert _run_pair([windy, plain], np.random.default_rng(4), n) > n
+    assert torch.equal(windy.get_dynamics(), plain.get_dynamics())
+    windy.close()
+    plain.close()
+
+
+# ---- 2. physics against the independent integrator ----------------------------------------------------------------------
+@pytest.mark.parametrize("with_dynamics", [False, True])
+def test_steady_wind_step_matches_independent_integrator(with_dynamics, monkeypatch):
+    """Random tumbling states, random thrusts and random steady winds: the HIP step against tests/rigid_body_ref.py with
+    extra_world_force = k (.) w (and with random body scales: M, J per drone, forces x s_kf, z-torque x s_km).  1e-5 abs + 1e-6 rel."""
+    pkg = _pkg()
+    rng = np.random.default_rng(41)
+    n = 512
+    quat = Rotation.random(n, random_state=8).as_quat().astype(np.float32)
+    quat /= np.linalg.norm(quat.astype(np.float64), axis=1, keepdims=True).astype(np.float32)
+    pos = (rng.uniform(-2, 2, (n, 3)) + [0, 0, 3]).astype(np.float32)
+    vel = rng.normal(0, 2.0, (n, 3)).astype(np.float32)
+    ang_v = rng.normal(0, 8.0, (n, 3)).astype(np.float32)
+    thrust = rng.uniform(0.02, 0.16, (n, 4)).astype(np.float32)
+    wind = np.zeros((n, 4), np.float32)
+    wind[:, :3] = rng.normal(0, 6.0, (n, 3))
+    cfg = pkg.WindDisturbance(resample=False, coeff=(5.5626e-3, 6.2490e-3))
+    kw = {}
+    scales = np.ones((n, 4), np.float32)
+    if with_dynamics:
+        scales = rng.uniform(0.7, 1.3, (n, 4)).astype(np.float32)
+        kw["dynamics"] = pkg.DynamicsRandomization(resample=False)
+    env = _bullet_env(pkg, n, cfg, **kw)
+    env.reset_tensor()
+    st = env.get_state()
+    st["pos"], st["quat"], st["vel"], st["ang_v"], st["cur_pos"] = pos, quat, vel, ang_v, pos
+    env.set_state(st)
+    if with_dynamics:
+        env.set_dynamics(torch.from_numpy(scales).to(DEV))
+    env.set_wind(mean=torch.from_numpy(wind).to(DEV), gust=torch.zeros((n, 4), device=DEV))
+    _, _, done, _ = env.step_tensor(torch.from_numpy(thrust).to(DEV))
+    torch.cuda.synchronize()
+    assert not done.any().item()
+    got_state = env.get_state()
+    env.close()
+    f, tq = RB.thrust_to_force(thrust.astype(np.float64))
+    zt = (tq * RB.YAW_SIGN).sum(-1)
+    k = np.array([np.float32(cfg.coeff[0]), np.float32(cfg.coeff[0]), np.float32(cfg.coeff[1])], np.float64)
+    M0, J0 = RB.M, RB.J.copy()
+    s = scales.astype(np.float64)
+    for i in range(n):
+        monkeypatch.setattr(RB, "M", M0 * s[i, 0])
+        monkeypatch.setattr(RB, "J", J0 * s[i, 1])
+        ref = RB.step(pos[i], quat[i].astype(np.float64), vel[i], ang_v[i], f[i] * s[i, 2], zt[i] * s[i, 3],
+                      extra_world_force=k * wind[i, :3].astype(np.float64))
+        for name, r in zip(("pos", "quat", "vel", "ang_v"), ref):
+            got = got_state[name][i].astype(np.float64)
+            if name == "quat" and np.dot(got, r) < 0:
+                r = -r
+            assert np.all(np.abs(got - r) <= 1e-5 + 1e-6 * np.abs(r)), f"drone {i}: {name} {got} vs {r}"
+
+
+# ---- 3. closed form -----------------------------------------------------------------------------------------------------
+def test_level_hover_in_steady_wind_closed_form():
+    pkg = _pkg()
+    n, steps, speed = 8, 48, 5.0
+    theta = np.linspace(-math.pi, math.pi, n, endpoint=False).astype(np.float64) + 0.3
+    cfg = pkg.WindDisturbance(resample=False)
+    env = _bullet_env(pkg, n, cfg, zero_damping=True)
+    env.reset_tensor()
+    mean = np.zeros((n, 4), np.float32)
+    mean[:, 0], mean[:, 1] = speed * np.cos(theta), speed * np.sin(theta)
+    env.set_wind(mean=torch.from_numpy(mean).to(DEV))
+    hover = torch.full((n, 4), RB.M * RB.G / 4.0, device=DEV)
+    for _ in range(steps):
+        _, _, done, _ = env.step_tensor(hover)
+        assert not done.any().item()
+    st = env.get_state()
+    env.close()
+    kxy = float(np.float32(cfg.coeff[0]))
+    v = st["vel"].astype(np.float64)
+    want = steps * DT * kxy * mean[:, :2].astype(np.float64) / RB.M
+    assert abs(kxy * speed / RB.M - 1.03) < 0.01                     # the documented scale: 5 m/s ~ 1.03 m/s^2 on the nominal body
+    np.testing.assert_allclose(v[:, :2], want, rtol=1e-5, atol=0)
+    np.testing.assert_array_equal(st["ang_v"], 0.0)
+
+
+# ---- 4. draws -----------------------------------------------------------------------------------------------------------
+def test_reset_draws_follow_their_definition():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    n, seed = 65536, 0x2468_ACE0_1357
+    w = pkg.WindDisturbance(speed=(1.0, 7.0), azimuth=(-2.0, 2.5), vertical=(-0.75, 0.5), gust_sigma=(0.8, 0.3), gust_tau=0.25)
+    env = pkg.DroneVecEnv(tracks.reaching(), n, wind=w, seed=seed, normalize_obs=False, device=DEV)
+    assert bytes(env.wind_config().to_c()) == bytes(w.to_c())
+    sc = env.step_count
+    env.reset_tensor()
+    mean, gust = (x.cpu().numpy() for x in env.get_wind())
+    ids = list(range(512)) + list(range(n - 512, n))
+    want = np.stack([_mean_draw(w, g, sc, seed) for g in ids])
+    assert _ulps(mean[ids], want).max(initial=0) <= 1
+    wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
+    wg[:, 3] = 0.0
+    assert _ulps(gust, wg).max(initial=0) <= 1
+    assert np.mean(gust == wg) > 0.999
+    s = np.hypot(mean[:, 0].astype(np.float64), mean[:, 1].astype(np.float64))
+    th = np.arctan2(mean[:, 1], mean[:, 0]).astype(np.float64)
+    for x, (lo, hi) in ((s, w.speed), (th, w.azimuth), (mean[:, 2].astype(np.float64), w.vertical)):
+        assert x.min() >= lo - 1e-5 and x.max() <= hi + 1e-5
+        p = stats.kstest((x - lo) / (hi - lo), "uniform").pvalue
+        assert p > 1e-3, p
+    assert not mean[:, 3].any()
+    env.close()
+
+
+# ---- 5. gust recursion and statistics -----------------------------------------------------------------------------------
+def test_gust_recursion_follows_its_definition():
+    pkg = _pkg()
+    n, seed = 256, 99
+    w = pkg.WindDisturbance(speed=(0.0, 3.0), gust_sigma=(0.8, 0.3), gust_tau=0.25)
+    env = _bullet_env(pkg, n, w, seed=seed)
+    env.reset_tensor()
+    a = math.exp(-DT / float(np.float32(w.gust_tau)))            # a and b as the host computes them: float64 from the float32 config
+    b = _sigma3(w)[:3].astype(np.float64) * math.sqrt(1.0 - a * a)
+    hover = torch.full((n, 4), RB.M * RB.G / 4.0, device=DEV)
+    mean0, g = (x.cpu().numpy() for x in env.get_wind())
+    for t in range(64):
+        sc = env.step_count
+        _, _, done, _ = env.step_tensor(hover)
+        assert not done.any().item()
+        mean, g1 = (x.cpu().numpy() for x in env.get_wind())
+        xi = _noise(seed, 0, n, sc, 15)[:, :3].astype(np.float64)
+        want = (a * g[:, :3].astype(np.float64) + b * xi).astype(np.float32)
+        assert _ulps(g1[:, :3], want).max(initial=0) <= 1, t
+        assert np.array_equal(mean, mean0)
+        g = g1
+    env.close()
+
+
+def test_gust_statistics():
+    pkg = _pkg()
+    n, seed, T = 65536, 5, 240
+    w = pkg.WindDisturbance(gust_sigma=(0.8, 0.3), gust_tau=0.25)
+    env = _bullet_env(pkg, n, w, seed=seed)
+    env.reset_tensor()
+    hover = torch.full((T, n, 4), RB.M * RB.G / 4.0, device=DEV)
+    out = env.rollout_tensor(hover[:T - 1])
+    assert not out["done"].any().item()
+    g0 = env.get_wind()[1].cpu().numpy().astype(np.float64)[:, :3]
+    env.step_tensor(hover[0])
+    g1 = env.get_wind()[1].cpu().numpy().astype(np.float64)[:, :3]
+    env.close()
+    a = math.exp(-DT / w.gust_tau)
+    sig = np.array([w.gust_sigma[0], w.gust_sigma[0], w.gust_sigma[1]])
+    for j in range(3):
+        assert abs(g1[:, j].mean()) < 5 * sig[j] / math.sqrt(n), j
+        assert abs(g1[:, j].std() / sig[j] - 1.0) < 0.02, j
+        r = np.corrcoef(g0[:, j], g1[:, j])[0, 1]
+        assert abs(r - a) < 0.002, (j, r, a)
+
+
+# ---- 6. launch shape ----------------------------------------------------------------------------------------------------
+def test_one_fused_launch_equals_single_steps():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    n, K = 4096, 64
+    kw = dict(max_steps=15, seed=21, device=DEV, normalize_obs=True, wind=pkg.WindDisturbance(**GUSTY))
+    track = tracks.reaching()
+    a, b = pkg.DroneVecEnv(track, n, **kw), pkg.DroneVecEnv(track, n, **kw)
+    assert a.kernel_waves(fused=True) == a.kernel_waves(fused=False) == 1
+    assert torch.equal(a.reset_tensor(), b.reset_tensor())
+    acts = _acts(np.random.default_rng(6), n, K)
+    ra = {k: v.clone() for k, v in a.rollout_tensor(acts, want_terminal=True).items()}
+    n_done = 0
+    for t in range(K):
+        obs, rew, done, _ = b.step_tensor(acts[t].contiguous())
+        assert torch.equal(obs, ra["obs"][t]) and torch.equal(rew, ra["reward"][t]) and torch.equal(done, ra["done"][t]), t
+        n_done += int(done.sum())
+    assert n_done > n
+    _same_state(a.get_state(), b.get_state())
+    _same_wind(a, b)
+    a.close()
+    b.close()
+
+
+# ---- 7. episode starts --------------------------------------------------------------------------------------------------
+def test_episode_starts_redraw_only_the_finished_drones():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    n, seed = 1024, 77
+    w = pkg.WindDisturbance(**GUSTY)
+    env = pkg.DroneVecEnv(tracks.reaching(), n, wind=w, seed=seed, max_steps=6, normalize_obs=False, device=DEV)
+    env.reset_tensor()
+    rng = np.random.default_rng(2)
+    cur = env.get_wind()[0].cpu().numpy()
+    redrawn = 0
+    for t in range(9):
+        sc = env.step_count
+        _, _, done, _ = env.step_tensor(torch.from_numpy(_mixed(rng, n)).to(DEV))
+        done = done.cpu().numpy().astype(bool)
+        mean, gust = (x.cpu().numpy() for x in env.get_wind())
+        fin = np.flatnonzero(done)
+        for i in fin:
+            cur[i] = _mean_draw(w, i, sc, seed)         # the draw of the step the new episode starts on
+        assert _ulps(mean, cur).max(initial=0) <= 1, t
+        cur = mean.copy()
+        wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
+        assert _ulps(gust[fin, :3], wg[fin, :3]).max(initial=0) <= 1, t
+        redrawn += len(fin)
+    assert redrawn >= n                                 # max_steps = 6: every drone's episode ended at least once
+    env.close()
+
+
+def test_without_resample_set_wind_survives_resets_and_the_gust_is_redrawn():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    n, seed = 1024, 78
+    w = pkg.WindDisturbance(**dict(GUSTY, resample=False))
+    env = pkg.DroneVecEnv(tracks.reaching(), n, wind=w, seed=seed, max_steps=6, normalize_obs=False, device=DEV)
+    env.reset_tensor()
+    assert not bool(env.get_wind()[0].any())            # resample off: still air until set_wind
+    mean = torch.zeros((n, 4), device=DEV)
+    mean[:, :3] = torch.randn((n, 3), device=DEV, generator=torch.Generator(DEV).manual_seed(1)) * 3
+    env.set_wind(mean=mean)
+    rng = np.random.default_rng(3)
+    n_done = 0
+    for t in range(9):
+        sc = env.step_count
+        _, _, done, _ = env.step_tensor(torch.from_numpy(_mixed(rng, n)).to(DEV))
+        m, gust = env.get_wind()
+        assert torch.equal(m, mean), t
+        fin = np.flatnonzero(done.cpu().numpy())
+        wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
+        assert _ulps(gust.cpu().numpy()[fin, :3], wg[fin, :3]).max(initial=0) <= 1, t
+        n_done += len(fin)
+    assert n_done >= n
+    sc = env.step_count
+    env.reset_tensor()
+    m, gust = env.get_wind()
+    assert torch.equal(m, mean)
+    wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
+    assert _ulps(gust.cpu().numpy()[:, :3], wg[:, :3]).max(initial=0) <= 1
+    env.close()
+
+
+# ---- 8. sharding --------------------------------------------------------------------------------------------------------
+def test_eight_shards_equal_the_whole_fleet():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    n, R, K = 32768, 8, 20
+    m = n // R
+    kw = dict(normalize_obs=False, max_steps=12, seed=2026, device=DEV, wind=pkg.WindDisturbance(**GUSTY),
+              dynamics=pkg.DynamicsRandomization(mass=(0.8, 1.2), inertia=(0.5, 1.5), kf=(0.9, 1.1), km=(0.7, 1.05)))
+    track = tracks.reaching()
+    whole = pkg.DroneVecEnv(track, n, **kw)
+    parts = [pkg.DroneVecEnv(track, m, env_id_offset=r * m, **kw) for r in range(R)]
+    assert torch.equal(whole.reset_tensor(), torch.cat([p.reset_tensor() for p in parts]))
+    rng = np.random.default_rng(5)
+    n_done = 0
+    for rep in range(3):
+        acts = _acts(rng, n, K)
+        a = whole.rollout_tensor(acts)
+        bs = [p.rollout_tensor(acts[:, r * m:(r + 1) * m].contiguous()) for r, p in enumerate(parts)]
+        for k in ("obs", "reward", "done", "truncated", "found_targets"):
+            assert torch.equal(a[k], torch.cat([b[k] for b in bs], dim=1)), (k, rep)
+        n_done += int(a["done"].sum())
+        for j in range(2):
+            assert torch.equal(whole.get_wind()[j], torch.cat([p.get_wind()[j] for p in parts])), rep
+        assert torch.equal(whole.get_dynamics(), torch.cat([p.get_dynamics() for p in parts])), rep
+    assert n_done >= n
+    _same_state(whole.get_state(), np.concatenate([p.get_state() for p in parts]))
+    for e in [whole] + parts:
+        e.close()
+
+
+# ---- 9. refusals and fallback -------------------------------------------------------------------------------------------
+def test_sampling_fused_entry_points_refuse_and_the_collectors_fall_back():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import _capi, tracks
+    from drl_dronenavigation_amd.collector import FusedRolloutCollector, OffPolicyCollector
+    from drl_dronenavigation_amd.policy_mfma import mlp_forward
+    lib = _capi.load()
+    dev = torch.device(DEV)
+    track = tracks.reaching()
+    n, T, seed = 512, 10, 17
+    kw = dict(normalize_obs=True, max_steps=6, seed=3, device=dev)
+    w = pkg.WindDisturbance(**GUSTY)
+    env, twin = pkg.DroneVecEnv(track, n, wind=w, **kw), pkg.DroneVecEnv(track, n, wind=w, **kw)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    z4, z1 = torch.zeros((n, 4), device=dev), torch.zeros(n, device=dev)
+    z13, zb, zi = torch.zeros((n, 13), device=dev), torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+    z8, zk = torch.zeros((n, 8), device=dev), torch.zeros((n, 13), dtype=torch.float64, device=dev)
+    log_std = (C.c_float * 4)(-5.0, -5.0, -5.0, -5.0)
+    env.reset_tensor()
+    sc0 = env.step_count
+
+    def refused(name, rc):
+        assert rc == -1 and b"wind" in lib.dn_last_error(), (name, rc, lib.dn_last_error())
+
+    calls = {
+        "dn_step_sampled": lambda: lib.dn_step_sampled(env._handle, z4.data_ptr(), log_std, seed, 0, z4.data_ptr(), z1.data_ptr(), z13.data_ptr(),
+                                               z1.data_ptr(), zb.data_ptr(), zb.data_ptr(), zi.data_ptr(), None, None, None, None, stream),
+        "dn_step_squashed": lambda: lib.dn_step_squashed(env._handle, z8.data_ptr(), seed, 0, z4.data_ptr(), None, z13.data_ptr(), z1.data_ptr(),
+                                                 zb.data_ptr(), zb.data_ptr(), zi.data_ptr(), None, None, None, None, stream),
+        "dn_mlp_step_sampled": lambda: lib.dn_mlp_step_sampled(env._handle, C.byref(_capi.DnMlpNet()), 1, z13.data_ptr(), 13, log_std, seed, 0,
+                                                       z4.data_ptr(), z1.data_ptr(), z13.data_ptr(), z1.data_ptr(), zb.data_ptr(), zb.data_ptr(),
+                                                       zi.data_ptr(), None, None, None, None, stream),
+        "dn_eval_kinematics": lambda: lib.dn_eval_kinematics(env._handle, zk.data_ptr(), z13.data_ptr(), z1.data_ptr(), zb.data_ptr(), zb.data_ptr(),
+                                                     zi.data_ptr(), None, None, None, stream),
+    }
+    for name, call in calls.items():
+        refused(name, call())
+    torch.cuda.synchronize()
+    assert env.step_count == sc0                         # the refused calls launched nothing
+
+    torch.manual_seed(4)
+    net = pkg.MlpActorCritic(log_std_init=-5.0).to(dev)
+    with torch.no_grad():
+        net.action_net.bias.fill_(0.0922)
+    pol = pkg.FusedMlpPolicy(net, n, dev)
+    env2 = pkg.DroneVecEnv(track, n, wind=w, **kw)
+    col = FusedRolloutCollector(env2, pol, T, bootstrap_truncated=False, use_graph=False, seed=seed)
+    assert not col._sampled_step
+    out = {k: v.clone() for k, v in col.collect().items()}
+    obs = twin.reset_tensor().clone()
+    assert torch.equal(obs, out["obs"][0])
+    act, clipped, logp = torch.zeros((n, 4), device=dev), torch.zeros((n, 4), device=dev), torch.zeros(n, device=dev)
+    mean, val = torch.zeros((n, 4), device=dev), torch.zeros((n, 1), device=dev)
+    for t in range(T):
+        mlp_forward([pol.pi, pol.vf], obs, [mean, val])
+        _capi.check(lib.dn_policy_sample(twin._handle, mean.data_ptr(), log_std, seed, 0, act.data_ptr(), clipped.data_ptr(), logp.data_ptr(), stream))
+        nobs, rew, done, _ = twin.step_tensor(clipped, want_terminal=False)
+        assert torch.equal(act, out["actions"][t]) and torch.equal(logp, out["log_probs"][t]) and torch.equal(rew, out["rewards"][t]), t
+        assert torch.equal(nobs, out["next_obs"] if t == T - 1 else out["obs"][t + 1]), t
+        obs = nobs.clone()
+    assert int(out["episode_starts"].sum()) > n
+    _same_wind(env2, twin)
+    # ... and the wind is live: the same rollout in still air goes elsewhere
+    plain = pkg.DroneVecEnv(track, n, **kw)
+    colp = FusedRolloutCollector(plain, pol, T, bootstrap_truncated=False, use_graph=False, seed=seed)
+    assert colp._sampled_step
+    outp = colp.collect()
+    assert not torch.equal(outp["obs"][T - 1], out["obs"][T - 1])
+    torch.manual_seed(8)
+    sac = pkg.FusedSacActor(pkg.SacActor().to(dev), n, dev, grade="bf16")
+    assert not OffPolicyCollector(twin, sac, buffer_size=4)._fused_sample and OffPolicyCollector(plain, sac, buffer_size=4)._fused_sample
+    for e in (env, env2, twin, plain):
+        e.close()
+
+
+# ---- 10. round trip and checkpoint --------------------------------------------------------------------------------------
+def test_set_get_round_trip_and_checkpoint_continuation():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    n, K = 4096, 20
+    kw = dict(normalize_obs=False, max_steps=15, seed=9, device=DEV, wind=pkg.WindDisturbance(**GUSTY))
+    track = tracks.reaching()
+    a = pkg.DroneVecEnv(track, n, **kw)
+    a.reset_tensor()
+    x, y = torch.randn((n, 4), device=DEV), torch.randn((n, 4), device=DEV)
+    a.set_wind(mean=x, gust=y)
+    assert all(torch.equal(u, v) for u, v in zip(a.get_wind(), (x, y)))
+    a.set_wind(gust=x)
+    assert all(torch.equal(u, v) for u, v in zip(a.get_wind(), (x, x)))
+    for bad in (dict(mean=x.double()), dict(mean=x[:-1]), dict(gust=x * float("inf")), dict(gust=x * float("nan")), dict(mean=x.cpu())):
+        with pytest.raises((TypeError, ValueError)):
+            a.set_wind(**bad)
+    rng = np.random.default_rng(12)
+    a.rollout_tensor(_acts(rng, n, K))
+    st, (mean, gust), sc = a.get_state(), a.get_wind(), a.step_count
+    b = pkg.DroneVecEnv(track, n, **kw)
+    b.reset_tensor()
+    b.set_state(st)
+    b.set_wind(mean=mean, gust=gust)
+    b.step_count = sc
+    for _ in range(2):
+        acts = _acts(rng, n, K)
+        ra = {k: v.clone() for k, v in a.rollout_tensor(acts, want_terminal=True).items()}
+        rb = b.rollout_tensor(acts, want_terminal=True)
+        assert int(ra["done"].sum()) > 0
+        for k in ra:
+            assert torch.equal(ra[k], rb[k]), k
+    _same_wind(a, b)
+    _same_state(a.get_state(), b.get_state())
+    off = pkg.DroneVecEnv(track, 64, device=DEV)
+    assert off.wind_config() is None
+    with pytest.raises(RuntimeError):
+        off.get_wind()
+    off.close()
+    a.close()
+    b.close()
