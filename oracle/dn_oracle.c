@@ -208,7 +208,16 @@ void orc_bullet_step_ex(double pos[3], double quat[4], double vel[3], double ang
 void orc_bullet_step_damp(double pos[3], double quat[4], double vel[3], double ang_v[3],
                           const double forces[4], double z_torque, const double body_force[3], double damp)
 {
+    orc_bullet_step_dw(pos, quat, vel, ang_v, forces, z_torque, body_force, damp, 1.0, 1.0, NULL);
+}
+
+/* mass_scale / inertia_scale: the body M s_m, diag(Ixx, Iyy, Izz) s_I (dn_enable_dynamics; 1 = cf2x, the same bits).
+ * world_force: dn_enable_wind's F_w, a world-frame force at the centre of mass (no torque), over M s_m; NULL = none. */
+void orc_bullet_step_dw(double pos[3], double quat[4], double vel[3], double ang_v[3], const double forces[4], double z_torque,
+                        const double body_force[3], double damp, double mass_scale, double inertia_scale, const double world_force[3])
+{
     const double dt = ORC_DT;
+    const double m = ORC_M * mass_scale;
     double R[9];
     quat_to_mat(quat, R);                       /* base -> world */
     double vb[3], wb[3];
@@ -223,7 +232,7 @@ void orc_bullet_step_damp(double pos[3], double quat[4], double vel[3], double a
         ty -= ORC_PROP_X[i] * forces[i];
     }
     /* gravity is a world-frame base force m*g, rotated into the base frame */
-    const double gw[3] = {0.0, 0.0, -ORC_G * ORC_M};
+    const double gw[3] = {0.0, 0.0, -ORC_G * m};
     double gb[3];
     matT_vec(R, gw, gb);
 
@@ -231,10 +240,10 @@ void orc_bullet_step_damp(double pos[3], double quat[4], double vel[3], double a
     double kl = damp + damp * nv;
     double ka = damp + damp * nw;
     /* body_force: LINK_FRAME force on link 4, whose frame coincides with the base frame (cf2x.urdf:88-98) */
-    double Fb[3] = { body_force[0] + gb[0] - ORC_M * vb[0] * kl,
-                     body_force[1] + gb[1] - ORC_M * vb[1] * kl,
-                     body_force[2] + fz + gb[2] - ORC_M * vb[2] * kl };
-    const double I[3] = {ORC_IXX, ORC_IYY, ORC_IZZ};
+    double Fb[3] = { body_force[0] + gb[0] - m * vb[0] * kl,
+                     body_force[1] + gb[1] - m * vb[1] * kl,
+                     body_force[2] + fz + gb[2] - m * vb[2] * kl };
+    const double I[3] = {ORC_IXX * inertia_scale, ORC_IYY * inertia_scale, ORC_IZZ * inertia_scale};
     double Iw[3] = {I[0] * wb[0], I[1] * wb[1], I[2] * wb[2]};
     double gyro[3] = { wb[1] * Iw[2] - wb[2] * Iw[1],
                        wb[2] * Iw[0] - wb[0] * Iw[2],
@@ -242,11 +251,13 @@ void orc_bullet_step_damp(double pos[3], double quat[4], double vel[3], double a
     double Tb[3] = { tx - gyro[0] - Iw[0] * ka,
                      ty - gyro[1] - Iw[1] * ka,
                      z_torque - gyro[2] - Iw[2] * ka };
-    double ab[3] = {Fb[0] / ORC_M, Fb[1] / ORC_M, Fb[2] / ORC_M};
+    double ab[3] = {Fb[0] / m, Fb[1] / m, Fb[2] / m};
     double wdb[3] = {Tb[0] / I[0], Tb[1] / I[1], Tb[2] / I[2]};
     double aw[3], wdw[3];
     mat_vec(R, ab, aw);
     mat_vec(R, wdb, wdw);
+    if (world_force)
+        for (int i = 0; i < 3; ++i) aw[i] += world_force[i] / m;
 
     for (int i = 0; i < 3; ++i) {               /* applyDeltaVeeMultiDof */
         ang_v[i] = clipd(ang_v[i] + wdw[i] * dt, -ORC_MAX_COORD_VEL, ORC_MAX_COORD_VEL);
@@ -737,6 +748,23 @@ void orc_env_reset(const orc_config *c, orc_env *e, float obs[ORC_OBS_DIM])
 /* PBDroneEnv.step (PBDroneEnv.py:171-199) around BaseAviary.step (BaseAviary.py:324-453). */
 void orc_env_step(const orc_config *c, orc_env *e, const float action[4], orc_step_out *out)
 {
+    orc_env_step_dw(c, NULL, NULL, e, action, out);
+}
+
+/* The same step flown by the body of s->dyn and pushed by the wind of s (dn_enable_dynamics / dn_enable_wind, dronenav.h): the
+ * action chain, HOVER_RPM and the PID loop stay nominal; s_kf multiplies every rotor force once the ground effect is added, s_km the
+ * yaw torque; mass and inertia scale in the rigid-body step; F_w is evaluated at step entry and acts over M s_m. */
+void orc_env_step_dw(const orc_config *c, const orc_dw_config *dwc, const orc_dw_state *s, orc_env *e, const float action[4],
+                     orc_step_out *out)
+{
+    const int dyn = dwc && s && dwc->dynamics, wind = dwc && s && dwc->wind;
+    double fw[3] = {0.0, 0.0, 0.0};
+    if (wind) {
+        const double kxy = (double)dwc->coeff[0], kz = (double)dwc->coeff[1];
+        fw[0] = kxy * ((double)s->wind_mean[0] + (double)s->wind_gust[0]);
+        fw[1] = kxy * ((double)s->wind_mean[1] + (double)s->wind_gust[1]);
+        fw[2] = kz * ((double)s->wind_mean[2] + (double)s->wind_gust[2]);
+    }
     float cmd[4], rpm32[4], f32[4], zt32;
     double rpm[4], f[4], zt, body_force[3] = {0.0, 0.0, 0.0};
     if (c->normalize_actions) orc_rescale_action(action, cmd);               /* :173-176 */
@@ -768,7 +796,12 @@ void orc_env_step(const orc_config *c, orc_env *e, const float action[4], orc_st
     }
     if (c->physics == 2 || c->physics == 4)                                  /* _drag(last_clipped_action), :425-427,435 */
         orc_drag(e->quat, e->vel, e->last_clipped_action, rpm_is_f32, body_force);
-    orc_bullet_step_damp(e->pos, e->quat, e->vel, e->ang_v, f, zt, body_force, c->zero_damping ? 0.0 : ORC_LIN_DAMP);   /* :439-440 */
+    if (dyn) {                                                               /* KF and KM of this drone's body */
+        for (int i = 0; i < 4; ++i) f[i] *= (double)s->dyn[2];
+        zt *= (double)s->dyn[3];
+    }
+    orc_bullet_step_dw(e->pos, e->quat, e->vel, e->ang_v, f, zt, body_force, c->zero_damping ? 0.0 : ORC_LIN_DAMP,   /* :439-440 */
+                       dyn ? (double)s->dyn[0] : 1.0, dyn ? (double)s->dyn[1] : 1.0, wind ? fw : NULL);
     memcpy(e->last_clipped_action, rpm, sizeof rpm);                         /* :442 */
     orc_euler_from_quat(e->quat, e->rpy);                                    /* :444 */
     orc_compute_obs(c, e, out->obs);                                         /* :446 */
@@ -924,7 +957,67 @@ static void finish_obs(const orc_config *c, orc_env *e, uint64_t env_id, uint32_
     }
 }
 
+/* Episode start of drone gid at vector step `step` (dn_enable_dynamics / dn_enable_wind, dronenav.h): with resample, new body scales
+ * lo + (hi - lo)(r + 0.5) / 2^32 from ONE Philox call on stream 13 and a new steady wind (speed, azimuth, vertical component uniform,
+ * stream 14), both in float64 stored as float32; the gust from its stationary law, float32(sigma xi') with xi' on stream 16 (0 with
+ * the gust off). */
+static int gust_on(const orc_dw_config *w) { return w->gust_sigma[0] > 0.0f || w->gust_sigma[1] > 0.0f; }
+static uint32_t ctr3(uint32_t stream, uint64_t step) { return stream | ((uint32_t)(step >> 32) << 8); }
+static void dw_episode_start(const orc_config *c, const orc_dw_config *w, orc_dw_state *s, uint64_t gid, uint64_t step)
+{
+    uint32_t r[4];
+    if (w->dynamics && w->dyn_resample) {
+        orc_philox4x32((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)step, ctr3(13u, step), (uint32_t)c->seed,
+                       (uint32_t)(c->seed >> 32), r);
+        for (int j = 0; j < 4; ++j) {
+            double u = ((double)r[j] + 0.5) * (1.0 / 4294967296.0);
+            double lo = w->dyn_lo[j], hi = w->dyn_hi[j];
+            s->dyn[j] = (float)(lo + (hi - lo) * u);
+        }
+    }
+    if (!w->wind) return;
+    if (w->wind_resample) {
+        orc_philox4x32((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)step, ctr3(14u, step), (uint32_t)c->seed,
+                       (uint32_t)(c->seed >> 32), r);
+        double u[3];
+        for (int j = 0; j < 3; ++j) u[j] = ((double)r[j] + 0.5) * (1.0 / 4294967296.0);
+        double sp = (double)w->speed[0] + ((double)w->speed[1] - (double)w->speed[0]) * u[0];
+        double th = (double)w->azimuth[0] + ((double)w->azimuth[1] - (double)w->azimuth[0]) * u[1];
+        double v = (double)w->vertical[0] + ((double)w->vertical[1] - (double)w->vertical[0]) * u[2];
+        s->wind_mean[0] = (float)(sp * cos(th)); s->wind_mean[1] = (float)(sp * sin(th)); s->wind_mean[2] = (float)v;
+        s->wind_mean[3] = 0.0f;
+    }
+    if (gust_on(w)) {
+        float z[4];
+        orc_noise4(c->seed, gid, step, 16u, z);
+        s->wind_gust[0] = w->gust_sigma[0] * z[0]; s->wind_gust[1] = w->gust_sigma[0] * z[1];
+        s->wind_gust[2] = w->gust_sigma[1] * z[2];
+    } else {
+        s->wind_gust[0] = s->wind_gust[1] = s->wind_gust[2] = 0.0f;
+    }
+    s->wind_gust[3] = 0.0f;
+}
+
+/* The gust's Ornstein-Uhlenbeck step after the physics of vector step `step`: g <- float32(a g + b xi), xi on stream 15, a = exp(-dt / tau)
+ * and b = sigma sqrt(1 - a^2) in float64 from the float32 configuration.  Off (no draws, g held) when sigma = (0, 0). */
+static void dw_gust_step(const orc_config *c, const orc_dw_config *w, orc_dw_state *s, uint64_t gid, uint64_t step)
+{
+    if (!w->wind || !gust_on(w)) return;
+    const double a = exp(-ORC_DT / (double)w->gust_tau);
+    const double root = sqrt(1.0 - a * a);
+    const double b[3] = {(double)w->gust_sigma[0] * root, (double)w->gust_sigma[0] * root, (double)w->gust_sigma[1] * root};
+    float z[4];
+    orc_noise4(c->seed, gid, step, 15u, z);
+    for (int j = 0; j < 3; ++j) s->wind_gust[j] = (float)(a * (double)s->wind_gust[j] + b[j] * (double)z[j]);
+}
+
 void orc_vec_reset(const orc_config *c, orc_env *envs, int64_t n, float *obs, int threads)
+{
+    orc_vec_reset_dw(c, NULL, NULL, envs, n, obs, threads);
+}
+
+void orc_vec_reset_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, orc_env *envs, int64_t n, float *obs,
+                      int threads)
 {
     (void)threads;
 #ifdef _OPENMP
@@ -934,6 +1027,7 @@ void orc_vec_reset(const orc_config *c, orc_env *envs, int64_t n, float *obs, in
         orc_env *e = &envs[i];
         orc_env_reset(c, e, &obs[i * ORC_OBS_DIM]);
         finish_obs(c, e, (uint64_t)(c->env_id_offset + i), 5u, &obs[i * ORC_OBS_DIM]);
+        if (dwc && dws) dw_episode_start(c, dwc, &dws[i], (uint64_t)(c->env_id_offset + i), e->step_count);
         e->ep_ret = 0.0; e->ep_len = 0;          /* Monitor.reset */
         if (c->f32_state) round_state_f32(e);
     }
@@ -942,6 +1036,14 @@ void orc_vec_reset(const orc_config *c, orc_env *envs, int64_t n, float *obs, in
 void orc_vec_step(const orc_config *c, orc_env *envs, int64_t n, const float *actions,
                   float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets,
                   float *terminal_obs, float *ep_ret, int32_t *ep_len, uint8_t *terminated, int threads)
+{
+    orc_vec_step_dw(c, NULL, NULL, envs, n, actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_ret, ep_len,
+                    terminated, threads);
+}
+
+void orc_vec_step_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, orc_env *envs, int64_t n,
+                     const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets,
+                     float *terminal_obs, float *ep_ret, int32_t *ep_len, uint8_t *terminated, int threads)
 {
     (void)threads;
 #ifdef _OPENMP
@@ -960,7 +1062,9 @@ void orc_vec_step(const orc_config *c, orc_env *envs, int64_t n, const float *ac
             }
         }
         orc_step_out so;
-        orc_env_step(c, e, a, &so);
+        orc_dw_state *s = (dwc && dws) ? &dws[i] : NULL;
+        orc_env_step_dw(c, dwc, s, e, a, &so);
+        if (s) dw_gust_step(c, dwc, s, gid, e->step_count);
         float *o = &obs[i * ORC_OBS_DIM];
         memcpy(o, so.obs, sizeof so.obs);
         finish_obs(c, e, gid, 1u, o);
@@ -979,6 +1083,7 @@ void orc_vec_step(const orc_config *c, orc_env *envs, int64_t n, const float *ac
             if (ep_len) ep_len[i] = e->ep_len;
             orc_env_reset(c, e, o);
             finish_obs(c, e, gid, 5u, o);
+            if (s) dw_episode_start(c, dwc, s, gid, e->step_count);      /* replaces the gust's update of this step */
             e->ep_ret = 0.0; e->ep_len = 0;
         }
         e->step_count += 1;
@@ -1024,6 +1129,8 @@ void orc_vec_refresh_rpy(orc_env *envs, int64_t n)
 
 int32_t orc_sizeof_env(void) { return (int32_t)sizeof(orc_env); }
 int32_t orc_sizeof_config(void) { return (int32_t)sizeof(orc_config); }
+int32_t orc_sizeof_dw_config(void) { return (int32_t)sizeof(orc_dw_config); }
+int32_t orc_sizeof_dw_state(void) { return (int32_t)sizeof(orc_dw_state); }
 int32_t orc_max_threads(void)
 {
 #ifdef _OPENMP

@@ -185,6 +185,50 @@ void orc_vec_step(const orc_config *cfg, orc_env *envs, int64_t n, const float *
 
 void orc_vec_refresh_rpy(orc_env *envs, int64_t n);   /* teacher-forcing helper: rpy cache <- quat */
 
+/* ---- per-drone dynamics randomisation and wind (dn_enable_dynamics / dn_enable_wind; not in the reference) ----
+ * Restated from the documented semantics (include/dronenav.h), not from the kernels.  Kept out of
+ * orc_config / orc_env so that their layout, the golden replays and bench.py's cpu_baseline see what they saw before.
+ *   body:  mass M s_m (linear acceleration, damping and PYB_DRAG force over M s_m; gravity stays g), inertia I s_I on all three
+ *          axes (I w, gyroscopic term, damping), every rotor force after the action chain x s_kf (ground effect included, after
+ *          it is added), the yaw torque x s_km.  Action chain, HOVER_RPM and DSLPIDControl stay nominal.
+ *   wind:  F_w = (k_xy w_x, k_xy w_y, k_z w_z), w = wbar + g at step entry, world frame, centre of mass, over M s_m; after every
+ *          physics step g <- float32(a g + b xi), xi = orc_noise4 on stream 15, a = exp(-dt / tau), b = sigma sqrt(1 - a^2) in float64.
+ *   episode starts (orc_vec_reset_dw and the auto-reset of orc_vec_step_dw), keyed (seed; gid, the step the episode starts on,
+ *          stream): resample -> new scales (ONE Philox call, stream 13), resample -> new wbar (stream 14); g = float32(sigma xi')
+ *          with xi' on stream 16 (0 with the gust off), taken instead of that step's update. */
+typedef struct orc_dw_config {
+    int32_t dynamics;                           /* 1: the body scales of orc_dw_state.dyn act */
+    int32_t dyn_resample;                       /* 1: draw new scales at every episode start */
+    float dyn_lo[4], dyn_hi[4];                 /* ranges of (s_m, s_I, s_kf, s_km) */
+    int32_t wind;                               /* 1: the wind of orc_dw_state acts */
+    int32_t wind_resample;                      /* 1: draw a new steady wind at every episode start */
+    float speed[2], azimuth[2], vertical[2];    /* ranges of the steady draw */
+    float gust_sigma[2];                        /* stationary gust standard deviation (xy, z); (0, 0): no gust process */
+    float gust_tau;                             /* gust correlation time, s */
+    float coeff[2];                             /* (k_xy, k_z), N s / m */
+} orc_dw_config;
+
+typedef struct orc_dw_state {
+    float dyn[4];                               /* s_m, s_I, s_kf, s_km */
+    float wind_mean[4];                         /* wbar (x, y, z, 0) */
+    float wind_gust[4];                         /* g (x, y, z, 0) */
+} orc_dw_state;
+
+/* one physics step with scaled mass and inertia and an extra WORLD-frame force at the centre of mass (may be NULL) */
+void orc_bullet_step_dw(double pos[3], double quat[4], double vel[3], double ang_v[3], const double forces[4], double z_torque,
+                        const double body_force[3], double damp, double mass_scale, double inertia_scale, const double world_force[3]);
+/* orc_env_step with the body and wind of *s (dwc / s NULL: the nominal step) */
+void orc_env_step_dw(const orc_config *cfg, const orc_dw_config *dwc, const orc_dw_state *s, orc_env *e, const float action[4],
+                     orc_step_out *out);
+/* the vec entry points with per-drone state dws[n]; dwc / dws NULL: exactly orc_vec_reset / orc_vec_step */
+void orc_vec_reset_dw(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_state *dws, orc_env *envs, int64_t n, float *obs,
+                      int threads);
+void orc_vec_step_dw(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_state *dws, orc_env *envs, int64_t n,
+                     const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets,
+                     float *terminal_obs, float *ep_ret, int32_t *ep_len, uint8_t *terminated, int threads);
+int32_t orc_sizeof_dw_config(void);
+int32_t orc_sizeof_dw_state(void);
+
 /* ---- N1: GAE (cleanRLPPO.py:234-248 + SB3 truncation bootstrap) ------------ */
 void orc_gae(const float *rewards, const float *values, const uint8_t *dones,
              const float *last_values, const uint8_t *last_dones,

@@ -66,6 +66,20 @@ class OrcEnv(C.Structure):
     ]
 
 
+class OrcDwConfig(C.Structure):
+    """orc_dw_config: per-drone dynamics randomisation and wind (dn_enable_dynamics / dn_enable_wind)."""
+    _fields_ = [
+        ("dynamics", C.c_int32), ("dyn_resample", C.c_int32), ("dyn_lo", C.c_float * 4), ("dyn_hi", C.c_float * 4),
+        ("wind", C.c_int32), ("wind_resample", C.c_int32),
+        ("speed", C.c_float * 2), ("azimuth", C.c_float * 2), ("vertical", C.c_float * 2), ("gust_sigma", C.c_float * 2),
+        ("gust_tau", C.c_float), ("coeff", C.c_float * 2),
+    ]
+
+
+# numpy view of orc_dw_state[n]: the per-drone body scales (s_m, s_I, s_kf, s_km), steady wind and gust (x, y, z, 0)
+DW_DTYPE = np.dtype([("dyn", "f4", 4), ("wind_mean", "f4", 4), ("wind_gust", "f4", 4)], align=True)
+
+
 class OrcStepOut(C.Structure):
     _fields_ = [("obs", C.c_float * OBS_DIM), ("reward", C.c_double),
                 ("terminated", C.c_int32), ("truncated", C.c_int32), ("found_targets", C.c_int32)]
@@ -141,16 +155,22 @@ def lib():
     L.orc_vec_refresh_rpy.argtypes = [C.c_void_p, C.c_int64]
     L.orc_vec_reset.argtypes = [cfgp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
     L.orc_vec_step.argtypes = [cfgp, C.c_void_p, C.c_int64] + [C.c_void_p] * 10 + [C.c_int]
+    dwcp = C.POINTER(OrcDwConfig)
+    L.orc_bullet_step_dw.argtypes = [dp, dp, dp, dp, dp, C.c_double, dp, C.c_double, C.c_double, C.c_double, dp]
+    L.orc_env_step_dw.argtypes = [cfgp, dwcp, C.c_void_p, envp, fp, C.POINTER(OrcStepOut)]
+    L.orc_vec_reset_dw.argtypes = [cfgp, dwcp, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+    L.orc_vec_step_dw.argtypes = [cfgp, dwcp, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10 + [C.c_int]
     L.orc_gae.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     L.orc_philox4x32.argtypes = [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]
     L.orc_noise4.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, fp]
     L.orc_noise4_many.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, C.c_uint64, C.c_uint32, fp]
     L.orc_noise4_many.restype = None
-    for name in ("orc_sizeof_env", "orc_sizeof_config", "orc_max_threads"):
+    for name in ("orc_sizeof_env", "orc_sizeof_config", "orc_max_threads", "orc_sizeof_dw_config", "orc_sizeof_dw_state"):
         getattr(L, name).restype = C.c_int32
     assert L.orc_sizeof_env() == C.sizeof(OrcEnv) == ENV_DTYPE.itemsize, \
         (L.orc_sizeof_env(), C.sizeof(OrcEnv), ENV_DTYPE.itemsize)
     assert L.orc_sizeof_config() == C.sizeof(OrcConfig)
+    assert L.orc_sizeof_dw_config() == C.sizeof(OrcDwConfig) and L.orc_sizeof_dw_state() == DW_DTYPE.itemsize
     _lib = L
     return L
 
@@ -183,6 +203,22 @@ def make_config(waypoints, spawn, dim, *, threshold=0.3, max_steps=4096, circle=
     return cfg
 
 
+def make_dw_config(dynamics=None, wind=None):
+    """orc_dw_config from a DynamicsRandomization-like object (mass / inertia / kf / km ranges, resample) and a WindDisturbance-like
+    one (speed / azimuth / vertical ranges, gust_sigma, gust_tau, coeff, resample); None = that feature off."""
+    c = OrcDwConfig()
+    if dynamics is not None:
+        c.dynamics, c.dyn_resample = 1, int(dynamics.resample)
+        for j, name in enumerate(("mass", "inertia", "kf", "km")):
+            c.dyn_lo[j], c.dyn_hi[j] = getattr(dynamics, name)
+    if wind is not None:
+        c.wind, c.wind_resample = 1, int(wind.resample)
+        for name in ("speed", "azimuth", "vertical", "gust_sigma", "coeff"):
+            getattr(c, name)[:] = getattr(wind, name)
+        c.gust_tau = wind.gust_tau
+    return c
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -190,17 +226,29 @@ def _p(a):
 class OracleVecEnv:
     """N oracle envs stepped the way SubprocVecEnv + Monitor + NormalizeObservation would."""
 
-    def __init__(self, cfg, num_envs, threads=1):
+    def __init__(self, cfg, num_envs, threads=1, dynamics=None, wind=None):
+        """dynamics / wind (optional): the per-drone body scales and wind of dn_enable_dynamics / dn_enable_wind, configured like
+        the package's DynamicsRandomization / WindDisturbance.  self.dw (DW_DTYPE [n]) holds their state -- scales of 1 and still
+        air until the first episode start draws, as after the first dn_enable_* -- and may be overwritten (teacher forcing)."""
         self.L = lib()
         self.cfg = cfg
         self.n = int(num_envs)
         self.threads = int(threads)
         self.envs = np.zeros(self.n, dtype=ENV_DTYPE)
         self.L.orc_vec_create(C.byref(cfg), _p(self.envs), self.n)
+        self.dw_cfg = None if dynamics is None and wind is None else make_dw_config(dynamics, wind)
+        self.dw = np.zeros(self.n, dtype=DW_DTYPE)
+        self.dw["dyn"] = 1.0
+
+    def _dw_args(self):
+        if self.dw_cfg is None:
+            return None, None
+        assert self.dw.dtype == DW_DTYPE and self.dw.flags.c_contiguous and len(self.dw) == self.n
+        return C.byref(self.dw_cfg), _p(self.dw)
 
     def reset(self):
         obs = np.empty((self.n, OBS_DIM), np.float32)
-        self.L.orc_vec_reset(C.byref(self.cfg), _p(self.envs), self.n, _p(obs), self.threads)
+        self.L.orc_vec_reset_dw(C.byref(self.cfg), *self._dw_args(), _p(self.envs), self.n, _p(obs), self.threads)
         return obs
 
     def refresh_rpy(self):
@@ -215,7 +263,7 @@ class OracleVecEnv:
             found_targets=np.empty(self.n, np.int32), terminal_obs=np.zeros((self.n, OBS_DIM), np.float32),
             ep_ret=np.zeros(self.n, np.float32), ep_len=np.zeros(self.n, np.int32),
             terminated=np.empty(self.n, np.uint8))
-        self.L.orc_vec_step(C.byref(self.cfg), _p(self.envs), self.n, _p(a), _p(out["obs"]), _p(out["reward"]),
+        self.L.orc_vec_step_dw(C.byref(self.cfg), *self._dw_args(), _p(self.envs), self.n, _p(a), _p(out["obs"]), _p(out["reward"]),
                             _p(out["done"]), _p(out["truncated"]), _p(out["found_targets"]),
                             _p(out["terminal_obs"]), _p(out["ep_ret"]), _p(out["ep_len"]), _p(out["terminated"]),
                             self.threads)
