@@ -11,10 +11,11 @@ from ._capi import DroneNavError, DroneNavLibraryError  # noqa: F401
 from .tracks import Track  # noqa: F401
 from .dynamics import DynamicsRandomization  # noqa: F401
 from .wind import WindDisturbance  # noqa: F401
+from .actuator import ActuatorModel  # noqa: F401
 
 __all__ = ["DroneVecEnv", "Track", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
            "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor",
-           "DynamicsRandomization", "WindDisturbance"]
+           "DynamicsRandomization", "WindDisturbance", "ActuatorModel"]
 
 
 def __getattr__(name):

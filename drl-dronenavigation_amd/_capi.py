@@ -76,6 +76,11 @@ class DnWindConfig(C.Structure):
                 ("gust_tau", C.c_float), ("coeff", C.c_float * 2), ("resample", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DnActuatorConfig(C.Structure):
+    _fields_ = [("latency", C.c_int32 * 2), ("motor_tau", C.c_float * 2), ("fill", C.c_float * 4), ("resample", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # every entry point declared in include/dronenav.h: name -> (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 PROTOTYPES = {
@@ -123,6 +128,10 @@ PROTOTYPES = {
     "dn_set_wind": (_I32, [_VP, _VP, _VP, _VP]),
     "dn_get_wind": (_I32, [_VP, _VP, _VP, _VP]),
     "dn_get_wind_config": (_I32, [_VP, C.POINTER(DnWindConfig)]),
+    "dn_enable_actuator": (_I32, [_VP, C.POINTER(DnActuatorConfig)]),
+    "dn_set_actuator": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "dn_get_actuator": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "dn_get_actuator_config": (_I32, [_VP, C.POINTER(DnActuatorConfig)]),
 }
 
 _lib = None

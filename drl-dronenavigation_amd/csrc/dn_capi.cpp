@@ -96,6 +96,8 @@ struct dn_env {
     dn_dynamics_config dyn_cfg = {};
     DnWind wind = {};           // dn_enable_wind: wind.mean / wind.gust are one allocation of its own (2 float4 per drone, outside the arena)
     dn_wind_config wind_cfg = {};
+    DnAct act = {};             // dn_enable_actuator: act.hist / rpm / coeff / lat are one allocation of its own (152 bytes per drone, outside the arena)
+    dn_actuator_config act_cfg = {};
 };
 
 thread_local hipEvent_t dn_tl_ev_start = nullptr, dn_tl_ev_stop = nullptr;
@@ -546,7 +548,7 @@ int32_t dn_destroy(dn_env *env)
 {
     if (!env) return DN_OK;
     hipError_t he = hipSuccess;
-    if (env->arena || env->dyn.dyn || env->wind.mean) (void)hipSetDevice(env->cfg.device_id);
+    if (env->arena || env->dyn.dyn || env->wind.mean || env->act.hist) (void)hipSetDevice(env->cfg.device_id);
     if (env->arena) he = hipFree(env->arena);
     if (env->dyn.dyn) {
         const hipError_t hd = hipFree(env->dyn.dyn);
@@ -555,6 +557,10 @@ int32_t dn_destroy(dn_env *env)
     if (env->wind.mean) {
         const hipError_t hw = hipFree(env->wind.mean);
         if (he == hipSuccess) he = hw;
+    }
+    if (env->act.hist) {
+        const hipError_t ha = hipFree(env->act.hist);
+        if (he == hipSuccess) he = ha;
     }
     delete env;
     if (he != hipSuccess) return fail(DN_ERR_HIP, "hipFree failed: %s", hipGetErrorString(he));
@@ -590,7 +596,7 @@ int32_t dn_reset(dn_env *env, float *obs, void *stream)
 {
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     if (!obs) return fail(DN_ERR_INVALID_ARGUMENT, "obs is NULL");
-    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn, &env->wind));
+    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn, &env->wind, &env->act));
     return DN_OK;
 }
 
@@ -610,7 +616,7 @@ int32_t dn_step(dn_env *env, const float *actions, float *obs, float *reward, ui
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn, &env->wind));
+    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn, &env->wind, &env->act));
     return DN_OK;
 }
 
@@ -632,6 +638,8 @@ int32_t dn_step_sampled(dn_env *env, const float *mean, const float *log_std, ui
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_policy_sample + dn_step there");
     if (env->wind.mean)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the wind (dn_enable_wind); use dn_policy_sample + dn_step there");
+    if (env->act.hist)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the actuator model (dn_enable_actuator); use dn_policy_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -662,6 +670,8 @@ int32_t dn_step_squashed(dn_env *env, const float *mu_log_std, uint64_t seed, in
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the randomised dynamics (dn_enable_dynamics); use dn_squashed_sample + dn_step there");
     if (env->wind.mean)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the wind (dn_enable_wind); use dn_squashed_sample + dn_step there");
+    if (env->act.hist)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the actuator model (dn_enable_actuator); use dn_squashed_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -691,6 +701,8 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_mlp_forward + dn_policy_sample + dn_step");
     if (env->wind.mean)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the wind (dn_enable_wind); use dn_mlp_forward + dn_policy_sample + dn_step");
+    if (env->act.hist)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the actuator model (dn_enable_actuator); use dn_mlp_forward + dn_policy_sample + dn_step");
     const dn_config &c = env->cfg;
     for (int k = 0; k < num_nets; ++k) {
         const dn_mlp_net &n = nets[k];
@@ -753,6 +765,8 @@ int32_t dn_eval_kinematics(dn_env *env, const double *kinematics, float *obs, fl
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given nominal-body transition: refused with the randomised dynamics (dn_enable_dynamics)");
     if (env->wind.mean)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given still-air transition: refused with the wind (dn_enable_wind)");
+    if (env->act.hist)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given transition: refused with the actuator model (dn_enable_actuator)");
     DnStepIO io;
     memset(&io, 0, sizeof io);
     io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated; io.found_targets = found_targets;
@@ -785,7 +799,7 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
     DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn, &env->wind));
+    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn, &env->wind, &env->act));
     return DN_OK;
 }
 
@@ -1136,6 +1150,101 @@ int32_t dn_get_wind_config(const dn_env *env, dn_wind_config *out)
     if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
     if (!env->wind.mean) return 0;
     *out = env->wind_cfg;
+    return 1;
+}
+
+int32_t dn_enable_actuator(dn_env *env, const dn_actuator_config *cfg)
+{
+    if (!env || !cfg) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    if (cfg->latency[0] < 0 || cfg->latency[1] > DN_MAX_LATENCY || cfg->latency[0] > cfg->latency[1])
+        return fail(DN_ERR_INVALID_ARGUMENT, "actuator latency = [%d, %d]: need 0 <= lo <= hi <= %d", cfg->latency[0], cfg->latency[1], DN_MAX_LATENCY);
+    const float tlo = cfg->motor_tau[0], thi = cfg->motor_tau[1];
+    if (!std::isfinite(tlo) || !std::isfinite(thi) || !(tlo >= 0.0f) || !(tlo <= thi))
+        return fail(DN_ERR_INVALID_ARGUMENT, "actuator motor_tau = [%g, %g]: need finite 0 <= lo <= hi", (double)tlo, (double)thi);
+    for (int j = 0; j < 4; ++j)
+        if (!std::isfinite(cfg->fill[j])) return fail(DN_ERR_INVALID_ARGUMENT, "actuator fill[%d] = %g: need finite", j, (double)cfg->fill[j]);
+    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    const int lag_on = thi > 0.0f;
+    if (lag_on && env->cfg.action_type != 0)
+        return fail(DN_ERR_INVALID_ARGUMENT, "the motor lag (motor_tau != [0, 0]) is built for ActionType.THRUST (action_type 0, got %d); "
+                                             "the command latency works with every action type", env->cfg.action_type);
+    DN_HIP(hipSetDevice(env->cfg.device_id));
+    // rpm_fill: the speeds the device's own action chain gives for `fill` (dn_preprocess_action's kernel), not host arithmetic
+    float4 rpm_fill;
+    {
+        float *tmp = nullptr;
+        if (hipMalloc(&tmp, 8 * sizeof(float)) != hipSuccess) return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(32 bytes) for the actuator's fill failed");
+        float host[4];
+        const bool ok = hipMemcpy(tmp, cfg->fill, 4 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess
+                        && dn_launch_action_chain(tmp, 1, env->cfg.normalize_actions, tmp + 4, nullptr, nullptr, nullptr) == hipSuccess
+                        && hipMemcpy(host, tmp + 4, 4 * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(tmp);
+        if (!ok) return fail(DN_ERR_HIP, "evaluating the action chain for the actuator's fill failed");
+        rpm_fill = make_float4(host[0], host[1], host[2], host[3]);
+    }
+    const float4 fill = make_float4(cfg->fill[0], cfg->fill[1], cfg->fill[2], cfg->fill[3]);
+    if (!env->act.hist) {                   // first call: d = 0, a = 0, r = rpm_fill, the history holds `fill`
+        const long long n = env->cfg.num_envs;
+        const size_t bytes = (size_t)n * (9 * sizeof(float4) + sizeof(float) + sizeof(int));
+        float4 *d = nullptr;
+        const hipError_t he = hipMalloc(&d, bytes);
+        if (he != hipSuccess)
+            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the actuator failed: %s", bytes, hipGetErrorString(he));
+        if (dn_launch_fill4(d, fill, 8 * n, nullptr) != hipSuccess || dn_launch_fill4(d + 8 * n, rpm_fill, n, nullptr) != hipSuccess
+            || hipMemsetAsync(d + 9 * n, 0, (size_t)n * (sizeof(float) + sizeof(int)), nullptr) != hipSuccess
+            || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(d);
+            return fail(DN_ERR_HIP, "initialising the actuator failed");
+        }
+        env->act.hist = d;
+        env->act.rpm = d + 8 * n;
+        env->act.coeff = reinterpret_cast<float *>(d + 9 * n);
+        env->act.lat = reinterpret_cast<int *>(env->act.coeff + n);
+    }
+    DnAct &a = env->act;
+    a.fill = fill;
+    a.rpm_fill = rpm_fill;
+    a.tau[0] = tlo; a.tau[1] = thi;
+    a.lat_lo = cfg->latency[0]; a.lat_hi = cfg->latency[1];
+    a.resample = cfg->resample;
+    a.lag_on = lag_on;
+    env->act_cfg = *cfg;
+    env->waves_fused = env->waves_single = 1;     // the actuator lives in the one-wave option kernels only
+    return DN_OK;
+}
+
+int32_t dn_set_actuator(dn_env *env, const int32_t *latency, const float *coeff, const float *rpm, const float *history, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    if (!env->act.hist) return fail(DN_ERR_BAD_STATE, "the actuator is not enabled (dn_enable_actuator)");
+    const size_t n = (size_t)env->cfg.num_envs;
+    hipStream_t s = (hipStream_t)stream;
+    if (latency) DN_HIP(hipMemcpyAsync(env->act.lat, latency, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (coeff) DN_HIP(hipMemcpyAsync(env->act.coeff, coeff, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rpm) DN_HIP(hipMemcpyAsync(env->act.rpm, rpm, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (history) DN_HIP(hipMemcpyAsync(env->act.hist, history, n * 8 * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    return DN_OK;
+}
+
+int32_t dn_get_actuator(dn_env *env, int32_t *latency, float *coeff, float *rpm, float *history, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    if (!env->act.hist) return fail(DN_ERR_BAD_STATE, "the actuator is not enabled (dn_enable_actuator)");
+    const size_t n = (size_t)env->cfg.num_envs;
+    hipStream_t s = (hipStream_t)stream;
+    if (latency) DN_HIP(hipMemcpyAsync(latency, env->act.lat, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (coeff) DN_HIP(hipMemcpyAsync(coeff, env->act.coeff, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rpm) DN_HIP(hipMemcpyAsync(rpm, env->act.rpm, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (history) DN_HIP(hipMemcpyAsync(history, env->act.hist, n * 8 * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    return DN_OK;
+}
+
+int32_t dn_get_actuator_config(const dn_env *env, dn_actuator_config *out)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    if (!env->act.hist) return 0;
+    *out = env->act_cfg;
     return 1;
 }
 

@@ -142,6 +142,23 @@ struct DnWind {
     int gust_on;            // sigma != (0, 0): launch-uniform; 0 = no draws, g held between episode starts and 0 from each
 };
 
+// Per-drone actuator model (dn_enable_actuator): command latency (an integer number of control steps) and a first-order motor lag on the
+// rotor speeds.  Not a field of DnParams for the same reason as DnDyn; it travels behind DnDyn and DnWind in the last argument of the
+// one-wave step kernels instantiated with it (dn_step_many_1w_kernel<..., DYN = true, WIND = true, ACT = true>) and as the last argument
+// of the reset kernel.  The four arrays are one allocation, hist first.
+struct DnAct {
+    float4 *hist;           // [N][8] hist[8 i + j] = the action commanded j + 1 vector steps ago; nullptr = actuator not enabled
+    float4 *rpm;            // [N] effective rotor speeds r
+    float *coeff;           // [N] a = exp(-dt / tau)
+    int *lat;               // [N] latency d, control steps
+    float4 fill;            // the action a fresh episode's pipeline holds
+    float4 rpm_fill;        // the chain's speeds for `fill` (device-evaluated once by dn_enable_actuator): r at an episode start
+    float tau[2];           // range of the time-constant draw [lo, hi], s
+    int lat_lo, lat_hi;     // range of the latency draw
+    int resample;           // 1: draw d and a at every episode start; 0: keep what dn_set_actuator wrote
+    int lag_on;             // tau range != [0, 0]: launch-uniform; 0 = the filter is skipped (the nominal bits), coeff and rpm are not read
+};
+
 // dn_set_launch_events (ABI 8): the step kernel of the next dn_step / dn_step_many launch is dispatched with these two hipEvents attached to
 // its own dispatch packet (hipExtLaunchKernelGGL) -- they time the kernel itself, like a profiler's kernel trace, where a pair of
 // hipEventRecord around the call would also time the host's launch path and add two marker packets to the stream.  One shot: the
@@ -156,9 +173,11 @@ extern thread_local hipEvent_t dn_tl_ev_start, dn_tl_ev_stop;
 int dn_norm_exact_compiled_in();      // 1 in libdronenav_exact.so (-DDN_NORM_EXACT=1: the normaliser's float64 output stage), else 0
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream,
                                const DnDyn *dy = nullptr,     // dy->dyn != nullptr: the one-wave kernel with the scales, whatever `waves` says
-                               const DnWind *wd = nullptr);   // wd->mean != nullptr: the one-wave kernel with the wind (and dy's scales, if any)
+                               const DnWind *wd = nullptr,    // wd->mean != nullptr: the one-wave kernel with the wind (and dy's scales, if any)
+                               const DnAct *ac = nullptr);    // ac->hist != nullptr: the one-wave kernel with the actuator (and dy's / wd's, if any)
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);   // dn_kernels_mw.hip
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy = nullptr, const DnWind *wd = nullptr);
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy = nullptr, const DnWind *wd = nullptr,
+                           const DnAct *ac = nullptr);
 hipError_t dn_launch_eval_kinematics(const DnParams &p, const DnStepIO &io, const double *kin, bool f32, hipStream_t stream);
 hipError_t dn_launch_gae(const float *rewards, const float *values, const uint8_t *dones,
                          const float *last_values, const uint8_t *last_dones, long long T, long long N,

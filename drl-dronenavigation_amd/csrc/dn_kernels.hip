@@ -1033,9 +1033,24 @@ struct ThrustX {       // XOPT kernels: float64 carriers (ActionType.RPM works i
     double f[4];
     double zt;
 };
-template <bool NOISE>
+// dn_enable_actuator's motor lag: the four effective rotor speeds r (float32 state, in registers across a launch) follow the speeds c the
+// action chain commands as a first-order filter, r <- float32(a r + (1 - a) c) with a = exp(-dt / tau) per drone, evaluated in the compute
+// type R in this one nesting (two products, one sum; the build contracts nothing).  a = 0 gives 0 r + 1 c = c.
+struct ActLag {
+    float r[4];
+    float a;
+};
+template <typename R> DN_DEV float lag_step(const float a, const float r, const float c)
+{
+    const R ar = (R)a * (R)r;
+    const R bc = ((R)1 - (R)a) * (R)c;
+    return (float)(ar + bc);
+}
+// ACT (the one-wave kernels with dn_enable_actuator): lag_on (launch-uniform) = the motor lag is on, ActionType.THRUST only; *lag is
+// always the kernel's own register copy (a pointer that may be null would pin it to scratch)
+template <bool NOISE, bool ACT = false, typename R = double>
 DN_DEV ThrustX thrust_phase_x(const DnParams &p, unsigned long long gid, unsigned long long step_count, const float4 A, Extras &x,
-                              const PidCtx *pid = nullptr)
+                              const PidCtx *pid = nullptr, ActLag *lag = nullptr, const bool lag_on = false)
 {
     float a[4] = {A.x, A.y, A.z, A.w};
     if (NOISE && p.act_noise_sigma > 0.0f) add_act_noise(p, gid, step_count, a);
@@ -1079,11 +1094,30 @@ DN_DEV ThrustX thrust_phase_x(const DnParams &p, unsigned long long gid, unsigne
         t.zt = z + tq[3];
     } else {
         float tq[4];
+        bool lagged = false;
+        if constexpr (ACT) {
+            if (lag_on) {   // the literal chain gives the commanded speeds; forces and torques from the filtered ones (BaseAviary.py:776-780)
+                lagged = true;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float rpm;
-            t.f[j] = (double)rotor_force_from_action(a[j], p.normalize_actions != 0, tq[j], &rpm);
-            x.rpm[j] = (double)rpm;
+                for (int j = 0; j < 4; ++j) {
+                    float cmd_rpm, tq_cmd;
+                    (void)rotor_force_from_action(a[j], p.normalize_actions != 0, tq_cmd, &cmd_rpm);
+                    const float r = lag_step<R>(lag->a, lag->r[j], cmd_rpm);
+                    lag->r[j] = r;
+                    const float sq = r * r;
+                    t.f[j] = (double)(sq * KF32);
+                    tq[j] = sq * KM32;
+                    x.rpm[j] = (double)r;
+                }
+            }
+        }
+        if (!lagged) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float rpm;
+                t.f[j] = (double)rotor_force_from_action(a[j], p.normalize_actions != 0, tq[j], &rpm);
+                x.rpm[j] = (double)rpm;
+            }
         }
         t.zt = (double)z_torque32(tq);
     }
@@ -1437,6 +1471,33 @@ DN_DEV float4 wind_gust_step(const DnWind &w, const float4 g, const unsigned lon
     noise4<true>(seed, gid, step, 15u, z);
     const R a = (R)w.a, bxy = (R)w.b[0], bz = (R)w.b[1];
     return make_float4((float)(a * (R)g.x + bxy * (R)z[0]), (float)(a * (R)g.y + bxy * (R)z[1]), (float)(a * (R)g.z + bz * (R)z[2]), 0.0f);
+}
+
+// ---- per-drone actuator model (dn_enable_actuator) ------------------------------------------------------------------------
+// The latency d and the lag coefficient a of an episode: ONE Philox4x32-10 call on stream 17, keyed like dyn_draw, u_j = (r_j + 0.5) / 2^32
+// in float64: d = lo + floor((hi - lo + 1) u0) clamped to hi; tau = tau_lo + (tau_hi - tau_lo) u1, a = float32(exp(-dt / tau)), 0 for
+// tau = 0 (r_2, r_3 unused).  An episode start only: the libm exp is not on the per-step path.
+DN_DEV void act_draw(const DnAct &ac, const unsigned long long seed, const unsigned long long gid, const unsigned long long step, int &d,
+                     float &a)
+{
+    unsigned r[4];
+    philox4x32((unsigned)gid, (unsigned)(gid >> 32), (unsigned)step, 17u | ((unsigned)(step >> 32) << 8), (unsigned)seed,
+               (unsigned)(seed >> 32), r);
+    const double u0 = ((double)r[0] + 0.5) * (1.0 / 4294967296.0), u1 = ((double)r[1] + 0.5) * (1.0 / 4294967296.0);
+    const int dd = ac.lat_lo + (int)floor((double)(ac.lat_hi - ac.lat_lo + 1) * u0);
+    d = dd > ac.lat_hi ? ac.lat_hi : dd;
+    const double tau = (double)ac.tau[0] + ((double)ac.tau[1] - (double)ac.tau[0]) * u1;
+    a = tau > 0.0 ? (float)exp(-(1.0 / 240.0) / tau) : 0.0f;
+}
+// The action the chain consumes at step t of a launch (t = 0: its first step) for a drone with latency d whose episode step counter at
+// step entry is s: the command of d vector steps ago -- this launch's own actions where t >= d, else the history (hist[j] = commanded
+// j + 1 steps before the launch) -- or `fill` while the episode is younger than the pipeline is deep.  A per-lane gather.
+DN_DEV float4 act_consume(const DnAct &ac, const float4 *act, const long long n, const unsigned li, const long long i, const int t, const int d,
+                          const int s)
+{
+    if (s < d) return ac.fill;
+    if (t >= d) return (act + (long long)(t - d) * n)[li];
+    return ac.hist[8 * i + (d - t - 1)];
 }
 
 // DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
@@ -2103,17 +2164,17 @@ DN_DEV BlockState block_state(const DnState &st, long long tile_base)
 }
 
 // thrust + physics of one step; the XOPT kernels take the float64 carriers and the optional force terms (N4)
-template <typename R, bool NOISE, bool XOPT, bool DYN = false, bool WIND = false>
+template <typename R, bool NOISE, bool XOPT, bool DYN = false, bool WIND = false, bool ACT = false>
 DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long long sc, const float4 A, const float4 G0, const float4 G1,
                      const float4 G2, const float4 G3, const float4 G7, float4 &rpm_now, double *pid_st = nullptr,
-                     const DynK<R> *dk = nullptr, const WindF<R> *wf = nullptr)
+                     const DynK<R> *dk = nullptr, const WindF<R> *wf = nullptr, ActLag *lag = nullptr, const bool lag_on = false)
 {
     if (XOPT) {
         Extras x;
         x.last = G7;
         PidCtx cx;
         cx.G0 = G0; cx.G1 = G1; cx.G2 = G2; cx.st = pid_st;
-        const ThrustX th = thrust_phase_x<NOISE>(p, gid, sc, A, x, pid_st ? &cx : nullptr);
+        const ThrustX th = thrust_phase_x<NOISE, ACT, R>(p, gid, sc, A, x, pid_st ? &cx : nullptr, lag, lag_on);
         rpm_now = make_float4((float)x.rpm[0], (float)x.rpm[1], (float)x.rpm[2], (float)x.rpm[3]);
         return physics_phase<R, ThrustX, true, DYN, WIND>(th, G0, G1, G2, G3, p.max_steps, &x, dk, wf);
     }
@@ -2193,12 +2254,19 @@ template <> struct DynArg<false> {};
 struct WindArg : DnDyn {
     DnWind w;
 };
-template <bool DYN, bool WIND> struct StepArg { using type = DynArg<DYN>; };
-template <> struct StepArg<true, true> { using type = WindArg; };
-template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false>
+// ACT (with WIND, DYN and XOPT): the argument carries dn_enable_actuator's state as well (ActArg); the wind's pointers are null when the wind
+// is off (zero wind, no draws), as the scale pointer is without dynamics.
+struct ActArg : WindArg {
+    DnAct a;
+};
+template <bool DYN, bool WIND, bool ACT = false> struct StepArg { using type = DynArg<DYN>; };
+template <> struct StepArg<true, true, false> { using type = WindArg; };
+template <> struct StepArg<true, true, true> { using type = ActArg; };
+template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false, bool ACT = false>
 __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg,
-                                                                   const typename StepArg<DYN, WIND>::type dy)
+                                                                   const typename StepArg<DYN, WIND, ACT>::type dy)
 {
+    static_assert(!ACT || (WIND && DYN && XOPT && !SAMPLE), "the actuator rides on the option kernels with the body terms and the wind");
     const int k_steps = ONE ? 1 : k_arg;
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -2227,8 +2295,24 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     else if constexpr (DYN) S = dy.dyn[i];
     // dn_enable_wind: this drone's steady wind and gust, held in registers across the launch
     float4 WB = make_float4(0.0f, 0.0f, 0.0f, 0.0f), WG = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if constexpr (WIND) { WB = dy.w.mean[i]; WG = dy.w.gust[i]; }
+    bool wind_have = WIND;                              // ACT: the wind itself may be off (null pointers: zero wind, nothing drawn or stored)
+    if constexpr (ACT) wind_have = dy.w.mean != nullptr;
+    if constexpr (WIND) { if (wind_have) { WB = dy.w.mean[i]; WG = dy.w.gust[i]; } }
     bool wind_new = false;                              // an episode started inside the launch: new wbar (resample) and g
+    // dn_enable_actuator: this drone's latency, lag coefficient and effective rotor speeds, held in registers across the launch
+    int LAT = 0;
+    ActLag lag = {{0.0f, 0.0f, 0.0f, 0.0f}, 0.0f};
+    bool act_new = false;                               // an episode started inside the launch: r = rpm_fill, new d and a (resample)
+    if constexpr (ACT) {
+        LAT = dy.a.lat[i];
+        LAT = LAT < 0 ? 0 : (LAT > DN_MAX_LATENCY ? DN_MAX_LATENCY : LAT);      // dn_set_actuator does not validate: the history is 8 deep
+        if (dy.a.lag_on) {
+            const float4 r4 = dy.a.rpm[i];
+            lag.r[0] = r4.x; lag.r[1] = r4.y; lag.r[2] = r4.z; lag.r[3] = r4.w;
+            lag.a = dy.a.coeff[i];
+        }
+        A = act_consume(dy.a, act, p.n, li, i, 0, LAT, unpack_meta(G3.w).steps);
+    }
     stage_table<R>(p, s_tab);
     block_lds_barrier();
     const long long n = p.n, words = (p.n + 63) / 64;
@@ -2236,6 +2320,8 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     if (ONE) slot0 = p.st.stats[blockIdx.x];                               // single-step launch: the whole slot now (see flush_stats_preloaded)
     const unsigned long long sc0 = ONE ? slot0.step_count : p.st.stats[blockIdx.x].step_count;      // this tile's vector-step counter
     if (sampled) A = sample_action(io0, gid, sc0, i, active);
+    bool lag_on = false;                                // ACT with the motor lag on (launch-uniform); off = the nominal chain
+    if constexpr (ACT) lag_on = dy.a.lag_on != 0;
     const R wp0[3] = {s_tab[DN_T_WP], s_tab[DN_T_WP + 1], s_tab[DN_T_WP + 2]};   // waypoint 0: every reset measures against it
     StatAcc acc;
     Rms rms;
@@ -2252,15 +2338,16 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
 #pragma clang loop unroll(disable)
     for (int t = 0; t < k_steps; ++t) {
         // prefetch the next step's action while this step computes
-        const float4 A_next = sampled ? A : (act + (long long)(t + 1 < k_steps ? t + 1 : t) * n)[li];
+        float4 A_next = A;                                  // ACT: gathered below, once this step's episode ends are known
+        if constexpr (!ACT) A_next = sampled ? A : (act + (long long)(t + 1 < k_steps ? t + 1 : t) * n)[li];
         const StepOut out = block_out(io0, tile_base, (long long)t * n, (long long)t * words);
         const unsigned long long sc = sc0 + (unsigned long long)t;
         float4 rpm_now;
         const GateRow<R> row_e = load_gate_row<R>(s_tab, unpack_meta(G3.w).idx);
         WindF<R> wf;
         if constexpr (WIND) wf = wind_force<R>(dy.w, WB, WG);
-        Flight<R> fl = fly<R, NOISE, XOPT, DYN, WIND>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr, DYN ? &dk : nullptr,
-                                                      WIND ? &wf : nullptr);
+        Flight<R> fl = fly<R, NOISE, XOPT, DYN, WIND, ACT>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr,
+                                                           DYN ? &dk : nullptr, WIND ? &wf : nullptr, &lag, lag_on);
         const float4 G0e = G0, G3e = G3;
         const Verdict<R> v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc);
         if (XOPT && p.drag) G7 = (v.terminated || fl.truncated) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : rpm_now;   // BaseAviary.py:442,545
@@ -2272,10 +2359,22 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
                 }
             }
         }
+        if constexpr (ACT) {
+            const bool done = v.terminated || fl.truncated;
+            if (__ballot(done) != 0ull) {               // wave-uniform: the episode starts of this step
+                if (done) {
+                    if (dy.a.resample) act_draw(dy.a, p.seed, gid, sc, LAT, lag.a);
+                    lag.r[0] = dy.a.rpm_fill.x; lag.r[1] = dy.a.rpm_fill.y; lag.r[2] = dy.a.rpm_fill.z; lag.r[3] = dy.a.rpm_fill.w;
+                    act_new = true;
+                }
+            }
+            // the next step's command: G3 now carries the step counter that step enters with (0 where the episode has just restarted)
+            if (t + 1 < k_steps) A_next = act_consume(dy.a, act, n, li, i, t + 1, LAT, unpack_meta(G3.w).steps);
+        }
         if constexpr (WIND) {
             const bool done = v.terminated || fl.truncated;
             if (dy.w.gust_on) WG = wind_gust_step<R>(dy.w, WG, p.seed, gid, sc);      // launch-uniform; sigma = 0: no draws
-            if (__ballot(done) != 0ull) {               // wave-uniform: the episode starts of this step take the stationary draw instead
+            if (wind_have && __ballot(done) != 0ull) {  // wave-uniform: the episode starts of this step take the stationary draw instead
                 if (done) {
                     if (dy.w.resample) WB = wind_mean_draw(dy.w, p.seed, gid, sc);
                     WG = dy.w.gust_on ? wind_gust_draw(dy.w, p.seed, gid, sc) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -2303,6 +2402,16 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         if constexpr (WIND) {
             if (dy.w.gust_on || wind_new) dy.w.gust[i] = WG;
             if (wind_new && dy.w.resample) dy.w.mean[i] = WB;
+        }
+        if constexpr (ACT) {
+            if (dy.a.lag_on || act_new) dy.a.rpm[i] = make_float4(lag.r[0], lag.r[1], lag.r[2], lag.r[3]);
+            if (act_new && dy.a.resample) { dy.a.lat[i] = LAT; dy.a.coeff[i] = lag.a; }
+            // the history becomes the last 8 commands: the old one shifted by k_steps (descending: every source is read before it is
+            // written), then this launch's commands, newest first
+            float4 *h = dy.a.hist + 8 * i;
+            for (int j = DN_MAX_LATENCY - 1; j >= k_steps; --j) h[j] = h[j - k_steps];
+            const int fresh = k_steps < DN_MAX_LATENCY ? k_steps : DN_MAX_LATENCY;
+            for (int j = 0; j < fresh; ++j) h[j] = (act + (long long)(k_steps - 1 - j) * n)[li];
         }
     }
 }
@@ -3847,7 +3956,7 @@ __global__ __launch_bounds__(3 * DN_BLOCK) void dn_step_pqx_kernel(const DnParam
 // VecEnv.reset(): every drone goes through Monitor.reset / NormalizeObservation.reset / PBDroneEnv.reset.
 // =====================================================================================================
 template <typename R>
-__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd)
+__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd, const DnAct ac)
 {
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -3901,6 +4010,16 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
             const unsigned long long sc = p.st.stats[blockIdx.x].step_count;
             if (wd.resample) wd.mean[i] = wind_mean_draw(wd, p.seed, gid, sc);
             wd.gust[i] = wd.gust_on ? wind_gust_draw(wd, p.seed, gid, sc) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        if (ac.hist) {                                                                                            // ... and its actuator
+            ac.rpm[i] = ac.rpm_fill;
+            if (ac.resample) {
+                int d;
+                float a;
+                act_draw(ac, p.seed, gid, p.st.stats[blockIdx.x].step_count, d, a);
+                ac.lat[i] = d;
+                ac.coeff[i] = a;
+            }
         }
     }
     store_obs_tile(s_tile, obs + tile_base * DN_OBS_DIM, rows, lane, o);
@@ -4263,9 +4382,32 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 #endif
 #elif DN_TU == 1
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnDyn *dy,
-                               const DnWind *wd)
+                               const DnWind *wd, const DnAct *ac)
 {
     const bool norm = p.normalize_obs != 0;
+    if (ac && ac->hist) {                   // dn_enable_actuator: the one-wave option kernel with the actuator, the wind and the body terms
+        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the actuator (the C ABI refuses them first)
+        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
+        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
+        ActArg aa;
+        static_cast<DnDyn &>(aa) = dy ? *dy : DnDyn{};
+        aa.w = wd ? *wd : DnWind{};
+        aa.a = *ac;
+#define DN_LA(R, NORM, NOISE)                                                                                                       \
+        do {                                                                                                                        \
+            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, aa); \
+            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, aa);   \
+        } while (0)
+        if (f32) {
+            if (norm) { if (noise) DN_LA(float, true, true); else DN_LA(float, true, false); }
+            else { if (noise) DN_LA(float, false, true); else DN_LA(float, false, false); }
+        } else {
+            if (norm) { if (noise) DN_LA(double, true, true); else DN_LA(double, true, false); }
+            else { if (noise) DN_LA(double, false, true); else DN_LA(double, false, false); }
+        }
+#undef DN_LA
+        return hipGetLastError();
+    }
     if (wd && wd->mean) {                   // dn_enable_wind: the one-wave option kernel with the wind and the body terms (scales of 1 without dynamics)
         if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the wind (the C ABI refuses them first)
         const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
@@ -4375,13 +4517,14 @@ hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, boo
 #undef DN_LAUNCH3
 
 #if DN_TU == 1
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy, const DnWind *wd)
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy, const DnWind *wd, const DnAct *ac)
 {
+    const DnAct act = ac ? *ac : DnAct{};
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
     const DnDyn dyn = dy ? *dy : DnDyn{};
     const DnWind wnd = wd ? *wd : DnWind{};
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd);
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act);
     return hipGetLastError();
 }
 

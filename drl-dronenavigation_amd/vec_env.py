@@ -28,6 +28,7 @@ import torch
 from . import _capi
 from .dynamics import DynamicsRandomization
 from .wind import WindDisturbance
+from .actuator import ActuatorModel
 from .spaces import Box
 from .tracks import Track
 
@@ -171,11 +172,13 @@ class DroneVecEnv(_VecEnvBase):
                  include_distance=True, normalize_actions=True, normalize_obs=True, ground_contact=None,
                  compute_dtype="float64", act_noise_sigma=0.0, obs_noise_sigma=0.0, seed=0, env_id_offset=0,
                  device=None, info_mode="sparse", clip_rew=False, norm_rew=False, physics="pyb", act="thrust", random_spawn=False,
-                 zero_damping=False, fresh_arrays=True, dynamics=None, wind=None):
+                 zero_damping=False, fresh_arrays=True, dynamics=None, wind=None, actuator=None):
         if dynamics is not None and not isinstance(dynamics, DynamicsRandomization):
             raise TypeError("dynamics must be a drl_dronenavigation_amd.DynamicsRandomization (or None)")
         if wind is not None and not isinstance(wind, WindDisturbance):
             raise TypeError("wind must be a drl_dronenavigation_amd.WindDisturbance (or None)")
+        if actuator is not None and not isinstance(actuator, ActuatorModel):
+            raise TypeError("actuator must be a drl_dronenavigation_amd.ActuatorModel (or None)")
         if track is not None:
             if not isinstance(track, Track):
                 raise TypeError("track must be a drl_dronenavigation_amd.tracks.Track")
@@ -217,8 +220,9 @@ class DroneVecEnv(_VecEnvBase):
         self.ground_contact = bool(self.cfg.ground_contact)
         self.dynamics = dynamics
         self.wind = wind
-        # before the first reset: dn_reset draws the first episode's bodies and winds
-        for enable, feature in (("dn_enable_dynamics", dynamics), ("dn_enable_wind", wind)):
+        self.actuator = actuator
+        # before the first reset: dn_reset draws the first episode's bodies, winds and actuators
+        for enable, feature in (("dn_enable_dynamics", dynamics), ("dn_enable_wind", wind), ("dn_enable_actuator", actuator)):
             if feature is None:
                 continue
             rc = getattr(self._lib, enable)(self._handle, C.byref(feature.to_c()))
@@ -700,6 +704,67 @@ class DroneVecEnv(_VecEnvBase):
     def _require_wind(self):
         if self.wind is None:
             raise RuntimeError("wind is not enabled: construct the env with wind=WindDisturbance(...)")
+
+    # ------------------------------------------------------------------ actuator (dn_enable_actuator)
+    def get_actuator(self):
+        """Every drone's actuator state as a dict of tensors on the env's device: latency int32 [N] (control steps), coeff float32 [N]
+        (a = exp(-dt / tau)), rpm float32 [N, 4] (the effective rotor speeds) and history float32 [N, 8, 4] (history[i, j] = the action
+        commanded j + 1 vector steps ago).  With get_state() and step_count this is a checkpoint of a fleet with the actuator model."""
+        self._require_actuator()
+        n, dev, f32 = self.num_envs, self.device, torch.float32
+        out = {"latency": torch.empty((n,), dtype=torch.int32, device=dev), "coeff": torch.empty((n,), dtype=f32, device=dev),
+               "rpm": torch.empty((n, 4), dtype=f32, device=dev), "history": torch.empty((n, 8, 4), dtype=f32, device=dev)}
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.dn_get_actuator(self._handle, out["latency"].data_ptr(), out["coeff"].data_ptr(), out["rpm"].data_ptr(),
+                                                  out["history"].data_ptr(), self._stream()))
+        return out
+
+    def set_actuator(self, latency=None, coeff=None, rpm=None, history=None):
+        """Writes every drone's latency (int32 [N], 0..8), lag coefficient (float32 [N], 0 <= a < 1), rotor speeds (float32 [N, 4]) and /
+        or command history (float32 [N, 8, 4]); tensors on the env's device, None = leave.  With resample=False latency and coefficient
+        hold until the next set_actuator; otherwise until the drone's next episode start."""
+        self._require_actuator()
+        n = self.num_envs
+        spec = (("latency", latency, torch.int32, (n,)), ("coeff", coeff, torch.float32, (n,)), ("rpm", rpm, torch.float32, (n, 4)),
+                ("history", history, torch.float32, (n, 8, 4)))
+        rows = []
+        for name, x, dtype, shape in spec:
+            if x is None:
+                rows.append(None)
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise TypeError(f"{name} must be a torch.Tensor")
+            if x.dtype != dtype:
+                raise TypeError(f"{name} must be {dtype}, got {x.dtype}")
+            if x.device != self.device:
+                raise ValueError(f"{name} must live on {self.device}, got {x.device}")
+            if tuple(x.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {tuple(x.shape)}")
+            x = x.contiguous()
+            if name == "latency":
+                if not bool(((x >= 0) & (x <= 8)).all()):
+                    raise ValueError("every latency must lie in [0, 8]")
+            elif name == "coeff":
+                if not bool(((x >= 0) & (x < 1)).all()):
+                    raise ValueError("every coeff must lie in [0, 1)")
+            elif not bool(torch.isfinite(x).all()):
+                raise ValueError(f"every value of {name} must be finite")
+            rows.append(x)
+        ptr = [None if x is None else x.data_ptr() for x in rows]
+        with torch.cuda.device(self.device):
+            _capi.check(self._lib.dn_set_actuator(self._handle, ptr[0], ptr[1], ptr[2], ptr[3], self._stream()))
+
+    def actuator_config(self):
+        """The ActuatorModel in force (dn_get_actuator_config), or None when the feature is off."""
+        c = _capi.DnActuatorConfig()
+        rc = self._lib.dn_get_actuator_config(self._handle, C.byref(c))
+        if rc < 0:
+            _capi.check(rc)
+        return ActuatorModel.from_c(c) if rc == 1 else None
+
+    def _require_actuator(self):
+        if self.actuator is None:
+            raise RuntimeError("the actuator model is not enabled: construct the env with actuator=ActuatorModel(...)")
 
     def stats(self):
         s = _capi.DnStats()

@@ -38,6 +38,7 @@ extern "C" {
 #define DN_MAX_WAYPOINTS 64
 #define DN_OBS_DIM 13      /* 12 kinematic + distance, PBDroneEnv._computeObs, PBDroneEnv.py:296-336 */
 #define DN_ACT_DIM 4       /* four rotor thrust commands, PBDroneEnv._actionSpace, PBDroneEnv.py:225-243 */
+#define DN_MAX_LATENCY 8   /* deepest command pipeline of dn_enable_actuator, control steps (33 ms) */
 #define DN_GROUND_CONTACT_AUTO 2   /* dn_config.ground_contact: resolved by dn_create (see the field) */
 
 typedef enum dn_status {
@@ -103,7 +104,8 @@ typedef struct dn_config {
 /* One drone's persistent state, host-side AoS view used by dn_get_state/dn_set_state (tests,
  * checkpointing).  Field names follow the reference's attributes.  It does not carry the body scales of
  * dn_enable_dynamics: a checkpoint of a randomised fleet is dn_get_state + dn_get_dynamics (restore: dn_set_state + dn_set_dynamics),
- * nor the wind of dn_enable_wind (+ dn_get_wind / dn_set_wind). */
+ * nor the wind of dn_enable_wind (+ dn_get_wind / dn_set_wind), nor the actuator state of dn_enable_actuator (+ dn_get_actuator /
+ * dn_set_actuator). */
 typedef struct dn_env_state {
     float pos[3], quat[4], vel[3], ang_v[3];    /* Bullet base state, BaseAviary.py:596-598 (quat = x,y,z,w) */
     float prev_vel[3], prev_ang_v[3];           /* PBDroneEnv.prev_vel / prev_ang_v */
@@ -389,7 +391,8 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
 int32_t dn_set_launch_events(dn_env *env, void *start_event, void *stop_event);
 
 /* Bytes of HBM the persistent state of `num_envs` drones occupies (capacity planning).  The body scales of dn_enable_dynamics are a
- * separate allocation of 16 bytes per drone and are not included, nor is the wind of dn_enable_wind (32 bytes per drone). */
+ * separate allocation of 16 bytes per drone and are not included, nor is the wind of dn_enable_wind (32 bytes per drone), nor the
+ * actuator state of dn_enable_actuator (152 bytes per drone). */
 int64_t dn_state_bytes(int64_t num_envs, int32_t normalize_obs);
 
 /* Per-drone dynamics randomisation (sim-to-real).  Each drone carries four float32 scale factors relative to the nominal cf2x body:
@@ -462,6 +465,52 @@ int32_t dn_set_wind(dn_env *env, const float *mean, const float *gust, void *str
 int32_t dn_get_wind(dn_env *env, float *mean, float *gust, void *stream);
 /* 1: wind enabled, *out = the configuration last given to dn_enable_wind; 0: not enabled (*out untouched); < 0: error. */
 int32_t dn_get_wind_config(const dn_env *env, dn_wind_config *out);
+
+/* Per-drone actuator model (sim-to-real): command latency and motor lag between the action handed to dn_step and the rotors.
+ *   latency: every drone has an integer latency d in [0, DN_MAX_LATENCY] control steps.  At a control step which the drone enters with
+ *            episode step counter s (dn_env_state.steps), the action chain consumes the action commanded d vector steps ago if s >= d, and
+ *            `fill` otherwise: the pipeline of a fresh episode holds no command of that episode yet, and commands of the previous episode
+ *            never leak into the next one.  The rule is stateless apart from a per-drone history of the last 8 commanded actions (128
+ *            bytes), so dn_set_state needs no special case.  Action noise (act_noise_sigma) is drawn and added when a command is CONSUMED,
+ *            keyed by the vector step of consumption: an env with latency equals, bit for bit, the same env without latency fed the
+ *            shifted actions.  Works with every action_type.  The buffers of dn_step keep holding the COMMANDED action.
+ *   lag:     each drone carries four effective rotor speeds r (float32) and a coefficient a = exp(-dt / tau) (float32, dt = 1/240; tau = 0
+ *            gives a = 0).  After the nominal action chain has produced the commanded speeds c (float32, pwm2rpm),
+ *            r <- float32(a r + (1 - a) c), evaluated in the compute type (compute_f32) in exactly this nesting, unfused; the rotor forces
+ *            KF r^2 and the yaw torque from KM r^2 are formed from r in float32 as BaseAviary._physics forms them from c, and everything
+ *            downstream (ground effect, PYB_DRAG's last_rpm, s_kf, s_km) sees r.  a = 0 reproduces c exactly.  An episode start sets
+ *            r = rpm_fill, the chain's speeds for `fill`, evaluated once by dn_enable_actuator on the device (the dn_preprocess_action
+ *            path).  motor_tau = [0, 0] switches the filter off: the nominal bits, `coeff` is not read and `rpm` only changes at episode
+ *            starts.  Any other range needs ActionType.THRUST (DN_ERR_INVALID_ARGUMENT otherwise; latency stays available).
+ *   draws:   resample = 1: every episode start (dn_reset and every in-kernel auto-reset) draws from ONE Philox4x32-10 call keyed (seed;
+ *            global drone id, the vector step the episode starts on, stream 17) with u_j = (r_j + 0.5) / 2^32 in float64:
+ *            d = latency lo + floor((hi - lo + 1) u_0) clamped to hi; tau = tau lo + (tau hi - tau lo) u_1, a = float32(exp(-dt / tau))
+ *            (the device library's exp, at episode starts only), a = 0 where tau = 0.  Sharding does not move the draws, and a hipGraph
+ *            replay keeps drawing fresh ones.  resample = 0: d and a are what dn_set_actuator last wrote (0 and 0 after the first enable).
+ * New values act from the first step of the new episode; the terminal step and the reset observation do not depend on them.  r, a, d and
+ * the history are held in registers / gathered per lane across a fused launch and stored at its end: K steps in one launch equal K
+ * single steps bit for bit.  A checkpoint is dn_get_state + dn_get_actuator + dn_get_step_count.
+ * The actuator lives in the one-wave option kernels: enabling forces dn_get_kernel_waves(env, 0 / 1) == 1.  dn_step_sampled,
+ * dn_step_squashed, dn_mlp_step_sampled and dn_eval_kinematics refuse an env with the actuator enabled (DN_ERR_INVALID_ARGUMENT). */
+typedef struct dn_actuator_config {
+    int32_t latency[2];   /* latency range [lo, hi], control steps: 0 <= lo <= hi <= DN_MAX_LATENCY */
+    float motor_tau[2];   /* motor time constant range [lo, hi], s: finite, 0 <= lo <= hi; [0, 0] = no lag */
+    float fill[4];        /* the action a fresh episode's pipeline holds: finite */
+    int32_t resample;     /* 1: draw d and a at every episode start; 0: keep dn_set_actuator's */
+    int32_t reserved;     /* must be 0 */
+} dn_actuator_config;
+/* Validates the configuration and enables the feature.  The first call allocates 152 bytes per drone (outside dn_state_bytes) and sets
+ * d = 0, a = 0, r = rpm_fill and every history entry to `fill`; a later call changes the configuration (rpm_fill included) and keeps the
+ * current values.  Synchronises the device. */
+int32_t dn_enable_actuator(dn_env *env, const dn_actuator_config *cfg);
+/* Device buffers, copied on `stream`; NULL = leave (set) / skip (get): latency int32[N] (d), coeff float[N] (a), rpm float[N][4] (r),
+ * history float[N][8][4] with history[i][j] = the action drone i was commanded j + 1 vector steps ago.  DN_ERR_BAD_STATE if the actuator
+ * is not enabled.  dn_set_actuator does not validate the values (the caller's device buffers are not read on the host): d must lie in
+ * [0, DN_MAX_LATENCY] (the kernels clamp it), a in [0, 1), every other value finite. */
+int32_t dn_set_actuator(dn_env *env, const int32_t *latency, const float *coeff, const float *rpm, const float *history, void *stream);
+int32_t dn_get_actuator(dn_env *env, int32_t *latency, float *coeff, float *rpm, float *history, void *stream);
+/* 1: actuator enabled, *out = the configuration last given to dn_enable_actuator; 0: not enabled (*out untouched); < 0: error. */
+int32_t dn_get_actuator_config(const dn_env *env, dn_actuator_config *out);
 
 #ifdef __cplusplus
 }

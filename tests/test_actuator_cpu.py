@@ -1,0 +1,84 @@
+"""Per-drone actuator model (include/dronenav.h dn_enable_actuator) without a GPU: the C struct against its ctypes twin, the exported
+symbols, and the host-side validation of ActuatorModel."""
+import ctypes as C
+import dataclasses
+import os
+import subprocess
+import tempfile
+
+import pytest
+
+NEW_SYMBOLS = ("dn_enable_actuator", "dn_set_actuator", "dn_get_actuator", "dn_get_actuator_config")
+FIELDS = ("latency", "motor_tau", "fill", "resample", "reserved")
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import drl_dronenavigation_amd as p
+    return p
+
+
+def test_actuator_config_layout_matches_header(pkg):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    offs = ", ".join(f"offsetof(dn_actuator_config, {f})" for f in FIELDS)
+    prog = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "dronenav.h"
+int main(void) {
+    printf("%zu %zu %zu %zu %zu %zu %d %d %zu %zu\n", sizeof(dn_actuator_config), ''' + offs + r''', DN_ABI_VERSION, DN_MAX_LATENCY,
+           sizeof(dn_config), sizeof(dn_env_state));
+    return 0;
+}
+'''
+    with tempfile.TemporaryDirectory() as td:
+        src, exe = os.path.join(td, "act.c"), os.path.join(td, "act")
+        with open(src, "w") as f:
+            f.write(prog)
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), src, "-o", exe])
+        got = [int(v) for v in subprocess.check_output([exe]).split()]
+    A = pkg._capi.DnActuatorConfig
+    from drl_dronenavigation_amd import actuator
+    assert got == [C.sizeof(A)] + [getattr(A, f).offset for f in FIELDS] + [pkg._capi.ABI_VERSION, actuator.MAX_LATENCY,
+                                                                           C.sizeof(pkg._capi.DnConfig), C.sizeof(pkg._capi.DnEnvState)], got
+    assert C.sizeof(A) == 40 and pkg._capi.ABI_VERSION == 9 and actuator.MAX_LATENCY == 8      # additive: the ABI version stays
+
+
+def test_actuator_symbols_are_exported_and_bound(pkg):
+    lib = pkg._capi.load()
+    for name in NEW_SYMBOLS:
+        assert name in pkg._capi.PROTOTYPES, name
+        assert getattr(lib, name).argtypes == pkg._capi.PROTOTYPES[name][1], name
+    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg._capi.library_path()]).decode()
+    for name in NEW_SYMBOLS:
+        assert f" T {name}\n" in out, name
+
+
+NAN, INF = float("nan"), float("inf")
+
+
+@pytest.mark.parametrize("bad", [
+    dict(latency=(-1, 2)), dict(latency=(0, 9)), dict(latency=(9, 9)), dict(latency=(5, 3)),              # negative, > 8, lo > hi
+    dict(latency=(0.5, 2)), dict(latency=(0,)), dict(latency=3), dict(latency=(0, 1, 2)), dict(latency=(NAN, 2)),
+    dict(motor_tau=(-0.01, 0.1)), dict(motor_tau=(0.2, 0.1)), dict(motor_tau=(0.0, -0.1)),                # negative, lo > hi
+    dict(motor_tau=(NAN, 0.1)), dict(motor_tau=(0.0, INF)), dict(motor_tau=0.1), dict(motor_tau=(0.1,)),  # non-finite, arity
+    dict(fill=(0, 0, 0, NAN)), dict(fill=(INF, 0, 0, 0)), dict(fill=(0, 0, 0)), dict(fill=0.0), dict(fill=(0, 0, 0, 0, 0)),
+])
+def test_actuator_model_rejects_bad_values(pkg, bad):
+    with pytest.raises(ValueError):
+        pkg.ActuatorModel(**bad)
+
+
+def test_actuator_model_defaults_and_c_image(pkg):
+    a = pkg.ActuatorModel()
+    assert (a.latency, a.motor_tau, a.fill, a.resample) == ((0, 0), (0.0, 0.0), (0.0, 0.0, 0.0, 0.0), True)
+    d = pkg.ActuatorModel(latency=(1, 8), motor_tau=(0.02, 0.15), fill=(0.1, -0.2, 0.3, 0.0922), resample=False)
+    c = d.to_c()
+    assert list(c.latency) == [1, 8] and list(c.motor_tau) == pytest.approx([0.02, 0.15]) and list(c.fill) == pytest.approx([0.1, -0.2, 0.3, 0.0922])
+    assert c.resample == 0 and c.reserved == 0
+    back = pkg.ActuatorModel.from_c(c)
+    assert bytes(back.to_c()) == bytes(c)
+    assert back.latency == (1, 8) and back.resample is False
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        d.latency = (0, 0)
+    assert "ActuatorModel" in pkg.__all__
