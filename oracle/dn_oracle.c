@@ -757,6 +757,22 @@ void orc_env_step(const orc_config *c, orc_env *e, const float action[4], orc_st
 void orc_env_step_dw(const orc_config *c, const orc_dw_config *dwc, const orc_dw_state *s, orc_env *e, const float action[4],
                      orc_step_out *out)
 {
+    orc_env_step_act(c, dwc, s, NULL, NULL, e, action, out);
+}
+
+/* ... and with the motor lag of dn_enable_actuator (dronenav.h): `action` is the CONSUMED action (latency and action noise are the vec
+ * step's business).  ActionType.THRUST with a motor_tau range other than [0, 0]: the nominal float32 chain gives the commanded speeds
+ * c, r <- float32(a r + (1 - a) c) in float64 in that nesting, and forces, yaw torque, ground effect and last_clipped_action are
+ * formed from r exactly as the chain forms them from c.  Otherwise the nominal path; as->rpm is not touched. */
+static int act_lag_on(const orc_config *c, const orc_act_config *actc)
+{
+    return actc && actc->on && c->action_type == 0 && (actc->motor_tau[0] > 0.0f || actc->motor_tau[1] > 0.0f);
+}
+
+void orc_env_step_act(const orc_config *c, const orc_dw_config *dwc, const orc_dw_state *s, const orc_act_config *actc,
+                      orc_act_state *as, orc_env *e, const float action[4], orc_step_out *out)
+{
+    const int lag = as && act_lag_on(c, actc);
     const int dyn = dwc && s && dwc->dynamics, wind = dwc && s && dwc->wind;
     double fw[3] = {0.0, 0.0, 0.0};
     if (wind) {
@@ -785,6 +801,15 @@ void orc_env_step_dw(const orc_config *c, const orc_dw_config *dwc, const orc_dw
         zt = zt + tq[3];
     } else {
         orc_preprocess_action(cmd, rpm32);                                   /* BaseAviary.py:408 */
+        if (lag) {                                                           /* the rotors follow the command: rpm32 becomes r */
+            const double a = (double)as->coeff;
+            for (int i = 0; i < 4; ++i) {
+                double kept = a * (double)as->rpm[i];
+                double gained = (1.0 - a) * (double)rpm32[i];
+                as->rpm[i] = (float)(kept + gained);
+                rpm32[i] = as->rpm[i];
+            }
+        }
         orc_rotor_forces(rpm32, f32, &zt32);                                 /* :420-421 */
         for (int i = 0; i < 4; ++i) { rpm[i] = rpm32[i]; f[i] = f32[i]; }
         zt = (double)zt32;
@@ -1011,6 +1036,62 @@ static void dw_gust_step(const orc_config *c, const orc_dw_config *w, orc_dw_sta
     for (int j = 0; j < 3; ++j) s->wind_gust[j] = (float)(a * (double)s->wind_gust[j] + b[j] * (double)z[j]);
 }
 
+/* The actuator of dn_enable_actuator (dronenav.h).  rpm_fill: the nominal chain's speeds for `fill`, rescaled first when the env
+ * normalises its actions (what the chain does to any action), no noise. */
+void orc_act_rpm_fill(const orc_config *c, orc_act_config *actc)
+{
+    float cmd[4];
+    if (c->normalize_actions) orc_rescale_action(actc->fill, cmd);
+    else memcpy(cmd, actc->fill, sizeof cmd);
+    orc_preprocess_action(cmd, actc->rpm_fill);
+}
+
+/* The state after the first dn_enable_actuator: d = 0, a = 0, r = rpm_fill, every history entry = fill. */
+void orc_act_init(const orc_act_config *actc, orc_act_state *acts, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        acts[i].latency = 0;
+        acts[i].coeff = 0.0f;
+        memcpy(acts[i].rpm, actc->rpm_fill, sizeof actc->rpm_fill);
+        for (int j = 0; j < ORC_MAX_LATENCY; ++j) memcpy(acts[i].history[j], actc->fill, sizeof actc->fill);
+    }
+}
+
+/* Episode start of drone gid at vector step `step`: r = rpm_fill; with resample, ONE Philox call on stream 17 gives
+ * d = lo + floor((hi - lo + 1) u_0) clamped to hi and tau = tau lo + (tau hi - tau lo) u_1, a = float32(exp(-dt / tau)), 0 where tau = 0.
+ * The history stays: the rule "s >= d, else fill" keeps the previous episode's commands out. */
+static void act_episode_start(const orc_config *c, const orc_act_config *actc, orc_act_state *as, uint64_t gid, uint64_t step)
+{
+    memcpy(as->rpm, actc->rpm_fill, sizeof as->rpm);
+    if (!actc->resample) return;
+    uint32_t r[4];
+    orc_philox4x32((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)step, ctr3(17u, step), (uint32_t)c->seed,
+                   (uint32_t)(c->seed >> 32), r);
+    const double u0 = ((double)r[0] + 0.5) * (1.0 / 4294967296.0), u1 = ((double)r[1] + 0.5) * (1.0 / 4294967296.0);
+    const int32_t lo = actc->latency[0], hi = actc->latency[1];
+    int32_t d = lo + (int32_t)floor((double)(hi - lo + 1) * u0);
+    as->latency = d > hi ? hi : d;
+    const double tau = (double)actc->motor_tau[0] + ((double)actc->motor_tau[1] - (double)actc->motor_tau[0]) * u1;
+    as->coeff = tau > 0.0 ? (float)exp(-ORC_DT / tau) : 0.0f;
+}
+
+/* What the chain consumes at a step entered with episode step counter s: the action commanded d vector steps ago if s >= d (d = 0:
+ * the action commanded now), `fill` otherwise.  history[j] = commanded j + 1 vector steps ago. */
+static void act_consume(const orc_act_config *actc, const orc_act_state *as, int32_t s, const float commanded[4], float out[4])
+{
+    int32_t d = as->latency;
+    if (d < 0) d = 0;
+    if (d > ORC_MAX_LATENCY) d = ORC_MAX_LATENCY;
+    const float *src = d == 0 ? commanded : (s >= d ? as->history[d - 1] : actc->fill);
+    memcpy(out, src, 4 * sizeof(float));
+}
+
+static void act_push(orc_act_state *as, const float commanded[4])
+{
+    memmove(as->history[1], as->history[0], (ORC_MAX_LATENCY - 1) * sizeof as->history[0]);
+    memcpy(as->history[0], commanded, sizeof as->history[0]);
+}
+
 void orc_vec_reset(const orc_config *c, orc_env *envs, int64_t n, float *obs, int threads)
 {
     orc_vec_reset_dw(c, NULL, NULL, envs, n, obs, threads);
@@ -1019,6 +1100,13 @@ void orc_vec_reset(const orc_config *c, orc_env *envs, int64_t n, float *obs, in
 void orc_vec_reset_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, orc_env *envs, int64_t n, float *obs,
                       int threads)
 {
+    orc_vec_reset_act(c, dwc, dws, NULL, NULL, envs, n, obs, threads);
+}
+
+void orc_vec_reset_act(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                       orc_act_state *acts, orc_env *envs, int64_t n, float *obs, int threads)
+{
+    const int act = actc && acts && actc->on;
     (void)threads;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
@@ -1028,6 +1116,7 @@ void orc_vec_reset_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_stat
         orc_env_reset(c, e, &obs[i * ORC_OBS_DIM]);
         finish_obs(c, e, (uint64_t)(c->env_id_offset + i), 5u, &obs[i * ORC_OBS_DIM]);
         if (dwc && dws) dw_episode_start(c, dwc, &dws[i], (uint64_t)(c->env_id_offset + i), e->step_count);
+        if (act) act_episode_start(c, actc, &acts[i], (uint64_t)(c->env_id_offset + i), e->step_count);
         e->ep_ret = 0.0; e->ep_len = 0;          /* Monitor.reset */
         if (c->f32_state) round_state_f32(e);
     }
@@ -1045,6 +1134,19 @@ void orc_vec_step_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_state
                      const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets,
                      float *terminal_obs, float *ep_ret, int32_t *ep_len, uint8_t *terminated, int threads)
 {
+    orc_vec_step_act(c, dwc, dws, NULL, NULL, envs, n, actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_ret,
+                     ep_len, terminated, threads);
+}
+
+/* With the actuator: the chain consumes the delayed action (act_consume) with the action noise of THIS vector step added to it, the
+ * filter runs on its speeds (orc_env_step_act), the history takes the COMMANDED action after the step, and an episode that ends
+ * starts the next one with r = rpm_fill and (resample) a new (d, a), keyed by this step like the body and the wind. */
+void orc_vec_step_act(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                      orc_act_state *acts, orc_env *envs, int64_t n, const float *actions, float *obs, float *reward, uint8_t *done,
+                      uint8_t *truncated, int32_t *found_targets, float *terminal_obs, float *ep_ret, int32_t *ep_len,
+                      uint8_t *terminated, int threads)
+{
+    const int act = actc && acts && actc->on;
     (void)threads;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
@@ -1052,7 +1154,11 @@ void orc_vec_step_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_state
     for (int64_t i = 0; i < n; ++i) {
         orc_env *e = &envs[i];
         uint64_t gid = (uint64_t)(c->env_id_offset + i);
-        float a[4] = {actions[4 * i], actions[4 * i + 1], actions[4 * i + 2], actions[4 * i + 3]};
+        const float commanded[4] = {actions[4 * i], actions[4 * i + 1], actions[4 * i + 2], actions[4 * i + 3]};
+        orc_act_state *as = act ? &acts[i] : NULL;
+        float a[4];
+        if (as) act_consume(actc, as, e->steps, commanded, a);
+        else memcpy(a, commanded, sizeof a);
         if (c->act_noise_sigma > 0.0f) {
             float z[4];
             orc_noise4(c->seed, gid, e->step_count, 0u, z);
@@ -1063,7 +1169,8 @@ void orc_vec_step_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_state
         }
         orc_step_out so;
         orc_dw_state *s = (dwc && dws) ? &dws[i] : NULL;
-        orc_env_step_dw(c, dwc, s, e, a, &so);
+        orc_env_step_act(c, dwc, s, actc, as, e, a, &so);
+        if (as) act_push(as, commanded);
         if (s) dw_gust_step(c, dwc, s, gid, e->step_count);
         float *o = &obs[i * ORC_OBS_DIM];
         memcpy(o, so.obs, sizeof so.obs);
@@ -1084,6 +1191,7 @@ void orc_vec_step_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_state
             orc_env_reset(c, e, o);
             finish_obs(c, e, gid, 5u, o);
             if (s) dw_episode_start(c, dwc, s, gid, e->step_count);      /* replaces the gust's update of this step */
+            if (as) act_episode_start(c, actc, as, gid, e->step_count);
             e->ep_ret = 0.0; e->ep_len = 0;
         }
         e->step_count += 1;
@@ -1131,6 +1239,8 @@ int32_t orc_sizeof_env(void) { return (int32_t)sizeof(orc_env); }
 int32_t orc_sizeof_config(void) { return (int32_t)sizeof(orc_config); }
 int32_t orc_sizeof_dw_config(void) { return (int32_t)sizeof(orc_dw_config); }
 int32_t orc_sizeof_dw_state(void) { return (int32_t)sizeof(orc_dw_state); }
+int32_t orc_sizeof_act_config(void) { return (int32_t)sizeof(orc_act_config); }
+int32_t orc_sizeof_act_state(void) { return (int32_t)sizeof(orc_act_state); }
 int32_t orc_max_threads(void)
 {
 #ifdef _OPENMP

@@ -229,6 +229,55 @@ void orc_vec_step_dw(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_sta
 int32_t orc_sizeof_dw_config(void);
 int32_t orc_sizeof_dw_state(void);
 
+/* ---- per-drone actuator model (dn_enable_actuator; not in the reference: its actuator is ideal) ----
+ * Restated from the documented semantics (include/dronenav.h), not from the kernels; kept out of orc_config /
+ * orc_env / orc_dw_* like the body and the wind.
+ *   latency: at a vector step a drone enters with episode step counter s (orc_env.steps) the chain consumes the action commanded
+ *            d vector steps ago if s >= d, else `fill`; the action noise of THIS vector step (stream 0) is added to what is consumed;
+ *            after every vector step the history shifts by one and takes the COMMANDED action.
+ *   lag:     ActionType.THRUST and a motor_tau range other than [0, 0]: c = the nominal float32 chain's speeds for the consumed action,
+ *            r <- float32(a r + (1 - a) c) in float64 in that nesting; forces KF r^2, the yaw torque from KM r^2 (float32, as the chain
+ *            forms them from c), the ground effect and last_clipped_action see r; s_kf / s_km scale what comes of it.  a = 0 gives c
+ *            bit for bit.  motor_tau = [0, 0]: the nominal path, `coeff` not read, `rpm` only set at episode starts.
+ *   episode starts (orc_vec_reset_act and the auto-reset of orc_vec_step_act): r = rpm_fill; with resample ONE Philox call keyed
+ *            (seed; gid, the step the episode starts on, stream 17): d = lo + floor((hi - lo + 1) u_0) clamped to hi,
+ *            tau = tau lo + (tau hi - tau lo) u_1, a = float32(exp(-dt / tau)), 0 where tau = 0.  The new a acts from the first step
+ *            of the new episode; the terminal step has used the old one. */
+#define ORC_MAX_LATENCY 8
+typedef struct orc_act_config {
+    int32_t on;                                 /* 1: the actuator of orc_act_state acts */
+    int32_t latency[2];                         /* latency range [lo, hi], control steps, 0 <= lo <= hi <= ORC_MAX_LATENCY */
+    float motor_tau[2];                         /* motor time constant range [lo, hi], s; [0, 0]: no lag */
+    float fill[4];                              /* the action a fresh episode's pipeline holds */
+    int32_t resample;                           /* 1: draw (d, a) at every episode start */
+    float rpm_fill[4];                          /* the nominal chain's speeds for `fill` (orc_act_rpm_fill) */
+} orc_act_config;
+
+/* the per-drone layout dn_get_actuator returns, 152 bytes */
+typedef struct orc_act_state {
+    int32_t latency;                            /* d */
+    float coeff;                                /* a */
+    float rpm[4];                               /* r */
+    float history[ORC_MAX_LATENCY][4];          /* history[j] = the action commanded j + 1 vector steps ago */
+} orc_act_state;
+
+/* rpm_fill <- orc_preprocess_action of `fill` (after orc_rescale_action when cfg->normalize_actions) */
+void orc_act_rpm_fill(const orc_config *cfg, orc_act_config *actc);
+/* the state after the first enable: d = 0, a = 0, r = rpm_fill, history = fill */
+void orc_act_init(const orc_act_config *actc, orc_act_state *acts, int64_t n);
+/* orc_env_step_dw with the motor lag of *as; `action` is the consumed action (actc / as NULL: orc_env_step_dw) */
+void orc_env_step_act(const orc_config *cfg, const orc_dw_config *dwc, const orc_dw_state *s, const orc_act_config *actc,
+                      orc_act_state *as, orc_env *e, const float action[4], orc_step_out *out);
+/* the vec entry points with per-drone state acts[n]; actc / acts NULL: exactly orc_vec_reset_dw / orc_vec_step_dw */
+void orc_vec_reset_act(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                       orc_act_state *acts, orc_env *envs, int64_t n, float *obs, int threads);
+void orc_vec_step_act(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                      orc_act_state *acts, orc_env *envs, int64_t n, const float *actions, float *obs, float *reward, uint8_t *done,
+                      uint8_t *truncated, int32_t *found_targets, float *terminal_obs, float *ep_ret, int32_t *ep_len,
+                      uint8_t *terminated, int threads);
+int32_t orc_sizeof_act_config(void);
+int32_t orc_sizeof_act_state(void);
+
 /* ---- N1: GAE (cleanRLPPO.py:234-248 + SB3 truncation bootstrap) ------------ */
 void orc_gae(const float *rewards, const float *values, const uint8_t *dones,
              const float *last_values, const uint8_t *last_dones,

@@ -80,6 +80,17 @@ class OrcDwConfig(C.Structure):
 DW_DTYPE = np.dtype([("dyn", "f4", 4), ("wind_mean", "f4", 4), ("wind_gust", "f4", 4)], align=True)
 
 
+class OrcActConfig(C.Structure):
+    """orc_act_config: the per-drone actuator model (dn_enable_actuator)."""
+    _fields_ = [("on", C.c_int32), ("latency", C.c_int32 * 2), ("motor_tau", C.c_float * 2), ("fill", C.c_float * 4),
+                ("resample", C.c_int32), ("rpm_fill", C.c_float * 4)]
+
+
+# numpy view of orc_act_state[n], the 152-byte rows of dn_get_actuator: latency d, coefficient a, rotor speeds r and the last 8
+# commanded actions (history[j] = commanded j + 1 vector steps ago)
+ACT_DTYPE = np.dtype([("latency", "i4"), ("coeff", "f4"), ("rpm", "f4", 4), ("history", "f4", (8, 4))], align=True)
+
+
 class OrcStepOut(C.Structure):
     _fields_ = [("obs", C.c_float * OBS_DIM), ("reward", C.c_double),
                 ("terminated", C.c_int32), ("truncated", C.c_int32), ("found_targets", C.c_int32)]
@@ -160,17 +171,25 @@ def lib():
     L.orc_env_step_dw.argtypes = [cfgp, dwcp, C.c_void_p, envp, fp, C.POINTER(OrcStepOut)]
     L.orc_vec_reset_dw.argtypes = [cfgp, dwcp, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
     L.orc_vec_step_dw.argtypes = [cfgp, dwcp, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10 + [C.c_int]
+    actcp = C.POINTER(OrcActConfig)
+    L.orc_act_rpm_fill.argtypes = [cfgp, actcp]
+    L.orc_act_init.argtypes = [actcp, C.c_void_p, C.c_int64]
+    L.orc_env_step_act.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, envp, fp, C.POINTER(OrcStepOut)]
+    L.orc_vec_reset_act.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+    L.orc_vec_step_act.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10 + [C.c_int]
     L.orc_gae.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     L.orc_philox4x32.argtypes = [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]
     L.orc_noise4.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, fp]
     L.orc_noise4_many.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, C.c_uint64, C.c_uint32, fp]
     L.orc_noise4_many.restype = None
-    for name in ("orc_sizeof_env", "orc_sizeof_config", "orc_max_threads", "orc_sizeof_dw_config", "orc_sizeof_dw_state"):
+    for name in ("orc_sizeof_env", "orc_sizeof_config", "orc_max_threads", "orc_sizeof_dw_config", "orc_sizeof_dw_state",
+                 "orc_sizeof_act_config", "orc_sizeof_act_state"):
         getattr(L, name).restype = C.c_int32
     assert L.orc_sizeof_env() == C.sizeof(OrcEnv) == ENV_DTYPE.itemsize, \
         (L.orc_sizeof_env(), C.sizeof(OrcEnv), ENV_DTYPE.itemsize)
     assert L.orc_sizeof_config() == C.sizeof(OrcConfig)
     assert L.orc_sizeof_dw_config() == C.sizeof(OrcDwConfig) and L.orc_sizeof_dw_state() == DW_DTYPE.itemsize
+    assert L.orc_sizeof_act_config() == C.sizeof(OrcActConfig) and L.orc_sizeof_act_state() == ACT_DTYPE.itemsize == 152
     _lib = L
     return L
 
@@ -219,6 +238,20 @@ def make_dw_config(dynamics=None, wind=None):
     return c
 
 
+def make_act_config(cfg, actuator):
+    """orc_act_config from an ActuatorModel-like object (latency / motor_tau ranges, fill, resample); rpm_fill is evaluated by the
+    oracle's own chain for cfg.normalize_actions.  A motor_tau range other than (0, 0) needs ActionType.THRUST, as on the device."""
+    c = OrcActConfig()
+    c.on, c.resample = 1, int(actuator.resample)
+    c.latency[:] = [int(v) for v in actuator.latency]
+    c.motor_tau[:] = actuator.motor_tau
+    c.fill[:] = actuator.fill
+    assert 0 <= c.latency[0] <= c.latency[1] <= 8 and 0.0 <= c.motor_tau[0] <= c.motor_tau[1]
+    assert cfg.action_type == 0 or c.motor_tau[1] == 0.0, "the motor lag needs ActionType.THRUST"
+    lib().orc_act_rpm_fill(C.byref(cfg), C.byref(c))
+    return c
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -226,10 +259,13 @@ def _p(a):
 class OracleVecEnv:
     """N oracle envs stepped the way SubprocVecEnv + Monitor + NormalizeObservation would."""
 
-    def __init__(self, cfg, num_envs, threads=1, dynamics=None, wind=None):
+    def __init__(self, cfg, num_envs, threads=1, dynamics=None, wind=None, actuator=None):
         """dynamics / wind (optional): the per-drone body scales and wind of dn_enable_dynamics / dn_enable_wind, configured like
         the package's DynamicsRandomization / WindDisturbance.  self.dw (DW_DTYPE [n]) holds their state -- scales of 1 and still
-        air until the first episode start draws, as after the first dn_enable_* -- and may be overwritten (teacher forcing)."""
+        air until the first episode start draws, as after the first dn_enable_* -- and may be overwritten (teacher forcing).
+        actuator (optional): the command latency and motor lag of dn_enable_actuator, configured like the package's ActuatorModel.
+        self.act (ACT_DTYPE [n], the rows of dn_get_actuator) starts as after the first enable (d = 0, a = 0, r = rpm_fill, history =
+        fill) and may be overwritten too."""
         self.L = lib()
         self.cfg = cfg
         self.n = int(num_envs)
@@ -239,6 +275,14 @@ class OracleVecEnv:
         self.dw_cfg = None if dynamics is None and wind is None else make_dw_config(dynamics, wind)
         self.dw = np.zeros(self.n, dtype=DW_DTYPE)
         self.dw["dyn"] = 1.0
+        self.enable_actuator(actuator)
+
+    def enable_actuator(self, actuator):
+        """The first dn_enable_actuator (None: off): the configuration, and the state d = 0, a = 0, r = rpm_fill, history = fill."""
+        self.act_cfg = None if actuator is None else make_act_config(self.cfg, actuator)
+        self.act = np.zeros(self.n, dtype=ACT_DTYPE)
+        if self.act_cfg is not None:
+            self.L.orc_act_init(C.byref(self.act_cfg), _p(self.act), self.n)
 
     def _dw_args(self):
         if self.dw_cfg is None:
@@ -246,9 +290,15 @@ class OracleVecEnv:
         assert self.dw.dtype == DW_DTYPE and self.dw.flags.c_contiguous and len(self.dw) == self.n
         return C.byref(self.dw_cfg), _p(self.dw)
 
+    def _act_args(self):
+        if self.act_cfg is None:
+            return None, None
+        assert self.act.dtype == ACT_DTYPE and self.act.flags.c_contiguous and len(self.act) == self.n
+        return C.byref(self.act_cfg), _p(self.act)
+
     def reset(self):
         obs = np.empty((self.n, OBS_DIM), np.float32)
-        self.L.orc_vec_reset_dw(C.byref(self.cfg), *self._dw_args(), _p(self.envs), self.n, _p(obs), self.threads)
+        self.L.orc_vec_reset_act(C.byref(self.cfg), *self._dw_args(), *self._act_args(), _p(self.envs), self.n, _p(obs), self.threads)
         return obs
 
     def refresh_rpy(self):
@@ -263,8 +313,8 @@ class OracleVecEnv:
             found_targets=np.empty(self.n, np.int32), terminal_obs=np.zeros((self.n, OBS_DIM), np.float32),
             ep_ret=np.zeros(self.n, np.float32), ep_len=np.zeros(self.n, np.int32),
             terminated=np.empty(self.n, np.uint8))
-        self.L.orc_vec_step_dw(C.byref(self.cfg), *self._dw_args(), _p(self.envs), self.n, _p(a), _p(out["obs"]), _p(out["reward"]),
-                            _p(out["done"]), _p(out["truncated"]), _p(out["found_targets"]),
+        self.L.orc_vec_step_act(C.byref(self.cfg), *self._dw_args(), *self._act_args(), _p(self.envs), self.n, _p(a), _p(out["obs"]),
+                            _p(out["reward"]), _p(out["done"]), _p(out["truncated"]), _p(out["found_targets"]),
                             _p(out["terminal_obs"]), _p(out["ep_ret"]), _p(out["ep_len"]), _p(out["terminated"]),
                             self.threads)
         return out

@@ -4,7 +4,8 @@
 2. latency = the same env without latency fed the shifted actions, bit for bit (plain, noise, normaliser, dynamics + wind);
 3. one fused launch = single steps, bit for bit, K = 20, 5 (< 8) and 64, history crossings and in-launch fills asserted;
 4. / 7. every instantiation of dn_step_many_1w_kernel<R, NORM, NOISE, ONE, true, false, true, true, ACT = true> against the CPU oracle
-   fed the shifted actions (the oracle knows nothing of the actuator), at tests/test_gpu_dynamics_wind_oracle.py's bars;
+   fed the shifted actions (this file leaves the oracle's actuator off and shifts on the host; the oracle's own actuator model is
+   held against the kernels in tests/test_gpu_actuator_oracle.py), at tests/test_gpu_dynamics_wind_oracle.py's bars;
 5. the draws against their definition on orc_philox4x32;
 6. the motor lag against the oracle's own pieces (chain -> filter in numpy -> orc_rotor_forces -> orc_bullet_step);
 8. sharding, checkpoint, refusals, collectors.
@@ -210,7 +211,7 @@ def test_one_fused_launch_equals_single_steps(K):
 
 # ---- 4. / 7. against the CPU oracle, every instantiation --------------------------------------------------------------------
 def _oracle_cell(dt, norm, noise, mode, dw):
-    """The oracle (unchanged: it knows nothing of the actuator) is fed the shifted actions, teacher-forced from the device state before
+    """The oracle (its own actuator model left off) is fed the shifted actions, teacher-forced from the device state before
     every step (step) or launch (rollout, K = 5: the latency of a drone whose episode ends inside the launch follows the documented
     draw).  Bars: tests/test_gpu_dynamics_wind_oracle.py's (float64 compute: compare_step's 1e-5, flags exact; float32 compute: 5e-4
     on the observations over the running std, at most 1e-4 of the done flags flipped)."""
