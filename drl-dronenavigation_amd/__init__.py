@@ -12,10 +12,11 @@ from .tracks import Track  # noqa: F401
 from .dynamics import DynamicsRandomization  # noqa: F401
 from .wind import WindDisturbance  # noqa: F401
 from .actuator import ActuatorModel  # noqa: F401
+from .sensor import SensorModel  # noqa: F401
 
 __all__ = ["DroneVecEnv", "Track", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
            "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor",
-           "DynamicsRandomization", "WindDisturbance", "ActuatorModel"]
+           "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel"]
 
 
 def __getattr__(name):

@@ -81,6 +81,10 @@ class DnActuatorConfig(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class DnSensorConfig(C.Structure):
+    _fields_ = [("latency", C.c_int32 * 2), ("bias_amp", C.c_float * 13), ("resample", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every entry point declared in include/dronenav.h: name -> (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 PROTOTYPES = {
@@ -132,6 +136,10 @@ PROTOTYPES = {
     "dn_set_actuator": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "dn_get_actuator": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "dn_get_actuator_config": (_I32, [_VP, C.POINTER(DnActuatorConfig)]),
+    "dn_enable_sensor": (_I32, [_VP, C.POINTER(DnSensorConfig)]),
+    "dn_set_sensor": (_I32, [_VP, _VP, _VP, _VP, _VP]),
+    "dn_get_sensor": (_I32, [_VP, _VP, _VP, _VP, _VP]),
+    "dn_get_sensor_config": (_I32, [_VP, C.POINTER(DnSensorConfig)]),
 }
 
 _lib = None

@@ -336,7 +336,8 @@ class OffPolicyCollector:
             cfg = env.cfg
             self._fused_sample = fused_sample and not (cfg.clip_rew or cfg.norm_rew or cfg.physics or cfg.action_type or cfg.random_spawn
                                                        or cfg.zero_damping or env.dynamics is not None
-                                                       or env.wind is not None or env.actuator is not None)   # dn_step_squashed's scope
+                                                       or env.wind is not None or env.actuator is not None
+                                                       or env.sensor is not None)       # dn_step_squashed's scope
         else:
             self.buffer = ReplayBuffer(buffer_size, env.num_envs, env.obs_dim, ACT_DIM, env.device)
             self._obs = env.reset_tensor().clone()
@@ -462,7 +463,8 @@ class FusedRolloutCollector:
         cfg = env.cfg
         self._sampled_step = not (cfg.clip_rew or cfg.norm_rew or cfg.physics or cfg.action_type or cfg.random_spawn or cfg.zero_damping
                                   or env.dynamics is not None or env.wind is not None
-                                  or env.actuator is not None)   # dn_step_sampled's scope (randomised dynamics, wind, actuator: sample + dn_step)
+                                  or env.actuator is not None
+                                  or env.sensor is not None)   # dn_step_sampled's scope (randomised dynamics, wind, actuator, sensor: sample + dn_step)
         self._clipped = None if self._sampled_step else torch.empty((n, ACT_DIM), dtype=f32, device=dev)
         # ONE launch per step (dn_mlp_step_sampled: the actor's workgroups step the drones they evaluated) where that kernel is built:
         # the float64 reference configuration without noise / ground contact, fleets on the three-wave single step, whole workgroups

@@ -98,6 +98,8 @@ struct dn_env {
     dn_wind_config wind_cfg = {};
     DnAct act = {};             // dn_enable_actuator: act.hist / rpm / coeff / lat are one allocation of its own (152 bytes per drone, outside the arena)
     dn_actuator_config act_cfg = {};
+    DnSens sens = {};           // dn_enable_sensor: sens.ring / bias / lat are one allocation of its own (1092 bytes per drone, outside the arena)
+    dn_sensor_config sens_cfg = {};
 };
 
 thread_local hipEvent_t dn_tl_ev_start = nullptr, dn_tl_ev_stop = nullptr;
@@ -548,7 +550,7 @@ int32_t dn_destroy(dn_env *env)
 {
     if (!env) return DN_OK;
     hipError_t he = hipSuccess;
-    if (env->arena || env->dyn.dyn || env->wind.mean || env->act.hist) (void)hipSetDevice(env->cfg.device_id);
+    if (env->arena || env->dyn.dyn || env->wind.mean || env->act.hist || env->sens.ring) (void)hipSetDevice(env->cfg.device_id);
     if (env->arena) he = hipFree(env->arena);
     if (env->dyn.dyn) {
         const hipError_t hd = hipFree(env->dyn.dyn);
@@ -561,6 +563,10 @@ int32_t dn_destroy(dn_env *env)
     if (env->act.hist) {
         const hipError_t ha = hipFree(env->act.hist);
         if (he == hipSuccess) he = ha;
+    }
+    if (env->sens.ring) {
+        const hipError_t hs = hipFree(env->sens.ring);
+        if (he == hipSuccess) he = hs;
     }
     delete env;
     if (he != hipSuccess) return fail(DN_ERR_HIP, "hipFree failed: %s", hipGetErrorString(he));
@@ -596,7 +602,7 @@ int32_t dn_reset(dn_env *env, float *obs, void *stream)
 {
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     if (!obs) return fail(DN_ERR_INVALID_ARGUMENT, "obs is NULL");
-    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn, &env->wind, &env->act));
+    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn, &env->wind, &env->act, &env->sens));
     return DN_OK;
 }
 
@@ -616,7 +622,7 @@ int32_t dn_step(dn_env *env, const float *actions, float *obs, float *reward, ui
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn, &env->wind, &env->act));
+    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn, &env->wind, &env->act, &env->sens));
     return DN_OK;
 }
 
@@ -640,6 +646,8 @@ int32_t dn_step_sampled(dn_env *env, const float *mean, const float *log_std, ui
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the wind (dn_enable_wind); use dn_policy_sample + dn_step there");
     if (env->act.hist)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the actuator model (dn_enable_actuator); use dn_policy_sample + dn_step there");
+    if (env->sens.ring)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the sensor model (dn_enable_sensor); use dn_policy_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -672,6 +680,8 @@ int32_t dn_step_squashed(dn_env *env, const float *mu_log_std, uint64_t seed, in
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the wind (dn_enable_wind); use dn_squashed_sample + dn_step there");
     if (env->act.hist)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the actuator model (dn_enable_actuator); use dn_squashed_sample + dn_step there");
+    if (env->sens.ring)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the sensor model (dn_enable_sensor); use dn_squashed_sample + dn_step there");
     DnStepIO io;
     io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
     io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
@@ -703,6 +713,8 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the wind (dn_enable_wind); use dn_mlp_forward + dn_policy_sample + dn_step");
     if (env->act.hist)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the actuator model (dn_enable_actuator); use dn_mlp_forward + dn_policy_sample + dn_step");
+    if (env->sens.ring)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the sensor model (dn_enable_sensor); use dn_mlp_forward + dn_policy_sample + dn_step");
     const dn_config &c = env->cfg;
     for (int k = 0; k < num_nets; ++k) {
         const dn_mlp_net &n = nets[k];
@@ -767,6 +779,8 @@ int32_t dn_eval_kinematics(dn_env *env, const double *kinematics, float *obs, fl
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given still-air transition: refused with the wind (dn_enable_wind)");
     if (env->act.hist)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given transition: refused with the actuator model (dn_enable_actuator)");
+    if (env->sens.ring)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics reports the observation of the given transition: refused with the sensor model (dn_enable_sensor)");
     DnStepIO io;
     memset(&io, 0, sizeof io);
     io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated; io.found_targets = found_targets;
@@ -799,7 +813,7 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
     io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
     io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
     DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn, &env->wind, &env->act));
+    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn, &env->wind, &env->act, &env->sens));
     return DN_OK;
 }
 
@@ -1248,6 +1262,82 @@ int32_t dn_get_actuator_config(const dn_env *env, dn_actuator_config *out)
     return 1;
 }
 
+int32_t dn_enable_sensor(dn_env *env, const dn_sensor_config *cfg)
+{
+    if (!env || !cfg) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    if (cfg->latency[0] < 0 || cfg->latency[1] > DN_MAX_LATENCY || cfg->latency[0] > cfg->latency[1])
+        return fail(DN_ERR_INVALID_ARGUMENT, "sensor latency = [%d, %d]: need 0 <= lo <= hi <= %d", cfg->latency[0], cfg->latency[1], DN_MAX_LATENCY);
+    bool any_amp = false;
+    for (int j = 0; j < DN_OBS_DIM; ++j) {
+        if (!std::isfinite(cfg->bias_amp[j]) || !(cfg->bias_amp[j] >= 0.0f))
+            return fail(DN_ERR_INVALID_ARGUMENT, "sensor bias_amp[%d] = %g: need finite >= 0", j, (double)cfg->bias_amp[j]);
+        any_amp = any_amp || cfg->bias_amp[j] > 0.0f;
+    }
+    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    DN_HIP(hipSetDevice(env->cfg.device_id));
+    if (!env->sens.ring) {                  // first call: d = 0, b = 0, an all-zero ring
+        const long long n = env->cfg.num_envs;
+        const size_t quads = (size_t)n * (DN_SENS_SLOTS * 4 + 4);
+        const size_t bytes = quads * sizeof(float4) + (size_t)n * sizeof(int);
+        float4 *d = nullptr;
+        const hipError_t he = hipMalloc(&d, bytes);
+        if (he != hipSuccess)
+            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the sensor model failed: %s", bytes, hipGetErrorString(he));
+        if (hipMemsetAsync(d, 0, bytes, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(d);
+            return fail(DN_ERR_HIP, "initialising the sensor model failed");
+        }
+        env->sens.ring = d;
+        env->sens.bias = d + (size_t)n * DN_SENS_SLOTS * 4;
+        env->sens.lat = reinterpret_cast<int *>(d + quads);
+        env->sens.base = 0;
+    } else {
+        DN_HIP(hipDeviceSynchronize());     // launches in flight carry the previous configuration
+    }
+    DnSens &s = env->sens;
+    for (int j = 0; j < DN_OBS_DIM; ++j) s.amp[j] = cfg->bias_amp[j];
+    s.lat_lo = cfg->latency[0]; s.lat_hi = cfg->latency[1];
+    s.resample = cfg->resample;
+    s.lat_on = cfg->latency[1] > 0 || !cfg->resample;
+    s.bias_on = any_amp || !cfg->resample;
+    env->sens_cfg = *cfg;
+    env->waves_fused = env->waves_single = 1;     // the sensor model lives in the one-wave option kernels only
+    return DN_OK;
+}
+
+int32_t dn_set_sensor(dn_env *env, const int32_t *latency, const float *bias, const float *history, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    if (!env->sens.ring) return fail(DN_ERR_BAD_STATE, "the sensor model is not enabled (dn_enable_sensor)");
+    const size_t n = (size_t)env->cfg.num_envs;
+    hipStream_t s = (hipStream_t)stream;
+    if (latency) DN_HIP(hipMemcpyAsync(env->sens.lat, latency, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (bias) DN_HIP(dn_launch_sensor_bias(env->sens, env->cfg.num_envs, const_cast<float *>(bias), 1, s));
+    if (history) DN_HIP(dn_launch_sensor_history(env->p, env->sens, const_cast<float *>(history), 1, s));
+    return DN_OK;
+}
+
+int32_t dn_get_sensor(dn_env *env, int32_t *latency, float *bias, float *history, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    if (!env->sens.ring) return fail(DN_ERR_BAD_STATE, "the sensor model is not enabled (dn_enable_sensor)");
+    const size_t n = (size_t)env->cfg.num_envs;
+    hipStream_t s = (hipStream_t)stream;
+    if (latency) DN_HIP(hipMemcpyAsync(latency, env->sens.lat, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (bias) DN_HIP(dn_launch_sensor_bias(env->sens, env->cfg.num_envs, bias, 0, s));
+    if (history) DN_HIP(dn_launch_sensor_history(env->p, env->sens, history, 0, s));
+    return DN_OK;
+}
+
+int32_t dn_get_sensor_config(const dn_env *env, dn_sensor_config *out)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    if (!env->sens.ring) return 0;
+    *out = env->sens_cfg;
+    return 1;
+}
+
 int32_t dn_get_step_count(const dn_env *env, uint64_t *out)
 {
     if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
@@ -1265,6 +1355,11 @@ int32_t dn_set_step_count(dn_env *env, uint64_t value)
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     DN_HIP(hipSetDevice(env->cfg.device_id));
     DN_HIP(hipDeviceSynchronize());
+    if (env->sens.ring) {                   // the sensor ring's slots are keyed by the vector step: the rows stay where they are, the offset moves
+        unsigned long long old = 0;
+        DN_HIP(hipMemcpy(&old, &env->p.st.stats[0].step_count, sizeof old, hipMemcpyDeviceToHost));
+        env->sens.base = (int)(((unsigned)env->sens.base + (unsigned)old - (unsigned)value) & (DN_SENS_SLOTS - 1u));
+    }
     DN_HIP(dn_launch_set_step_count(env->p.st.stats, env->blocks, value, nullptr));
     DN_HIP(hipStreamSynchronize(nullptr));
     return DN_OK;

@@ -159,6 +159,24 @@ struct DnAct {
     int lag_on;             // tau range != [0, 0]: launch-uniform; 0 = the filter is skipped (the nominal bits), coeff and rpm are not read
 };
 
+// Per-drone sensor model (dn_enable_sensor): the observation row delivered to the normaliser / the output is the pre-normaliser row of d
+// control steps ago plus a per-episode bias.  Not a field of DnParams for the same reason as DnDyn; it travels behind DnDyn, DnWind and DnAct
+// in the last argument of the one-wave step kernels instantiated with it (dn_step_many_1w_kernel<..., ACT = true, SENS = true>) and as the
+// last argument of the reset kernel.  The three arrays are one allocation, ring first: (16 * 64 + 64 + 4) = 1092 bytes per drone.
+#define DN_SENS_SLOTS 16    // ring depth: a power of two >= DN_MAX_LATENCY + 1
+struct DnSens {
+    float4 *ring;           // [16][4][N]: quad q of the pre-bias row measured at vector step sc sits at ring[(((sc + base) & 15) * 4 + q) * N + i]
+                            // (columns 13..15 of the last quad are padding); nullptr = sensor not enabled
+    float4 *bias;           // [4][N]: quad q of drone i's bias row at bias[q * N + i]
+    int *lat;               // [N] latency d, control steps
+    float amp[13];          // bias amplitudes, observation-column units
+    int lat_lo, lat_hi;     // range of the latency draw
+    int resample;           // 1: draw d and b at every episode start; 0: keep what dn_set_sensor wrote
+    int lat_on;             // launch-uniform: the delay is applied and the ring is maintained (latency != [0, 0], or resample = 0)
+    int bias_on;            // launch-uniform: the bias is added (some amplitude > 0, or resample = 0)
+    int base;               // host-side ring offset: dn_set_step_count moves it so that the slot of a vector step never changes
+};
+
 // dn_set_launch_events (ABI 8): the step kernel of the next dn_step / dn_step_many launch is dispatched with these two hipEvents attached to
 // its own dispatch packet (hipExtLaunchKernelGGL) -- they time the kernel itself, like a profiler's kernel trace, where a pair of
 // hipEventRecord around the call would also time the host's launch path and add two marker packets to the stream.  One shot: the
@@ -174,10 +192,15 @@ int dn_norm_exact_compiled_in();      // 1 in libdronenav_exact.so (-DDN_NORM_EX
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream,
                                const DnDyn *dy = nullptr,     // dy->dyn != nullptr: the one-wave kernel with the scales, whatever `waves` says
                                const DnWind *wd = nullptr,    // wd->mean != nullptr: the one-wave kernel with the wind (and dy's scales, if any)
-                               const DnAct *ac = nullptr);    // ac->hist != nullptr: the one-wave kernel with the actuator (and dy's / wd's, if any)
+                               const DnAct *ac = nullptr,     // ac->hist != nullptr: the one-wave kernel with the actuator (and dy's / wd's, if any)
+                               const DnSens *sn = nullptr);   // sn->ring != nullptr: the one-wave kernel with the sensor model (and the other three, if any)
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);   // dn_kernels_mw.hip
 hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy = nullptr, const DnWind *wd = nullptr,
-                           const DnAct *ac = nullptr);
+                           const DnAct *ac = nullptr, const DnSens *sn = nullptr);
+// dn_set_sensor / dn_get_sensor: history[N][9][13] (logical order, history[i][j] = the row of j control steps ago) <-> the ring
+hipError_t dn_launch_sensor_history(const DnParams &p, const DnSens &sn, float *history, int to_ring, hipStream_t stream);
+// bias[N][13] <-> the quads
+hipError_t dn_launch_sensor_bias(const DnSens &sn, long long n, float *bias, int to_dev, hipStream_t stream);
 hipError_t dn_launch_eval_kinematics(const DnParams &p, const DnStepIO &io, const double *kin, bool f32, hipStream_t stream);
 hipError_t dn_launch_gae(const float *rewards, const float *values, const uint8_t *dones,
                          const float *last_values, const uint8_t *last_dones, long long T, long long N,

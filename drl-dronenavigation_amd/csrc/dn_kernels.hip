@@ -1500,6 +1500,94 @@ DN_DEV float4 act_consume(const DnAct &ac, const float4 *act, const long long n,
     return ac.hist[8 * i + (d - t - 1)];
 }
 
+// ---- per-drone sensor model (dn_enable_sensor) ------------------------------------------------------------------------------
+// The latency d and the bias row b of an episode: FOUR Philox4x32-10 calls on streams 18..21, keyed like dyn_draw.  Value c of call q
+// (stream 18 + q) is u_m = (r_c + 0.5) / 2^32 in float64 with m = 4 q + c: b_j = float32(amp_j (2 u_j - 1)) for the 13 columns,
+// d = lo + floor((hi - lo + 1) u_13) clamped to hi (the actuator's expression); u_14 and u_15 are unused.  An episode start only.
+DN_DEV void sens_draw(const DnSens &sn, const unsigned long long seed, const unsigned long long gid, const unsigned long long step, int &d,
+                      float b[DN_OBS_DIM])
+{
+    double u[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        unsigned r[4];
+        philox4x32((unsigned)gid, (unsigned)(gid >> 32), (unsigned)step, (18u + (unsigned)q) | ((unsigned)(step >> 32) << 8), (unsigned)seed,
+                   (unsigned)(seed >> 32), r);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) u[4 * q + c] = ((double)r[c] + 0.5) * (1.0 / 4294967296.0);
+    }
+#pragma unroll
+    for (int j = 0; j < DN_OBS_DIM; ++j) b[j] = (float)((double)sn.amp[j] * (2.0 * u[j] - 1.0));
+    const int dd = sn.lat_lo + (int)floor((double)(sn.lat_hi - sn.lat_lo + 1) * u[13]);
+    d = dd > sn.lat_hi ? sn.lat_hi : dd;
+}
+// A row as four quads of a [..][4][N] array: quad q of drone i at base[q * n + i] (a wave's 64 drones: 1 KiB contiguous per quad)
+DN_DEV void sens_store_quads(float4 *base, const long long n, const long long i, const float o[DN_OBS_DIM])
+{
+    base[i] = make_float4(o[0], o[1], o[2], o[3]);
+    base[n + i] = make_float4(o[4], o[5], o[6], o[7]);
+    base[2 * n + i] = make_float4(o[8], o[9], o[10], o[11]);
+    base[3 * n + i] = make_float4(o[12], 0.0f, 0.0f, 0.0f);
+}
+DN_DEV void sens_load_quads(const float4 *base, const long long n, const long long i, float o[DN_OBS_DIM])
+{
+    const float4 a = base[i], b = base[n + i], c = base[2 * n + i], d = base[3 * n + i];
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    o[8] = c.x; o[9] = c.y; o[10] = c.z; o[11] = c.w; o[12] = d.x;
+}
+// the ring slot of the row measured at vector step sc (the reset row of dn_reset: sc = step counter - 1)
+DN_DEV unsigned sens_slot(const DnSens &sn, const unsigned long long sc) { return ((unsigned)sc + (unsigned)sn.base) & (DN_SENS_SLOTS - 1u); }
+DN_DEV float4 *sens_ring(const DnSens &sn, const long long n, const unsigned slot) { return sn.ring + (long long)(slot * 4u) * n; }
+// What a step kernel carries per lane: the latency (a register copy across the launch; a new episode's draw replaces it) and the number of
+// control steps the episode has flown once the current step is over.
+struct SensCtx {
+    const DnSens *sn;
+    long long n, i;
+    int d, k;
+    bool active;
+};
+// The step row (also terminal_observation), between add_obs_noise and normalize_obs: the pre-bias row o_k goes to the ring slot of vector
+// step sc (wave-uniform slot: four coalesced 16-byte stores), the row of min(d, k) steps ago comes back (a per-lane gather; the lane's own
+// row where that is 0), and the bias is added: y_k = float32(o_{k - min(d, k)} + b), one float32 add per column.
+DN_DEV void sens_deliver(const SensCtx &x, const unsigned long long sc, float o[DN_OBS_DIM])
+{
+    const DnSens &sn = *x.sn;
+    if (sn.lat_on) {                        // launch-uniform
+        const unsigned slot = sens_slot(sn, sc);
+        if (x.active) sens_store_quads(sens_ring(sn, x.n, slot), x.n, x.i, o);
+        const int dd = x.d < x.k ? x.d : x.k;
+        if (__ballot(dd > 0) != 0ull) {     // wave-uniform
+            float h[DN_OBS_DIM];
+            sens_load_quads(sens_ring(sn, x.n, (slot - (unsigned)dd) & (DN_SENS_SLOTS - 1u)), x.n, x.i, h);
+#pragma unroll
+            for (int j = 0; j < DN_OBS_DIM; ++j) o[j] = dd > 0 ? h[j] : o[j];
+        }
+    }
+    if (sn.bias_on) {                       // launch-uniform: no add otherwise (-0.0f + 0.0f would flip a sign bit)
+        float b[DN_OBS_DIM];
+        sens_load_quads(sn.bias, x.n, x.i, b);
+#pragma unroll
+        for (int j = 0; j < DN_OBS_DIM; ++j) o[j] = o[j] + b[j];
+    }
+}
+// The reset row o_0 of an episode that starts at vector step sc (the step that ended the previous one; dn_reset: the step counter), between
+// add_obs_noise and normalize_obs: the new episode's d and b are drawn (resample) and stored, o_0 takes ring slot `slot` -- the terminal row
+// of that step has been delivered by then -- and leaves as float32(o_0 + b_new), undelayed.
+DN_DEV void sens_restart(const DnSens &sn, const long long n, const long long i, const bool active, const unsigned long long seed,
+                         const unsigned long long gid, const unsigned long long sc, const unsigned slot, int &d, float o[DN_OBS_DIM])
+{
+    float b[DN_OBS_DIM];
+    if (sn.resample) {
+        sens_draw(sn, seed, gid, sc, d, b);
+        if (active) { sn.lat[i] = d; sens_store_quads(sn.bias, n, i, b); }
+    } else if (sn.bias_on) sens_load_quads(sn.bias, n, i, b);
+    if (sn.lat_on && active) sens_store_quads(sens_ring(sn, n, slot), n, i, o);
+    if (sn.bias_on) {
+#pragma unroll
+        for (int j = 0; j < DN_OBS_DIM; ++j) o[j] = o[j] + b[j];
+    }
+}
+
 // DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
 // WIND (with DYN): the wind force *wf over the mass of *dk joins the extra accelerations
 template <typename R, typename TH = Thrust, bool XOPT = false, bool DYN = false, bool WIND = false>
@@ -1922,16 +2010,18 @@ DN_DEV void reward_candidates(const DnParams &p, const DnConsts<R> &c, const R *
     const RewardPre<R> q = reward_entry<R>(p, c, fl, G4, G5);
     reward_pose<R>(p, s_tab, fl, q, r_normal, r_found32);
 }
-template <typename R, bool NORM, bool NOISE>
+// SENS (the one-wave kernels with dn_enable_sensor): *sx is the kernel's own register copy; the delivered row replaces the true one
+template <typename R, bool NORM, bool NOISE, bool SENS = false>
 DN_DEV Observed<R> observe_phase(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const Flight<R> &fl,
                                  const float4 G4, const float4 G5, const unsigned long long gid, const unsigned long long step_count,
-                                 Rms &rms)
+                                 Rms &rms, SensCtx *sx = nullptr)
 {
     Observed<R> ob;
     observe_columns<R>(p, c, fl, ob.o);
     reward_candidates<R>(p, c, s_tab, fl, G4, G5, ob.r_normal, ob.r_found32);
     // sensor noise / per-drone normaliser act on the step observation (which is also terminal_observation)
     if (NOISE && p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, step_count, 1u, ob.o);
+    if constexpr (SENS) sens_deliver(*sx, step_count, ob.o);
     if (NORM) normalize_obs(rms, ob.o);
     return ob;
 }
@@ -2109,10 +2199,10 @@ DN_DEV void report_scalars(const DnParams &p, const DnConsts<R> &c, const StepOu
     }
     if (out.done_word && lane == 0) *out.done_word = done_ballot;
 }
-template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false>
+template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false, bool SENS = false>
 DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const bool truncated,
                        const Verdict<R> &v, float *o, const unsigned long long gid, const unsigned long long step_count,
-                       const unsigned li, const unsigned lane, const unsigned rows, const bool active, Rms &rms)
+                       const unsigned li, const unsigned lane, const unsigned rows, const bool active, Rms &rms, SensCtx *sx = nullptr)
 {
     const bool done = v.terminated != 0 || truncated;
     const unsigned long long done_mask = __ballot(done && active);
@@ -2134,6 +2224,10 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
             }
             if (across) add_obs_noise_drawn(p, zr, o);
             else if (NOISE && p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, step_count, 5u, o);
+            if constexpr (SENS) {
+                if (sx->sn->lat_on || sx->sn->bias_on)      // launch-uniform: both off = the existing path
+                    sens_restart(*sx->sn, sx->n, sx->i, sx->active, p.seed, gid, step_count, sens_slot(*sx->sn, step_count), sx->d, o);
+            }
             if (NORM) normalize_obs(rms, o);
         }
     }
@@ -2141,14 +2235,14 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
     else if (TILE == 1) tile_park(s_tile, lane, o);        // streamed out by the caller one step later
     else store_obs_tile(s_tile, out.obs, rows, lane, o);
 }
-template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false>
+template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false, bool SENS = false>
 DN_DEV void report_phase(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const Flight<R> &fl,
                          const Verdict<R> &v, Observed<R> &ob, const unsigned long long gid, const unsigned long long step_count,
                          const unsigned li, const unsigned lane, const unsigned rows, const bool active,
-                         float4 &G4, float4 &G5, StatAcc &acc, Rms &rms, RewNorm &rn)
+                         float4 &G4, float4 &G5, StatAcc &acc, Rms &rms, RewNorm &rn, SensCtx *sx = nullptr)
 {
     report_scalars<R, REW>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn);
-    report_obs<R, NORM, NOISE, TILE, SPAWN>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active, rms);
+    report_obs<R, NORM, NOISE, TILE, SPAWN, SENS>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active, rms, sx);
 }
 
 struct BlockState {
@@ -2259,14 +2353,22 @@ struct WindArg : DnDyn {
 struct ActArg : WindArg {
     DnAct a;
 };
-template <bool DYN, bool WIND, bool ACT = false> struct StepArg { using type = DynArg<DYN>; };
-template <> struct StepArg<true, true, false> { using type = WindArg; };
-template <> struct StepArg<true, true, true> { using type = ActArg; };
-template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false, bool ACT = false>
+// SENS (with ACT, WIND, DYN and XOPT): the argument carries dn_enable_sensor's state as well (SensArg); the actuator's pointers are null when
+// the actuator is off (latency 0, no lag, nothing drawn or stored).
+struct SensArg : ActArg {
+    DnSens s;
+};
+template <bool DYN, bool WIND, bool ACT = false, bool SENS = false> struct StepArg { using type = DynArg<DYN>; };
+template <> struct StepArg<true, true, false, false> { using type = WindArg; };
+template <> struct StepArg<true, true, true, false> { using type = ActArg; };
+template <> struct StepArg<true, true, true, true> { using type = SensArg; };
+template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false, bool ACT = false,
+          bool SENS = false>
 __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg,
-                                                                   const typename StepArg<DYN, WIND, ACT>::type dy)
+                                                                   const typename StepArg<DYN, WIND, ACT, SENS>::type dy)
 {
     static_assert(!ACT || (WIND && DYN && XOPT && !SAMPLE), "the actuator rides on the option kernels with the body terms and the wind");
+    static_assert(!SENS || ACT, "the sensor model rides on the option kernels with the actuator");
     const int k_steps = ONE ? 1 : k_arg;
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -2303,8 +2405,10 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     int LAT = 0;
     ActLag lag = {{0.0f, 0.0f, 0.0f, 0.0f}, 0.0f};
     bool act_new = false;                               // an episode started inside the launch: r = rpm_fill, new d and a (resample)
+    bool act_have = ACT;                                // SENS: the actuator itself may be off (null pointers: latency 0, no lag, no stores)
+    if constexpr (SENS) act_have = dy.a.hist != nullptr;
     if constexpr (ACT) {
-        LAT = dy.a.lat[i];
+        if (act_have) LAT = dy.a.lat[i];
         LAT = LAT < 0 ? 0 : (LAT > DN_MAX_LATENCY ? DN_MAX_LATENCY : LAT);      // dn_set_actuator does not validate: the history is 8 deep
         if (dy.a.lag_on) {
             const float4 r4 = dy.a.rpm[i];
@@ -2322,6 +2426,13 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     if (sampled) A = sample_action(io0, gid, sc0, i, active);
     bool lag_on = false;                                // ACT with the motor lag on (launch-uniform); off = the nominal chain
     if constexpr (ACT) lag_on = dy.a.lag_on != 0;
+    // dn_enable_sensor: this drone's sensor latency, held in a register across the launch; the bias and the ring stay in memory
+    SensCtx sx = {nullptr, p.n, i, 0, 0, active};
+    if constexpr (SENS) {
+        sx.sn = &dy.s;
+        const int sd = dy.s.lat[i];
+        sx.d = sd < 0 ? 0 : (sd > DN_MAX_LATENCY ? DN_MAX_LATENCY : sd);        // dn_set_sensor does not validate: the ring serves 8 steps back
+    }
     const R wp0[3] = {s_tab[DN_T_WP], s_tab[DN_T_WP + 1], s_tab[DN_T_WP + 2]};   // waypoint 0: every reset measures against it
     StatAcc acc;
     Rms rms;
@@ -2361,7 +2472,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         }
         if constexpr (ACT) {
             const bool done = v.terminated || fl.truncated;
-            if (__ballot(done) != 0ull) {               // wave-uniform: the episode starts of this step
+            if (act_have && __ballot(done) != 0ull) {   // wave-uniform: the episode starts of this step
                 if (done) {
                     if (dy.a.resample) act_draw(dy.a, p.seed, gid, sc, LAT, lag.a);
                     lag.r[0] = dy.a.rpm_fill.x; lag.r[1] = dy.a.rpm_fill.y; lag.r[2] = dy.a.rpm_fill.z; lag.r[3] = dy.a.rpm_fill.w;
@@ -2383,8 +2494,10 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
             }
         }
         attitude_phase<R>(fl);
-        Observed<R> ob = observe_phase<R, NORM, NOISE>(p, c, s_tab, fl, G4, G5, gid, sc, rms);
-        report_phase<R, NORM, NOISE, XOPT, 0, XOPT>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn);
+        if constexpr (SENS) sx.k = unpack_meta(G3e.w).steps + 1;    // control steps of the episode flown once this step is over
+        Observed<R> ob = observe_phase<R, NORM, NOISE, SENS>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx);
+        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, SENS>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn,
+                                                          &sx);
         A = A_next;
     }
     if (ONE) flush_stats_preloaded(p, slot0, acc, sc0 + 1ull, lane, (long long)blockIdx.x);
@@ -2403,7 +2516,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
             if (dy.w.gust_on || wind_new) dy.w.gust[i] = WG;
             if (wind_new && dy.w.resample) dy.w.mean[i] = WB;
         }
-        if constexpr (ACT) {
+        if constexpr (ACT) if (act_have) {
             if (dy.a.lag_on || act_new) dy.a.rpm[i] = make_float4(lag.r[0], lag.r[1], lag.r[2], lag.r[3]);
             if (act_new && dy.a.resample) { dy.a.lat[i] = LAT; dy.a.coeff[i] = lag.a; }
             // the history becomes the last 8 commands: the old one shifted by k_steps (descending: every source is read before it is
@@ -3956,7 +4069,8 @@ __global__ __launch_bounds__(3 * DN_BLOCK) void dn_step_pqx_kernel(const DnParam
 // VecEnv.reset(): every drone goes through Monitor.reset / NormalizeObservation.reset / PBDroneEnv.reset.
 // =====================================================================================================
 template <typename R>
-__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd, const DnAct ac)
+__global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd, const DnAct ac,
+                                                            const DnSens sn)
 {
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -3988,6 +4102,11 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
         o[0] = (float)((R)sx * c.inv_dim[0]); o[1] = (float)((R)sy * c.inv_dim[1]); o[2] = (float)((R)sz * c.inv_dim[2]);
     }
     if (p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, p.st.stats[blockIdx.x].step_count, 5u, o);
+    if (sn.ring && (sn.lat_on || sn.bias_on)) {      // dn_enable_sensor: this episode's d and b; o_0 seeds the ring where the first step (k = 1) looks one step back
+        const unsigned long long sc = p.st.stats[blockIdx.x].step_count;
+        int d = 0;
+        sens_restart(sn, p.n, i, active, p.seed, gid, sc, sens_slot(sn, sc - 1ull), d, o);
+    }
     if (p.normalize_obs) {
         Rms rms;
         load_rms(p, i, rms);
@@ -4231,6 +4350,46 @@ __global__ __launch_bounds__(256) void dn_set_step_count_kernel(DnStatSlot *slot
         slots[i].step_count = value;
 }
 
+// dn_set_sensor / dn_get_sensor: history[i][j] (the pre-bias row of j control steps ago, j = 0..8) <-> the ring.  The last vector step run
+// is the tile's counter - 1, so the row of j steps ago sits in the slot of vector step counter - 1 - j.  One thread per (drone, j).
+__global__ __launch_bounds__(256) void dn_sensor_history_kernel(const DnStatSlot *slots, const long long n, const DnSens sn, float *history,
+                                                                const int to_ring)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * (DN_MAX_LATENCY + 1)) return;
+    const long long i = t / (DN_MAX_LATENCY + 1);
+    const int j = (int)(t - i * (DN_MAX_LATENCY + 1));
+    const unsigned long long sc = slots[i / DN_BLOCK].step_count;
+    float4 *row = sens_ring(sn, n, sens_slot(sn, sc - 1ull - (unsigned long long)j));
+    float *h = history + t * DN_OBS_DIM;
+    float o[DN_OBS_DIM];
+    if (to_ring) {
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) o[c] = h[c];
+        sens_store_quads(row, n, i, o);
+    } else {
+        sens_load_quads(row, n, i, o);
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) h[c] = o[c];
+    }
+}
+// bias[i][13] <-> the four quads of drone i
+__global__ __launch_bounds__(256) void dn_sensor_bias_kernel(const DnSens sn, const long long n, float *bias, const int to_dev)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float o[DN_OBS_DIM];
+    if (to_dev) {
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) o[c] = bias[i * DN_OBS_DIM + c];
+        sens_store_quads(sn.bias, n, i, o);
+    } else {
+        sens_load_quads(sn.bias, n, i, o);
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) bias[i * DN_OBS_DIM + c] = o[c];
+    }
+}
+
 __global__ __launch_bounds__(256) void dn_fill4_kernel(float4 *dst, float4 v, long long n)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dst[i] = v;
@@ -4382,9 +4541,33 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 #endif
 #elif DN_TU == 1
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnDyn *dy,
-                               const DnWind *wd, const DnAct *ac)
+                               const DnWind *wd, const DnAct *ac, const DnSens *sn)
 {
     const bool norm = p.normalize_obs != 0;
+    if (sn && sn->ring) {                   // dn_enable_sensor: the one-wave option kernel with the sensor model and the other three features
+        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the sensor (the C ABI refuses them first)
+        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
+        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
+        SensArg sa;
+        static_cast<DnDyn &>(sa) = dy ? *dy : DnDyn{};
+        sa.w = wd ? *wd : DnWind{};
+        sa.a = ac ? *ac : DnAct{};
+        sa.s = *sn;
+#define DN_LSN(R, NORM, NOISE)                                                                                                      \
+        do {                                                                                                                        \
+            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, sa); \
+            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, sa);   \
+        } while (0)
+        if (f32) {
+            if (norm) { if (noise) DN_LSN(float, true, true); else DN_LSN(float, true, false); }
+            else { if (noise) DN_LSN(float, false, true); else DN_LSN(float, false, false); }
+        } else {
+            if (norm) { if (noise) DN_LSN(double, true, true); else DN_LSN(double, true, false); }
+            else { if (noise) DN_LSN(double, false, true); else DN_LSN(double, false, false); }
+        }
+#undef DN_LSN
+        return hipGetLastError();
+    }
     if (ac && ac->hist) {                   // dn_enable_actuator: the one-wave option kernel with the actuator, the wind and the body terms
         if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the actuator (the C ABI refuses them first)
         const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
@@ -4517,14 +4700,29 @@ hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, boo
 #undef DN_LAUNCH3
 
 #if DN_TU == 1
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy, const DnWind *wd, const DnAct *ac)
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy, const DnWind *wd, const DnAct *ac,
+                           const DnSens *sn)
 {
     const DnAct act = ac ? *ac : DnAct{};
+    const DnSens sen = sn ? *sn : DnSens{};
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
     const DnDyn dyn = dy ? *dy : DnDyn{};
     const DnWind wnd = wd ? *wd : DnWind{};
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act);
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act, sen);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act, sen);
+    return hipGetLastError();
+}
+
+hipError_t dn_launch_sensor_history(const DnParams &p, const DnSens &sn, float *history, int to_ring, hipStream_t stream)
+{
+    const long long m = p.n * (DN_MAX_LATENCY + 1);
+    hipLaunchKernelGGL(dn_sensor_history_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, p.st.stats, p.n, sn, history, to_ring);
+    return hipGetLastError();
+}
+
+hipError_t dn_launch_sensor_bias(const DnSens &sn, long long n, float *bias, int to_dev, hipStream_t stream)
+{
+    hipLaunchKernelGGL(dn_sensor_bias_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sn, n, bias, to_dev);
     return hipGetLastError();
 }
 

@@ -105,7 +105,7 @@ typedef struct dn_config {
  * checkpointing).  Field names follow the reference's attributes.  It does not carry the body scales of
  * dn_enable_dynamics: a checkpoint of a randomised fleet is dn_get_state + dn_get_dynamics (restore: dn_set_state + dn_set_dynamics),
  * nor the wind of dn_enable_wind (+ dn_get_wind / dn_set_wind), nor the actuator state of dn_enable_actuator (+ dn_get_actuator /
- * dn_set_actuator). */
+ * dn_set_actuator), nor the sensor state of dn_enable_sensor (+ dn_get_sensor / dn_set_sensor). */
 typedef struct dn_env_state {
     float pos[3], quat[4], vel[3], ang_v[3];    /* Bullet base state, BaseAviary.py:596-598 (quat = x,y,z,w) */
     float prev_vel[3], prev_ang_v[3];           /* PBDroneEnv.prev_vel / prev_ang_v */
@@ -392,7 +392,7 @@ int32_t dn_set_launch_events(dn_env *env, void *start_event, void *stop_event);
 
 /* Bytes of HBM the persistent state of `num_envs` drones occupies (capacity planning).  The body scales of dn_enable_dynamics are a
  * separate allocation of 16 bytes per drone and are not included, nor is the wind of dn_enable_wind (32 bytes per drone), nor the
- * actuator state of dn_enable_actuator (152 bytes per drone). */
+ * actuator state of dn_enable_actuator (152 bytes per drone), nor the sensor state of dn_enable_sensor (1092 bytes per drone). */
 int64_t dn_state_bytes(int64_t num_envs, int32_t normalize_obs);
 
 /* Per-drone dynamics randomisation (sim-to-real).  Each drone carries four float32 scale factors relative to the nominal cf2x body:
@@ -511,6 +511,58 @@ int32_t dn_set_actuator(dn_env *env, const int32_t *latency, const float *coeff,
 int32_t dn_get_actuator(dn_env *env, int32_t *latency, float *coeff, float *rpm, float *history, void *stream);
 /* 1: actuator enabled, *out = the configuration last given to dn_enable_actuator; 0: not enabled (*out untouched); < 0: error. */
 int32_t dn_get_actuator_config(const dn_env *env, dn_actuator_config *out);
+
+/* Per-drone sensor model (sim-to-real): observation latency and a per-episode constant bias (a state-estimator offset) between the state
+ * and the observation row the policy sees.  Let o_k be the observation row as produced BEFORE the normaliser -- the observation columns plus
+ * the white noise of obs_noise_sigma -- after the episode's k-th control step (k = dn_env_state.steps once the step is over; o_0 is the reset
+ * observation, noise stream 5; o_k for k >= 1 the step observation, noise stream 1; the noise stays keyed by the vector step at which the row
+ * was MEASURED).  Every drone has an integer latency d in [0, DN_MAX_LATENCY] control steps and a bias row b[13] (float32, observation-column
+ * units).  The row handed to the normaliser (normalize_obs), or written to the output without it, after the episode's k-th step is
+ *       y_k = float32(o_{k - min(d, k)} + b)          one float32 add per column, unfused
+ *   - a fresh episode's pipeline holds that episode's own reset observation: rows of the previous episode never leak into the next one;
+ *   - terminal_observation of a step that ends an episode is y_k of that step;
+ *   - the reset observation written for a finished drone, and by dn_reset, is float32(o_0 + b_new): the NEW episode's bias, no delay;
+ *   - with normalize_obs the running statistics are updated with the delivered rows, once each, exactly where they are updated today;
+ *   - nothing feeds back: state, reward, done, truncated, found_targets and the Monitor outputs are bit for bit those of the same env
+ *     without the sensor model.
+ *   draws:   resample = 1: every episode start (dn_reset and every in-kernel auto-reset) draws from FOUR Philox4x32-10 calls keyed (seed;
+ *            global drone id, the vector step the episode starts on, streams 18, 19, 20, 21; streams 0-9 and 11-17 belong to the other
+ *            features).  Value c of the call on stream 18 + q is u_m = (r_c + 0.5) / 2^32 in float64 with m = 4 q + c:
+ *            b_j = float32(bias_amp[j] (2 u_j - 1)) in float64 for the 13 columns, d = latency lo + floor((hi - lo + 1) u_13) clamped to
+ *            hi (u_14, u_15 unused).  Sharding does not move the draws.  resample = 0: d and b are what dn_set_sensor last wrote (0 and 0
+ *            after the first enable).
+ *   off:     with resample = 1, latency = [0, 0] switches the delay off (no history traffic) and all-zero bias_amp switches the add off
+ *            (-0.0f + 0.0f would flip a sign bit); with both off the kernels take the path of an env without the sensor model.  With
+ *            resample = 0 the values are the caller's and both are always applied.  The history is maintained only while the delay is on.
+ *   units:   bias_amp is in observation-column units: metres / aviary extent for columns 0-2, radians / pi for 3-5, (m/s) / 3 for 6-8,
+ *            the unit angular-velocity columns 9-11 as they are, metres / max_target_dist for 12.
+ *   memory:  1092 bytes per drone in one allocation of its own: a ring of 16 slots x 64 bytes (the pre-bias row of each of the last 16
+ *            vector steps, stored [slot][4 quads of 16 bytes][N], slot = (vector step + offset) mod 16), the bias row (64 bytes, [4][N])
+ *            and d.  dn_set_step_count adjusts the offset so that rows already stored keep their meaning; a launch captured in a hipGraph
+ *            bakes the offset in, so re-capture after dn_set_step_count.
+ * K steps in one launch equal K single steps bit for bit, history included.  A checkpoint is dn_get_state + dn_get_sensor +
+ * dn_get_step_count (plus the other features' getters); restore the step counter before dn_set_sensor's history.
+ * The sensor model lives in the one-wave option kernels: enabling forces dn_get_kernel_waves(env, 0 / 1) == 1.  dn_step_sampled,
+ * dn_step_squashed, dn_mlp_step_sampled and dn_eval_kinematics refuse an env with the sensor enabled (DN_ERR_INVALID_ARGUMENT).
+ * Layout: 4-byte members only, no padding: latency at 0, bias_amp at 8, resample at 60, reserved at 64; 68 bytes. */
+typedef struct dn_sensor_config {
+    int32_t latency[2];   /* latency range [lo, hi], control steps: 0 <= lo <= hi <= DN_MAX_LATENCY */
+    float bias_amp[13];   /* bias amplitude per observation column, column units: finite, >= 0; b_j is uniform in [-amp_j, amp_j] */
+    int32_t resample;     /* 1: draw d and b at every episode start; 0: keep dn_set_sensor's */
+    int32_t reserved;     /* must be 0 */
+} dn_sensor_config;
+/* Validates the configuration and enables the feature.  The first call allocates 1092 bytes per drone (outside dn_state_bytes) and sets
+ * d = 0, b = 0 and an all-zero history; a later call changes the configuration and keeps the current values.  Synchronises the device. */
+int32_t dn_enable_sensor(dn_env *env, const dn_sensor_config *cfg);
+/* Device buffers, read / written on `stream`; NULL = leave (set) / skip (get): latency int32[N] (d), bias float[N][13] (b),
+ * history float[N][9][13] with history[i][j] = the pre-bias row o_{k - j} of drone i, k = its dn_env_state.steps, in this LOGICAL order
+ * whatever the device layout (the calls convert, reading the step counter on the device).  Entries with k - j < 0 are ignored on set
+ * and unspecified on get.  DN_ERR_BAD_STATE if the sensor is not enabled.  dn_set_sensor does not validate the values (the caller's device
+ * buffers are not read on the host): d must lie in [0, DN_MAX_LATENCY] (the kernels clamp it), every other value finite. */
+int32_t dn_set_sensor(dn_env *env, const int32_t *latency, const float *bias, const float *history, void *stream);
+int32_t dn_get_sensor(dn_env *env, int32_t *latency, float *bias, float *history, void *stream);
+/* 1: sensor enabled, *out = the configuration last given to dn_enable_sensor; 0: not enabled (*out untouched); < 0: error. */
+int32_t dn_get_sensor_config(const dn_env *env, dn_sensor_config *out);
 
 #ifdef __cplusplus
 }

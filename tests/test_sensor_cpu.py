@@ -1,0 +1,109 @@
+"""Per-drone sensor model (include/dronenav.h dn_enable_sensor) without a GPU: the C struct against its ctypes twin, the exported
+symbols, the host-side validation of SensorModel and the loud failure on a NULL env."""
+import ctypes as C
+import dataclasses
+import os
+import subprocess
+import tempfile
+
+import pytest
+
+NEW_SYMBOLS = ("dn_enable_sensor", "dn_set_sensor", "dn_get_sensor", "dn_get_sensor_config")
+FIELDS = ("latency", "bias_amp", "resample", "reserved")
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import drl_dronenavigation_amd as p
+    return p
+
+
+def test_sensor_config_layout_matches_header(pkg):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    offs = ", ".join(f"offsetof(dn_sensor_config, {f})" for f in FIELDS)
+    prog = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "dronenav.h"
+int main(void) {
+    printf("%zu %zu %zu %zu %zu %d %d %d %zu %zu\n", sizeof(dn_sensor_config), ''' + offs + r''', DN_ABI_VERSION, DN_MAX_LATENCY, DN_OBS_DIM,
+           sizeof(dn_config), sizeof(dn_env_state));
+    return 0;
+}
+'''
+    with tempfile.TemporaryDirectory() as td:
+        src, exe = os.path.join(td, "sens.c"), os.path.join(td, "sens")
+        with open(src, "w") as f:
+            f.write(prog)
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), src, "-o", exe])
+        got = [int(v) for v in subprocess.check_output([exe]).split()]
+    S = pkg._capi.DnSensorConfig
+    from drl_dronenavigation_amd import sensor
+    assert got == [C.sizeof(S)] + [getattr(S, f).offset for f in FIELDS] + [pkg._capi.ABI_VERSION, sensor.MAX_LATENCY, sensor.OBS_DIM,
+                                                                           C.sizeof(pkg._capi.DnConfig), C.sizeof(pkg._capi.DnEnvState)], got
+    assert [getattr(S, f).offset for f in FIELDS] == [0, 8, 60, 64] and C.sizeof(S) == 68       # the layout the header documents
+    assert pkg._capi.ABI_VERSION == 9 and sensor.MAX_LATENCY == 8 and sensor.OBS_DIM == 13      # additive: the ABI version stays
+
+
+def test_sensor_symbols_are_exported_and_bound(pkg):
+    lib = pkg._capi.load()
+    P = pkg._capi.PROTOTYPES
+    vp, i32 = C.c_void_p, C.c_int32
+    cfg_p = C.POINTER(pkg._capi.DnSensorConfig)
+    want = {"dn_enable_sensor": (i32, [vp, cfg_p]), "dn_set_sensor": (i32, [vp] * 5), "dn_get_sensor": (i32, [vp] * 5),
+            "dn_get_sensor_config": (i32, [vp, cfg_p])}
+    for name in NEW_SYMBOLS:
+        assert name in P, name
+        assert (P[name][0], list(P[name][1])) == want[name], name
+        fn = getattr(lib, name)
+        assert fn.restype == want[name][0] and list(fn.argtypes) == want[name][1], name
+    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg._capi.library_path()]).decode()
+    for name in NEW_SYMBOLS:
+        assert f" T {name}\n" in out, name
+
+
+NAN, INF = float("nan"), float("inf")
+
+
+@pytest.mark.parametrize("bad", [
+    dict(latency=(-1, 2)), dict(latency=(0, 9)), dict(latency=(9, 9)), dict(latency=(5, 3)),              # negative, > 8, lo > hi
+    dict(latency=(0.5, 2)), dict(latency=(0,)), dict(latency=3), dict(latency=(0, 1, 2)), dict(latency=(NAN, 2)),
+    dict(bias=-0.01), dict(bias=NAN), dict(bias=INF), dict(bias=True), dict(bias="0.1"),                  # scalar: negative, non-finite, type
+    dict(bias=(0.0,) * 12), dict(bias=(0.0,) * 14), dict(bias=()),                                        # arity
+    dict(bias=(0.0,) * 12 + (-1e-9,)), dict(bias=(NAN,) + (0.0,) * 12), dict(bias=(0.0,) * 6 + (INF,) + (0.0,) * 6),
+])
+def test_sensor_model_rejects_bad_values(pkg, bad):
+    with pytest.raises(ValueError):
+        pkg.SensorModel(**bad)
+
+
+def test_sensor_model_defaults_broadcast_and_c_image(pkg):
+    s = pkg.SensorModel()
+    assert (s.latency, s.bias, s.resample) == ((0, 0), (0.0,) * 13, True)
+    assert pkg.SensorModel(bias=0.25).bias == (0.25,) * 13 and pkg.SensorModel(bias=1).bias == (1.0,) * 13
+    amps = tuple(0.01 * (j + 1) for j in range(13))
+    d = pkg.SensorModel(latency=(1, 8), bias=amps, resample=False)
+    c = d.to_c()
+    assert list(c.latency) == [1, 8] and list(c.bias_amp) == pytest.approx(list(amps)) and c.resample == 0 and c.reserved == 0
+    back = pkg.SensorModel.from_c(c)
+    assert bytes(back.to_c()) == bytes(c)
+    assert back.latency == (1, 8) and back.resample is False and len(back.bias) == 13
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        d.latency = (0, 0)
+    assert "SensorModel" in pkg.__all__
+
+
+def test_enable_sensor_on_null_env_fails_loudly(pkg):
+    lib = pkg._capi.load()
+    INVALID = -1                            # DN_ERR_INVALID_ARGUMENT
+    assert pkg._capi.STATUS_NAMES[INVALID] == "DN_ERR_INVALID_ARGUMENT"
+    cfg = pkg.SensorModel(latency=(0, 8), bias=0.01).to_c()
+    rc = lib.dn_enable_sensor(None, C.byref(cfg))
+    assert rc == INVALID
+    with pytest.raises(pkg.DroneNavError):
+        pkg._capi.check(rc)
+    assert b"env" in lib.dn_last_error()
+    out = pkg._capi.DnSensorConfig()
+    assert lib.dn_get_sensor_config(None, C.byref(out)) == INVALID
+    assert lib.dn_set_sensor(None, None, None, None, None) == INVALID
+    assert lib.dn_get_sensor(None, None, None, None, None) == INVALID
