@@ -92,13 +92,12 @@ struct dn_env {
     int waves_fused = 2;        // kernel shape of dn_step_many (k > 1), see dn_launch_step_many
     int waves_single = 1;       // kernel shape of dn_step (k == 1)
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // dn_set_launch_events: attached to the next step kernel's dispatch, then cleared
-    DnDyn dyn = {};             // dn_enable_dynamics: dyn.dyn is an allocation of its own (not in the arena: dn_state_bytes is unchanged)
+    // dn_enable_*: each model's arrays are one allocation of its own, outside the arena (dn_state_bytes is unchanged): 16 bytes per drone
+    // for the dynamics, 32 for the wind, 152 for the actuator, 1092 for the sensor model.  MODELS below names the pointer that owns each.
+    DnModels m = {};
     dn_dynamics_config dyn_cfg = {};
-    DnWind wind = {};           // dn_enable_wind: wind.mean / wind.gust are one allocation of its own (2 float4 per drone, outside the arena)
     dn_wind_config wind_cfg = {};
-    DnAct act = {};             // dn_enable_actuator: act.hist / rpm / coeff / lat are one allocation of its own (152 bytes per drone, outside the arena)
     dn_actuator_config act_cfg = {};
-    DnSens sens = {};           // dn_enable_sensor: sens.ring / bias / lat are one allocation of its own (1092 bytes per drone, outside the arena)
     dn_sensor_config sens_cfg = {};
 };
 
@@ -304,6 +303,84 @@ int32_t init_state(dn_env *e, hipStream_t s)
     if (e->p.pid_mode) DN_HIP(dn_launch_filld(e->p.st.pid, 0.0, 9 * n, s));                       // DSLPIDControl.reset(), DSLPIDControl.py:63-76
     DN_HIP(hipMemsetAsync(e->p.st.stats, 0, (size_t)e->blocks * sizeof(DnStatSlot), s));
     return DN_OK;
+}
+
+// The per-drone models, shallowest first (the order of the kernels' argument chain, dn_kernels.hip SensArg).  dn_destroy and the entry
+// points that carry none of them walk this table; a new model is one more row.
+struct ModelRow {
+    float4 *&(*slot)(DnModels &);   // the pointer that owns the model's allocation: non-null = the model is on
+    const char *phrase, *enable;    // how a refusal names the model, and the entry point that turns it on
+    const char *replay;             // what dn_eval_kinematics does that the model would falsify
+};
+const ModelRow MODELS[] = {
+    {[](DnModels &m) -> float4 *& { return m.dyn.dyn; }, "the randomised dynamics", "dn_enable_dynamics", "replays a given nominal-body transition"},
+    {[](DnModels &m) -> float4 *& { return m.wind.mean; }, "the wind", "dn_enable_wind", "replays a given still-air transition"},
+    {[](DnModels &m) -> float4 *& { return m.act.hist; }, "the actuator model", "dn_enable_actuator", "replays a given transition"},
+    {[](DnModels &m) -> float4 *& { return m.sens.ring; }, "the sensor model", "dn_enable_sensor", "reports the observation of the given transition"},
+};
+
+// DN_OK, or the refusal of entry point `who`, whose kernels carry no model, for the first model that is on.  `instead` names the calls
+// that do carry it; nullptr = dn_eval_kinematics, which has a reason per model and no alternative.
+int32_t refuse_models(dn_env *env, const char *who, const char *instead)
+{
+    for (const ModelRow &r : MODELS) {
+        if (!r.slot(env->m)) continue;
+        if (!instead) return fail(DN_ERR_INVALID_ARGUMENT, "%s %s: refused with %s (%s)", who, r.replay, r.phrase, r.enable);
+        return fail(DN_ERR_INVALID_ARGUMENT, "%s does not carry %s (%s); %s", who, r.phrase, r.enable, instead);
+    }
+    return DN_OK;
+}
+
+// The DnStepIO of every step-family entry point, every field set.  Without a sampler (mean, act_out and logp_out null) the kernels read
+// `actions`; dn_mlp_step_sampled draws from the mean its policy kernel holds in registers, so it passes act_out / logp_out without `mean`.
+DnStepIO make_io(const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets, float *terminal_obs,
+                 float *ep_return, int32_t *ep_length, uint64_t *done_mask, const float *mean = nullptr, float *act_out = nullptr,
+                 float *logp_out = nullptr, const float *log_std = nullptr, uint64_t seed = 0, int32_t deterministic = 0, int squash = 0)
+{
+    DnStepIO io;
+    io.actions = actions; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
+    io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
+    io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
+    io.mean = mean; io.act_out = act_out; io.logp_out = logp_out;
+    for (int j = 0; j < 4; ++j) io.log_std[j] = log_std ? log_std[j] : 0.0f;
+    io.sample_seed = seed; io.sample_deterministic = deterministic != 0; io.sample_squash = squash;
+    return io;
+}
+
+// The checks every dn_*_config shares.
+int32_t check_resample_reserved(int32_t resample, int32_t reserved)
+{
+    if (resample != 0 && resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", resample);
+    if (reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", reserved);
+    return DN_OK;
+}
+
+// The tail of every dn_enable_* once its configuration is valid: on the first call, the model's allocation (`bytes`, handed to
+// init(float4 *) to fill on the null stream, freed again if that fails); on every call, the kernel shape -- the models live in the
+// one-wave option kernels only (as the random spawn does).  `what` names the allocation in messages.
+template <typename Init>
+int32_t model_storage(dn_env *env, float4 *&slot, size_t bytes, const char *what, Init init)
+{
+    if (!slot) {
+        float4 *d = nullptr;
+        const hipError_t he = hipMalloc(&d, bytes);
+        if (he != hipSuccess) return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for %s failed: %s", bytes, what, hipGetErrorString(he));
+        if (!init(d) || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(d);
+            return fail(DN_ERR_HIP, "initialising %s failed", what);
+        }
+        slot = d;
+    }
+    env->waves_fused = env->waves_single = 1;
+    return DN_OK;
+}
+
+// dn_set_* (set = true) and dn_get_* of a model share one body: this is its copy, in the direction asked for.  user == nullptr = leave.
+hipError_t copy_rows(bool set, void *model, const void *user, size_t bytes, hipStream_t s)
+{
+    if (!user) return hipSuccess;
+    return set ? hipMemcpyAsync(model, user, bytes, hipMemcpyDeviceToDevice, s)
+               : hipMemcpyAsync(const_cast<void *>(user), model, bytes, hipMemcpyDeviceToDevice, s);
 }
 
 }  // namespace
@@ -550,23 +627,16 @@ int32_t dn_destroy(dn_env *env)
 {
     if (!env) return DN_OK;
     hipError_t he = hipSuccess;
-    if (env->arena || env->dyn.dyn || env->wind.mean || env->act.hist || env->sens.ring) (void)hipSetDevice(env->cfg.device_id);
-    if (env->arena) he = hipFree(env->arena);
-    if (env->dyn.dyn) {
-        const hipError_t hd = hipFree(env->dyn.dyn);
-        if (he == hipSuccess) he = hd;
-    }
-    if (env->wind.mean) {
-        const hipError_t hw = hipFree(env->wind.mean);
-        if (he == hipSuccess) he = hw;
-    }
-    if (env->act.hist) {
-        const hipError_t ha = hipFree(env->act.hist);
-        if (he == hipSuccess) he = ha;
-    }
-    if (env->sens.ring) {
-        const hipError_t hs = hipFree(env->sens.ring);
-        if (he == hipSuccess) he = hs;
+    void *owned[1 + sizeof MODELS / sizeof MODELS[0]] = {env->arena};
+    int k = 1;
+    for (const ModelRow &r : MODELS) owned[k++] = r.slot(env->m);
+    bool device_set = false;
+    for (void *ptr : owned) {               // the first failure is the one reported; the rest are still freed
+        if (!ptr) continue;
+        if (!device_set) (void)hipSetDevice(env->cfg.device_id);
+        device_set = true;
+        const hipError_t h = hipFree(ptr);
+        if (he == hipSuccess) he = h;
     }
     delete env;
     if (he != hipSuccess) return fail(DN_ERR_HIP, "hipFree failed: %s", hipGetErrorString(he));
@@ -602,7 +672,7 @@ int32_t dn_reset(dn_env *env, float *obs, void *stream)
 {
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     if (!obs) return fail(DN_ERR_INVALID_ARGUMENT, "obs is NULL");
-    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->dyn, &env->wind, &env->act, &env->sens));
+    DN_HIP(dn_launch_reset(env->p, obs, env->cfg.compute_f32 != 0, (hipStream_t)stream, &env->m));
     return DN_OK;
 }
 
@@ -617,12 +687,8 @@ int32_t dn_step(dn_env *env, const float *actions, float *obs, float *reward, ui
     if (((uintptr_t)actions & 15u) || ((uintptr_t)obs & 15u))
         return fail(DN_ERR_INVALID_ARGUMENT, "actions and obs must be 16-byte aligned");
     DN_REFUSE_ARMED_CAPTURE(stream);
-    DnStepIO io;
-    io.actions = actions; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
-    io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
-    io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
-    io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->dyn, &env->wind, &env->act, &env->sens));
+    const DnStepIO io = make_io(actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask);
+    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->m));
     return DN_OK;
 }
 
@@ -640,21 +706,9 @@ int32_t dn_step_sampled(dn_env *env, const float *mean, const float *log_std, ui
     if (env->cfg.clip_rew || env->cfg.norm_rew || env->cfg.physics != 0 || env->cfg.action_type != 0 || env->cfg.random_spawn || env->cfg.zero_damping)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled is built for the configuration without reward wrappers / extra physics terms / RPM actions / random spawn / zero damping; "
                                              "use dn_policy_sample + dn_step there");
-    if (env->dyn.dyn)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_policy_sample + dn_step there");
-    if (env->wind.mean)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the wind (dn_enable_wind); use dn_policy_sample + dn_step there");
-    if (env->act.hist)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the actuator model (dn_enable_actuator); use dn_policy_sample + dn_step there");
-    if (env->sens.ring)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled does not carry the sensor model (dn_enable_sensor); use dn_policy_sample + dn_step there");
-    DnStepIO io;
-    io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
-    io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
-    io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
-    io.mean = mean; io.act_out = actions_out; io.logp_out = log_prob_out;
-    for (int j = 0; j < 4; ++j) io.log_std[j] = log_std[j];
-    io.sample_seed = seed; io.sample_deterministic = deterministic != 0; io.sample_squash = 0;
+    if (const int32_t rc = refuse_models(env, "dn_step_sampled", "use dn_policy_sample + dn_step there")) return rc;
+    const DnStepIO io = make_io(nullptr, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask,
+                                mean, actions_out, log_prob_out, log_std, seed, deterministic, 0);
     // the sampling lives in the single-step kernels (one wave, or three waves cut by dependency)
     DN_REFUSE_ARMED_CAPTURE(stream);
     DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single == 3 ? 3 : 1, (hipStream_t)stream));
@@ -674,21 +728,9 @@ int32_t dn_step_squashed(dn_env *env, const float *mu_log_std, uint64_t seed, in
     if (env->cfg.clip_rew || env->cfg.norm_rew || env->cfg.physics != 0 || env->cfg.action_type != 0 || env->cfg.random_spawn || env->cfg.zero_damping)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed is built for the configuration without reward wrappers / extra physics terms / RPM actions / random spawn / zero damping; "
                                              "use dn_squashed_sample + dn_step there");
-    if (env->dyn.dyn)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the randomised dynamics (dn_enable_dynamics); use dn_squashed_sample + dn_step there");
-    if (env->wind.mean)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the wind (dn_enable_wind); use dn_squashed_sample + dn_step there");
-    if (env->act.hist)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the actuator model (dn_enable_actuator); use dn_squashed_sample + dn_step there");
-    if (env->sens.ring)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed does not carry the sensor model (dn_enable_sensor); use dn_squashed_sample + dn_step there");
-    DnStepIO io;
-    io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
-    io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
-    io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
-    io.mean = mu_log_std; io.act_out = actions_out; io.logp_out = log_prob_out;
-    for (int j = 0; j < 4; ++j) io.log_std[j] = 0.0f;
-    io.sample_seed = seed; io.sample_deterministic = deterministic != 0; io.sample_squash = 1;
+    if (const int32_t rc = refuse_models(env, "dn_step_squashed", "use dn_squashed_sample + dn_step there")) return rc;
+    const DnStepIO io = make_io(nullptr, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask,
+                                mu_log_std, actions_out, log_prob_out, nullptr, seed, deterministic, 1);     // the rows carry log_std
     DN_REFUSE_ARMED_CAPTURE(stream);
     DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single == 3 ? 3 : 1, (hipStream_t)stream));
     return DN_OK;
@@ -707,14 +749,7 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
     if (num_nets < 1 || num_nets > 2) return fail(DN_ERR_INVALID_ARGUMENT, "num_nets must be 1 (actor) or 2 (actor, critic)");
     if (obs_dim < 1 || obs_dim > 16) return fail(DN_ERR_INVALID_ARGUMENT, "obs_dim must be in 1..16 (got %d)", obs_dim);
     if (((uintptr_t)actions_out & 15u) || ((uintptr_t)obs & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "actions_out and obs must be 16-byte aligned");
-    if (env->dyn.dyn)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the randomised dynamics (dn_enable_dynamics); use dn_mlp_forward + dn_policy_sample + dn_step");
-    if (env->wind.mean)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the wind (dn_enable_wind); use dn_mlp_forward + dn_policy_sample + dn_step");
-    if (env->act.hist)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the actuator model (dn_enable_actuator); use dn_mlp_forward + dn_policy_sample + dn_step");
-    if (env->sens.ring)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled does not carry the sensor model (dn_enable_sensor); use dn_mlp_forward + dn_policy_sample + dn_step");
+    if (const int32_t rc = refuse_models(env, "dn_mlp_step_sampled", "use dn_mlp_forward + dn_policy_sample + dn_step")) return rc;
     const dn_config &c = env->cfg;
     for (int k = 0; k < num_nets; ++k) {
         const dn_mlp_net &n = nets[k];
@@ -747,13 +782,8 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
                                              "physics / ground contact on fleets that take the three-wave single step; use dn_mlp_forward + dn_step_sampled");
     const long long per_wg = nets[0].grade == 1 ? 64 : 128;
     if (c.num_envs % per_wg) return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled needs num_envs %% %lld == 0 (got %lld)", per_wg, (long long)c.num_envs);
-    DnStepIO io;
-    io.actions = nullptr; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
-    io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
-    io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
-    io.mean = nullptr; io.act_out = actions_out; io.logp_out = log_prob_out;
-    for (int j = 0; j < 4; ++j) io.log_std[j] = log_std[j];
-    io.sample_seed = seed; io.sample_deterministic = deterministic != 0; io.sample_squash = 0;
+    const DnStepIO io = make_io(nullptr, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask,
+                                nullptr, actions_out, log_prob_out, log_std, seed, deterministic, 0);
     DN_HIP(hipSetDevice(c.device_id));
     DN_HIP(dn_launch_mlp_step(env->p, io, nets, num_nets, policy_obs, obs_dim, (hipStream_t)stream));
     return DN_OK;
@@ -773,18 +803,8 @@ int32_t dn_eval_kinematics(dn_env *env, const double *kinematics, float *obs, fl
     if (c.act_noise_sigma > 0.0f || c.obs_noise_sigma > 0.0f || c.clip_rew || c.norm_rew || c.physics != 0 || c.action_type != 0 || c.random_spawn)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics is built for the reference configuration (no noise, no reward wrappers, "
                                              "Physics.PYB, ActionType.THRUST, fixed spawn)");
-    if (env->dyn.dyn)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given nominal-body transition: refused with the randomised dynamics (dn_enable_dynamics)");
-    if (env->wind.mean)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given still-air transition: refused with the wind (dn_enable_wind)");
-    if (env->act.hist)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics replays a given transition: refused with the actuator model (dn_enable_actuator)");
-    if (env->sens.ring)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics reports the observation of the given transition: refused with the sensor model (dn_enable_sensor)");
-    DnStepIO io;
-    memset(&io, 0, sizeof io);
-    io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated; io.found_targets = found_targets;
-    io.terminal_obs = terminal_obs; io.ep_return = ep_return; io.ep_length = ep_length;
+    if (const int32_t rc = refuse_models(env, "dn_eval_kinematics", nullptr)) return rc;
+    const DnStepIO io = make_io(nullptr, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, nullptr);
     DN_HIP(dn_launch_eval_kinematics(env->p, io, kinematics, c.compute_f32 != 0, (hipStream_t)stream));
     return DN_OK;
 }
@@ -807,13 +827,9 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
         return fail(DN_ERR_INVALID_ARGUMENT, "actions and obs must be 16-byte aligned");
     if (k > (1 << 30)) return fail(DN_ERR_INVALID_ARGUMENT, "k too large");
     // one fused launch: the state stays in registers for all k steps (dn_step_many_kernel)
-    DnStepIO io;
-    io.actions = actions; io.obs = obs; io.reward = reward; io.done = done; io.truncated = truncated;
-    io.found_targets = found_targets; io.terminal_obs = terminal_obs; io.ep_return = ep_return;
-    io.ep_length = ep_length; io.done_mask = (unsigned long long *)done_mask;
-    io.mean = nullptr; io.act_out = nullptr; io.logp_out = nullptr; io.sample_squash = 0;
+    const DnStepIO io = make_io(actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask);
     DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->dyn, &env->wind, &env->act, &env->sens));
+    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->m));
     return DN_OK;
 }
 
@@ -1041,48 +1057,35 @@ int32_t dn_enable_dynamics(dn_env *env, const dn_dynamics_config *cfg)
         if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo > 0.0f) || !(lo <= hi))
             return fail(DN_ERR_INVALID_ARGUMENT, "dynamics range %s = [%g, %g]: need finite 0 < lo <= hi", names[j], (double)lo, (double)hi);
     }
-    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (const int32_t rc = check_resample_reserved(cfg->resample, cfg->reserved)) return rc;
     DN_HIP(hipSetDevice(env->cfg.device_id));
-    if (!env->dyn.dyn) {                    // first call: the per-drone scales, all 1 (the nominal body) until a reset draws or dn_set_dynamics writes
-        const long long n = env->cfg.num_envs;
-        float4 *d = nullptr;
-        const hipError_t he = hipMalloc(&d, (size_t)n * sizeof(float4));
-        if (he != hipSuccess)
-            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the dynamics scales failed: %s", (size_t)n * sizeof(float4), hipGetErrorString(he));
-        if (dn_launch_fill4(d, make_float4(1.0f, 1.0f, 1.0f, 1.0f), n, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipFree(d);
-            return fail(DN_ERR_HIP, "initialising the dynamics scales failed");
-        }
-        env->dyn.dyn = d;
-    }
-    for (int j = 0; j < 4; ++j) { env->dyn.lo[j] = rng[j][0]; env->dyn.hi[j] = rng[j][1]; }
-    env->dyn.resample = cfg->resample;
+    const long long n = env->cfg.num_envs;
+    DnDyn &d = env->m.dyn;
+    // first call: the per-drone scales, all 1 (the nominal body) until a reset draws or dn_set_dynamics writes
+    if (const int32_t rc = model_storage(env, d.dyn, (size_t)n * sizeof(float4), "the dynamics scales", [&](float4 *mem) {
+            return dn_launch_fill4(mem, make_float4(1.0f, 1.0f, 1.0f, 1.0f), n, nullptr) == hipSuccess;
+        }))
+        return rc;
+    for (int j = 0; j < 4; ++j) { d.lo[j] = rng[j][0]; d.hi[j] = rng[j][1]; }
+    d.resample = cfg->resample;
     env->dyn_cfg = *cfg;
-    env->waves_fused = env->waves_single = 1;     // the scales live in the one-wave option kernels only (as the random spawn does)
     return DN_OK;
 }
 
-int32_t dn_set_dynamics(dn_env *env, const float *scales, void *stream)
+static int32_t dynamics_rows(dn_env *env, bool set, const float *scales, void *stream)
 {
     if (!env || !scales) return fail(DN_ERR_INVALID_ARGUMENT, "env and scales are required");
-    if (!env->dyn.dyn) return fail(DN_ERR_BAD_STATE, "dynamics randomisation is not enabled (dn_enable_dynamics)");
-    DN_HIP(hipMemcpyAsync(env->dyn.dyn, scales, (size_t)env->cfg.num_envs * sizeof(float4), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (!env->m.dyn.dyn) return fail(DN_ERR_BAD_STATE, "dynamics randomisation is not enabled (dn_enable_dynamics)");
+    DN_HIP(copy_rows(set, env->m.dyn.dyn, scales, (size_t)env->cfg.num_envs * sizeof(float4), (hipStream_t)stream));
     return DN_OK;
 }
-
-int32_t dn_get_dynamics(dn_env *env, float *scales, void *stream)
-{
-    if (!env || !scales) return fail(DN_ERR_INVALID_ARGUMENT, "env and scales are required");
-    if (!env->dyn.dyn) return fail(DN_ERR_BAD_STATE, "dynamics randomisation is not enabled (dn_enable_dynamics)");
-    DN_HIP(hipMemcpyAsync(scales, env->dyn.dyn, (size_t)env->cfg.num_envs * sizeof(float4), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return DN_OK;
-}
+int32_t dn_set_dynamics(dn_env *env, const float *scales, void *stream) { return dynamics_rows(env, true, scales, stream); }
+int32_t dn_get_dynamics(dn_env *env, float *scales, void *stream) { return dynamics_rows(env, false, scales, stream); }
 
 int32_t dn_get_dynamics_config(const dn_env *env, dn_dynamics_config *out)
 {
     if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
-    if (!env->dyn.dyn) return 0;
+    if (!env->m.dyn.dyn) return 0;
     *out = env->dyn_cfg;
     return 1;
 }
@@ -1106,23 +1109,16 @@ int32_t dn_enable_wind(dn_env *env, const dn_wind_config *cfg)
     }
     if (!std::isfinite(cfg->gust_tau) || !(cfg->gust_tau > 0.0f))
         return fail(DN_ERR_INVALID_ARGUMENT, "gust_tau = %g: need finite > 0", (double)cfg->gust_tau);
-    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (const int32_t rc = check_resample_reserved(cfg->resample, cfg->reserved)) return rc;
     DN_HIP(hipSetDevice(env->cfg.device_id));
-    if (!env->wind.mean) {                  // first call: wbar and g of every drone, 0 (still air) until an episode start draws or dn_set_wind writes
-        const long long n = env->cfg.num_envs;
-        float4 *d = nullptr;
-        const hipError_t he = hipMalloc(&d, (size_t)(2 * n) * sizeof(float4));
-        if (he != hipSuccess)
-            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the wind failed: %s", (size_t)(2 * n) * sizeof(float4), hipGetErrorString(he));
-        if (dn_launch_fill4(d, make_float4(0.0f, 0.0f, 0.0f, 0.0f), 2 * n, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipFree(d);
-            return fail(DN_ERR_HIP, "initialising the wind failed");
-        }
-        env->wind.mean = d;
-        env->wind.gust = d + n;
-    }
-    DnWind &w = env->wind;
+    const long long n = env->cfg.num_envs;
+    DnWind &w = env->m.wind;
+    // first call: wbar and g of every drone, 0 (still air) until an episode start draws or dn_set_wind writes
+    if (const int32_t rc = model_storage(env, w.mean, (size_t)(2 * n) * sizeof(float4), "the wind", [&](float4 *mem) {
+            return dn_launch_fill4(mem, make_float4(0.0f, 0.0f, 0.0f, 0.0f), 2 * n, nullptr) == hipSuccess;
+        }))
+        return rc;
+    w.gust = w.mean + n;
     for (int j = 0; j < 2; ++j) {
         w.speed[j] = cfg->speed[j]; w.azimuth[j] = cfg->azimuth[j]; w.vertical[j] = cfg->vertical[j];
         w.sigma[j] = cfg->gust_sigma[j]; w.k[j] = cfg->coeff[j];
@@ -1135,34 +1131,25 @@ int32_t dn_enable_wind(dn_env *env, const dn_wind_config *cfg)
     w.resample = cfg->resample;
     w.gust_on = cfg->gust_sigma[0] > 0.0f || cfg->gust_sigma[1] > 0.0f;
     env->wind_cfg = *cfg;
-    env->waves_fused = env->waves_single = 1;     // the wind lives in the one-wave option kernels only
     return DN_OK;
 }
 
-int32_t dn_set_wind(dn_env *env, const float *mean, const float *gust, void *stream)
+static int32_t wind_rows(dn_env *env, bool set, const float *mean, const float *gust, void *stream)
 {
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
-    if (!env->wind.mean) return fail(DN_ERR_BAD_STATE, "wind is not enabled (dn_enable_wind)");
+    if (!env->m.wind.mean) return fail(DN_ERR_BAD_STATE, "wind is not enabled (dn_enable_wind)");
     const size_t bytes = (size_t)env->cfg.num_envs * sizeof(float4);
-    if (mean) DN_HIP(hipMemcpyAsync(env->wind.mean, mean, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (gust) DN_HIP(hipMemcpyAsync(env->wind.gust, gust, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    DN_HIP(copy_rows(set, env->m.wind.mean, mean, bytes, (hipStream_t)stream));
+    DN_HIP(copy_rows(set, env->m.wind.gust, gust, bytes, (hipStream_t)stream));
     return DN_OK;
 }
-
-int32_t dn_get_wind(dn_env *env, float *mean, float *gust, void *stream)
-{
-    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
-    if (!env->wind.mean) return fail(DN_ERR_BAD_STATE, "wind is not enabled (dn_enable_wind)");
-    const size_t bytes = (size_t)env->cfg.num_envs * sizeof(float4);
-    if (mean) DN_HIP(hipMemcpyAsync(mean, env->wind.mean, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (gust) DN_HIP(hipMemcpyAsync(gust, env->wind.gust, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return DN_OK;
-}
+int32_t dn_set_wind(dn_env *env, const float *mean, const float *gust, void *stream) { return wind_rows(env, true, mean, gust, stream); }
+int32_t dn_get_wind(dn_env *env, float *mean, float *gust, void *stream) { return wind_rows(env, false, mean, gust, stream); }
 
 int32_t dn_get_wind_config(const dn_env *env, dn_wind_config *out)
 {
     if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
-    if (!env->wind.mean) return 0;
+    if (!env->m.wind.mean) return 0;
     *out = env->wind_cfg;
     return 1;
 }
@@ -1177,8 +1164,7 @@ int32_t dn_enable_actuator(dn_env *env, const dn_actuator_config *cfg)
         return fail(DN_ERR_INVALID_ARGUMENT, "actuator motor_tau = [%g, %g]: need finite 0 <= lo <= hi", (double)tlo, (double)thi);
     for (int j = 0; j < 4; ++j)
         if (!std::isfinite(cfg->fill[j])) return fail(DN_ERR_INVALID_ARGUMENT, "actuator fill[%d] = %g: need finite", j, (double)cfg->fill[j]);
-    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (const int32_t rc = check_resample_reserved(cfg->resample, cfg->reserved)) return rc;
     const int lag_on = thi > 0.0f;
     if (lag_on && env->cfg.action_type != 0)
         return fail(DN_ERR_INVALID_ARGUMENT, "the motor lag (motor_tau != [0, 0]) is built for ActionType.THRUST (action_type 0, got %d); "
@@ -1198,25 +1184,17 @@ int32_t dn_enable_actuator(dn_env *env, const dn_actuator_config *cfg)
         rpm_fill = make_float4(host[0], host[1], host[2], host[3]);
     }
     const float4 fill = make_float4(cfg->fill[0], cfg->fill[1], cfg->fill[2], cfg->fill[3]);
-    if (!env->act.hist) {                   // first call: d = 0, a = 0, r = rpm_fill, the history holds `fill`
-        const long long n = env->cfg.num_envs;
-        const size_t bytes = (size_t)n * (9 * sizeof(float4) + sizeof(float) + sizeof(int));
-        float4 *d = nullptr;
-        const hipError_t he = hipMalloc(&d, bytes);
-        if (he != hipSuccess)
-            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the actuator failed: %s", bytes, hipGetErrorString(he));
-        if (dn_launch_fill4(d, fill, 8 * n, nullptr) != hipSuccess || dn_launch_fill4(d + 8 * n, rpm_fill, n, nullptr) != hipSuccess
-            || hipMemsetAsync(d + 9 * n, 0, (size_t)n * (sizeof(float) + sizeof(int)), nullptr) != hipSuccess
-            || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipFree(d);
-            return fail(DN_ERR_HIP, "initialising the actuator failed");
-        }
-        env->act.hist = d;
-        env->act.rpm = d + 8 * n;
-        env->act.coeff = reinterpret_cast<float *>(d + 9 * n);
-        env->act.lat = reinterpret_cast<int *>(env->act.coeff + n);
-    }
-    DnAct &a = env->act;
+    const long long n = env->cfg.num_envs;
+    DnAct &a = env->m.act;
+    // first call: d = 0, a = 0, r = rpm_fill, the history holds `fill`
+    if (const int32_t rc = model_storage(env, a.hist, (size_t)n * (9 * sizeof(float4) + sizeof(float) + sizeof(int)), "the actuator", [&](float4 *mem) {
+            return dn_launch_fill4(mem, fill, 8 * n, nullptr) == hipSuccess && dn_launch_fill4(mem + 8 * n, rpm_fill, n, nullptr) == hipSuccess
+                   && hipMemsetAsync(mem + 9 * n, 0, (size_t)n * (sizeof(float) + sizeof(int)), nullptr) == hipSuccess;
+        }))
+        return rc;
+    a.rpm = a.hist + 8 * n;
+    a.coeff = reinterpret_cast<float *>(a.hist + 9 * n);
+    a.lat = reinterpret_cast<int *>(a.coeff + n);
     a.fill = fill;
     a.rpm_fill = rpm_fill;
     a.tau[0] = tlo; a.tau[1] = thi;
@@ -1224,40 +1202,35 @@ int32_t dn_enable_actuator(dn_env *env, const dn_actuator_config *cfg)
     a.resample = cfg->resample;
     a.lag_on = lag_on;
     env->act_cfg = *cfg;
-    env->waves_fused = env->waves_single = 1;     // the actuator lives in the one-wave option kernels only
     return DN_OK;
 }
 
+static int32_t actuator_rows(dn_env *env, bool set, const int32_t *latency, const float *coeff, const float *rpm, const float *history, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    const DnAct &a = env->m.act;
+    if (!a.hist) return fail(DN_ERR_BAD_STATE, "the actuator is not enabled (dn_enable_actuator)");
+    const size_t n = (size_t)env->cfg.num_envs;
+    hipStream_t s = (hipStream_t)stream;
+    DN_HIP(copy_rows(set, a.lat, latency, n * sizeof(int32_t), s));
+    DN_HIP(copy_rows(set, a.coeff, coeff, n * sizeof(float), s));
+    DN_HIP(copy_rows(set, a.rpm, rpm, n * sizeof(float4), s));
+    DN_HIP(copy_rows(set, a.hist, history, n * 8 * sizeof(float4), s));
+    return DN_OK;
+}
 int32_t dn_set_actuator(dn_env *env, const int32_t *latency, const float *coeff, const float *rpm, const float *history, void *stream)
 {
-    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
-    if (!env->act.hist) return fail(DN_ERR_BAD_STATE, "the actuator is not enabled (dn_enable_actuator)");
-    const size_t n = (size_t)env->cfg.num_envs;
-    hipStream_t s = (hipStream_t)stream;
-    if (latency) DN_HIP(hipMemcpyAsync(env->act.lat, latency, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (coeff) DN_HIP(hipMemcpyAsync(env->act.coeff, coeff, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rpm) DN_HIP(hipMemcpyAsync(env->act.rpm, rpm, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    if (history) DN_HIP(hipMemcpyAsync(env->act.hist, history, n * 8 * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    return DN_OK;
+    return actuator_rows(env, true, latency, coeff, rpm, history, stream);
 }
-
 int32_t dn_get_actuator(dn_env *env, int32_t *latency, float *coeff, float *rpm, float *history, void *stream)
 {
-    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
-    if (!env->act.hist) return fail(DN_ERR_BAD_STATE, "the actuator is not enabled (dn_enable_actuator)");
-    const size_t n = (size_t)env->cfg.num_envs;
-    hipStream_t s = (hipStream_t)stream;
-    if (latency) DN_HIP(hipMemcpyAsync(latency, env->act.lat, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (coeff) DN_HIP(hipMemcpyAsync(coeff, env->act.coeff, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rpm) DN_HIP(hipMemcpyAsync(rpm, env->act.rpm, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    if (history) DN_HIP(hipMemcpyAsync(history, env->act.hist, n * 8 * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    return DN_OK;
+    return actuator_rows(env, false, latency, coeff, rpm, history, stream);
 }
 
 int32_t dn_get_actuator_config(const dn_env *env, dn_actuator_config *out)
 {
     if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
-    if (!env->act.hist) return 0;
+    if (!env->m.act.hist) return 0;
     *out = env->act_cfg;
     return 1;
 }
@@ -1273,67 +1246,53 @@ int32_t dn_enable_sensor(dn_env *env, const dn_sensor_config *cfg)
             return fail(DN_ERR_INVALID_ARGUMENT, "sensor bias_amp[%d] = %g: need finite >= 0", j, (double)cfg->bias_amp[j]);
         any_amp = any_amp || cfg->bias_amp[j] > 0.0f;
     }
-    if (cfg->resample != 0 && cfg->resample != 1) return fail(DN_ERR_INVALID_ARGUMENT, "resample must be 0 or 1 (got %d)", cfg->resample);
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (const int32_t rc = check_resample_reserved(cfg->resample, cfg->reserved)) return rc;
     DN_HIP(hipSetDevice(env->cfg.device_id));
-    if (!env->sens.ring) {                  // first call: d = 0, b = 0, an all-zero ring
-        const long long n = env->cfg.num_envs;
-        const size_t quads = (size_t)n * (DN_SENS_SLOTS * 4 + 4);
-        const size_t bytes = quads * sizeof(float4) + (size_t)n * sizeof(int);
-        float4 *d = nullptr;
-        const hipError_t he = hipMalloc(&d, bytes);
-        if (he != hipSuccess)
-            return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for the sensor model failed: %s", bytes, hipGetErrorString(he));
-        if (hipMemsetAsync(d, 0, bytes, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipFree(d);
-            return fail(DN_ERR_HIP, "initialising the sensor model failed");
-        }
-        env->sens.ring = d;
-        env->sens.bias = d + (size_t)n * DN_SENS_SLOTS * 4;
-        env->sens.lat = reinterpret_cast<int *>(d + quads);
-        env->sens.base = 0;
-    } else {
-        DN_HIP(hipDeviceSynchronize());     // launches in flight carry the previous configuration
-    }
-    DnSens &s = env->sens;
+    const long long n = env->cfg.num_envs;
+    const size_t quads = (size_t)n * (DN_SENS_SLOTS * 4 + 4);
+    const size_t bytes = quads * sizeof(float4) + (size_t)n * sizeof(int);
+    DnSens &s = env->m.sens;
+    if (s.ring) DN_HIP(hipDeviceSynchronize());     // launches in flight carry the previous configuration
+    else s.base = 0;
+    // first call: d = 0, b = 0, an all-zero ring
+    if (const int32_t rc = model_storage(env, s.ring, bytes, "the sensor model", [&](float4 *mem) { return hipMemsetAsync(mem, 0, bytes, nullptr) == hipSuccess; }))
+        return rc;
+    s.bias = s.ring + (size_t)n * DN_SENS_SLOTS * 4;
+    s.lat = reinterpret_cast<int *>(s.ring + quads);
     for (int j = 0; j < DN_OBS_DIM; ++j) s.amp[j] = cfg->bias_amp[j];
     s.lat_lo = cfg->latency[0]; s.lat_hi = cfg->latency[1];
     s.resample = cfg->resample;
     s.lat_on = cfg->latency[1] > 0 || !cfg->resample;
     s.bias_on = any_amp || !cfg->resample;
     env->sens_cfg = *cfg;
-    env->waves_fused = env->waves_single = 1;     // the sensor model lives in the one-wave option kernels only
     return DN_OK;
 }
 
+static int32_t sensor_rows(dn_env *env, bool set, const int32_t *latency, const float *bias, const float *history, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    const DnSens &sn = env->m.sens;
+    if (!sn.ring) return fail(DN_ERR_BAD_STATE, "the sensor model is not enabled (dn_enable_sensor)");
+    hipStream_t s = (hipStream_t)stream;
+    DN_HIP(copy_rows(set, sn.lat, latency, (size_t)env->cfg.num_envs * sizeof(int32_t), s));
+    // the bias and the history are laid out for the kernels (quads, a ring): a kernel of their own, which takes the direction
+    if (bias) DN_HIP(dn_launch_sensor_bias(sn, env->cfg.num_envs, const_cast<float *>(bias), set, s));
+    if (history) DN_HIP(dn_launch_sensor_history(env->p, sn, const_cast<float *>(history), set, s));
+    return DN_OK;
+}
 int32_t dn_set_sensor(dn_env *env, const int32_t *latency, const float *bias, const float *history, void *stream)
 {
-    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
-    if (!env->sens.ring) return fail(DN_ERR_BAD_STATE, "the sensor model is not enabled (dn_enable_sensor)");
-    const size_t n = (size_t)env->cfg.num_envs;
-    hipStream_t s = (hipStream_t)stream;
-    if (latency) DN_HIP(hipMemcpyAsync(env->sens.lat, latency, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (bias) DN_HIP(dn_launch_sensor_bias(env->sens, env->cfg.num_envs, const_cast<float *>(bias), 1, s));
-    if (history) DN_HIP(dn_launch_sensor_history(env->p, env->sens, const_cast<float *>(history), 1, s));
-    return DN_OK;
+    return sensor_rows(env, true, latency, bias, history, stream);
 }
-
 int32_t dn_get_sensor(dn_env *env, int32_t *latency, float *bias, float *history, void *stream)
 {
-    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
-    if (!env->sens.ring) return fail(DN_ERR_BAD_STATE, "the sensor model is not enabled (dn_enable_sensor)");
-    const size_t n = (size_t)env->cfg.num_envs;
-    hipStream_t s = (hipStream_t)stream;
-    if (latency) DN_HIP(hipMemcpyAsync(latency, env->sens.lat, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (bias) DN_HIP(dn_launch_sensor_bias(env->sens, env->cfg.num_envs, bias, 0, s));
-    if (history) DN_HIP(dn_launch_sensor_history(env->p, env->sens, history, 0, s));
-    return DN_OK;
+    return sensor_rows(env, false, latency, bias, history, stream);
 }
 
 int32_t dn_get_sensor_config(const dn_env *env, dn_sensor_config *out)
 {
     if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
-    if (!env->sens.ring) return 0;
+    if (!env->m.sens.ring) return 0;
     *out = env->sens_cfg;
     return 1;
 }
@@ -1355,10 +1314,10 @@ int32_t dn_set_step_count(dn_env *env, uint64_t value)
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     DN_HIP(hipSetDevice(env->cfg.device_id));
     DN_HIP(hipDeviceSynchronize());
-    if (env->sens.ring) {                   // the sensor ring's slots are keyed by the vector step: the rows stay where they are, the offset moves
+    if (env->m.sens.ring) {                   // the sensor ring's slots are keyed by the vector step: the rows stay where they are, the offset moves
         unsigned long long old = 0;
         DN_HIP(hipMemcpy(&old, &env->p.st.stats[0].step_count, sizeof old, hipMemcpyDeviceToHost));
-        env->sens.base = (int)(((unsigned)env->sens.base + (unsigned)old - (unsigned)value) & (DN_SENS_SLOTS - 1u));
+        env->m.sens.base = (int)(((unsigned)env->m.sens.base + (unsigned)old - (unsigned)value) & (DN_SENS_SLOTS - 1u));
     }
     DN_HIP(dn_launch_set_step_count(env->p.st.stats, env->blocks, value, nullptr));
     DN_HIP(hipStreamSynchronize(nullptr));

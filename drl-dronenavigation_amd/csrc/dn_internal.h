@@ -177,6 +177,16 @@ struct DnSens {
     int base;               // host-side ring offset: dn_set_step_count moves it so that the slot of a vector step never changes
 };
 
+// The four per-drone models as the host carries them (dn_env, the launchers).  The kernels take them as before: the reset kernel as four
+// arguments, the option step kernels as the slice of the chain SensArg : ActArg : WindArg : DnDyn (dn_kernels.hip) their family reads.
+// A model that is off is its value-initialised struct (null pointers).
+struct DnModels {
+    DnDyn dyn;
+    DnWind wind;
+    DnAct act;
+    DnSens sens;
+};
+
 // dn_set_launch_events (ABI 8): the step kernel of the next dn_step / dn_step_many launch is dispatched with these two hipEvents attached to
 // its own dispatch packet (hipExtLaunchKernelGGL) -- they time the kernel itself, like a profiler's kernel trace, where a pair of
 // hipEventRecord around the call would also time the host's launch path and add two marker packets to the stream.  One shot: the
@@ -189,14 +199,11 @@ extern thread_local hipEvent_t dn_tl_ev_start, dn_tl_ev_stop;
     } while (0)
 
 int dn_norm_exact_compiled_in();      // 1 in libdronenav_exact.so (-DDN_NORM_EXACT=1: the normaliser's float64 output stage), else 0
-hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream,
-                               const DnDyn *dy = nullptr,     // dy->dyn != nullptr: the one-wave kernel with the scales, whatever `waves` says
-                               const DnWind *wd = nullptr,    // wd->mean != nullptr: the one-wave kernel with the wind (and dy's scales, if any)
-                               const DnAct *ac = nullptr,     // ac->hist != nullptr: the one-wave kernel with the actuator (and dy's / wd's, if any)
-                               const DnSens *sn = nullptr);   // sn->ring != nullptr: the one-wave kernel with the sensor model (and the other three, if any)
+// m: the per-drone models of the env.  With one of them on, the launch takes the one-wave option kernel of the deepest enabled family
+// (dynamics < wind < actuator < sensor; the shallower ones ride along, on or off), whatever `waves` says.
+hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnModels *m = nullptr);
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);   // dn_kernels_mw.hip
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy = nullptr, const DnWind *wd = nullptr,
-                           const DnAct *ac = nullptr, const DnSens *sn = nullptr);
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnModels *m = nullptr);
 // dn_set_sensor / dn_get_sensor: history[N][9][13] (logical order, history[i][j] = the row of j control steps ago) <-> the ring
 hipError_t dn_launch_sensor_history(const DnParams &p, const DnSens &sn, float *history, int to_ring, hipStream_t stream);
 // bias[N][13] <-> the quads

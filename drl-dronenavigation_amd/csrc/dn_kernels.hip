@@ -28,6 +28,7 @@
 #endif
 
 #include <float.h>
+#include <type_traits>
 
 #define DN_DEV __device__ __forceinline__
 
@@ -4447,84 +4448,77 @@ hipError_t dn_launch_filld(double *dst, double v, long long n, hipStream_t strea
 // dependent instruction stream and the other waves run on other SIMDs), one wave per 64 drones where there are enough
 // drones to fill every SIMD with whole steps.  All produce identical bits (test_kernel_shapes_are_bit_identical).
 //
-// This file is compiled twice (build.py).  DN_TU == 1 (with -mllvm -disable-machine-licm): everything except the
-// multi-wave kernels of the configuration without the normaliser; those live in DN_TU == 2 (dn_kernels_mw.hip, machine
-// LICM on).  Hoisting the float64 literals of the step body out of the K-step loop costs registers: it slows the
-// one-wave kernels that run several waves per SIMD (2 M drones fused: 72 -> 107 us per step) and speeds up the
-// kernels that are alone or nearly alone on their SIMD (32768 drones, three waves: 1.48 -> 1.37 us per step).
-#define DN_LAUNCH3(R, NORM, NOISE, ONE, XOPT)                                                                           \
-    do {                                                                                                                \
-        if (two_wave)                                                                                                   \
-            DN_KLAUNCH((dn_step_many_2w_kernel<R, NORM, NOISE, ONE, XOPT>), dim3(grid), dim3(2 * DN_BLOCK), 0, stream, p, io, k); \
-        else                                                                                                            \
-            DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, ONE, XOPT>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, DynArg<false>{}); \
-    } while (0)
-#define DN_LAUNCH2(R, NORM, NOISE, ONE)                                                                                 \
-    do {                                                                                                                \
-        if (rew) DN_LAUNCH3(R, NORM, NOISE, ONE, true); else DN_LAUNCH3(R, NORM, NOISE, ONE, false);                    \
-    } while (0)
-#define DN_LAUNCH(R, NORM, NOISE)                                                                                       \
-    do {                                                                                                                \
-        if (k == 1) DN_LAUNCH2(R, NORM, NOISE, true); else DN_LAUNCH2(R, NORM, NOISE, false);                           \
-    } while (0)
+// This file is compiled twice (build.py).  DN_TU == 1 (with -mllvm -disable-machine-licm): the single-step kernels, the
+// one-wave option kernels of the per-drone models, and the one- and two-wave kernels it launches with the normaliser on or
+// with one wave.  DN_TU == 2 (dn_kernels_mw.hip, machine LICM on): the multi-wave kernels -- two waves without the
+// normaliser, and the three-, four-, five-wave and eight-role fused kernels with or without it.  Hoisting the float64
+// literals of the step body out of the K-step loop costs registers: it slows the one-wave kernels that run several waves
+// per SIMD (2 M drones fused: 72 -> 107 us per step) and speeds up the kernels that are alone or nearly alone on their SIMD
+// (32768 drones, three waves: 1.48 -> 1.37 us per step).
+namespace {
+
+// Run-time bools to compile-time ones: calls f(std::bool_constant<b>{}...), the flags in the order given.  Every ladder of the
+// launchers goes through it, so a kernel template is instantiated for EVERY combination of the flags it is handed.
+template <typename F> void dn_bools(F &&f) { f(); }
+template <typename F, typename... Rest> void dn_bools(F &&f, bool b, Rest... rest)
+{
+    if (b) dn_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else dn_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <typename F32> using real_t = std::conditional_t<F32::value, float, double>;
+
+// What every step launch needs, worked out once per launcher.
+struct StepLaunch {
+    const DnParams &p;
+    const DnStepIO &io;
+    const int k;
+    const bool f32;
+    const hipStream_t stream;
+    const dim3 grid;
+    const bool norm, noise;
+    const bool rew;     // the rarely used options share one set of instantiations (runtime switches inside): reward wrappers, N4 physics terms
+    StepLaunch(const DnParams &p_, const DnStepIO &io_, int k_, bool f32_, hipStream_t stream_)
+        : p(p_), io(io_), k(k_), f32(f32_), stream(stream_), grid((unsigned)((p_.n + DN_BLOCK - 1) / DN_BLOCK)), norm(p_.normalize_obs != 0),
+          noise(p_.act_noise_sigma > 0.0f || p_.obs_noise_sigma > 0.0f),
+          rew(p_.clip_rew != 0 || p_.norm_rew != 0 || p_.gnd != 0 || p_.drag != 0 || p_.rpm_actions != 0 || p_.pid_mode != 0 || p_.random_spawn != 0 || p_.zero_damping != 0)
+    {
+    }
+};
+
+// One or two waves per tile, every configuration: both units launch these (unit 2 without the normaliser only).  two_wave is a
+// run-time switch on purpose: each unit carries both shapes of its NORM.
+template <bool NORM> void launch_1w_2w(const StepLaunch &L, bool two_wave)
+{
+    dn_bools([&](auto F32, auto NOISE, auto ONE, auto XOPT) {
+        using R = real_t<decltype(F32)>;
+        if (two_wave) DN_KLAUNCH((dn_step_many_2w_kernel<R, NORM, NOISE, ONE, XOPT>), L.grid, dim3(2 * DN_BLOCK), 0, L.stream, L.p, L.io, L.k);
+        else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, ONE, XOPT>), L.grid, dim3(DN_BLOCK), 0, L.stream, L.p, L.io, L.k, DynArg<false>{});
+    }, L.f32, L.noise, L.k == 1, L.rew);
+}
+
+}  // namespace
 
 #if DN_TU == 2
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream)
-{   // multi-wave kernels, normaliser off
-    constexpr bool two_wave = true;
-    const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-    const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-    // the rarely used options share one set of instantiations (runtime switches inside): reward wrappers, N4 physics terms
-    const bool rew = p.clip_rew != 0 || p.norm_rew != 0 || p.gnd != 0 || p.drag != 0 || p.rpm_actions != 0 || p.pid_mode != 0 || p.random_spawn != 0 || p.zero_damping != 0;
-    if (waves == 8 && k > 1 && !noise && !rew && p.normalize_obs) {   // role-pipelined kernel (round 4): eight roles, normaliser on
-        if (f32) DN_KLAUNCH((dn_step_many_rp8_kernel<float>), dim3(grid), dim3(8 * DN_BLOCK), 0, stream, p, io, k);
-        else DN_KLAUNCH((dn_step_many_rp8_kernel<double>), dim3(grid), dim3(8 * DN_BLOCK), 0, stream, p, io, k);
-        return hipGetLastError();
-    }
-    if (waves == 5 && k > 1) {                             // four waves + the normaliser's: fused launches of the plain configuration, normaliser on
-        const dim3 blk(5 * DN_BLOCK);
-        if (f32) {
-            if (noise) DN_KLAUNCH((dn_step_many_5w_kernel<float, true>), dim3(grid), blk, 0, stream, p, io, k);
-            else DN_KLAUNCH((dn_step_many_5w_kernel<float, false>), dim3(grid), blk, 0, stream, p, io, k);
-        } else {
-            if (noise) DN_KLAUNCH((dn_step_many_5w_kernel<double, true>), dim3(grid), blk, 0, stream, p, io, k);
-            else DN_KLAUNCH((dn_step_many_5w_kernel<double, false>), dim3(grid), blk, 0, stream, p, io, k);
-        }
-        return hipGetLastError();
-    }
-    if (waves == 4 && k > 1) {                             // four waves per tile: fused launches of the plain configuration (the caller checked)
-        const dim3 blk(4 * DN_BLOCK);
-        const bool norm = p.normalize_obs != 0;
-#define DN_L4(R, NORM)                                                                                                      \
-        do {                                                                                                                \
-            if (noise) DN_KLAUNCH((dn_step_many_4w_kernel<R, NORM, true>), dim3(grid), blk, 0, stream, p, io, k);    \
-            else DN_KLAUNCH((dn_step_many_4w_kernel<R, NORM, false>), dim3(grid), blk, 0, stream, p, io, k);         \
-        } while (0)
-        if (f32) { if (norm) DN_L4(float, true); else DN_L4(float, false); }
-        else { if (norm) DN_L4(double, true); else DN_L4(double, false); }
-#undef DN_L4
-        return hipGetLastError();
-    }
-    if (waves == 3 && k > 1) {                             // three waves per tile: fused launches
-        const dim3 blk(3 * DN_BLOCK);
-        const bool norm = p.normalize_obs != 0;
-#define DN_L3X(R, NORM, NOISE)                                                                                              \
-        do {                                                                                                                \
-            if (rew) DN_KLAUNCH((dn_step_many_3w_kernel<R, NORM, NOISE, true>), dim3(grid), blk, 0, stream, p, io, k);   \
-            else DN_KLAUNCH((dn_step_many_3w_kernel<R, NORM, NOISE, false>), dim3(grid), blk, 0, stream, p, io, k);      \
-        } while (0)
-#define DN_L3(R, NORM)                                                                                                      \
-        do {                                                                                                                \
-            if (noise) DN_L3X(R, NORM, true); else DN_L3X(R, NORM, false);                                                  \
-        } while (0)
-        if (f32) { if (norm) DN_L3(float, true); else DN_L3(float, false); }
-        else { if (norm) DN_L3(double, true); else DN_L3(double, false); }
-#undef DN_L3
-#undef DN_L3X
-        return hipGetLastError();
-    }
-    if (f32) { if (noise) DN_LAUNCH(float, false, true); else DN_LAUNCH(float, false, false); }
-    else { if (noise) DN_LAUNCH(double, false, true); else DN_LAUNCH(double, false, false); }
+{
+    const StepLaunch L(p, io, k, f32, stream);
+    if (waves == 8 && k > 1 && !L.noise && !L.rew && L.norm)    // role-pipelined kernel (round 4): eight roles, normaliser on
+        dn_bools([&](auto F32) {
+            DN_KLAUNCH((dn_step_many_rp8_kernel<real_t<decltype(F32)>>), L.grid, dim3(8 * DN_BLOCK), 0, stream, p, io, k);
+        }, f32);
+    else if (waves == 5 && k > 1)       // four waves + the normaliser's: fused launches of the plain configuration, normaliser on
+        dn_bools([&](auto F32, auto NOISE) {
+            DN_KLAUNCH((dn_step_many_5w_kernel<real_t<decltype(F32)>, NOISE>), L.grid, dim3(5 * DN_BLOCK), 0, stream, p, io, k);
+        }, f32, L.noise);
+    else if (waves == 4 && k > 1)       // four waves per tile: fused launches of the plain configuration (the caller checked)
+        dn_bools([&](auto F32, auto NORM, auto NOISE) {
+            DN_KLAUNCH((dn_step_many_4w_kernel<real_t<decltype(F32)>, NORM, NOISE>), L.grid, dim3(4 * DN_BLOCK), 0, stream, p, io, k);
+        }, f32, L.norm, L.noise);
+    else if (waves == 3 && k > 1)       // three waves per tile: fused launches
+        dn_bools([&](auto F32, auto NORM, auto NOISE, auto XOPT) {
+            DN_KLAUNCH((dn_step_many_3w_kernel<real_t<decltype(F32)>, NORM, NOISE, XOPT>), L.grid, dim3(3 * DN_BLOCK), 0, stream, p, io, k);
+        }, f32, L.norm, L.noise, L.rew);
+    else launch_1w_2w<false>(L, true);  // two waves, normaliser off
     return hipGetLastError();
 }
 #ifdef DN_MW_STAMP
@@ -4540,176 +4534,56 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 }
 #endif
 #elif DN_TU == 1
-hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnDyn *dy,
-                               const DnWind *wd, const DnAct *ac, const DnSens *sn)
+namespace {
+// The one-wave option kernel of one family of per-drone models (dn_enable_*): DYN always, then WIND, ACT, SENS in that order;
+// `arg` is the slice of the SensArg chain the family's kernels take.
+template <bool WIND, bool ACT, bool SENS> void launch_models(const StepLaunch &L, const typename StepArg<true, WIND, ACT, SENS>::type &arg)
 {
-    const bool norm = p.normalize_obs != 0;
-    if (sn && sn->ring) {                   // dn_enable_sensor: the one-wave option kernel with the sensor model and the other three features
-        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the sensor (the C ABI refuses them first)
-        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
+    dn_bools([&](auto F32, auto NORM, auto NOISE, auto ONE) {
+        DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, ONE, true, false, true, WIND, ACT, SENS>), L.grid, dim3(DN_BLOCK), 0,
+                   L.stream, L.p, L.io, L.k, arg);
+    }, L.f32, L.norm, L.noise, L.k == 1);
+}
+}  // namespace
+
+hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnModels *m)
+{
+    const StepLaunch L(p, io, k, f32, stream);
+    if (m && (m->dyn.dyn || m->wind.mean || m->act.hist || m->sens.ring)) {
+        // a model is on: the deepest enabled family's kernel, whatever `waves` says.  A model that is off rides along as its
+        // value-initialised struct (null pointers): the nominal body, still air, no latency, no bias.
+        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels carry no model (the C ABI refuses them first)
         SensArg sa;
-        static_cast<DnDyn &>(sa) = dy ? *dy : DnDyn{};
-        sa.w = wd ? *wd : DnWind{};
-        sa.a = ac ? *ac : DnAct{};
-        sa.s = *sn;
-#define DN_LSN(R, NORM, NOISE)                                                                                                      \
-        do {                                                                                                                        \
-            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, sa); \
-            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, sa);   \
-        } while (0)
-        if (f32) {
-            if (norm) { if (noise) DN_LSN(float, true, true); else DN_LSN(float, true, false); }
-            else { if (noise) DN_LSN(float, false, true); else DN_LSN(float, false, false); }
-        } else {
-            if (norm) { if (noise) DN_LSN(double, true, true); else DN_LSN(double, true, false); }
-            else { if (noise) DN_LSN(double, false, true); else DN_LSN(double, false, false); }
-        }
-#undef DN_LSN
-        return hipGetLastError();
-    }
-    if (ac && ac->hist) {                   // dn_enable_actuator: the one-wave option kernel with the actuator, the wind and the body terms
-        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the actuator (the C ABI refuses them first)
-        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-        ActArg aa;
-        static_cast<DnDyn &>(aa) = dy ? *dy : DnDyn{};
-        aa.w = wd ? *wd : DnWind{};
-        aa.a = *ac;
-#define DN_LA(R, NORM, NOISE)                                                                                                       \
-        do {                                                                                                                        \
-            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, aa); \
-            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, aa);   \
-        } while (0)
-        if (f32) {
-            if (norm) { if (noise) DN_LA(float, true, true); else DN_LA(float, true, false); }
-            else { if (noise) DN_LA(float, false, true); else DN_LA(float, false, false); }
-        } else {
-            if (norm) { if (noise) DN_LA(double, true, true); else DN_LA(double, true, false); }
-            else { if (noise) DN_LA(double, false, true); else DN_LA(double, false, false); }
-        }
-#undef DN_LA
-        return hipGetLastError();
-    }
-    if (wd && wd->mean) {                   // dn_enable_wind: the one-wave option kernel with the wind and the body terms (scales of 1 without dynamics)
-        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the wind (the C ABI refuses them first)
-        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-        WindArg wa;
-        static_cast<DnDyn &>(wa) = dy ? *dy : DnDyn{};
-        wa.w = *wd;
-#define DN_LW(R, NORM, NOISE)                                                                                                       \
-        do {                                                                                                                        \
-            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, wa); \
-            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, wa);   \
-        } while (0)
-        if (f32) {
-            if (norm) { if (noise) DN_LW(float, true, true); else DN_LW(float, true, false); }
-            else { if (noise) DN_LW(float, false, true); else DN_LW(float, false, false); }
-        } else {
-            if (norm) { if (noise) DN_LW(double, true, true); else DN_LW(double, true, false); }
-            else { if (noise) DN_LW(double, false, true); else DN_LW(double, false, false); }
-        }
-#undef DN_LW
-        return hipGetLastError();
-    }
-    if (dy && dy->dyn) {                    // dn_enable_dynamics: the one-wave option kernel with the body scales, whatever the configuration
-        if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels do not carry the scales (the C ABI refuses them first)
-        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-        const DynArg<true> dya = {*dy};
-#define DN_LD(R, NORM, NOISE)                                                                                                       \
-        do {                                                                                                                        \
-            if (k == 1) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, true, false, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, dya); \
-            else DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, false, true, false, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, k, dya);   \
-        } while (0)
-        if (f32) {
-            if (norm) { if (noise) DN_LD(float, true, true); else DN_LD(float, true, false); }
-            else { if (noise) DN_LD(float, false, true); else DN_LD(float, false, false); }
-        } else {
-            if (norm) { if (noise) DN_LD(double, true, true); else DN_LD(double, true, false); }
-            else { if (noise) DN_LD(double, false, true); else DN_LD(double, false, false); }
-        }
-#undef DN_LD
-        return hipGetLastError();
-    }
-    if (io.mean && waves == 3) {            // dn_step_sampled on three waves
-        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-#define DN_LPS(R, NORM, NOISE) DN_KLAUNCH((dn_step_pqx_kernel<R, NORM, NOISE, true>), dim3(grid), dim3(3 * DN_BLOCK), 0, stream, p, io)
-        if (f32) {
-            if (norm) { if (noise) DN_LPS(float, true, true); else DN_LPS(float, true, false); }
-            else { if (noise) DN_LPS(float, false, true); else DN_LPS(float, false, false); }
-        } else {
-            if (norm) { if (noise) DN_LPS(double, true, true); else DN_LPS(double, true, false); }
-            else { if (noise) DN_LPS(double, false, true); else DN_LPS(double, false, false); }
-        }
-#undef DN_LPS
-        return hipGetLastError();
-    }
-    if (io.mean) {                          // dn_step_sampled: one-wave single-step kernels with the sampler compiled in
-        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-#define DN_LS(R, NORM, NOISE) DN_KLAUNCH((dn_step_many_1w_kernel<R, NORM, NOISE, true, false, true>), dim3(grid), dim3(DN_BLOCK), 0, stream, p, io, 1, DynArg<false>{})
-        if (f32) {
-            if (norm) { if (noise) DN_LS(float, true, true); else DN_LS(float, true, false); }
-            else { if (noise) DN_LS(float, false, true); else DN_LS(float, false, false); }
-        } else {
-            if (norm) { if (noise) DN_LS(double, true, true); else DN_LS(double, true, false); }
-            else { if (noise) DN_LS(double, false, true); else DN_LS(double, false, false); }
-        }
-#undef DN_LS
-        return hipGetLastError();
-    }
-    if (waves == 3 && k == 1) {             // dn_step on three waves cut by dependency (plain configuration; the caller checked)
-        const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-        const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-#define DN_LP(R, NORM, NOISE) DN_KLAUNCH((dn_step_pqx_kernel<R, NORM, NOISE, false>), dim3(grid), dim3(3 * DN_BLOCK), 0, stream, p, io)
-        if (f32) {
-            if (norm) { if (noise) DN_LP(float, true, true); else DN_LP(float, true, false); }
-            else { if (noise) DN_LP(float, false, true); else DN_LP(float, false, false); }
-        } else {
-            if (norm) { if (noise) DN_LP(double, true, true); else DN_LP(double, true, false); }
-            else { if (noise) DN_LP(double, false, true); else DN_LP(double, false, false); }
-        }
-#undef DN_LP
-        return hipGetLastError();
-    }
-    if ((waves >= 2 && !norm) || (waves >= 3 && k > 1)) return dn_launch_step_many_mw(p, io, k, f32, waves, stream);
-    const bool two_wave = waves >= 2;       // with the normaliser: the two-wave kernels (there is no three-wave one)
-    const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-    const bool noise = p.act_noise_sigma > 0.0f || p.obs_noise_sigma > 0.0f;
-    const bool rew = p.clip_rew != 0 || p.norm_rew != 0 || p.gnd != 0 || p.drag != 0 || p.rpm_actions != 0 || p.pid_mode != 0 || p.random_spawn != 0 || p.zero_damping != 0;
-    if (two_wave) {                         // normaliser on
-        if (f32) { if (noise) DN_LAUNCH(float, true, true); else DN_LAUNCH(float, true, false); }
-        else { if (noise) DN_LAUNCH(double, true, true); else DN_LAUNCH(double, true, false); }
-        return hipGetLastError();
-    }
-    if (f32) {
-        if (norm) { if (noise) DN_LAUNCH(float, true, true); else DN_LAUNCH(float, true, false); }
-        else { if (noise) DN_LAUNCH(float, false, true); else DN_LAUNCH(float, false, false); }
-    } else {
-        if (norm) { if (noise) DN_LAUNCH(double, true, true); else DN_LAUNCH(double, true, false); }
-        else { if (noise) DN_LAUNCH(double, false, true); else DN_LAUNCH(double, false, false); }
-    }
+        static_cast<DnDyn &>(sa) = m->dyn;
+        sa.w = m->wind;
+        sa.a = m->act;
+        sa.s = m->sens;
+        if (m->sens.ring) launch_models<true, true, true>(L, sa);
+        else if (m->act.hist) launch_models<true, true, false>(L, sa);
+        else if (m->wind.mean) launch_models<true, false, false>(L, sa);
+        else launch_models<false, false, false>(L, DynArg<true>{static_cast<const DnDyn &>(sa)});
+    } else if (waves == 3 && (io.mean || k == 1))       // dn_step / dn_step_sampled on three waves cut by dependency (plain configuration; the caller checked)
+        dn_bools([&](auto F32, auto NORM, auto NOISE, auto SAMPLE) {
+            DN_KLAUNCH((dn_step_pqx_kernel<real_t<decltype(F32)>, NORM, NOISE, SAMPLE>), L.grid, dim3(3 * DN_BLOCK), 0, stream, p, io);
+        }, f32, L.norm, L.noise, io.mean != nullptr);
+    else if (io.mean)                                   // dn_step_sampled: one-wave single-step kernels with the sampler compiled in
+        dn_bools([&](auto F32, auto NORM, auto NOISE) {
+            DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, true, false, true>), L.grid, dim3(DN_BLOCK), 0, stream, p, io, 1, DynArg<false>{});
+        }, f32, L.norm, L.noise);
+    else if ((waves >= 2 && !L.norm) || (waves >= 3 && k > 1)) return dn_launch_step_many_mw(p, io, k, f32, waves, stream);
+    else                                                // one wave, or with the normaliser two (there is no three-wave kernel in this unit)
+        dn_bools([&](auto NORM) { launch_1w_2w<decltype(NORM)::value>(L, waves >= 2); }, L.norm);
     return hipGetLastError();
 }
 #endif
-#undef DN_LAUNCH
-#undef DN_LAUNCH2
-#undef DN_LAUNCH3
 
 #if DN_TU == 1
-hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnDyn *dy, const DnWind *wd, const DnAct *ac,
-                           const DnSens *sn)
+hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnModels *m)
 {
-    const DnAct act = ac ? *ac : DnAct{};
-    const DnSens sen = sn ? *sn : DnSens{};
+    const DnModels on = m ? *m : DnModels{};
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-    const DnDyn dyn = dy ? *dy : DnDyn{};
-    const DnWind wnd = wd ? *wd : DnWind{};
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act, sen);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, dyn, wnd, act, sen);
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens);
     return hipGetLastError();
 }
 

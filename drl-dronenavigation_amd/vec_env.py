@@ -621,6 +621,40 @@ class DroneVecEnv(_VecEnvBase):
         arr = _numpy_to_states(states, self.num_envs)
         _capi.check(self._lib.dn_set_state(self._handle, C.cast(arr, C.c_void_p), self.num_envs))
 
+    # ------------------------------------------------------------------ the per-drone models: shared plumbing
+    # value rules of _checked: (predicate over the whole tensor, message); one device-side reduction, one scalar back
+    _FINITE = (torch.isfinite, "every value of {name} must be finite")
+    _LATENCY = (lambda x: (x >= 0) & (x <= 8), "every latency must lie in [0, 8]")
+
+    def _checked(self, name, x, dtype, shape, rule=None, dtype_text=None):
+        """The contiguous form of tensor `x` for a set_* call, or None for None: a torch.Tensor of `dtype` on the env's device with
+        `shape` whose values pass `rule`."""
+        if x is None:
+            return None
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if x.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype_text or dtype}, got {x.dtype}")
+        if x.device != self.device:
+            raise ValueError(f"{name} must live on {self.device}, got {x.device}")
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(x.shape)}")
+        x = x.contiguous()
+        if rule is not None and not bool(rule[0](x).all()):
+            raise ValueError(rule[1].format(name=name))
+        return x
+
+    def _model_config(self, getter, c, from_c):
+        """A *_config(): the Python form of what dn_get_*_config wrote into `c`, or None when the model is off."""
+        rc = getter(self._handle, C.byref(c))
+        if rc < 0:
+            _capi.check(rc)
+        return from_c(c) if rc == 1 else None
+
+    def _require(self, model, what, how):
+        if model is None:
+            raise RuntimeError(f"{what} is not enabled: construct the env with {how}")
+
     # ------------------------------------------------------------------ dynamics randomisation (dn_enable_dynamics)
     def get_dynamics(self):
         """Every drone's body scales as a float32 tensor [N, 4] on the env's device: s_m, s_I, s_kf, s_km.  With get_state() this is
@@ -635,31 +669,19 @@ class DroneVecEnv(_VecEnvBase):
         """Writes every drone's body scales (float32 [N, 4] on the env's device; every value positive and finite).  With
         resample=False they hold until the next set_dynamics; with resample=True until the drone's next episode start."""
         self._require_dynamics()
-        if not isinstance(scales, torch.Tensor):
+        if scales is None:
             raise TypeError("scales must be a torch.Tensor")
-        if scales.dtype != torch.float32:
-            raise TypeError(f"scales must be float32, got {scales.dtype}")
-        if scales.device != self.device:
-            raise ValueError(f"scales must live on {self.device}, got {scales.device}")
-        if tuple(scales.shape) != (self.num_envs, 4):
-            raise ValueError(f"scales must have shape ({self.num_envs}, 4), got {tuple(scales.shape)}")
-        s = scales.contiguous()
-        if not bool(((s > 0) & torch.isfinite(s)).all()):      # one device-side reduction, one scalar back
-            raise ValueError("every scale must be positive and finite")
+        s = self._checked("scales", scales, torch.float32, (self.num_envs, 4),
+                          (lambda x: (x > 0) & torch.isfinite(x), "every scale must be positive and finite"), "float32")
         with torch.cuda.device(self.device):
             _capi.check(self._lib.dn_set_dynamics(self._handle, s.data_ptr(), self._stream()))
 
     def dynamics_config(self):
         """The DynamicsRandomization in force (dn_get_dynamics_config), or None when the feature is off."""
-        c = _capi.DnDynamicsConfig()
-        rc = self._lib.dn_get_dynamics_config(self._handle, C.byref(c))
-        if rc < 0:
-            _capi.check(rc)
-        return DynamicsRandomization.from_c(c) if rc == 1 else None
+        return self._model_config(self._lib.dn_get_dynamics_config, _capi.DnDynamicsConfig(), DynamicsRandomization.from_c)
 
     def _require_dynamics(self):
-        if self.dynamics is None:
-            raise RuntimeError("dynamics randomisation is not enabled: construct the env with dynamics=DynamicsRandomization(...)")
+        self._require(self.dynamics, "dynamics randomisation", "dynamics=DynamicsRandomization(...)")
 
     # ------------------------------------------------------------------ wind (dn_enable_wind)
     def get_wind(self):
@@ -677,38 +699,17 @@ class DroneVecEnv(_VecEnvBase):
         With resample=False the steady wind holds until the next set_wind; otherwise until the drone's next episode start, as does
         the gust between its steps."""
         self._require_wind()
-        rows = []
-        for name, x in (("mean", mean), ("gust", gust)):
-            if x is None:
-                rows.append(None)
-                continue
-            if not isinstance(x, torch.Tensor):
-                raise TypeError(f"{name} must be a torch.Tensor")
-            if x.dtype != torch.float32:
-                raise TypeError(f"{name} must be float32, got {x.dtype}")
-            if x.device != self.device:
-                raise ValueError(f"{name} must live on {self.device}, got {x.device}")
-            if tuple(x.shape) != (self.num_envs, 4):
-                raise ValueError(f"{name} must have shape ({self.num_envs}, 4), got {tuple(x.shape)}")
-            x = x.contiguous()
-            if not bool(torch.isfinite(x).all()):          # one device-side reduction, one scalar back
-                raise ValueError(f"every value of {name} must be finite")
-            rows.append(x)
+        rows = [self._checked(name, x, torch.float32, (self.num_envs, 4), self._FINITE, "float32") for name, x in (("mean", mean), ("gust", gust))]
         ptr = [None if x is None else x.data_ptr() for x in rows]
         with torch.cuda.device(self.device):
             _capi.check(self._lib.dn_set_wind(self._handle, ptr[0], ptr[1], self._stream()))
 
     def wind_config(self):
         """The WindDisturbance in force (dn_get_wind_config), or None when the feature is off."""
-        c = _capi.DnWindConfig()
-        rc = self._lib.dn_get_wind_config(self._handle, C.byref(c))
-        if rc < 0:
-            _capi.check(rc)
-        return WindDisturbance.from_c(c) if rc == 1 else None
+        return self._model_config(self._lib.dn_get_wind_config, _capi.DnWindConfig(), WindDisturbance.from_c)
 
     def _require_wind(self):
-        if self.wind is None:
-            raise RuntimeError("wind is not enabled: construct the env with wind=WindDisturbance(...)")
+        self._require(self.wind, "wind", "wind=WindDisturbance(...)")
 
     # ------------------------------------------------------------------ actuator (dn_enable_actuator)
     def get_actuator(self):
@@ -730,46 +731,20 @@ class DroneVecEnv(_VecEnvBase):
         hold until the next set_actuator; otherwise until the drone's next episode start."""
         self._require_actuator()
         n = self.num_envs
-        spec = (("latency", latency, torch.int32, (n,)), ("coeff", coeff, torch.float32, (n,)), ("rpm", rpm, torch.float32, (n, 4)),
-                ("history", history, torch.float32, (n, 8, 4)))
-        rows = []
-        for name, x, dtype, shape in spec:
-            if x is None:
-                rows.append(None)
-                continue
-            if not isinstance(x, torch.Tensor):
-                raise TypeError(f"{name} must be a torch.Tensor")
-            if x.dtype != dtype:
-                raise TypeError(f"{name} must be {dtype}, got {x.dtype}")
-            if x.device != self.device:
-                raise ValueError(f"{name} must live on {self.device}, got {x.device}")
-            if tuple(x.shape) != shape:
-                raise ValueError(f"{name} must have shape {shape}, got {tuple(x.shape)}")
-            x = x.contiguous()
-            if name == "latency":
-                if not bool(((x >= 0) & (x <= 8)).all()):
-                    raise ValueError("every latency must lie in [0, 8]")
-            elif name == "coeff":
-                if not bool(((x >= 0) & (x < 1)).all()):
-                    raise ValueError("every coeff must lie in [0, 1)")
-            elif not bool(torch.isfinite(x).all()):
-                raise ValueError(f"every value of {name} must be finite")
-            rows.append(x)
+        spec = (("latency", latency, torch.int32, (n,), self._LATENCY),
+                ("coeff", coeff, torch.float32, (n,), (lambda x: (x >= 0) & (x < 1), "every coeff must lie in [0, 1)")),
+                ("rpm", rpm, torch.float32, (n, 4), self._FINITE), ("history", history, torch.float32, (n, 8, 4), self._FINITE))
+        rows = [self._checked(*row) for row in spec]
         ptr = [None if x is None else x.data_ptr() for x in rows]
         with torch.cuda.device(self.device):
             _capi.check(self._lib.dn_set_actuator(self._handle, ptr[0], ptr[1], ptr[2], ptr[3], self._stream()))
 
     def actuator_config(self):
         """The ActuatorModel in force (dn_get_actuator_config), or None when the feature is off."""
-        c = _capi.DnActuatorConfig()
-        rc = self._lib.dn_get_actuator_config(self._handle, C.byref(c))
-        if rc < 0:
-            _capi.check(rc)
-        return ActuatorModel.from_c(c) if rc == 1 else None
+        return self._model_config(self._lib.dn_get_actuator_config, _capi.DnActuatorConfig(), ActuatorModel.from_c)
 
     def _require_actuator(self):
-        if self.actuator is None:
-            raise RuntimeError("the actuator model is not enabled: construct the env with actuator=ActuatorModel(...)")
+        self._require(self.actuator, "the actuator model", "actuator=ActuatorModel(...)")
 
     # ------------------------------------------------------------------ sensor model (dn_enable_sensor)
     def get_sensor(self):
@@ -793,38 +768,16 @@ class DroneVecEnv(_VecEnvBase):
         restoring a checkpoint, set step_count first."""
         self._require_sensor()
         n = self.num_envs
-        spec = (("latency", latency, torch.int32, (n,)), ("bias", bias, torch.float32, (n, 13)), ("history", history, torch.float32, (n, 9, 13)))
-        rows = []
-        for name, x, dtype, shape in spec:
-            if x is None:
-                rows.append(None)
-                continue
-            if not isinstance(x, torch.Tensor):
-                raise TypeError(f"{name} must be a torch.Tensor")
-            if x.dtype != dtype:
-                raise TypeError(f"{name} must be {dtype}, got {x.dtype}")
-            if x.device != self.device:
-                raise ValueError(f"{name} must live on {self.device}, got {x.device}")
-            if tuple(x.shape) != shape:
-                raise ValueError(f"{name} must have shape {shape}, got {tuple(x.shape)}")
-            x = x.contiguous()
-            if name == "latency":
-                if not bool(((x >= 0) & (x <= 8)).all()):
-                    raise ValueError("every latency must lie in [0, 8]")
-            elif name == "bias" and not bool(torch.isfinite(x).all()):
-                raise ValueError("every value of bias must be finite")      # history: entries older than the episode are unspecified
-            rows.append(x)
+        spec = (("latency", latency, torch.int32, (n,), self._LATENCY), ("bias", bias, torch.float32, (n, 13), self._FINITE),
+                ("history", history, torch.float32, (n, 9, 13)))      # no value rule: entries older than the episode are unspecified
+        rows = [self._checked(*row) for row in spec]
         ptr = [None if x is None else x.data_ptr() for x in rows]
         with torch.cuda.device(self.device):
             _capi.check(self._lib.dn_set_sensor(self._handle, ptr[0], ptr[1], ptr[2], self._stream()))
 
     def sensor_config(self):
         """The SensorModel in force (dn_get_sensor_config), or None when the feature is off."""
-        c = _capi.DnSensorConfig()
-        rc = self._lib.dn_get_sensor_config(self._handle, C.byref(c))
-        if rc < 0:
-            _capi.check(rc)
-        return SensorModel.from_c(c) if rc == 1 else None
+        return self._model_config(self._lib.dn_get_sensor_config, _capi.DnSensorConfig(), SensorModel.from_c)
 
     def observation_scale(self):
         """The 13 factors from physical units to observation columns (float64 numpy), e.g. for SensorModel(bias=...): 1 / aviary extent
@@ -835,8 +788,7 @@ class DroneVecEnv(_VecEnvBase):
         return np.array([1.0 / dim[3], 1.0 / dim[4], 1.0 / dim[5]] + [1.0 / np.pi] * 3 + [1.0 / 3.0] * 3 + [1.0] * 3 + [1.0 / m], dtype=np.float64)
 
     def _require_sensor(self):
-        if self.sensor is None:
-            raise RuntimeError("the sensor model is not enabled: construct the env with sensor=SensorModel(...)")
+        self._require(self.sensor, "the sensor model", "sensor=SensorModel(...)")
 
     def stats(self):
         s = _capi.DnStats()

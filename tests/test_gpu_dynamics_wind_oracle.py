@@ -3,7 +3,7 @@
 families, the run-time options inside them, and free-running fused launches through many in-launch episode starts.
 
 a. Every instantiation: both families are dn_step_many_1w_kernel<R, NORM, NOISE, ONE, XOPT = true, SAMPLE = false, DYN = true, WIND>
-   (dn_launch_step_many, macros DN_LD / DN_LW), one test ID per cell:
+   (dn_launch_step_many, launch_models), one test ID per cell:
 
        test ID cell [family-dtype-norm-noise-mode]   R       NORM   NOISE  ONE    WIND   dynamics scales
        dyn-f64-norm0-noise0-step / -rollout           double  false  false  true / false  false  on
