@@ -972,16 +972,6 @@ void orc_vec_create(const orc_config *c, orc_env *envs, int64_t n)
     }
 }
 
-static void finish_obs(const orc_config *c, orc_env *e, uint64_t env_id, uint32_t stream0, float obs[ORC_OBS_DIM])
-{
-    add_obs_noise(c, env_id, e->step_count, stream0, obs);
-    if (c->normalize_obs) {
-        double o[ORC_OBS_DIM];
-        orc_normalize_obs(e, obs, o);
-        for (int i = 0; i < ORC_OBS_DIM; ++i) obs[i] = (float)o[i];
-    }
-}
-
 /* Episode start of drone gid at vector step `step` (dn_enable_dynamics / dn_enable_wind, dronenav.h): with resample, new body scales
  * lo + (hi - lo)(r + 0.5) / 2^32 from ONE Philox call on stream 13 and a new steady wind (speed, azimuth, vertical component uniform,
  * stream 14), both in float64 stored as float32; the gust from its stationary law, float32(sigma xi') with xi' on stream 16 (0 with
@@ -1092,6 +1082,86 @@ static void act_push(orc_act_state *as, const float commanded[4])
     memcpy(as->history[0], commanded, sizeof as->history[0]);
 }
 
+/* The sensor model of dn_enable_sensor (dronenav.h), in the LOGICAL form dn_get_sensor returns: per drone d, b[13]
+ * and hist[9][13] with hist[j] = o_{k - j}, shifted every step -- no ring, no slot arithmetic.  "off" (dronenav.h): with resample = 1,
+ * latency [0, 0] switches the delay off and all-zero amplitudes switch the add off; with resample = 0 both are always applied. */
+void orc_sens_rule(orc_sens_config *sc)
+{
+    int any = 0;
+    for (int j = 0; j < ORC_OBS_DIM; ++j) any |= sc->bias_amp[j] > 0.0f;
+    sc->lat_on = !sc->resample || sc->latency[0] != 0 || sc->latency[1] != 0;
+    sc->bias_on = !sc->resample || any;
+}
+
+/* The state after the first dn_enable_sensor: d = 0, b = 0, an all-zero history. */
+void orc_sens_init(const orc_sens_config *sc, orc_sens_state *ss, int64_t n)
+{
+    (void)sc;
+    memset(ss, 0, (size_t)n * sizeof *ss);
+}
+
+static void sens_add_bias(const orc_sens_config *sc, const orc_sens_state *ss, float row[ORC_OBS_DIM])
+{
+    if (!sc->bias_on) return;                   /* no add at all: -0.0f + 0.0f would flip a sign bit */
+    for (int j = 0; j < ORC_OBS_DIM; ++j) row[j] = row[j] + ss->bias[j];
+}
+
+/* The sensor's part of one env step: `row` holds the pre-bias o_k of the episode's k-th control step (noise added) and leaves as
+ * y_k = float32(o_{k - min(d, k)} + b).  The history takes o_k first (only while the delay is on). */
+void orc_env_step_sens(const orc_sens_config *sc, orc_sens_state *ss, int32_t k, float row[ORC_OBS_DIM])
+{
+    if (sc->lat_on) {
+        memmove(ss->history[1], ss->history[0], (ORC_SENS_HIST - 1) * sizeof ss->history[0]);
+        memcpy(ss->history[0], row, sizeof ss->history[0]);
+        int32_t d = ss->latency;
+        if (d < 0) d = 0;
+        if (d > ORC_MAX_LATENCY) d = ORC_MAX_LATENCY;
+        if (d > k) d = k;
+        memcpy(row, ss->history[d], sizeof ss->history[0]);
+    }
+    sens_add_bias(sc, ss, row);
+}
+
+/* Episode start of drone gid at vector step `step` with the pre-bias reset row o_0 in `row`: with resample, FOUR Philox calls on
+ * streams 18..21, u_m = (r_c + 0.5) / 2^32 with m = 4 q + c: b_j = float32(amp_j (2 u_j - 1)) in float64, d = lo + floor((hi - lo + 1)
+ * u_13) clamped to hi.  The pipeline then holds o_0 alone, and the row leaves undelayed as float32(o_0 + b_new). */
+static void sens_episode_start(const orc_config *c, const orc_sens_config *sc, orc_sens_state *ss, uint64_t gid, uint64_t step,
+                               float row[ORC_OBS_DIM])
+{
+    if (sc->resample) {
+        double u[16];
+        for (uint32_t q = 0; q < 4; ++q) {
+            uint32_t r[4];
+            orc_philox4x32((uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)step, ctr3(18u + q, step), (uint32_t)c->seed,
+                           (uint32_t)(c->seed >> 32), r);
+            for (int j = 0; j < 4; ++j) u[4 * q + j] = ((double)r[j] + 0.5) * (1.0 / 4294967296.0);
+        }
+        for (int j = 0; j < ORC_OBS_DIM; ++j) ss->bias[j] = (float)((double)sc->bias_amp[j] * (2.0 * u[j] - 1.0));
+        const int32_t lo = sc->latency[0], hi = sc->latency[1];
+        int32_t d = lo + (int32_t)floor((double)(hi - lo + 1) * u[13]);
+        ss->latency = d > hi ? hi : d;
+    }
+    if (sc->lat_on)
+        for (int j = 0; j < ORC_SENS_HIST; ++j) memcpy(ss->history[j], row, sizeof ss->history[0]);
+    sens_add_bias(sc, ss, row);
+}
+
+/* noise, then the sensor (episode_start: the reset row o_0 of a new episode; else the step row o_k), then the normaliser */
+static void finish_obs_sens(const orc_config *c, orc_env *e, uint64_t env_id, uint32_t stream0, float obs[ORC_OBS_DIM],
+                            const orc_sens_config *sc, orc_sens_state *ss, int episode_start, int32_t k)
+{
+    add_obs_noise(c, env_id, e->step_count, stream0, obs);
+    if (ss) {
+        if (episode_start) sens_episode_start(c, sc, ss, env_id, e->step_count, obs);
+        else orc_env_step_sens(sc, ss, k, obs);
+    }
+    if (c->normalize_obs) {
+        double o[ORC_OBS_DIM];
+        orc_normalize_obs(e, obs, o);
+        for (int i = 0; i < ORC_OBS_DIM; ++i) obs[i] = (float)o[i];
+    }
+}
+
 void orc_vec_reset(const orc_config *c, orc_env *envs, int64_t n, float *obs, int threads)
 {
     orc_vec_reset_dw(c, NULL, NULL, envs, n, obs, threads);
@@ -1106,7 +1176,16 @@ void orc_vec_reset_dw(const orc_config *c, const orc_dw_config *dwc, orc_dw_stat
 void orc_vec_reset_act(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
                        orc_act_state *acts, orc_env *envs, int64_t n, float *obs, int threads)
 {
+    orc_vec_reset_sens(c, dwc, dws, actc, acts, NULL, NULL, envs, n, obs, threads);
+}
+
+/* With the sensor: the reset row is float32(o_0 + b_new), the new episode's bias, no delay; the normaliser sees that row. */
+void orc_vec_reset_sens(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                        orc_act_state *acts, const orc_sens_config *sensc, orc_sens_state *senss, orc_env *envs, int64_t n, float *obs,
+                        int threads)
+{
     const int act = actc && acts && actc->on;
+    const int sens = sensc && senss && (sensc->lat_on || sensc->bias_on);
     (void)threads;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
@@ -1114,7 +1193,7 @@ void orc_vec_reset_act(const orc_config *c, const orc_dw_config *dwc, orc_dw_sta
     for (int64_t i = 0; i < n; ++i) {
         orc_env *e = &envs[i];
         orc_env_reset(c, e, &obs[i * ORC_OBS_DIM]);
-        finish_obs(c, e, (uint64_t)(c->env_id_offset + i), 5u, &obs[i * ORC_OBS_DIM]);
+        finish_obs_sens(c, e, (uint64_t)(c->env_id_offset + i), 5u, &obs[i * ORC_OBS_DIM], sensc, sens ? &senss[i] : NULL, 1, 0);
         if (dwc && dws) dw_episode_start(c, dwc, &dws[i], (uint64_t)(c->env_id_offset + i), e->step_count);
         if (act) act_episode_start(c, actc, &acts[i], (uint64_t)(c->env_id_offset + i), e->step_count);
         e->ep_ret = 0.0; e->ep_len = 0;          /* Monitor.reset */
@@ -1146,7 +1225,21 @@ void orc_vec_step_act(const orc_config *c, const orc_dw_config *dwc, orc_dw_stat
                       uint8_t *truncated, int32_t *found_targets, float *terminal_obs, float *ep_ret, int32_t *ep_len,
                       uint8_t *terminated, int threads)
 {
+    orc_vec_step_sens(c, dwc, dws, actc, acts, NULL, NULL, envs, n, actions, obs, reward, done, truncated, found_targets, terminal_obs,
+                      ep_ret, ep_len, terminated, threads);
+}
+
+/* With the sensor (dronenav.h, dn_enable_sensor): between the observation noise and the normaliser the step row o_k (k = the episode's
+ * control steps once this step is over) enters the history and float32(o_{k - min(d, k)} + b) leaves -- it is also terminal_obs; a
+ * finished drone then draws (d, b) keyed by THIS vector step, its history holds o_0 alone and its reset row leaves as float32(o_0 +
+ * b_new).  The normaliser is fed the delivered rows where it was fed the true ones.  Nothing else reads them. */
+void orc_vec_step_sens(const orc_config *c, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                       orc_act_state *acts, const orc_sens_config *sensc, orc_sens_state *senss, orc_env *envs, int64_t n,
+                       const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets,
+                       float *terminal_obs, float *ep_ret, int32_t *ep_len, uint8_t *terminated, int threads)
+{
     const int act = actc && acts && actc->on;
+    const int sens = sensc && senss && (sensc->lat_on || sensc->bias_on);
     (void)threads;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
@@ -1169,12 +1262,14 @@ void orc_vec_step_act(const orc_config *c, const orc_dw_config *dwc, orc_dw_stat
         }
         orc_step_out so;
         orc_dw_state *s = (dwc && dws) ? &dws[i] : NULL;
+        orc_sens_state *ss = sens ? &senss[i] : NULL;
+        const int32_t k = e->steps + 1;           /* this is the episode's k-th control step */
         orc_env_step_act(c, dwc, s, actc, as, e, a, &so);
         if (as) act_push(as, commanded);
         if (s) dw_gust_step(c, dwc, s, gid, e->step_count);
         float *o = &obs[i * ORC_OBS_DIM];
         memcpy(o, so.obs, sizeof so.obs);
-        finish_obs(c, e, gid, 1u, o);
+        finish_obs_sens(c, e, gid, 1u, o, sensc, ss, 0, k);
         int dn = so.terminated || so.truncated;
         so.reward = orc_reward_wrappers(c, e, so.reward, dn);
         e->ep_ret += so.reward;                   /* Monitor.step */
@@ -1189,7 +1284,7 @@ void orc_vec_step_act(const orc_config *c, const orc_dw_config *dwc, orc_dw_stat
             if (ep_ret) ep_ret[i] = (float)e->ep_ret;
             if (ep_len) ep_len[i] = e->ep_len;
             orc_env_reset(c, e, o);
-            finish_obs(c, e, gid, 5u, o);
+            finish_obs_sens(c, e, gid, 5u, o, sensc, ss, 1, 0);
             if (s) dw_episode_start(c, dwc, s, gid, e->step_count);      /* replaces the gust's update of this step */
             if (as) act_episode_start(c, actc, as, gid, e->step_count);
             e->ep_ret = 0.0; e->ep_len = 0;
@@ -1241,6 +1336,8 @@ int32_t orc_sizeof_dw_config(void) { return (int32_t)sizeof(orc_dw_config); }
 int32_t orc_sizeof_dw_state(void) { return (int32_t)sizeof(orc_dw_state); }
 int32_t orc_sizeof_act_config(void) { return (int32_t)sizeof(orc_act_config); }
 int32_t orc_sizeof_act_state(void) { return (int32_t)sizeof(orc_act_state); }
+int32_t orc_sizeof_sens_config(void) { return (int32_t)sizeof(orc_sens_config); }
+int32_t orc_sizeof_sens_state(void) { return (int32_t)sizeof(orc_sens_state); }
 int32_t orc_max_threads(void)
 {
 #ifdef _OPENMP

@@ -278,6 +278,51 @@ void orc_vec_step_act(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_st
 int32_t orc_sizeof_act_config(void);
 int32_t orc_sizeof_act_state(void);
 
+/* ---- per-drone sensor model (dn_enable_sensor; not in the reference: its observation is the state of this very step) ----
+ * Restated from the documented semantics (include/dronenav.h), not from the kernels, and NOT as a ring keyed by the
+ * vector step: the state is the logical one dn_get_sensor returns, shifted every step.  Kept out of orc_config / orc_env like the others.
+ *   o_k:     the row BEFORE the normaliser (columns + observation noise) after the episode's k-th control step; o_0 the reset row.
+ *   step:    o_k enters the history (history[0] = o_k, the rest move down), float32(o_{k - min(d, k)} + b) leaves, one float32 add per
+ *            column and no add at all when the bias is off; it is terminal_obs when the step ends the episode.
+ *   episode starts (orc_vec_reset_sens and the auto-reset of orc_vec_step_sens): with resample FOUR Philox calls keyed (seed; gid, the
+ *            vector step the episode starts on, streams 18..21), u_m = (r_c + 0.5) / 2^32 with m = 4 q + c: b_j = float32(amp_j (2 u_j -
+ *            1)) in float64, d = lo + floor((hi - lo + 1) u_13) clamped to hi; the history holds o_0 alone; float32(o_0 + b_new) leaves,
+ *            undelayed.  resample = 0 keeps d and b, which are then always applied.
+ *   the normaliser is fed the delivered rows, once each, where it was fed the true rows; nothing else reads them. */
+#define ORC_SENS_HIST (ORC_MAX_LATENCY + 1)
+typedef struct orc_sens_config {
+    int32_t latency[2];                         /* dn_sensor_config, member for member (68 bytes) */
+    float bias_amp[ORC_OBS_DIM];
+    int32_t resample;
+    int32_t reserved;
+    int32_t lat_on;                             /* orc_sens_rule: the delay is applied and the history maintained */
+    int32_t bias_on;                            /* orc_sens_rule: the bias is added; both 0 = the path without the sensor */
+} orc_sens_config;
+
+/* the per-drone arrays dn_get_sensor returns, 524 bytes */
+typedef struct orc_sens_state {
+    int32_t latency;                            /* d */
+    float bias[ORC_OBS_DIM];                    /* b */
+    float history[ORC_SENS_HIST][ORC_OBS_DIM];  /* history[j] = o_{k - j}, k = orc_env.steps; entries with k - j < 0 are never read */
+} orc_sens_state;
+
+/* lat_on / bias_on from the header's "off" rule: resample = 1: latency != [0, 0] / some amplitude > 0; resample = 0: both 1 */
+void orc_sens_rule(orc_sens_config *sensc);
+/* the state after the first enable: d = 0, b = 0, an all-zero history */
+void orc_sens_init(const orc_sens_config *sensc, orc_sens_state *senss, int64_t n);
+/* the sensor's part of one env step: row = o_k of the episode's k-th control step on entry, y_k on return */
+void orc_env_step_sens(const orc_sens_config *sensc, orc_sens_state *ss, int32_t k, float row[ORC_OBS_DIM]);
+/* the vec entry points with per-drone state senss[n]; sensc / senss NULL (or both flags 0): exactly orc_vec_reset_act / orc_vec_step_act */
+void orc_vec_reset_sens(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                        orc_act_state *acts, const orc_sens_config *sensc, orc_sens_state *senss, orc_env *envs, int64_t n, float *obs,
+                        int threads);
+void orc_vec_step_sens(const orc_config *cfg, const orc_dw_config *dwc, orc_dw_state *dws, const orc_act_config *actc,
+                       orc_act_state *acts, const orc_sens_config *sensc, orc_sens_state *senss, orc_env *envs, int64_t n,
+                       const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets,
+                       float *terminal_obs, float *ep_ret, int32_t *ep_len, uint8_t *terminated, int threads);
+int32_t orc_sizeof_sens_config(void);
+int32_t orc_sizeof_sens_state(void);
+
 /* ---- N1: GAE (cleanRLPPO.py:234-248 + SB3 truncation bootstrap) ------------ */
 void orc_gae(const float *rewards, const float *values, const uint8_t *dones,
              const float *last_values, const uint8_t *last_dones,

@@ -91,6 +91,17 @@ class OrcActConfig(C.Structure):
 ACT_DTYPE = np.dtype([("latency", "i4"), ("coeff", "f4"), ("rpm", "f4", 4), ("history", "f4", (8, 4))], align=True)
 
 
+class OrcSensConfig(C.Structure):
+    """orc_sens_config: the per-drone sensor model (dn_enable_sensor): dn_sensor_config member for member, then lat_on / bias_on."""
+    _fields_ = [("latency", C.c_int32 * 2), ("bias_amp", C.c_float * OBS_DIM), ("resample", C.c_int32), ("reserved", C.c_int32),
+                ("lat_on", C.c_int32), ("bias_on", C.c_int32)]
+
+
+# numpy view of orc_sens_state[n], the 524 bytes per drone dn_get_sensor returns: latency d, bias row b and the logical history
+# (history[j] = the pre-bias row o_{k - j}, k = the drone's episode step counter)
+SENS_DTYPE = np.dtype([("latency", "i4"), ("bias", "f4", OBS_DIM), ("history", "f4", (9, OBS_DIM))], align=True)
+
+
 class OrcStepOut(C.Structure):
     _fields_ = [("obs", C.c_float * OBS_DIM), ("reward", C.c_double),
                 ("terminated", C.c_int32), ("truncated", C.c_int32), ("found_targets", C.c_int32)]
@@ -177,19 +188,28 @@ def lib():
     L.orc_env_step_act.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, envp, fp, C.POINTER(OrcStepOut)]
     L.orc_vec_reset_act.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
     L.orc_vec_step_act.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10 + [C.c_int]
+    senscp = C.POINTER(OrcSensConfig)
+    L.orc_sens_rule.argtypes = [senscp]
+    L.orc_sens_init.argtypes = [senscp, C.c_void_p, C.c_int64]
+    L.orc_env_step_sens.argtypes = [senscp, C.c_void_p, C.c_int32, fp]
+    L.orc_vec_reset_sens.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, senscp, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_int]
+    L.orc_vec_step_sens.argtypes = [cfgp, dwcp, C.c_void_p, actcp, C.c_void_p, senscp, C.c_void_p, C.c_void_p, C.c_int64] \
+        + [C.c_void_p] * 10 + [C.c_int]
     L.orc_gae.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     L.orc_philox4x32.argtypes = [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]
     L.orc_noise4.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, fp]
     L.orc_noise4_many.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, C.c_uint64, C.c_uint32, fp]
     L.orc_noise4_many.restype = None
     for name in ("orc_sizeof_env", "orc_sizeof_config", "orc_max_threads", "orc_sizeof_dw_config", "orc_sizeof_dw_state",
-                 "orc_sizeof_act_config", "orc_sizeof_act_state"):
+                 "orc_sizeof_act_config", "orc_sizeof_act_state", "orc_sizeof_sens_config", "orc_sizeof_sens_state"):
         getattr(L, name).restype = C.c_int32
     assert L.orc_sizeof_env() == C.sizeof(OrcEnv) == ENV_DTYPE.itemsize, \
         (L.orc_sizeof_env(), C.sizeof(OrcEnv), ENV_DTYPE.itemsize)
     assert L.orc_sizeof_config() == C.sizeof(OrcConfig)
     assert L.orc_sizeof_dw_config() == C.sizeof(OrcDwConfig) and L.orc_sizeof_dw_state() == DW_DTYPE.itemsize
     assert L.orc_sizeof_act_config() == C.sizeof(OrcActConfig) and L.orc_sizeof_act_state() == ACT_DTYPE.itemsize == 152
+    assert L.orc_sizeof_sens_config() == C.sizeof(OrcSensConfig) and L.orc_sizeof_sens_state() == SENS_DTYPE.itemsize == 524
     _lib = L
     return L
 
@@ -252,6 +272,19 @@ def make_act_config(cfg, actuator):
     return c
 
 
+def make_sens_config(sensor):
+    """orc_sens_config from a SensorModel-like object (latency range, 13 bias amplitudes or one number, resample); lat_on / bias_on
+    follow the header's "off" rule (orc_sens_rule)."""
+    c = OrcSensConfig()
+    c.latency[:] = [int(v) for v in sensor.latency]
+    bias = sensor.bias
+    c.bias_amp[:] = [float(bias)] * OBS_DIM if isinstance(bias, (int, float)) else [float(v) for v in bias]
+    c.resample = int(sensor.resample)
+    assert 0 <= c.latency[0] <= c.latency[1] <= 8 and all(v >= 0.0 for v in c.bias_amp)
+    lib().orc_sens_rule(C.byref(c))
+    return c
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -259,13 +292,16 @@ def _p(a):
 class OracleVecEnv:
     """N oracle envs stepped the way SubprocVecEnv + Monitor + NormalizeObservation would."""
 
-    def __init__(self, cfg, num_envs, threads=1, dynamics=None, wind=None, actuator=None):
+    def __init__(self, cfg, num_envs, threads=1, dynamics=None, wind=None, actuator=None, sensor=None):
         """dynamics / wind (optional): the per-drone body scales and wind of dn_enable_dynamics / dn_enable_wind, configured like
         the package's DynamicsRandomization / WindDisturbance.  self.dw (DW_DTYPE [n]) holds their state -- scales of 1 and still
         air until the first episode start draws, as after the first dn_enable_* -- and may be overwritten (teacher forcing).
         actuator (optional): the command latency and motor lag of dn_enable_actuator, configured like the package's ActuatorModel.
         self.act (ACT_DTYPE [n], the rows of dn_get_actuator) starts as after the first enable (d = 0, a = 0, r = rpm_fill, history =
-        fill) and may be overwritten too."""
+        fill) and may be overwritten too.
+        sensor (optional): the observation latency and bias of dn_enable_sensor, configured like the package's SensorModel.  self.sens
+        (SENS_DTYPE [n], the arrays of dn_get_sensor: latency, bias, history) starts as after the first enable (all zero) and may be
+        overwritten too."""
         self.L = lib()
         self.cfg = cfg
         self.n = int(num_envs)
@@ -276,6 +312,8 @@ class OracleVecEnv:
         self.dw = np.zeros(self.n, dtype=DW_DTYPE)
         self.dw["dyn"] = 1.0
         self.enable_actuator(actuator)
+        self.sens_cfg, self.sens = None, np.zeros(self.n, dtype=SENS_DTYPE)
+        self.enable_sensor(sensor)
 
     def enable_actuator(self, actuator):
         """The first dn_enable_actuator (None: off): the configuration, and the state d = 0, a = 0, r = rpm_fill, history = fill."""
@@ -283,6 +321,14 @@ class OracleVecEnv:
         self.act = np.zeros(self.n, dtype=ACT_DTYPE)
         if self.act_cfg is not None:
             self.L.orc_act_init(C.byref(self.act_cfg), _p(self.act), self.n)
+
+    def enable_sensor(self, sensor):
+        """dn_enable_sensor (None: off).  The first enable sets d = 0, b = 0 and an all-zero history; a later one changes the
+        configuration and keeps the current values."""
+        first = self.sens_cfg is None
+        self.sens_cfg = None if sensor is None else make_sens_config(sensor)
+        if self.sens_cfg is not None and first:
+            self.L.orc_sens_init(C.byref(self.sens_cfg), _p(self.sens), self.n)
 
     def _dw_args(self):
         if self.dw_cfg is None:
@@ -296,9 +342,16 @@ class OracleVecEnv:
         assert self.act.dtype == ACT_DTYPE and self.act.flags.c_contiguous and len(self.act) == self.n
         return C.byref(self.act_cfg), _p(self.act)
 
+    def _sens_args(self):
+        if self.sens_cfg is None:
+            return None, None
+        assert self.sens.dtype == SENS_DTYPE and self.sens.flags.c_contiguous and len(self.sens) == self.n
+        return C.byref(self.sens_cfg), _p(self.sens)
+
     def reset(self):
         obs = np.empty((self.n, OBS_DIM), np.float32)
-        self.L.orc_vec_reset_act(C.byref(self.cfg), *self._dw_args(), *self._act_args(), _p(self.envs), self.n, _p(obs), self.threads)
+        self.L.orc_vec_reset_sens(C.byref(self.cfg), *self._dw_args(), *self._act_args(), *self._sens_args(), _p(self.envs), self.n,
+                                  _p(obs), self.threads)
         return obs
 
     def refresh_rpy(self):
@@ -313,10 +366,10 @@ class OracleVecEnv:
             found_targets=np.empty(self.n, np.int32), terminal_obs=np.zeros((self.n, OBS_DIM), np.float32),
             ep_ret=np.zeros(self.n, np.float32), ep_len=np.zeros(self.n, np.int32),
             terminated=np.empty(self.n, np.uint8))
-        self.L.orc_vec_step_act(C.byref(self.cfg), *self._dw_args(), *self._act_args(), _p(self.envs), self.n, _p(a), _p(out["obs"]),
-                            _p(out["reward"]), _p(out["done"]), _p(out["truncated"]), _p(out["found_targets"]),
-                            _p(out["terminal_obs"]), _p(out["ep_ret"]), _p(out["ep_len"]), _p(out["terminated"]),
-                            self.threads)
+        self.L.orc_vec_step_sens(C.byref(self.cfg), *self._dw_args(), *self._act_args(), *self._sens_args(), _p(self.envs), self.n,
+                                 _p(a), _p(out["obs"]), _p(out["reward"]), _p(out["done"]), _p(out["truncated"]),
+                                 _p(out["found_targets"]), _p(out["terminal_obs"]), _p(out["ep_ret"]), _p(out["ep_len"]),
+                                 _p(out["terminated"]), self.threads)
         return out
 
 

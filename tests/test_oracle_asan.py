@@ -1,7 +1,7 @@
 """Sanitizer run of the CPU restatement ("ASan on the CPU restatement"; GPU ASan is not available on the
 pool): oracle/liboracle_asan.so is the same dn_oracle.c built with -fsanitize=address,undefined, and the golden-fixture
-replays of tests/test_oracle_golden.py, the dynamics / wind tests of tests/test_oracle_dynamics_wind.py and the actuator tests of
-tests/test_oracle_actuator.py run under it in a child process with libasan preloaded.  Any out-of-bounds access,
+replays of tests/test_oracle_golden.py, the dynamics / wind tests of tests/test_oracle_dynamics_wind.py, the actuator tests of
+tests/test_oracle_actuator.py and the sensor tests of tests/test_oracle_sensor.py run under it in a child process with libasan preloaded.  Any out-of-bounds access,
 use of uninitialised stack, signed overflow or misaligned access in the restatement aborts that child."""
 import os
 import subprocess
@@ -45,6 +45,12 @@ def test_golden_replays_are_clean_under_asan_and_ubsan():
     assert "passed" in r.stdout and "AddressSanitizer" not in tail and "runtime error" not in tail, tail
     # the actuator model of the restatement (orc_*_act), every test of its own file
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_oracle_actuator.py"), "-x", "-q",
+                        "-p", "no:cacheprovider"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    tail = (r.stdout + r.stderr)[-3000:]
+    assert r.returncode == 0, tail
+    assert "passed" in r.stdout and "AddressSanitizer" not in tail and "runtime error" not in tail, tail
+    # the sensor model of the restatement (orc_*_sens), every test of its own file
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_oracle_sensor.py"), "-x", "-q",
                         "-p", "no:cacheprovider"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     tail = (r.stdout + r.stderr)[-3000:]
     assert r.returncode == 0, tail
