@@ -85,6 +85,10 @@ class DnSensorConfig(C.Structure):
     _fields_ = [("latency", C.c_int32 * 2), ("bias_amp", C.c_float * 13), ("resample", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DnPrivilegedConfig(C.Structure):
+    _fields_ = [("groups", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every entry point declared in include/dronenav.h: name -> (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 PROTOTYPES = {
@@ -140,6 +144,9 @@ PROTOTYPES = {
     "dn_set_sensor": (_I32, [_VP, _VP, _VP, _VP, _VP]),
     "dn_get_sensor": (_I32, [_VP, _VP, _VP, _VP, _VP]),
     "dn_get_sensor_config": (_I32, [_VP, C.POINTER(DnSensorConfig)]),
+    "dn_enable_privileged": (_I32, [_VP, C.POINTER(DnPrivilegedConfig)]),
+    "dn_get_privileged_config": (_I32, [_VP, C.POINTER(DnPrivilegedConfig)]),
+    "dn_bind_privileged": (_I32, [_VP, _VP, _VP, _I64]),
 }
 
 _lib = None

@@ -102,6 +102,13 @@ class RolloutGather:
         return self.recv[:, 0].permute(1, 0, 2), self.recv[:, 1].permute(1, 0, 2)      # [T, R, n] views, no copy
 
 
+def _refuse_privileged(env, who):
+    """The collectors built on the 16-input policy kernels (dn_mlp_forward takes obs_dim <= 16) cannot feed a critic the 52-wide rows."""
+    if getattr(env, "privileged", None) is not None:
+        raise ValueError(f"{who} does not carry privileged observations (its critic kernel, dn_mlp_forward, takes at most 16 inputs); "
+                         "use RolloutCollector(..., value_input='privileged') with a torch value_fn")
+
+
 class RolloutCollector:
     """n_steps x (policy -> dn_step) on one GPU's shard, then GAE (+ optional all-gather).
 
@@ -115,13 +122,27 @@ class RolloutCollector:
     doubles as the warm-up) and replayed afterwards: the loop is launch-bound (a 13->512->512->256 MLP step is a
     dozen small kernels), and a graph replay takes the host out of it.  Every tensor the loop touches is a static
     buffer; the environment's vector-step counter lives on the device, so noise streams keep advancing under replay.
-    The policy must be capture-safe (no host synchronisation, no data-dependent shapes)."""
+    The policy must be capture-safe (no host synchronisation, no data-dependent shapes).
+
+    `value_input="privileged"` (asymmetric actor-critic; the env needs privileged=PrivilegedObservation(...), and `value_fn` is
+    required): the critic sees the env's privileged rows [N, 52] instead of the observation -- `values[t]` is value_fn of the rows that
+    go with `obs[t]`, the truncation bootstrap is value_fn of the TERMINAL privileged rows (the true terminal state with the finished
+    episode's parameters, where the terminal observation is the delayed and biased one), `last_values` is value_fn of the last rows,
+    and the buffer dict gains `privileged` [n_steps, N, 52].  The policy's own value output is ignored."""
 
     def __init__(self, env, policy, n_steps, *, value_fn=None, gamma=0.99, gae_lambda=0.95, bootstrap_truncated=True,
-                 gather=False, group=None, use_graph=False):
+                 gather=False, group=None, use_graph=False, value_input="observation"):
         from .vec_env import ACT_DIM, DroneVecEnv
         if not isinstance(env, DroneVecEnv):
             raise TypeError("RolloutCollector drives a DroneVecEnv (HIP); there is no CPU path")
+        if value_input not in ("observation", "privileged"):
+            raise ValueError(f"value_input must be 'observation' or 'privileged', got {value_input!r}")
+        self.value_privileged = value_input == "privileged"
+        if self.value_privileged:
+            if env.privileged is None:
+                raise ValueError("value_input='privileged' needs an env built with privileged=PrivilegedObservation(...)")
+            if value_fn is None:
+                raise ValueError("value_input='privileged' needs value_fn: the policy's own value head sees the observation")
         self.env, self.policy, self.value_fn = env, policy, value_fn
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
         self.bootstrap_truncated, self.gather, self.group = bool(bootstrap_truncated), bool(gather), group
@@ -142,6 +163,9 @@ class RolloutCollector:
             last_values=torch.empty(n, dtype=f32, device=dev), last_dones=torch.empty(n, dtype=torch.uint8, device=dev))
         self._clipped = torch.empty((n, ACT_DIM), dtype=f32, device=dev)
         self._last_obs = env.reset_tensor().clone()
+        if self.value_privileged:
+            self.buf["privileged"] = torch.empty((T, n, env.privileged.shape[1]), dtype=f32, device=dev)
+            self._last_priv = env.privileged.clone()
         self._last_done = torch.ones(n, dtype=torch.uint8, device=dev)       # SB3: _last_episode_starts = True
         self.num_timesteps = 0
         self._graph = None
@@ -160,8 +184,12 @@ class RolloutCollector:
         import ctypes as C
         env, b = self.env, self.buf
         obs, done = self._last_obs, self._last_done
+        priv = self._last_priv if self.value_privileged else None
         for t in range(self.n_steps):
             actions, values, log_probs = self.policy(obs)
+            if priv is not None:
+                b["privileged"][t].copy_(priv)
+                values = self._values(priv)
             b["obs"][t].copy_(obs)
             b["episode_starts"][t].copy_(done)
             b["values"][t].copy_(values.reshape(-1))
@@ -171,13 +199,19 @@ class RolloutCollector:
             next_obs, reward, next_done, info = env.step_tensor(self._clipped, want_terminal=self.bootstrap_truncated)
             if self.bootstrap_truncated:
                 # rows of terminal_obs are valid only where done; `truncated` is zero elsewhere
-                tv = self._values(torch.where(next_done.bool()[:, None], info["terminal_obs"], next_obs),
-                                  row_mask=info["truncated"])
+                if priv is not None:
+                    tv = self._values(torch.where(next_done.bool()[:, None], info["terminal_privileged"], info["privileged"]),
+                                      row_mask=info["truncated"])
+                else:
+                    tv = self._values(torch.where(next_done.bool()[:, None], info["terminal_obs"], next_obs),
+                                      row_mask=info["truncated"])
                 reward = reward + self.gamma * tv * info["truncated"].to(reward.dtype)
             b["rewards"][t].copy_(reward)
             obs.copy_(next_obs)
             done.copy_(next_done)
-        b["last_values"].copy_(self._values(obs))
+            if priv is not None:
+                priv.copy_(info["privileged"])
+        b["last_values"].copy_(self._values(obs if priv is None else priv))
         b["last_dones"].copy_(done)
         dev = env.device
         _capi.check(_capi.load().dn_gae(
@@ -322,6 +356,7 @@ class OffPolicyCollector:
     def __init__(self, env, actor, buffer_size, *, seed=0, deterministic=False, fused_sample=True):
         from .policy_mfma import FusedSacActor
         from .vec_env import ACT_DIM, DroneVecEnv
+        _refuse_privileged(env, "OffPolicyCollector")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("OffPolicyCollector drives a DroneVecEnv (HIP); there is no CPU path")
         self.env, self.actor = env, actor
@@ -437,6 +472,7 @@ class FusedRolloutCollector:
                  group=None, use_graph=True, seed=0, one_launch=False):
         from .policy_mfma import FusedMlpPolicy
         from .vec_env import ACT_DIM, OBS_DIM, DroneVecEnv
+        _refuse_privileged(env, "FusedRolloutCollector")
         if not isinstance(env, DroneVecEnv) or not isinstance(policy, FusedMlpPolicy):
             raise TypeError("FusedRolloutCollector needs a DroneVecEnv and a FusedMlpPolicy (HIP); there is no CPU path")
         if env.num_envs % 4 or env.obs_dim != OBS_DIM:

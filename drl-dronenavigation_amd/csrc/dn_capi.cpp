@@ -99,6 +99,7 @@ struct dn_env {
     dn_wind_config wind_cfg = {};
     dn_actuator_config act_cfg = {};
     dn_sensor_config sens_cfg = {};
+    dn_privileged_config priv_cfg = {};
 };
 
 thread_local hipEvent_t dn_tl_ev_start = nullptr, dn_tl_ev_stop = nullptr;
@@ -308,15 +309,23 @@ int32_t init_state(dn_env *e, hipStream_t s)
 // The per-drone models, shallowest first (the order of the kernels' argument chain, dn_kernels.hip SensArg).  dn_destroy and the entry
 // points that carry none of them walk this table; a new model is one more row.
 struct ModelRow {
-    float4 *&(*slot)(DnModels &);   // the pointer that owns the model's allocation: non-null = the model is on
+    void *(*slot)(const DnModels &);    // the pointer that owns the model's allocation, nullptr where it owns none
+    bool (*on)(const DnModels &);
     const char *phrase, *enable;    // how a refusal names the model, and the entry point that turns it on
     const char *replay;             // what dn_eval_kinematics does that the model would falsify
 };
 const ModelRow MODELS[] = {
-    {[](DnModels &m) -> float4 *& { return m.dyn.dyn; }, "the randomised dynamics", "dn_enable_dynamics", "replays a given nominal-body transition"},
-    {[](DnModels &m) -> float4 *& { return m.wind.mean; }, "the wind", "dn_enable_wind", "replays a given still-air transition"},
-    {[](DnModels &m) -> float4 *& { return m.act.hist; }, "the actuator model", "dn_enable_actuator", "replays a given transition"},
-    {[](DnModels &m) -> float4 *& { return m.sens.ring; }, "the sensor model", "dn_enable_sensor", "reports the observation of the given transition"},
+    {[](const DnModels &m) -> void * { return m.dyn.dyn; }, [](const DnModels &m) { return m.dyn.dyn != nullptr; }, "the randomised dynamics",
+     "dn_enable_dynamics", "replays a given nominal-body transition"},
+    {[](const DnModels &m) -> void * { return m.wind.mean; }, [](const DnModels &m) { return m.wind.mean != nullptr; }, "the wind", "dn_enable_wind",
+     "replays a given still-air transition"},
+    {[](const DnModels &m) -> void * { return m.act.hist; }, [](const DnModels &m) { return m.act.hist != nullptr; }, "the actuator model",
+     "dn_enable_actuator", "replays a given transition"},
+    {[](const DnModels &m) -> void * { return m.sens.ring; }, [](const DnModels &m) { return m.sens.ring != nullptr; }, "the sensor model",
+     "dn_enable_sensor", "reports the observation of the given transition"},
+    // the rows are the caller's memory: nothing to free
+    {[](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.priv.groups != 0; }, "the privileged observations",
+     "dn_enable_privileged", "writes no privileged rows"},
 };
 
 // DN_OK, or the refusal of entry point `who`, whose kernels carry no model, for the first model that is on.  `instead` names the calls
@@ -324,7 +333,7 @@ const ModelRow MODELS[] = {
 int32_t refuse_models(dn_env *env, const char *who, const char *instead)
 {
     for (const ModelRow &r : MODELS) {
-        if (!r.slot(env->m)) continue;
+        if (!r.on(env->m)) continue;
         if (!instead) return fail(DN_ERR_INVALID_ARGUMENT, "%s %s: refused with %s (%s)", who, r.replay, r.phrase, r.enable);
         return fail(DN_ERR_INVALID_ARGUMENT, "%s does not carry %s (%s); %s", who, r.phrase, r.enable, instead);
     }
@@ -826,6 +835,9 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
     if (((uintptr_t)actions & 15u) || ((uintptr_t)obs & 15u))
         return fail(DN_ERR_INVALID_ARGUMENT, "actions and obs must be 16-byte aligned");
     if (k > (1 << 30)) return fail(DN_ERR_INVALID_ARGUMENT, "k too large");
+    if (env->m.priv.groups && env->m.priv.rows && k > env->m.priv.cap)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_many: k = %lld exceeds the %lld steps the privileged rows hold (dn_bind_privileged capacity_steps)",
+                    (long long)k, env->m.priv.cap);
     // one fused launch: the state stays in registers for all k steps (dn_step_many_kernel)
     const DnStepIO io = make_io(actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask);
     DN_REFUSE_ARMED_CAPTURE(stream);
@@ -1295,6 +1307,52 @@ int32_t dn_get_sensor_config(const dn_env *env, dn_sensor_config *out)
     if (!env->m.sens.ring) return 0;
     *out = env->sens_cfg;
     return 1;
+}
+
+int32_t dn_enable_privileged(dn_env *env, const dn_privileged_config *cfg)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    // the mask first: it needs no env (and no device) to be wrong
+    if (cfg->groups == 0 || (cfg->groups & ~DN_PRIV_ALL))
+        return fail(DN_ERR_INVALID_ARGUMENT, "privileged groups = 0x%x: need a non-empty mask of DN_PRIV_OBS | DYN | WIND | ACT | SENS (0x%x)",
+                    (unsigned)cfg->groups, (unsigned)DN_PRIV_ALL);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    if (env->m.priv.groups) {                       // launches in flight carry the previous mask
+        DN_HIP(hipSetDevice(env->cfg.device_id));
+        DN_HIP(hipDeviceSynchronize());
+    }
+    env->m.priv.groups = cfg->groups;
+    env->priv_cfg = *cfg;
+    env->waves_fused = env->waves_single = 1;       // the rows are written by the one-wave option kernels only
+    return DN_OK;
+}
+
+int32_t dn_get_privileged_config(const dn_env *env, dn_privileged_config *out)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    if (!env->m.priv.groups) return 0;
+    *out = env->priv_cfg;
+    return 1;
+}
+
+int32_t dn_bind_privileged(dn_env *env, float *rows, float *terminal_rows, int64_t capacity_steps)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    DnPriv &pv = env->m.priv;
+    if (!pv.groups) return fail(DN_ERR_BAD_STATE, "the privileged observations are not enabled (dn_enable_privileged)");
+    if (!rows) {
+        if (terminal_rows) return fail(DN_ERR_INVALID_ARGUMENT, "terminal_rows without rows: rows = NULL unbinds both");
+        pv.rows = pv.term = nullptr;
+        pv.cap = 0;
+        return DN_OK;
+    }
+    if (((uintptr_t)rows & 15u) || ((uintptr_t)terminal_rows & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "rows and terminal_rows must be 16-byte aligned");
+    if (capacity_steps < 1) return fail(DN_ERR_INVALID_ARGUMENT, "capacity_steps must be >= 1 (got %lld)", (long long)capacity_steps);
+    pv.rows = rows;
+    pv.term = terminal_rows;
+    pv.cap = capacity_steps;
+    return DN_OK;
 }
 
 int32_t dn_get_step_count(const dn_env *env, uint64_t *out)

@@ -1589,6 +1589,66 @@ DN_DEV void sens_restart(const DnSens &sn, const long long n, const long long i,
     }
 }
 
+// ---- privileged observations (dn_enable_privileged) --------------------------------------------------------------------------
+// One row is thirteen 16-byte quads (include/dronenav.h); a lane writes its drone's quads as float4 stores into the 208-byte row.  Every
+// test of pv.groups is launch-uniform.  What a step kernel carries per lane: the step row and the terminal row of this step (the latter
+// null where unbound), and whether the drone's episode ended in this step.
+struct PrivCtx {
+    const DnPriv *pv;
+    float *row, *trow;
+    bool done, active;
+};
+template <bool ON> struct PrivRegs {
+    PrivCtx x;
+    float r_entry[4];
+};
+template <> struct PrivRegs<false> {};
+DN_DEV float4 *priv_quad(float *row, const int q) { return reinterpret_cast<float4 *>(row) + q; }
+// quads 0-3: the true observation
+DN_DEV void priv_store_obs(float *row, const float o[DN_OBS_DIM])
+{
+    *priv_quad(row, 0) = make_float4(o[0], o[1], o[2], o[3]);
+    *priv_quad(row, 1) = make_float4(o[4], o[5], o[6], o[7]);
+    *priv_quad(row, 2) = make_float4(o[8], o[9], o[10], o[11]);
+    *priv_quad(row, 3) = make_float4(o[12], 0.0f, 0.0f, 0.0f);
+}
+// observe_phase, on the columns as observe_columns left them: the step row where the episode goes on, the terminal row where it ended
+DN_DEV void priv_true_obs(const PrivCtx &x, const float o[DN_OBS_DIM])
+{
+    if (!(x.pv->groups & DN_PRIV_OBS) || !x.active) return;
+    if (!x.done) priv_store_obs(x.row, o);
+    else if (x.trow) priv_store_obs(x.trow, o);
+}
+// quads 4-8: scales, wind, rotor speeds and the quad of scalars, whose four columns belong to three groups (one store where all are selected)
+DN_DEV void priv_store_params(const DnPriv &pv, float *row, const float4 S, const float4 WB, const float4 WG, const float r[4], const int act_d,
+                              const float act_a, const int sens_d, const int steps)
+{
+    const int g = pv.groups;
+    if (g & DN_PRIV_DYN) *priv_quad(row, 4) = S;
+    if (g & DN_PRIV_WIND) {
+        *priv_quad(row, 5) = make_float4(WB.x, WB.y, WB.z, 0.0f);
+        *priv_quad(row, 6) = make_float4(WG.x, WG.y, WG.z, 0.0f);
+    }
+    if (g & DN_PRIV_ACT) *priv_quad(row, 7) = make_float4(r[0], r[1], r[2], r[3]);
+    constexpr int all = DN_PRIV_ACT | DN_PRIV_SENS | DN_PRIV_OBS;
+    if ((g & all) == all) *priv_quad(row, 8) = make_float4((float)act_d, act_a, (float)sens_d, (float)steps);
+    else {
+        if (g & DN_PRIV_ACT) { row[32] = (float)act_d; row[33] = act_a; }
+        if (g & DN_PRIV_SENS) row[34] = (float)sens_d;
+        if (g & DN_PRIV_OBS) row[35] = (float)steps;
+    }
+}
+// quads 9-12: the sensor bias as it stands in memory (zeros without the sensor model)
+DN_DEV void priv_store_bias(const DnPriv &pv, float *row, const DnSens &sn, const long long n, const long long i)
+{
+    if (!(pv.groups & DN_PRIV_SENS)) return;
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 a = z, b = z, c = z, d = z;
+    if (sn.ring) { a = sn.bias[i]; b = sn.bias[n + i]; c = sn.bias[2 * n + i]; d = sn.bias[3 * n + i]; }
+    *priv_quad(row, 9) = a; *priv_quad(row, 10) = b; *priv_quad(row, 11) = c;
+    *priv_quad(row, 12) = make_float4(d.x, 0.0f, 0.0f, 0.0f);
+}
+
 // DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
 // WIND (with DYN): the wind force *wf over the mass of *dk joins the extra accelerations
 template <typename R, typename TH = Thrust, bool XOPT = false, bool DYN = false, bool WIND = false>
@@ -2012,13 +2072,15 @@ DN_DEV void reward_candidates(const DnParams &p, const DnConsts<R> &c, const R *
     reward_pose<R>(p, s_tab, fl, q, r_normal, r_found32);
 }
 // SENS (the one-wave kernels with dn_enable_sensor): *sx is the kernel's own register copy; the delivered row replaces the true one
-template <typename R, bool NORM, bool NOISE, bool SENS = false>
+// PRIV (with SENS, dn_enable_privileged): the true row leaves for the privileged rows from the registers that hold it, before the noise
+template <typename R, bool NORM, bool NOISE, bool SENS = false, bool PRIV = false>
 DN_DEV Observed<R> observe_phase(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const Flight<R> &fl,
                                  const float4 G4, const float4 G5, const unsigned long long gid, const unsigned long long step_count,
-                                 Rms &rms, SensCtx *sx = nullptr)
+                                 Rms &rms, SensCtx *sx = nullptr, const PrivCtx *px = nullptr)
 {
     Observed<R> ob;
     observe_columns<R>(p, c, fl, ob.o);
+    if constexpr (PRIV) priv_true_obs(*px, ob.o);
     reward_candidates<R>(p, c, s_tab, fl, G4, G5, ob.r_normal, ob.r_found32);
     // sensor noise / per-drone normaliser act on the step observation (which is also terminal_observation)
     if (NOISE && p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, step_count, 1u, ob.o);
@@ -2200,10 +2262,11 @@ DN_DEV void report_scalars(const DnParams &p, const DnConsts<R> &c, const StepOu
     }
     if (out.done_word && lane == 0) *out.done_word = done_ballot;
 }
-template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false, bool SENS = false>
+template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false, bool SENS = false, bool PRIV = false>
 DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const bool truncated,
                        const Verdict<R> &v, float *o, const unsigned long long gid, const unsigned long long step_count,
-                       const unsigned li, const unsigned lane, const unsigned rows, const bool active, Rms &rms, SensCtx *sx = nullptr)
+                       const unsigned li, const unsigned lane, const unsigned rows, const bool active, Rms &rms, SensCtx *sx = nullptr,
+                       const PrivCtx *px = nullptr)
 {
     const bool done = v.terminated != 0 || truncated;
     const unsigned long long done_mask = __ballot(done && active);
@@ -2223,6 +2286,9 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
 #pragma unroll
                 for (int k = 0; k < 3; ++k) o[k] = (float)((R)(float)q[k] * c.inv_dim[k]);
             }
+            if constexpr (PRIV) {                                         // the new episode's noise-free reset row is its true observation
+                if ((px->pv->groups & DN_PRIV_OBS) && active) priv_store_obs(px->row, o);
+            }
             if (across) add_obs_noise_drawn(p, zr, o);
             else if (NOISE && p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, step_count, 5u, o);
             if constexpr (SENS) {
@@ -2236,14 +2302,15 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
     else if (TILE == 1) tile_park(s_tile, lane, o);        // streamed out by the caller one step later
     else store_obs_tile(s_tile, out.obs, rows, lane, o);
 }
-template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false, bool SENS = false>
+template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false, bool SENS = false, bool PRIV = false>
 DN_DEV void report_phase(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const Flight<R> &fl,
                          const Verdict<R> &v, Observed<R> &ob, const unsigned long long gid, const unsigned long long step_count,
                          const unsigned li, const unsigned lane, const unsigned rows, const bool active,
-                         float4 &G4, float4 &G5, StatAcc &acc, Rms &rms, RewNorm &rn, SensCtx *sx = nullptr)
+                         float4 &G4, float4 &G5, StatAcc &acc, Rms &rms, RewNorm &rn, SensCtx *sx = nullptr, const PrivCtx *px = nullptr)
 {
     report_scalars<R, REW>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn);
-    report_obs<R, NORM, NOISE, TILE, SPAWN, SENS>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active, rms, sx);
+    report_obs<R, NORM, NOISE, TILE, SPAWN, SENS, PRIV>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active, rms,
+                                                        sx, px);
 }
 
 struct BlockState {
@@ -2359,17 +2426,24 @@ struct ActArg : WindArg {
 struct SensArg : ActArg {
     DnSens s;
 };
-template <bool DYN, bool WIND, bool ACT = false, bool SENS = false> struct StepArg { using type = DynArg<DYN>; };
-template <> struct StepArg<true, true, false, false> { using type = WindArg; };
-template <> struct StepArg<true, true, true, false> { using type = ActArg; };
-template <> struct StepArg<true, true, true, true> { using type = SensArg; };
+// PRIV (with SENS, ACT, WIND, DYN and XOPT): the argument carries dn_bind_privileged's rows as well (PrivArg); the sensor's pointers are null
+// when the sensor model is off (latency 0, no bias, no ring).
+struct PrivArg : SensArg {
+    DnPriv pv;
+};
+template <bool DYN, bool WIND, bool ACT = false, bool SENS = false, bool PRIV = false> struct StepArg { using type = DynArg<DYN>; };
+template <> struct StepArg<true, true, false, false, false> { using type = WindArg; };
+template <> struct StepArg<true, true, true, false, false> { using type = ActArg; };
+template <> struct StepArg<true, true, true, true, false> { using type = SensArg; };
+template <> struct StepArg<true, true, true, true, true> { using type = PrivArg; };
 template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false, bool ACT = false,
-          bool SENS = false>
+          bool SENS = false, bool PRIV = false>
 __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg,
-                                                                   const typename StepArg<DYN, WIND, ACT, SENS>::type dy)
+                                                                   const typename StepArg<DYN, WIND, ACT, SENS, PRIV>::type dy)
 {
     static_assert(!ACT || (WIND && DYN && XOPT && !SAMPLE), "the actuator rides on the option kernels with the body terms and the wind");
     static_assert(!SENS || ACT, "the sensor model rides on the option kernels with the actuator");
+    static_assert(!PRIV || SENS, "the privileged rows ride on the option kernels with the sensor model");
     const int k_steps = ONE ? 1 : k_arg;
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -2411,7 +2485,9 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     if constexpr (ACT) {
         if (act_have) LAT = dy.a.lat[i];
         LAT = LAT < 0 ? 0 : (LAT > DN_MAX_LATENCY ? DN_MAX_LATENCY : LAT);      // dn_set_actuator does not validate: the history is 8 deep
-        if (dy.a.lag_on) {
+        bool lag_load = dy.a.lag_on != 0;
+        if constexpr (PRIV) lag_load = act_have;        // the rows report r and a with the filter off too (registers mirror memory)
+        if (lag_load) {
             const float4 r4 = dy.a.rpm[i];
             lag.r[0] = r4.x; lag.r[1] = r4.y; lag.r[2] = r4.z; lag.r[3] = r4.w;
             lag.a = dy.a.coeff[i];
@@ -2431,8 +2507,18 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
     SensCtx sx = {nullptr, p.n, i, 0, 0, active};
     if constexpr (SENS) {
         sx.sn = &dy.s;
-        const int sd = dy.s.lat[i];
+        int sd = 0;
+        if constexpr (PRIV) { if (dy.s.ring) sd = dy.s.lat[i]; }       // PRIV: the sensor model itself may be off (null pointers: no delay, no bias)
+        else sd = dy.s.lat[i];
         sx.d = sd < 0 ? 0 : (sd > DN_MAX_LATENCY ? DN_MAX_LATENCY : sd);        // dn_set_sensor does not validate: the ring serves 8 steps back
+    }
+    // dn_enable_privileged: the rows of this drone in step slot 0; the launch is of this family only while rows are bound
+    // (the registers exist in the PRIV kernels only: PrivRegs<false> is empty, so that every other kernel keeps its instruction stream)
+    PrivRegs<PRIV> pr;
+    const PrivCtx *px = nullptr;
+    if constexpr (PRIV) {
+        pr.x = {&dy.pv, dy.pv.rows + i * DN_PRIV_DIM, dy.pv.term ? dy.pv.term + i * DN_PRIV_DIM : nullptr, false, active};
+        px = &pr.x;
     }
     const R wp0[3] = {s_tab[DN_T_WP], s_tab[DN_T_WP + 1], s_tab[DN_T_WP + 2]};   // waypoint 0: every reset measures against it
     StatAcc acc;
@@ -2458,11 +2544,24 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         const GateRow<R> row_e = load_gate_row<R>(s_tab, unpack_meta(G3.w).idx);
         WindF<R> wf;
         if constexpr (WIND) wf = wind_force<R>(dy.w, WB, WG);
+        if constexpr (PRIV) {                           // the rotor speeds this step is entered with (the terminal row's)
+            pr.r_entry[0] = lag.r[0]; pr.r_entry[1] = lag.r[1]; pr.r_entry[2] = lag.r[2]; pr.r_entry[3] = lag.r[3];
+        }
         Flight<R> fl = fly<R, NOISE, XOPT, DYN, WIND, ACT>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr,
                                                            DYN ? &dk : nullptr, WIND ? &wf : nullptr, &lag, lag_on);
         const float4 G0e = G0, G3e = G3;
         const Verdict<R> v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc);
         if (XOPT && p.drag) G7 = (v.terminated || fl.truncated) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : rpm_now;   // BaseAviary.py:442,545
+        if constexpr (PRIV) {
+            // the terminal row's parameters are those the step was ENTERED with: stored before the episode starts below redraw them
+            pr.x.done = v.terminated || fl.truncated;
+            if (pr.x.trow && __ballot(pr.x.done) != 0ull) {     // wave-uniform: most wave-steps skip this
+                if (pr.x.done && active) {
+                    priv_store_params(dy.pv, pr.x.trow, S, WB, WG, pr.r_entry, LAT, lag.a, sx.d, unpack_meta(G3e.w).steps + 1);
+                    priv_store_bias(dy.pv, pr.x.trow, dy.s, n, i);
+                }
+            }
+        }
         if constexpr (DYN) {
             if (dy.resample) {       // the body reloaded by the auto-reset (rules_commit) is a new draw, flown from the next step on
                 const bool done = v.terminated || fl.truncated;
@@ -2496,9 +2595,18 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         }
         attitude_phase<R>(fl);
         if constexpr (SENS) sx.k = unpack_meta(G3e.w).steps + 1;    // control steps of the episode flown once this step is over
-        Observed<R> ob = observe_phase<R, NORM, NOISE, SENS>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx);
-        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, SENS>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn,
-                                                          &sx);
+        Observed<R> ob = observe_phase<R, NORM, NOISE, SENS, PRIV>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx, px);
+        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, SENS, PRIV>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms,
+                                                                rn, &sx, px);
+        if constexpr (PRIV) {
+            // the step row's parameters: what the getters would return after this step (a restarted drone: the new episode's draws)
+            if (active) {
+                priv_store_params(dy.pv, pr.x.row, S, WB, WG, lag.r, LAT, lag.a, sx.d, unpack_meta(G3.w).steps);
+                priv_store_bias(dy.pv, pr.x.row, dy.s, n, i);
+            }
+            pr.x.row += n * DN_PRIV_DIM;
+            if (pr.x.trow) pr.x.trow += n * DN_PRIV_DIM;
+        }
         A = A_next;
     }
     if (ONE) flush_stats_preloaded(p, slot0, acc, sc0 + 1ull, lane, (long long)blockIdx.x);
@@ -4071,7 +4179,7 @@ __global__ __launch_bounds__(3 * DN_BLOCK) void dn_step_pqx_kernel(const DnParam
 // =====================================================================================================
 template <typename R>
 __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd, const DnAct ac,
-                                                            const DnSens sn)
+                                                            const DnSens sn, const DnPriv pv)
 {
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -4102,6 +4210,8 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
         cpx = (R)sx; cpy = (R)sy; cpz = (R)sz;
         o[0] = (float)((R)sx * c.inv_dim[0]); o[1] = (float)((R)sy * c.inv_dim[1]); o[2] = (float)((R)sz * c.inv_dim[2]);
     }
+    float *const prow = pv.rows ? pv.rows + i * DN_PRIV_DIM : nullptr;       // dn_bind_privileged: the fresh episode's step row, slot 0
+    if (prow && (pv.groups & DN_PRIV_OBS) && active) priv_store_obs(prow, o);     // the noise-free reset row is the true observation
     if (p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, p.st.stats[blockIdx.x].step_count, 5u, o);
     if (sn.ring && (sn.lat_on || sn.bias_on)) {      // dn_enable_sensor: this episode's d and b; o_0 seeds the ring where the first step (k = 1) looks one step back
         const unsigned long long sc = p.st.stats[blockIdx.x].step_count;
@@ -4140,6 +4250,16 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
                 ac.lat[i] = d;
                 ac.coeff[i] = a;
             }
+        }
+        if (prow) {         // the parameter columns: the models' values as this kernel leaves them (its own stores above, read back)
+            const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            const float4 S = dy.dyn ? dy.dyn[i] : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+            const float4 WB = wd.mean ? wd.mean[i] : z4, WG = wd.mean ? wd.gust[i] : z4;
+            const float4 r4 = ac.hist ? ac.rpm[i] : z4;
+            const float r[4] = {r4.x, r4.y, r4.z, r4.w};
+            const int ad = ac.hist ? ac.lat[i] : 0, sd = sn.ring ? sn.lat[i] : 0;
+            priv_store_params(pv, prow, S, WB, WG, r, clipv(ad, 0, DN_MAX_LATENCY), ac.hist ? ac.coeff[i] : 0.0f, clipv(sd, 0, DN_MAX_LATENCY), 0);
+            priv_store_bias(pv, prow, sn, p.n, i);
         }
     }
     store_obs_tile(s_tile, obs + tile_base * DN_OBS_DIM, rows, lane, o);
@@ -4537,10 +4657,11 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 namespace {
 // The one-wave option kernel of one family of per-drone models (dn_enable_*): DYN always, then WIND, ACT, SENS in that order;
 // `arg` is the slice of the SensArg chain the family's kernels take.
-template <bool WIND, bool ACT, bool SENS> void launch_models(const StepLaunch &L, const typename StepArg<true, WIND, ACT, SENS>::type &arg)
+template <bool WIND, bool ACT, bool SENS, bool PRIV = false>
+void launch_models(const StepLaunch &L, const typename StepArg<true, WIND, ACT, SENS, PRIV>::type &arg)
 {
     dn_bools([&](auto F32, auto NORM, auto NOISE, auto ONE) {
-        DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, ONE, true, false, true, WIND, ACT, SENS>), L.grid, dim3(DN_BLOCK), 0,
+        DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, ONE, true, false, true, WIND, ACT, SENS, PRIV>), L.grid, dim3(DN_BLOCK), 0,
                    L.stream, L.p, L.io, L.k, arg);
     }, L.f32, L.norm, L.noise, L.k == 1);
 }
@@ -4549,16 +4670,21 @@ template <bool WIND, bool ACT, bool SENS> void launch_models(const StepLaunch &L
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnModels *m)
 {
     const StepLaunch L(p, io, k, f32, stream);
-    if (m && (m->dyn.dyn || m->wind.mean || m->act.hist || m->sens.ring)) {
+    const bool priv = m && m->priv.groups && m->priv.rows;      // enabled AND bound: unbound, nothing is written and the family below serves
+    if (m && (m->dyn.dyn || m->wind.mean || m->act.hist || m->sens.ring || priv)) {
         // a model is on: the deepest enabled family's kernel, whatever `waves` says.  A model that is off rides along as its
         // value-initialised struct (null pointers): the nominal body, still air, no latency, no bias.
         if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels carry no model (the C ABI refuses them first)
-        SensArg sa;
+        PrivArg sa;
         static_cast<DnDyn &>(sa) = m->dyn;
         sa.w = m->wind;
         sa.a = m->act;
         sa.s = m->sens;
-        if (m->sens.ring) launch_models<true, true, true>(L, sa);
+        sa.pv = m->priv;
+        if (priv) {
+            if (k > m->priv.cap) return hipErrorInvalidValue;      // the C ABI refuses it first
+            launch_models<true, true, true, true>(L, sa);
+        } else if (m->sens.ring) launch_models<true, true, true>(L, sa);
         else if (m->act.hist) launch_models<true, true, false>(L, sa);
         else if (m->wind.mean) launch_models<true, false, false>(L, sa);
         else launch_models<false, false, false>(L, DynArg<true>{static_cast<const DnDyn &>(sa)});
@@ -4582,8 +4708,8 @@ hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t 
 {
     const DnModels on = m ? *m : DnModels{};
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens);
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv);
     return hipGetLastError();
 }
 

@@ -564,6 +564,58 @@ int32_t dn_get_sensor(dn_env *env, int32_t *latency, float *bias, float *history
 /* 1: sensor enabled, *out = the configuration last given to dn_enable_sensor; 0: not enabled (*out untouched); < 0: error. */
 int32_t dn_get_sensor_config(const dn_env *env, dn_sensor_config *out);
 
+/* Privileged observations (asymmetric actor-critic, teacher-student): the ground truth the four models above hide from the policy, written
+ * per drone and step by the step kernels themselves -- inside a fused launch too, where episodes restart and parameters are redrawn.  One
+ * row is DN_PRIV_DIM = 52 float32 (208 bytes), thirteen 16-byte quads; a group of columns is written when its bit is in `groups`:
+ *   columns  0..12  DN_PRIV_OBS   the TRUE observation: the observation columns of the state this step leaves, before obs_noise_sigma's
+ *                                 noise, before the sensor model and before the normaliser; 13..15 are 0
+ *           16..19  DN_PRIV_DYN   s_m, s_I, s_kf, s_km                                      (dn_get_dynamics)
+ *           20..22  DN_PRIV_WIND  wbar, 23 is 0;  24..26: g, 27 is 0                        (dn_get_wind)
+ *           28..31  DN_PRIV_ACT   the effective rotor speeds r                              (dn_get_actuator rpm)
+ *           32, 33  DN_PRIV_ACT   the actuator's latency d and coefficient a; d as a float32 number
+ *               34  DN_PRIV_SENS  the sensor's latency d, as a float32 number
+ *               35  DN_PRIV_OBS   the episode step counter (dn_env_state.steps), as a float32 number
+ *           36..48  DN_PRIV_SENS  the sensor bias b[13]; 49..51 are 0
+ *   step row (`rows`): where the episode goes on, the true observation of the new state; where it ended, the new episode's noise-free
+ *     reset observation -- as `obs` is the reset row there.  Every parameter column holds what the model's dn_get_* would return right
+ *     after this step: for a drone whose episode restarted, the NEW episode's draws, r = rpm_fill and step counter 0.  The latency
+ *     columns carry the values the kernels use, i.e. clamped to [0, DN_MAX_LATENCY].
+ *   terminal row (`terminal_rows`, optional): written only where done, like terminal_obs.  Columns 0..12 are the true observation of the
+ *     terminal state; every parameter column holds the value at the ENTRY of the terminal step (what dn_get_* returned before it: the
+ *     finished episode's body, wind, actuator and sensor); column 35 is the finished episode's length.
+ *   a model that is not enabled is written as its neutral value: scales 1, wind 0, d 0, a 0, r 0, bias 0.
+ *   a group that is not in `groups` is not written at all: the caller's bytes stay as they are (a launch-uniform branch per group: a
+ *     caller that wants the 64-byte true observation alone does not pay for 208 bytes).
+ *   nothing feeds back: every other output and every byte of state is that of the same env without the feature.
+ * The rows are a persistent binding (dn_bind_privileged), not an argument of dn_step: the entry points keep their signatures and a
+ * captured hipGraph keeps writing into the bound buffers.  Every launch rewrites all selected columns of every step row it covers; K steps
+ * in one launch equal K single steps bit for bit.  dn_reset writes the step row of the fresh episodes into step slot 0.
+ * The rows are written by one more family of the one-wave option kernels, which carries the four models (on or off): enabling forces
+ * dn_get_kernel_waves(env, 0 / 1) == 1.  dn_step_sampled, dn_step_squashed, dn_mlp_step_sampled and dn_eval_kinematics refuse an env with
+ * the feature enabled (DN_ERR_INVALID_ARGUMENT).
+ * Layout: groups at 0, reserved at 4; 8 bytes. */
+#define DN_PRIV_DIM 52
+#define DN_PRIV_OBS 1
+#define DN_PRIV_DYN 2
+#define DN_PRIV_WIND 4
+#define DN_PRIV_ACT 8
+#define DN_PRIV_SENS 16
+#define DN_PRIV_ALL 31
+typedef struct dn_privileged_config {
+    int32_t groups;       /* mask of DN_PRIV_*: non-zero, known bits only */
+    int32_t reserved;     /* must be 0 */
+} dn_privileged_config;
+/* Validates the mask and enables the feature; a later call changes the mask and keeps the binding.  Allocates nothing. */
+int32_t dn_enable_privileged(dn_env *env, const dn_privileged_config *cfg);
+/* 1: enabled, *out = the configuration last given to dn_enable_privileged; 0: not enabled (*out untouched); < 0: error. */
+int32_t dn_get_privileged_config(const dn_env *env, dn_privileged_config *out);
+/* Binds the caller's device buffers, 16-byte aligned: rows float[capacity_steps][N][DN_PRIV_DIM], step-major like every dn_step_many
+ * buffer, and terminal_rows of the same shape or NULL.  dn_step and dn_reset write step slot 0; dn_step_many with k > capacity_steps
+ * fails with DN_ERR_INVALID_ARGUMENT.  rows = NULL unbinds (terminal_rows must be NULL too, capacity_steps is ignored): an env that is
+ * enabled but unbound writes nothing.  DN_ERR_BAD_STATE if the feature is not enabled.  The buffers must outlive the binding; a launch
+ * captured in a hipGraph bakes the pointers in. */
+int32_t dn_bind_privileged(dn_env *env, float *rows, float *terminal_rows, int64_t capacity_steps);
+
 #ifdef __cplusplus
 }
 #endif
