@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, tests/golden/gen_golden.py,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg.  The product package never
-imports this module (tests/test_layout.py enforces that).
+imports this module.
 """
 import ctypes as C
 import os

@@ -17,42 +17,18 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from test_gpu_dynamics_wind_oracle import BODY, NOISE, _features, _load, _pair, _stagger
-from test_gpu_parity import actions_mixed, compare_step
-from test_gpu_wind import DEV, GUSTY, _acts, _bullet_env, _mixed, _philox, _run_pair, _same_state, _ulps
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-DT = 1.0 / 240.0
+from gpu_support import (DEV, _acts, _bullet_env, _features, _pair, _run_pair, _same_actuator, _same_state, _stagger,  # noqa: E402
+                         load_dw)
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import (BODY, DT, GUSTY, LAG_F32_BOUND, LAG_F32_STEP, NOISE, RPM_SPAN, _act_draw, _mixed, actions_mixed,  # noqa: E402
+                           compare_step, ulps)
+
 FP = C.POINTER(C.c_float)
-# pwm2rpm over the PWM range [20000, 65535] (env_utils.py:39, :58): the span of the speeds the chain can command
-RPM_SPAN = 0.2685 * (65535.0 - 20000.0)
-# float32-compute filter against its float64 definition.  A priori: three float32 roundings of values below 21 667 (a r, (1 - a) c and
-# their sum; ulp 2^-9 = 1.95e-3 above 16 384) of half an ulp each plus the relative 2^-24 of float32(1 - a) on a term below 21 667
-# (another ~0.65 ulp), then the float32 store of the float64 definition itself (half an ulp): <= 2.7 ulp = 5.2e-3 rpm = 4.3e-7 span.
-LAG_F32_BOUND = 4.3e-7
-# ... and as measured on one MI355X (test_motor_lag_matches_the_oracles_pieces[f32], 512 drones x 40 steps, tau in [0.02, 0.15]): see
-# that test's docstring; the bar is about 2x the measured maximum and inside the a-priori bound.
-LAG_F32_STEP = 3.0e-7
-
-
-def _pkg():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    return pkg
-
-
-def _draw(act, gid, step, seed):
-    """The documented episode-start draw: one Philox4x32-10 call on (seed; gid, step, stream 17) -> (d, float32 a)."""
-    u = (_philox(gid, step, 17, seed)[:2] + 0.5) / 4294967296.0
-    lo, hi = act.latency
-    d = min(lo + int(math.floor((hi - lo + 1) * u[0])), hi)
-    t0, t1 = float(np.float32(act.motor_tau[0])), float(np.float32(act.motor_tau[1]))
-    tau = t0 + (t1 - t0) * u[1]
-    return d, (np.float32(math.exp(-DT / tau)) if tau > 0.0 else np.float32(0.0))
 
 
 class Shifter:
@@ -85,12 +61,6 @@ def _same_outputs(a, b, tag):
     for k in ("terminal_obs", "ep_return", "ep_length"):       # rows written only where done
         assert torch.equal(ia[k][m], ib[k][m]), (tag, k)
     return int(m.sum())
-
-
-def _same_actuator(a, b):
-    x, y = a.get_actuator(), b.get_actuator()
-    for k in x:
-        assert torch.equal(x[k], y[k]), k
 
 
 # ---- 1. off is off --------------------------------------------------------------------------------------------------------
@@ -235,7 +205,7 @@ def _oracle_cell(dt, norm, noise, mode, dw):
     dev = torch.device(DEV)
     n_done = flips = 0
     for launch in range(T // K):
-        _load(env, ora)
+        load_dw(env, ora)
         sc0 = env.step_count
         d = env.get_actuator()["latency"].cpu().numpy().copy()
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
@@ -253,7 +223,7 @@ def _oracle_cell(dt, norm, noise, mode, dw):
             ref = ora.step(eff)
             sh.push(acts[t])
             for i in np.flatnonzero(ref["done"]):                       # the episode that starts now flies a new draw
-                d[i] = _draw(model, i, sc0 + t, seed)[0]
+                d[i] = _act_draw(model, i, sc0 + t, seed)[0]
             tag = f"{dt}/norm{norm}/noise{noise}/{mode}/dw{int(dw)} launch {launch} t={t}"
             if f32:
                 agree &= out[2].cpu().numpy() == ref["done"]
@@ -296,19 +266,19 @@ def test_draws_follow_their_definition(offset, sc0):
                           actuator=model)
     env.step_count = sc0
     env.reset_tensor()
-    want = [_draw(model, offset + i, sc0, seed) for i in range(n)]
+    want = [_act_draw(model, offset + i, sc0, seed) for i in range(n)]
     rng = np.random.default_rng(2)
     seen = set()
     for t in range(14):
         got = env.get_actuator()
         d, a = got["latency"].cpu().numpy(), got["coeff"].cpu().numpy()
         assert np.array_equal(d, [w[0] for w in want]), t
-        assert _ulps(a, np.array([w[1] for w in want], np.float32)).max() <= 1, t
+        assert ulps(a, np.array([w[1] for w in want], np.float32)).max() <= 1, t
         seen.update(d.tolist())
         sc = env.step_count
         _, _, done, _ = env.step_tensor(torch.from_numpy(_mixed(rng, n)).to(DEV))
         for i in np.flatnonzero(done.cpu().numpy()):
-            want[i] = _draw(model, offset + i, sc, seed)
+            want[i] = _act_draw(model, offset + i, sc, seed)
     assert seen == set(range(1, 9)) and env.step_count == sc0 + 14
     # resample = 0: what set_actuator wrote survives episode starts
     env.close()
@@ -365,7 +335,7 @@ def test_motor_lag_matches_the_oracles_pieces(dt):
     f32 = dt == "f32"
     n, T = 512, 40
     model = pkg.ActuatorModel(motor_tau=(0.02, 0.15), fill=(0.05, 0.05, 0.05, 0.05))
-    env = _bullet_env(pkg, n, None, actuator=model, seed=5, compute_dtype="float32" if f32 else "float64")
+    env = _bullet_env(pkg, n, wind=None, actuator=model, seed=5, compute_dtype="float32" if f32 else "float64")
     env.reset_tensor()
     rng = np.random.default_rng(6)
     a = env.get_actuator()["coeff"].cpu().numpy()
@@ -387,7 +357,7 @@ def test_motor_lag_matches_the_oracles_pieces(dt):
         dist = float(np.abs(r_got.astype(np.float64) - (a64 * r_prev + (1.0 - a64) * c)).max() / RPM_SPAN)
         worst_r = max(worst_r, dist)
         if not f32:
-            assert _ulps(r_got, r_ref).max() <= 1, t
+            assert ulps(r_got, r_ref).max() <= 1, t
         got = env.get_state()
         for i in range(n):
             p, q, v, w = (st[k][i].astype(np.float64).copy() for k in ("pos", "quat", "vel", "ang_v"))
@@ -414,7 +384,7 @@ def test_constant_command_follows_the_closed_form():
     gives a = 0.812, 0.5 / (1 - a) = 2.7 -> 4 ulp."""
     pkg = _pkg()
     n, steps = 64, 24
-    env = _bullet_env(pkg, n, None, actuator=pkg.ActuatorModel(motor_tau=(0.02, 0.02), fill=(0.03, 0.03, 0.03, 0.03), resample=False))
+    env = _bullet_env(pkg, n, wind=None, actuator=pkg.ActuatorModel(motor_tau=(0.02, 0.02), fill=(0.03, 0.03, 0.03, 0.03), resample=False))
     env.reset_tensor()
     a = np.float32(math.exp(-DT / float(np.float32(0.02))))
     env.set_actuator(coeff=torch.full((n,), float(a), device=DEV))
@@ -424,7 +394,7 @@ def test_constant_command_follows_the_closed_form():
     for k in range(1, steps + 1):
         env.step_tensor(torch.from_numpy(thrust).to(DEV))
         want = c + (r0 - c) * float(a) ** k
-        assert _ulps(env.get_actuator()["rpm"].cpu().numpy(), want.astype(np.float32)).max() <= 4, k
+        assert ulps(env.get_actuator()["rpm"].cpu().numpy(), want.astype(np.float32)).max() <= 4, k
     env.close()
 
 

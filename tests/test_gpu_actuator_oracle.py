@@ -1,6 +1,6 @@
 """The per-drone actuator model (dn_enable_actuator: command latency + motor lag) on the HIP path against the CPU oracle
 (oracle/dn_oracle.c orc_vec_step_act, written from include/dronenav.h and itself pinned by tests/test_oracle_actuator.py).  The
-configurations, seeds and action streams live in tests/test_oracle_actuator.py, which shows on the oracle alone that they reach the
+configurations, seeds and action streams live in tests/model_support.py; tests/test_oracle_actuator.py shows on the oracle alone that they reach the
 cases claimed here (episode ends, fills, latencies 0 and 8, history entries consumed across a launch boundary, restarts inside a
 launch, the ground effect acting); every test here first checks that its oracle has that file's configuration, byte for byte.
 
@@ -17,77 +17,22 @@ d. Short launches (K around the history's depth, interleaved) and an env whose a
 import numpy as np
 import pytest
 
-import test_oracle_actuator as CPU
+import model_support as M
 from oracle import oracle as O
-from test_gpu_actuator import LAG_F32_BOUND, LAG_F32_STEP, RPM_SPAN
-from test_gpu_dynamics_wind_oracle import BODY, DEV, GUSTY, NOISE, _check_dw, _features, _pair, _stagger, _ulps
-from test_gpu_dynamics_wind_oracle import _load as _load_dw
-from test_gpu_parity import _step_mismatch, actions_mixed, compare_step
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-# float32-compute rpm after a 5-step launch against the float64 oracle run from the launch's first state.  c depends only on the
-# action and its float64-drawn noise, so it is the same on both sides and every step adds at most LAG_F32_BOUND: a priori
-# 5 x 4.3e-7 = 2.15e-6 of RPM_SPAN.  Measured on one MI355X over the eight float32 cells of (a): see
-# test_every_instantiation_with_latency_and_lag_matches_oracle's docstring; the bar is about 2x the measured maximum.
-LAG_F32_LAUNCH_BOUND = 5 * LAG_F32_BOUND
-LAG_F32_LAUNCH = 1.0e-6
-
-
-def _pkg():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    assert BODY == CPU.BODY and GUSTY == CPU.GUSTY_KW and NOISE == CPU.NOISE        # the CPU file's coverage runs speak of these
-    return pkg
-
-
-def _same_config(ora, ref):
-    """The oracle of this test is the one tests/test_oracle_actuator.py ran its coverage on."""
-    assert bytes(ora.cfg) == bytes(ref.cfg) and bytes(ora.act_cfg) == bytes(ref.act_cfg), "oracle configuration drifted from the CPU file"
-    assert (ora.dw_cfg is None and ref.dw_cfg is None) or bytes(ora.dw_cfg) == bytes(ref.dw_cfg if ref.dw_cfg is not None else O.make_dw_config())
-
-
-def _get_act(env):
-    return {k: v.cpu().numpy() for k, v in env.get_actuator().items()}
-
-
-def _load(env, ora):
-    """Teacher forcing: the device's state, scales, wind and the four actuator arrays into the oracle."""
-    _load_dw(env, ora)
-    for k, v in _get_act(env).items():
-        ora.act[k] = v
-
-
-def _check_act(env, ora, rows, f32, fused, tag, stats=None):
-    got = _get_act(env)
-    assert np.array_equal(got["latency"][rows], ora.act["latency"][rows]), f"{tag}: latency"
-    assert np.array_equal(got["history"][rows], ora.act["history"][rows]), f"{tag}: history"
-    c_u = _ulps(got["coeff"][rows], ora.act["coeff"][rows]).max(initial=0)
-    assert c_u <= 1, f"{tag}: coeff {c_u} ulps"
-    r, want = got["rpm"][rows], ora.act["rpm"][rows]
-    dist = float(np.abs(r.astype(np.float64) - want).max(initial=0) / RPM_SPAN)
-    eq = float(np.mean(r == want)) if len(r) else 1.0
-    if f32:
-        bar = LAG_F32_LAUNCH if fused else LAG_F32_STEP
-        assert dist <= bar, f"{tag}: float32-compute rpm {dist:.3e} span from the oracle (bar {bar:.1e})"
-    else:
-        r_u = _ulps(r, want).max(initial=0)
-        assert r_u <= 1 and eq >= 0.999, f"{tag}: rpm {r_u} ulps, {eq:.5f} bit-equal"
-    if stats is not None:
-        stats["dist"], stats["eq"] = max(stats.get("dist", 0.0), dist), min(stats.get("eq", 1.0), eq)
-
-
-def _rollout_outs(r, K):
-    return [(r["obs"][t], r["reward"][t], r["done"][t],
-             dict(truncated=r["truncated"][t], found_targets=r["found_targets"][t], terminal_obs=r["terminal_obs"][t],
-                  ep_length=r["ep_length"][t], ep_return=r["ep_return"][t])) for t in range(K)]
+from gpu_support import (DEV, _features, _get_act, _pair, _rollout_outs, _same_config, _stagger, check_act, check_dw,  # noqa: E402
+                         load_act)
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import (LAG_F32_BOUND, LAG_F32_LAUNCH, LAG_F32_LAUNCH_BOUND, LAG_F32_STEP, NOISE, _step_mismatch,  # noqa: E402
+                           actions_mixed, compare_step)
 
 
 # ---- a. every instantiation, latency and lag together ------------------------------------------------------------------------
-@pytest.mark.parametrize("dt,norm,noise,mode", CPU.INST_CELLS, ids=[f"{d}-norm{a}-noise{b}-{m}" for d, a, b, m in CPU.INST_CELLS])
+@pytest.mark.parametrize("dt,norm,noise,mode", M.INST_CELLS, ids=[f"{d}-norm{a}-noise{b}-{m}" for d, a, b, m in M.INST_CELLS])
 def test_every_instantiation_with_latency_and_lag_matches_oracle(dt, norm, noise, mode, monkeypatch):
     """n = 1000, 150 steps, max_steps = 40, staggered step counters.  Measured on one MI355X (3661 episodes per cell): float64
     compute, rpm bit-equal to the oracle in 100 % of the compared values in all eight cells (0 ulp); float32 compute, max
@@ -96,7 +41,7 @@ def test_every_instantiation_with_latency_and_lag_matches_oracle(dt, norm, noise
     largest, a priori 2.15e-6); no done flag flipped."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    n, T, K = CPU.INST["n"], CPU.INST["T"], (1 if mode == "step" else CPU.INST["K"])
+    n, T, K = M.INST["n"], M.INST["T"], (1 if mode == "step" else M.INST["K"])
     f32 = dt == "f32"
     if norm and noise and not f32:
         # The default observation-noise draws use the hardware's float32 transcendentals, within 1.2e-6 of the float64 definition
@@ -109,24 +54,24 @@ def test_every_instantiation_with_latency_and_lag_matches_oracle(dt, norm, noise
         # in the float64 form (a run-time flag).  The float32 cells scale their bar by the std and keep the default draws.
         monkeypatch.setenv("DN_EXACT_OBS_NOISE", "1")
     dynamics, wind = _features(pkg, bool(norm), bool(norm))
-    kw = dict(max_steps=CPU.INST["max_steps"], normalize_obs=bool(norm), seed=CPU.inst_seed(dt, norm, noise),
-              compute_dtype="float32" if f32 else "float64", actuator=pkg.ActuatorModel(**CPU.FULL), **(NOISE if noise else {}))
+    kw = dict(max_steps=M.INST["max_steps"], normalize_obs=bool(norm), seed=M.act_inst_seed(dt, norm, noise),
+              compute_dtype="float32" if f32 else "float64", actuator=pkg.ActuatorModel(**M.FULL), **(NOISE if noise else {}))
     env, ora = _pair(tracks.circle(1, 4, 1), n, dynamics, wind, **kw)
-    ora.enable_actuator(CPU.act(**CPU.FULL))
-    _same_config(ora, CPU.inst_oracle(dt, norm, noise))
+    ora.enable_actuator(M.act(**M.FULL))
+    _same_config(ora, M.act_inst_oracle(dt, norm, noise))
     assert env.kernel_waves(fused=True) == env.kernel_waves(fused=False) == 1
     assert LAG_F32_LAUNCH <= LAG_F32_LAUNCH_BOUND and LAG_F32_STEP <= LAG_F32_BOUND
     env.reset_tensor()
     ora.reset()
-    _check_act(env, ora, np.ones(n, bool), False, False, "reset")
-    rng = np.random.default_rng(CPU.INST["rng"])
+    check_act(env, ora, np.ones(n, bool), False, False, "reset")
+    rng = np.random.default_rng(M.INST["rng"])
     _stagger(env, rng)
     dev = torch.device(DEV)
     n_done = flips = 0
     stats = {}
     tag0 = f"{dt}/norm{norm}/noise{noise}/{mode}"
     for launch in range(T // K):
-        _load(env, ora)
+        load_act(env, ora)
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
         if mode == "step":
             outs = [env.step_tensor(torch.from_numpy(acts[0]).to(dev))]
@@ -147,8 +92,8 @@ def test_every_instantiation_with_latency_and_lag_matches_oracle(dt, norm, noise
                 n_done += int(ref["done"].sum())
             else:
                 n_done += compare_step(out, ref, tag, rew_atol=1e-5 if mode == "step" else 1e-4)
-        _check_dw(env, ora, agree, f32, mode == "rollout", f"{tag0} launch {launch}")
-        _check_act(env, ora, agree, f32, mode == "rollout", f"{tag0} launch {launch}", stats)
+        check_dw(env, ora, agree, f32, mode == "rollout", f"{tag0} launch {launch}")
+        check_act(env, ora, agree, f32, mode == "rollout", f"{tag0} launch {launch}", stats)
     assert n_done > n
     assert flips <= n * T * 1e-4, f"{flips} done flags differ"
     print(f"ACT {tag0}: {n_done} episodes, rpm max {stats['dist']:.3e} span from the oracle, {stats['eq']:.5f} bit-equal, {flips} flags flipped")
@@ -156,7 +101,7 @@ def test_every_instantiation_with_latency_and_lag_matches_oracle(dt, norm, noise
 
 
 # ---- b. options -------------------------------------------------------------------------------------------------------------
-OPTION_CELLS = ([(p, "thrust", na, e, f) for p, na, e, f in CPU.LAG_OPTION_CELLS] + [(p, a, False, {}, "both") for p, a in CPU.LAT_OPTION_CELLS])
+OPTION_CELLS = ([(p, "thrust", na, e, f) for p, na, e, f in M.LAG_OPTION_CELLS] + [(p, a, False, {}, "both") for p, a in M.LAT_OPTION_CELLS])
 
 
 @pytest.mark.parametrize("physics,act,normalized,extra,feat", OPTION_CELLS,
@@ -167,33 +112,33 @@ def test_options_with_the_actuator_match_oracle(physics, act, normalized, extra,
     s_km), normalised and raw actions.  Other action types: latency [0, 8] alone -- the delayed command goes through HOVER_RPM (1 +
     0.05 a) or the PID loop, whose integrals and last attitude the teacher forcing carries along."""
     pkg = _pkg()
-    n, T = CPU.OPT["n"], CPU.OPT["T"]
-    wp, spawn, dim, circle, kw, model = CPU.option_setup(physics, act, normalized, extra)
+    n, T = M.ACT_OPT["n"], M.ACT_OPT["T"]
+    wp, spawn, dim, circle, kw, model = M.option_setup(physics, act, normalized, extra)
     dynamics, wind = _features(pkg, feat == "both", feat == "both")
     env = pkg.DroneVecEnv(None, n, target_points=wp, initial_xyzs=spawn, aviary_dim=dim, circle=circle, device=DEV, physics=physics,
                           act=act, dynamics=dynamics, wind=wind, actuator=pkg.ActuatorModel(**model), **kw)
     assert env.kernel_waves(fused=True) == env.kernel_waves(fused=False) == 1
-    assert pkg.vec_env.PHYSICS == CPU.PHYSICS and pkg.vec_env.ACTION_TYPES == CPU.ACTION_TYPES
-    cfg = O.make_config(wp, spawn.ravel(), dim, circle=circle, f32_state=True, physics=CPU.PHYSICS[physics], action_type=CPU.ACTION_TYPES[act], **kw)
+    assert pkg.vec_env.PHYSICS == M.PHYSICS and pkg.vec_env.ACTION_TYPES == M.ACTION_TYPES
+    cfg = O.make_config(wp, spawn.ravel(), dim, circle=circle, f32_state=True, physics=M.PHYSICS[physics], action_type=M.ACTION_TYPES[act], **kw)
     assert bool(cfg.ground_contact) == env.ground_contact
-    ora = O.OracleVecEnv(cfg, n, threads=8, dynamics=dynamics, wind=wind, actuator=CPU.act(**model))
+    ora = O.OracleVecEnv(cfg, n, threads=8, dynamics=dynamics, wind=wind, actuator=M.act(**model))
     ora.dw_cfg = O.make_dw_config(dynamics, wind)
     env.reset_tensor()
     ora.reset()
-    _check_act(env, ora, np.ones(n, bool), False, False, "reset")
-    rng = np.random.default_rng(CPU.OPT["rng"])
+    check_act(env, ora, np.ones(n, bool), False, False, "reset")
+    rng = np.random.default_rng(M.ACT_OPT["rng"])
     dev = torch.device(DEV)
     n_done = 0
     every = np.ones(n, bool)
     tag0 = f"{physics}/{act}/{'norm' if normalized else 'raw'}/{extra}/{feat}"
     for t in range(T):
-        _load(env, ora)
-        a = CPU.option_actions(rng, n, act, normalized)
+        load_act(env, ora)
+        a = M.option_actions(rng, n, act, normalized)
         out = env.step_tensor(torch.from_numpy(a).to(dev))
         torch.cuda.synchronize()
         n_done += compare_step(out, ora.step(a), f"{tag0} t={t}")
-        _check_dw(env, ora, every, False, False, f"{tag0} t={t}")
-        _check_act(env, ora, every, False, False, f"{tag0} t={t}")
+        check_dw(env, ora, every, False, False, f"{tag0} t={t}")
+        check_act(env, ora, every, False, False, f"{tag0} t={t}")
     assert n_done > n // 2
     env.close()
 
@@ -222,35 +167,35 @@ def _lockstep_launch(env, ora, acts, lock, tag):
     return n_done
 
 
-@pytest.mark.parametrize("where", list(CPU.FREE_WHERE))
+@pytest.mark.parametrize("where", list(M.FREE_WHERE))
 def test_free_running_fused_launches_with_the_actuator_match_oracle(where):
     """K = 64, 4096 drones, 256 steps of U(-1, 1) commands on the race track, max_steps = 100, dynamics + wind + latency + lag; both
     sides keep their own state.  Actuator state of the drones in lockstep after every launch at (a)'s float64 bars."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    n, K = CPU.FREE["n"], CPU.FREE["K"]
-    off, sc0 = CPU.FREE_WHERE[where]
+    n, K = M.ACT_FREE["n"], M.ACT_FREE["K"]
+    off, sc0 = M.FREE_WHERE[where]
     dynamics, wind = _features(pkg, True, True)
-    env, ora = _pair(tracks.reaching(), n, dynamics, wind, max_steps=CPU.FREE["max_steps"], normalize_obs=False, seed=CPU.FREE["seed"],
-                     env_id_offset=off, actuator=pkg.ActuatorModel(**CPU.FULL))
-    ora.enable_actuator(CPU.act(**CPU.FULL))
-    _same_config(ora, CPU.track_oracle("race", 1, CPU.FULL, True, max_steps=CPU.FREE["max_steps"], normalize_obs=False,
-                                       seed=CPU.FREE["seed"], env_id_offset=off))
+    env, ora = _pair(tracks.reaching(), n, dynamics, wind, max_steps=M.ACT_FREE["max_steps"], normalize_obs=False, seed=M.ACT_FREE["seed"],
+                     env_id_offset=off, actuator=pkg.ActuatorModel(**M.FULL))
+    ora.enable_actuator(M.act(**M.FULL))
+    _same_config(ora, M.act_track_oracle("race", 1, M.FULL, True, max_steps=M.ACT_FREE["max_steps"], normalize_obs=False,
+                                       seed=M.ACT_FREE["seed"], env_id_offset=off))
     env.step_count = sc0
     ora.envs["step_count"] = sc0
     np.testing.assert_allclose(env.reset_tensor().cpu().numpy(), ora.reset(), rtol=0, atol=1e-6)
-    _check_act(env, ora, np.ones(n, bool), False, False, "reset")
-    rng = np.random.default_rng(CPU.FREE["rng"])
+    check_act(env, ora, np.ones(n, bool), False, False, "reset")
+    rng = np.random.default_rng(M.ACT_FREE["rng"])
     _stagger(env, rng, ora)
     lock = np.ones(n, bool)
     n_done = 0
     stats = {}
-    for rep in range(CPU.FREE["launches"]):
+    for rep in range(M.ACT_FREE["launches"]):
         acts = np.stack([rng.uniform(-1, 1, (n, 4)).astype(np.float32) for _ in range(K)])
         n_done += _lockstep_launch(env, ora, acts, lock, f"{where} launch {rep}")
-        _check_dw(env, ora, lock, False, True, f"{where} launch {rep}")
-        _check_act(env, ora, lock, False, True, f"{where} launch {rep}", stats)
-    assert n_done > 2 * n and env.step_count == sc0 + K * CPU.FREE["launches"]
+        check_dw(env, ora, lock, False, True, f"{where} launch {rep}")
+        check_act(env, ora, lock, False, True, f"{where} launch {rep}", stats)
+    assert n_done > 2 * n and env.step_count == sc0 + K * M.ACT_FREE["launches"]
     print(f"ACT {where}: {n_done} episodes compared, {int((~lock).sum())} drones dropped at a branch cut, rpm {stats['eq']:.5f} bit-equal")
     env.close()
 
@@ -260,28 +205,28 @@ def test_short_launches_around_the_history_depth_match_oracle():
     its depth, each after each), half the drones held at latency 8 by set_actuator before every launch."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    n = CPU.SHORT["n"]
+    n = M.SHORT["n"]
     dynamics, wind = _features(pkg, True, True)
-    kw = dict(max_steps=CPU.SHORT["max_steps"], normalize_obs=False, seed=CPU.SHORT["seed"])
-    env, ora = _pair(tracks.circle(1, 4, 1), n, dynamics, wind, actuator=pkg.ActuatorModel(**CPU.FULL), **kw)
-    ora.enable_actuator(CPU.act(**CPU.FULL))
-    _same_config(ora, CPU.track_oracle("circle4", 1, CPU.FULL, True, **kw))
+    kw = dict(max_steps=M.SHORT["max_steps"], normalize_obs=False, seed=M.SHORT["seed"])
+    env, ora = _pair(tracks.circle(1, 4, 1), n, dynamics, wind, actuator=pkg.ActuatorModel(**M.FULL), **kw)
+    ora.enable_actuator(M.act(**M.FULL))
+    _same_config(ora, M.act_track_oracle("circle4", 1, M.FULL, True, **kw))
     np.testing.assert_allclose(env.reset_tensor().cpu().numpy(), ora.reset(), rtol=0, atol=1e-6)
-    rng = np.random.default_rng(CPU.SHORT["rng"])
+    rng = np.random.default_rng(M.SHORT["rng"])
     st = env.get_state()
-    st["steps"] = rng.integers(0, CPU.SHORT["max_steps"], n).astype(st["steps"].dtype)
+    st["steps"] = rng.integers(0, M.SHORT["max_steps"], n).astype(st["steps"].dtype)
     env.set_state(st)
     ora.envs["steps"] = st["steps"]
     lock = np.ones(n, bool)
     n_done = 0
-    for li, K in enumerate(CPU.SHORT["Ks"]):
+    for li, K in enumerate(M.SHORT["Ks"]):
         lat = env.get_actuator()["latency"].clone()
         lat[: n // 2] = 8
         env.set_actuator(latency=lat)
         ora.act["latency"][: n // 2] = 8
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
         n_done += _lockstep_launch(env, ora, acts, lock, f"short launch {li} K={K}")
-        _check_act(env, ora, lock, False, True, f"short launch {li} K={K}")
+        check_act(env, ora, lock, False, True, f"short launch {li} K={K}")
     assert n_done > n
     env.close()
 
@@ -291,24 +236,24 @@ def test_values_written_by_set_actuator_are_flown_as_the_oracle_flies_them():
     free-running launches of 20 steps with max_steps = 15: every drone starts more than one episode; d and a must hold."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    n, K = CPU.SETV["n"], CPU.SETV["K"]
-    model = dict(CPU.FULL, resample=False)
-    kw = dict(max_steps=CPU.SETV["max_steps"], normalize_obs=False, seed=CPU.SETV["seed"])
+    n, K = M.ACT_SETV["n"], M.ACT_SETV["K"]
+    model = dict(M.FULL, resample=False)
+    kw = dict(max_steps=M.ACT_SETV["max_steps"], normalize_obs=False, seed=M.ACT_SETV["seed"])
     env, ora = _pair(tracks.circle(1, 4, 1), n, None, None, actuator=pkg.ActuatorModel(**model), **kw)
-    ora.enable_actuator(CPU.act(**model))
-    _same_config(ora, CPU.track_oracle("circle4", 1, model, False, **kw))
+    ora.enable_actuator(M.act(**model))
+    _same_config(ora, M.act_track_oracle("circle4", 1, model, False, **kw))
     np.testing.assert_allclose(env.reset_tensor().cpu().numpy(), ora.reset(), rtol=0, atol=1e-6)
-    rng = np.random.default_rng(CPU.SETV["rng"])
-    vals = CPU.short_set_values(rng, n)
+    rng = np.random.default_rng(M.ACT_SETV["rng"])
+    vals = M.short_set_values(rng, n)
     env.set_actuator(**{k: torch.from_numpy(v).to(DEV) for k, v in vals.items()})
     for k, v in vals.items():
         ora.act[k] = v
     lock = np.ones(n, bool)
     n_done = 0
-    for rep in range(CPU.SETV["launches"]):
+    for rep in range(M.ACT_SETV["launches"]):
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
         n_done += _lockstep_launch(env, ora, acts, lock, f"set values launch {rep}")
-        _check_act(env, ora, lock, False, True, f"set values launch {rep}")
+        check_act(env, ora, lock, False, True, f"set values launch {rep}")
         got = _get_act(env)
         assert np.array_equal(got["latency"], vals["latency"]) and np.array_equal(got["coeff"], vals["coeff"])
     assert n_done > 2 * n - 16

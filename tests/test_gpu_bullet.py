@@ -13,20 +13,14 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from gpu_support import _bullet_env, pkg  # noqa: E402
+
 HOVER_F = RB.M * RB.G / 4.0
-WIDE = [-1e4, -1e4, -1e4, 1e4, 1e4, 1e4]
 
 
 def _env(n, **kw):
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
     # thrust commands in newton (normalize_actions=False), no corridor / ground / box to end the episode, no gate in reach
-    opts = dict(target_points=np.array([[5e3, 5e3, 5e3]]), initial_xyzs=np.array([[0.0, 0.0, 1.0]]), aviary_dim=WIDE,
-                circle=False, cylinder=False, ground_contact=False, normalize_actions=False, normalize_obs=False,
-                threshold=0.0, max_steps=1 << 20, device="cuda:0")
-    opts.update(kw)
-    return pkg.DroneVecEnv(None, n, **opts)
+    return _bullet_env(pkg(), n, **kw)
 
 
 def one_step(pos, quat, vel, ang_v, thrust, **kw):

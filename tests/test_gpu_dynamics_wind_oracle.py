@@ -35,111 +35,24 @@ a. Every instantiation: both families are dn_step_many_1w_kernel<R, NORM, NOISE,
    with about 2x margin.  With the normaliser on, the float32 observation bar is 5e-4 divided by the column's running std (where
    that is below 1): the normaliser scales an arithmetic difference by 1 / std.  The drones' episode step counters start spread
    over [0, 40), so that in every wave some lanes start an episode (redraw) while others fly on.
-b. The option matrix of test_physics_options_match_oracle with both features on (mass 0.7-1.3, the gusts of test_gpu_wind.GUSTY),
+b. The option matrix of test_physics_options_match_oracle with both features on (mass 0.7-1.3, the gusts of model_support.GUSTY),
    plus random spawn, the reward wrappers, zero damping and include_distance = False, and a few cells with one feature alone.
 c. Free-running fused launches, K = 64, n = 4096, 256 steps, with the lockstep discipline of
    test_baseline_full_size_fused_launch_matches_oracle: once with env_id_offset = 2^33 + 12345, once with the step counter just
    below 2^32 so that the draws cross the word boundary.
 """
-import math
-
 import numpy as np
 import pytest
 
 from oracle import oracle as O
-from test_gpu_parity import _step_mismatch, actions_mixed, compare_step, gpu_state_to_oracle, make_pair
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-DEV = "cuda:0"
-BODY = dict(mass=(0.7, 1.3), inertia=(0.7, 1.3), kf=(0.8, 1.2), km=(0.7, 1.3))
-GUSTY = dict(speed=(0.5, 6.0), azimuth=(-math.pi, math.pi), vertical=(-0.5, 0.5), gust_sigma=(0.8, 0.3), gust_tau=0.25)
-NOISE = dict(obs_noise_sigma=0.01, act_noise_sigma=0.001)
-# the float32-compute gust's distance from the float64 definition, in units of its sigma: measured on one MI355X over the eight
-# float32 wind cells (150 000 drone-steps each), at most 3.97e-7 after a teacher-forced step (about one float32 ulp of a gust near
-# 1.3 sigma) and 1.19e-6 after a 5-step launch; the bars are ~2x that
-GUST_F32_STEP = 8e-7
-GUST_F32_LAUNCH = 2.5e-6
-
-
-def _pkg():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    return pkg
-
-
-def _ulps(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    ia, ib = a.view(np.int32).astype(np.int64), b.view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia)
-    ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
-    return np.abs(ia - ib)
-
-
-def _features(pkg, dynamics, wind):
-    d = pkg.DynamicsRandomization(**BODY) if dynamics is True else dynamics
-    w = pkg.WindDisturbance(**GUSTY) if wind is True else wind
-    return d or None, w or None
-
-
-def _pair(track, n, dynamics, wind, **kw):
-    """make_pair of test_gpu_parity with the features on both sides (float32 state in the oracle)."""
-    env, ora = make_pair(track, n, f32_state=True, dynamics=dynamics, wind=wind, **kw)
-    ora.dw_cfg = O.make_dw_config(dynamics, wind)
-    return env, ora
-
-
-def _stagger(env, rng, ora=None):
-    """Spread the drones' episode step counters over [0, 40) so that time limits end episodes at different steps: waves in which
-    some lanes start an episode and others fly on, inside launches too."""
-    st = env.get_state()
-    st["steps"] = rng.integers(0, 40, len(st)).astype(st["steps"].dtype)
-    env.set_state(st)
-    if ora is not None:
-        ora.envs["steps"] = st["steps"]
-
-
-def _load(env, ora):
-    """Teacher forcing: the device's state, scales and wind into the oracle."""
-    gpu_state_to_oracle(env.get_state(), ora.envs, env.step_count)
-    ora.refresh_rpy()
-    if ora.dw_cfg.dynamics:
-        ora.dw["dyn"] = env.get_dynamics().cpu().numpy()
-    if ora.dw_cfg.wind:
-        m, g = env.get_wind()
-        ora.dw["wind_mean"], ora.dw["wind_gust"] = m.cpu().numpy(), g.cpu().numpy()
-
-
-def _dw_distance(env, ora, rows):
-    """(scale ulps, steady-wind ulps, gust ulps, gust |diff| / sigma, gust bit-equal fraction) over `rows`."""
-    z = np.zeros(0)
-    s_u = m_u = g_u = g_rel = z
-    g_eq = 1.0
-    if ora.dw_cfg.dynamics:
-        s_u = _ulps(env.get_dynamics().cpu().numpy()[rows], ora.dw["dyn"][rows])
-    if ora.dw_cfg.wind:
-        m, g = (x.cpu().numpy()[rows] for x in env.get_wind())
-        m_u = _ulps(m, ora.dw["wind_mean"][rows])
-        g_u = _ulps(g[:, :3], ora.dw["wind_gust"][rows, :3])
-        sig = np.array([ora.dw_cfg.gust_sigma[0], ora.dw_cfg.gust_sigma[0], ora.dw_cfg.gust_sigma[1]], np.float64)
-        g_rel = np.abs(g[:, :3].astype(np.float64) - ora.dw["wind_gust"][rows, :3]) / sig
-        g_eq = float(np.mean(g[:, :3] == ora.dw["wind_gust"][rows, :3])) if len(g) else 1.0
-    mx = lambda a: float(a.max(initial=0))      # noqa: E731
-    return mx(s_u), mx(m_u), mx(g_u), mx(g_rel), g_eq
-
-
-def _check_dw(env, ora, rows, f32, fused, tag):
-    s_u, m_u, g_u, g_rel, g_eq = _dw_distance(env, ora, rows)
-    assert s_u <= 1 and m_u <= 1, f"{tag}: scales {s_u} / steady wind {m_u} ulps"
-    if f32:
-        bar = GUST_F32_LAUNCH if fused else GUST_F32_STEP
-        assert g_rel <= bar, f"{tag}: float32-compute gust {g_rel:.3e} sigma from the float64 definition (bar {bar:.0e})"
-    else:
-        assert g_u <= 1 and g_eq >= 0.999, f"{tag}: gust {g_u} ulps, {g_eq:.5f} bit-equal"
-    return g_rel
+from gpu_support import DEV, _features, _pair, _stagger, check_dw, load_dw  # noqa: E402
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import NOISE, _step_mismatch, actions_mixed, compare_step  # noqa: E402
 
 
 # ---- a. every instantiation ----------------------------------------------------------------------------------------------
@@ -166,7 +79,7 @@ def test_every_instantiation_matches_oracle(fam, dt, norm, noise, mode):
     n_done = flips = 0
     worst = 0.0
     for launch in range(T // K):
-        _load(env, ora)
+        load_dw(env, ora)
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
         if mode == "step":
             outs = [env.step_tensor(torch.from_numpy(acts[0]).to(dev))]
@@ -191,7 +104,7 @@ def test_every_instantiation_matches_oracle(fam, dt, norm, noise, mode):
                 n_done += int(ref["done"].sum())
             else:
                 n_done += compare_step(out, ref, tag, rew_atol=1e-5 if mode == "step" else 1e-4)
-        worst = max(worst, _check_dw(env, ora, agree, f32, mode == "rollout", f"{fam}/{dt}/norm{norm}/noise{noise}/{mode} launch {launch}"))
+        worst = max(worst, check_dw(env, ora, agree, f32, mode == "rollout", f"{fam}/{dt}/norm{norm}/noise{noise}/{mode} launch {launch}"))
     assert n_done > n                                           # episodes ended and redrew (inside launches in the rollout cells)
     assert flips <= n * T * 1e-4, f"{flips} done flags differ"
     print(f"{fam}/{dt}/norm{norm}/noise{noise}/{mode}: {n_done} episodes, gust max {worst:.3e} sigma, {flips} flags flipped")
@@ -236,17 +149,17 @@ def test_options_with_dynamics_and_wind_match_oracle(physics, act, extra, feat):
     ora = O.OracleVecEnv(cfg, n, threads=8, dynamics=dynamics, wind=wind)
     env.reset_tensor()
     ora.reset()
-    _check_dw(env, ora, np.ones(n, bool), False, False, "reset")
+    check_dw(env, ora, np.ones(n, bool), False, False, "reset")
     rng = np.random.default_rng(5)
     dev = torch.device(DEV)
     n_done = 0
     for t in range(T):
-        _load(env, ora)
+        load_dw(env, ora)
         a = actions_mixed(rng, n) if act == "thrust" else rng.uniform(-1, 1, (n, 4)).astype(np.float32)
         out = env.step_tensor(torch.from_numpy(a).to(dev))
         torch.cuda.synchronize()
         n_done += compare_step(out, ora.step(a), f"{physics}/{act}/{extra}/{feat} t={t}")
-        _check_dw(env, ora, np.ones(n, bool), False, False, f"{physics}/{act}/{extra}/{feat} t={t}")
+        check_dw(env, ora, np.ones(n, bool), False, False, f"{physics}/{act}/{extra}/{feat} t={t}")
     assert n_done > n // 2
     env.close()
 
@@ -268,7 +181,7 @@ def test_free_running_fused_launches_match_oracle(where):
     env.step_count = sc0
     ora.envs["step_count"] = sc0
     np.testing.assert_allclose(env.reset_tensor().cpu().numpy(), ora.reset(), rtol=0, atol=1e-6)
-    _check_dw(env, ora, np.ones(n, bool), False, False, "reset")
+    check_dw(env, ora, np.ones(n, bool), False, False, "reset")
     rng = np.random.default_rng(64)
     _stagger(env, rng, ora)
     dev = torch.device(DEV)
@@ -293,7 +206,7 @@ def test_free_running_fused_launches_match_oracle(where):
             lock &= ~bad
             assert (~lock).sum() <= 8, f"{where} launch {rep} t={t}: {int((~lock).sum())} drones out of lockstep"
             n_done += int((ref["done"].astype(bool) & lock).sum())
-        _check_dw(env, ora, lock, False, True, f"{where} launch {rep}")
+        check_dw(env, ora, lock, False, True, f"{where} launch {rep}")
     assert n_done > 2 * n
     assert env.step_count == sc0 + K * launches
     print(f"{where}: {n_done} episodes compared, {int((~lock).sum())} drones dropped at a branch cut")

@@ -18,12 +18,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-
-def _pkg():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    return pkg
+from gpu_support import pkg as _pkg  # noqa: E402
 
 
 def _kin(pos, quat, vel, ang_v):

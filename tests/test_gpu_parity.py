@@ -12,13 +12,9 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from oracle import oracle as O  # noqa: E402
-
-
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    return pkg
+from gpu_support import make_pair  # noqa: E402
+from gpu_support import pkg as _gpu  # noqa: E402
+from model_support import STATE_F32, _step_mismatch, actions_mixed, compare_step, gpu_state_to_oracle  # noqa: E402
 
 
 def _tracks():
@@ -29,69 +25,6 @@ def _tracks():
 def _bench_fused_waves(norm):
     """The fused-launch shape dn_create picks at 32 768 drones (two tiles per CU): what bench.py's headline times."""
     return 5 if norm else 4
-
-
-def make_pair(track, n, *, f32_state, max_steps=4096, **kw):
-    pkg = _gpu()
-    env = pkg.DroneVecEnv(track, n, max_steps=max_steps, device="cuda:0", **kw)
-    okw = {k: v for k, v in kw.items() if k in ("normalize_obs", "include_distance", "normalize_actions",
-                                                "act_noise_sigma", "obs_noise_sigma", "seed", "env_id_offset",
-                                                "ground_contact", "threshold", "cylinder", "clip_rew", "norm_rew", "random_spawn")}
-    okw.setdefault("normalize_obs", True)
-    okw["ground_contact"] = env.ground_contact     # DroneVecEnv's default is DN_GROUND_CONTACT_AUTO: the oracle gets what dn_create resolved
-    cfg = O.make_config(track.targets(), track.initial_xyzs, track.aviary_dim, circle=track.is_circle,
-                        max_steps=max_steps, f32_state=f32_state, **okw)
-    return env, O.OracleVecEnv(cfg, n, threads=8)
-
-
-def gpu_state_to_oracle(st, envs, step_count):
-    """Teacher forcing: load the GPU's float32 state into the oracle's float64 variables."""
-    for k in ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev", "idx", "steps",
-              "just_found", "ep_ret", "ep_len", "rms_mean", "rms_var", "rms_count", "rr_returns", "rr_mean", "rr_var",
-              "rr_count", "pid"):
-        envs[k] = st[k]
-    envs["ep_ret"] = st["ep_ret"].astype(np.float64) + st["ep_ret_lo"].astype(np.float64)    # Monitor's running return: a float32 pair
-    envs["last_clipped_action"] = st["last_rpm"]
-    envs["cur_vel"] = st["vel"]
-    envs["cur_ang_v"] = st["ang_v"]
-    envs["is_done"] = 0
-    envs["step_count"] = step_count
-
-
-def actions_mixed(rng, n):
-    """Even drones: bang-bang U(-1,1) (crash within tens of steps, BASELINE config 2's stream); odd drones:
-    hover + noise, 0.0922 + 0.003 N(0,1) (long flights, truncation, gate passes); one step in eight the two
-    regimes swap so that hovering drones get kicked."""
-    bang = rng.uniform(-1, 1, (n, 4))
-    hover = 0.0922 + 0.003 * rng.standard_normal((n, 4))
-    swap = rng.random((n, 1)) < 0.125
-    even = (np.arange(n) % 2 == 0)[:, None]
-    a = np.where(even ^ swap, bang, hover)
-    return a.astype(np.float32)
-
-
-STATE_F32 = ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev")
-
-
-def compare_step(out, ref, tag, obs_atol=1e-5, rew_atol=1e-5):
-    """rew_atol: 1e-5 teacher-forced.  Free-running comparisons (both sides keep their own float32 state) pass 1e-4:
-    a stored distance may differ by one float32 ulp (1.2e-7) and the reward carries 3000 (d_prev - d) / 25 = 120x that."""
-    obs, rew, done, info = out
-    assert np.array_equal(done.cpu().numpy(), ref["done"]), f"{tag}: done"
-    assert np.array_equal(info["truncated"].cpu().numpy(), ref["truncated"]), f"{tag}: TimeLimit.truncated"
-    assert np.array_equal(info["found_targets"].cpu().numpy(), ref["found_targets"]), f"{tag}: waypoint index"
-    k = obs.shape[1]                       # 12 columns when include_distance is off
-    np.testing.assert_allclose(obs.cpu().numpy(), ref["obs"][:, :k], rtol=0, atol=obs_atol, err_msg=f"{tag}: obs")
-    # reward carries 3000*(d_prev - d)/25: 1e-5 relative + 1e-5 absolute
-    np.testing.assert_allclose(rew.cpu().numpy(), ref["reward"], rtol=1e-5, atol=rew_atol, err_msg=f"{tag}: reward")
-    dn = ref["done"].astype(bool)
-    if dn.any():
-        np.testing.assert_allclose(info["terminal_obs"].cpu().numpy()[dn], ref["terminal_obs"][dn][:, :k], rtol=0,
-                                   atol=obs_atol, err_msg=f"{tag}: terminal_observation")
-        assert np.array_equal(info["ep_length"].cpu().numpy()[dn], ref["ep_len"][dn]), f"{tag}: episode l"
-        np.testing.assert_allclose(info["ep_return"].cpu().numpy()[dn], ref["ep_ret"][dn], rtol=1e-5, atol=1e-4,
-                                   err_msg=f"{tag}: episode r")
-    return int(dn.sum())
 
 
 @pytest.mark.parametrize("track_name,n,T,norm", [("circle4", 4096, 260, False), ("reaching", 4096, 260, False),
@@ -1020,26 +953,6 @@ def test_baseline_full_size_matches_oracle_free_running():
         n_done += compare_step(env.step_tensor(torch.from_numpy(a).to(dev)), ora.step(a), f"full-size t={t}", rew_atol=1e-4)
     assert n_done >= n // 2
     env.close()
-
-
-def _step_mismatch(out, ref, obs_atol, rew_atol):
-    """Per-drone mismatch mask of one step (the checks of compare_step, drone by drone)."""
-    obs, rew, done, info = out
-    k = obs.shape[1]
-    bad = done.cpu().numpy() != ref["done"]
-    bad |= info["truncated"].cpu().numpy() != ref["truncated"]
-    bad |= info["found_targets"].cpu().numpy() != ref["found_targets"]
-    bad |= ~(np.abs(obs.cpu().numpy().astype(np.float64) - ref["obs"][:, :k]) <= obs_atol).all(axis=1)
-    r = ref["reward"].astype(np.float64)
-    bad |= ~(np.abs(rew.cpu().numpy().astype(np.float64) - r) <= rew_atol + 1e-5 * np.abs(r))
-    dn = ref["done"].astype(bool) & ~bad
-    if dn.any():
-        t_ok = (np.abs(info["terminal_obs"].cpu().numpy().astype(np.float64) - ref["terminal_obs"][:, :k]) <= obs_atol).all(axis=1)
-        l_ok = info["ep_length"].cpu().numpy() == ref["ep_len"]
-        e = ref["ep_ret"].astype(np.float64)
-        r_ok = np.abs(info["ep_return"].cpu().numpy().astype(np.float64) - e) <= 1e-4 + 1e-5 * np.abs(e)
-        bad |= dn & ~(t_ok & l_ok & r_ok)
-    return bad
 
 
 def _expected_fused_waves(env, n, norm):

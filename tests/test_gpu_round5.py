@@ -11,12 +11,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-
-def _gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    return pkg
+from gpu_support import pkg as _gpu  # noqa: E402
 
 
 def test_launch_events_time_the_kernel_alone_and_change_nothing():

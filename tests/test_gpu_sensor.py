@@ -1,7 +1,7 @@
 """Per-drone sensor model (include/dronenav.h dn_enable_sensor) on the HIP path: observation latency and per-episode bias.
 
 The contract makes the feature a pure function of the PLAIN env's outputs, so the reference is the env without the sensor model plus a
-few lines of numpy (Delivery below): o_k is the plain env's pre-normaliser row, y_k = float32(o_{k - min(d, k)} + b).
+few lines of numpy (model_support.Delivery): o_k is the plain env's pre-normaliser row, y_k = float32(o_{k - min(d, k)} + b).
 
  1. off is off, bit for bit, alone and on top of dynamics + wind + actuator;
  2. transparency: nothing feeds back into reward, episode ends, Monitor outputs or the body state over 300 steps;
@@ -17,123 +17,23 @@ few lines of numpy (Delivery below): o_k is the plain env's pre-normaliser row, 
 Every run through _drive asserts that it met the boundaries: every latency 0..8, >= 100 episode ends, a delivery with k < d.
 """
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
-
-from test_gpu_dynamics_wind_oracle import BODY, NOISE
-from test_gpu_wind import DEV, GUSTY, _acts, _mixed, _philox, _run_pair, _same_state
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-AMPS = (0.02, 0.02, 0.03, 0.01, 0.01, 0.04, 0.05, 0.05, 0.05, 0.1, 0.1, 0.1, 0.02)
-ACT = dict(latency=(0, 8), motor_tau=(0.02, 0.15), fill=(0.0922, 0.0922, 0.0922, 0.0922))
-BODY_KEYS = ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev", "idx", "steps", "just_found", "ep_ret",
-             "ep_len", "last_rpm", "ep_ret_lo")
-RTOL = ATOL = 1e-5          # the project's observation bar
-
-
-def _pkg():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    return pkg
+from gpu_support import DEV, _acts, _advance, _run_pair, _same_sensor, _same_state  # noqa: E402
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import (AMPS, BODY, BODY_KEYS, FULL, GUSTY, NOISE, Delivery, Rms64, Worst, bits)  # noqa: E402
 
 
 def _model(pkg, **kw):
     opts = dict(latency=(0, 8), bias=AMPS)
     opts.update(kw)
     return pkg.SensorModel(**opts)
-
-
-def _sens_draw(model, gid, step, seed):
-    """The documented episode-start draw: four Philox4x32-10 calls on (seed; gid, step, streams 18..21), u_m = (r + 0.5) / 2^32 with
-    m = 4 q + c: b_j = float32(amp_j (2 u_j - 1)) in float64, d = lo + floor((hi - lo + 1) u_13) clamped to hi."""
-    u = (np.concatenate([_philox(gid, step, 18 + q, seed) for q in range(4)]) + 0.5) / 4294967296.0
-    amp = np.asarray(model.bias, np.float32).astype(np.float64)
-    lo, hi = model.latency
-    return min(lo + int(math.floor((hi - lo + 1) * u[13])), hi), (amp * (2.0 * u[:13] - 1.0)).astype(np.float32)
-
-
-class Delivery:
-    """The host's statement of the rule.  hist[i, j] = the pre-bias row o_{k - j} of drone i, k[i] = control steps of its episode."""
-
-    def __init__(self, model, n, seed, gid0):
-        self.model, self.n, self.seed, self.gid0 = model, n, seed, gid0
-        self.d = np.zeros(n, np.int64)
-        self.b = np.zeros((n, 13), np.float32)
-        self.hist = np.zeros((n, 9, 13), np.float32)
-        self.k = np.zeros(n, np.int64)
-        self.seen, self.young, self.ends = set(), 0, 0
-        self.bias_on = any(v > 0.0 for v in model.bias)      # all-zero amplitudes: no add at all (-0.0f + 0.0f would flip a sign bit)
-
-    def _plus_bias(self, o, rows):
-        return o + self.b[rows] if self.bias_on else o.copy()
-
-    def start(self, rows, o0, step):
-        """Episodes of `rows` start at vector step `step` with pre-bias reset rows o0: returns float32(o_0 + b_new)."""
-        for i, r in zip(rows, o0):
-            self.d[i], self.b[i] = _sens_draw(self.model, self.gid0 + int(i), step, self.seed)
-            self.hist[i] = 0.0
-            self.hist[i, 0] = r
-            self.k[i] = 0
-        return self._plus_bias(np.asarray(o0, np.float32), rows)
-
-    def step(self, o):
-        """The pre-bias step rows o (also the terminal rows) of all drones: returns y."""
-        self.hist = np.roll(self.hist, 1, axis=1)
-        self.hist[:, 0] = o
-        self.k += 1
-        dd = np.minimum(self.d, self.k)
-        self.seen.update(np.unique(self.d).tolist())
-        self.young += int((self.k < self.d).sum())
-        return self._plus_bias(self.hist[np.arange(self.n), dd], np.arange(self.n))
-
-
-class Rms64:
-    """gymnasium's NormalizeObservation on a batch of one, float64: RunningMeanStd.update then (x - mean) / sqrt(var + 1e-8)."""
-
-    def __init__(self, n):
-        self.mean, self.var, self.count = np.zeros((n, 13)), np.ones((n, 13)), np.full(n, 1e-4)
-
-    def __call__(self, x, rows=None):
-        rows = np.arange(len(self.count)) if rows is None else rows
-        x = np.asarray(x, np.float64)
-        mean, var, count = self.mean[rows], self.var[rows], self.count[rows][:, None]
-        delta, tot = x - mean, count + 1.0
-        mean = mean + delta / tot
-        var = (var * count + delta * delta * count / tot) / tot
-        self.mean[rows], self.var[rows], self.count[rows] = mean, var, tot[:, 0]
-        return (x - mean) / np.sqrt(var + 1e-8)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.int32)
-
-
-class Worst:
-    def __init__(self):
-        self.excess, self.abs = 0.0, 0.0
-
-    def close(self, got, want, tag):
-        err = np.abs(got.astype(np.float64) - want)
-        self.abs = max(self.abs, float(err.max(initial=0.0)))
-        self.excess = max(self.excess, float((err / (ATOL + RTOL * np.abs(want))).max(initial=0.0)))
-        assert self.excess <= 1.0, (tag, self.abs, self.excess)
-
-
-def _advance(env, acts):
-    """K = len(acts) control steps (one dn_step for K = 1, else one fused launch): step-major numpy copies."""
-    if acts.shape[0] == 1:
-        o, r, d, info = env.step_tensor(acts[0])
-        out = dict(obs=o, reward=r, done=d, truncated=info["truncated"], found_targets=info["found_targets"], terminal_obs=info["terminal_obs"],
-                   ep_return=info["ep_return"], ep_length=info["ep_length"])
-        return {k: v.cpu().numpy()[None] for k, v in out.items()}
-    out = env.rollout_tensor(acts, want_terminal=True)
-    return {k: out[k].cpu().numpy() for k in ("obs", "reward", "done", "truncated", "found_targets", "terminal_obs", "ep_return", "ep_length")}
 
 
 def _envs(pkg, n, model, *, f32=False, norm=False, noise=False, full=False, seed=31, offset=0, pinned=False):
@@ -144,7 +44,7 @@ def _envs(pkg, n, model, *, f32=False, norm=False, noise=False, full=False, seed
     if noise:
         kw.update(NOISE)
     if full:
-        kw.update(dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), actuator=pkg.ActuatorModel(**ACT))
+        kw.update(dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), actuator=pkg.ActuatorModel(**FULL))
     track = tracks.circle(1, 4, 1)
     S = pkg.DroneVecEnv(track, n, sensor=model, normalize_obs=norm, **kw)
     P = pkg.DroneVecEnv(track, n, normalize_obs=False, **kw)
@@ -170,7 +70,7 @@ def _drive(pkg, model, *, n=2048, K=1, steps=60, norm=False, sc0=0, seed=31, off
         if norm:
             worst.close(got, ref(y, rows), tag)
         else:
-            assert np.array_equal(_bits(got), _bits(y)), tag
+            assert np.array_equal(bits(got), bits(y)), tag
 
     o0 = P.reset_tensor().cpu().numpy()
     check(S.reset_tensor().cpu().numpy(), dl.start(allrows, o0, sc0), allrows, "reset")
@@ -218,9 +118,9 @@ def _drive(pkg, model, *, n=2048, K=1, steps=60, norm=False, sc0=0, seed=31, off
         assert np.ascontiguousarray(a[k]).tobytes() == np.ascontiguousarray(b[k]).tobytes(), k
     assert np.array_equal(a["steps"], dl.k)
     g = {k: v.cpu().numpy() for k, v in S.get_sensor().items()}
-    assert np.array_equal(g["latency"], dl.d) and np.array_equal(_bits(g["bias"]), _bits(dl.b))
+    assert np.array_equal(g["latency"], dl.d) and np.array_equal(bits(g["bias"]), bits(dl.b))
     valid = np.arange(9)[None, :] <= dl.k[:, None]                      # entries older than the episode are unspecified
-    assert np.array_equal(_bits(g["history"])[valid], _bits(dl.hist)[valid])
+    assert np.array_equal(bits(g["history"])[valid], bits(dl.hist)[valid])
     if norm:
         print(f"normaliser: worst |diff| {worst.abs:.3e}, worst fraction of the bar {worst.excess:.3f}")
     for e in envs:
@@ -239,7 +139,7 @@ def test_sensor_off_is_off_bit_for_bit(full, monkeypatch):
     n = 2048
     kw = dict(max_steps=15, seed=21, device=DEV, normalize_obs=True, **NOISE)
     if full:
-        kw.update(dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), actuator=pkg.ActuatorModel(**ACT))
+        kw.update(dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), actuator=pkg.ActuatorModel(**FULL))
     track = tracks.reaching()
     sens = pkg.DroneVecEnv(track, n, sensor=pkg.SensorModel(), **kw)
     plain = pkg.DroneVecEnv(track, n, **kw)
@@ -260,7 +160,7 @@ def test_sensor_model_feeds_nothing_back(full):
     n, K, launches = 2048, 20, 16                                        # 320 control steps
     kw = dict(max_steps=40, seed=8, device=DEV, normalize_obs=True, **NOISE)
     if full:
-        kw.update(dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), actuator=pkg.ActuatorModel(**ACT))
+        kw.update(dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), actuator=pkg.ActuatorModel(**FULL))
     track = tracks.circle(1, 4, 1)
     S, P = pkg.DroneVecEnv(track, n, sensor=_model(pkg), **kw), pkg.DroneVecEnv(track, n, **kw)
     S.reset_tensor()
@@ -312,7 +212,7 @@ def test_latency_alone_and_bias_alone():
     o0 = P.reset_tensor().cpu().numpy()
     g = S.reset_tensor().cpu().numpy()
     dl = Delivery(S.sensor, 1024, 31, 0)
-    assert np.array_equal(_bits(g), _bits(dl.start(np.arange(1024), o0, 0)))
+    assert np.array_equal(bits(g), bits(dl.start(np.arange(1024), o0, 0)))
     acts = _acts(np.random.default_rng(1), 1024, 50)
     rS, rP = _advance(S, acts), _advance(P, acts)
     ends = 0
@@ -320,8 +220,8 @@ def test_latency_alone_and_bias_alone():
         done = rP["done"][t].astype(bool)
         rows = np.flatnonzero(done)
         y = dl.step(np.where(done[:, None], rP["terminal_obs"][t], rP["obs"][t]))
-        assert np.array_equal(_bits(rS["obs"][t][~done]), _bits(y[~done])) and np.array_equal(_bits(rS["terminal_obs"][t][rows]), _bits(y[rows]))
-        assert np.array_equal(_bits(rS["obs"][t][rows]), _bits(dl.start(rows, rP["obs"][t][rows], t)))
+        assert np.array_equal(bits(rS["obs"][t][~done]), bits(y[~done])) and np.array_equal(bits(rS["terminal_obs"][t][rows]), bits(y[rows]))
+        assert np.array_equal(bits(rS["obs"][t][rows]), bits(dl.start(rows, rP["obs"][t][rows], t)))
         ends += len(rows)
     assert ends >= 100 and not bool(S.get_sensor()["latency"].any())
     S.close()
@@ -329,18 +229,12 @@ def test_latency_alone_and_bias_alone():
 
 
 # ---- 6. fused = single ----------------------------------------------------------------------------------------------------
-def _same_sensor(a, b):
-    x, y = a.get_sensor(), b.get_sensor()
-    for k in x:
-        assert torch.equal(x[k], y[k]), k
-
-
 @pytest.mark.parametrize("K", [5, 20, 64])
 def test_one_fused_launch_equals_single_steps(K):
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
     n, launches = 2048, 3 if K > 5 else 8
-    kw = dict(max_steps=40, seed=77, device=DEV, normalize_obs=True, sensor=_model(pkg), actuator=pkg.ActuatorModel(**ACT),
+    kw = dict(max_steps=40, seed=77, device=DEV, normalize_obs=True, sensor=_model(pkg), actuator=pkg.ActuatorModel(**FULL),
               dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), **NOISE)
     track = tracks.circle(1, 4, 1)
     F, S = pkg.DroneVecEnv(track, n, **kw), pkg.DroneVecEnv(track, n, **kw)
@@ -418,7 +312,7 @@ def test_set_get_round_trip_and_checkpoint_continuation():
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
     n, K = 2048, 20
-    kw = dict(normalize_obs=False, max_steps=15, seed=9, device=DEV, sensor=_model(pkg), actuator=pkg.ActuatorModel(**ACT),
+    kw = dict(normalize_obs=False, max_steps=15, seed=9, device=DEV, sensor=_model(pkg), actuator=pkg.ActuatorModel(**FULL),
               dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), **NOISE)
     track = tracks.reaching()
     a = pkg.DroneVecEnv(track, n, **kw)

@@ -1,6 +1,6 @@
 """The per-drone sensor model (dn_enable_sensor: observation latency + per-episode bias) on the HIP path against the CPU oracle
 (oracle/dn_oracle.c orc_vec_step_sens, written from include/dronenav.h as a shifted logical history, no ring, and itself pinned by
-tests/test_oracle_sensor.py).  The configurations, seeds and action streams live in tests/test_oracle_sensor.py, which shows on the
+tests/test_oracle_sensor.py).  The configurations, seeds and action streams live in tests/model_support.py; tests/test_oracle_sensor.py shows on the
 oracle alone that they reach the cases claimed here (every latency 0..8, deliveries with k < d and d <= k, episode ends inside a fused
 launch followed by a delayed delivery, moved spawn points, an episode end on the last drone of a partial tile); every test here first
 checks that its oracle has that file's configuration, byte for byte.
@@ -37,57 +37,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_oracle_actuator as ACTF
-import test_oracle_sensor as CPU
+import model_support as M
 from oracle import oracle as O
-from test_gpu_actuator_oracle import _check_act, _rollout_outs
-from test_gpu_actuator_oracle import _load as _load_act
-from test_gpu_dynamics_wind_oracle import BODY, DEV, GUSTY, NOISE, _check_dw, _features, _pair, _stagger
-from test_gpu_dynamics_wind_oracle import _load as _load_dw
-from test_gpu_parity import _step_mismatch, actions_mixed, compare_step
-from test_gpu_sensor import AMPS
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-
-def _pkg():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    assert BODY == ACTF.BODY and GUSTY == ACTF.GUSTY_KW and NOISE == CPU.NOISE and CPU.SENSOR["bias"] == AMPS
-    return pkg
-
-
-def _same_config(ora, ref):
-    """The oracle of this test is the one tests/test_oracle_sensor.py ran its coverage on."""
-    def same(a, b):
-        return (a is None and b is None) or (a is not None and b is not None and bytes(a) == bytes(b))
-    assert bytes(ora.cfg) == bytes(ref.cfg) and same(ora.act_cfg, ref.act_cfg) and same(ora.sens_cfg, ref.sens_cfg), \
-        "oracle configuration drifted from the CPU file"
-    assert bytes(ora.dw_cfg) == bytes(ref.dw_cfg if ref.dw_cfg is not None else O.make_dw_config())
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.int32)
-
-
-def _get_sens(env):
-    return {k: v.cpu().numpy() for k, v in env.get_sensor().items()}
-
-
-def _load(env, ora):
-    """Teacher forcing: the device's state, scales, wind, actuator arrays and get_sensor() (latency, bias, history) into the oracle.
-    Returns the loaded sensor arrays."""
-    if ora.act_cfg is not None:
-        _load_act(env, ora)
-    else:
-        _load_dw(env, ora)
-    g = _get_sens(env)
-    for k, v in g.items():
-        ora.sens[k] = v
-    return g
+from gpu_support import (DEV, _features, _get_sens, _pair, _rollout_outs, _same_config, _stagger, check_act, check_dw,  # noqa: E402
+                         check_sens, load_sens)
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import NOISE, _step_mismatch, actions_mixed, bits, compare_step  # noqa: E402
 
 
 def _launch(env, acts, single):
@@ -143,32 +103,11 @@ def _exact_deliveries(outs, g0, k0, stats, tag, ncol=13):
         back = (dd > t) & ~restarted
         row = np.where(done.astype(bool)[:, None], info["terminal_obs"], obs)[:, :ncol]
         want = (g0["history"][idx, np.maximum(dd - t - 1, 0)] + g0["bias"])[:, :ncol]
-        assert np.array_equal(_bits(row[back]), _bits(want[back])), f"{tag} t={t}: a row of the loaded history left changed"
+        assert np.array_equal(bits(row[back]), bits(want[back])), f"{tag} t={t}: a row of the loaded history left changed"
         stats.delivered += n
         stats.exact += int(back.sum())
         restarted |= done.astype(bool)
     return restarted
-
-
-def _check_sens(env, ora, rows, g0, k0, K, restarted, bar, tag, ncol=13):
-    """After a launch of K steps: latency and bias exact (draws included), history entries that were already loaded -- entry j >= K of
-    a drone that did not restart -- bit-equal to the loaded entry j - K, entries written during the launch at the observation bar."""
-    got = _get_sens(env)
-    assert np.array_equal(got["latency"][rows], ora.sens["latency"][rows]), f"{tag}: latency"
-    assert np.array_equal(_bits(got["bias"][rows]), _bits(ora.sens["bias"][rows])), f"{tag}: bias"
-    if not ora.sens_cfg.lat_on:
-        return got
-    k = ora.envs["steps"].astype(np.int64)
-    j = np.arange(9)[None, :]
-    valid = (j <= k[:, None]) & rows[:, None]
-    old = valid & (j >= K) & ~restarted[:, None] & (j - K <= k0[:, None])
-    if K < 9:
-        assert np.array_equal(_bits(got["history"][:, K:, :ncol])[old[:, K:]], _bits(g0["history"][:, : 9 - K, :ncol])[old[:, K:]]), \
-            f"{tag}: a loaded history entry changed"
-    new = valid & ~old
-    err = np.abs(got["history"].astype(np.float64) - ora.sens["history"])[:, :, :ncol][new]
-    assert (err <= bar).all(), f"{tag}: history entries written in the launch off the oracle by {err.max():.3e} (bar {bar:.0e})"
-    return got
 
 
 def _outputs(out, ref, f32, norm_var, fused, stats, tag):
@@ -195,7 +134,7 @@ def _outputs(out, ref, f32, norm_var, fused, stats, tag):
 
 
 # ---- a. every instantiation ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dt,norm,noise,mode", CPU.INST_CELLS, ids=[f"{d}-norm{a}-noise{b}-{m}" for d, a, b, m in CPU.INST_CELLS])
+@pytest.mark.parametrize("dt,norm,noise,mode", M.INST_CELLS, ids=[f"{d}-norm{a}-noise{b}-{m}" for d, a, b, m in M.INST_CELLS])
 def test_every_sensor_instantiation_matches_oracle(dt, norm, noise, mode, monkeypatch):
     """n = 1000 (15 full tiles and one of 40 lanes), 150 steps, max_steps = 40, staggered step counters, latency [0, 8] + bias AMPS.
     Measured on one MI355X against the oracle (every run prints the line): 3661 episodes compared in each of the 16 cells, no done
@@ -208,35 +147,35 @@ def test_every_sensor_instantiation_matches_oracle(dt, norm, noise, mode, monkey
     every delayed delivery: 8 of 9 latencies; the rest are undelayed rows or rows measured inside the launch, held at the bar)."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    n, T, K = CPU.INST["n"], CPU.INST["T"], (1 if mode == "step" else CPU.INST["K"])
+    n, T, K = M.INST["n"], M.INST["T"], (1 if mode == "step" else M.INST["K"])
     f32 = dt == "f32"
     if norm and noise and not f32:
         # the reason written in tests/test_gpu_actuator_oracle.py: the default noise draws are float32 transcendentals, one ulp of
         # obs + noise over a running std of 0.01 is 1.2e-5; DN_EXACT_OBS_NOISE=1 is the same kernel with the float64 form of the draws
         monkeypatch.setenv("DN_EXACT_OBS_NOISE", "1")
     dynamics, wind = _features(pkg, bool(norm), bool(norm))
-    kw = dict(max_steps=CPU.INST["max_steps"], normalize_obs=bool(norm), seed=CPU.inst_seed(dt, norm, noise),
-              compute_dtype="float32" if f32 else "float64", sensor=pkg.SensorModel(**CPU.SENSOR), **(NOISE if noise else {}))
+    kw = dict(max_steps=M.INST["max_steps"], normalize_obs=bool(norm), seed=M.sens_inst_seed(dt, norm, noise),
+              compute_dtype="float32" if f32 else "float64", sensor=pkg.SensorModel(**M.SENSOR), **(NOISE if noise else {}))
     if norm:
-        kw.update(actuator=pkg.ActuatorModel(**ACTF.FULL))
+        kw.update(actuator=pkg.ActuatorModel(**M.FULL))
     env, ora = _pair(tracks.circle(1, 4, 1), n, dynamics, wind, **kw)
-    ora.enable_actuator(ACTF.act(**ACTF.FULL) if norm else None)
-    ora.enable_sensor(CPU.sens(**CPU.SENSOR))
-    _same_config(ora, CPU.inst_oracle(dt, norm, noise, n=1))
+    ora.enable_actuator(M.act(**M.FULL) if norm else None)
+    ora.enable_sensor(M.sens(**M.SENSOR))
+    _same_config(ora, M.sens_inst_oracle(dt, norm, noise, n=1))
     assert env.kernel_waves(fused=True) == env.kernel_waves(fused=False) == 1
     r0 = env.reset_tensor().cpu().numpy()
     want0 = ora.reset()
     if not norm:
         np.testing.assert_allclose(r0, want0, rtol=0, atol=5e-4 if f32 else 1e-5, err_msg="reset rows")
     every = np.ones(n, bool)
-    _check_sens(env, ora, every, None, np.zeros(n, np.int64), 9, np.ones(n, bool), 5e-4 if f32 else 1e-5, "reset")
-    rng = np.random.default_rng(CPU.INST["rng"])
+    check_sens(env, ora, every, None, np.zeros(n, np.int64), 9, np.ones(n, bool), 5e-4 if f32 else 1e-5, "reset")
+    rng = np.random.default_rng(M.INST["rng"])
     _stagger(env, rng)
     stats = Stats()
     bar = 5e-4 if f32 else 1e-5
     tag0 = f"{dt}/norm{norm}/noise{noise}/{mode}"
     for launch in range(T // K):
-        g0 = _load(env, ora)
+        g0 = load_sens(env, ora)
         k0 = ora.envs["steps"].astype(np.int64)
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
         outs = _launch(env, acts, mode == "step")
@@ -251,9 +190,9 @@ def test_every_sensor_instantiation_matches_oracle(dt, norm, noise, mode, monkey
             if norm:
                 restarted |= ref["done"].astype(bool)
         if norm:
-            _check_dw(env, ora, agree, f32, mode == "rollout", tag)
-            _check_act(env, ora, agree, f32, mode == "rollout", tag)
-        _check_sens(env, ora, agree, g0, k0, K, restarted, bar, tag)
+            check_dw(env, ora, agree, f32, mode == "rollout", tag)
+            check_act(env, ora, agree, f32, mode == "rollout", tag)
+        check_sens(env, ora, agree, g0, k0, K, restarted, bar, tag)
     assert stats.episodes > n
     assert stats.flips <= n * T * 1e-4, f"{stats.flips} done flags differ"
     assert norm or stats.exact > n, "no delivered row reached back past a launch start"
@@ -262,7 +201,7 @@ def test_every_sensor_instantiation_matches_oracle(dt, norm, noise, mode, monkey
 
 
 # ---- b. options ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cell", range(len(CPU.OPTION_CELLS)), ids=CPU.OPTION_IDS)
+@pytest.mark.parametrize("cell", range(len(M.SENS_OPTION_CELLS)), ids=M.SENS_OPTION_IDS)
 def test_options_with_the_sensor_match_oracle(cell):
     """Teacher-forced single steps, 100 steps at 1024 drones, compare_step's 1e-5, float64 compute.  The 18 cells of
     tests/test_gpu_actuator_oracle.py with the sensor on top, three with the sensor and nothing else (thrust, PID, random_spawn) and
@@ -274,18 +213,18 @@ def test_options_with_the_sensor_match_oracle(cell):
     sensor-only pyb_gnd_drag_dw pid), 0.003 for one_d_rpm, 0.167 in the normaliser cell; 91 454 of 102 400 delivered
     rows (0.8931) checked bit for bit in every raw cell, 91 800 (0.8965) in the random_spawn cells, none in the normaliser cell."""
     pkg = _pkg()
-    n, T = CPU.OPT["n"], CPU.OPT["T"]
-    physics, act, normalized, extra, feat = CPU.OPTION_CELLS[cell]
-    wp, spawn, dim, circle, kw, model, both = CPU.option_cell(cell)
+    n, T = M.SENS_OPT["n"], M.SENS_OPT["T"]
+    physics, act, normalized, extra, feat = M.SENS_OPTION_CELLS[cell]
+    wp, spawn, dim, circle, kw, model, both = M.option_cell(cell)
     dynamics, wind = _features(pkg, both, both)
     env = pkg.DroneVecEnv(None, n, target_points=wp, initial_xyzs=spawn, aviary_dim=dim, circle=circle, device=DEV, physics=physics,
                           act=act, dynamics=dynamics, wind=wind, actuator=None if model is None else pkg.ActuatorModel(**model),
-                          sensor=pkg.SensorModel(**CPU.SENSOR), **kw)
+                          sensor=pkg.SensorModel(**M.SENSOR), **kw)
     assert env.kernel_waves(fused=True) == env.kernel_waves(fused=False) == 1
-    assert pkg.vec_env.PHYSICS == ACTF.PHYSICS and pkg.vec_env.ACTION_TYPES == ACTF.ACTION_TYPES
-    ora = CPU.option_oracle(cell, n, ground_contact=env.ground_contact)
+    assert pkg.vec_env.PHYSICS == M.PHYSICS and pkg.vec_env.ACTION_TYPES == M.ACTION_TYPES
+    ora = M.option_oracle(cell, n, ground_contact=env.ground_contact)
     ora.dw_cfg = O.make_dw_config(dynamics, wind)
-    _same_config(ora, CPU.option_oracle(cell, 1))
+    _same_config(ora, M.option_oracle(cell, 1))
     norm = bool(kw["normalize_obs"])
     ncol = env.obs_dim
     assert ncol == (13 if kw.get("include_distance", True) else 12)
@@ -294,24 +233,24 @@ def test_options_with_the_sensor_match_oracle(cell):
     if not norm:
         np.testing.assert_allclose(r0, want0[:, :ncol], rtol=0, atol=1e-5, err_msg="dn_reset rows")
     every = np.ones(n, bool)
-    _check_sens(env, ora, every, None, np.zeros(n, np.int64), 9, every, 1e-5, "reset", ncol)
-    rng = np.random.default_rng(CPU.OPT["rng"])
+    check_sens(env, ora, every, None, np.zeros(n, np.int64), 9, every, 1e-5, "reset", ncol)
+    rng = np.random.default_rng(M.SENS_OPT["rng"])
     stats = Stats()
-    tag0 = CPU.OPTION_IDS[cell]
+    tag0 = M.SENS_OPTION_IDS[cell]
     for t in range(T):
-        g0 = _load(env, ora)
+        g0 = load_sens(env, ora)
         k0 = ora.envs["steps"].astype(np.int64)
-        a = ACTF.option_actions(rng, n, act, normalized)
+        a = M.option_actions(rng, n, act, normalized)
         outs = _launch(env, a[None], True)
         restarted = outs[0][2].astype(bool)
         if not norm:
             _exact_deliveries(outs, g0, k0, stats, f"{tag0} t={t}", ncol)
         _outputs(outs[0], ora.step(a), False, None, False, stats, f"{tag0} t={t}")
         if both:
-            _check_dw(env, ora, every, False, False, f"{tag0} t={t}")
+            check_dw(env, ora, every, False, False, f"{tag0} t={t}")
         if model is not None:
-            _check_act(env, ora, every, False, False, f"{tag0} t={t}")
-        _check_sens(env, ora, every, g0, k0, 1, restarted, 1e-5, f"{tag0} t={t}", ncol)
+            check_act(env, ora, every, False, False, f"{tag0} t={t}")
+        check_sens(env, ora, every, g0, k0, 1, restarted, 1e-5, f"{tag0} t={t}", ncol)
     assert stats.episodes >= n and (norm or stats.exact > n)
     print(stats.line(tag0))
     env.close()
@@ -344,11 +283,11 @@ def _lockstep(env, ora, acts, lock, tag, single=False):
 def _exact_state(env, ora, lock, tag):
     got = _get_sens(env)
     assert np.array_equal(got["latency"][lock], ora.sens["latency"][lock]), f"{tag}: latency"
-    assert np.array_equal(_bits(got["bias"][lock]), _bits(ora.sens["bias"][lock])), f"{tag}: bias"
+    assert np.array_equal(bits(got["bias"][lock]), bits(ora.sens["bias"][lock])), f"{tag}: bias"
     return got
 
 
-@pytest.mark.parametrize("where", list(CPU.FREE_WHERE))
+@pytest.mark.parametrize("where", list(M.FREE_WHERE))
 def test_free_running_fused_launches_with_the_sensor_match_oracle(where):
     """K = 64 (the 16-slot ring wraps four times per launch), 4096 drones, 256 steps of U(-1, 1) commands on the race track,
     max_steps = 100, dynamics + wind + actuator + sensor; both sides keep their own state.  Sensor latency and bias of the drones in
@@ -358,34 +297,34 @@ def test_free_running_fused_launches_with_the_sensor_match_oracle(where):
     Measured on one MI355X: 8200 (ids past 2^33) and 8195 (step counter across 2^32) episodes compared, 0 drones dropped."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    n, K = CPU.FREE["n"], CPU.FREE["K"]
-    off, sc0 = CPU.FREE_WHERE[where]
+    n, K = M.SENS_FREE["n"], M.SENS_FREE["K"]
+    off, sc0 = M.FREE_WHERE[where]
     dynamics, wind = _features(pkg, True, True)
-    kw = dict(max_steps=CPU.FREE["max_steps"], normalize_obs=False, seed=CPU.FREE["seed"], env_id_offset=off)
-    env, ora = _pair(tracks.reaching(), n, dynamics, wind, actuator=pkg.ActuatorModel(**ACTF.FULL), sensor=pkg.SensorModel(**CPU.SENSOR), **kw)
-    ora.enable_actuator(ACTF.act(**ACTF.FULL))
-    ora.enable_sensor(CPU.sens(**CPU.SENSOR))
-    _same_config(ora, CPU.track_oracle("race", 1, CPU.SENSOR, True, **kw))
+    kw = dict(max_steps=M.SENS_FREE["max_steps"], normalize_obs=False, seed=M.SENS_FREE["seed"], env_id_offset=off)
+    env, ora = _pair(tracks.reaching(), n, dynamics, wind, actuator=pkg.ActuatorModel(**M.FULL), sensor=pkg.SensorModel(**M.SENSOR), **kw)
+    ora.enable_actuator(M.act(**M.FULL))
+    ora.enable_sensor(M.sens(**M.SENSOR))
+    _same_config(ora, M.sens_track_oracle("race", 1, M.SENSOR, True, **kw))
     env.step_count = sc0
     ora.envs["step_count"] = sc0
     np.testing.assert_allclose(env.reset_tensor().cpu().numpy(), ora.reset(), rtol=0, atol=1e-6)
-    rng = np.random.default_rng(CPU.FREE["rng"])
+    rng = np.random.default_rng(M.SENS_FREE["rng"])
     _stagger(env, rng, ora)
     ora.sens["history"] = _get_sens(env)["history"]      # the staggered counters reach behind the reset row: both sides find the same rows there
     lock = np.ones(n, bool)
     n_done = 0
-    for rep in range(CPU.FREE["launches"]):
+    for rep in range(M.SENS_FREE["launches"]):
         acts = np.stack([rng.uniform(-1, 1, (n, 4)).astype(np.float32) for _ in range(K)])
         n_done += _lockstep(env, ora, acts, lock, f"{where} launch {rep}")[0]
-        _check_dw(env, ora, lock, False, True, f"{where} launch {rep}")
-        _check_act(env, ora, lock, False, True, f"{where} launch {rep}")
+        check_dw(env, ora, lock, False, True, f"{where} launch {rep}")
+        check_act(env, ora, lock, False, True, f"{where} launch {rep}")
         _exact_state(env, ora, lock, f"{where} launch {rep}")
-    assert n_done > 2 * n and env.step_count == sc0 + K * CPU.FREE["launches"]
+    assert n_done > 2 * n and env.step_count == sc0 + K * M.SENS_FREE["launches"]
     print(f"SENS {where}: {n_done} episodes compared, {int((~lock).sum())} drones dropped at a branch cut")
     env.close()
 
 
-@pytest.mark.parametrize("n", CPU.SHAPES + CPU.LAUNCH_SHAPES)
+@pytest.mark.parametrize("n", M.SHAPES + M.LAUNCH_SHAPES)
 def test_tile_shapes_match_oracle_and_shadow_lanes_store_nothing(n):
     """resample = 0, latency i mod 9 and a bias row per drone written by set_sensor, max_steps = 6, against the free-running oracle:
     14 single steps, then two launches of 20 in which every drone restarts.  dn_step_many refuses K > 1 unless num_envs % 4 == 0, so at
@@ -397,29 +336,29 @@ def test_tile_shapes_match_oracle_and_shadow_lanes_store_nothing(n):
     476 / 1316; 0 drones dropped in all eight."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    kw = dict(max_steps=CPU.SHAPE["max_steps"], normalize_obs=False, seed=CPU.SHAPE["seed"], **NOISE)
-    model = dict(CPU.SENSOR, resample=False)
+    kw = dict(max_steps=M.SHAPE["max_steps"], normalize_obs=False, seed=M.SHAPE["seed"], **NOISE)
+    model = dict(M.SENSOR, resample=False)
     env, ora = _pair(tracks.circle(1, 4, 1), n, None, None, sensor=pkg.SensorModel(**model), **kw)
-    ora.enable_sensor(CPU.sens(**model))
-    _same_config(ora, CPU.shape_oracle(1))
+    ora.enable_sensor(M.sens(**model))
+    _same_config(ora, M.shape_oracle(1))
     extra = 4 if n % 4 == 0 else 1
     big = pkg.DroneVecEnv(tracks.circle(1, 4, 1), n + extra, device=DEV, sensor=pkg.SensorModel(**model), **kw)
     r_env = env.reset_tensor().cpu().numpy()
     np.testing.assert_allclose(r_env, ora.reset(), rtol=0, atol=1e-6)
-    assert np.array_equal(_bits(big.reset_tensor().cpu().numpy()[:n]), _bits(r_env))
-    vals, vbig = CPU.shape_values(n), CPU.shape_values(n + extra)
+    assert np.array_equal(bits(big.reset_tensor().cpu().numpy()[:n]), bits(r_env))
+    vals, vbig = M.shape_values(n), M.shape_values(n + extra)
     assert all(np.array_equal(vals[k], vbig[k][:n]) for k in vals)
     env.set_sensor(**{k: torch.from_numpy(v).to(DEV) for k, v in vals.items()})
     big.set_sensor(**{k: torch.from_numpy(v).to(DEV) for k, v in vbig.items()})
     for k, v in vals.items():
         ora.sens[k] = v
-    rng = np.random.default_rng(CPU.SHAPE["rng"])
+    rng = np.random.default_rng(M.SHAPE["rng"])
     lock = np.ones(n, bool)
     n_done = last_done = 0
     if n % 4:
         with pytest.raises(pkg._capi.DroneNavError, match="num_envs % 4 == 0"):
-            env.rollout_tensor(torch.zeros((CPU.SHAPE["K"], n, 4), device=DEV))
-    for li, (K, single) in enumerate(CPU.shape_plan(n)):
+            env.rollout_tensor(torch.zeros((M.SHAPE["K"], n, 4), device=DEV))
+    for li, (K, single) in enumerate(M.shape_plan(n)):
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
         tag = f"n={n} launch {li} K={K}"
         done_n, outs = _lockstep(env, ora, acts, lock, tag, single)
@@ -428,14 +367,14 @@ def test_tile_shapes_match_oracle_and_shadow_lanes_store_nothing(n):
         wide = _launch(big, np.concatenate([acts, np.zeros((K, extra, 4), np.float32)], axis=1), single)
         for t, (a, b) in enumerate(zip(outs, wide)):
             dn = a[2].astype(bool)
-            assert np.array_equal(_bits(a[0]), _bits(b[0][:n])) and np.array_equal(_bits(a[1]), _bits(b[1][:n])), f"{tag} t={t}"
-            assert np.array_equal(a[2], b[2][:n]) and np.array_equal(_bits(a[3]["terminal_obs"][dn]), _bits(b[3]["terminal_obs"][:n][dn])), f"{tag} t={t}"
+            assert np.array_equal(bits(a[0]), bits(b[0][:n])) and np.array_equal(bits(a[1]), bits(b[1][:n])), f"{tag} t={t}"
+            assert np.array_equal(a[2], b[2][:n]) and np.array_equal(bits(a[3]["terminal_obs"][dn]), bits(b[3]["terminal_obs"][:n][dn])), f"{tag} t={t}"
         got = _exact_state(env, ora, lock, tag)
-        assert np.array_equal(got["latency"], vals["latency"]) and np.array_equal(_bits(got["bias"]), _bits(vals["bias"])), tag
+        assert np.array_equal(got["latency"], vals["latency"]) and np.array_equal(bits(got["bias"]), bits(vals["bias"])), tag
         gb = _get_sens(big)
         kk = ora.envs["steps"].astype(np.int64)
         valid = (np.arange(9)[None, :] <= kk[:, None]) & lock[:, None]
-        assert np.array_equal(_bits(got["history"])[valid], _bits(gb["history"][:n])[valid]), tag
+        assert np.array_equal(bits(got["history"])[valid], bits(gb["history"][:n])[valid]), tag
     assert n_done >= 2 * n - 8 and last_done > 0, (n_done, last_done)      # ... an episode end on the last drone of the partial tile
     print(f"SENS shape n={n}: {n_done} episodes compared, {int((~lock).sum())} drones dropped at a branch cut")
     env.close()
@@ -448,15 +387,15 @@ def test_values_written_by_set_sensor_are_flown_as_the_oracle_flies_them():
     Measured on one MI355X: 7500 episodes compared, 0 drones dropped."""
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
-    n, K = CPU.SETV["n"], CPU.SETV["K"]
-    model = dict(CPU.SENSOR, resample=False)
-    kw = dict(max_steps=CPU.SETV["max_steps"], normalize_obs=False, seed=CPU.SETV["seed"])
+    n, K = M.SENS_SETV["n"], M.SENS_SETV["K"]
+    model = dict(M.SENSOR, resample=False)
+    kw = dict(max_steps=M.SENS_SETV["max_steps"], normalize_obs=False, seed=M.SENS_SETV["seed"])
     env, ora = _pair(tracks.circle(1, 4, 1), n, None, None, sensor=pkg.SensorModel(**model), **kw)
-    ora.enable_sensor(CPU.sens(**model))
-    _same_config(ora, CPU.setv_oracle(1))
+    ora.enable_sensor(M.sens(**model))
+    _same_config(ora, M.setv_oracle(1))
     np.testing.assert_allclose(env.reset_tensor().cpu().numpy(), ora.reset(), rtol=0, atol=1e-6)
-    rng = np.random.default_rng(CPU.SETV["rng"])
-    steps, vals = CPU.setv_start(rng, n)
+    rng = np.random.default_rng(M.SENS_SETV["rng"])
+    steps, vals = M.setv_start(rng, n)
     st = env.get_state()
     st["steps"] = steps.astype(st["steps"].dtype)
     env.set_state(st)
@@ -466,11 +405,11 @@ def test_values_written_by_set_sensor_are_flown_as_the_oracle_flies_them():
         ora.sens[k] = v
     lock = np.ones(n, bool)
     n_done = 0
-    for rep in range(CPU.SETV["launches"]):
+    for rep in range(M.SENS_SETV["launches"]):
         acts = np.stack([actions_mixed(rng, n) for _ in range(K)])
         n_done += _lockstep(env, ora, acts, lock, f"set values launch {rep}")[0]
         got = _exact_state(env, ora, lock, f"set values launch {rep}")
-        assert np.array_equal(got["latency"], vals["latency"]) and np.array_equal(_bits(got["bias"]), _bits(vals["bias"]))
+        assert np.array_equal(got["latency"], vals["latency"]) and np.array_equal(bits(got["bias"]), bits(vals["bias"]))
     assert n_done > 4 * n - 40
     print(f"SENS set values: {n_done} episodes compared, {int((~lock).sum())} drones dropped at a branch cut")
     env.close()
@@ -483,13 +422,13 @@ def test_late_enable_and_second_enable_match_oracle():
     Measured on one MI355X: 3000 episodes compared, 0 drones dropped."""
     pkg = _pkg()
     from drl_dronenavigation_amd import _capi, tracks
-    R = CPU.REENABLE
+    R = M.REENABLE
     n, K = R["n"], R["K"]
     dynamics, wind = _features(pkg, True, True)
     kw = dict(max_steps=R["max_steps"], normalize_obs=False, seed=R["seed"], **NOISE)
-    env, ora = _pair(tracks.circle(1, 4, 1), n, dynamics, wind, actuator=pkg.ActuatorModel(**ACTF.FULL), **kw)
-    ora.enable_actuator(ACTF.act(**ACTF.FULL))
-    _same_config(ora, CPU.reenable_oracle(1))
+    env, ora = _pair(tracks.circle(1, 4, 1), n, dynamics, wind, actuator=pkg.ActuatorModel(**M.FULL), **kw)
+    ora.enable_actuator(M.act(**M.FULL))
+    _same_config(ora, M.reenable_oracle(1))
     np.testing.assert_allclose(env.reset_tensor().cpu().numpy(), ora.reset(), rtol=0, atol=1e-6)
     rng = np.random.default_rng(R["rng"])
     lock = np.ones(n, bool)
@@ -500,10 +439,10 @@ def test_late_enable_and_second_enable_match_oracle():
         model = pkg.SensorModel(**model_kw)
         _capi.check(lib.dn_enable_sensor(env._handle, C.byref(model.to_c())))
         env.sensor = model
-        ora.enable_sensor(CPU.sens(**model_kw))
+        ora.enable_sensor(M.sens(**model_kw))
         assert bytes(env.sensor_config().to_c()) == bytes(model.to_c())
 
-    enable(CPU.SENSOR)
+    enable(M.SENSOR)
     assert env.kernel_waves(fused=True) == env.kernel_waves(fused=False) == 1
     first = _get_sens(env)
     assert not first["latency"].any() and not first["bias"].any()
@@ -521,8 +460,8 @@ def test_late_enable_and_second_enable_match_oracle():
     after = _get_sens(env)
     kk = env.get_state()["steps"].astype(np.int64)
     valid = np.arange(9)[None, :] <= kk[:, None]
-    assert np.array_equal(after["latency"], before["latency"]) and np.array_equal(_bits(after["bias"]), _bits(before["bias"]))
-    assert np.array_equal(_bits(after["history"])[valid], _bits(before["history"])[valid])
+    assert np.array_equal(after["latency"], before["latency"]) and np.array_equal(bits(after["bias"]), bits(before["bias"]))
+    assert np.array_equal(bits(after["history"])[valid], bits(before["history"])[valid])
     for rep in range(R["launches"]):
         n_done += _lockstep(env, ora, np.stack([actions_mixed(rng, n) for _ in range(K)]), lock, f"second enable launch {rep}")[0]
         got = _exact_state(env, ora, lock, f"second enable launch {rep}")

@@ -16,110 +16,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-WIDE = [-1e4, -1e4, -1e4, 1e4, 1e4, 1e4]
-DEV = "cuda:0"
-STATE_KEYS = ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev", "idx", "steps", "just_found", "ep_ret",
-              "ep_len", "rms_mean", "rms_var", "rms_count", "last_rpm", "ep_ret_lo")
-ZERO = dict(speed=(0.0, 0.0), azimuth=(0.0, 0.0), vertical=(0.0, 0.0), gust_sigma=(0.0, 0.0))
-GUSTY = dict(speed=(0.5, 6.0), azimuth=(-math.pi, math.pi), vertical=(-0.5, 0.5), gust_sigma=(0.8, 0.3), gust_tau=0.25)
-DT = 1.0 / 240.0
-
-
-def _pkg():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU: the HIP path has no CPU fallback")
-    import drl_dronenavigation_amd as pkg
-    return pkg
-
-
-def _mixed(rng, n):
-    bang = rng.uniform(-1, 1, (n, 4))
-    hover = 0.0922 + 0.003 * rng.standard_normal((n, 4))
-    return np.where((np.arange(n) % 2 == 0)[:, None], bang, hover).astype(np.float32)
-
-
-def _acts(rng, n, K):
-    return torch.from_numpy(np.stack([_mixed(rng, n) for _ in range(K)])).to(DEV)
-
-
-def _philox(gid, step, stream, seed):
-    from oracle import oracle as O
-    out = (C.c_uint32 * 4)()
-    O.lib().orc_philox4x32(gid & 0xFFFFFFFF, gid >> 32, step & 0xFFFFFFFF, stream | ((step >> 32) << 8), seed & 0xFFFFFFFF, seed >> 32, out)
-    return np.array(list(out), dtype=np.float64)
-
-
-def _noise(seed, gid0, n, step, stream):
-    """orc_noise4 of drones gid0 .. gid0 + n - 1: [n, 4] float32 (Box-Muller on the C library's log / sqrt / cos / sin)."""
-    from oracle import oracle as O
-    out = np.zeros((n, 4), np.float32)
-    O.lib().orc_noise4_many(seed, gid0, n, step, stream, out.ctypes.data_as(C.POINTER(C.c_float)))
-    return out
-
-
-def _mean_draw(w, gid, step, seed):
-    """The documented steady draw: one Philox4x32-10 call on (seed; gid, step, stream 14), float64, stored as float32."""
-    u = (_philox(gid, step, 14, seed)[:3] + 0.5) / 4294967296.0
-    f = lambda r: (float(np.float32(r[0])), float(np.float32(r[1])))
-    (s0, s1), (a0, a1), (v0, v1) = f(w.speed), f(w.azimuth), f(w.vertical)
-    s, th, v = s0 + (s1 - s0) * u[0], a0 + (a1 - a0) * u[1], v0 + (v1 - v0) * u[2]
-    return np.array([s * math.cos(th), s * math.sin(th), v, 0.0], dtype=np.float32)
-
-
-def _ulps(a, b):
-    """Distance in float32 ulps (same-sign values; 0 and -0 are 0 apart)."""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    ia, ib = a.view(np.int32).astype(np.int64), b.view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia)
-    ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
-    return np.abs(ia - ib)
-
-
-def _sigma3(w):
-    return np.array([w.gust_sigma[0], w.gust_sigma[0], w.gust_sigma[1], 0.0], np.float32)
-
-
-def _same_state(a, b):
-    for k in STATE_KEYS:
-        assert np.ascontiguousarray(a[k]).tobytes() == np.ascontiguousarray(b[k]).tobytes(), k
-
-
-def _same_wind(a, b):
-    for x, y in zip(a.get_wind(), b.get_wind()):
-        assert torch.equal(x, y)
-
-
-def _run_pair(envs, rng, n, launches=3, K=20):
-    """Reset, one dn_step and `launches` fused launches of K steps on every env with the same actions: the outputs, bit for bit."""
-    outs = [e.reset_tensor().clone() for e in envs]
-    for o in outs[1:]:
-        assert torch.equal(outs[0], o)
-    a = torch.from_numpy(_mixed(rng, n)).to(DEV)
-    res = [tuple(x.clone() for x in e.step_tensor(a)[:3]) for e in envs]
-    for r in res[1:]:
-        for x, y in zip(res[0], r):
-            assert torch.equal(x, y)
-    n_done = 0
-    for _ in range(launches):
-        acts = _acts(rng, n, K)
-        rs = [{k: v.clone() for k, v in e.rollout_tensor(acts, want_terminal=True).items()} for e in envs]
-        for r in rs[1:]:
-            for k in rs[0]:
-                assert torch.equal(rs[0][k], r[k]), k
-        n_done += int(rs[0]["done"].sum())
-    sts = [e.get_state() for e in envs]
-    for s in sts[1:]:
-        _same_state(sts[0], s)
-    return n_done
-
-
-def _bullet_env(pkg, n, wind, **kw):
-    """A free body far from every target and wall: no episode ends, actions are the four rotor thrusts."""
-    opts = dict(target_points=np.array([[5e3, 5e3, 5e3]]), initial_xyzs=np.array([[0.0, 0.0, 1.0]]), aviary_dim=WIDE,
-                circle=False, cylinder=False, ground_contact=False, normalize_actions=False, normalize_obs=False,
-                threshold=0.0, max_steps=1 << 20, device=DEV, wind=wind)
-    opts.update(kw)
-    return pkg.DroneVecEnv(None, n, **opts)
+from gpu_support import DEV, _acts, _bullet_env, _run_pair, _same_state, _same_wind  # noqa: E402
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import DT, GUSTY, ZERO, _mean_draw, _mixed, _noise, _sigma3, ulps  # noqa: E402
 
 
 # ---- 1. identity --------------------------------------------------------------------------------------------------------
@@ -179,7 +78,7 @@ def test_steady_wind_step_matches_independent_integrator(with_dynamics, monkeypa
     if with_dynamics:
         scales = rng.uniform(0.7, 1.3, (n, 4)).astype(np.float32)
         kw["dynamics"] = pkg.DynamicsRandomization(resample=False)
-    env = _bullet_env(pkg, n, cfg, **kw)
+    env = _bullet_env(pkg, n, wind=cfg, **kw)
     env.reset_tensor()
     st = env.get_state()
     st["pos"], st["quat"], st["vel"], st["ang_v"], st["cur_pos"] = pos, quat, vel, ang_v, pos
@@ -215,7 +114,7 @@ def test_level_hover_in_steady_wind_closed_form():
     n, steps, speed = 8, 48, 5.0
     theta = np.linspace(-math.pi, math.pi, n, endpoint=False).astype(np.float64) + 0.3
     cfg = pkg.WindDisturbance(resample=False)
-    env = _bullet_env(pkg, n, cfg, zero_damping=True)
+    env = _bullet_env(pkg, n, wind=cfg, zero_damping=True)
     env.reset_tensor()
     mean = np.zeros((n, 4), np.float32)
     mean[:, 0], mean[:, 1] = speed * np.cos(theta), speed * np.sin(theta)
@@ -247,10 +146,10 @@ def test_reset_draws_follow_their_definition():
     mean, gust = (x.cpu().numpy() for x in env.get_wind())
     ids = list(range(512)) + list(range(n - 512, n))
     want = np.stack([_mean_draw(w, g, sc, seed) for g in ids])
-    assert _ulps(mean[ids], want).max(initial=0) <= 1
+    assert ulps(mean[ids], want).max(initial=0) <= 1
     wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
     wg[:, 3] = 0.0
-    assert _ulps(gust, wg).max(initial=0) <= 1
+    assert ulps(gust, wg).max(initial=0) <= 1
     assert np.mean(gust == wg) > 0.999
     s = np.hypot(mean[:, 0].astype(np.float64), mean[:, 1].astype(np.float64))
     th = np.arctan2(mean[:, 1], mean[:, 0]).astype(np.float64)
@@ -267,7 +166,7 @@ def test_gust_recursion_follows_its_definition():
     pkg = _pkg()
     n, seed = 256, 99
     w = pkg.WindDisturbance(speed=(0.0, 3.0), gust_sigma=(0.8, 0.3), gust_tau=0.25)
-    env = _bullet_env(pkg, n, w, seed=seed)
+    env = _bullet_env(pkg, n, wind=w, seed=seed)
     env.reset_tensor()
     a = math.exp(-DT / float(np.float32(w.gust_tau)))            # a and b as the host computes them: float64 from the float32 config
     b = _sigma3(w)[:3].astype(np.float64) * math.sqrt(1.0 - a * a)
@@ -280,7 +179,7 @@ def test_gust_recursion_follows_its_definition():
         mean, g1 = (x.cpu().numpy() for x in env.get_wind())
         xi = _noise(seed, 0, n, sc, 15)[:, :3].astype(np.float64)
         want = (a * g[:, :3].astype(np.float64) + b * xi).astype(np.float32)
-        assert _ulps(g1[:, :3], want).max(initial=0) <= 1, t
+        assert ulps(g1[:, :3], want).max(initial=0) <= 1, t
         assert np.array_equal(mean, mean0)
         g = g1
     env.close()
@@ -290,7 +189,7 @@ def test_gust_statistics():
     pkg = _pkg()
     n, seed, T = 65536, 5, 240
     w = pkg.WindDisturbance(gust_sigma=(0.8, 0.3), gust_tau=0.25)
-    env = _bullet_env(pkg, n, w, seed=seed)
+    env = _bullet_env(pkg, n, wind=w, seed=seed)
     env.reset_tensor()
     hover = torch.full((T, n, 4), RB.M * RB.G / 4.0, device=DEV)
     out = env.rollout_tensor(hover[:T - 1])
@@ -351,10 +250,10 @@ def test_episode_starts_redraw_only_the_finished_drones():
         fin = np.flatnonzero(done)
         for i in fin:
             cur[i] = _mean_draw(w, i, sc, seed)         # the draw of the step the new episode starts on
-        assert _ulps(mean, cur).max(initial=0) <= 1, t
+        assert ulps(mean, cur).max(initial=0) <= 1, t
         cur = mean.copy()
         wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
-        assert _ulps(gust[fin, :3], wg[fin, :3]).max(initial=0) <= 1, t
+        assert ulps(gust[fin, :3], wg[fin, :3]).max(initial=0) <= 1, t
         redrawn += len(fin)
     assert redrawn >= n                                 # max_steps = 6: every drone's episode ended at least once
     env.close()
@@ -380,7 +279,7 @@ def test_without_resample_set_wind_survives_resets_and_the_gust_is_redrawn():
         assert torch.equal(m, mean), t
         fin = np.flatnonzero(done.cpu().numpy())
         wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
-        assert _ulps(gust.cpu().numpy()[fin, :3], wg[fin, :3]).max(initial=0) <= 1, t
+        assert ulps(gust.cpu().numpy()[fin, :3], wg[fin, :3]).max(initial=0) <= 1, t
         n_done += len(fin)
     assert n_done >= n
     sc = env.step_count
@@ -388,7 +287,7 @@ def test_without_resample_set_wind_survives_resets_and_the_gust_is_redrawn():
     m, gust = env.get_wind()
     assert torch.equal(m, mean)
     wg = _sigma3(w) * _noise(seed, 0, n, sc, 16)
-    assert _ulps(gust.cpu().numpy()[:, :3], wg[:, :3]).max(initial=0) <= 1
+    assert ulps(gust.cpu().numpy()[:, :3], wg[:, :3]).max(initial=0) <= 1
     env.close()
 
 

@@ -9,13 +9,12 @@ dn_enable_actuator), pinned on its own before the GPU tes
   tests/rigid_body_ref.py driven by forces formed from a numpy float64 filter (1e-12), with drag, ground effect and scaled bodies;
 - episode starts: r = rpm_fill after every done; the new a acts from the first step of the new episode, the terminal step flew the old;
 - draws: (d, a) against a restatement on orc_philox4x32 words, ids past 2^32 and step counters across 2^32; resample = 0 keeps values;
-- coverage: the configurations, seeds and action streams of tests/test_gpu_actuator_oracle.py (defined HERE, imported there) reach
+- coverage: the configurations, seeds and action streams of tests/test_gpu_actuator_oracle.py (defined once in tests/model_support.py) reach
   the cases that file claims to test -- episode ends, fills, latencies 0 and 8, history entries consumed across a launch boundary,
   episode restarts inside a launch, the ground effect acting -- shown on the oracle alone.
 CPU only; tests/test_oracle_asan.py runs this file under AddressSanitizer / UBSan too."""
 import ctypes as C
 import math
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -23,98 +22,13 @@ from scipy.spatial.transform import Rotation
 
 import rigid_body_ref as RB
 from oracle import oracle as O
-from test_gpu_parity import actions_mixed            # a plain numpy stream; importing that module touches no GPU
-from test_oracle_dynamics_wind import (CASES, CIRCLE6, GUSTY, LOW, WIDE, WIDE_BODY, config, dyn, f32, philox, ulps, unit, wind)
+from model_support import (ACT_FREE, ACT_OPT, ACT_SETV, ACTION_TYPES, BODY, CASES, CIRCLE6, DT, FREE_WHERE, FULL, GUSTY, GUSTY_WIND,
+                           HOVER_FILL, INST, INST_CELLS, LAG_OPTION_CELLS, LAT_OPTION_CELLS, LOW, NOISE, PHYSICS, RAW_FILL, SHORT, WIDE,
+                           WIDE_BODY, act, act_inst_oracle, act_track_oracle, actions_mixed, config, dyn, f32, free_body, option_actions,
+                           option_setup, philox, same_step, short_set_values, stagger, ulps, unit, wind)
 
-DT = 1.0 / 240.0
 FP, DP = C.POINTER(C.c_float), C.POINTER(C.c_double)
-HOVER_FILL = (0.0922, 0.0922, 0.0922, 0.0922)         # normalised hover, the `fill` of tests/test_gpu_actuator.py
 ODD_FILL = (0.05, -0.3, 0.0922, 0.7)
-
-
-def act(latency=(0, 0), motor_tau=(0.0, 0.0), fill=(0.0, 0.0, 0.0, 0.0), resample=True):
-    """What the package's ActuatorModel carries (the oracle reads the attributes only)."""
-    return SimpleNamespace(latency=latency, motor_tau=motor_tau, fill=fill, resample=resample)
-
-
-# ---- the configurations of tests/test_gpu_actuator_oracle.py, defined once -------------------------------------------------
-FULL = dict(latency=(0, 8), motor_tau=(0.02, 0.15), fill=HOVER_FILL)
-BODY = dict(mass=(0.7, 1.3), inertia=(0.7, 1.3), kf=(0.8, 1.2), km=(0.7, 1.3))
-GUSTY_KW = dict(speed=(0.5, 6.0), azimuth=(-math.pi, math.pi), vertical=(-0.5, 0.5), gust_sigma=(0.8, 0.3), gust_tau=0.25)
-NOISE = dict(obs_noise_sigma=0.01, act_noise_sigma=0.001)
-# a. every instantiation
-INST = dict(n=1000, T=150, K=5, max_steps=40, rng=7)
-INST_CELLS = [(dt, norm, noise, mode) for dt in ("f64", "f32") for norm in (0, 1) for noise in (0, 1) for mode in ("step", "rollout")]
-
-
-def inst_seed(dt, norm, noise):
-    return 5000 + norm * 4 + noise * 2 + (dt == "f32")
-
-
-# b. options.  (physics, normalize_actions, extra options, features on)
-LAG_OPTION_CELLS = [("pyb", True, {}, "both"), ("pyb_gnd", True, {}, "both"), ("pyb_drag", True, {}, "both"), ("pyb_dw", True, {}, "both"),
-                    ("pyb_gnd_drag_dw", True, {}, "both"), ("pyb_gnd_drag_dw", True, {}, "none"), ("pyb_gnd_drag_dw", False, {}, "both"),
-                    ("pyb", True, dict(random_spawn=True), "both"), ("pyb", True, dict(clip_rew=True, norm_rew=True), "both"),
-                    ("pyb_drag", True, dict(zero_damping=True), "both"), ("pyb", True, dict(include_distance=False), "both")]
-LAT_OPTION_CELLS = [("pyb_gnd_drag_dw", "rpm"), ("pyb", "rpm"), ("pyb", "pid"), ("pyb", "vel"), ("pyb_drag", "one_d_rpm"),
-                    ("pyb", "one_d_pid"), ("pyb_gnd_drag_dw", "pid")]          # the non-THRUST pairs of OPTION_PAIRS
-OPT = dict(n=1024, T=100, seed=31, rng=5)
-RAW_FILL = (0.07, 0.07, 0.07, 0.07)                    # newton per rotor (normalize_actions off): a little above hover's 0.066
-LAT_FILL = (0.1, -0.2, 0.05, 0.3)
-PHYSICS = {"pyb": 0, "pyb_gnd": 1, "pyb_drag": 2, "pyb_dw": 3, "pyb_gnd_drag_dw": 4}
-ACTION_TYPES = {"thrust": 0, "rpm": 1, "pid": 2, "vel": 3, "one_d_rpm": 4, "one_d_pid": 5}
-LOW_TRACK = (np.array(LOW["waypoints"]), np.array([LOW["spawn"]]), np.array(LOW["dim"]), False)
-
-
-def option_setup(physics, act_name, normalize_actions, extra):
-    """(waypoints, spawn, dim, circle, kw shared by DroneVecEnv and make_config, the actuator's kw) of one option cell."""
-    kw = dict(max_steps=60, normalize_obs=False, seed=OPT["seed"], **extra)
-    if extra.get("random_spawn"):
-        wp, spawn, dim, circle = np.array(CIRCLE6["waypoints"])[1:], np.array([CIRCLE6["spawn"]]), np.array(CIRCLE6["dim"]), True
-        kw.update(max_steps=25, cylinder=False, ground_contact=False)
-    else:
-        wp, spawn, dim, circle = LOW_TRACK
-        kw.update(ground_contact=False, cylinder=False, normalize_actions=normalize_actions)
-    if act_name == "thrust":
-        model = dict(FULL, fill=HOVER_FILL if normalize_actions else RAW_FILL)
-    else:
-        model = dict(latency=(0, 8), fill=LAT_FILL)
-    return wp, spawn, dim, circle, kw, model
-
-
-def option_actions(rng, n, act_name, normalize_actions):
-    if act_name != "thrust":
-        return rng.uniform(-1, 1, (n, 4)).astype(np.float32)
-    return actions_mixed(rng, n) if normalize_actions else rng.uniform(0.02, 0.16, (n, 4)).astype(np.float32)
-
-
-# c. free-running fused launches; d. short launches and set values
-FREE = dict(n=4096, K=64, launches=4, max_steps=100, seed=0xAC7, rng=64)
-FREE_WHERE = {"gid-past-2^33": ((1 << 33) + 12345, 0), "step-across-2^32": (0, (1 << 32) - 100)}
-SHORT = dict(n=2048, Ks=(1, 3, 7, 8, 9, 8, 1, 7, 3, 9, 1, 8, 9, 7, 3, 1, 9, 8, 3, 7), max_steps=30, seed=0x5A0, rng=11)
-SETV = dict(n=2048, K=20, launches=4, max_steps=15, seed=77, rng=12)
-RACE = dict(waypoints=[[(x + 0.0) / 5, y / 5, (z + 3) / 5] for x, y, z in
-                       [[-2.5, 4.5, 3], [10, 3.5, 1], [8, -4.5, 1], [-4.5, -6, 2], [-5, -5, 2], [5, -1, 3], [2.5, 6, 3], [-2.5, 4.5, 3]]],
-            dim=[-4, -4, 0, 4, 4, 4])
-_ANG = np.linspace(0, 2 * np.pi, 5, endpoint=True)
-CIRCLE4 = dict(waypoints=np.stack([0.0 + 1.0 * np.cos(_ANG), 0.0 + 1.0 * np.sin(_ANG), np.full(5, 1.0)], axis=1)[1:], spawn=[1.0, 0.0, 1.0],
-               dim=[-2.0, -2.0, 0.0, 2.0, 2.0, 2.0])
-
-
-def track_oracle(track, n, actuator, dw, **kw):
-    """The oracle side of make_pair for the circle4 (`tracks.circle(1, 4, 1)`) and race (`tracks.reaching()`) tracks: float32 state,
-    the normaliser on unless told, ground contact off (what DN_GROUND_CONTACT_AUTO resolves to on both)."""
-    t = CIRCLE4 if track == "circle4" else dict(RACE, spawn=RACE["waypoints"][0])
-    kw.setdefault("normalize_obs", True)
-    cfg = O.make_config(t["waypoints"], t["spawn"], t["dim"], circle=track == "circle4", f32_state=True, ground_contact=False, **kw)
-    return O.OracleVecEnv(cfg, n, threads=8, dynamics=dyn(**BODY) if dw else None, wind=wind(**GUSTY_KW) if dw else None,
-                          actuator=act(**actuator))
-
-
-def short_set_values(rng, n):
-    """d. the values written by set_actuator: latency 8 for half the drones / random valid values."""
-    return dict(latency=rng.integers(0, 9, n).astype(np.int32), coeff=rng.uniform(0.3, 0.99, n).astype(np.float32),
-                rpm=rng.uniform(9500.0, 21000.0, (n, 4)).astype(np.float32), history=rng.uniform(-1, 1, (n, 8, 4)).astype(np.float32))
 
 
 class Coverage:
@@ -154,10 +68,6 @@ def run_oracle(ora, launches, cov, gnd_every=0):
     return n_gnd
 
 
-def stagger(ora, rng, hi=40):
-    ora.envs["steps"] = rng.integers(0, hi, ora.n).astype(np.int32)
-
-
 # ---- the pieces restated ---------------------------------------------------------------------------------------------------
 def chain(actions, normalized):
     """The nominal float32 action chain's speeds (orc_rescale_action -> orc_preprocess_action, pinned by the golden vectors)."""
@@ -189,18 +99,6 @@ def want_draw(model, gid, step, seed):
     return d, (f32(math.exp(-DT / tau)) if tau > 0.0 else 0.0)
 
 
-def free_body(n, actuator, seed=3, max_steps=1 << 20, **kw):
-    opts = dict(circle=False, cylinder=False, threshold=0.0, max_steps=max_steps, normalize_actions=False, normalize_obs=False, seed=seed)
-    opts.update(kw)
-    cfg = O.make_config([[5e3, 5e3, 5e3]], [0.0, 0.0, 1.0], WIDE, **opts)
-    return O.OracleVecEnv(cfg, n, actuator=actuator)
-
-
-def same_step(ra, rb, tag):
-    for k in ra:
-        assert ra[k].tobytes() == rb[k].tobytes(), (tag, k)
-
-
 # ---- layout -----------------------------------------------------------------------------------------------------------------
 def test_layouts():
     L = O.lib()
@@ -225,7 +123,7 @@ def test_off_is_off_bit_for_bit(physics, act_type, spawn):
     track = CIRCLE6 if spawn else LOW
     kw = dict(max_steps=30, normalize_obs=True, ground_contact=False, physics=physics, action_type=act_type, random_spawn=spawn,
               normalize_actions=act_type == 0, seed=7, f32_state=True, act_noise_sigma=0.01, obs_noise_sigma=0.01)
-    feat = dict(dynamics=WIDE_BODY, wind=GUSTY) if physics % 2 == 0 else {}
+    feat = dict(dynamics=WIDE_BODY, wind=GUSTY_WIND) if physics % 2 == 0 else {}
     base = O.OracleVecEnv(config(track, **kw), n, **feat)
     none = O.OracleVecEnv(config(track, **kw), n, actuator=None, **feat)
     zero = O.OracleVecEnv(config(track, **kw), n, actuator=act(fill=ODD_FILL), **feat)
@@ -266,8 +164,8 @@ def test_latency_equals_the_oracle_fed_shifted_actions(variant):
     if variant != "plain":
         kw.update(NOISE)
     dw = variant == "dynamics+wind"
-    A = track_oracle("circle4", n, dict(latency=(0, 8), fill=ODD_FILL), dw, **kw)
-    B = track_oracle("circle4", n, dict(), dw, **kw)
+    A = act_track_oracle("circle4", n, dict(latency=(0, 8), fill=ODD_FILL), dw, **kw)
+    B = act_track_oracle("circle4", n, dict(), dw, **kw)
     B.enable_actuator(None)
     assert A.reset().tobytes() == B.reset().tobytes()
     rng = np.random.default_rng(5)
@@ -299,9 +197,9 @@ def test_zero_coefficient_is_the_nominal_path_bit_for_bit(normalized):
     n, T = 200, 70
     kw = dict(max_steps=25, normalize_obs=True, ground_contact=False, physics=4, seed=9, f32_state=True, normalize_actions=normalized,
               obs_noise_sigma=0.01)
-    lagged = O.OracleVecEnv(config(LOW, **kw), n, dynamics=WIDE_BODY, wind=GUSTY,
+    lagged = O.OracleVecEnv(config(LOW, **kw), n, dynamics=WIDE_BODY, wind=GUSTY_WIND,
                             actuator=act(motor_tau=(0.02, 0.15), fill=HOVER_FILL if normalized else RAW_FILL, resample=False))
-    plain = O.OracleVecEnv(config(LOW, **kw), n, dynamics=WIDE_BODY, wind=GUSTY)
+    plain = O.OracleVecEnv(config(LOW, **kw), n, dynamics=WIDE_BODY, wind=GUSTY_WIND)
     assert lagged.reset().tobytes() == plain.reset().tobytes()
     rng = np.random.default_rng(2)
     n_done = 0
@@ -484,15 +382,10 @@ def test_without_resample_written_values_survive_episode_starts():
 
 
 # ---- coverage of the GPU configurations, on the reference alone --------------------------------------------------------------------
-def inst_oracle(dt, norm, noise):
-    return track_oracle("circle4", INST["n"], FULL, bool(norm), max_steps=INST["max_steps"], normalize_obs=bool(norm),
-                        seed=inst_seed(dt, norm, noise), **(NOISE if noise else {}))
-
-
 @pytest.mark.parametrize("dt,norm,noise,mode", INST_CELLS, ids=[f"{d}-norm{a}-noise{b}-{m}" for d, a, b, m in INST_CELLS])
 def test_coverage_of_the_instantiation_cells(dt, norm, noise, mode):
     n, T, K = INST["n"], INST["T"], (1 if mode == "step" else INST["K"])
-    ora = inst_oracle(dt, norm, noise)
+    ora = act_inst_oracle(dt, norm, noise)
     ora.reset()
     rng = np.random.default_rng(INST["rng"])
     stagger(ora, rng)
@@ -507,7 +400,7 @@ def test_coverage_of_the_instantiation_cells(dt, norm, noise, mode):
 
 @pytest.mark.parametrize("cell", range(len(LAG_OPTION_CELLS) + len(LAT_OPTION_CELLS)))
 def test_coverage_of_the_option_cells(cell):
-    n, T = OPT["n"], OPT["T"]
+    n, T = ACT_OPT["n"], ACT_OPT["T"]
     if cell < len(LAG_OPTION_CELLS):
         physics, normalized, extra, feat = LAG_OPTION_CELLS[cell]
         act_name = "thrust"
@@ -516,10 +409,10 @@ def test_coverage_of_the_option_cells(cell):
     wp, spawn, dim, circle, kw, model = option_setup(physics, act_name, normalized, extra)
     cfg = O.make_config(wp, spawn.ravel(), dim, circle=circle, f32_state=True, physics=PHYSICS[physics], action_type=ACTION_TYPES[act_name], **kw)
     both = feat == "both"
-    ora = O.OracleVecEnv(cfg, n, threads=8, dynamics=dyn(**BODY) if both else None, wind=wind(**GUSTY_KW) if both else None,
+    ora = O.OracleVecEnv(cfg, n, threads=8, dynamics=dyn(**BODY) if both else None, wind=wind(**GUSTY) if both else None,
                          actuator=act(**model))
     ora.reset()
-    rng = np.random.default_rng(OPT["rng"])
+    rng = np.random.default_rng(ACT_OPT["rng"])
     cov = Coverage()
     gnd = "gnd" in physics and not extra.get("random_spawn")
     n_gnd = run_oracle(ora, ([option_actions(rng, n, act_name, normalized)] for _ in range(T)), cov, gnd_every=5 if gnd else 0)
@@ -534,22 +427,22 @@ def test_coverage_of_the_option_cells(cell):
 
 @pytest.mark.parametrize("where", list(FREE_WHERE))
 def test_coverage_of_the_free_running_launches(where):
-    n, K = FREE["n"], FREE["K"]
+    n, K = ACT_FREE["n"], ACT_FREE["K"]
     off, sc0 = FREE_WHERE[where]
-    ora = track_oracle("race", n, FULL, True, max_steps=FREE["max_steps"], normalize_obs=False, seed=FREE["seed"], env_id_offset=off)
+    ora = act_track_oracle("race", n, FULL, True, max_steps=ACT_FREE["max_steps"], normalize_obs=False, seed=ACT_FREE["seed"], env_id_offset=off)
     ora.envs["step_count"] = sc0
     ora.reset()
-    rng = np.random.default_rng(FREE["rng"])
+    rng = np.random.default_rng(ACT_FREE["rng"])
     stagger(ora, rng)
     cov = Coverage()
-    run_oracle(ora, (np.stack([rng.uniform(-1, 1, (n, 4)).astype(np.float32) for _ in range(K)]) for _ in range(FREE["launches"])), cov)
+    run_oracle(ora, (np.stack([rng.uniform(-1, 1, (n, 4)).astype(np.float32) for _ in range(K)]) for _ in range(ACT_FREE["launches"])), cov)
     assert cov.n_done > 2 * n and cov.restarted > 0 and cov.crossed > 0 and {0, 8} <= cov.seen, vars(cov)
-    assert int(ora.envs["step_count"][0]) == sc0 + K * FREE["launches"]
+    assert int(ora.envs["step_count"][0]) == sc0 + K * ACT_FREE["launches"]
 
 
 def test_coverage_of_the_short_launches_and_set_values():
     n = SHORT["n"]
-    ora = track_oracle("circle4", n, FULL, True, max_steps=SHORT["max_steps"], normalize_obs=False, seed=SHORT["seed"])
+    ora = act_track_oracle("circle4", n, FULL, True, max_steps=SHORT["max_steps"], normalize_obs=False, seed=SHORT["seed"])
     ora.reset()
     rng = np.random.default_rng(SHORT["rng"])
     stagger(ora, rng, hi=SHORT["max_steps"])
@@ -562,11 +455,11 @@ def test_coverage_of_the_short_launches_and_set_values():
     for K, cov in per_k.items():
         assert cov.crossed > 0 and cov.n_done > 0 and 8 in cov.seen, (K, vars(cov))
         assert (cov.restarted > 0) == (K > 1), (K, vars(cov))
-    ora = track_oracle("circle4", n, dict(FULL, resample=False), False, max_steps=SETV["max_steps"], normalize_obs=False, seed=SETV["seed"])
+    ora = act_track_oracle("circle4", n, dict(FULL, resample=False), False, max_steps=ACT_SETV["max_steps"], normalize_obs=False, seed=ACT_SETV["seed"])
     ora.reset()
-    rng = np.random.default_rng(SETV["rng"])
+    rng = np.random.default_rng(ACT_SETV["rng"])
     for k, v in short_set_values(rng, n).items():
         ora.act[k] = v
     cov = Coverage()
-    run_oracle(ora, (np.stack([actions_mixed(rng, n) for _ in range(SETV["K"])]) for _ in range(SETV["launches"])), cov)
+    run_oracle(ora, (np.stack([actions_mixed(rng, n) for _ in range(ACT_SETV["K"])]) for _ in range(ACT_SETV["launches"])), cov)
     assert cov.n_done > 2 * n and cov.crossed > 0 and cov.restarted > 0 and cov.seen == set(range(9)), vars(cov)

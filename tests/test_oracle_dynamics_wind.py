@@ -13,7 +13,6 @@ dn_enable_dynamics / dn_enable_wind), pinned on its own b
 CPU only; tests/test_oracle_asan.py runs this file under AddressSanitizer / UBSan too."""
 import ctypes as C
 import math
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -21,103 +20,13 @@ from scipy.spatial.transform import Rotation
 
 import rigid_body_ref as RB
 from oracle import oracle as O
-
-DT = 1.0 / 240.0
-WIDE = [-1e4, -1e4, -1e4, 1e4, 1e4, 1e4]
-CIRCLE6 = dict(waypoints=[[math.cos(a), math.sin(a), 1.0] for a in np.linspace(0, 2 * np.pi, 7)], spawn=[1.0, 0.0, 1.0],
-               dim=[-2.0, -2.0, 0.0, 2.0, 2.0, 2.0], circle=True)
-LOW = dict(waypoints=[[0.0, 1.0, 0.4], [-1.0, 0.0, 0.8], [0.0, -1.0, 0.4]], spawn=[1.0, 0.0, 0.05], dim=[-2.0, -2.0, 0.0, 2.0, 2.0, 2.0],
-           circle=False, cylinder=False)
-
-
-def dyn(mass=(1.0, 1.0), inertia=(1.0, 1.0), kf=(1.0, 1.0), km=(1.0, 1.0), resample=True):
-    """What the package's DynamicsRandomization carries (the oracle reads the attributes only)."""
-    return SimpleNamespace(mass=mass, inertia=inertia, kf=kf, km=km, resample=resample)
-
-
-def wind(speed=(0.0, 0.0), azimuth=(0.0, 2.0 * math.pi), vertical=(0.0, 0.0), gust_sigma=(0.0, 0.0), gust_tau=0.5,
-         coeff=(5.5626e-3, 6.2490e-3), resample=True):
-    """What the package's WindDisturbance carries."""
-    return SimpleNamespace(speed=speed, azimuth=azimuth, vertical=vertical, gust_sigma=gust_sigma, gust_tau=gust_tau, coeff=coeff,
-                           resample=resample)
-
+from model_support import (CASES, CIRCLE6, DT, GUSTY_WIND, LOW, WIDE, WIDE_BODY, config, dyn, f32, ulps, want_gust_start,
+                           want_gust_step, want_mean, want_scales, wind)
 
 SIZEOF_ENV, SIZEOF_CONFIG = 696, 1704        # orc_env / orc_config before this extension: the golden replays' layout
-GUSTY = wind(speed=(0.5, 6.0), azimuth=(-math.pi, math.pi), vertical=(-0.5, 0.5), gust_sigma=(0.8, 0.3), gust_tau=0.25)
-WIDE_BODY = dyn(mass=(0.7, 1.3), inertia=(0.7, 1.3), kf=(0.8, 1.2), km=(0.7, 1.3))
-
-
-def f32(x):
-    return float(np.float32(x))
-
-
-def philox(gid, step, stream, seed):
-    out = (C.c_uint32 * 4)()
-    O.lib().orc_philox4x32(gid & 0xFFFFFFFF, gid >> 32, step & 0xFFFFFFFF, stream | ((step >> 32) << 8), seed & 0xFFFFFFFF, seed >> 32, out)
-    return [int(v) for v in out]
-
-
-def unit(r):
-    return (r + 0.5) / 4294967296.0
-
-
-def normals(gid, step, stream, seed):
-    """orc_noise4's definition restated: Box-Muller in float64 on the four Philox words, rounded to float32."""
-    r = philox(gid, step, stream, seed)
-    z = []
-    for h in range(2):
-        rad = math.sqrt(-2.0 * math.log(unit(r[2 * h])))
-        ang = 2.0 * math.pi * unit(r[2 * h + 1])
-        z += [f32(rad * math.cos(ang)), f32(rad * math.sin(ang))]
-    return z
-
-
-def want_scales(d, gid, step, seed):
-    r = philox(gid, step, 13, seed)
-    return [f32(f32(lo) + (f32(hi) - f32(lo)) * unit(r[j])) for j, (lo, hi) in enumerate((d.mass, d.inertia, d.kf, d.km))]
-
-
-def want_mean(w, gid, step, seed):
-    r = philox(gid, step, 14, seed)
-    s = f32(w.speed[0]) + (f32(w.speed[1]) - f32(w.speed[0])) * unit(r[0])
-    th = f32(w.azimuth[0]) + (f32(w.azimuth[1]) - f32(w.azimuth[0])) * unit(r[1])
-    v = f32(w.vertical[0]) + (f32(w.vertical[1]) - f32(w.vertical[0])) * unit(r[2])
-    return [f32(s * math.cos(th)), f32(s * math.sin(th)), f32(v), 0.0]
-
-
-def want_gust_start(w, gid, step, seed):
-    z = normals(gid, step, 16, seed)
-    sx, sz = np.float32(w.gust_sigma[0]), np.float32(w.gust_sigma[1])
-    return [float(sx * np.float32(z[0])), float(sx * np.float32(z[1])), float(sz * np.float32(z[2])), 0.0]
-
-
-def want_gust_step(w, g, gid, step, seed):
-    a = math.exp(-DT / f32(w.gust_tau))
-    root = math.sqrt(1.0 - a * a)
-    b = [f32(w.gust_sigma[0]) * root, f32(w.gust_sigma[0]) * root, f32(w.gust_sigma[1]) * root]
-    z = normals(gid, step, 15, seed)
-    return [f32(a * float(g[j]) + b[j] * z[j]) for j in range(3)] + [0.0]
-
-
-def ulps(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    ia, ib = a.view(np.int32).astype(np.int64), b.view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia)
-    ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
-    return np.abs(ia - ib)
-
-
-def config(track, **kw):
-    t = dict(track)
-    opts = dict(circle=t.pop("circle"), cylinder=t.pop("cylinder", True))
-    opts.update(kw)
-    return O.make_config(t["waypoints"], t["spawn"], t["dim"], **opts)
 
 
 # ---- identity -----------------------------------------------------------------------------------------------------------
-CASES = [(p, a, False) for p in range(5) for a in range(6)] + [(0, 0, True), (4, 2, True)]
-
-
 @pytest.mark.parametrize("physics,act,spawn", CASES)
 def test_unit_scales_and_still_air_are_the_nominal_oracle(physics, act, spawn):
     """dynamics on with ranges [1, 1] (resample: every episode start draws exactly 1) and wind on with every range 0 and the gust
@@ -225,7 +134,7 @@ def test_episode_start_and_gust_draws_follow_the_header(offset, step0):
     against the header's formulas on orc_philox4x32 words: scales exact, steady wind and gusts within one float32 ulp (libm cos /
     sin / log on both sides: equal here)."""
     n, seed = 40, 0x1234_5678_9ABC
-    d, w = WIDE_BODY, GUSTY
+    d, w = WIDE_BODY, GUSTY_WIND
     for max_steps, T in ((0, 3), (1 << 20, 3)):
         cfg = O.make_config([[5e3, 5e3, 5e3]], [0.0, 0.0, 1.0], WIDE, circle=False, cylinder=False, threshold=0.0, max_steps=max_steps,
                             normalize_obs=False, seed=seed, env_id_offset=offset, action_type=1, normalize_actions=False)

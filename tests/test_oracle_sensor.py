@@ -7,152 +7,30 @@ LOGICAL state dn_get_sensor returns -- d, b[13], hist[9][13] with hist[j] = o_{k
   action-type x spawn grid of tests/test_oracle_actuator.py;
 - transparency: reward, done, truncated, found_targets, ep_ret, ep_len and every state field outside the normaliser statistics are
   byte-equal to the same oracle without the sensor;
-- the delivery rule, bit for bit, against tests/test_gpu_sensor.py's numpy Delivery on the sensor-less oracle's rows, terminal and
+- the delivery rule, bit for bit, against tests/model_support.py's numpy Delivery on the sensor-less oracle's rows, terminal and
   reset rows included; the normaliser against the float64 Rms64 on the delivered stream at 1e-5 + 1e-5 |x|;
 - draws against a restatement on orc_philox4x32 words, ids past 2^33 and step counters across 2^32;
 - resample = 0: written d and b survive episode starts and are always applied, the reset row carries the written bias, and no row of
   the previous episode is delivered in the new one;
-- coverage: the configurations, seeds and action streams of tests/test_gpu_sensor_oracle.py (defined HERE, imported there) reach the
+- coverage: the configurations, seeds and action streams of tests/test_gpu_sensor_oracle.py (defined once in tests/model_support.py) reach the
   cases that file claims to test, shown on the oracle alone.
 CPU only; tests/test_oracle_asan.py runs this file under AddressSanitizer / UBSan too."""
 import ctypes as C
 import math
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-import test_oracle_actuator as ACTF
+from model_support import (AMPS, CASES, CIRCLE6, FREE_WHERE, GUSTY_WIND, INST, INST_CELLS, LAT_FILL, LAUNCH_SHAPES, LOW, NOISE,
+                           REENABLE, SENS_FREE, SENS_OPT, SENS_OPTION_CELLS, SENS_OPTION_IDS, SENS_SETV, SENSOR, SHAPE, SHAPES, WIDE_BODY,
+                           Delivery, Rms64, act, actions_mixed, bits, config, free_body, option_actions, option_oracle, philox,
+                           reenable_oracle, same_step, sens, sens_inst_oracle, sens_track_oracle, set_values, setv_oracle, setv_start,
+                           shape_oracle, shape_plan, shape_values, stagger, unit)
 from oracle import oracle as O
-# actions_mixed is a plain numpy stream; AMPS, Delivery and Rms64 are numpy statements.  Importing their modules touches no GPU, but they
-# import torch at module level (pytest.importorskip), as test_oracle_actuator's own import of test_gpu_parity already does: without torch
-# this file is skipped with them.
-from test_gpu_parity import actions_mixed
-from test_gpu_sensor import AMPS, Delivery, Rms64
-from test_oracle_dynamics_wind import CASES, CIRCLE6, GUSTY, LOW, WIDE_BODY, config, dyn, philox, unit, wind
 
 FP = C.POINTER(C.c_float)
 OUT_KEYS = ("reward", "done", "truncated", "found_targets", "ep_ret", "ep_len", "terminated")
 NOT_RMS = [k for k in O.ENV_DTYPE.names if not k.startswith("rms_")]
-
-
-def sens(latency=(0, 0), bias=0.0, resample=True):
-    """What the package's SensorModel carries (the oracle reads the attributes only)."""
-    b = (float(bias),) * 13 if isinstance(bias, (int, float)) else tuple(float(v) for v in bias)
-    return SimpleNamespace(latency=tuple(latency), bias=b, resample=resample)
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.int32)
-
-
-# ---- the configurations of tests/test_gpu_sensor_oracle.py, defined once --------------------------------------------------------
-SENSOR = dict(latency=(0, 8), bias=AMPS)
-NOISE = ACTF.NOISE
-# a. every instantiation: the shapes of ACTF.INST; the norm cells carry dynamics + wind + actuator, the raw cells the sensor alone
-INST = ACTF.INST
-INST_CELLS = ACTF.INST_CELLS
-
-
-def inst_seed(dt, norm, noise):
-    return 7000 + norm * 4 + noise * 2 + (dt == "f32")
-
-
-def track_oracle(track, n, sensor, full, **kw):
-    """ACTF.track_oracle with the sensor; full: dynamics + wind + the FULL actuator ride along, else the sensor is alone."""
-    ora = ACTF.track_oracle(track, n, ACTF.FULL if full else {}, full, **kw)
-    if not full:
-        ora.enable_actuator(None)
-    ora.enable_sensor(None if sensor is None else sens(**sensor))
-    return ora
-
-
-def inst_oracle(dt, norm, noise, n=None):
-    return track_oracle("circle4", INST["n"] if n is None else n, SENSOR, bool(norm), max_steps=INST["max_steps"], normalize_obs=bool(norm),
-                        seed=inst_seed(dt, norm, noise), **(NOISE if noise else {}))
-
-
-# b. options: the 18 cells of the actuator file with the sensor on top, two (three) with the sensor and nothing else, one with the
-# normaliser.  (physics, action type, normalize_actions, extra options, features: both | none | sensor)
-OPTION_CELLS = ([(p, "thrust", na, e, f) for p, na, e, f in ACTF.LAG_OPTION_CELLS] + [(p, a, False, {}, "both") for p, a in ACTF.LAT_OPTION_CELLS]
-                + [("pyb", "thrust", True, {}, "sensor"), ("pyb_gnd_drag_dw", "pid", False, {}, "sensor"),
-                   ("pyb", "thrust", True, dict(random_spawn=True), "sensor"), ("pyb_gnd", "thrust", True, dict(normalize_obs=True), "both")])
-OPTION_IDS = [f"{p}-{a}-{'norm' if na else 'raw'}-{'-'.join(e) or 'plain'}-{f}" for p, a, na, e, f in OPTION_CELLS]
-OPT = dict(ACTF.OPT, seed=47)
-
-
-def option_cell(cell):
-    """(waypoints, spawn, dim, circle, kw shared by DroneVecEnv and make_config, the actuator's kw or None, dynamics + wind on) of a cell."""
-    physics, act_name, normalized, extra, feat = OPTION_CELLS[cell]
-    extra = dict(extra)
-    norm_obs = extra.pop("normalize_obs", False)
-    wp, spawn, dim, circle, kw, model = ACTF.option_setup(physics, act_name, normalized, extra)
-    kw.update(normalize_obs=norm_obs, seed=OPT["seed"])
-    return wp, spawn, dim, circle, kw, (None if feat == "sensor" else model), feat == "both"
-
-
-def option_oracle(cell, n, ground_contact=None):
-    physics, act_name = OPTION_CELLS[cell][:2]
-    wp, spawn, dim, circle, kw, model, both = option_cell(cell)
-    if ground_contact is not None:
-        kw = dict(kw, ground_contact=ground_contact)
-    cfg = O.make_config(wp, spawn.ravel(), dim, circle=circle, f32_state=True, physics=ACTF.PHYSICS[physics],
-                        action_type=ACTF.ACTION_TYPES[act_name], **kw)
-    return O.OracleVecEnv(cfg, n, threads=8, dynamics=dyn(**ACTF.BODY) if both else None, wind=wind(**ACTF.GUSTY_KW) if both else None,
-                          actuator=None if model is None else ACTF.act(**model), sensor=sens(**SENSOR))
-
-
-# c. free-running launches; d. tile shapes; e. set values; f. late enable and re-enable
-FREE = dict(ACTF.FREE, seed=0x5E75)
-FREE_WHERE = ACTF.FREE_WHERE
-SHAPES = (1, 63, 65, 191)
-# dn_step_many refuses K > 1 unless num_envs % 4 == 0, so the K = 20 launches cannot run at SHAPES: those fly the same number of steps as
-# single steps, and the nearest fleet sizes a launch accepts (still one partial tile each) fly the launches
-LAUNCH_SHAPES = (4, 60, 68, 188)
-SHAPE = dict(singles=14, K=20, launches=2, max_steps=6, seed=0x7A9, rng=21)
-SETV = dict(n=1500, K=20, launches=4, max_steps=15, seed=79, rng=13)
-REENABLE = dict(n=1000, pre=30, K=20, launches=3, max_steps=40, seed=91, rng=17, second=dict(latency=(2, 5), bias=tuple(2.0 * a for a in AMPS)))
-
-
-def shape_oracle(n):
-    return track_oracle("circle4", n, dict(SENSOR, resample=False), False, max_steps=SHAPE["max_steps"], normalize_obs=False,
-                        seed=SHAPE["seed"], **NOISE)
-
-
-def shape_plan(n):
-    """d. the (K, single step?) sequence of a shape: 14 single steps, then two launches of 20 where dn_step_many takes the fleet size,
-    40 more single steps where it does not."""
-    tail = [(SHAPE["K"], False)] * SHAPE["launches"] if n % 4 == 0 else [(1, True)] * (SHAPE["K"] * SHAPE["launches"])
-    return [(1, True)] * SHAPE["singles"] + tail
-
-
-def shape_values(n):
-    """d. what set_sensor writes: latency i mod 9, a bias row that names its drone and column."""
-    i = np.arange(n)
-    return dict(latency=(i % 9).astype(np.int32),
-                bias=(0.01 * ((i[:, None] * 13 + np.arange(13)[None, :]) % 17 - 8)).astype(np.float32))
-
-
-def setv_oracle(n=None):
-    return track_oracle("circle4", SETV["n"] if n is None else n, dict(SENSOR, resample=False), False, max_steps=SETV["max_steps"],
-                        normalize_obs=False, seed=SETV["seed"])
-
-
-def set_values(rng, n):
-    """e. random valid latency / bias / history for set_sensor."""
-    return dict(latency=rng.integers(0, 9, n).astype(np.int32), bias=rng.uniform(-0.1, 0.1, (n, 13)).astype(np.float32),
-                history=rng.uniform(-1, 1, (n, 9, 13)).astype(np.float32))
-
-
-def setv_start(rng, n):
-    """e. the staggered episode step counters (so that written history entries are inside the episode and get delivered), then the values."""
-    return rng.integers(0, SETV["max_steps"], n).astype(np.int32), set_values(rng, n)
-
-
-def reenable_oracle(n=None):
-    """f. starts WITHOUT the sensor (enable_sensor comes later), dynamics + wind + actuator on."""
-    return track_oracle("circle4", REENABLE["n"] if n is None else n, None, True, max_steps=REENABLE["max_steps"], normalize_obs=False,
-                        seed=REENABLE["seed"], **NOISE)
 
 
 class Coverage:
@@ -201,7 +79,7 @@ def test_layouts():
     assert [O.SENS_DTYPE.fields[k][1] for k in ("latency", "bias", "history")] == [0, 4, 56]
     f = O.OrcSensConfig
     assert (f.latency.offset, f.bias_amp.offset, f.resample.offset, f.reserved.offset) == (0, 8, 60, 64)     # dn_sensor_config's
-    ora = ACTF.free_body(3, None)
+    ora = free_body(3, None)
     ora.enable_sensor(sens(latency=(2, 5), bias=AMPS))
     assert not ora.sens.tobytes().strip(b"\0")                           # the first enable: d = 0, b = 0, an all-zero history
     rule = {(lat, amp, rs): (c.lat_on, c.bias_on) for lat in ((0, 0), (0, 3), (2, 2)) for amp in (0.0, 0.1) for rs in (True, False)
@@ -219,7 +97,7 @@ def test_off_is_off_bit_for_bit(physics, act_type, spawn):
     track = CIRCLE6 if spawn else LOW
     kw = dict(max_steps=30, normalize_obs=True, ground_contact=False, physics=physics, action_type=act_type, random_spawn=spawn,
               normalize_actions=act_type == 0, seed=7, f32_state=True, act_noise_sigma=0.01, obs_noise_sigma=0.01)
-    feat = dict(dynamics=WIDE_BODY, wind=GUSTY, actuator=ACTF.act(latency=(0, 8), fill=ACTF.LAT_FILL)) if physics % 2 == 0 else {}
+    feat = dict(dynamics=WIDE_BODY, wind=GUSTY_WIND, actuator=act(latency=(0, 8), fill=LAT_FILL)) if physics % 2 == 0 else {}
     base = O.OracleVecEnv(config(track, **kw), n, **feat)
     others = [O.OracleVecEnv(config(track, **kw), n, sensor=s, **feat) for s in (None, sens(), sens(latency=(0, 0), bias=(0.0,) * 13))]
     L = O.lib()
@@ -239,7 +117,7 @@ def test_off_is_off_bit_for_bit(physics, act_type, spawn):
         L.orc_vec_step_act(C.byref(base.cfg), *base._dw_args(), *base._act_args(), O._p(base.envs), n, O._p(acts), *(O._p(out[k]) for k in (
             "obs", "reward", "done", "truncated", "found_targets", "terminal_obs", "ep_ret", "ep_len", "terminated")), 1)
         for o in others:
-            ACTF.same_step(out, o.step(acts), t)
+            same_step(out, o.step(acts), t)
         n_done += int(out["done"].sum())
     for o in others:
         assert base.envs.tobytes() == o.envs.tobytes() and base.dw.tobytes() == o.dw.tobytes() and base.act.tobytes() == o.act.tobytes()
@@ -300,8 +178,8 @@ def drive(S, P, model, T, rng, make_acts, norm, seed, gid0=0, sc0=0, stagger=Tru
 def test_delivery_rule_transparency_and_normaliser(full, norm):
     n, T, seed = 300, 240, 31
     kw = dict(max_steps=40, seed=seed, **NOISE)
-    S = track_oracle("circle4", n, SENSOR, full, normalize_obs=norm, **kw)
-    P = track_oracle("circle4", n, None, full, normalize_obs=False, **kw)
+    S = sens_track_oracle("circle4", n, SENSOR, full, normalize_obs=norm, **kw)
+    P = sens_track_oracle("circle4", n, None, full, normalize_obs=False, **kw)
     dl, worst = drive(S, P, sens(**SENSOR), T, np.random.default_rng(5), actions_mixed, norm, seed)
     assert dl.seen == set(range(9)) and dl.ends >= 3 * n and dl.young > 0, (dl.seen, dl.ends, dl.young)
     if norm:
@@ -315,7 +193,7 @@ def test_each_half_alone(which):
     model = dict(latency=(0, 8), bias=0.0) if which == "latency-alone" else dict(latency=(0, 0), bias=AMPS)
     n, seed = 200, 33
     kw = dict(max_steps=25, seed=seed, normalize_obs=False, **NOISE)
-    S, P = track_oracle("circle4", n, model, False, **kw), track_oracle("circle4", n, None, False, **kw)
+    S, P = sens_track_oracle("circle4", n, model, False, **kw), sens_track_oracle("circle4", n, None, False, **kw)
     assert (S.sens_cfg.lat_on, S.sens_cfg.bias_on) == ((1, 0) if which == "latency-alone" else (0, 1))
     dl, _ = drive(S, P, sens(**model), 100, np.random.default_rng(6), actions_mixed, False, seed, stagger=which == "latency-alone")
     assert dl.ends > n
@@ -341,7 +219,7 @@ def test_draws_follow_the_header(offset, step0):
     model = sens(latency=(1, 8), bias=AMPS)
     seen = set()
     for max_steps, T in ((0, 3), (1 << 20, 3)):
-        ora = ACTF.free_body(n, None, seed=seed, max_steps=max_steps, env_id_offset=offset)
+        ora = free_body(n, None, seed=seed, max_steps=max_steps, env_id_offset=offset)
         ora.enable_sensor(model)
         steps = np.array([step0 + (i % 7) - 3 for i in range(n)], np.uint64)
         ora.envs["step_count"] = steps
@@ -374,9 +252,9 @@ def test_without_resample_written_values_survive_and_are_always_applied():
     the written history being a constant 1000 no observation reaches -- no row older than the episode is ever delivered."""
     n, T, seed = 256, 60, 12
     kw = dict(max_steps=7, seed=seed, normalize_obs=False, **NOISE)
-    S, P = track_oracle("circle4", n, dict(SENSOR, resample=False), False, **kw), track_oracle("circle4", n, None, False, **kw)
+    S, P = sens_track_oracle("circle4", n, dict(SENSOR, resample=False), False, **kw), sens_track_oracle("circle4", n, None, False, **kw)
     assert (S.sens_cfg.lat_on, S.sens_cfg.bias_on) == (1, 1)
-    zero = track_oracle("circle4", n, dict(latency=(0, 0), bias=0.0, resample=False), False, **kw)
+    zero = sens_track_oracle("circle4", n, dict(latency=(0, 0), bias=0.0, resample=False), False, **kw)
     assert (zero.sens_cfg.lat_on, zero.sens_cfg.bias_on) == (1, 1)       # the values are the caller's: applied whatever the ranges say
     o0 = P.reset()
     assert np.array_equal(bits(S.reset()), bits(o0 + np.float32(0.0)))   # d = 0, b = 0 after the first enable
@@ -411,12 +289,12 @@ def test_without_resample_written_values_survive_and_are_always_applied():
 def test_a_second_enable_keeps_the_values_and_a_late_enable_waits_for_the_next_episode():
     n, seed = 200, 5
     kw = dict(max_steps=30, seed=seed, normalize_obs=False, **NOISE)
-    S, P = track_oracle("circle4", n, None, False, **kw), track_oracle("circle4", n, None, False, **kw)
+    S, P = sens_track_oracle("circle4", n, None, False, **kw), sens_track_oracle("circle4", n, None, False, **kw)
     S.reset(), P.reset()
     rng = np.random.default_rng(3)
     for t in range(12):
         a = actions_mixed(rng, n)
-        ACTF.same_step(S.step(a), P.step(a), t)
+        same_step(S.step(a), P.step(a), t)
     S.enable_sensor(sens(**SENSOR))                                       # late: d = 0, b = 0 until each drone's next episode start
     started = np.zeros(n, bool)
     for t in range(40):
@@ -443,11 +321,11 @@ def test_a_second_enable_keeps_the_values_and_a_late_enable_waits_for_the_next_e
 def test_coverage_of_the_instantiation_cells(dt, norm, noise, mode):
     n, T, K = INST["n"], INST["T"], (1 if mode == "step" else INST["K"])
     assert n % 64 != 0                                                   # a partial last tile
-    ora = inst_oracle(dt, norm, noise)
+    ora = sens_inst_oracle(dt, norm, noise)
     assert (ora.act_cfg is None) == (ora.dw_cfg is None) == (not norm)   # the raw cells fly the sensor alone
     ora.reset()
     rng = np.random.default_rng(INST["rng"])
-    ACTF.stagger(ora, rng)
+    stagger(ora, rng)
     cov = Coverage(n)
     run_oracle(ora, (np.stack([actions_mixed(rng, n) for _ in range(K)]) for _ in range(T // K)), cov)
     assert cov.n_done > n and cov.seen == set(range(9)) and cov.young > 0 and cov.delayed > 0 and cov.crossed > n, vars(cov)
@@ -456,16 +334,16 @@ def test_coverage_of_the_instantiation_cells(dt, norm, noise, mode):
         assert cov.after_restart > 0, vars(cov)
 
 
-@pytest.mark.parametrize("cell", range(len(OPTION_CELLS)), ids=OPTION_IDS)
+@pytest.mark.parametrize("cell", range(len(SENS_OPTION_CELLS)), ids=SENS_OPTION_IDS)
 def test_coverage_of_the_option_cells(cell):
-    n, T = OPT["n"], OPT["T"]
-    physics, act_name, normalized, extra, feat = OPTION_CELLS[cell]
+    n, T = SENS_OPT["n"], SENS_OPT["T"]
+    physics, act_name, normalized, extra, feat = SENS_OPTION_CELLS[cell]
     ora = option_oracle(cell, n)
     assert (ora.act_cfg is None) == (feat == "sensor") and (ora.dw_cfg is None) == (feat != "both")
     ora.reset()
-    rng = np.random.default_rng(OPT["rng"])
+    rng = np.random.default_rng(SENS_OPT["rng"])
     cov = Coverage(n)
-    run_oracle(ora, ([ACTF.option_actions(rng, n, act_name, normalized)] for _ in range(T)), cov)
+    run_oracle(ora, ([option_actions(rng, n, act_name, normalized)] for _ in range(T)), cov)
     assert cov.n_done >= n and cov.seen == set(range(9)) and cov.young > 0 and cov.delayed > 0, vars(cov)
     if extra.get("random_spawn"):
         assert cov.moved_spawn > n // 2, vars(cov)                        # reset rows whose columns 0-2 are not cfg.spawn's
@@ -475,17 +353,17 @@ def test_coverage_of_the_option_cells(cell):
 
 @pytest.mark.parametrize("where", list(FREE_WHERE))
 def test_coverage_of_the_free_running_launches(where):
-    n, K = FREE["n"], FREE["K"]
+    n, K = SENS_FREE["n"], SENS_FREE["K"]
     off, sc0 = FREE_WHERE[where]
-    ora = track_oracle("race", n, SENSOR, True, max_steps=FREE["max_steps"], normalize_obs=False, seed=FREE["seed"], env_id_offset=off)
+    ora = sens_track_oracle("race", n, SENSOR, True, max_steps=SENS_FREE["max_steps"], normalize_obs=False, seed=SENS_FREE["seed"], env_id_offset=off)
     ora.envs["step_count"] = sc0
     ora.reset()
-    rng = np.random.default_rng(FREE["rng"])
-    ACTF.stagger(ora, rng)
+    rng = np.random.default_rng(SENS_FREE["rng"])
+    stagger(ora, rng)
     cov = Coverage(n)
-    run_oracle(ora, (np.stack([rng.uniform(-1, 1, (n, 4)).astype(np.float32) for _ in range(K)]) for _ in range(FREE["launches"])), cov)
+    run_oracle(ora, (np.stack([rng.uniform(-1, 1, (n, 4)).astype(np.float32) for _ in range(K)]) for _ in range(SENS_FREE["launches"])), cov)
     assert cov.n_done > 2 * n and cov.after_restart > n and cov.crossed > 0 and cov.seen == set(range(9)) and cov.young > 0, vars(cov)
-    assert int(ora.envs["step_count"][0]) == sc0 + K * FREE["launches"] and K // 16 == 4       # the 16-slot ring wraps four times a launch
+    assert int(ora.envs["step_count"][0]) == sc0 + K * SENS_FREE["launches"] and K // 16 == 4       # the 16-slot ring wraps four times a launch
 
 
 @pytest.mark.parametrize("n", SHAPES + LAUNCH_SHAPES)
@@ -510,15 +388,15 @@ def test_coverage_of_the_tile_shapes(n):
 
 
 def test_coverage_of_the_set_values_and_the_late_enable():
-    n = SETV["n"]
+    n = SENS_SETV["n"]
     ora = setv_oracle()
     ora.reset()
-    rng = np.random.default_rng(SETV["rng"])
+    rng = np.random.default_rng(SENS_SETV["rng"])
     ora.envs["steps"], vals = setv_start(rng, n)
     for k, v in vals.items():
         ora.sens[k] = v
     cov = Coverage(n)
-    run_oracle(ora, (np.stack([actions_mixed(rng, n) for _ in range(SETV["K"])]) for _ in range(SETV["launches"])), cov)
+    run_oracle(ora, (np.stack([actions_mixed(rng, n) for _ in range(SENS_SETV["K"])]) for _ in range(SENS_SETV["launches"])), cov)
     assert cov.n_done > 4 * n and cov.crossed > 0 and cov.after_restart > 0 and cov.young > 0 and cov.seen == set(range(9)), vars(cov)
     assert np.array_equal(ora.sens["latency"], vals["latency"]) and n % 64 != 0
     n = REENABLE["n"]
