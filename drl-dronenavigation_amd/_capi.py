@@ -89,6 +89,10 @@ class DnPrivilegedConfig(C.Structure):
     _fields_ = [("groups", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DnGoalConfig(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every entry point declared in include/dronenav.h: name -> (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 PROTOTYPES = {
@@ -147,6 +151,9 @@ PROTOTYPES = {
     "dn_enable_privileged": (_I32, [_VP, C.POINTER(DnPrivilegedConfig)]),
     "dn_get_privileged_config": (_I32, [_VP, C.POINTER(DnPrivilegedConfig)]),
     "dn_bind_privileged": (_I32, [_VP, _VP, _VP, _I64]),
+    "dn_enable_goal": (_I32, [_VP, C.POINTER(DnGoalConfig)]),
+    "dn_get_goal_config": (_I32, [_VP, C.POINTER(DnGoalConfig)]),
+    "dn_bind_goal": (_I32, [_VP, _VP, _VP, _I64]),
 }
 
 _lib = None

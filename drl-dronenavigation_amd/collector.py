@@ -109,6 +109,14 @@ def _refuse_privileged(env, who):
                          "use RolloutCollector(..., value_input='privileged') with a torch value_fn")
 
 
+def _refuse_goal(env, who):
+    """The fused collectors feed the policy kernels the 13 observation columns from the step kernel's own output; the goal rows are
+    written by another kernel family, which carries no sampling-fused entry point."""
+    if getattr(env, "goal", None) is not None:
+        raise ValueError(f"{who} does not carry goal observations (its policy kernels read the 13-column observation); "
+                         "use RolloutCollector(..., policy_input='observation+goal') with a torch policy")
+
+
 class RolloutCollector:
     """n_steps x (policy -> dn_step) on one GPU's shard, then GAE (+ optional all-gather).
 
@@ -128,11 +136,17 @@ class RolloutCollector:
     required): the critic sees the env's privileged rows [N, 52] instead of the observation -- `values[t]` is value_fn of the rows that
     go with `obs[t]`, the truncation bootstrap is value_fn of the TERMINAL privileged rows (the true terminal state with the finished
     episode's parameters, where the terminal observation is the delayed and biased one), `last_values` is value_fn of the last rows,
-    and the buffer dict gains `privileged` [n_steps, N, 52].  The policy's own value output is ignored."""
+    and the buffer dict gains `privileged` [n_steps, N, 52].  The policy's own value output is ignored.
+
+    `policy_input="observation+goal"` (the env needs goal=GoalObservation(...)): the policy -- and the value function, unless
+    `value_input="privileged"` -- sees cat(obs, goal), [N, obs_dim + 8]; the truncation bootstrap is evaluated on
+    cat(terminal_obs, terminal_goal), and the buffer dict gains `goal` [n_steps, N, 8] (`obs` stays the observation alone)."""
 
     def __init__(self, env, policy, n_steps, *, value_fn=None, gamma=0.99, gae_lambda=0.95, bootstrap_truncated=True,
-                 gather=False, group=None, use_graph=False, value_input="observation"):
+                 gather=False, group=None, use_graph=False, value_input="observation", policy_input="observation"):
         from .vec_env import ACT_DIM, DroneVecEnv
+        if policy_input not in ("observation", "observation+goal"):       # a misspelt mode is wrong whatever the env
+            raise ValueError(f"policy_input must be 'observation' or 'observation+goal', got {policy_input!r}")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("RolloutCollector drives a DroneVecEnv (HIP); there is no CPU path")
         if value_input not in ("observation", "privileged"):
@@ -143,6 +157,9 @@ class RolloutCollector:
                 raise ValueError("value_input='privileged' needs an env built with privileged=PrivilegedObservation(...)")
             if value_fn is None:
                 raise ValueError("value_input='privileged' needs value_fn: the policy's own value head sees the observation")
+        self.policy_goal = policy_input == "observation+goal"
+        if self.policy_goal and env.goal is None:
+            raise ValueError("policy_input='observation+goal' needs an env built with goal=GoalObservation(...)")
         self.env, self.policy, self.value_fn = env, policy, value_fn
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
         self.bootstrap_truncated, self.gather, self.group = bool(bootstrap_truncated), bool(gather), group
@@ -166,6 +183,9 @@ class RolloutCollector:
         if self.value_privileged:
             self.buf["privileged"] = torch.empty((T, n, env.privileged.shape[1]), dtype=f32, device=dev)
             self._last_priv = env.privileged.clone()
+        if self.policy_goal:
+            self.buf["goal"] = torch.empty((T, n, env.goal.shape[1]), dtype=f32, device=dev)
+            self._last_goal = env.goal.clone()
         self._last_done = torch.ones(n, dtype=torch.uint8, device=dev)       # SB3: _last_episode_starts = True
         self.num_timesteps = 0
         self._graph = None
@@ -185,8 +205,15 @@ class RolloutCollector:
         env, b = self.env, self.buf
         obs, done = self._last_obs, self._last_done
         priv = self._last_priv if self.value_privileged else None
+        goal = self._last_goal if self.policy_goal else None
+
+        def seen(o, g):         # what the policy (and the value function on observations) is shown
+            return o if goal is None else torch.cat((o, g), dim=1)
+
         for t in range(self.n_steps):
-            actions, values, log_probs = self.policy(obs)
+            actions, values, log_probs = self.policy(seen(obs, goal))
+            if goal is not None:
+                b["goal"][t].copy_(goal)
             if priv is not None:
                 b["privileged"][t].copy_(priv)
                 values = self._values(priv)
@@ -203,15 +230,17 @@ class RolloutCollector:
                     tv = self._values(torch.where(next_done.bool()[:, None], info["terminal_privileged"], info["privileged"]),
                                       row_mask=info["truncated"])
                 else:
-                    tv = self._values(torch.where(next_done.bool()[:, None], info["terminal_obs"], next_obs),
-                                      row_mask=info["truncated"])
+                    tv = self._values(torch.where(next_done.bool()[:, None], seen(info["terminal_obs"], info.get("terminal_goal")),
+                                                  seen(next_obs, info.get("goal"))), row_mask=info["truncated"])
                 reward = reward + self.gamma * tv * info["truncated"].to(reward.dtype)
             b["rewards"][t].copy_(reward)
             obs.copy_(next_obs)
             done.copy_(next_done)
             if priv is not None:
                 priv.copy_(info["privileged"])
-        b["last_values"].copy_(self._values(obs if priv is None else priv))
+            if goal is not None:
+                goal.copy_(info["goal"])
+        b["last_values"].copy_(self._values(seen(obs, goal) if priv is None else priv))
         b["last_dones"].copy_(done)
         dev = env.device
         _capi.check(_capi.load().dn_gae(
@@ -357,6 +386,7 @@ class OffPolicyCollector:
         from .policy_mfma import FusedSacActor
         from .vec_env import ACT_DIM, DroneVecEnv
         _refuse_privileged(env, "OffPolicyCollector")
+        _refuse_goal(env, "OffPolicyCollector")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("OffPolicyCollector drives a DroneVecEnv (HIP); there is no CPU path")
         self.env, self.actor = env, actor
@@ -473,6 +503,7 @@ class FusedRolloutCollector:
         from .policy_mfma import FusedMlpPolicy
         from .vec_env import ACT_DIM, OBS_DIM, DroneVecEnv
         _refuse_privileged(env, "FusedRolloutCollector")
+        _refuse_goal(env, "FusedRolloutCollector")
         if not isinstance(env, DroneVecEnv) or not isinstance(policy, FusedMlpPolicy):
             raise TypeError("FusedRolloutCollector needs a DroneVecEnv and a FusedMlpPolicy (HIP); there is no CPU path")
         if env.num_envs % 4 or env.obs_dim != OBS_DIM:

@@ -100,6 +100,7 @@ struct dn_env {
     dn_actuator_config act_cfg = {};
     dn_sensor_config sens_cfg = {};
     dn_privileged_config priv_cfg = {};
+    dn_goal_config goal_cfg = {};
 };
 
 thread_local hipEvent_t dn_tl_ev_start = nullptr, dn_tl_ev_stop = nullptr;
@@ -326,6 +327,8 @@ const ModelRow MODELS[] = {
     // the rows are the caller's memory: nothing to free
     {[](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.priv.groups != 0; }, "the privileged observations",
      "dn_enable_privileged", "writes no privileged rows"},
+    {[](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.goal.on != 0; }, "the goal observations", "dn_enable_goal",
+     "writes no goal rows"},
 };
 
 // DN_OK, or the refusal of entry point `who`, whose kernels carry no model, for the first model that is on.  `instead` names the calls
@@ -838,6 +841,9 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
     if (env->m.priv.groups && env->m.priv.rows && k > env->m.priv.cap)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_many: k = %lld exceeds the %lld steps the privileged rows hold (dn_bind_privileged capacity_steps)",
                     (long long)k, env->m.priv.cap);
+    if (env->m.goal.on && env->m.goal.rows && k > env->m.goal.cap)
+        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_many: k = %lld exceeds the %lld steps the goal rows hold (dn_bind_goal capacity_steps)",
+                    (long long)k, env->m.goal.cap);
     // one fused launch: the state stays in registers for all k steps (dn_step_many_kernel)
     const DnStepIO io = make_io(actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask);
     DN_REFUSE_ARMED_CAPTURE(stream);
@@ -1352,6 +1358,52 @@ int32_t dn_bind_privileged(dn_env *env, float *rows, float *terminal_rows, int64
     pv.rows = rows;
     pv.term = terminal_rows;
     pv.cap = capacity_steps;
+    return DN_OK;
+}
+
+int32_t dn_enable_goal(dn_env *env, const dn_goal_config *cfg)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    // the frame first: it needs no env (and no device) to be wrong
+    if (cfg->frame != DN_GOAL_FRAME_WORLD && cfg->frame != DN_GOAL_FRAME_BODY)
+        return fail(DN_ERR_INVALID_ARGUMENT, "goal frame = %d: need DN_GOAL_FRAME_WORLD (0) or DN_GOAL_FRAME_BODY (1)", cfg->frame);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    if (env->m.goal.on) {                           // launches in flight carry the previous frame
+        DN_HIP(hipSetDevice(env->cfg.device_id));
+        DN_HIP(hipDeviceSynchronize());
+    }
+    env->m.goal.on = 1;
+    env->m.goal.frame = cfg->frame;
+    env->goal_cfg = *cfg;
+    env->waves_fused = env->waves_single = 1;       // the rows are written by the one-wave option kernels only
+    return DN_OK;
+}
+
+int32_t dn_get_goal_config(const dn_env *env, dn_goal_config *out)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    if (!env->m.goal.on) return 0;
+    *out = env->goal_cfg;
+    return 1;
+}
+
+int32_t dn_bind_goal(dn_env *env, float *rows, float *terminal_rows, int64_t capacity_steps)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    DnGoal &g = env->m.goal;
+    if (!g.on) return fail(DN_ERR_BAD_STATE, "the goal observations are not enabled (dn_enable_goal)");
+    if (!rows) {
+        if (terminal_rows) return fail(DN_ERR_INVALID_ARGUMENT, "terminal_rows without rows: rows = NULL unbinds both");
+        g.rows = g.term = nullptr;
+        g.cap = 0;
+        return DN_OK;
+    }
+    if (((uintptr_t)rows & 15u) || ((uintptr_t)terminal_rows & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "rows and terminal_rows must be 16-byte aligned");
+    if (capacity_steps < 1) return fail(DN_ERR_INVALID_ARGUMENT, "capacity_steps must be >= 1 (got %lld)", (long long)capacity_steps);
+    g.rows = rows;
+    g.term = terminal_rows;
+    g.cap = capacity_steps;
     return DN_OK;
 }
 

@@ -188,15 +188,27 @@ struct DnPriv {
     int pad_;
 };
 
+// Goal observations (dn_enable_goal): the vector to the current target waypoint and the segment after it, one row of DN_GOAL_DIM float32
+// per drone and step, written by the step kernels of the deepest family (dn_step_many_1w_kernel<..., PRIV = true, GOAL = true>, argument
+// GoalArg = PrivArg + DnGoal) and by the reset kernel.  It owns no memory: the rows are the caller's (dn_bind_goal).
+struct DnGoal {
+    float *rows;            // [cap][N][DN_GOAL_DIM] step rows, step-major; nullptr = unbound (nothing is written)
+    float *term;            // the terminal rows, same shape, or nullptr
+    long long cap;          // steps the two buffers hold (host side: dn_step_many checks k against it)
+    int frame;              // DN_GOAL_FRAME_WORLD / DN_GOAL_FRAME_BODY: launch-uniform
+    int on;                 // 0 = the feature is not enabled
+};
+
 // The per-drone models as the host carries them (dn_env, the launchers).  The kernels take them as before: the reset kernel as one argument
-// each, the option step kernels as the slice of the chain PrivArg : SensArg : ActArg : WindArg : DnDyn (dn_kernels.hip) their family reads.
-// A model that is off is its value-initialised struct (null pointers, groups 0).
+// each, the option step kernels as the slice of the chain GoalArg : PrivArg : SensArg : ActArg : WindArg : DnDyn (dn_kernels.hip) their
+// family reads.  A model that is off is its value-initialised struct (null pointers, groups 0, on 0).
 struct DnModels {
     DnDyn dyn;
     DnWind wind;
     DnAct act;
     DnSens sens;
     DnPriv priv;
+    DnGoal goal;
 };
 
 // dn_set_launch_events (ABI 8): the step kernel of the next dn_step / dn_step_many launch is dispatched with these two hipEvents attached to
@@ -212,7 +224,7 @@ extern thread_local hipEvent_t dn_tl_ev_start, dn_tl_ev_stop;
 
 int dn_norm_exact_compiled_in();      // 1 in libdronenav_exact.so (-DDN_NORM_EXACT=1: the normaliser's float64 output stage), else 0
 // m: the per-drone models of the env.  With one of them on, the launch takes the one-wave option kernel of the deepest enabled family
-// (dynamics < wind < actuator < sensor < privileged rows, bound; the shallower ones ride along, on or off), whatever `waves` says.
+// (dynamics < wind < actuator < sensor < privileged rows, bound < goal rows, bound; the shallower ones ride along, on or off), whatever `waves` says.
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnModels *m = nullptr);
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);   // dn_kernels_mw.hip
 hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnModels *m = nullptr);

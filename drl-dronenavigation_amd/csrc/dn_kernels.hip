@@ -1649,6 +1649,68 @@ DN_DEV void priv_store_bias(const DnPriv &pv, float *row, const DnSens &sn, cons
     *priv_quad(row, 12) = make_float4(d.x, 0.0f, 0.0f, 0.0f);
 }
 
+// ---- goal observations (dn_enable_goal) ----------------------------------------------------------------------------------------
+// One row is two 16-byte quads (include/dronenav.h): the vector to target waypoint `idx` from the position the DELIVERED row y shows, and
+// the segment after it, both over max_target_dist, world frame or rotated into the body frame of y's own Euler columns.  A pure function of
+// (y, idx, the LDS table): computed where y is in registers and stored at once, nothing is carried from step to step.  g.frame is
+// launch-uniform.  The arithmetic is written operation by operation (no contraction licence in this build), so every kernel shape and the
+// reset kernel produce the same bits.
+template <typename R>
+DN_DEV void goal_to_body(R v[3], const R sr, const R cr, const R sp, const R cp, const R sy, const R cy)
+{
+    const R x1 = cy * v[0] + sy * v[1], y1 = cy * v[1] - sy * v[0];
+    const R x2 = cp * x1 - sp * v[2], z2 = sp * x1 + cp * v[2];
+    v[0] = x2; v[1] = cr * y1 + sr * z2; v[2] = cr * z2 - sr * y1;
+}
+template <typename R>
+DN_DEV void goal_store(const DnGoal &g, const DnParams &p, const DnConsts<R> &c, const R *s_tab, float *row, const float y[DN_OBS_DIM], const int idx)
+{
+    const bool more = idx + 1 < p.num_waypoints;
+    const R *w = s_tab + idx * DN_T_STRIDE + DN_T_WP;
+    const R *w1 = s_tab + (more ? idx + 1 : idx) * DN_T_STRIDE + DN_T_WP;      // per-lane LDS reads; never past the last entry
+    R e[3], s[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const R p_hat = (R)y[j] * c.dim[3 + j];
+        e[j] = (w[j] - p_hat) * c.inv_max_target_dist;
+        s[j] = more ? (w1[j] - w[j]) * c.inv_max_target_dist : R(0.0);
+    }
+    if (g.frame == DN_GOAL_FRAME_BODY) {
+        // v_body = Rx(roll)^T Ry(pitch)^T Rz(yaw)^T v, one axis after the other
+        const float pi32 = (float)K<R>::PI;
+        const float roll = pi32 * y[3], pitch = pi32 * y[4], yaw = pi32 * y[5];
+        const R sr = (R)sinf(roll), cr = (R)cosf(roll), sp = (R)sinf(pitch), cp = (R)cosf(pitch), sy = (R)sinf(yaw), cy = (R)cosf(yaw);
+        goal_to_body<R>(e, sr, cr, sp, cp, sy, cy);
+        goal_to_body<R>(s, sr, cr, sp, cp, sy, cy);
+    }
+    float4 *q = reinterpret_cast<float4 *>(row);
+    q[0] = make_float4((float)e[0], (float)e[1], (float)e[2], (float)idx);
+    q[1] = make_float4((float)s[0], (float)s[1], (float)s[2], more ? 1.0f : 0.0f);
+}
+// What a step kernel hands observe_phase / report_obs for the step at hand (rebuilt every step from the step index: no register of the
+// feature lives across a step): the two rows of this drone and step (trow null where unbound), the index the step leaves (0 where the
+// episode restarted), the index the terminal row takes, and whether the episode ended.
+template <typename R> struct GoalCtx {
+    const DnGoal *g;
+    const R *tab;
+    float *row, *trow;
+    int idx, tidx;
+    bool done, active;
+};
+// (exists in the GOAL kernels only: an empty struct elsewhere, so that every other kernel keeps its instruction stream -- see PrivRegs)
+template <typename R, bool ON> struct GoalRegs {
+    GoalCtx<R> x;
+};
+template <typename R> struct GoalRegs<R, false> {};
+// observe_phase, on the row as sens_deliver left it: the step row where the episode goes on, the terminal row where it ended (one store
+// site for both: a per-lane pointer and index)
+template <typename R>
+DN_DEV void goal_observe(const GoalCtx<R> &x, const DnParams &p, const DnConsts<R> &c, const float y[DN_OBS_DIM])
+{
+    float *const dst = x.done ? x.trow : x.row;
+    if (x.active && dst) goal_store<R>(*x.g, p, c, x.tab, dst, y, x.done ? x.tidx : x.idx);
+}
+
 // DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
 // WIND (with DYN): the wind force *wf over the mass of *dk joins the extra accelerations
 template <typename R, typename TH = Thrust, bool XOPT = false, bool DYN = false, bool WIND = false>
@@ -1877,11 +1939,12 @@ template <typename R, bool SPAWN = false>
 DN_DEV Verdict<R> rules_phase(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const GateRow<R> &row_e, const R (&wp0)[3],
                               const Flight<R> &fl, const float4 G0e, const float4 G3e, float4 *g6_blk, const unsigned li,
                               const bool active, float4 &G0, float4 &G1, float4 &G2, float4 &G3,
-                              const unsigned long long gid = 0ull, const unsigned long long step = 0ull)
+                              const unsigned long long gid = 0ull, const unsigned long long step = 0ull, int *idx_v = nullptr)
 {
     RulesMid<R> m;
     const Verdict<R> v = rules_verdict<R>(p, c, s_tab, row_e, fl, G3e, m);
     rules_commit<R, SPAWN>(c, wp0, fl, m, G0e, G3e, g6_blk, li, active, G0, G1, G2, G3, &p, gid, step);
+    if (idx_v) *idx_v = m.idx;      // the GOAL kernels: the index the verdict leaves, before the auto-reset zeroes the committed one
     return v;
 }
 
@@ -2073,10 +2136,11 @@ DN_DEV void reward_candidates(const DnParams &p, const DnConsts<R> &c, const R *
 }
 // SENS (the one-wave kernels with dn_enable_sensor): *sx is the kernel's own register copy; the delivered row replaces the true one
 // PRIV (with SENS, dn_enable_privileged): the true row leaves for the privileged rows from the registers that hold it, before the noise
-template <typename R, bool NORM, bool NOISE, bool SENS = false, bool PRIV = false>
+// GOAL (with PRIV, dn_enable_goal): the goal row is computed from the delivered row, before the normaliser
+template <typename R, bool NORM, bool NOISE, bool SENS = false, bool PRIV = false, bool GOAL = false>
 DN_DEV Observed<R> observe_phase(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const Flight<R> &fl,
                                  const float4 G4, const float4 G5, const unsigned long long gid, const unsigned long long step_count,
-                                 Rms &rms, SensCtx *sx = nullptr, const PrivCtx *px = nullptr)
+                                 Rms &rms, SensCtx *sx = nullptr, const PrivCtx *px = nullptr, const GoalCtx<R> *gx = nullptr)
 {
     Observed<R> ob;
     observe_columns<R>(p, c, fl, ob.o);
@@ -2085,6 +2149,7 @@ DN_DEV Observed<R> observe_phase(const DnParams &p, const DnConsts<R> &c, const 
     // sensor noise / per-drone normaliser act on the step observation (which is also terminal_observation)
     if (NOISE && p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, step_count, 1u, ob.o);
     if constexpr (SENS) sens_deliver(*sx, step_count, ob.o);
+    if constexpr (GOAL) goal_observe<R>(*gx, p, c, ob.o);
     if (NORM) normalize_obs(rms, ob.o);
     return ob;
 }
@@ -2262,11 +2327,11 @@ DN_DEV void report_scalars(const DnParams &p, const DnConsts<R> &c, const StepOu
     }
     if (out.done_word && lane == 0) *out.done_word = done_ballot;
 }
-template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false, bool SENS = false, bool PRIV = false>
+template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false, bool SENS = false, bool PRIV = false, bool GOAL = false>
 DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const bool truncated,
                        const Verdict<R> &v, float *o, const unsigned long long gid, const unsigned long long step_count,
                        const unsigned li, const unsigned lane, const unsigned rows, const bool active, Rms &rms, SensCtx *sx = nullptr,
-                       const PrivCtx *px = nullptr)
+                       const PrivCtx *px = nullptr, const GoalCtx<R> *gx = nullptr)
 {
     const bool done = v.terminated != 0 || truncated;
     const unsigned long long done_mask = __ballot(done && active);
@@ -2295,6 +2360,9 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
                 if (sx->sn->lat_on || sx->sn->bias_on)      // launch-uniform: both off = the existing path
                     sens_restart(*sx->sn, sx->n, sx->i, sx->active, p.seed, gid, step_count, sens_slot(*sx->sn, step_count), sx->d, o);
             }
+            if constexpr (GOAL) {                                         // the new episode's delivered reset row, against waypoint 0
+                if (active) goal_store<R>(*gx->g, p, c, gx->tab, gx->row, o, 0);
+            }
             if (NORM) normalize_obs(rms, o);
         }
     }
@@ -2302,15 +2370,16 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
     else if (TILE == 1) tile_park(s_tile, lane, o);        // streamed out by the caller one step later
     else store_obs_tile(s_tile, out.obs, rows, lane, o);
 }
-template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false, bool SENS = false, bool PRIV = false>
+template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false, bool SENS = false, bool PRIV = false, bool GOAL = false>
 DN_DEV void report_phase(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const Flight<R> &fl,
                          const Verdict<R> &v, Observed<R> &ob, const unsigned long long gid, const unsigned long long step_count,
                          const unsigned li, const unsigned lane, const unsigned rows, const bool active,
-                         float4 &G4, float4 &G5, StatAcc &acc, Rms &rms, RewNorm &rn, SensCtx *sx = nullptr, const PrivCtx *px = nullptr)
+                         float4 &G4, float4 &G5, StatAcc &acc, Rms &rms, RewNorm &rn, SensCtx *sx = nullptr, const PrivCtx *px = nullptr,
+                         const GoalCtx<R> *gx = nullptr)
 {
     report_scalars<R, REW>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn);
-    report_obs<R, NORM, NOISE, TILE, SPAWN, SENS, PRIV>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active, rms,
-                                                        sx, px);
+    report_obs<R, NORM, NOISE, TILE, SPAWN, SENS, PRIV, GOAL>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active,
+                                                              rms, sx, px, gx);
 }
 
 struct BlockState {
@@ -2431,16 +2500,23 @@ struct SensArg : ActArg {
 struct PrivArg : SensArg {
     DnPriv pv;
 };
-template <bool DYN, bool WIND, bool ACT = false, bool SENS = false, bool PRIV = false> struct StepArg { using type = DynArg<DYN>; };
-template <> struct StepArg<true, true, false, false, false> { using type = WindArg; };
-template <> struct StepArg<true, true, true, false, false> { using type = ActArg; };
-template <> struct StepArg<true, true, true, true, false> { using type = SensArg; };
-template <> struct StepArg<true, true, true, true, true> { using type = PrivArg; };
+// GOAL (with PRIV, SENS, ACT, WIND, DYN and XOPT): the argument carries dn_bind_goal's rows as well (GoalArg); the privileged rows are off
+// (groups 0, null pointers) unless they are enabled and bound too.
+struct GoalArg : PrivArg {
+    DnGoal gl;
+};
+template <bool DYN, bool WIND, bool ACT = false, bool SENS = false, bool PRIV = false, bool GOAL = false> struct StepArg { using type = DynArg<DYN>; };
+template <> struct StepArg<true, true, false, false, false, false> { using type = WindArg; };
+template <> struct StepArg<true, true, true, false, false, false> { using type = ActArg; };
+template <> struct StepArg<true, true, true, true, false, false> { using type = SensArg; };
+template <> struct StepArg<true, true, true, true, true, false> { using type = PrivArg; };
+template <> struct StepArg<true, true, true, true, true, true> { using type = GoalArg; };
 template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false, bool ACT = false,
-          bool SENS = false, bool PRIV = false>
+          bool SENS = false, bool PRIV = false, bool GOAL = false>
 __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg,
-                                                                   const typename StepArg<DYN, WIND, ACT, SENS, PRIV>::type dy)
+                                                                   const typename StepArg<DYN, WIND, ACT, SENS, PRIV, GOAL>::type dy)
 {
+    static_assert(!GOAL || PRIV, "the goal rows ride on the option kernels with the privileged rows");
     static_assert(!ACT || (WIND && DYN && XOPT && !SAMPLE), "the actuator rides on the option kernels with the body terms and the wind");
     static_assert(!SENS || ACT, "the sensor model rides on the option kernels with the actuator");
     static_assert(!PRIV || SENS, "the privileged rows ride on the option kernels with the sensor model");
@@ -2520,6 +2596,10 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         pr.x = {&dy.pv, dy.pv.rows + i * DN_PRIV_DIM, dy.pv.term ? dy.pv.term + i * DN_PRIV_DIM : nullptr, false, active};
         px = &pr.x;
     }
+    // dn_enable_goal: filled anew in every step (GoalRegs<R, false> is empty, as PrivRegs<false> is and for the same reason)
+    GoalRegs<R, GOAL> gr;
+    const GoalCtx<R> *gx = nullptr;
+    if constexpr (GOAL) gx = &gr.x;
     const R wp0[3] = {s_tab[DN_T_WP], s_tab[DN_T_WP + 1], s_tab[DN_T_WP + 2]};   // waypoint 0: every reset measures against it
     StatAcc acc;
     Rms rms;
@@ -2550,8 +2630,18 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         Flight<R> fl = fly<R, NOISE, XOPT, DYN, WIND, ACT>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr,
                                                            DYN ? &dk : nullptr, WIND ? &wf : nullptr, &lag, lag_on);
         const float4 G0e = G0, G3e = G3;
-        const Verdict<R> v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc);
+        int *idx_v = nullptr;
+        if constexpr (GOAL) idx_v = &gr.x.tidx;
+        const Verdict<R> v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc, idx_v);
         if (XOPT && p.drag) G7 = (v.terminated || fl.truncated) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : rpm_now;   // BaseAviary.py:442,545
+        if constexpr (GOAL) {
+            // this step's rows; the step row takes the committed index (0 where the episode restarted), the terminal row the verdict's,
+            // held to the last waypoint (a completed track leaves W)
+            const long long at = ((long long)t * n + i) * DN_GOAL_DIM;
+            const int tidx = gr.x.tidx < p.num_waypoints - 1 ? gr.x.tidx : p.num_waypoints - 1;
+            gr.x = {&dy.gl, s_tab, dy.gl.rows + at, dy.gl.term ? dy.gl.term + at : nullptr, unpack_meta(G3.w).idx, tidx,
+                    v.terminated || fl.truncated, active};
+        }
         if constexpr (PRIV) {
             // the terminal row's parameters are those the step was ENTERED with: stored before the episode starts below redraw them
             pr.x.done = v.terminated || fl.truncated;
@@ -2595,9 +2685,9 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         }
         attitude_phase<R>(fl);
         if constexpr (SENS) sx.k = unpack_meta(G3e.w).steps + 1;    // control steps of the episode flown once this step is over
-        Observed<R> ob = observe_phase<R, NORM, NOISE, SENS, PRIV>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx, px);
-        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, SENS, PRIV>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms,
-                                                                rn, &sx, px);
+        Observed<R> ob = observe_phase<R, NORM, NOISE, SENS, PRIV, GOAL>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx, px, gx);
+        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, SENS, PRIV, GOAL>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc,
+                                                                      rms, rn, &sx, px, gx);
         if constexpr (PRIV) {
             // the step row's parameters: what the getters would return after this step (a restarted drone: the new episode's draws)
             if (active) {
@@ -4179,7 +4269,7 @@ __global__ __launch_bounds__(3 * DN_BLOCK) void dn_step_pqx_kernel(const DnParam
 // =====================================================================================================
 template <typename R>
 __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd, const DnAct ac,
-                                                            const DnSens sn, const DnPriv pv)
+                                                            const DnSens sn, const DnPriv pv, const DnGoal gl)
 {
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -4218,6 +4308,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
         int d = 0;
         sens_restart(sn, p.n, i, active, p.seed, gid, sc, sens_slot(sn, sc - 1ull), d, o);
     }
+    if (gl.rows && active) goal_store<R>(gl, p, c, s_tab, gl.rows + i * DN_GOAL_DIM, o, 0);     // dn_bind_goal: the delivered reset row, slot 0
     if (p.normalize_obs) {
         Rms rms;
         load_rms(p, i, rms);
@@ -4655,14 +4746,14 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 #endif
 #elif DN_TU == 1
 namespace {
-// The one-wave option kernel of one family of per-drone models (dn_enable_*): DYN always, then WIND, ACT, SENS in that order;
-// `arg` is the slice of the SensArg chain the family's kernels take.
-template <bool WIND, bool ACT, bool SENS, bool PRIV = false>
-void launch_models(const StepLaunch &L, const typename StepArg<true, WIND, ACT, SENS, PRIV>::type &arg)
+// The one-wave option kernel of one family of per-drone models (dn_enable_*): DYN always, then WIND, ACT, SENS, PRIV, GOAL in that order;
+// `arg` is the slice of the GoalArg chain the family's kernels take.
+template <bool WIND, bool ACT, bool SENS, bool PRIV = false, bool GOAL = false>
+void launch_models(const StepLaunch &L, const typename StepArg<true, WIND, ACT, SENS, PRIV, GOAL>::type &arg)
 {
     dn_bools([&](auto F32, auto NORM, auto NOISE, auto ONE) {
-        DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, ONE, true, false, true, WIND, ACT, SENS, PRIV>), L.grid, dim3(DN_BLOCK), 0,
-                   L.stream, L.p, L.io, L.k, arg);
+        DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, ONE, true, false, true, WIND, ACT, SENS, PRIV, GOAL>), L.grid,
+                   dim3(DN_BLOCK), 0, L.stream, L.p, L.io, L.k, arg);
     }, L.f32, L.norm, L.noise, L.k == 1);
 }
 }  // namespace
@@ -4671,20 +4762,25 @@ hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, boo
 {
     const StepLaunch L(p, io, k, f32, stream);
     const bool priv = m && m->priv.groups && m->priv.rows;      // enabled AND bound: unbound, nothing is written and the family below serves
-    if (m && (m->dyn.dyn || m->wind.mean || m->act.hist || m->sens.ring || priv)) {
+    const bool goal = m && m->goal.on && m->goal.rows;          // likewise
+    if (m && (m->dyn.dyn || m->wind.mean || m->act.hist || m->sens.ring || priv || goal)) {
         // a model is on: the deepest enabled family's kernel, whatever `waves` says.  A model that is off rides along as its
         // value-initialised struct (null pointers): the nominal body, still air, no latency, no bias.
         if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels carry no model (the C ABI refuses them first)
-        PrivArg sa;
+        GoalArg sa;
         static_cast<DnDyn &>(sa) = m->dyn;
         sa.w = m->wind;
         sa.a = m->act;
         sa.s = m->sens;
         sa.pv = m->priv;
-        if (priv) {
-            if (k > m->priv.cap) return hipErrorInvalidValue;      // the C ABI refuses it first
-            launch_models<true, true, true, true>(L, sa);
-        } else if (m->sens.ring) launch_models<true, true, true>(L, sa);
+        sa.gl = m->goal;
+        if (priv && k > m->priv.cap) return hipErrorInvalidValue;   // the C ABI refuses it first
+        if (goal) {
+            if (k > m->goal.cap) return hipErrorInvalidValue;       // likewise
+            if (!priv) sa.pv = DnPriv{};                            // enabled but unbound: this family writes no privileged rows either
+            launch_models<true, true, true, true, true>(L, sa);
+        } else if (priv) launch_models<true, true, true, true>(L, sa);
+        else if (m->sens.ring) launch_models<true, true, true>(L, sa);
         else if (m->act.hist) launch_models<true, true, false>(L, sa);
         else if (m->wind.mean) launch_models<true, false, false>(L, sa);
         else launch_models<false, false, false>(L, DynArg<true>{static_cast<const DnDyn &>(sa)});
@@ -4708,8 +4804,8 @@ hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t 
 {
     const DnModels on = m ? *m : DnModels{};
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv);
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv, on.goal);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv, on.goal);
     return hipGetLastError();
 }
 

@@ -616,6 +616,51 @@ int32_t dn_get_privileged_config(const dn_env *env, dn_privileged_config *out);
  * captured in a hipGraph bakes the pointers in. */
 int32_t dn_bind_privileged(dn_env *env, float *rows, float *terminal_rows, int64_t capacity_steps);
 
+/* Goal observations: where the drone is supposed to fly, as the policy may see it.  The 13 observation columns carry no direction to the
+ * target; with this feature the step kernels write, per drone and step -- inside a fused launch too --, one row of DN_GOAL_DIM = 8 float32
+ * (two 16-byte quads).  The row is a pure function of
+ *   y   the observation row as delivered to the normaliser: after obs_noise_sigma's noise and after the sensor model's latency and bias,
+ *       before the normaliser (the row `obs` holds when normalize_obs is off),
+ *   i   the target index the row is written with, and
+ *   the waypoints wp[0..W-1], dim_high = (x_high, y_high, z_high) of the aviary box and 1 / max_target_dist (the scale of column 12):
+ *     p_hat = y[0:3] * dim_high                                 the position the policy is shown: noise, latency and bias are in it
+ *     e     = (wp[i] - p_hat) / max_target_dist                 to the current target
+ *     n     = (wp[i+1] - wp[i]) / max_target_dist               the segment after it; (0, 0, 0) where i + 1 == W
+ *     DN_GOAL_FRAME_WORLD:  row = [ e_x e_y e_z float(i) | n_x n_y n_z (i + 1 < W ? 1 : 0) ]
+ *     DN_GOAL_FRAME_BODY:   e and n multiplied by R^T, R = Rz(yaw) Ry(pitch) Rx(roll), (roll, pitch, yaw) = pi * y[3:6]: the
+ *                           convention of the observation's own Euler columns, applied to the DELIVERED columns (float32 sinf / cosf)
+ *   The row is built from the delivered position on purpose: from the true position, wp - e would hand the policy what the sensor model
+ *   hides.  The index is the true one (a lap counter knows which gate is next).
+ *   step row (`rows`): where the episode goes on, i = the waypoint index the step leaves (dn_env_state.idx after it) and y = the
+ *     step's row; where it ended, i = 0 and y = the new episode's reset row -- as `obs` is the reset row there.
+ *   terminal row (`terminal_rows`, optional): written only where done, like terminal_obs; y = the terminal row (terminal_obs before the
+ *     normaliser), i = min(index the episode ended with, W - 1) -- a completed track ends with index W.
+ *   The rows are neither normalised nor clipped, and nothing feeds back: every other output and every byte of state is that of the same
+ *   env without the feature.
+ * The rows are a persistent binding (dn_bind_goal) like the privileged rows: the entry points keep their signatures and a captured
+ * hipGraph keeps writing.  K steps in one launch equal K single steps bit for bit.  dn_reset writes the fresh episodes' rows (i = 0) into
+ * step slot 0.  The rows are written by one more family of the one-wave option kernels, which carries the four models and the privileged
+ * rows (on or off): enabling forces dn_get_kernel_waves(env, 0 / 1) == 1.  dn_step_sampled, dn_step_squashed, dn_mlp_step_sampled and
+ * dn_eval_kinematics refuse an env with the feature enabled (DN_ERR_INVALID_ARGUMENT).
+ * Layout: frame at 0, reserved at 4; 8 bytes. */
+#define DN_GOAL_DIM 8
+#define DN_GOAL_FRAME_WORLD 0
+#define DN_GOAL_FRAME_BODY 1
+typedef struct dn_goal_config {
+    int32_t frame;        /* DN_GOAL_FRAME_WORLD or DN_GOAL_FRAME_BODY */
+    int32_t reserved;     /* must be 0 */
+} dn_goal_config;
+/* Validates the frame and enables the feature; a later call changes the frame and keeps the binding.  Allocates nothing. */
+int32_t dn_enable_goal(dn_env *env, const dn_goal_config *cfg);
+/* 1: enabled, *out = the configuration last given to dn_enable_goal; 0: not enabled (*out untouched); < 0: error. */
+int32_t dn_get_goal_config(const dn_env *env, dn_goal_config *out);
+/* Binds the caller's device buffers, 16-byte aligned: rows float[capacity_steps][N][DN_GOAL_DIM], step-major like every dn_step_many
+ * buffer, and terminal_rows of the same shape or NULL.  dn_step and dn_reset write step slot 0; dn_step_many with k > capacity_steps
+ * fails with DN_ERR_INVALID_ARGUMENT.  rows = NULL unbinds (terminal_rows must be NULL too, capacity_steps is ignored): an env that is
+ * enabled but unbound writes nothing and launches the kernels it would launch without the feature.  DN_ERR_BAD_STATE if the feature is
+ * not enabled.  The buffers must outlive the binding; a launch captured in a hipGraph bakes the pointers in. */
+int32_t dn_bind_goal(dn_env *env, float *rows, float *terminal_rows, int64_t capacity_steps);
+
 #ifdef __cplusplus
 }
 #endif

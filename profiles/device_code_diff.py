@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Is the device code of two builds the same?  For a host-only change (launchers, the C ABI) the answer must be yes.
 
-    python profiles/device_code_diff.py OLD/csrc NEW/csrc
+    python profiles/device_code_diff.py OLD/csrc NEW/csrc [--new-template-arg]
 
 For every object with a gfx950 code object in both directories: extracts the code object (llvm-objdump --offloading), lists its FUNC
 symbols (llvm-readelf -s --wide), disassembles it (llvm-objdump -d), splits the text by symbol and strips the address and encoding
 columns.  Prints the symbol count per object and every symbol that exists on one side only or whose instruction text differs; the
 exit status is 0 when there is none.  Needs no GPU.
+
+--new-template-arg: for a change that gives a kernel template one more trailing bool argument (default false) and adds code objects.
+A kernel that exists on the new side only is compared with the old kernel of the same name less that trailing `false` (its last Lb0E,
+and the last XT<n>_E of a dependent argument type such as StepArg<...>::type), where the old side has one.  Two things that move with the
+code object's layout and the symbol's name, not with the kernel, are masked on both sides: the immediates of the s_add_u32 / s_addc_u32
+pair after an s_getpc_b64 (pc-relative data offsets) and the symbol names inside <...> branch-target annotations.
 """
 import os
 import re
@@ -53,11 +59,41 @@ def functions(obj, work):
     return {s: "\n".join(t) for s, t in text.items()}, listed
 
 
-def main(old, new):
+def less_trailing_false(sym):
+    """sym with the last Lb0E of its first run of bool template arguments dropped (and the last XT<n>_E of a dependent list), or None."""
+    m = re.match(r"^(.*?I[df]?)((?:Lb[01]E)+)(E.*)$", sym)
+    if not m or not m.group(2).endswith("Lb0E"):
+        return None
+    rest = re.sub(r"XT\d+_E(E4typeE)", r"\1", m.group(3), count=1)
+    return m.group(1) + m.group(2)[:-4] + rest
+
+
+def masked(text):
+    out, pc = [], 0
+    for line in text.split("\n"):
+        line = re.sub(r"<[^>]*>", "<L>", line)
+        if "s_getpc_b64" in line:
+            pc = 3
+        elif pc:
+            pc -= 1
+            if line.startswith(("s_add_u32", "s_addc_u32")):
+                line = re.sub(r"0x[0-9a-f]+|\b\d+$", "IMM", line)
+        out.append(line)
+    return "\n".join(out)
+
+
+def main(old, new, new_template_arg=False):
     bad = 0
     for name in OBJECTS:
         with tempfile.TemporaryDirectory() as work:
             (a, na), (b, nb) = functions(os.path.join(old, name), work), functions(os.path.join(new, name), work)
+        if new_template_arg:
+            a = {s: masked(t) for s, t in a.items()}
+            renamed = {}
+            for s, t in b.items():
+                was = less_trailing_false(s) if s not in a else None
+                renamed[was if was in a and was not in b else s] = masked(t)
+            b = renamed
         only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
         differ = sorted(s for s in set(a) & set(b) if a[s] != b[s])
         print(f"{name}: {len(a)} | {len(b)} functions ({na} | {nb} FUNC entries), {len(only_a)} only old, {len(only_b)} only new, {len(differ)} with different text")
@@ -70,4 +106,5 @@ def main(old, new):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    args = [x for x in sys.argv[1:] if x != "--new-template-arg"]
+    sys.exit(main(args[0], args[1], "--new-template-arg" in sys.argv[1:]))

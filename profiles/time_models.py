@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of the step kernels with and without one of the per-drone models, interleaved A/B:
-    python3 profiles/time_models.py MODEL [reps] [configs]    (MODEL: dynamics, wind, actuator, sensor or privileged; configs: a comma
+    python3 profiles/time_models.py MODEL [reps] [configs]    (MODEL: dynamics, wind, actuator, sensor, privileged or goal; configs: a comma
                                                                list of the model's configuration names below; default all of them)
 The A/B against another tree (without the model) runs the configurations that tree knows from a checkout of each tree in turn.
 Each launch is timed by the two events dn_set_launch_events attaches to its own dispatch (the kernel alone, as a kernel trace sees it);
@@ -41,6 +41,11 @@ privileged (dn_enable_privileged)
   only: no terminal rows are bound) and `fused_term` with want_terminal=True (those four outputs in every configuration, and the terminal
   rows bound as well), which is what a collector that bootstraps truncated episodes runs.  The single steps are step_tensor's default,
   want_terminal=True: both row buffers bound.
+goal (dn_enable_goal)
+  sens           the sensor model's sens+lat+bias, no privileged rows: what a sim-to-real user runs without the feature
+  goal-world     the same with GoalObservation(frame="world"): the goal family, 32 bytes stored per drone-step
+  goal-body      the same with frame="body": three float32 sin / cos pairs and two rotations per row as well
+  The fused launch binds step rows only (no want_terminal); the single steps are step_tensor's default, both row buffers bound.
 
 Every model's rows carry <config>_over_<baseline>_<kind> for each of its own configurations against its baseline (the first
 configuration; `opt` for wind); dynamics keeps the names it was first measured under (dr_over_opt, dr_over_ref, dr1_over_opt).
@@ -80,10 +85,12 @@ def configs(model):
                    "sens+lat+bias": sens, "opt": {}, "ref": REF},
         "privileged": {"sens": sens, "priv-obs": dict(sens, privileged=pkg.PrivilegedObservation(groups=("obs",))),
                        "priv-all": dict(sens, privileged=pkg.PrivilegedObservation(groups=("obs", "dyn", "wind", "act", "sens")))},
+        "goal": {"sens": sens, "goal-world": dict(sens, goal=pkg.GoalObservation(frame="world")),
+                 "goal-body": dict(sens, goal=pkg.GoalObservation(frame="body"))},
     }[model]
 
 
-BASELINE = {"wind": "opt", "actuator": "dr+gust", "sensor": "act", "privileged": "sens"}
+BASELINE = {"wind": "opt", "actuator": "dr+gust", "sensor": "act", "privileged": "sens", "goal": "sens"}
 # (key, numerator, denominator) of the ratio columns; dynamics keeps the names of its committed results
 RATIOS = {m: [(f"{nm}_over_{b}", nm, b) for nm in configs(m) if nm not in (b, "opt", "ref")] for m, b in BASELINE.items()}
 RATIOS["dynamics"] = [("dr_over_opt", "opt+dr", "opt"), ("dr_over_ref", "opt+dr", "ref"), ("dr1_over_opt", "opt+dr1", "opt")]
@@ -131,8 +138,8 @@ for n in (32768, 262144):
         e.reset_tensor()
     acts = torch.rand((K, n, 4), device=dev) * 2 - 1
     one = acts[0].contiguous()
-    # one set of output buffers for every env (the launches are serial), from an env that hands out the privileged rows if there is one
-    priv = [nm for nm in names if "privileged" in (configs(model)[nm] or {})]
+    # one set of output buffers for every env (the launches are serial), from an env that hands out the privileged / goal rows if there is one
+    priv = [nm for nm in names if {"privileged", "goal"} & set(configs(model)[nm] or {})]
     widest = envs[priv[-1] if priv else names[0]]
     outs = {"fused": widest.rollout_tensor(acts)}
     if with_term:

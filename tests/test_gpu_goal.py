@@ -1,0 +1,686 @@
+"""Goal observations (include/dronenav.h dn_enable_goal) on the HIP path: the vector to the current target waypoint and the segment after
+it, per drone and step.
+
+The reference is the definition evaluated in NumPy float64 (tests/goal_support.py) on the float32 rows an env with the normaliser off
+outputs (`obs` / `terminal_obs`: the delivered rows), the index column of the row and the float64 waypoints of the configuration.
+
+ 1. nothing feeds back: every output, the state and the four getters, bit for bit, with and without the feature over 304 steps;
+ 2. values: step, reset and terminal rows against the reference, both frames, float64 and float32 compute; the index columns;
+ 3. the normaliser is transparent: the same env with normalize_obs=True writes the same bits;
+ 4. the sensor model is in the row: delayed, biased rows match the reference on the delivered y and differ from a twin without sensor;
+ 5. one fused launch = K single steps, K in {5, 20, 64}, both buffers;
+ 6. all 16 instantiations at 1 000 drones with some models off; a poison pattern in the terminal buffer survives where not done;
+ 7. fleet edges, two shards, hipGraph replay, dn_reset, capacity_steps, unbind, the refusing entry points;
+ 8. RolloutCollector(policy_input="observation+goal") against a host recomputation, and "observation" unchanged by the feature.
+
+Driving input.  Random actions rarely pass a gate, so gate passes are made on purpose: the track has three waypoints and no corridor test
+(cylinder=False), and before a launch `_place` puts a share of the drones beside a drawn waypoint with set_state (position at the
+waypoint, _distance_to_target = 0.05 <= threshold = 0.3).  rules_verdict tests the ENTRY distance, so each of them passes its gate in the
+next step unless it collides in it: a drone placed at the last waypoint completes the track (terminal index clamped to W - 1), the others
+fly on with index 1 or 2 (rows with index > 0 for the rest of their episode).  Episodes end by the time limit: max_steps = 40 with the
+step counters spread over [0, 40) ends about half the fleet in any 20 steps, inside fused launches too.  Every driving run asserts the
+boundaries it met (Seen.check).
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import goal_support as G  # noqa: E402
+from gpu_support import DEV, _acts, _same_state, _stagger  # noqa: E402
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import AMPS, BODY, FULL, GUSTY, NOISE, SHAPES, LAUNCH_SHAPES  # noqa: E402
+from model_support import bits as _bits  # noqa: E402
+
+WP = np.array([[0.0, 1.0, 0.6], [-1.0, 0.0, 1.0], [0.0, -1.0, 0.6]])
+SPAWN = np.array([[1.0, 0.0, 0.5]])
+DIM = [-2.0, -2.0, 0.0, 2.0, 2.0, 2.0]
+W = len(WP)
+PATTERN = 0x7FC12345                    # a quiet NaN no kernel produces
+ALL_LAT = set(range(9))
+ALL = ("dynamics", "wind", "actuator", "sensor")
+VEC = [0, 1, 2, 4, 5, 6]                # the scaled components of a row
+KEYS = ("obs", "reward", "done", "truncated", "found_targets", "terminal_obs", "ep_return", "ep_length", "goal", "terminal_goal")
+
+
+def _models(pkg, which=ALL):
+    full = dict(dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), actuator=pkg.ActuatorModel(**FULL),
+                sensor=pkg.SensorModel(latency=(0, 8), bias=AMPS))
+    return {k: v for k, v in full.items() if k in which}
+
+
+def _env(pkg, n, *, goal="world", which=ALL, **kw):
+    opts = dict(target_points=WP, initial_xyzs=SPAWN, aviary_dim=DIM, circle=False, cylinder=False, max_steps=40, seed=17, device=DEV,
+                normalize_obs=False)
+    opts.update(kw)
+    opts.update(_models(pkg, which))
+    if goal:
+        opts["goal"] = pkg.GoalObservation(frame=goal)
+    return pkg.DroneVecEnv(None, n, **opts)
+
+
+def _place(envs, rng, share=0.3, every=None):
+    """Puts `share` of the drones of every env (the same ones) beside a drawn waypoint: they pass that gate in the next step.  A fifth of
+    them get a step counter at the time limit as well: their episode is truncated in the very step that passes the gate, so the
+    verdict's index (entry + 1) and the entry index differ in a terminal row.  `every` = a launch number: every drone is placed, drone j
+    beside waypoint (every + j) % W (the small fleets, where a drawn share may be nobody).  Returns (placed, waypoint, late) per drone."""
+    st = envs[0].get_state()
+    n = len(st)
+    if every is None:
+        pick = rng.random(n) < share
+        idx = rng.integers(0, W, n)
+    else:
+        pick = np.ones(n, bool)
+        idx = (every + np.arange(n)) % W
+    late = pick & (rng.random(n) < 0.2)
+    for e in envs:
+        st = e.get_state()
+        st["idx"][pick] = idx[pick]
+        st["pos"][pick] = WP[idx[pick]].astype(np.float32)
+        st["cur_pos"][pick] = WP[idx[pick]].astype(np.float32)
+        st["d"][pick] = 0.05
+        st["d_prev"][pick] = 0.05
+        st["steps"][late] = e.cfg.max_steps
+        e.set_state(st)
+    return pick, idx, late
+
+
+def _adv(env, acts):
+    """K = len(acts) control steps (dn_step for K = 1, else one fused launch): step-major numpy copies, the goal rows included."""
+    if acts.shape[0] == 1:
+        o, r, d, info = env.step_tensor(acts[0])
+        out = dict(info, obs=o, reward=r, done=d)
+        return {k: out[k].cpu().numpy()[None] for k in KEYS if k in out}
+    out = env.rollout_tensor(acts, want_terminal=True)
+    return {k: out[k].cpu().numpy() for k in KEYS if k in out}
+
+
+def _same_bits(got, want, tag):
+    a, b = _bits(got), _bits(want)
+    if not np.array_equal(a, b):
+        bad = np.argwhere(a != b)
+        raise AssertionError((tag, len(bad), bad[:5].tolist(), np.asarray(got)[tuple(bad[0])], np.asarray(want)[tuple(bad[0])]))
+
+
+class Seen:
+    """The boundaries a driving run must meet."""
+
+    def __init__(self):
+        self.ends = self.inside = self.ahead = self.completed = self.crossing = 0
+        self.sens_lat = set()
+
+    def rows(self, res):
+        done = res["done"].astype(bool)
+        self.ends += int(done.sum())
+        self.inside += int(done[:-1].sum()) if done.shape[0] > 1 else 0
+        self.ahead += int((res["goal"][..., 3] > 0).sum())
+        if "terminal_goal" in res:
+            full = done & (res["found_targets"] == W)
+            self.completed += int((res["terminal_goal"][..., 3][full] == W - 1).sum())
+
+    def crossed(self, res, placed):
+        """Step 0 of the launch after _place: a drone placed late beside a gate that is not the last passes it and is truncated in the
+        same step -- its terminal row carries the verdict's index, entry + 1, not the entry index."""
+        pick, idx, late = placed
+        m = late & (idx < W - 1) & res["done"][0].astype(bool) & (res["found_targets"][0] == idx + 1)
+        assert np.array_equal(res["terminal_goal"][0, m, 3], (idx[m] + 1).astype(np.float32)), "terminal index is not the verdict's"
+        assert (res["truncated"][0, m] == 1).all()
+        self.crossing += int(m.sum())
+
+    def latencies(self, env):
+        self.sens_lat.update(np.unique(env.get_sensor()["latency"].cpu().numpy()).astype(int).tolist())
+
+    def check(self, fused=True, latencies=False, crossing=False):
+        assert self.ends >= 100, self.ends
+        assert not crossing or self.crossing >= 1, "no episode was truncated in the step that passed a gate"
+        assert not fused or self.inside > 0, "no episode ended inside a fused launch"
+        assert self.ahead >= 50, f"{self.ahead} rows with index > 0"
+        assert self.completed >= 1, "no completed track: no terminal row with a clamped index"
+        assert not latencies or self.sens_lat == ALL_LAT, self.sens_lat
+
+
+def _check(res, frame, tag, y=None):
+    """The rows of `res` against the reference on res's own obs / terminal_obs (or those of `y`, an env with the normaliser off)."""
+    y = res if y is None else y
+    done = res["done"].astype(bool)
+    rows = res["goal"]
+    idx = rows[..., 3]
+    assert np.array_equal(idx, np.floor(idx)) and idx.min() >= 0 and idx.max() <= W - 1, tag
+    assert not idx[done].any(), f"{tag}: a restarted drone's row is not against waypoint 0"
+    want = G.goal_rows(y["obs"], idx.astype(np.int64), WP, DIM, frame)
+    assert np.abs(want[..., VEC]).max() < G.MAG and np.abs(rows[..., VEC]).max() < G.MAG, tag
+    err = np.abs(rows.astype(np.float64) - want).max()
+    print(f"{tag}: step rows off the reference by {err:.3e}")
+    assert err <= G.ATOL, f"{tag}: step rows off the reference by {err:.3e}"
+    worst = err
+    if "terminal_goal" in res and done.any():
+        trow = res["terminal_goal"][done]
+        tidx = trow[:, 3]
+        found = res["found_targets"][done]
+        assert np.array_equal(tidx, np.floor(tidx)) and tidx.min() >= 0 and tidx.max() <= W - 1, tag
+        # found_targets is the entry index plus this step's gate pass, from report_scalars: the verdict's index, stated independently
+        assert np.array_equal(tidx, np.minimum(found, W - 1).astype(np.float32)), f"{tag}: terminal index is not min(found_targets, W - 1)"
+        twant = G.goal_rows(y["terminal_obs"][done], tidx.astype(np.int64), WP, DIM, frame)
+        assert np.abs(twant[:, VEC]).max() < G.MAG, tag
+        terr = np.abs(trow.astype(np.float64) - twant).max()
+        print(f"{tag}: terminal rows off the reference by {terr:.3e}")
+        assert terr <= G.ATOL, f"{tag}: terminal rows off the reference by {terr:.3e}"
+        worst = max(worst, terr)
+    return worst
+
+
+def _check_reset(env, frame, tag, y=None):
+    obs = (env if y is None else y).reset_tensor().cpu().numpy()
+    if y is not None:
+        env.reset_tensor()
+    rows = env.goal.cpu().numpy()
+    assert not rows[:, 3].any() and (rows[:, 7] == 1).all(), tag
+    want = G.goal_rows(obs, np.zeros(len(obs), np.int64), WP, DIM, frame)
+    err = np.abs(rows.astype(np.float64) - want).max()
+    assert err <= G.ATOL and np.abs(want[:, VEC]).max() < G.MAG, f"{tag}: reset rows off the reference by {err:.3e}"
+
+
+# ---- 1. nothing feeds back -----------------------------------------------------------------------------------------------
+def test_goal_rows_feed_nothing_back():
+    pkg = _pkg()
+    n = 2048
+    kw = dict(normalize_obs=True, **NOISE)
+    A, B = _env(pkg, n, goal="body", **kw), _env(pkg, n, goal=None, **kw)
+    assert A.kernel_waves(fused=True) == A.kernel_waves(fused=False) == 1
+    assert A.goal_config() == pkg.GoalObservation(frame="body") and B.goal_config() is None and B.goal is None
+    assert torch.equal(A.reset_tensor(), B.reset_tensor())
+    rng, seen = np.random.default_rng(4), Seen()
+    for e in (A, B):
+        _stagger(e, np.random.default_rng(40))
+    plan = [1] * 4 + [20] * 15                                            # 304 control steps
+    for launch, K in enumerate(plan):
+        if launch % 3 == 0:
+            _place((A, B), rng)
+        acts = _acts(rng, n, K)
+        ra, rb = _adv(A, acts), _adv(B, acts)
+        assert "goal" in ra and "goal" not in rb
+        for k in rb:
+            if k in ("terminal_obs", "ep_return", "ep_length"):
+                m = rb["done"].astype(bool)
+                assert np.array_equal(_bits(ra[k][m]) if ra[k].dtype == np.float32 else ra[k][m],
+                                      _bits(rb[k][m]) if rb[k].dtype == np.float32 else rb[k][m]), (k, launch)
+            elif ra[k].dtype == np.float32:
+                _same_bits(ra[k], rb[k], (k, launch))
+            else:
+                assert np.array_equal(ra[k], rb[k]), (k, launch)
+        seen.rows(ra)
+        seen.latencies(A)
+        _same_state(A.get_state(), B.get_state())                         # the normaliser statistics included
+        assert torch.equal(A.get_dynamics(), B.get_dynamics())
+        for x, y in zip(A.get_wind(), B.get_wind()):
+            assert torch.equal(x, y)
+        for ga, gb in ((A.get_actuator(), B.get_actuator()), (A.get_sensor(), B.get_sensor())):
+            for k in ga:
+                assert torch.equal(ga[k], gb[k]), (k, launch)
+    assert A.step_count == B.step_count == sum(plan)
+    seen.check(latencies=True)
+    A.close()
+    B.close()
+
+
+# ---- 2. values ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+@pytest.mark.parametrize("frame", ["world", "body"])
+def test_rows_equal_the_reference(frame, f32):
+    pkg = _pkg()
+    n = 1000
+    A = _env(pkg, n, goal=frame, compute_dtype="float32" if f32 else "float64", **NOISE)
+    _check_reset(A, frame, "reset")
+    rng, seen = np.random.default_rng(6), Seen()
+    _stagger(A, np.random.default_rng(60))
+    for launch, K in enumerate([1] * 6 + [20] * 3):
+        placed = _place((A,), rng) if launch % 2 == 0 else None
+        res = _adv(A, _acts(rng, n, K))
+        _check(res, frame, f"{frame} {'f32' if f32 else 'f64'} launch {launch}")
+        if placed is not None:
+            seen.crossed(res, placed)
+        if K == 1:       # the index column is the state's waypoint index after the step (0 for a restarted drone)
+            assert np.array_equal(res["goal"][0, :, 3], A.get_state()["idx"].astype(np.float32)), launch
+            assert torch.equal(A.goal, torch.from_numpy(res["goal"][0]).to(DEV))
+        else:
+            assert torch.equal(A.goal, torch.from_numpy(res["goal"][-1]).to(DEV))          # env.goal follows the launch's last rows
+        seen.rows(res)
+        seen.latencies(A)
+    seen.check(latencies=True, crossing=True)
+    A.close()
+
+
+# ---- 3. the normaliser is transparent ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("frame", ["world", "body"])
+def test_the_normaliser_does_not_touch_the_rows(frame):
+    pkg = _pkg()
+    n = 1000
+    A, R = _env(pkg, n, goal=frame, normalize_obs=True, **NOISE), _env(pkg, n, goal=frame, **NOISE)
+    A.reset_tensor()
+    R.reset_tensor()
+    _same_bits(A.goal.cpu().numpy(), R.goal.cpu().numpy(), "reset")
+    rng, seen = np.random.default_rng(8), Seen()
+    for e in (A, R):
+        _stagger(e, np.random.default_rng(80))
+    for launch, K in enumerate([1, 1, 20, 20, 20]):
+        _place((A, R), rng)
+        acts = _acts(rng, n, K)
+        ra, rr = _adv(A, acts), _adv(R, acts)
+        done = rr["done"].astype(bool)
+        assert np.array_equal(ra["done"], rr["done"]) and not np.array_equal(_bits(ra["obs"]), _bits(rr["obs"]))
+        _same_bits(ra["goal"], rr["goal"], ("goal", launch))
+        _same_bits(ra["terminal_goal"][done], rr["terminal_goal"][done], ("terminal_goal", launch))
+        seen.rows(ra)
+    seen.check()
+    A.close()
+    R.close()
+
+
+# ---- 4. the sensor model is in the row ---------------------------------------------------------------------------------------
+def test_the_rows_are_built_from_the_delivered_observation():
+    pkg = _pkg()
+    n = 1000
+    A = _env(pkg, n, goal="world", **NOISE)
+    T = _env(pkg, n, goal="world", which=("dynamics", "wind", "actuator"), **NOISE)          # the twin without the sensor model
+    A.reset_tensor()
+    T.reset_tensor()
+    rng, seen = np.random.default_rng(9), Seen()
+    for e in (A, T):
+        _stagger(e, np.random.default_rng(90))
+    differ = 0
+    for launch, K in enumerate([1, 1, 20, 20, 20]):
+        _place((A, T), rng)
+        acts = _acts(rng, n, K)
+        ra, rt = _adv(A, acts), _adv(T, acts)
+        _check(ra, "world", f"sensor launch {launch}")
+        _check(rt, "world", f"twin launch {launch}")
+        assert np.array_equal(ra["done"], rt["done"]) and np.array_equal(ra["goal"][..., 3], rt["goal"][..., 3])       # the same flight
+        differ += int((np.abs(ra["goal"][..., 0:3] - rt["goal"][..., 0:3]).max(axis=-1) > 1e-3).sum())
+        seen.rows(ra)
+        seen.latencies(A)
+    assert differ > 0, "the sensor model's latency and bias are not in the rows"
+    seen.check(latencies=True)
+    A.close()
+    T.close()
+
+
+# ---- 5. one fused launch = K single steps ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", [5, 20, 64])
+def test_one_fused_launch_equals_single_steps(K):
+    pkg = _pkg()
+    n = 1000
+    kw = dict(goal="body", normalize_obs=True, **NOISE)
+    F, S = _env(pkg, n, **kw), _env(pkg, n, **kw)
+    F.reset_tensor()
+    S.reset_tensor()
+    rng, seen = np.random.default_rng(10 + K), Seen()
+    for e in (F, S):
+        _stagger(e, np.random.default_rng(100))
+    for launch in range(max(2, 120 // K)):
+        _place((F, S), rng)
+        acts = _acts(rng, n, K)
+        rf = _adv(F, acts)
+        singles = [_adv(S, acts[t:t + 1]) for t in range(K)]
+        rs = {k: np.concatenate([s[k] for s in singles]) for k in ("done", "goal", "terminal_goal")}
+        done = rf["done"].astype(bool)
+        assert np.array_equal(rf["done"], rs["done"])
+        _same_bits(rf["goal"], rs["goal"], ("goal", launch))
+        _same_bits(rf["terminal_goal"][done], rs["terminal_goal"][done], ("terminal_goal", launch))
+        seen.rows(rf)
+    seen.check()
+    _same_state(F.get_state(), S.get_state())
+    F.close()
+    S.close()
+
+
+# ---- 6. all 16 instantiations ------------------------------------------------------------------------------------------------
+OFF = [("sensor",), ("dynamics", "actuator"), (), ("wind", "sensor"), ALL, ("actuator",), ("dynamics", "wind"), ("sensor", "actuator")]
+
+
+@pytest.mark.parametrize("K", [1, 20], ids=["single", "fused"])
+@pytest.mark.parametrize("noise", [False, True], ids=["quiet", "noise"])
+@pytest.mark.parametrize("norm", [False, True], ids=["raw", "norm"])
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+def test_every_instantiation_with_some_models_off(f32, norm, noise, K):
+    pkg = _pkg()
+    n = 1000                                                              # 15 full tiles and one of 40 drones
+    cell = 4 * f32 + 2 * norm + noise
+    frame = ("world", "body")[cell % 2]
+    kw = dict(goal=frame, which=OFF[cell], compute_dtype="float32" if f32 else "float64", **(NOISE if noise else {}))
+    A = _env(pkg, n, normalize_obs=bool(norm), **kw)
+    R = _env(pkg, n, **kw) if norm else None                              # the delivered rows: the same env with the normaliser off (test 3)
+    _check_reset(A, frame, "reset", y=R)
+    rng, seen = np.random.default_rng(20 + cell), Seen()
+    for e in (A, R):
+        if e is not None:
+            _stagger(e, np.random.default_rng(200))
+    out = None
+    for launch in range(40 if K == 1 else 4):
+        if launch % (8 if K == 1 else 1) == 0:
+            _place([e for e in (A, R) if e is not None], rng)
+        acts = _acts(rng, n, K)
+        if K == 1:
+            A._term_goal.view(torch.int32).fill_(PATTERN)
+            res = _adv(A, acts)
+        else:
+            out = A.rollout_tensor(acts, want_terminal=True, out=out)
+            torch.cuda.synchronize()
+            res = {k: out[k].cpu().numpy() for k in KEYS}
+            out["terminal_goal"].view(torch.int32).fill_(PATTERN)         # for the next launch
+        ry = _adv(R, acts) if R is not None else None
+        _check(res, frame, f"cell {cell} K {K} launch {launch}", y=ry)
+        if K == 1 or launch > 0:                                          # the caller's bytes stay where no episode ended
+            keep = ~res["done"].astype(bool)
+            assert (res["terminal_goal"].view(np.int32)[keep] == PATTERN).all(), launch
+            assert not (res["terminal_goal"].view(np.int32)[~keep] == PATTERN).any(), launch
+        seen.rows(res)
+    seen.check(fused=K > 1)
+    A.close()
+    if R is not None:
+        R.close()
+
+
+# ---- 7. fleet edges, shards, graph, reset, capacity, unbind, refusals --------------------------------------------------------
+@pytest.mark.parametrize("n,K", [(s, 1) for s in SHAPES] + [(s, 20) for s in LAUNCH_SHAPES])
+def test_fleet_edges(n, K):
+    """Every drone is placed before every launch, drone j beside waypoint (launch + j) % W: a third of the fleet completes the track in
+    the launch's first step, the others fly on with index 1 or 2.  3 * ceil(100 / n) launches give at least 100 completions, whatever
+    the fleet size; the time limit ends the other episodes inside the fused launches."""
+    pkg = _pkg()
+    A = _env(pkg, n, goal="body", **NOISE)
+    if K > 1:
+        assert n % 4 == 0                                                 # dn_step_many needs it for K > 1
+    _check_reset(A, "body", f"n {n} reset")
+    rng, seen = np.random.default_rng(n), Seen()
+    _stagger(A, np.random.default_rng(n + 1))
+    for launch in range(max(6, 3 * -(-100 // n))):
+        placed = _place((A,), rng, every=launch)
+        res = _adv(A, _acts(rng, n, K))
+        _check(res, "body", f"n {n} K {K} launch {launch}")
+        seen.crossed(res, placed)
+        seen.rows(res)
+    seen.check(fused=K > 1)
+    A.close()
+
+
+def test_rows_end_at_the_fleet():
+    """A bound buffer of exactly [K][n][8] inside a poisoned allocation: every row is written, nothing behind it."""
+    pkg = _pkg()
+    for n, K in ((65, 1), (68, 20)):
+        A = _env(pkg, n, goal="world", **NOISE)
+        A.reset_tensor()
+        big = torch.zeros(K * n * 8 + 64, dtype=torch.float32, device=DEV)
+        big.view(torch.int32).fill_(PATTERN)
+        pkg._capi.check(A._lib.dn_bind_goal(A._handle, big.data_ptr(), None, K))
+        acts = _acts(np.random.default_rng(n), n, K)
+        o = dict(obs=torch.zeros((K, n, 13), device=DEV), reward=torch.zeros((K, n), device=DEV),
+                 done=torch.zeros((K, n), dtype=torch.uint8, device=DEV), truncated=torch.zeros((K, n), dtype=torch.uint8, device=DEV),
+                 found=torch.zeros((K, n), dtype=torch.int32, device=DEV))
+        if K == 1:
+            rc = A._lib.dn_step(A._handle, acts.data_ptr(), *(o[k].data_ptr() for k in ("obs", "reward", "done", "truncated", "found")),
+                                None, None, None, None, None)
+        else:
+            rc = A._lib.dn_step_many(A._handle, K, acts.data_ptr(), *(o[k].data_ptr() for k in ("obs", "reward", "done", "truncated", "found")),
+                                     None, None, None, None, None)
+        pkg._capi.check(rc)
+        torch.cuda.synchronize()
+        w = big.view(torch.int32)
+        assert not bool((w[:K * n * 8] == PATTERN).any()) and bool((w[K * n * 8:] == PATTERN).all()), (n, K)
+        pkg._capi.check(A._lib.dn_bind_goal(A._handle, None, None, 0))
+        A.close()
+
+
+def test_two_shards_equal_the_whole_fleet():
+    pkg = _pkg()
+    n, K = 1024, 20
+    kw = dict(goal="body", max_steps=15, normalize_obs=True, **NOISE)
+    Wh = _env(pkg, n, **kw)
+    halves = [_env(pkg, n // 2, env_id_offset=off, **kw) for off in (0, n // 2)]
+    Wh.reset_tensor()
+    for h in halves:
+        h.reset_tensor()
+    assert torch.equal(Wh.goal, torch.cat([h.goal for h in halves]))
+    rng, seen = np.random.default_rng(2), Seen()
+    for launch in range(3):
+        st = Wh.get_state()
+        pick = rng.random(n) < 0.3
+        idx = rng.integers(0, W, n)
+        st["idx"][pick], st["d"][pick] = idx[pick], 0.05
+        Wh.set_state(st)
+        for i, h in enumerate(halves):
+            h.set_state(st[i * n // 2:(i + 1) * n // 2])
+        acts = _acts(rng, n, K)
+        rw = _adv(Wh, acts)
+        rh = [_adv(h, acts[:, i * n // 2:(i + 1) * n // 2].contiguous()) for i, h in enumerate(halves)]
+        done = rw["done"].astype(bool)
+        for k in ("goal", "terminal_goal"):
+            both = np.concatenate([r[k] for r in rh], axis=1)
+            _same_bits(rw[k][done] if k.startswith("terminal") else rw[k], both[done] if k.startswith("terminal") else both, (k, launch))
+        seen.rows(rw)
+    seen.check()
+    for e in [Wh] + halves:
+        e.close()
+
+
+def test_a_captured_graph_keeps_writing():
+    pkg = _pkg()
+    n = 1024
+    kw = dict(goal="world", max_steps=15, normalize_obs=True, **NOISE)
+    Gr, E = _env(pkg, n, **kw), _env(pkg, n, **kw)
+    Gr.reset_tensor()
+    E.reset_tensor()
+    rng = np.random.default_rng(5)
+    static = torch.zeros((n, 4), dtype=torch.float32, device=DEV)
+    for _ in range(3):                                                    # warm-up, eager
+        a = _acts(rng, n, 1)[0]
+        static.copy_(a)
+        Gr.step_tensor(static)
+        E.step_tensor(a)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    a = _acts(rng, n, 1)[0]
+    static.copy_(a)
+    with torch.cuda.graph(graph):
+        Gr.step_tensor(static)
+    graph.replay()
+    E.step_tensor(a)
+    seen = Seen()
+    for t in range(30):
+        if t % 10 == 0:
+            torch.cuda.synchronize()
+            _place((Gr, E), rng)
+        a = _acts(rng, n, 1)[0]
+        static.copy_(a)
+        for x in (Gr.goal, Gr._term_goal):
+            x.view(torch.int32).fill_(PATTERN)
+        graph.replay()
+        _, _, done, info = E.step_tensor(a)
+        m = done.bool()
+        assert torch.equal(Gr.goal.view(torch.int32), info["goal"].view(torch.int32)), t
+        assert torch.equal(Gr._term_goal.view(torch.int32)[m], info["terminal_goal"].view(torch.int32)[m]), t
+        assert bool((Gr._term_goal.view(torch.int32)[~m] == PATTERN).all())
+        seen.rows({k: v.cpu().numpy()[None] for k, v in dict(done=done, goal=info["goal"], terminal_goal=info["terminal_goal"],
+                                                              found_targets=info["found_targets"]).items()})
+    seen.check(fused=False)
+    _same_state(Gr.get_state(), E.get_state())
+    Gr.close()
+    E.close()
+
+
+def test_reset_writes_the_fresh_rows():
+    pkg = _pkg()
+    n = 1000
+    for frame in ("world", "body"):
+        A = _env(pkg, n, goal=frame, normalize_obs=True, random_spawn=True, **NOISE)
+        R = _env(pkg, n, goal=frame, random_spawn=True, **NOISE)
+        for _ in range(2):                                                # the second reset redraws spawn points, bias and noise
+            _check_reset(A, frame, f"{frame} reset", y=R)
+            acts = _acts(np.random.default_rng(1), n, 7)
+            A.rollout_tensor(acts)
+            R.rollout_tensor(acts)
+        # without want_terminal there are no terminal rows: none handed out, none written
+        A._term_goal.view(torch.int32).fill_(PATTERN)
+        info = A.step_tensor(acts[0], want_terminal=False)[3]
+        assert info["terminal_goal"] is None and info["goal"] is A.goal
+        assert bool((A._term_goal.view(torch.int32) == PATTERN).all())
+        A.close()
+        R.close()
+
+
+def test_capacity_unbind_and_refusals():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import collector
+    n = 1024
+    A, P = _env(pkg, n, **NOISE), _env(pkg, n, goal=None, **NOISE)         # unbound, A launches P's family: the sensor model's
+    lib, h = A._lib, A._handle
+    A.reset_tensor()
+    P.reset_tensor()
+    rng = np.random.default_rng(7)
+    # capacity_steps: k beyond it is refused before anything is launched
+    rows = torch.zeros((4, n, 8), dtype=torch.float32, device=DEV)
+    rows.view(torch.int32).fill_(PATTERN)
+    pkg._capi.check(lib.dn_bind_goal(h, rows.data_ptr(), None, 4))
+    A._goal_bound = None
+    acts = _acts(rng, n, 5)
+    o = dict(obs=torch.zeros((5, n, 13), device=DEV), reward=torch.zeros((5, n), device=DEV), done=torch.zeros((5, n), dtype=torch.uint8, device=DEV),
+             truncated=torch.zeros((5, n), dtype=torch.uint8, device=DEV), found=torch.zeros((5, n), dtype=torch.int32, device=DEV))
+
+    def many(k):
+        return lib.dn_step_many(h, k, acts.data_ptr(), o["obs"].data_ptr(), o["reward"].data_ptr(), o["done"].data_ptr(), o["truncated"].data_ptr(),
+                                o["found"].data_ptr(), None, None, None, None, None)
+    assert many(5) == -1 and b"capacity_steps" in lib.dn_last_error() and b"dn_bind_goal" in lib.dn_last_error()
+    torch.cuda.synchronize()
+    assert bool((rows.view(torch.int32) == PATTERN).all()) and A.step_count == 0
+    assert many(4) == 0
+    torch.cuda.synchronize()
+    assert not bool((rows.view(torch.int32) == PATTERN).any()) and A.step_count == 4
+    P.rollout_tensor(acts[:4].contiguous())
+    # misuse of the binding
+    assert lib.dn_bind_goal(h, rows.data_ptr() + 4, None, 4) == -1 and b"aligned" in lib.dn_last_error()
+    assert lib.dn_bind_goal(h, rows.data_ptr(), None, 0) == -1
+    assert lib.dn_bind_goal(h, None, rows.data_ptr(), 4) == -1
+    assert lib.dn_bind_goal(P._handle, rows.data_ptr(), None, 4) == -5                # DN_ERR_BAD_STATE: not enabled
+    # unbind: enabled but unbound writes nothing, and flies the same steps on the family without the feature
+    pkg._capi.check(lib.dn_bind_goal(h, None, None, 0))
+    rows.view(torch.int32).fill_(PATTERN)
+    A.goal.view(torch.int32).fill_(PATTERN)
+    assert A.kernel_waves(fused=True) == A.kernel_waves(fused=False) == 1
+    a = _acts(rng, n, 1)[0]
+    A._launch(a)
+    ref = P.step_tensor(a)
+    torch.cuda.synchronize()
+    assert bool((rows.view(torch.int32) == PATTERN).all()) and bool((A.goal.view(torch.int32) == PATTERN).all())
+    assert torch.equal(A._obs, P._obs) and torch.equal(A._reward, ref[1])
+    assert many(5) == 0                                                   # no binding, no capacity to exceed
+    P.rollout_tensor(acts)
+    # the next step_tensor binds the env's own buffers again
+    a = _acts(rng, n, 1)[0]
+    _, _, _, info = A.step_tensor(a)
+    P.step_tensor(a)
+    assert not bool((info["goal"].view(torch.int32) == PATTERN).any())
+    _same_state(A.get_state(), P.get_state())
+    # the entry points whose kernels carry no rows (no other model on: the refusal names this feature)
+    B = _env(pkg, n, which=())
+    assert B.kernel_waves(fused=True) == B.kernel_waves(fused=False) == 1
+    with pytest.raises(pkg.DroneNavError, match="goal"):
+        B.eval_kinematics_tensor(torch.zeros((n, 13), dtype=torch.float64, device=DEV))
+    mean, out4, lp = torch.zeros((n, 4), device=DEV), torch.zeros((n, 4), device=DEV), torch.zeros(n, device=DEV)
+    log_std = (C.c_float * 4)(0, 0, 0, 0)
+    rc = lib.dn_step_sampled(B._handle, mean.data_ptr(), log_std, 1, 0, out4.data_ptr(), lp.data_ptr(), *B._ptrs[0], None, None, None, None, None)
+    assert rc == -1 and b"dn_enable_goal" in lib.dn_last_error()
+    rc = lib.dn_step_squashed(B._handle, torch.zeros((n, 8), device=DEV).data_ptr(), 1, 0, out4.data_ptr(), lp.data_ptr(), *B._ptrs[0],
+                              None, None, None, None, None)
+    assert rc == -1 and b"dn_enable_goal" in lib.dn_last_error()
+    rc = lib.dn_mlp_step_sampled(B._handle, C.byref(pkg._capi.DnMlpNet()), 1, B._obs.data_ptr(), 13, log_std, 1, 0, out4.data_ptr(),
+                                 lp.data_ptr(), *B._ptrs[0], None, None, None, None, None)
+    assert rc == -1 and b"dn_enable_goal" in lib.dn_last_error()
+    for cls in (collector.FusedRolloutCollector, collector.OffPolicyCollector):
+        with pytest.raises(ValueError, match="goal"):
+            cls(B, None, 8)
+    with pytest.raises(ValueError, match="goal"):
+        collector.RolloutCollector(P, lambda o: None, 8, policy_input="observation+goal")          # the env has no rows
+    with pytest.raises(ValueError, match="policy_input"):
+        collector.RolloutCollector(A, lambda o: None, 8, policy_input="goal")
+    for e in (A, P, B):
+        e.close()
+
+
+# ---- 8. the collector ----------------------------------------------------------------------------------------------------
+def _policy(width):
+    g = torch.Generator(device="cpu").manual_seed(3)
+    Wa = (0.05 * torch.randn((width, 4), generator=g)).to(DEV)
+    Wv = (0.1 * torch.randn((width,), generator=g)).to(DEV)
+
+    def policy(x):
+        assert x.shape[1] == width, x.shape
+        x = torch.nan_to_num(x).clamp(-5, 5)
+        return 0.0922 + 0.01 * torch.tanh(x @ Wa), x @ Wv, -(x * x).sum(dim=1)
+    return policy
+
+
+def test_collector_feeds_the_policy_observation_and_goal():
+    pkg = _pkg()
+    from drl_dronenavigation_amd.collector import RolloutCollector
+    n, T, gamma = 1024, 48, 0.99
+    kw = dict(goal="body", max_steps=40, normalize_obs=True, **NOISE)
+    A, R = _env(pkg, n, **kw), _env(pkg, n, **kw)
+    policy = _policy(21)
+    col = RolloutCollector(A, policy, T, policy_input="observation+goal", gamma=gamma)
+    obs = R.reset_tensor().clone()
+    goal = R.goal.clone()
+    assert torch.equal(col._last_obs, obs) and torch.equal(col._last_goal, goal)
+    trunc = ahead_boot = 0
+    rng, seen = np.random.default_rng(12), Seen()
+    for e in (A, R):
+        _stagger(e, np.random.default_rng(120))
+    for rollout in range(3):                                              # the later rollouts start mid-episode
+        # gate passes in the rollout's first step: rows with index > 0 in the policy's input until the episode ends, a clamped
+        # terminal row where the track was completed, truncations with index > 0 in the bootstrap's input
+        _place((A, R), rng)
+        buf = col.collect()
+        assert tuple(buf["goal"].shape) == (T, n, 8) and tuple(buf["obs"].shape) == (T, n, 13)
+        for t in range(T):
+            x = torch.cat((obs, goal), dim=1)
+            actions, values, log_probs = policy(x)
+            assert torch.equal(buf["obs"][t], obs) and torch.equal(buf["goal"][t], goal), (rollout, t)
+            assert torch.equal(buf["actions"][t], actions) and torch.equal(buf["values"][t], values), (rollout, t)
+            next_obs, reward, done, info = R.step_tensor(actions.clamp(-1.0, 1.0))
+            seen_rows = torch.where(done.bool()[:, None], torch.cat((info["terminal_obs"], info["terminal_goal"]), dim=1),
+                                    torch.cat((next_obs, info["goal"]), dim=1))
+            want = reward + gamma * policy(seen_rows)[1] * info["truncated"].to(reward.dtype)
+            assert torch.equal(buf["rewards"][t], want), (rollout, t)
+            trunc += int(info["truncated"].sum())
+            ahead_boot += int((info["truncated"].bool() & (info["terminal_goal"][:, 3] > 0)).sum())
+            seen.rows({k: v.cpu().numpy()[None] for k, v in dict(done=done, goal=info["goal"], terminal_goal=info["terminal_goal"],
+                                                                  found_targets=info["found_targets"]).items()})
+            obs, goal = next_obs.clone(), info["goal"].clone()
+        assert torch.equal(buf["last_values"], policy(torch.cat((obs, goal), dim=1))[1])
+    seen.check(fused=False)
+    assert trunc > 0 and ahead_boot > 0, (trunc, ahead_boot)            # the bootstrap saw terminal rows with index > 0
+    A.close()
+    R.close()
+
+
+def test_collector_on_observations_is_unchanged_by_the_feature():
+    pkg = _pkg()
+    from drl_dronenavigation_amd.collector import RolloutCollector
+    n, T = 1024, 48
+    kw = dict(max_steps=40, normalize_obs=True, **NOISE)
+    A, P = _env(pkg, n, goal="world", **kw), _env(pkg, n, goal=None, **kw)
+    ca, cp = RolloutCollector(A, _policy(13), T), RolloutCollector(P, _policy(13), T)
+    ends = 0
+    for rollout in range(2):
+        ba, bp = ca.collect(), cp.collect()
+        assert set(ba) == set(bp)
+        ends += int(bp["episode_starts"][1:].sum()) + int(bp["last_dones"].sum())
+        for k in bp:
+            assert torch.equal(ba[k].view(torch.int32) if ba[k].dtype == torch.float32 else ba[k],
+                               bp[k].view(torch.int32) if bp[k].dtype == torch.float32 else bp[k]), (k, rollout)
+    assert ends >= 100, ends
+    _same_state(A.get_state(), P.get_state())
+    A.close()
+    P.close()
