@@ -909,7 +909,24 @@ template <typename R> struct Flight {
     float d_e, dprev_e;                                      // entry _distance_to_target / _prev_distance_to_target, float32 state
     int idx_e, just_found_e, truncated;                      // entry index / flag; _computeTruncated (entry _steps)
 };
-constexpr int DN_NMAIL64 = 7;                                // R-valued words that cross to the report wave: position, forward vector, Verdict.d_obs
+// The same step with its float32 state words held WIDENED: every R below that is a float in Flight is exactly (R)(that float32 word), never
+// the double it was rounded from.  (R)(float) gives the same bits wherever it is evaluated, so a wave that receives the widened word
+// from the wave that owns it computes what it would have computed from the float (the four- / five-wave fused kernels, see MailL).
+// The functions that read these words take the flight's type as a parameter: on a FlightW their `(R)word` is no conversion at all.
+template <typename R> struct FlightW {
+    R px, py, pz, qx, qy, qz, qw;
+    R fwx, fwy, fwz;
+    float roll_num32, roll_den32, pitch32, yaw32;
+    R vx, vy, vz;                                            // (R)(float32 state word)
+    float wx, wy, wz;                                        // read as floats (observation columns 9 .. 11)
+    R vex, vey, vez, aex, aey, aez;                          // (R)(float32 state word)
+    R d_e, dprev_e;                                          // (R)(float32 state word)
+    int idx_e, just_found_e, truncated;
+};
+template <typename R> struct Vec3R {                         // three float32 state words, widened: each is exactly (R)(float)
+    R x, y, z;
+};
+constexpr int DN_NMAIL64 = 7;                              // R-valued words that cross to the report wave: position, forward vector, Verdict.d_obs
 template <typename R> struct Verdict {
     R d_obs;           // the distance the reset observation shows (quirk Q2)
     int coll1;         // _computeTerminated inside _computeReward (entry index)
@@ -1253,8 +1270,9 @@ template <typename R> DN_DEV QuatTerms<R> quat_terms_identity()
 template <typename R> struct LinPre {
     R vkx, vky, kl;        // vx kl, vy kl, kl = c + c |v|
 };
-template <typename R>
-DN_DEV LinPre<R> physics_linear_pre(const float4 G2, const R damp = K<R>::LIN_DAMP)
+// V: the velocity words, a float4 of state or a Vec3R that holds the same words already widened (the same values either way)
+template <typename R, typename V>
+DN_DEV LinPre<R> physics_linear_pre(const V G2, const R damp = K<R>::LIN_DAMP)
 {
     LinPre<R> l;
     const R vx = G2.x, vy = G2.y, vz = G2.z;
@@ -1263,8 +1281,8 @@ DN_DEV LinPre<R> physics_linear_pre(const float4 G2, const R damp = K<R>::LIN_DA
     l.vkx = vx * l.kl; l.vky = vy * l.kl;
     return l;
 }
-template <typename R>
-DN_DEV Lin<R> physics_linear_post(const float4 G0, const float4 G2, const AttCol<R> col, const LinPre<R> &l, const R fz, const R dax, const R day,
+template <typename R, typename V>
+DN_DEV Lin<R> physics_linear_post(const float4 G0, const V G2, const AttCol<R> col, const LinPre<R> &l, const R fz, const R dax, const R day,
                                   const R daz, const bool extra, const R inv_m = K<R>::INV_M)     // inv_m: 1 / (M s_m) of a randomised body
 {
     Lin<R> o;
@@ -1285,8 +1303,8 @@ DN_DEV Lin<R> physics_linear_post(const float4 G0, const float4 G2, const AttCol
     o.vx = vx; o.vy = vy; o.vz = vz;
     return o;
 }
-template <typename R>
-DN_DEV Lin<R> physics_linear_col(const float4 G0, const float4 G2, const AttCol<R> col, const R fz, const R dax, const R day, const R daz,
+template <typename R, typename V>
+DN_DEV Lin<R> physics_linear_col(const float4 G0, const V G2, const AttCol<R> col, const R fz, const R dax, const R day, const R daz,
                                  const bool extra, const R damp = K<R>::LIN_DAMP, const R inv_m = K<R>::INV_M)
 {
     return physics_linear_post<R>(G0, G2, col, physics_linear_pre<R>(G2, damp), fz, dax, day, daz, extra, inv_m);
@@ -2003,8 +2021,8 @@ template <typename R> struct Observed {
 // same Flight and share no intermediate, so a kernel may run them on two waves; observe_phase = both on one.
 // The row in two halves that share nothing: the columns that read the linear state (position, velocity, distance: 0 1 2 6 7 8 12)
 // and those that read the attitude and the angular velocity (3 4 5 9 10 11) -- a kernel may fill them on two waves.
-template <typename R>
-DN_DEV void observe_columns_lin(const DnParams &p, const DnConsts<R> &c, const Flight<R> &fl, float o[DN_OBS_DIM])
+template <typename R, typename FL>      // FL: Flight<R> or FlightW<R>
+DN_DEV void observe_columns_lin(const DnParams &p, const DnConsts<R> &c, const FL &fl, float o[DN_OBS_DIM])
 {
     // _computeObs (PBDroneEnv.py:296-336, :338-398), stale distance d_e (quirk Q1).  The reference clips position /
     // yaw / distance columns to the float32 range before the cast (:326); positions are bounded by the aviary box
@@ -2024,8 +2042,8 @@ DN_DEV void observe_columns_lin(const DnParams &p, const DnConsts<R> &c, const F
     }
     o[12] = p.include_distance ? (float)((R)fl.d_e * c.inv_max_target_dist) : 0.0f;
 }
-template <typename R>
-DN_DEV void observe_columns_att(const Flight<R> &fl, float o[DN_OBS_DIM])
+template <typename R, typename FL>
+DN_DEV void observe_columns_att(const FL &fl, float o[DN_OBS_DIM])
 {
     const float roll32 = atan2_fast32(fl.roll_num32, fl.roll_den32), pitch32 = fl.pitch32, yaw32 = fl.yaw32;    // attitude_phase
     const float inv_pi32 = (float)K<R>::INV_PI;
@@ -2079,9 +2097,21 @@ DN_DEV Smooth<R> smooth_term(const float ex, const float ey, const float ez, con
     if (o.pen) o.s = (R)__builtin_amdgcn_sqrtf((float)a2);
     return o;
 }
-// the terms of reward_entry that read the distance pair and the gate index only
+// ... on words that are already widened: e and P are exactly (R)(the float32 words), so the differences are the same bits
 template <typename R>
-DN_DEV void reward_entry_core(const DnParams &p, const DnConsts<R> &c, const Flight<R> &fl, RewardPre<R> &q)
+DN_DEV Smooth<R> smooth_term(const R ex, const R ey, const R ez, const Vec3R<R> &P, const R lim2)
+{
+    const R lx = ex - P.x, ly = ey - P.y, lz = ez - P.z;
+    const R a2 = FM<R>::fma(lz, lz, FM<R>::fma(ly, ly, lx * lx));
+    Smooth<R> o;
+    o.pen = a2 > lim2;
+    o.s = R(0.0);
+    if (o.pen) o.s = (R)__builtin_amdgcn_sqrtf((float)a2);
+    return o;
+}
+// the terms of reward_entry that read the distance pair and the gate index only
+template <typename R, typename FL>
+DN_DEV void reward_entry_core(const DnParams &p, const DnConsts<R> &c, const FL &fl, RewardPre<R> &q)
 {
     q.found_now = (R)fl.d_e <= c.threshold;
     q.last_gate = fl.idx_e + 1 == p.num_waypoints;
@@ -2101,10 +2131,21 @@ DN_DEV RewardPre<R> reward_entry(const DnParams &p, const DnConsts<R> &c, const 
     q.s_lin = sl.s; q.s_ang = sa.s;
     return q;
 }
+template <typename R>
+DN_DEV RewardPre<R> reward_entry(const DnParams &p, const DnConsts<R> &c, const FlightW<R> &fl, const Vec3R<R> &P4, const Vec3R<R> &P5)
+{
+    RewardPre<R> q;
+    reward_entry_core<R>(p, c, fl, q);
+    const Smooth<R> sl = smooth_term<R>(fl.vex, fl.vey, fl.vez, P4, R(0.7) * R(0.7));
+    const Smooth<R> sa = smooth_term<R>(fl.aex, fl.aey, fl.aez, P5, R(0.3) * R(0.3));
+    q.pen_lin = sl.pen; q.pen_ang = sa.pen;
+    q.s_lin = sl.s; q.s_ang = sa.s;
+    return q;
+}
 // reward_pose in two halves: the orientation term against the waypoint the taken branch refers to (reads the pose), and the assembly
 // of both value branches in the reference's order of additions (reads the entry-state terms) -- a kernel may run them on two waves.
-template <typename R>
-DN_DEV int reward_orientation(const DnParams &p, const R *s_tab, const Flight<R> &fl, const bool found_now, const bool last_gate)
+template <typename R, typename FL>
+DN_DEV int reward_orientation(const DnParams &p, const R *s_tab, const FL &fl, const bool found_now, const bool last_gate)
 {
     const int idx_ori = (found_now && !last_gate) ? fl.idx_e + 1 : fl.idx_e;
     return orientation_reward<R>(fl.fwx, fl.fwy, fl.fwz, fl.px, fl.py, fl.pz, s_tab + idx_ori * DN_T_STRIDE);
@@ -2121,8 +2162,8 @@ DN_DEV void reward_assemble(const RewardPre<R> &q, const int ori, R &r_normal, f
     if (q.pen_ang) r = r - q.s_ang;
     r_normal = r;
 }
-template <typename R>
-DN_DEV void reward_pose(const DnParams &p, const R *s_tab, const Flight<R> &fl, const RewardPre<R> &q, R &r_normal, float &r_found32)
+template <typename R, typename FL>
+DN_DEV void reward_pose(const DnParams &p, const R *s_tab, const FL &fl, const RewardPre<R> &q, R &r_normal, float &r_found32)
 {
     // The orientation term is evaluated once, against the waypoint the taken branch refers to.
     reward_assemble<R>(q, reward_orientation<R>(p, s_tab, fl, q.found_now, q.last_gate), r_normal, r_found32);
@@ -2259,13 +2300,15 @@ DN_DEV int ret_lo_byte(const double ep_ret, const float hi)
 // report_scalars: A7 select + Monitor + episode statistics + the scalar outputs; report_obs: the observation row(s) of
 // the step -- terminal_observation and the reset observation of a finished drone (quirk Q2), sensor noise, normaliser.
 // The two share only the verdict, so a kernel may run them on two waves; report_phase = both on one.
-template <typename R, bool REW>
+// FOUND_BIT: `d_e <= threshold` arrives as found_mail, from the wave that formed it for the reward (the four- / five-wave fused
+// kernels); fl.d_e is not read then.
+template <typename R, bool REW, bool FOUND_BIT = false>
 DN_DEV void report_scalars(const DnParams &p, const DnConsts<R> &c, const StepOut &out, const Flight<R> &fl, const Verdict<R> &v,
                            const R r_normal, const float r_found32, const unsigned li, const unsigned lane, const bool active,
-                           float4 &G4, float4 &G5, StatAcc &acc, RewNorm &rn)
+                           float4 &G4, float4 &G5, StatAcc &acc, RewNorm &rn, const bool found_mail = false)
 {
     const bool coll1 = v.coll1 != 0, terminated = v.terminated != 0, truncated = fl.truncated != 0;
-    const bool found_now = !coll1 && (R)fl.d_e <= c.threshold;
+    const bool found_now = !coll1 && (FOUND_BIT ? found_mail : (R)fl.d_e <= c.threshold);
     const bool is_done = found_now && fl.idx_e + 1 == p.num_waypoints;
     const int found = fl.idx_e + (found_now ? 1 : 0);
     const bool done = terminated || truncated;
@@ -3015,7 +3058,7 @@ template <typename R> DN_DEV void post_maila(MailA<R> &m, unsigned lane, const F
     m.f32[2][lane] = make_float4(ob.o[8], ob.o[9], ob.o[10], ob.o[11]);
     m.f32[3][lane] = make_float4(ob.o[12], ob.r_found32, f.d_e, __int_as_float(bits));
 }
-template <typename R> DN_DEV void take_maila(const MailA<R> &m, unsigned lane, Flight<R> &f, Verdict<R> &v, Observed<R> &ob)
+template <typename R> DN_DEV void take_maila(const MailA<R> &m, unsigned lane, Flight<R> &f, Verdict<R> &v, Observed<R> &ob, int *flag_word = nullptr)
 {
     ob.r_normal = m.f64[0][lane]; v.d_obs = m.f64[1][lane];
     const float4 a = m.f32[0][lane], b = m.f32[1][lane], c = m.f32[2][lane], d = m.f32[3][lane];
@@ -3025,6 +3068,21 @@ template <typename R> DN_DEV void take_maila(const MailA<R> &m, unsigned lane, F
     const int bits = __float_as_int(d.w);
     f.idx_e = bits & 0xFF; f.truncated = (bits >> 9) & 1; v.coll1 = (bits >> 10) & 1; v.terminated = (bits >> 11) & 1;
     f.vex = f.vey = f.vez = f.aex = f.aey = f.aez = 0.0f;     // prev_vel / prev_ang_v live on the aux wave
+    if (flag_word) *flag_word = bits;
+}
+// The four- / five-wave fused kernels: the observation wave holds the float32 words widened (FlightW) and has already formed
+// `d_e <= threshold` for the reward, so bit 12 of the flag word carries that compare and the d_e slot goes unused (the report wave's
+// report_scalars<.., FOUND_BIT = true> reads the bit).  Narrowing d_e for the slot would cost the conversion this saves.
+constexpr int DN_MAILA_FOUND_SHIFT = 12;
+template <typename R> DN_DEV void post_maila_found(MailA<R> &m, unsigned lane, const FlightW<R> &f, const Verdict<R> &v, const Observed<R> &ob,
+                                                   const bool found)
+{
+    m.f64[0][lane] = ob.r_normal; m.f64[1][lane] = v.d_obs;
+    const int bits = f.idx_e | (f.truncated << 9) | (v.coll1 << 10) | (v.terminated << 11) | ((int)found << DN_MAILA_FOUND_SHIFT);
+    m.f32[0][lane] = make_float4(ob.o[0], ob.o[1], ob.o[2], ob.o[3]);
+    m.f32[1][lane] = make_float4(ob.o[4], ob.o[5], ob.o[6], ob.o[7]);
+    m.f32[2][lane] = make_float4(ob.o[8], ob.o[9], ob.o[10], ob.o[11]);
+    m.f32[3][lane] = make_float4(ob.o[12], ob.r_found32, 0.0f, __int_as_float(bits));
 }
 
 // XOPT: the aux wave's thrust goes over as the float64 carriers with this step's rpm (what the ground-effect and drag
@@ -3224,7 +3282,9 @@ __global__ __launch_bounds__(3 * DN_BLOCK, NORM ? 2 : 3) void dn_step_many_3w_ke
 // -----------------------------------------------------------------------------------------------------
 template <typename R> struct MailL {      // L -> Q (and its flag word -> A): the linear half of the new state and the verdict
     R f64[4][DN_BLOCK];                   // position (3), Verdict.d_obs
-    float4 f32[2][DN_BLOCK];              // (vx, vy, vz, d_e), (vex, vey, vez, dprev_e)
+    // The float32 state words Q reads, WIDENED by L, which holds each of them as an R for its own step anyway: the value sent is exactly
+    // (R)(float32 word) -- never the double the word was rounded from -- so Q computes the bits it would compute from the float.
+    R wide[8][DN_BLOCK];                  // new velocity (3), entry velocity (3), d_e, dprev_e
     int flags[DN_BLOCK];                  // idx_e | just_found_e << 8 | truncated << 9 | coll1 << 10 | terminated << 11
 };
 template <typename R> struct MailG {      // A -> L (qnew) and A -> Q (the rest): the angular half and the attitude read-outs
@@ -3233,7 +3293,9 @@ template <typename R> struct MailG {      // A -> L (qnew) and A -> Q (the rest)
     R fw[3][DN_BLOCK];                    // forward vector of the new pose
     float4 eul[DN_BLOCK];                 // roll_num32, roll_den32, pitch32, yaw32
     float4 w[DN_BLOCK];                   // new angular velocity (float32 state words)
-    float4 we[DN_BLOCK];                  // entry angular velocity (prev_ang_v of the smoothness term)
+    // entry angular velocity (prev_ang_v of the smoothness term), WIDENED by A, which holds it as R for physics_angular_pre_terms: the
+    // value sent is exactly (R)(float32 word), so Q's smoothness term is the bits it would form from the float
+    R we[3][DN_BLOCK];
 };
 
 // NW = 5 (normaliser on, round 3): the report wave is cut in two.  A wave issues one instruction per ~7.5 cycles however idle its SIMD
@@ -3337,6 +3399,7 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
         block_lds_barrier(); MW_EDGE(1);                                   // P
         const R wp0[3] = {s_tab[DN_T_WP], s_tab[DN_T_WP + 1], s_tab[DN_T_WP + 2]};
         bool done_prev = false;
+        Vec3R<R> W2 = {(R)G2.x, (R)G2.y, (R)G2.z};                         // G2.xyz widened: formed once per word, mailed to Q, carried to the next step
 #pragma clang loop unroll(disable)
         for (int t = 0; t <= k_steps; ++t) {
             MW_ROLE_MARK("L");
@@ -3348,24 +3411,30 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
                 }
                 const GateRow<R> row_e = load_gate_row<R>(s_tab, unpack_meta(G3.w).idx);
                 const R fz = tmail[t & 1].v[0][lane];
-                const Lin<R> lin = physics_linear_col<R>(G0, G2, col, fz, R(0.0), R(0.0), R(0.0), false);
+                const Lin<R> lin = physics_linear_col<R>(G0, W2, col, fz, R(0.0), R(0.0), R(0.0), false);
                 Flight<R> fl;
                 flight_entry<R>(fl, G0, G2, G3, p.max_steps);
                 fl.px = lin.px; fl.py = lin.py; fl.pz = lin.pz;
                 fl.vx = (float)lin.vx; fl.vy = (float)lin.vy; fl.vz = (float)lin.vz;
+                const Vec3R<R> Wn = {(R)fl.vx, (R)fl.vy, (R)fl.vz};        // of the state WORD, not lin.v
                 fl.qx = fl.qy = fl.qz = R(0.0); fl.qw = R(1.0);            // the attitude belongs to A (no ground-contact term here)
                 fl.wx = fl.wy = fl.wz = 0.0f;
                 RulesMid<R> m;
                 const Verdict<R> v = rules_verdict<R>(p, c, s_tab, row_e, fl, G3, m);
                 MailL<R> &ml = maill[t & 1];
                 ml.f64[0][lane] = fl.px; ml.f64[1][lane] = fl.py; ml.f64[2][lane] = fl.pz; ml.f64[3][lane] = v.d_obs;
-                ml.f32[0][lane] = make_float4(fl.vx, fl.vy, fl.vz, fl.d_e);
-                ml.f32[1][lane] = make_float4(fl.vex, fl.vey, fl.vez, fl.dprev_e);
+                ml.wide[0][lane] = Wn.x; ml.wide[1][lane] = Wn.y; ml.wide[2][lane] = Wn.z;
+                ml.wide[3][lane] = W2.x; ml.wide[4][lane] = W2.y; ml.wide[5][lane] = W2.z;
+                ml.wide[6][lane] = (R)fl.d_e; ml.wide[7][lane] = (R)fl.dprev_e;      // the conversions rules_verdict makes
                 ml.flags[lane] = fl.idx_e | (fl.just_found_e << 8) | (fl.truncated << 9) | (v.coll1 << 10) | (v.terminated << 11);
                 float4 S0, S1, S2, S3;
                 rules_commit<R>(c, wp0, fl, m, G0, G3, b.g6, li, active, S0, S1, S2, S3);
                 G0 = S0; G2 = S2; G3.w = S3.w;
                 done_prev = v.terminated != 0 || fl.truncated != 0;
+                W2 = Wn;                                                   // = (R)G2.xyz: a finished drone restarts at rest
+                if (__ballot(done_prev) != 0ull) {
+                    if (done_prev) W2.x = W2.y = W2.z = R(0.0);
+                }
             }
             MW_BARRIER();                                                  // barrier t
         }
@@ -3392,12 +3461,14 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
                 }
             }
             if (t < k_steps) {
+                MailG<R> &mg = mailg[t & 1];
+                // first, so that the widened words do not stay live through the step (the conversions are physics_angular_pre_terms' own)
+                mg.we[0][lane] = (R)G3.x; mg.we[1][lane] = (R)G3.y; mg.we[2][lane] = (R)G3.z;
                 const R tx = tmail[t & 1].v[1][lane], ty = tmail[t & 1].v[2][lane], zt = tmail[t & 1].v[3][lane];
                 const Ang<R> ang = physics_angular_post<R>(physics_angular_pre_terms<R>(G1, G3, qt), tx, ty, zt);
                 Flight<R> fl;
                 fl.qx = ang.qx; fl.qy = ang.qy; fl.qz = ang.qz; fl.qw = ang.qw;
                 attitude_phase<R>(fl);
-                MailG<R> &mg = mailg[t & 1];
                 const float4 qn = make_float4((float)ang.qx, (float)ang.qy, (float)ang.qz, (float)ang.qw);
                 const float4 wn = make_float4((float)ang.wx, (float)ang.wy, (float)ang.wz, 0.0f);
                 qt = quat_terms<R>((R)qn.x, (R)qn.y, (R)qn.z, (R)qn.w);   // of the state word, as the next step reads it
@@ -3406,7 +3477,6 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
                 mg.fw[0][lane] = fl.fwx; mg.fw[1][lane] = fl.fwy; mg.fw[2][lane] = fl.fwz;
                 mg.eul[lane] = make_float4(fl.roll_num32, fl.roll_den32, fl.pitch32, fl.yaw32);
                 mg.w[lane] = wn;
-                mg.we[lane] = make_float4(G3.x, G3.y, G3.z, 0.0f);
                 G1 = qn; G3.x = wn.x; G3.y = wn.y; G3.z = wn.z;
             }
             MW_BARRIER();                                                  // barrier t
@@ -3418,8 +3488,13 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
             g3[0] = G3.x; g3[1] = G3.y; g3[2] = G3.z;
         }
     } else if (role == 2) {
-        float4 P4 = b.g4[li], P5 = b.g5[li];                               // .xyz: prev_vel, prev_ang_v
-        Rms rms;                                                           // never touched here: the observation leaves raw
+        // prev_vel, prev_ang_v (g4.xyz, g5.xyz): float32 state words, held widened for the launch -- they are last step's entry velocities,
+        // which arrive widened -- and narrowed (exactly) for the stores at the end
+        Vec3R<R> P4, P5;
+        {
+            const float4 g4 = b.g4[li], g5 = b.g5[li];
+            P4.x = (R)g4.x; P4.y = (R)g4.y; P4.z = (R)g4.z; P5.x = (R)g5.x; P5.y = (R)g5.y; P5.z = (R)g5.z;
+        }
         // the thrust chain lives here: with it on the report wave (its stores, the episode statistics, the normaliser) that wave was
         // the longest of the four and set the pace (16 384 drones: 1.17 us per step against 1.02 with it here)
         const float4 *act = reinterpret_cast<const float4 *>(io0.actions) + tile_base;
@@ -3443,37 +3518,43 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
                 const int u = t - 1;
                 const MailL<R> &ml = maill[u & 1];
                 const MailG<R> &mg = mailg[u & 1];
-                Flight<R> fl;
+                FlightW<R> fl;
                 Verdict<R> v;
                 fl.px = ml.f64[0][lane]; fl.py = ml.f64[1][lane]; fl.pz = ml.f64[2][lane]; v.d_obs = ml.f64[3][lane];
-                const float4 a0 = ml.f32[0][lane], a1 = ml.f32[1][lane];
-                fl.vx = a0.x; fl.vy = a0.y; fl.vz = a0.z; fl.d_e = a0.w;
-                fl.vex = a1.x; fl.vey = a1.y; fl.vez = a1.z; fl.dprev_e = a1.w;
+                fl.vx = ml.wide[0][lane]; fl.vy = ml.wide[1][lane]; fl.vz = ml.wide[2][lane];
+                fl.vex = ml.wide[3][lane]; fl.vey = ml.wide[4][lane]; fl.vez = ml.wide[5][lane];
+                fl.d_e = ml.wide[6][lane]; fl.dprev_e = ml.wide[7][lane];
                 const int fb = ml.flags[lane];
                 fl.idx_e = fb & 0xFF; fl.just_found_e = (fb >> 8) & 1; fl.truncated = (fb >> 9) & 1;
                 v.coll1 = (fb >> 10) & 1; v.terminated = (fb >> 11) & 1;
-                const float4 e = mg.eul[lane], wn = mg.w[lane], we = mg.we[lane];
+                const float4 e = mg.eul[lane], wn = mg.w[lane];
                 fl.qx = fl.qy = fl.qz = R(0.0); fl.qw = R(1.0);            // not read by the observation / reward (the attitude's read-outs came over)
                 fl.fwx = mg.fw[0][lane]; fl.fwy = mg.fw[1][lane]; fl.fwz = mg.fw[2][lane];
                 fl.roll_num32 = e.x; fl.roll_den32 = e.y; fl.pitch32 = e.z; fl.yaw32 = e.w;
                 fl.wx = wn.x; fl.wy = wn.y; fl.wz = wn.z;
-                fl.aex = we.x; fl.aey = we.y; fl.aez = we.z;
-                const Observed<R> ob = observe_phase<R, false, NOISE>(p, c, s_tab, fl, P4, P5, gid, sc0 + (unsigned long long)u, rms);
-                post_maila<R>(maila[u & 1], lane, fl, v, ob);
+                fl.aex = mg.we[0][lane]; fl.aey = mg.we[1][lane]; fl.aez = mg.we[2][lane];
+                // observe_phase<R, false, NOISE> on the widened words: the row, both reward candidates, the sensor noise -- in that order
+                Observed<R> ob;
+                observe_columns_lin<R>(p, c, fl, ob.o);
+                observe_columns_att<R>(fl, ob.o);
+                const RewardPre<R> pre = reward_entry<R>(p, c, fl, P4, P5);
+                reward_pose<R>(p, s_tab, fl, pre, ob.r_normal, ob.r_found32);
+                if (NOISE && p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, sc0 + (unsigned long long)u, 1u, ob.o);
+                post_maila_found<R>(maila[u & 1], lane, fl, v, ob, pre.found_now);
                 // prev_vel / prev_ang_v: _update_state_post_step (skipped on a terminated step, quirk Q5), zero after a reset
                 // (a terminated step is a finished one, so the old copies never survive: one select per word)
                 {
                     const bool fin = v.terminated != 0 || fl.truncated != 0;
-                    P4 = fin ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(fl.vex, fl.vey, fl.vez, 0.0f);
-                    P5 = fin ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(fl.aex, fl.aey, fl.aez, 0.0f);
+                    P4.x = fin ? R(0.0) : fl.vex; P4.y = fin ? R(0.0) : fl.vey; P4.z = fin ? R(0.0) : fl.vez;
+                    P5.x = fin ? R(0.0) : fl.aex; P5.y = fin ? R(0.0) : fl.aey; P5.z = fin ? R(0.0) : fl.aez;
                 }
             }
             MW_BARRIER();                                                  // barrier t
         }
         MW_EDGE(2);
-        if (active) {
+        if (active) {                                                      // every word is (R)(a float32): the narrowing is exact
             float *g4 = reinterpret_cast<float *>(b.g4 + li), *g5 = reinterpret_cast<float *>(b.g5 + li);
-            g4[0] = P4.x; g4[1] = P4.y; g4[2] = P4.z; g5[0] = P5.x; g5[1] = P5.y; g5[2] = P5.z;
+            g4[0] = (float)P4.x; g4[1] = (float)P4.y; g4[2] = (float)P4.z; g5[0] = (float)P5.x; g5[1] = (float)P5.y; g5[2] = (float)P5.z;
         }
     } else if (role == 4) {
         // ---- N (NW == 5): observation -> normaliser -> rows, the reset observation of a finished drone included
@@ -3526,13 +3607,14 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
                 Flight<R> fl;
                 Verdict<R> v;
                 Observed<R> ob;
-                take_maila<R>(maila[u & 1], lane, fl, v, ob);
+                int fb;
+                take_maila<R>(maila[u & 1], lane, fl, v, ob, &fb);
+                const bool found_mail = ((fb >> DN_MAILA_FOUND_SHIFT) & 1) != 0;       // Q's `d_e <= threshold` (post_maila_found)
                 const StepOut out = block_out(io0, tile_base, (long long)u * n, (long long)u * words);
-                if (NW == 5) report_scalars<R, false>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn);
-                else {
-                    if (NORM) normalize_obs(rms, ob.o);                        // the step observation (= terminal_observation)
-                    report_phase<R, NORM, NOISE, false, 2>(p, c, nullptr, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn);
-                }
+                if (NW != 5 && NORM) normalize_obs(rms, ob.o);             // the step observation (= terminal_observation)
+                report_scalars<R, false, true>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn, found_mail);
+                if (NW != 5)                                               // report_phase = the two back to back
+                    report_obs<R, NORM, NOISE, 2>(p, c, nullptr, out, fl.truncated != 0, v, ob.o, gid, sc, li, lane, rows, active, rms);
             }
             if (t <= k_steps) MW_BARRIER();                                // barrier t
         }
