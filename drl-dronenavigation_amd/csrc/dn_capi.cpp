@@ -307,29 +307,32 @@ int32_t init_state(dn_env *e, hipStream_t s)
     return DN_OK;
 }
 
-// The per-drone models, shallowest first (the order of the kernels' argument chain, dn_kernels.hip SensArg).  dn_destroy and the entry
-// points that carry none of them walk this table; a new model is one more row.
+// The per-drone models, one row per DnModelLevel above DN_M_NONE and in its order (dn_internal.h).  dn_destroy and the entry points that
+// carry none of them walk this table; a new model is one more level and one more row.
 struct ModelRow {
+    int level;
     void *(*slot)(const DnModels &);    // the pointer that owns the model's allocation, nullptr where it owns none
     bool (*on)(const DnModels &);
     const char *phrase, *enable;    // how a refusal names the model, and the entry point that turns it on
     const char *replay;             // what dn_eval_kinematics does that the model would falsify
 };
-const ModelRow MODELS[] = {
-    {[](const DnModels &m) -> void * { return m.dyn.dyn; }, [](const DnModels &m) { return m.dyn.dyn != nullptr; }, "the randomised dynamics",
+constexpr ModelRow MODELS[] = {
+    {DN_M_DYN, [](const DnModels &m) -> void * { return m.dyn.dyn; }, [](const DnModels &m) { return m.dyn.dyn != nullptr; }, "the randomised dynamics",
      "dn_enable_dynamics", "replays a given nominal-body transition"},
-    {[](const DnModels &m) -> void * { return m.wind.mean; }, [](const DnModels &m) { return m.wind.mean != nullptr; }, "the wind", "dn_enable_wind",
+    {DN_M_WIND, [](const DnModels &m) -> void * { return m.wind.mean; }, [](const DnModels &m) { return m.wind.mean != nullptr; }, "the wind", "dn_enable_wind",
      "replays a given still-air transition"},
-    {[](const DnModels &m) -> void * { return m.act.hist; }, [](const DnModels &m) { return m.act.hist != nullptr; }, "the actuator model",
+    {DN_M_ACT, [](const DnModels &m) -> void * { return m.act.hist; }, [](const DnModels &m) { return m.act.hist != nullptr; }, "the actuator model",
      "dn_enable_actuator", "replays a given transition"},
-    {[](const DnModels &m) -> void * { return m.sens.ring; }, [](const DnModels &m) { return m.sens.ring != nullptr; }, "the sensor model",
+    {DN_M_SENS, [](const DnModels &m) -> void * { return m.sens.ring; }, [](const DnModels &m) { return m.sens.ring != nullptr; }, "the sensor model",
      "dn_enable_sensor", "reports the observation of the given transition"},
     // the rows are the caller's memory: nothing to free
-    {[](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.priv.groups != 0; }, "the privileged observations",
+    {DN_M_PRIV, [](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.priv.groups != 0; }, "the privileged observations",
      "dn_enable_privileged", "writes no privileged rows"},
-    {[](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.goal.on != 0; }, "the goal observations", "dn_enable_goal",
+    {DN_M_GOAL, [](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.goal.on != 0; }, "the goal observations", "dn_enable_goal",
      "writes no goal rows"},
 };
+constexpr bool models_follow_levels(int k = 0) { return k == DN_M_COUNT - 1 || (MODELS[k].level == k + 1 && models_follow_levels(k + 1)); }
+static_assert(sizeof MODELS / sizeof MODELS[0] == DN_M_COUNT - 1 && models_follow_levels(), "MODELS[]: one row per DnModelLevel, in its order");
 
 // DN_OK, or the refusal of entry point `who`, whose kernels carry no model, for the first model that is on.  `instead` names the calls
 // that do carry it; nullptr = dn_eval_kinematics, which has a reason per model and no alternative.

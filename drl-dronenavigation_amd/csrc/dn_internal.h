@@ -3,7 +3,9 @@
 #define DN_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#ifdef __HIP__      // DN_KLAUNCH's hipExtLaunchKernelGGL: HIP translation units only (a plain C++ host compiler cannot parse the header)
 #include <hip/hip_ext.h>
+#endif
 #include <stdint.h>
 
 #include "../../include/dronenav.h"
@@ -116,10 +118,17 @@ struct DnParams {
     DnConsts<float> c32;
 };
 
+// The per-drone models as one chain, shallowest first: the one statement of their order.  A step launch has ONE level, the deepest model
+// that is on (dn_model_level below); the one-wave option kernel of level M (dn_step_many_1w_kernel<..., M>) carries every model up to M,
+// each switched on or off at run time by its null pointers, and takes the first M slices of the argument chain
+// DnDyn : DnWind : DnAct : DnSens : DnPriv : DnGoal (dn_kernels.hip StepArg) as its last argument.  DN_M_NONE is the plain kernel: that
+// argument is an empty struct.  The structs below and MODELS[] (dn_capi.cpp) follow this order.
+enum DnModelLevel { DN_M_NONE = 0, DN_M_DYN, DN_M_WIND, DN_M_ACT, DN_M_SENS, DN_M_PRIV, DN_M_GOAL, DN_M_COUNT };
+
 // Per-drone dynamics randomisation (dn_enable_dynamics): the scale factors of the simulated body and how they are drawn.  Not a field of
 // DnParams: DnParams is the first argument of every step kernel, and growing it would move every later kernel argument (a different
-// instruction stream for every kernel).  It is the last argument of the kernels that read it: the one-wave step kernels instantiated with
-// the scales (dn_step_many_1w_kernel<..., DYN = true>) and the reset kernel.
+// instruction stream for every kernel).  It is the last argument of the kernels that read it: the one-wave step kernels of a level
+// >= DN_M_DYN and the reset kernel.
 struct DnDyn {
     float4 *dyn;            // [N] s_m, s_I, s_kf, s_km; nullptr = dynamics not enabled (the nominal cf2x body)
     float lo[4], hi[4];     // scale ranges of the draws, in the order of the float4
@@ -128,8 +137,8 @@ struct DnDyn {
 };
 
 // Per-drone wind (dn_enable_wind): a steady part wbar drawn per episode and an Ornstein-Uhlenbeck gust g, both world frame, m/s.  Not a
-// field of DnParams for the same reason as DnDyn; it travels with DnDyn in the last argument of the one-wave step kernels instantiated with
-// the wind (dn_step_many_1w_kernel<..., DYN = true, WIND = true>) and as the last argument of the reset kernel.
+// field of DnParams for the same reason as DnDyn; it travels with DnDyn in the last argument of the one-wave step kernels of a level
+// >= DN_M_WIND and as the last argument of the reset kernel.
 struct DnWind {
     float4 *mean;           // [N] wbar (x, y, z, 0); nullptr = wind not enabled
     float4 *gust;           // [N] g (x, y, z, 0): mean + N of the same allocation
@@ -144,8 +153,7 @@ struct DnWind {
 
 // Per-drone actuator model (dn_enable_actuator): command latency (an integer number of control steps) and a first-order motor lag on the
 // rotor speeds.  Not a field of DnParams for the same reason as DnDyn; it travels behind DnDyn and DnWind in the last argument of the
-// one-wave step kernels instantiated with it (dn_step_many_1w_kernel<..., DYN = true, WIND = true, ACT = true>) and as the last argument
-// of the reset kernel.  The four arrays are one allocation, hist first.
+// one-wave step kernels of a level >= DN_M_ACT and as the last argument of the reset kernel.  The four arrays are one allocation, hist first.
 struct DnAct {
     float4 *hist;           // [N][8] hist[8 i + j] = the action commanded j + 1 vector steps ago; nullptr = actuator not enabled
     float4 *rpm;            // [N] effective rotor speeds r
@@ -161,8 +169,7 @@ struct DnAct {
 
 // Per-drone sensor model (dn_enable_sensor): the observation row delivered to the normaliser / the output is the pre-normaliser row of d
 // control steps ago plus a per-episode bias.  Not a field of DnParams for the same reason as DnDyn; it travels behind DnDyn, DnWind and DnAct
-// in the last argument of the one-wave step kernels instantiated with it (dn_step_many_1w_kernel<..., ACT = true, SENS = true>) and as the
-// last argument of the reset kernel.  The three arrays are one allocation, ring first: (16 * 64 + 64 + 4) = 1092 bytes per drone.
+// in the last argument of the one-wave step kernels of a level >= DN_M_SENS and as the last argument of the reset kernel.  The three arrays are one allocation, ring first: (16 * 64 + 64 + 4) = 1092 bytes per drone.
 #define DN_SENS_SLOTS 16    // ring depth: a power of two >= DN_MAX_LATENCY + 1
 struct DnSens {
     float4 *ring;           // [16][4][N]: quad q of the pre-bias row measured at vector step sc sits at ring[(((sc + base) & 15) * 4 + q) * N + i]
@@ -178,8 +185,7 @@ struct DnSens {
 };
 
 // Privileged observations (dn_enable_privileged): the true observation and the four models' current values, one row of DN_PRIV_DIM float32
-// per drone and step, written by the step kernels of the deepest family (dn_step_many_1w_kernel<..., SENS = true, PRIV = true>, argument
-// PrivArg = SensArg + DnPriv) and by the reset kernel.  It owns no memory: the rows are the caller's (dn_bind_privileged).
+// per drone and step, written by the step kernels of a level >= DN_M_PRIV (argument PrivArg = SensArg + DnPriv) and by the reset kernel.  It owns no memory: the rows are the caller's (dn_bind_privileged).
 struct DnPriv {
     float *rows;            // [cap][N][DN_PRIV_DIM] step rows, step-major; nullptr = unbound (nothing is written)
     float *term;            // the terminal rows, same shape, or nullptr
@@ -189,8 +195,7 @@ struct DnPriv {
 };
 
 // Goal observations (dn_enable_goal): the vector to the current target waypoint and the segment after it, one row of DN_GOAL_DIM float32
-// per drone and step, written by the step kernels of the deepest family (dn_step_many_1w_kernel<..., PRIV = true, GOAL = true>, argument
-// GoalArg = PrivArg + DnGoal) and by the reset kernel.  It owns no memory: the rows are the caller's (dn_bind_goal).
+// per drone and step, written by the step kernels of level DN_M_GOAL (argument GoalArg = PrivArg + DnGoal) and by the reset kernel.  It owns no memory: the rows are the caller's (dn_bind_goal).
 struct DnGoal {
     float *rows;            // [cap][N][DN_GOAL_DIM] step rows, step-major; nullptr = unbound (nothing is written)
     float *term;            // the terminal rows, same shape, or nullptr
@@ -200,8 +205,8 @@ struct DnGoal {
 };
 
 // The per-drone models as the host carries them (dn_env, the launchers).  The kernels take them as before: the reset kernel as one argument
-// each, the option step kernels as the slice of the chain GoalArg : PrivArg : SensArg : ActArg : WindArg : DnDyn (dn_kernels.hip) their
-// family reads.  A model that is off is its value-initialised struct (null pointers, groups 0, on 0).
+// each, the option step kernels as the slice of the chain (DnModelLevel above) their level reads.  A model that is off is its
+// value-initialised struct (null pointers, groups 0, on 0).
 struct DnModels {
     DnDyn dyn;
     DnWind wind;
@@ -210,6 +215,17 @@ struct DnModels {
     DnPriv priv;
     DnGoal goal;
 };
+// The level a step launch takes: the deepest model that is on.  The two row writers count only when enabled AND bound: unbound, nothing
+// would be written, and the level below serves.
+inline int dn_model_level(const DnModels &m)
+{
+    if (m.goal.on && m.goal.rows) return DN_M_GOAL;
+    if (m.priv.groups && m.priv.rows) return DN_M_PRIV;
+    if (m.sens.ring) return DN_M_SENS;
+    if (m.act.hist) return DN_M_ACT;
+    if (m.wind.mean) return DN_M_WIND;
+    return m.dyn.dyn ? DN_M_DYN : DN_M_NONE;
+}
 
 // dn_set_launch_events (ABI 8): the step kernel of the next dn_step / dn_step_many launch is dispatched with these two hipEvents attached to
 // its own dispatch packet (hipExtLaunchKernelGGL) -- they time the kernel itself, like a profiler's kernel trace, where a pair of
@@ -223,8 +239,8 @@ extern thread_local hipEvent_t dn_tl_ev_start, dn_tl_ev_stop;
     } while (0)
 
 int dn_norm_exact_compiled_in();      // 1 in libdronenav_exact.so (-DDN_NORM_EXACT=1: the normaliser's float64 output stage), else 0
-// m: the per-drone models of the env.  With one of them on, the launch takes the one-wave option kernel of the deepest enabled family
-// (dynamics < wind < actuator < sensor < privileged rows, bound < goal rows, bound; the shallower ones ride along, on or off), whatever `waves` says.
+// m: the per-drone models of the env.  With one of them on, the launch takes the one-wave option kernel of dn_model_level(*m) (the
+// shallower models ride along, on or off), whatever `waves` says.
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnModels *m = nullptr);
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream);   // dn_kernels_mw.hip
 hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t stream, const DnModels *m = nullptr);

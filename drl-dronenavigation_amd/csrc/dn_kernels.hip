@@ -1064,12 +1064,13 @@ template <typename R> DN_DEV float lag_step(const float a, const float r, const 
     const R bc = ((R)1 - (R)a) * (R)c;
     return (float)(ar + bc);
 }
-// ACT (the one-wave kernels with dn_enable_actuator): lag_on (launch-uniform) = the motor lag is on, ActionType.THRUST only; *lag is
-// always the kernel's own register copy (a pointer that may be null would pin it to scratch)
-template <bool NOISE, bool ACT = false, typename R = double>
+// M (DnModelLevel) >= DN_M_ACT (the one-wave kernels with dn_enable_actuator): lag_on (launch-uniform) = the motor lag is on,
+// ActionType.THRUST only; *lag is always the kernel's own register copy (a pointer that may be null would pin it to scratch)
+template <bool NOISE, int M = DN_M_NONE, typename R = double>
 DN_DEV ThrustX thrust_phase_x(const DnParams &p, unsigned long long gid, unsigned long long step_count, const float4 A, Extras &x,
                               const PidCtx *pid = nullptr, ActLag *lag = nullptr, const bool lag_on = false)
 {
+    constexpr bool ACT = M >= DN_M_ACT;
     float a[4] = {A.x, A.y, A.z, A.w};
     if (NOISE && p.act_noise_sigma > 0.0f) add_act_noise(p, gid, step_count, a);
     ThrustX t;
@@ -1729,13 +1730,14 @@ DN_DEV void goal_observe(const GoalCtx<R> &x, const DnParams &p, const DnConsts<
     if (x.active && dst) goal_store<R>(*x.g, p, c, x.tab, dst, y, x.done ? x.tidx : x.idx);
 }
 
-// DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
-// WIND (with DYN): the wind force *wf over the mass of *dk joins the extra accelerations
-template <typename R, typename TH = Thrust, bool XOPT = false, bool DYN = false, bool WIND = false>
+// M (DnModelLevel) >= DN_M_DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
+// M >= DN_M_WIND: the wind force *wf over the mass of *dk joins the extra accelerations
+template <typename R, typename TH = Thrust, bool XOPT = false, int M = DN_M_NONE>
 DN_DEV Flight<R> physics_phase(const TH &th, const float4 G0, const float4 G1, const float4 G2, const float4 G3,
                                const int max_steps, const Extras *x = nullptr, const DynK<R> *dk = nullptr, const WindF<R> *wf = nullptr)
 {
-    static_assert(!WIND || (DYN && XOPT), "the wind rides on the option kernels with the body terms");
+    static_assert(M == DN_M_NONE || XOPT, "the per-drone models ride on the option kernels");
+    constexpr bool DYN = M >= DN_M_DYN, WIND = M >= DN_M_WIND;
     Flight<R> fl;
     flight_entry<R>(fl, G0, G2, G3, max_steps);
     // rotor thrusts along body z at the prop offsets (+,-) (-,-) (-,+) (+,+) * 0.028 (cf2x.urdf:42,54,66,78)
@@ -2175,14 +2177,15 @@ DN_DEV void reward_candidates(const DnParams &p, const DnConsts<R> &c, const R *
     const RewardPre<R> q = reward_entry<R>(p, c, fl, G4, G5);
     reward_pose<R>(p, s_tab, fl, q, r_normal, r_found32);
 }
-// SENS (the one-wave kernels with dn_enable_sensor): *sx is the kernel's own register copy; the delivered row replaces the true one
-// PRIV (with SENS, dn_enable_privileged): the true row leaves for the privileged rows from the registers that hold it, before the noise
-// GOAL (with PRIV, dn_enable_goal): the goal row is computed from the delivered row, before the normaliser
-template <typename R, bool NORM, bool NOISE, bool SENS = false, bool PRIV = false, bool GOAL = false>
+// M (DnModelLevel) >= DN_M_SENS (one-wave kernels with dn_enable_sensor): *sx is the kernel's own register copy; the delivered row replaces the true one
+// M >= DN_M_PRIV (dn_enable_privileged): the true row leaves for the privileged rows from the registers that hold it, before the noise
+// M >= DN_M_GOAL (dn_enable_goal): the goal row is computed from the delivered row, before the normaliser
+template <typename R, bool NORM, bool NOISE, int M = DN_M_NONE>
 DN_DEV Observed<R> observe_phase(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const Flight<R> &fl,
                                  const float4 G4, const float4 G5, const unsigned long long gid, const unsigned long long step_count,
                                  Rms &rms, SensCtx *sx = nullptr, const PrivCtx *px = nullptr, const GoalCtx<R> *gx = nullptr)
 {
+    constexpr bool SENS = M >= DN_M_SENS, PRIV = M >= DN_M_PRIV, GOAL = M >= DN_M_GOAL;
     Observed<R> ob;
     observe_columns<R>(p, c, fl, ob.o);
     if constexpr (PRIV) priv_true_obs(*px, ob.o);
@@ -2370,12 +2373,13 @@ DN_DEV void report_scalars(const DnParams &p, const DnConsts<R> &c, const StepOu
     }
     if (out.done_word && lane == 0) *out.done_word = done_ballot;
 }
-template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false, bool SENS = false, bool PRIV = false, bool GOAL = false>
+template <typename R, bool NORM, bool NOISE, int TILE, bool SPAWN = false, int M = DN_M_NONE>
 DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const bool truncated,
                        const Verdict<R> &v, float *o, const unsigned long long gid, const unsigned long long step_count,
                        const unsigned li, const unsigned lane, const unsigned rows, const bool active, Rms &rms, SensCtx *sx = nullptr,
                        const PrivCtx *px = nullptr, const GoalCtx<R> *gx = nullptr)
 {
+    constexpr bool SENS = M >= DN_M_SENS, PRIV = M >= DN_M_PRIV, GOAL = M >= DN_M_GOAL;
     const bool done = v.terminated != 0 || truncated;
     const unsigned long long done_mask = __ballot(done && active);
     if (done_mask != 0ull) {
@@ -2413,7 +2417,7 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
     else if (TILE == 1) tile_park(s_tile, lane, o);        // streamed out by the caller one step later
     else store_obs_tile(s_tile, out.obs, rows, lane, o);
 }
-template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false, bool SENS = false, bool PRIV = false, bool GOAL = false>
+template <typename R, bool NORM, bool NOISE, bool REW, int TILE = 0, bool SPAWN = false, int M = DN_M_NONE>
 DN_DEV void report_phase(const DnParams &p, const DnConsts<R> &c, float *s_tile, const StepOut &out, const Flight<R> &fl,
                          const Verdict<R> &v, Observed<R> &ob, const unsigned long long gid, const unsigned long long step_count,
                          const unsigned li, const unsigned lane, const unsigned rows, const bool active,
@@ -2421,7 +2425,7 @@ DN_DEV void report_phase(const DnParams &p, const DnConsts<R> &c, float *s_tile,
                          const GoalCtx<R> *gx = nullptr)
 {
     report_scalars<R, REW>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn);
-    report_obs<R, NORM, NOISE, TILE, SPAWN, SENS, PRIV, GOAL>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active,
+    report_obs<R, NORM, NOISE, TILE, SPAWN, M>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active,
                                                               rms, sx, px, gx);
 }
 
@@ -2438,7 +2442,7 @@ DN_DEV BlockState block_state(const DnState &st, long long tile_base)
 }
 
 // thrust + physics of one step; the XOPT kernels take the float64 carriers and the optional force terms (N4)
-template <typename R, bool NOISE, bool XOPT, bool DYN = false, bool WIND = false, bool ACT = false>
+template <typename R, bool NOISE, bool XOPT, int M = DN_M_NONE>
 DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long long sc, const float4 A, const float4 G0, const float4 G1,
                      const float4 G2, const float4 G3, const float4 G7, float4 &rpm_now, double *pid_st = nullptr,
                      const DynK<R> *dk = nullptr, const WindF<R> *wf = nullptr, ActLag *lag = nullptr, const bool lag_on = false)
@@ -2448,9 +2452,9 @@ DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long lo
         x.last = G7;
         PidCtx cx;
         cx.G0 = G0; cx.G1 = G1; cx.G2 = G2; cx.st = pid_st;
-        const ThrustX th = thrust_phase_x<NOISE, ACT, R>(p, gid, sc, A, x, pid_st ? &cx : nullptr, lag, lag_on);
+        const ThrustX th = thrust_phase_x<NOISE, M, R>(p, gid, sc, A, x, pid_st ? &cx : nullptr, lag, lag_on);
         rpm_now = make_float4((float)x.rpm[0], (float)x.rpm[1], (float)x.rpm[2], (float)x.rpm[3]);
-        return physics_phase<R, ThrustX, true, DYN, WIND>(th, G0, G1, G2, G3, p.max_steps, &x, dk, wf);
+        return physics_phase<R, ThrustX, true, M>(th, G0, G1, G2, G3, p.max_steps, &x, dk, wf);
     }
     const Thrust th = thrust_phase<NOISE>(p, gid, sc, A);
     return physics_phase<R>(th, G0, G1, G2, G3, p.max_steps);
@@ -2519,50 +2523,34 @@ DN_DEV float4 sample_action(const DnStepIO &io, const unsigned long long gid, co
 // -----------------------------------------------------------------------------------------------------
 // ONE = true is the single-step launch (dn_step): k_steps is the constant 1, and the kernel gets its own name in
 // profiles (dn_step_many_*_kernel<..., true> = one control step per launch, <..., false> = k_arg steps per launch).
-// DYN (with XOPT): the per-drone body scales of dn_enable_dynamics, passed as the last argument.  Without them that argument is an empty
-// struct, which leaves the offsets of the kernel's other arguments -- and with them every instruction of the kernel -- as they were.
-// WIND (with DYN and XOPT): the argument also carries dn_enable_wind's state (WindArg); its scale pointer is null when dynamics are off,
-// and the body is then the nominal one (scales of 1).
+// M (DnModelLevel, dn_internal.h; with XOPT): the kernel carries the per-drone models up to level M and takes their state as its last
+// argument, StepArg<M>: the first M slices of the chain below.  A model shallower than M rides along, switched off by its null pointers.
+//   DN_M_NONE  an empty struct, which leaves the offsets of the kernel's other arguments -- and with them every instruction -- as they were
+//   DN_M_DYN   the per-drone body scales of dn_enable_dynamics
+//   DN_M_WIND  + dn_enable_wind's state; the scale pointer is null when dynamics are off, and the body is then the nominal one (scales of 1)
+//   DN_M_ACT   + dn_enable_actuator's state; the wind's pointers are null when the wind is off (zero wind, no draws)
+//   DN_M_SENS  + dn_enable_sensor's state; the actuator's pointers are null when it is off (latency 0, no lag, nothing drawn or stored)
+//   DN_M_PRIV  + dn_bind_privileged's rows; the sensor's pointers are null when the sensor model is off (latency 0, no bias, no ring)
+//   DN_M_GOAL  + dn_bind_goal's rows; the privileged rows are off (groups 0, null pointers) unless they are enabled and bound too
 template <bool DYN> struct DynArg : DnDyn {};
 template <> struct DynArg<false> {};
-struct WindArg : DnDyn {
-    DnWind w;
-};
-// ACT (with WIND, DYN and XOPT): the argument carries dn_enable_actuator's state as well (ActArg); the wind's pointers are null when the wind
-// is off (zero wind, no draws), as the scale pointer is without dynamics.
-struct ActArg : WindArg {
-    DnAct a;
-};
-// SENS (with ACT, WIND, DYN and XOPT): the argument carries dn_enable_sensor's state as well (SensArg); the actuator's pointers are null when
-// the actuator is off (latency 0, no lag, nothing drawn or stored).
-struct SensArg : ActArg {
-    DnSens s;
-};
-// PRIV (with SENS, ACT, WIND, DYN and XOPT): the argument carries dn_bind_privileged's rows as well (PrivArg); the sensor's pointers are null
-// when the sensor model is off (latency 0, no bias, no ring).
-struct PrivArg : SensArg {
-    DnPriv pv;
-};
-// GOAL (with PRIV, SENS, ACT, WIND, DYN and XOPT): the argument carries dn_bind_goal's rows as well (GoalArg); the privileged rows are off
-// (groups 0, null pointers) unless they are enabled and bound too.
-struct GoalArg : PrivArg {
-    DnGoal gl;
-};
-template <bool DYN, bool WIND, bool ACT = false, bool SENS = false, bool PRIV = false, bool GOAL = false> struct StepArg { using type = DynArg<DYN>; };
-template <> struct StepArg<true, true, false, false, false, false> { using type = WindArg; };
-template <> struct StepArg<true, true, true, false, false, false> { using type = ActArg; };
-template <> struct StepArg<true, true, true, true, false, false> { using type = SensArg; };
-template <> struct StepArg<true, true, true, true, true, false> { using type = PrivArg; };
-template <> struct StepArg<true, true, true, true, true, true> { using type = GoalArg; };
-template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, bool DYN = false, bool WIND = false, bool ACT = false,
-          bool SENS = false, bool PRIV = false, bool GOAL = false>
-__global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg,
-                                                                   const typename StepArg<DYN, WIND, ACT, SENS, PRIV, GOAL>::type dy)
+struct WindArg : DnDyn { DnWind w; };
+struct ActArg : WindArg { DnAct a; };
+struct SensArg : ActArg { DnSens s; };
+struct PrivArg : SensArg { DnPriv pv; };
+struct GoalArg : PrivArg { DnGoal gl; };
+template <int M> struct StepArg { using type = DynArg<false>; };
+template <> struct StepArg<DN_M_DYN> { using type = DynArg<true>; };
+template <> struct StepArg<DN_M_WIND> { using type = WindArg; };
+template <> struct StepArg<DN_M_ACT> { using type = ActArg; };
+template <> struct StepArg<DN_M_SENS> { using type = SensArg; };
+template <> struct StepArg<DN_M_PRIV> { using type = PrivArg; };
+template <> struct StepArg<DN_M_GOAL> { using type = GoalArg; };
+template <typename R, bool NORM, bool NOISE, bool ONE, bool XOPT, bool SAMPLE = false, int M = DN_M_NONE>
+__global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParams p, const DnStepIO io0, const int k_arg, const typename StepArg<M>::type dy)
 {
-    static_assert(!GOAL || PRIV, "the goal rows ride on the option kernels with the privileged rows");
-    static_assert(!ACT || (WIND && DYN && XOPT && !SAMPLE), "the actuator rides on the option kernels with the body terms and the wind");
-    static_assert(!SENS || ACT, "the sensor model rides on the option kernels with the actuator");
-    static_assert(!PRIV || SENS, "the privileged rows ride on the option kernels with the sensor model");
+    static_assert(M == DN_M_NONE || (M < DN_M_COUNT && XOPT && !SAMPLE), "the per-drone models ride on the option kernels, which do not sample");
+    constexpr bool DYN = M >= DN_M_DYN, WIND = M >= DN_M_WIND, ACT = M >= DN_M_ACT, SENS = M >= DN_M_SENS, PRIV = M >= DN_M_PRIV, GOAL = M >= DN_M_GOAL;
     const int k_steps = ONE ? 1 : k_arg;
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -2670,8 +2658,8 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         if constexpr (PRIV) {                           // the rotor speeds this step is entered with (the terminal row's)
             pr.r_entry[0] = lag.r[0]; pr.r_entry[1] = lag.r[1]; pr.r_entry[2] = lag.r[2]; pr.r_entry[3] = lag.r[3];
         }
-        Flight<R> fl = fly<R, NOISE, XOPT, DYN, WIND, ACT>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr,
-                                                           DYN ? &dk : nullptr, WIND ? &wf : nullptr, &lag, lag_on);
+        Flight<R> fl = fly<R, NOISE, XOPT, M>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr, DYN ? &dk : nullptr,
+                                              WIND ? &wf : nullptr, &lag, lag_on);
         const float4 G0e = G0, G3e = G3;
         int *idx_v = nullptr;
         if constexpr (GOAL) idx_v = &gr.x.tidx;
@@ -2728,9 +2716,9 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         }
         attitude_phase<R>(fl);
         if constexpr (SENS) sx.k = unpack_meta(G3e.w).steps + 1;    // control steps of the episode flown once this step is over
-        Observed<R> ob = observe_phase<R, NORM, NOISE, SENS, PRIV, GOAL>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx, px, gx);
-        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, SENS, PRIV, GOAL>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc,
-                                                                      rms, rn, &sx, px, gx);
+        Observed<R> ob = observe_phase<R, NORM, NOISE, M>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx, px, gx);
+        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, M>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn,
+                                                       &sx, px, gx);
         if constexpr (PRIV) {
             // the step row's parameters: what the getters would return after this step (a restarted drone: the new episode's draws)
             if (active) {
@@ -4759,6 +4747,14 @@ template <typename F, typename... Rest> void dn_bools(F &&f, bool b, Rest... res
     else dn_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 template <typename F32> using real_t = std::conditional_t<F32::value, float, double>;
+// A run-time model level above DN_M_NONE to a compile-time one, likewise: calls f(std::integral_constant<int, level>{})
+template <int M = DN_M_DYN, typename F> void dn_level(F &&f, int level)
+{
+    if constexpr (M < DN_M_COUNT) {
+        if (level == M) f(std::integral_constant<int, M>{});
+        else dn_level<M + 1>(f, level);
+    }
+}
 
 // What every step launch needs, worked out once per launcher.
 struct StepLaunch {
@@ -4828,14 +4824,12 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 #endif
 #elif DN_TU == 1
 namespace {
-// The one-wave option kernel of one family of per-drone models (dn_enable_*): DYN always, then WIND, ACT, SENS, PRIV, GOAL in that order;
-// `arg` is the slice of the GoalArg chain the family's kernels take.
-template <bool WIND, bool ACT, bool SENS, bool PRIV = false, bool GOAL = false>
-void launch_models(const StepLaunch &L, const typename StepArg<true, WIND, ACT, SENS, PRIV, GOAL>::type &arg)
+// The one-wave option kernel of model level M (dn_enable_*); `arg` is the slice of the GoalArg chain the level's kernels take.
+template <int M> void launch_models(const StepLaunch &L, const typename StepArg<M>::type &arg)
 {
     dn_bools([&](auto F32, auto NORM, auto NOISE, auto ONE) {
-        DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, ONE, true, false, true, WIND, ACT, SENS, PRIV, GOAL>), L.grid,
-                   dim3(DN_BLOCK), 0, L.stream, L.p, L.io, L.k, arg);
+        DN_KLAUNCH((dn_step_many_1w_kernel<real_t<decltype(F32)>, NORM, NOISE, ONE, true, false, M>), L.grid, dim3(DN_BLOCK), 0, L.stream, L.p,
+                   L.io, L.k, arg);
     }, L.f32, L.norm, L.noise, L.k == 1);
 }
 }  // namespace
@@ -4843,29 +4837,22 @@ void launch_models(const StepLaunch &L, const typename StepArg<true, WIND, ACT, 
 hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream, const DnModels *m)
 {
     const StepLaunch L(p, io, k, f32, stream);
-    const bool priv = m && m->priv.groups && m->priv.rows;      // enabled AND bound: unbound, nothing is written and the family below serves
-    const bool goal = m && m->goal.on && m->goal.rows;          // likewise
-    if (m && (m->dyn.dyn || m->wind.mean || m->act.hist || m->sens.ring || priv || goal)) {
-        // a model is on: the deepest enabled family's kernel, whatever `waves` says.  A model that is off rides along as its
+    const int level = m ? dn_model_level(*m) : DN_M_NONE;
+    if (level != DN_M_NONE) {
+        // a model is on: the kernel of the deepest one's level, whatever `waves` says.  A model that is off rides along as its
         // value-initialised struct (null pointers): the nominal body, still air, no latency, no bias.
         if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels carry no model (the C ABI refuses them first)
+        const bool priv = m->priv.groups && m->priv.rows, goal = level == DN_M_GOAL;    // rows are written where enabled AND bound
         GoalArg sa;
         static_cast<DnDyn &>(sa) = m->dyn;
-        sa.w = m->wind;
-        sa.a = m->act;
-        sa.s = m->sens;
-        sa.pv = m->priv;
-        sa.gl = m->goal;
+        sa.w = m->wind; sa.a = m->act; sa.s = m->sens; sa.pv = m->priv; sa.gl = m->goal;
         if (priv && k > m->priv.cap) return hipErrorInvalidValue;   // the C ABI refuses it first
-        if (goal) {
-            if (k > m->goal.cap) return hipErrorInvalidValue;       // likewise
-            if (!priv) sa.pv = DnPriv{};                            // enabled but unbound: this family writes no privileged rows either
-            launch_models<true, true, true, true, true>(L, sa);
-        } else if (priv) launch_models<true, true, true, true>(L, sa);
-        else if (m->sens.ring) launch_models<true, true, true>(L, sa);
-        else if (m->act.hist) launch_models<true, true, false>(L, sa);
-        else if (m->wind.mean) launch_models<true, false, false>(L, sa);
-        else launch_models<false, false, false>(L, DynArg<true>{static_cast<const DnDyn &>(sa)});
+        if (goal && k > m->goal.cap) return hipErrorInvalidValue;   // likewise
+        if (goal && !priv) sa.pv = DnPriv{};                        // enabled but unbound: this level writes no privileged rows either
+        dn_level([&](auto M) {
+            if constexpr (decltype(M)::value == DN_M_DYN) launch_models<DN_M_DYN>(L, DynArg<true>{static_cast<const DnDyn &>(sa)});
+            else launch_models<decltype(M)::value>(L, sa);
+        }, level);
     } else if (waves == 3 && (io.mean || k == 1))       // dn_step / dn_step_sampled on three waves cut by dependency (plain configuration; the caller checked)
         dn_bools([&](auto F32, auto NORM, auto NOISE, auto SAMPLE) {
             DN_KLAUNCH((dn_step_pqx_kernel<real_t<decltype(F32)>, NORM, NOISE, SAMPLE>), L.grid, dim3(3 * DN_BLOCK), 0, stream, p, io);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the device code of two builds the same?  For a host-only change (launchers, the C ABI) the answer must be yes.
 
-    python profiles/device_code_diff.py OLD/csrc NEW/csrc [--new-template-arg]
+    python profiles/device_code_diff.py OLD/csrc NEW/csrc [--new-template-arg | --model-level]
 
 For every object with a gfx950 code object in both directories: extracts the code object (llvm-objdump --offloading), lists its FUNC
 symbols (llvm-readelf -s --wide), disassembles it (llvm-objdump -d), splits the text by symbol and strips the address and encoding
@@ -13,6 +13,14 @@ A kernel that exists on the new side only is compared with the old kernel of the
 and the last XT<n>_E of a dependent argument type such as StepArg<...>::type), where the old side has one.  Two things that move with the
 code object's layout and the symbol's name, not with the kernel, are masked on both sides: the immediates of the s_add_u32 / s_addc_u32
 pair after an s_getpc_b64 (pc-relative data offsets) and the symbol names inside <...> branch-target annotations.
+
+--model-level: for the change that names dn_step_many_1w_kernel's model family by one level.  An old kernel <R, NORM, NOISE, ONE, XOPT,
+SAMPLE, DYN, WIND, ACT, SENS, PRIV, GOAL> is compared with the new kernel <R, NORM, NOISE, ONE, XOPT, SAMPLE, M>, M = the number of
+`true`s in DYN ... GOAL; it is an error if they are not a prefix of that run.  The StepArg<...>::type inside the name maps likewise.
+Every other function pairs by identical name; both sides are masked as above.
+
+With either pairing, and without one, the entries of the code object's metadata note are compared for every paired kernel as well: VGPR,
+AGPR and SGPR counts, both spill counts, LDS size, private segment size and kernarg segment size.
 """
 import os
 import re
@@ -53,10 +61,41 @@ def functions(obj, work):
                 text[cur] = []
         elif cur and line.strip():
             text[cur].append(re.sub(r"\s*//.*$", "", line).strip())     # "\tinsn operands   // ADDR: ENCODING"
+    meta = metadata(subprocess.check_output([tool("llvm-readelf"), "--notes", co], text=True))
     for f in os.listdir(work):
         os.remove(os.path.join(work, f))
     assert set(text) == syms, (len(text), len(syms))
-    return {s: "\n".join(t) for s, t in text.items()}, listed
+    return {s: "\n".join(t) for s, t in text.items()}, listed, meta
+
+
+META_KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".group_segment_fixed_size",
+             ".private_segment_fixed_size", ".kernarg_segment_size")
+
+
+def metadata(notes):
+    """{kernel name: {key: value}} for META_KEYS, from the amdhsa.kernels list of the AMDGPU metadata note as llvm-readelf prints it."""
+    out, cur, at = {}, None, None
+    for line in notes.splitlines():
+        indent = len(line) - len(line.lstrip())
+        if at is None:
+            if line.strip() == "amdhsa.kernels:":
+                at = -1
+            continue
+        if at < 0:
+            at = indent                                             # the column of the list's dashes
+        if indent < at or (indent == at and not line.lstrip().startswith("- ")):
+            break                                                   # the next key of the note
+        m = re.match(r"^\s{%d}(?:- | {2})(\.\w+):\s*(\S*)$" % at, line)       # the kernel's own keys, not those of its .args
+        if not m:
+            continue
+        if line[at] == "-":
+            cur = {}
+        if m.group(1) == ".name":
+            out[m.group(2)] = cur
+        elif m.group(1) in META_KEYS:
+            cur[m.group(1)] = m.group(2)
+    assert all(len(v) == len(META_KEYS) for v in out.values()), "metadata note: a kernel lacks one of %s" % (META_KEYS,)
+    return out
 
 
 def less_trailing_false(sym):
@@ -66,6 +105,20 @@ def less_trailing_false(sym):
         return None
     rest = re.sub(r"XT\d+_E(E4typeE)", r"\1", m.group(3), count=1)
     return m.group(1) + m.group(2)[:-4] + rest
+
+
+def model_level_name(sym):
+    """The new name of an old dn_step_many_1w_kernel instantiation (any other symbol: unchanged); ValueError off the chain."""
+    m = re.match(r"^(.*22dn_step_many_1w_kernelI[df](?:Lb[01]E){5})((?:Lb[01]E){6})(E.*7StepArgI)(?:XT\d+_E){6}(E4typeE.*)$", sym)
+    if not m:
+        if "22dn_step_many_1w_kernelI" in sym and not re.search(r"22dn_step_many_1w_kernelI[df](?:Lb[01]E){5}Li\d+EE", sym):
+            raise ValueError("dn_step_many_1w_kernel with an unexpected argument list: " + sym)
+        return sym
+    flags = re.findall(r"Lb([01])E", m.group(2))
+    level = flags.count("1")
+    if flags != ["1"] * level + ["0"] * (6 - level):
+        raise ValueError("the model flags %s are not a prefix of DYN ... GOAL: %s" % ("".join(flags), sym))
+    return "%sLi%dE%sXT5_E%s" % (m.group(1), level, m.group(3), m.group(4))
 
 
 def masked(text):
@@ -82,29 +135,39 @@ def masked(text):
     return "\n".join(out)
 
 
-def main(old, new, new_template_arg=False):
+def main(old, new, new_template_arg=False, model_level=False):
     bad = 0
     for name in OBJECTS:
         with tempfile.TemporaryDirectory() as work:
-            (a, na), (b, nb) = functions(os.path.join(old, name), work), functions(os.path.join(new, name), work)
+            (a, na, ma), (b, nb, mb) = functions(os.path.join(old, name), work), functions(os.path.join(new, name), work)
         if new_template_arg:
             a = {s: masked(t) for s, t in a.items()}
-            renamed = {}
+            renamed, meta = {}, {}
             for s, t in b.items():
                 was = less_trailing_false(s) if s not in a else None
                 renamed[was if was in a and was not in b else s] = masked(t)
-            b = renamed
+                if s in mb:
+                    meta[was if was in a and was not in b else s] = mb[s]
+            b, mb = renamed, meta
+        elif model_level:
+            a, ma = {model_level_name(s): masked(t) for s, t in a.items()}, {model_level_name(s): v for s, v in ma.items()}
+            b = {s: masked(t) for s, t in b.items()}
         only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
         differ = sorted(s for s in set(a) & set(b) if a[s] != b[s])
-        print(f"{name}: {len(a)} | {len(b)} functions ({na} | {nb} FUNC entries), {len(only_a)} only old, {len(only_b)} only new, {len(differ)} with different text")
+        kernels = sorted(set(ma) & set(mb) & set(a) & set(b))
+        meta_differ = [s for s in kernels if ma[s] != mb[s]]
+        print(f"{name}: {len(a)} | {len(b)} functions ({na} | {nb} FUNC entries), {len(only_a)} only old, {len(only_b)} only new, {len(differ)} with different text; "
+              f"{len(kernels)} paired kernels ({len(ma)} | {len(mb)}), {len(meta_differ)} with different metadata")
         for tag, group in (("only old", only_a), ("only new", only_b), ("differs", differ)):
             for s in group:
                 print(f"    {tag}: {s}")
-        bad += len(only_a) + len(only_b) + len(differ)
+        for s in meta_differ:
+            print(f"    metadata: {s}: " + ", ".join(f"{k} {ma[s][k]} | {mb[s][k]}" for k in META_KEYS if ma[s][k] != mb[s][k]))
+        bad += len(only_a) + len(only_b) + len(differ) + len(meta_differ) + abs(len(ma) - len(kernels)) + abs(len(mb) - len(kernels))
     print("device code identical" if not bad else f"{bad} differences")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    args = [x for x in sys.argv[1:] if x != "--new-template-arg"]
-    sys.exit(main(args[0], args[1], "--new-template-arg" in sys.argv[1:]))
+    args = [x for x in sys.argv[1:] if not x.startswith("--")]
+    sys.exit(main(args[0], args[1], "--new-template-arg" in sys.argv[1:], "--model-level" in sys.argv[1:]))

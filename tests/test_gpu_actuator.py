@@ -3,7 +3,7 @@
 1. off is off (latency [0, 0], tau [0, 0]) bit for bit, alone and with dynamics + wind;
 2. latency = the same env without latency fed the shifted actions, bit for bit (plain, noise, normaliser, dynamics + wind);
 3. one fused launch = single steps, bit for bit, K = 20, 5 (< 8) and 64, history crossings and in-launch fills asserted;
-4. / 7. every instantiation of dn_step_many_1w_kernel<R, NORM, NOISE, ONE, true, false, true, true, ACT = true> against the CPU oracle
+4. / 7. every instantiation of dn_step_many_1w_kernel<R, NORM, NOISE, ONE, true, false, M = DN_M_ACT> against the CPU oracle
    fed the shifted actions (this file leaves the oracle's actuator off and shifts on the host; the oracle's own actuator model is
    held against the kernels in tests/test_gpu_actuator_oracle.py), at tests/test_gpu_dynamics_wind_oracle.py's bars;
 5. the draws against their definition on orc_philox4x32;

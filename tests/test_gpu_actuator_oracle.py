@@ -4,7 +4,7 @@ configurations, seeds and action streams live in tests/model_support.py; tests/t
 cases claimed here (episode ends, fills, latencies 0 and 8, history entries consumed across a launch boundary, restarts inside a
 launch, the ground effect acting); every test here first checks that its oracle has that file's configuration, byte for byte.
 
-a. All 16 instantiations of dn_step_many_1w_kernel<R, NORM, NOISE, ONE, ..., DYN, WIND, ACT = true> with latency [0, 8] AND lag
+a. All 16 instantiations of dn_step_many_1w_kernel<R, NORM, NOISE, ONE, ..., M = DN_M_ACT> with latency [0, 8] AND lag
    (motor_tau [0.02, 0.15]) on together, dynamics + wind riding in the norm cells; the oracle is loaded with the device's state,
    scales, wind and actuator state before every step (step) or 5-step launch (rollout).  Outputs at the bars of
    tests/test_gpu_dynamics_wind_oracle.py.  Actuator state afterwards: latency and history exact, coeff <= 1 float32 ulp (device exp

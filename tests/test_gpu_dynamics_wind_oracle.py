@@ -2,7 +2,7 @@
 (oracle/dn_oracle.c orc_vec_step_dw, itself pinned by tests/test_oracle_dynamics_wind.py): every kernel instantiation of the two
 families, the run-time options inside them, and free-running fused launches through many in-launch episode starts.
 
-a. Every instantiation: both families are dn_step_many_1w_kernel<R, NORM, NOISE, ONE, XOPT = true, SAMPLE = false, DYN = true, WIND>
+a. Every instantiation: both families are dn_step_many_1w_kernel<R, NORM, NOISE, ONE, XOPT = true, SAMPLE = false, M = DN_M_DYN | DN_M_WIND>
    (dn_launch_step_many, launch_models), one test ID per cell:
 
        test ID cell [family-dtype-norm-noise-mode]   R       NORM   NOISE  ONE    WIND   dynamics scales

@@ -5,7 +5,7 @@ oracle alone that they reach the cases claimed here (every latency 0..8, deliver
 launch followed by a delayed delivery, moved spawn points, an episode end on the last drone of a partial tile); every test here first
 checks that its oracle has that file's configuration, byte for byte.
 
-a. All 16 instantiations of dn_step_many_1w_kernel<R, NORM, NOISE, ONE, ..., SENS = true> at n = 1000 (a partial last tile): dynamics +
+a. All 16 instantiations of dn_step_many_1w_kernel<R, NORM, NOISE, ONE, ..., M = DN_M_SENS> at n = 1000 (a partial last tile): dynamics +
    wind + actuator ride in the norm cells, the raw cells fly the sensor alone (the null-pointer paths of the family).  The oracle is
    loaded with the device's state AND its sensor state (latency, bias, logical history) before every step / 5-step launch.  Outputs
    at the existing bars.  Bit-exact part: a delivered row that reaches back past the start of the launch is float32(loaded history +
