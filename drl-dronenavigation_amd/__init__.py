@@ -8,7 +8,7 @@ Importing this package needs the compiled library (there is no CPU fallback); bu
 """
 from . import _capi, build, tracks  # noqa: F401
 from ._capi import DroneNavError, DroneNavLibraryError  # noqa: F401
-from .tracks import Track  # noqa: F401
+from .tracks import Track, TrackBank  # noqa: F401
 from .dynamics import DynamicsRandomization  # noqa: F401
 from .wind import WindDisturbance  # noqa: F401
 from .actuator import ActuatorModel  # noqa: F401
@@ -16,7 +16,7 @@ from .sensor import SensorModel  # noqa: F401
 from .privileged import PrivilegedObservation, PRIV_DIM, PRIV_GROUPS, PRIV_SLICES  # noqa: F401
 from .goal import GoalObservation, GOAL_DIM, GOAL_FRAMES, GOAL_SLICES  # noqa: F401
 
-__all__ = ["DroneVecEnv", "Track", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
+__all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
            "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor",
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",

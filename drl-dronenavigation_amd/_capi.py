@@ -9,6 +9,7 @@ import os
 from . import build as _build
 
 MAX_WAYPOINTS = 64
+MAX_TRACKS = 64
 OBS_DIM = 13
 ACT_DIM = 4
 ABI_VERSION = 9
@@ -93,6 +94,11 @@ class DnGoalConfig(C.Structure):
     _fields_ = [("frame", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DnTrackBankConfig(C.Structure):
+    _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
+                ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every entry point declared in include/dronenav.h: name -> (restype, argtypes)
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 PROTOTYPES = {
@@ -154,6 +160,11 @@ PROTOTYPES = {
     "dn_enable_goal": (_I32, [_VP, C.POINTER(DnGoalConfig)]),
     "dn_get_goal_config": (_I32, [_VP, C.POINTER(DnGoalConfig)]),
     "dn_bind_goal": (_I32, [_VP, _VP, _VP, _I64]),
+    "dn_enable_tracks": (_I32, [_VP, C.POINTER(DnTrackBankConfig)]),
+    "dn_set_tracks": (_I32, [_VP, _VP, _VP]),
+    "dn_get_tracks": (_I32, [_VP, _VP, _VP, _VP]),
+    "dn_get_track_stats": (_I32, [_VP, _VP, _I32]),
+    "dn_get_track_bank_config": (_I32, [_VP, C.POINTER(DnTrackBankConfig)]),
 }
 
 _lib = None

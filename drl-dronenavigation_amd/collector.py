@@ -109,6 +109,13 @@ def _refuse_privileged(env, who):
                          "use RolloutCollector(..., value_input='privileged') with a torch value_fn")
 
 
+def _refuse_tracks(env, who):
+    """A track bank rides in the goal family of the step kernels, which carries no sampling-fused entry point."""
+    if getattr(env, "track_ids", None) is not None:
+        raise ValueError(f"{who} does not carry a track bank (its sampling-fused step kernels fly the one track of the env); "
+                         "use RolloutCollector with a torch policy")
+
+
 def _refuse_goal(env, who):
     """The fused collectors feed the policy kernels the 13 observation columns from the step kernel's own output; the goal rows are
     written by another kernel family, which carries no sampling-fused entry point."""
@@ -140,7 +147,10 @@ class RolloutCollector:
 
     `policy_input="observation+goal"` (the env needs goal=GoalObservation(...)): the policy -- and the value function, unless
     `value_input="privileged"` -- sees cat(obs, goal), [N, obs_dim + 8]; the truncation bootstrap is evaluated on
-    cat(terminal_obs, terminal_goal), and the buffer dict gains `goal` [n_steps, N, 8] (`obs` stays the observation alone)."""
+    cat(terminal_obs, terminal_goal), and the buffer dict gains `goal` [n_steps, N, 8] (`obs` stays the observation alone).
+
+    An env with a track bank (tracks=TrackBank(...)): the buffer dict gains `track` [n_steps, N] int32, the track each drone is on
+    when `obs[t]` is observed."""
 
     def __init__(self, env, policy, n_steps, *, value_fn=None, gamma=0.99, gae_lambda=0.95, bootstrap_truncated=True,
                  gather=False, group=None, use_graph=False, value_input="observation", policy_input="observation"):
@@ -186,6 +196,10 @@ class RolloutCollector:
         if self.policy_goal:
             self.buf["goal"] = torch.empty((T, n, env.goal.shape[1]), dtype=f32, device=dev)
             self._last_goal = env.goal.clone()
+        self.has_tracks = env.track_ids is not None
+        if self.has_tracks:         # the track each drone is on when obs[t] is observed
+            self.buf["track"] = torch.empty((T, n), dtype=torch.int32, device=dev)
+            self._last_track = env.track_ids.clone()
         self._last_done = torch.ones(n, dtype=torch.uint8, device=dev)       # SB3: _last_episode_starts = True
         self.num_timesteps = 0
         self._graph = None
@@ -214,6 +228,8 @@ class RolloutCollector:
             actions, values, log_probs = self.policy(seen(obs, goal))
             if goal is not None:
                 b["goal"][t].copy_(goal)
+            if self.has_tracks:
+                b["track"][t].copy_(self._last_track)
             if priv is not None:
                 b["privileged"][t].copy_(priv)
                 values = self._values(priv)
@@ -240,6 +256,8 @@ class RolloutCollector:
                 priv.copy_(info["privileged"])
             if goal is not None:
                 goal.copy_(info["goal"])
+            if self.has_tracks:
+                self._last_track.copy_(info["track"])
         b["last_values"].copy_(self._values(seen(obs, goal) if priv is None else priv))
         b["last_dones"].copy_(done)
         dev = env.device
@@ -387,6 +405,7 @@ class OffPolicyCollector:
         from .vec_env import ACT_DIM, DroneVecEnv
         _refuse_privileged(env, "OffPolicyCollector")
         _refuse_goal(env, "OffPolicyCollector")
+        _refuse_tracks(env, "OffPolicyCollector")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("OffPolicyCollector drives a DroneVecEnv (HIP); there is no CPU path")
         self.env, self.actor = env, actor
@@ -504,6 +523,7 @@ class FusedRolloutCollector:
         from .vec_env import ACT_DIM, OBS_DIM, DroneVecEnv
         _refuse_privileged(env, "FusedRolloutCollector")
         _refuse_goal(env, "FusedRolloutCollector")
+        _refuse_tracks(env, "FusedRolloutCollector")
         if not isinstance(env, DroneVecEnv) or not isinstance(policy, FusedMlpPolicy):
             raise TypeError("FusedRolloutCollector needs a DroneVecEnv and a FusedMlpPolicy (HIP); there is no CPU path")
         if env.num_envs % 4 or env.obs_dim != OBS_DIM:

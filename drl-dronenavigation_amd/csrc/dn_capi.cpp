@@ -101,6 +101,8 @@ struct dn_env {
     dn_sensor_config sens_cfg = {};
     dn_privileged_config priv_cfg = {};
     dn_goal_config goal_cfg = {};
+    dn_track_bank_config track_cfg = {};
+    bool ground_contact_auto = false;   // created with DN_GROUND_CONTACT_AUTO: dn_enable_tracks resolves the term again over the bank
 };
 
 thread_local hipEvent_t dn_tl_ev_start = nullptr, dn_tl_ev_stop = nullptr;
@@ -308,7 +310,8 @@ int32_t init_state(dn_env *e, hipStream_t s)
 }
 
 // The per-drone models, one row per DnModelLevel above DN_M_NONE and in its order (dn_internal.h).  dn_destroy and the entry points that
-// carry none of them walk this table; a new model is one more level and one more row.
+// carry none of them walk this table; a new model is one more level and one more row.  The track bank is a row without a level of its
+// own: it shares the deepest one (dn_internal.h dn_model_level).
 struct ModelRow {
     int level;
     void *(*slot)(const DnModels &);    // the pointer that owns the model's allocation, nullptr where it owns none
@@ -330,9 +333,17 @@ constexpr ModelRow MODELS[] = {
      "dn_enable_privileged", "writes no privileged rows"},
     {DN_M_GOAL, [](const DnModels &) -> void * { return nullptr; }, [](const DnModels &m) { return m.goal.on != 0; }, "the goal observations", "dn_enable_goal",
      "writes no goal rows"},
+    {DN_M_GOAL, [](const DnModels &m) -> void * { return m.track.track; }, [](const DnModels &m) { return m.track.track != nullptr; }, "the track bank",
+     "dn_enable_tracks", "flies the one track of dn_config"},
 };
-constexpr bool models_follow_levels(int k = 0) { return k == DN_M_COUNT - 1 || (MODELS[k].level == k + 1 && models_follow_levels(k + 1)); }
-static_assert(sizeof MODELS / sizeof MODELS[0] == DN_M_COUNT - 1 && models_follow_levels(), "MODELS[]: one row per DnModelLevel, in its order");
+constexpr int NUM_MODELS = (int)(sizeof MODELS / sizeof MODELS[0]);
+// row k carries level k + 1, and the rows past the last level (the track bank) share it
+constexpr bool models_follow_levels(int k = 0)
+{
+    return k == NUM_MODELS || (MODELS[k].level == (k + 1 < DN_M_COUNT ? k + 1 : DN_M_COUNT - 1) && models_follow_levels(k + 1));
+}
+static_assert(NUM_MODELS == DN_M_COUNT && models_follow_levels(),
+              "MODELS[]: one row per DnModelLevel, in its order, then the track bank, which shares the deepest level");
 
 // DN_OK, or the refusal of entry point `who`, whose kernels carry no model, for the first model that is on.  `instead` names the calls
 // that do carry it; nullptr = dn_eval_kinematics, which has a reason per model and no alternative.
@@ -398,6 +409,16 @@ hipError_t copy_rows(bool set, void *model, const void *user, size_t bytes, hipS
                : hipMemcpyAsync(const_cast<void *>(user), model, bytes, hipMemcpyDeviceToDevice, s);
 }
 
+// The single-track configuration of track t of the bank: what build_table and ground_contact_reachable are given for it.
+dn_config track_as_config(const dn_config &c, const dn_track_bank_config &b, int t, int base)
+{
+    dn_config one = c;
+    one.num_waypoints = b.num_waypoints[t];
+    memcpy(one.waypoints, b.waypoints + 3 * base, sizeof(double) * 3 * (size_t)b.num_waypoints[t]);
+    return one;
+}
+size_t track_off_cdf(long long n) { return align_up((size_t)n * 2 * sizeof(int), 256); }
+
 }  // namespace
 
 extern "C" {
@@ -450,7 +471,8 @@ int32_t dn_create(const dn_config *cfg, dn_env **out)
     dn_env *e = new (std::nothrow) dn_env();
     if (!e) return fail(DN_ERR_OUT_OF_MEMORY, "host allocation failed");
     e->cfg = *cfg;
-    if (e->cfg.ground_contact == DN_GROUND_CONTACT_AUTO) e->cfg.ground_contact = ground_contact_reachable(*cfg) ? 1 : 0;
+    e->ground_contact_auto = e->cfg.ground_contact == DN_GROUND_CONTACT_AUTO;
+    if (e->ground_contact_auto) e->cfg.ground_contact = ground_contact_reachable(*cfg) ? 1 : 0;
     cfg = &e->cfg;                                      // from here on: the resolved configuration (dn_get_config returns it)
     {
         int cus = 0;
@@ -994,12 +1016,26 @@ int32_t dn_set_state(dn_env *env, const dn_env_state *states, int64_t count)
     if (env->p.drag) g7.resize((size_t)n);
     std::vector<double> pid;
     if (env->p.pid_mode) pid.resize((size_t)n * 9);
+    // dn_enable_tracks: idx is the index within the drone's OWN track, so it is held to that track's count -- the assignment as it stands
+    // on the device (a checkpoint is restored as dn_set_tracks, then dn_set_state), an index outside the bank held to it as the kernels do
+    std::vector<int32_t> track;
+    if (env->m.track.track) {
+        track.resize((size_t)n);
+        DN_HIP(hipSetDevice(env->cfg.device_id));
+        DN_HIP(hipDeviceSynchronize());
+        DN_HIP(hipMemcpy(track.data(), env->m.track.track, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
     for (long long i = 0; i < n; ++i) {
         const dn_env_state &s = states[i];
+        int num_waypoints = env->cfg.num_waypoints;
+        if (!track.empty()) {
+            const int T = env->track_cfg.num_tracks, t = track[(size_t)i] < 0 ? 0 : (track[(size_t)i] >= T ? T - 1 : track[(size_t)i]);
+            num_waypoints = env->track_cfg.num_waypoints[t];
+        }
         if (env->p.pid_mode) for (int k = 0; k < 9; ++k) pid[(size_t)k * n + i] = s.pid[k];
         if (env->p.drag) g7[(size_t)i] = make_float4(s.last_rpm[0], s.last_rpm[1], s.last_rpm[2], s.last_rpm[3]);
         if (env->cfg.norm_rew) { rr[(size_t)i] = s.rr_returns; rr[(size_t)n + i] = s.rr_mean; rr[(size_t)2 * n + i] = s.rr_var; rr[(size_t)3 * n + i] = s.rr_count; }
-        if (s.idx < 0 || s.idx >= env->cfg.num_waypoints || s.steps < 0 || s.steps > (1 << 24) - 1)
+        if (s.idx < 0 || s.idx >= num_waypoints || s.steps < 0 || s.steps > (1 << 24) - 1)
             return fail(DN_ERR_INVALID_ARGUMENT, "state %lld: idx/steps out of range", i);
         if (s.steps > 0 && (s.cur_pos[0] != s.pos[0] || s.cur_pos[1] != s.pos[1] || s.cur_pos[2] != s.pos[2]))
             return fail(DN_ERR_BAD_STATE, "state %lld: _current_position must equal pos once _steps > 0", i);
@@ -1407,6 +1443,133 @@ int32_t dn_bind_goal(dn_env *env, float *rows, float *terminal_rows, int64_t cap
     g.rows = rows;
     g.term = terminal_rows;
     g.cap = capacity_steps;
+    return DN_OK;
+}
+
+// ---- track bank ----
+int32_t dn_enable_tracks(dn_env *env, const dn_track_bank_config *cfg)
+{
+    if (!env || !cfg) return fail(DN_ERR_INVALID_ARGUMENT, "env and cfg are required");
+    const dn_config &c = env->cfg;
+    if (c.circle) return fail(DN_ERR_INVALID_ARGUMENT, "dn_enable_tracks: a circle env has no waypoint corridor table to bank (circle = %d)", c.circle);
+    if (c.random_spawn) return fail(DN_ERR_INVALID_ARGUMENT, "dn_enable_tracks: refused with random_spawn (the spawn draw reads the one track's lines)");
+    if (cfg->num_tracks < 1 || cfg->num_tracks > DN_MAX_TRACKS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "num_tracks must be in 1..%d (got %d)", DN_MAX_TRACKS, cfg->num_tracks);
+    const int T = cfg->num_tracks;
+    int total = 0;
+    for (int t = 0; t < T; ++t) {
+        if (cfg->num_waypoints[t] < 1 || cfg->num_waypoints[t] > DN_MAX_WAYPOINTS)
+            return fail(DN_ERR_INVALID_ARGUMENT, "track %d: num_waypoints must be in 1..%d (got %d)", t, DN_MAX_WAYPOINTS, cfg->num_waypoints[t]);
+        total += cfg->num_waypoints[t];
+    }
+    if (total > DN_MAX_WAYPOINTS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "the bank has %d waypoints in all: at most %d (the corridor table the kernels stage)", total, DN_MAX_WAYPOINTS);
+    for (int j = 0; j < total * 3; ++j)
+        if (!std::isfinite(cfg->waypoints[j])) return fail(DN_ERR_INVALID_ARGUMENT, "bank waypoint %d is not finite", j / 3);
+    double sum = 0.0, cdf[DN_MAX_TRACKS] = {};
+    for (int t = 0; t < T; ++t) {
+        const float w = cfg->weight[t];
+        if (!std::isfinite(w) || w < 0.0f) return fail(DN_ERR_INVALID_ARGUMENT, "weight[%d] = %g: need finite and >= 0", t, (double)w);
+        sum += (double)w;
+        cdf[t] = sum;                                   // S_t: float64 partial sums of the float32 weights, in index order
+    }
+    if (!(sum > 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "every weight is zero: no track could be drawn");
+    for (int t = 0; t < T; ++t) cdf[t] = cdf[t] / sum;
+    if (const int32_t rc = check_resample_reserved(cfg->resample, cfg->reserved)) return rc;
+    if (cfg->num_waypoints[0] != c.num_waypoints || memcmp(cfg->waypoints, c.waypoints, sizeof(double) * 3 * (size_t)c.num_waypoints) != 0)
+        return fail(DN_ERR_INVALID_ARGUMENT, "track 0 of the bank must be the track of dn_config (the same count and bit-equal waypoints)");
+    DnTrack &tk = env->m.track;
+    if (tk.track) {
+        const dn_track_bank_config &was = env->track_cfg;
+        if (was.num_tracks != T || memcmp(was.num_waypoints, cfg->num_waypoints, sizeof(int32_t) * (size_t)T) != 0 ||
+            memcmp(was.waypoints, cfg->waypoints, sizeof(double) * 3 * (size_t)total) != 0)
+            return fail(DN_ERR_INVALID_ARGUMENT, "dn_enable_tracks: the bank's geometry (tracks, counts, waypoints) cannot change once enabled; weights and resample can");
+    }
+    DN_HIP(hipSetDevice(c.device_id));
+    DN_HIP(hipDeviceSynchronize());                     // launches in flight read the table, the weights and the ground-contact switch
+    const long long n = c.num_envs;
+    const size_t off_cdf = track_off_cdf(n), off_bw = off_cdf + DN_MAX_TRACKS * sizeof(double), off_count = off_bw + DN_MAX_TRACKS * sizeof(int);
+    const size_t bytes = off_count + DN_MAX_TRACKS * 5 * sizeof(unsigned long long);
+    const bool first = tk.track == nullptr;
+    float4 *mem = reinterpret_cast<float4 *>(tk.track);
+    // first call: every drone on track 0, no episode finished yet, zero counters
+    if (const int32_t rc = model_storage(env, mem, bytes, "the track bank", [&](float4 *d) {
+            char *b = reinterpret_cast<char *>(d);
+            return hipMemsetAsync(b, 0, bytes, nullptr) == hipSuccess &&
+                   hipMemsetAsync(b + (size_t)n * sizeof(int), 0xFF, (size_t)n * sizeof(int), nullptr) == hipSuccess;
+        }))
+        return rc;
+    char *base = reinterpret_cast<char *>(mem);
+    int bw[DN_MAX_TRACKS] = {};
+    bool contact = false;
+    std::vector<double> t64(DN_MAX_WAYPOINTS * DN_T_STRIDE, 0.0);
+    std::vector<float> t32(DN_MAX_WAYPOINTS * DN_T_STRIDE, 0.0f);
+    for (int t = 0, row = 0; t < T; row += cfg->num_waypoints[t], ++t) {
+        const dn_config one = track_as_config(c, *cfg, t, row);
+        build_table(one, t64.data() + (size_t)row * DN_T_STRIDE);       // the rows of the single-track configuration: the definition
+        contact = contact || ground_contact_reachable(one);
+        bw[t] = row | (cfg->num_waypoints[t] << 8);
+    }
+    for (size_t j = 0; j < t64.size(); ++j) t32[j] = (float)t64[j];
+    if ((first && (hipMemcpy(env->tab64, t64.data(), t64.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+                   hipMemcpy(env->tab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) ||
+        hipMemcpy(base + off_cdf, cdf, sizeof cdf, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(base + off_bw, bw, sizeof bw, hipMemcpyHostToDevice) != hipSuccess) {
+        if (first) (void)hipFree(mem);
+        return fail(DN_ERR_HIP, "uploading the track bank failed");
+    }
+    tk.track = reinterpret_cast<int *>(base);
+    tk.finished = tk.track + n;
+    tk.cdf = reinterpret_cast<const double *>(base + off_cdf);
+    tk.bw = reinterpret_cast<const int *>(base + off_bw);
+    tk.count = reinterpret_cast<unsigned long long *>(base + off_count);
+    tk.num_tracks = T;
+    tk.total = total;
+    tk.resample = cfg->resample;
+    if (env->ground_contact_auto) {                     // DN_GROUND_CONTACT_AUTO: on if any track of the bank needs the term
+        env->cfg.ground_contact = contact ? 1 : 0;
+        env->p.ground_contact = contact ? 1 : 0;
+    }
+    env->track_cfg = *cfg;
+    return DN_OK;
+}
+
+int32_t dn_set_tracks(dn_env *env, const int32_t *track, void *stream)
+{
+    if (!env || !track) return fail(DN_ERR_INVALID_ARGUMENT, "env and track are required");
+    if (!env->m.track.track) return fail(DN_ERR_BAD_STATE, "the track bank is not enabled (dn_enable_tracks)");
+    DN_HIP(copy_rows(true, env->m.track.track, track, (size_t)env->cfg.num_envs * sizeof(int32_t), (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_get_tracks(dn_env *env, int32_t *track, int32_t *finished, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
+    if (!env->m.track.track) return fail(DN_ERR_BAD_STATE, "the track bank is not enabled (dn_enable_tracks)");
+    const size_t bytes = (size_t)env->cfg.num_envs * sizeof(int32_t);
+    DN_HIP(copy_rows(false, env->m.track.track, track, bytes, (hipStream_t)stream));
+    DN_HIP(copy_rows(false, env->m.track.finished, finished, bytes, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_get_track_stats(dn_env *env, int64_t *out, int32_t reset)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    const DnTrack &tk = env->m.track;
+    if (!tk.track) return fail(DN_ERR_BAD_STATE, "the track bank is not enabled (dn_enable_tracks)");
+    DN_HIP(hipSetDevice(env->cfg.device_id));
+    DN_HIP(hipDeviceSynchronize());
+    const size_t bytes = (size_t)tk.num_tracks * 5 * sizeof(int64_t);
+    DN_HIP(hipMemcpy(out, tk.count, bytes, hipMemcpyDeviceToHost));
+    if (reset) DN_HIP(hipMemset(tk.count, 0, bytes));
+    return DN_OK;
+}
+
+int32_t dn_get_track_bank_config(const dn_env *env, dn_track_bank_config *out)
+{
+    if (!env || !out) return fail(DN_ERR_INVALID_ARGUMENT, "env and out are required");
+    if (!env->m.track.track) return fail(DN_ERR_BAD_STATE, "the track bank is not enabled (dn_enable_tracks)");
+    *out = env->track_cfg;
     return DN_OK;
 }
 

@@ -121,7 +121,7 @@ struct DnParams {
 // The per-drone models as one chain, shallowest first: the one statement of their order.  A step launch has ONE level, the deepest model
 // that is on (dn_model_level below); the one-wave option kernel of level M (dn_step_many_1w_kernel<..., M>) carries every model up to M,
 // each switched on or off at run time by its null pointers, and takes the first M slices of the argument chain
-// DnDyn : DnWind : DnAct : DnSens : DnPriv : DnGoal (dn_kernels.hip StepArg) as its last argument.  DN_M_NONE is the plain kernel: that
+// DnDyn : DnWind : DnAct : DnSens : DnPriv : DnGoal + DnTrack (dn_kernels.hip StepArg) as its last argument.  DN_M_NONE is the plain kernel: that
 // argument is an empty struct.  The structs below and MODELS[] (dn_capi.cpp) follow this order.
 enum DnModelLevel { DN_M_NONE = 0, DN_M_DYN, DN_M_WIND, DN_M_ACT, DN_M_SENS, DN_M_PRIV, DN_M_GOAL, DN_M_COUNT };
 
@@ -204,6 +204,22 @@ struct DnGoal {
     int on;                 // 0 = the feature is not enabled
 };
 
+// Per-drone track bank (dn_enable_tracks): T tracks whose table rows sit one after the other in the corridor table the kernels stage into
+// LDS (track t = rows base_t .. base_t + W_t - 1, track 0 first: the rows of dn_config), and each drone's track.  Not a level of its own:
+// it rides in the DN_M_GOAL family (GoalArg = PrivArg + DnGoal + DnTrack) and is an argument of the reset kernel.  track and finished are
+// one allocation, track first; cdf, bw and count follow them in it.
+struct DnTrack {
+    int *track;             // [N] the track of the drone's current episode; nullptr = the bank is off (one track: base 0, W = DnParams.num_waypoints)
+    int *finished;          // [N] the track of its most recently ended episode, -1 before the first: track + N
+    const double *cdf;      // [T] cumulative weights S_k / S_{T-1}, float64 partial sums of the float32 weights formed on the host
+    const int *bw;          // [T] base_t | W_t << 8
+    unsigned long long *count;  // [T][5] episodes, completed, truncated, sum of found_targets, sum of episode lengths, under the entry track
+    int num_tracks;
+    int total;              // rows of the whole bank: what stage_table stages
+    int resample;           // 1: draw the track at every episode start; 0: keep what dn_set_tracks wrote
+    int pad_;
+};
+
 // The per-drone models as the host carries them (dn_env, the launchers).  The kernels take them as before: the reset kernel as one argument
 // each, the option step kernels as the slice of the chain (DnModelLevel above) their level reads.  A model that is off is its
 // value-initialised struct (null pointers, groups 0, on 0).
@@ -214,12 +230,14 @@ struct DnModels {
     DnSens sens;
     DnPriv priv;
     DnGoal goal;
+    DnTrack track;
 };
 // The level a step launch takes: the deepest model that is on.  The two row writers count only when enabled AND bound: unbound, nothing
-// would be written, and the level below serves.
+// would be written, and the level below serves.  The track bank shares the deepest level, whatever the goal rows' binding: unbound, that
+// family runs with null rows and writes none.
 inline int dn_model_level(const DnModels &m)
 {
-    if (m.goal.on && m.goal.rows) return DN_M_GOAL;
+    if (m.track.track || (m.goal.on && m.goal.rows)) return DN_M_GOAL;
     if (m.priv.groups && m.priv.rows) return DN_M_PRIV;
     if (m.sens.ring) return DN_M_SENS;
     if (m.act.hist) return DN_M_ACT;

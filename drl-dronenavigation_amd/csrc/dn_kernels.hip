@@ -842,11 +842,14 @@ DN_DEV void store_obs_tile(float *s_tile, float *gtile, unsigned rows, unsigned 
     tile_stream(t, s_tile, gtile, rows, lane);
 }
 
-template <typename R>
-DN_DEV void stage_table(const DnParams &p, R *s_tab)
+// BANK (the DN_M_GOAL kernels and the reset kernel, dn_enable_tracks): `rows` rows are staged, the whole track bank's.  The track-bank
+// forms of the phase functions below are compile-time ones (BANK, false by default), so that every kernel that has no bank compiles
+// from the statements it always had.
+template <typename R, bool BANK = false>
+DN_DEV void stage_table(const DnParams &p, R *s_tab, const int rows = 0)
 {   // all threads of the workgroup cooperate; the caller's next block barrier publishes the table
     const R *g = table_ptr<R>(p);
-    for (unsigned j = threadIdx.x; j < (unsigned)(p.num_waypoints * DN_T_STRIDE); j += blockDim.x) s_tab[j] = g[j];
+    for (unsigned j = threadIdx.x; j < (unsigned)((BANK ? rows : p.num_waypoints) * DN_T_STRIDE); j += blockDim.x) s_tab[j] = g[j];
 }
 template <typename R>
 DN_DEV void stage_table_by(const DnParams &p, R *s_tab, const unsigned tid, const unsigned nthreads)
@@ -1668,6 +1671,35 @@ DN_DEV void priv_store_bias(const DnPriv &pv, float *row, const DnSens &sn, cons
     *priv_quad(row, 12) = make_float4(d.x, 0.0f, 0.0f, 0.0f);
 }
 
+// ---- track bank (dn_enable_tracks) ------------------------------------------------------------------------------------------------
+// A drone's track as one word: first table row | waypoint count << 8 | track << 16 (rows and counts are <= DN_MAX_WAYPOINTS = 64, tracks
+// < DN_MAX_TRACKS = 64).  dn_set_tracks does not validate: an index outside the bank is held to it, so that no lane reads past the table.
+DN_DEV int track_word(const DnTrack &tk, const int t_raw)
+{
+    const int t = t_raw < 0 ? 0 : (t_raw >= tk.num_tracks ? tk.num_tracks - 1 : t_raw);
+    return tk.bw[t] | (t << 16);
+}
+// The track of the episode that starts at vector step `step`: ONE Philox call keyed (seed; global drone id, step, stream 22),
+// u = (r_0 + 0.5) / 2^32 in float64, t = the number of k in 0..T-2 with u >= cdf_k.  A zero weight repeats its predecessor's cdf and is never drawn.
+DN_DEV int track_draw(const DnTrack &tk, const unsigned long long seed, const unsigned long long gid, const unsigned long long step)
+{
+    unsigned r[4];
+    philox4x32((unsigned)gid, (unsigned)(gid >> 32), (unsigned)step, 22u | ((unsigned)(step >> 32) << 8), (unsigned)seed,
+               (unsigned)(seed >> 32), r);
+    const double u = ((double)r[0] + 0.5) * (1.0 / 4294967296.0);
+    int t = 0;
+    for (int k = 0; k + 1 < tk.num_tracks; ++k) t += u >= tk.cdf[k] ? 1 : 0;
+    return t;
+}
+
+// The per-track counters' add: the ordinary vector atomic add on a 64-bit word of device memory (relaxed, device scope).  The counters are
+// device memory by construction, and saying so spares the generic-pointer form of the atomic its test for a scratch address.
+DN_DEV void track_count_add(unsigned long long *p, const unsigned long long v)
+{
+    typedef __attribute__((address_space(1))) unsigned long long global_u64;
+    __hip_atomic_fetch_add((global_u64 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- goal observations (dn_enable_goal) ----------------------------------------------------------------------------------------
 // One row is two 16-byte quads (include/dronenav.h): the vector to target waypoint `idx` from the position the DELIVERED row y shows, and
 // the segment after it, both over max_target_dist, world frame or rotated into the body frame of y's own Euler columns.  A pure function of
@@ -1682,9 +1714,9 @@ DN_DEV void goal_to_body(R v[3], const R sr, const R cr, const R sp, const R cp,
     v[0] = x2; v[1] = cr * y1 + sr * z2; v[2] = cr * z2 - sr * y1;
 }
 template <typename R>
-DN_DEV void goal_store(const DnGoal &g, const DnParams &p, const DnConsts<R> &c, const R *s_tab, float *row, const float y[DN_OBS_DIM], const int idx)
-{
-    const bool more = idx + 1 < p.num_waypoints;
+DN_DEV void goal_store(const DnGoal &g, const int W, const DnConsts<R> &c, const R *s_tab, float *row, const float y[DN_OBS_DIM], const int idx)
+{   // s_tab, W: the rows and the waypoint count of this drone's track (dn_enable_tracks; the one track otherwise)
+    const bool more = idx + 1 < W;
     const R *w = s_tab + idx * DN_T_STRIDE + DN_T_WP;
     const R *w1 = s_tab + (more ? idx + 1 : idx) * DN_T_STRIDE + DN_T_WP;      // per-lane LDS reads; never past the last entry
     R e[3], s[3];
@@ -1709,12 +1741,16 @@ DN_DEV void goal_store(const DnGoal &g, const DnParams &p, const DnConsts<R> &c,
 // What a step kernel hands observe_phase / report_obs for the step at hand (rebuilt every step from the step index: no register of the
 // feature lives across a step): the two rows of this drone and step (trow null where unbound), the index the step leaves (0 where the
 // episode restarted), the index the terminal row takes, and whether the episode ended.
+// tab, W: the track the step was entered with (the step row of an episode that goes on, the terminal row, the reward);  tab + roff, rW:
+// the track of the episode that starts where this one ended (dn_enable_tracks: the reset row's) -- the same pair while the bank is off.
 template <typename R> struct GoalCtx {
     const DnGoal *g;
     const R *tab;
     float *row, *trow;
     int idx, tidx;
     bool done, active;
+    int W;
+    int roff, rW;
 };
 // (exists in the GOAL kernels only: an empty struct elsewhere, so that every other kernel keeps its instruction stream -- see PrivRegs)
 template <typename R, bool ON> struct GoalRegs {
@@ -1727,7 +1763,7 @@ template <typename R>
 DN_DEV void goal_observe(const GoalCtx<R> &x, const DnParams &p, const DnConsts<R> &c, const float y[DN_OBS_DIM])
 {
     float *const dst = x.done ? x.trow : x.row;
-    if (x.active && dst) goal_store<R>(*x.g, p, c, x.tab, dst, y, x.done ? x.tidx : x.idx);
+    if (x.active && dst) goal_store<R>(*x.g, x.W, c, x.tab, dst, y, x.done ? x.tidx : x.idx);
 }
 
 // M (DnModelLevel) >= DN_M_DYN (one-wave option kernels with dn_enable_dynamics): the body of *dk instead of the cf2x constants
@@ -1863,10 +1899,10 @@ template <typename R> struct RulesMid {
     R d, d_prev;
     bool terminated, done;
 };
-template <typename R>
+template <typename R, bool BANK = false>
 DN_DEV Verdict<R> rules_verdict(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const GateRow<R> &row_e,
-                                const Flight<R> &fl, const float4 G3e, RulesMid<R> &m)
-{
+                                const Flight<R> &fl, const float4 G3e, RulesMid<R> &m, const int W_lane = 0)
+{   // BANK (the DN_M_GOAL kernels, dn_enable_tracks): W_lane = the waypoint count of this drone's track, s_tab = that track's first row
 // (explicit fused multiply-adds, no contraction licence: see physics_linear)
     const Meta m_e = unpack_meta(G3e.w);
     const R px = fl.px, py = fl.py, pz = fl.pz;
@@ -1877,7 +1913,7 @@ DN_DEV Verdict<R> rules_verdict(const DnParams &p, const DnConsts<R> &c, const R
     const bool coll1 = collision_common<R>(p, c, px, py, pz, r22n) ||
                        (seg_track && outside_segment_corridor_row<R>(c, row_e, px, py, pz));
     const bool found_now = (R)fl.d_e <= c.threshold;   // :539
-    const bool last_gate = idx + 1 == p.num_waypoints;
+    const bool last_gate = idx + 1 == (BANK ? W_lane : p.num_waypoints);
     R d_prev = (R)fl.dprev_e;
     bool terminated;
     if (coll1) terminated = true;                      // :489-490 (entry _is_done is always False here)
@@ -1959,12 +1995,11 @@ template <typename R, bool SPAWN = false>
 DN_DEV Verdict<R> rules_phase(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const GateRow<R> &row_e, const R (&wp0)[3],
                               const Flight<R> &fl, const float4 G0e, const float4 G3e, float4 *g6_blk, const unsigned li,
                               const bool active, float4 &G0, float4 &G1, float4 &G2, float4 &G3,
-                              const unsigned long long gid = 0ull, const unsigned long long step = 0ull, int *idx_v = nullptr)
+                              const unsigned long long gid = 0ull, const unsigned long long step = 0ull)
 {
     RulesMid<R> m;
     const Verdict<R> v = rules_verdict<R>(p, c, s_tab, row_e, fl, G3e, m);
     rules_commit<R, SPAWN>(c, wp0, fl, m, G0e, G3e, g6_blk, li, active, G0, G1, G2, G3, &p, gid, step);
-    if (idx_v) *idx_v = m.idx;      // the GOAL kernels: the index the verdict leaves, before the auto-reset zeroes the committed one
     return v;
 }
 
@@ -2112,20 +2147,21 @@ DN_DEV Smooth<R> smooth_term(const R ex, const R ey, const R ez, const Vec3R<R> 
     return o;
 }
 // the terms of reward_entry that read the distance pair and the gate index only
-template <typename R, typename FL>
-DN_DEV void reward_entry_core(const DnParams &p, const DnConsts<R> &c, const FL &fl, RewardPre<R> &q)
+template <typename R, typename FL, bool BANK = false>
+DN_DEV void reward_entry_core(const DnParams &p, const DnConsts<R> &c, const FL &fl, RewardPre<R> &q, const int W_lane = 0)
 {
     q.found_now = (R)fl.d_e <= c.threshold;
-    q.last_gate = fl.idx_e + 1 == p.num_waypoints;
+    q.last_gate = fl.idx_e + 1 == (BANK ? W_lane : p.num_waypoints);        // BANK, W_lane: see rules_verdict
     // :555 3 e^{-2d} (v_exp_f32: 1e-7 rel, 1e-8 in the reward) + :556
     const R gain = fl.just_found_e ? R(0.0) : ((R)fl.dprev_e - (R)fl.d_e) * R(3000.0);
     q.r0 = FM<R>::fma(R(3.0), (R)__builtin_amdgcn_exp2f((float)(R(-2.0 * 1.4426950408889634) * (R)fl.d_e)), gain);
 }
-template <typename R>
-DN_DEV RewardPre<R> reward_entry(const DnParams &p, const DnConsts<R> &c, const Flight<R> &fl, const float4 G4, const float4 G5)
+template <typename R, bool BANK = false>
+DN_DEV RewardPre<R> reward_entry(const DnParams &p, const DnConsts<R> &c, const Flight<R> &fl, const float4 G4, const float4 G5, const int W_lane = 0)
 {
     RewardPre<R> q;
-    reward_entry_core<R>(p, c, fl, q);
+    if constexpr (BANK) reward_entry_core<R, Flight<R>, true>(p, c, fl, q, W_lane);
+    else reward_entry_core<R>(p, c, fl, q);
     // smoothness_reward (:599-607) on the stale post-step copies (quirk Q4): -|dv| if |dv| > 0.7 (needs > 160 m/s^2: rare), -|dw| if > 0.3
     const Smooth<R> sl = smooth_term<R>(fl.vex, fl.vey, fl.vez, G4, R(0.7) * R(0.7));
     const Smooth<R> sa = smooth_term<R>(fl.aex, fl.aey, fl.aez, G5, R(0.3) * R(0.3));
@@ -2170,11 +2206,11 @@ DN_DEV void reward_pose(const DnParams &p, const R *s_tab, const FL &fl, const R
     // The orientation term is evaluated once, against the waypoint the taken branch refers to.
     reward_assemble<R>(q, reward_orientation<R>(p, s_tab, fl, q.found_now, q.last_gate), r_normal, r_found32);
 }
-template <typename R>
+template <typename R, bool BANK = false>
 DN_DEV void reward_candidates(const DnParams &p, const DnConsts<R> &c, const R *s_tab, const Flight<R> &fl, const float4 G4,
-                              const float4 G5, R &r_normal, float &r_found32)
+                              const float4 G5, R &r_normal, float &r_found32, const int W_lane = 0)
 {
-    const RewardPre<R> q = reward_entry<R>(p, c, fl, G4, G5);
+    const RewardPre<R> q = reward_entry<R, BANK>(p, c, fl, G4, G5, W_lane);
     reward_pose<R>(p, s_tab, fl, q, r_normal, r_found32);
 }
 // M (DnModelLevel) >= DN_M_SENS (one-wave kernels with dn_enable_sensor): *sx is the kernel's own register copy; the delivered row replaces the true one
@@ -2189,7 +2225,8 @@ DN_DEV Observed<R> observe_phase(const DnParams &p, const DnConsts<R> &c, const 
     Observed<R> ob;
     observe_columns<R>(p, c, fl, ob.o);
     if constexpr (PRIV) priv_true_obs(*px, ob.o);
-    reward_candidates<R>(p, c, s_tab, fl, G4, G5, ob.r_normal, ob.r_found32);
+    if constexpr (GOAL) reward_candidates<R, true>(p, c, s_tab, fl, G4, G5, ob.r_normal, ob.r_found32, gx->W);     // s_tab: this drone's track (dn_enable_tracks)
+    else reward_candidates<R>(p, c, s_tab, fl, G4, G5, ob.r_normal, ob.r_found32);
     // sensor noise / per-drone normaliser act on the step observation (which is also terminal_observation)
     if (NOISE && p.obs_noise_sigma > 0.0f) add_obs_noise(p, gid, step_count, 1u, ob.o);
     if constexpr (SENS) sens_deliver(*sx, step_count, ob.o);
@@ -2305,14 +2342,15 @@ DN_DEV int ret_lo_byte(const double ep_ret, const float hi)
 // The two share only the verdict, so a kernel may run them on two waves; report_phase = both on one.
 // FOUND_BIT: `d_e <= threshold` arrives as found_mail, from the wave that formed it for the reward (the four- / five-wave fused
 // kernels); fl.d_e is not read then.
-template <typename R, bool REW, bool FOUND_BIT = false>
+template <typename R, bool REW, bool FOUND_BIT = false, bool BANK = false>
 DN_DEV void report_scalars(const DnParams &p, const DnConsts<R> &c, const StepOut &out, const Flight<R> &fl, const Verdict<R> &v,
                            const R r_normal, const float r_found32, const unsigned li, const unsigned lane, const bool active,
-                           float4 &G4, float4 &G5, StatAcc &acc, RewNorm &rn, const bool found_mail = false)
+                           float4 &G4, float4 &G5, StatAcc &acc, RewNorm &rn, const bool found_mail = false, const int W_lane = 0,
+                           unsigned long long *track_count = nullptr, const int track_e = 0)
 {
     const bool coll1 = v.coll1 != 0, terminated = v.terminated != 0, truncated = fl.truncated != 0;
     const bool found_now = !coll1 && (FOUND_BIT ? found_mail : (R)fl.d_e <= c.threshold);
-    const bool is_done = found_now && fl.idx_e + 1 == p.num_waypoints;
+    const bool is_done = found_now && fl.idx_e + 1 == (BANK ? W_lane : p.num_waypoints);        // BANK, W_lane: see rules_verdict
     const int found = fl.idx_e + (found_now ? 1 : 0);
     const bool done = terminated || truncated;
     R reward;
@@ -2362,6 +2400,32 @@ DN_DEV void report_scalars(const DnParams &p, const DnConsts<R> &c, const StepOu
         }
         acc.episodes += __popcll(done_ballot); acc.truncated += n_trunc; acc.completed += n_compl;
         acc.sum_len += s_len; acc.sum_found += s_fd; acc.sum_ret_fix += s_ret;
+        // dn_enable_tracks: the same counts per track, under the track the step was entered with.  One add per wave and TRACK, not per
+        // lane: every drone of a track adds to the same five words, and a fleet that was reset together ends together.  The distinct
+        // tracks of the finished lanes are walked on the scalar unit, each one's sums formed as above, and lane 0 adds them.
+        if constexpr (BANK) if (track_count) {
+            for (unsigned long long left = done_ballot; left != 0ull;) {
+                const int t = __builtin_amdgcn_readlane(track_e, __builtin_ctzll(left));
+                const bool mine = done && active && track_e == t;
+                const unsigned long long same = __ballot(mine);
+                const unsigned long long c_compl = __popcll(__ballot(mine && is_done)), c_trunc = __popcll(__ballot(mine && truncated && !terminated));
+                unsigned long long t_len = 0, t_fd = 0;
+                for (unsigned long long m = same; m != 0ull; m &= m - 1ull) {
+                    const int l = __builtin_ctzll(m);
+                    t_len += (unsigned long long)(__builtin_amdgcn_readlane(eplen_e, l) + 1);
+                    t_fd += (unsigned long long)__builtin_amdgcn_readlane(found, l);
+                }
+                if (lane == 0) {
+                    unsigned long long *cnt = track_count + 5 * t;
+                    track_count_add(cnt + 0, (unsigned long long)__popcll(same));
+                    if (c_compl) track_count_add(cnt + 1, c_compl);
+                    if (c_trunc) track_count_add(cnt + 2, c_trunc);
+                    track_count_add(cnt + 3, t_fd);
+                    track_count_add(cnt + 4, t_len);
+                }
+                left &= ~same;
+            }
+        }
     }
     S4.w = (float)ep_ret; S5.w = __int_as_float(ep_len | (ret_lo_byte((double)ep_ret, S4.w) << 24));
     G4 = S4; G5 = S5;
@@ -2408,7 +2472,7 @@ DN_DEV void report_obs(const DnParams &p, const DnConsts<R> &c, float *s_tile, c
                     sens_restart(*sx->sn, sx->n, sx->i, sx->active, p.seed, gid, step_count, sens_slot(*sx->sn, step_count), sx->d, o);
             }
             if constexpr (GOAL) {                                         // the new episode's delivered reset row, against waypoint 0
-                if (active) goal_store<R>(*gx->g, p, c, gx->tab, gx->row, o, 0);
+                if (active && gx->row) goal_store<R>(*gx->g, gx->rW, c, gx->tab + gx->roff, gx->row, o, 0);
             }
             if (NORM) normalize_obs(rms, o);
         }
@@ -2422,9 +2486,11 @@ DN_DEV void report_phase(const DnParams &p, const DnConsts<R> &c, float *s_tile,
                          const Verdict<R> &v, Observed<R> &ob, const unsigned long long gid, const unsigned long long step_count,
                          const unsigned li, const unsigned lane, const unsigned rows, const bool active,
                          float4 &G4, float4 &G5, StatAcc &acc, Rms &rms, RewNorm &rn, SensCtx *sx = nullptr, const PrivCtx *px = nullptr,
-                         const GoalCtx<R> *gx = nullptr)
+                         const GoalCtx<R> *gx = nullptr, unsigned long long *track_count = nullptr, const int track_e = 0)
 {
-    report_scalars<R, REW>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn);
+    if constexpr (M >= DN_M_GOAL) report_scalars<R, REW, false, true>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn, false, gx->W,
+                                                                      track_count, track_e);
+    else report_scalars<R, REW>(p, c, out, fl, v, ob.r_normal, ob.r_found32, li, lane, active, G4, G5, acc, rn);
     report_obs<R, NORM, NOISE, TILE, SPAWN, M>(p, c, s_tile, out, fl.truncated != 0, v, ob.o, gid, step_count, li, lane, rows, active,
                                                               rms, sx, px, gx);
 }
@@ -2532,13 +2598,14 @@ DN_DEV float4 sample_action(const DnStepIO &io, const unsigned long long gid, co
 //   DN_M_SENS  + dn_enable_sensor's state; the actuator's pointers are null when it is off (latency 0, no lag, nothing drawn or stored)
 //   DN_M_PRIV  + dn_bind_privileged's rows; the sensor's pointers are null when the sensor model is off (latency 0, no bias, no ring)
 //   DN_M_GOAL  + dn_bind_goal's rows; the privileged rows are off (groups 0, null pointers) unless they are enabled and bound too
+//              + dn_enable_tracks' bank (the same level: null pointers when it is off, null goal rows when those are unbound)
 template <bool DYN> struct DynArg : DnDyn {};
 template <> struct DynArg<false> {};
 struct WindArg : DnDyn { DnWind w; };
 struct ActArg : WindArg { DnAct a; };
 struct SensArg : ActArg { DnSens s; };
 struct PrivArg : SensArg { DnPriv pv; };
-struct GoalArg : PrivArg { DnGoal gl; };
+struct GoalArg : PrivArg { DnGoal gl; DnTrack tk; };
 template <int M> struct StepArg { using type = DynArg<false>; };
 template <> struct StepArg<DN_M_DYN> { using type = DynArg<true>; };
 template <> struct StepArg<DN_M_WIND> { using type = WindArg; };
@@ -2601,8 +2668,22 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         }
         A = act_consume(dy.a, act, p.n, li, i, 0, LAT, unpack_meta(G3.w).steps);
     }
-    stage_table<R>(p, s_tab);
+    // dn_enable_tracks: this drone's track word (track_word), held in one register across the launch; it changes at an episode start only.
+    // Bank off (launch-uniform): row 0 and the one track's count.
+    [[maybe_unused]] int TW = 0;
+    [[maybe_unused]] bool bank = false;
+    if constexpr (GOAL) {
+        bank = dy.tk.track != nullptr;
+        stage_table<R, true>(p, s_tab, bank ? dy.tk.total : p.num_waypoints);
+    } else stage_table<R>(p, s_tab);
     block_lds_barrier();
+    // (the track word is loaded AFTER the barrier on purpose: loaded before it, one instantiation -- float32, noise, fused -- met a fault
+    // of the compiler's back end, an illegal v_cmp_ne_u32 0, src_private_base left by register allocation: seen with ROCm 7.2.0's
+    // AMD clang 22.0.0git (roc-7.2.0 26014), where the build stops with "Illegal instruction detected")
+    if constexpr (GOAL) {
+        TW = p.num_waypoints << 8;
+        if (bank) TW = track_word(dy.tk, dy.tk.track[i]);
+    }
     const long long n = p.n, words = (p.n + 63) / 64;
     DnStatSlot slot0;
     if (ONE) slot0 = p.st.stats[blockIdx.x];                               // single-step launch: the whole slot now (see flush_stats_preloaded)
@@ -2652,7 +2733,10 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         const StepOut out = block_out(io0, tile_base, (long long)t * n, (long long)t * words);
         const unsigned long long sc = sc0 + (unsigned long long)t;
         float4 rpm_now;
-        const GateRow<R> row_e = load_gate_row<R>(s_tab, unpack_meta(G3.w).idx);
+        // GOAL: the first table row of this drone's track, its waypoint count and its number, as the step is entered
+        [[maybe_unused]] const R *const tab = s_tab + (GOAL ? (TW & 0xFF) * DN_T_STRIDE : 0);
+        [[maybe_unused]] const int W_lane = (TW >> 8) & 0xFF, track_e = TW >> 16;
+        const GateRow<R> row_e = load_gate_row<R>(GOAL ? tab : s_tab, unpack_meta(G3.w).idx);
         WindF<R> wf;
         if constexpr (WIND) wf = wind_force<R>(dy.w, WB, WG);
         if constexpr (PRIV) {                           // the rotor speeds this step is entered with (the terminal row's)
@@ -2661,18 +2745,33 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         Flight<R> fl = fly<R, NOISE, XOPT, M>(p, gid, sc, A, G0, G1, G2, G3, G7, rpm_now, XOPT ? pid_st : nullptr, DYN ? &dk : nullptr,
                                               WIND ? &wf : nullptr, &lag, lag_on);
         const float4 G0e = G0, G3e = G3;
-        int *idx_v = nullptr;
-        if constexpr (GOAL) idx_v = &gr.x.tidx;
-        const Verdict<R> v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc, idx_v);
-        if (XOPT && p.drag) G7 = (v.terminated || fl.truncated) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : rpm_now;   // BaseAviary.py:442,545
+        Verdict<R> v;
         if constexpr (GOAL) {
+            // rules_phase taken apart: the track of the episode that starts here is drawn between the verdict and the commit, which
+            // measures the fresh episode against ITS waypoint 0 (read from the table inside the commit's reset branch only)
+            RulesMid<R> m;
+            v = rules_verdict<R, true>(p, c, tab, row_e, fl, G3e, m, W_lane);
+            const int TWe = TW;
+            if (bank && __ballot(m.done) != 0ull) {         // wave-uniform: the episode ends of this step
+                if (m.done) {
+                    if (dy.tk.resample) {
+                        const int t_new = track_draw(dy.tk, p.seed, gid, sc);
+                        TW = track_word(dy.tk, t_new);
+                        if (active) dy.tk.track[i] = t_new;
+                    }
+                    if (active) dy.tk.finished[i] = track_e;
+                }
+            }
+            const R *rtab = s_tab + (TW & 0xFF) * DN_T_STRIDE;
+            rules_commit<R, XOPT>(c, *reinterpret_cast<const R (*)[3]>(rtab + DN_T_WP), fl, m, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, &p, gid, sc);
             // this step's rows; the step row takes the committed index (0 where the episode restarted), the terminal row the verdict's,
-            // held to the last waypoint (a completed track leaves W)
+            // held to the last waypoint of the entry track (a completed track leaves W)
             const long long at = ((long long)t * n + i) * DN_GOAL_DIM;
-            const int tidx = gr.x.tidx < p.num_waypoints - 1 ? gr.x.tidx : p.num_waypoints - 1;
-            gr.x = {&dy.gl, s_tab, dy.gl.rows + at, dy.gl.term ? dy.gl.term + at : nullptr, unpack_meta(G3.w).idx, tidx,
-                    v.terminated || fl.truncated, active};
-        }
+            const int tidx = m.idx < W_lane - 1 ? m.idx : W_lane - 1;
+            gr.x = {&dy.gl, tab, dy.gl.rows ? dy.gl.rows + at : nullptr, dy.gl.term ? dy.gl.term + at : nullptr, unpack_meta(G3.w).idx, tidx,
+                    m.done, active, W_lane, ((TW & 0xFF) - (TWe & 0xFF)) * DN_T_STRIDE, (TW >> 8) & 0xFF};
+        } else v = rules_phase<R, XOPT>(p, c, s_tab, row_e, wp0, fl, G0e, G3e, b.g6, li, active, G0, G1, G2, G3, gid, sc);
+        if (XOPT && p.drag) G7 = (v.terminated || fl.truncated) ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : rpm_now;   // BaseAviary.py:442,545
         if constexpr (PRIV) {
             // the terminal row's parameters are those the step was ENTERED with: stored before the episode starts below redraw them
             pr.x.done = v.terminated || fl.truncated;
@@ -2716,9 +2815,11 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_step_many_1w_kernel(const DnParam
         }
         attitude_phase<R>(fl);
         if constexpr (SENS) sx.k = unpack_meta(G3e.w).steps + 1;    // control steps of the episode flown once this step is over
-        Observed<R> ob = observe_phase<R, NORM, NOISE, M>(p, c, s_tab, fl, G4, G5, gid, sc, rms, &sx, px, gx);
-        report_phase<R, NORM, NOISE, XOPT, 0, XOPT, M>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn,
-                                                       &sx, px, gx);
+        Observed<R> ob = observe_phase<R, NORM, NOISE, M>(p, c, GOAL ? tab : s_tab, fl, G4, G5, gid, sc, rms, &sx, px, gx);
+        if constexpr (GOAL) report_phase<R, NORM, NOISE, XOPT, 0, XOPT, M>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn,
+                                                                           &sx, px, gx, bank ? dy.tk.count : nullptr, track_e);
+        else report_phase<R, NORM, NOISE, XOPT, 0, XOPT, M>(p, c, s_tile, out, fl, v, ob, gid, sc, li, lane, rows, active, G4, G5, acc, rms, rn,
+                                                            &sx, px, gx);
         if constexpr (PRIV) {
             // the step row's parameters: what the getters would return after this step (a restarted drone: the new episode's draws)
             if (active) {
@@ -4339,7 +4440,7 @@ __global__ __launch_bounds__(3 * DN_BLOCK) void dn_step_pqx_kernel(const DnParam
 // =====================================================================================================
 template <typename R>
 __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, float *obs, const DnDyn dy, const DnWind wd, const DnAct ac,
-                                                            const DnSens sn, const DnPriv pv, const DnGoal gl)
+                                                            const DnSens sn, const DnPriv pv, const DnGoal gl, const DnTrack tk)
 {
     __shared__ R s_tab[DN_MAX_WAYPOINTS * DN_T_STRIDE];
     __shared__ __attribute__((aligned(16))) float s_tile[DN_BLOCK * DN_OBS_DIM];
@@ -4354,14 +4455,24 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
     const DnConsts<R> &c = consts<R>(p);
     const BlockState b = block_state(p.st, tile_base);
     const float4 G0 = b.g0[li], G3 = b.g3[li], G6 = b.g6[li];
-    stage_table<R>(p, s_tab);
+    const unsigned long long gid = (unsigned long long)(p.env_id_offset + i);
+    // dn_enable_tracks: the track this episode flies -- drawn here (resample) or what dn_set_tracks wrote; `tab` = its first table row
+    int TW = p.num_waypoints << 8;
+    if (tk.track) {
+        if (tk.resample) {
+            const int t_new = track_draw(tk, p.seed, gid, p.st.stats[blockIdx.x].step_count);
+            TW = track_word(tk, t_new);
+            if (active) tk.track[i] = t_new;
+        } else TW = track_word(tk, tk.track[i]);
+    }
+    stage_table<R, true>(p, s_tab, tk.track ? tk.total : p.num_waypoints);
     block_lds_barrier();
+    const R *tab = s_tab + (TW & 0xFF) * DN_T_STRIDE;
     const Meta m = unpack_meta(G3.w);
     R cpx, cpy, cpz;
     if (m.steps > 0) { cpx = G0.x; cpy = G0.y; cpz = G0.z; } else { cpx = G6.x; cpy = G6.y; cpz = G6.z; }
     float o[DN_OBS_DIM];
     reset_obs<R>(p, c, (R)G0.w, o);
-    const unsigned long long gid = (unsigned long long)(p.env_id_offset + i);
     float sx = (float)c.spawn[0], sy = (float)c.spawn[1], sz = (float)c.spawn[2];
     if (p.random_spawn) {                  // this episode's INIT_XYZS[0]; _current_position follows it (PBDroneEnv.py:624-626)
         double q[3];
@@ -4378,14 +4489,14 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
         int d = 0;
         sens_restart(sn, p.n, i, active, p.seed, gid, sc, sens_slot(sn, sc - 1ull), d, o);
     }
-    if (gl.rows && active) goal_store<R>(gl, p, c, s_tab, gl.rows + i * DN_GOAL_DIM, o, 0);     // dn_bind_goal: the delivered reset row, slot 0
+    if (gl.rows && active) goal_store<R>(gl, (TW >> 8) & 0xFF, c, tab, gl.rows + i * DN_GOAL_DIM, o, 0);     // dn_bind_goal: the delivered reset row, slot 0
     if (p.normalize_obs) {
         Rms rms;
         load_rms(p, i, rms);
         normalize_obs(rms, o);
         if (active) store_rms(p, i, rms);
     }
-    const R ex = cpx - s_tab[0], ey = cpy - s_tab[1], ez = cpz - s_tab[2];
+    const R ex = cpx - tab[0], ey = cpy - tab[1], ez = cpz - tab[2];
     const R d = FM<R>::sqrt0(FM<R>::fma(ez, ez, FM<R>::fma(ey, ey, ex * ex)));
     if (active) {
         b.g0[li] = make_float4(sx, sy, sz, (float)d);
@@ -4842,13 +4953,14 @@ hipError_t dn_launch_step_many(const DnParams &p, const DnStepIO &io, int k, boo
         // a model is on: the kernel of the deepest one's level, whatever `waves` says.  A model that is off rides along as its
         // value-initialised struct (null pointers): the nominal body, still air, no latency, no bias.
         if (io.mean) return hipErrorInvalidValue;       // the sampling-fused kernels carry no model (the C ABI refuses them first)
-        const bool priv = m->priv.groups && m->priv.rows, goal = level == DN_M_GOAL;    // rows are written where enabled AND bound
+        const bool priv = m->priv.groups && m->priv.rows, goal = m->goal.on && m->goal.rows;    // rows are written where enabled AND bound
         GoalArg sa;
         static_cast<DnDyn &>(sa) = m->dyn;
-        sa.w = m->wind; sa.a = m->act; sa.s = m->sens; sa.pv = m->priv; sa.gl = m->goal;
+        sa.w = m->wind; sa.a = m->act; sa.s = m->sens; sa.pv = m->priv; sa.gl = m->goal; sa.tk = m->track;
         if (priv && k > m->priv.cap) return hipErrorInvalidValue;   // the C ABI refuses it first
         if (goal && k > m->goal.cap) return hipErrorInvalidValue;   // likewise
-        if (goal && !priv) sa.pv = DnPriv{};                        // enabled but unbound: this level writes no privileged rows either
+        if (!priv) sa.pv = DnPriv{};                                // enabled but unbound: the goal level writes no privileged rows either
+        if (!goal) sa.gl.rows = sa.gl.term = nullptr;               // the track bank without bound goal rows: the goal level writes none
         dn_level([&](auto M) {
             if constexpr (decltype(M)::value == DN_M_DYN) launch_models<DN_M_DYN>(L, DynArg<true>{static_cast<const DnDyn &>(sa)});
             else launch_models<decltype(M)::value>(L, sa);
@@ -4873,8 +4985,8 @@ hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t 
 {
     const DnModels on = m ? *m : DnModels{};
     const unsigned grid = (unsigned)((p.n + DN_BLOCK - 1) / DN_BLOCK);
-    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv, on.goal);
-    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv, on.goal);
+    if (f32) hipLaunchKernelGGL(dn_reset_kernel<float>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv, on.goal, on.track);
+    else hipLaunchKernelGGL(dn_reset_kernel<double>, dim3(grid), dim3(DN_BLOCK), 0, stream, p, obs, on.dyn, on.wind, on.act, on.sens, on.priv, on.goal, on.track);
     return hipGetLastError();
 }
 

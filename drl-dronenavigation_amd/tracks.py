@@ -91,3 +91,86 @@ def default_track():
 REGISTRY = {"circle": circle, "circle4": lambda: circle(1, 4, 1), "circle6": lambda: circle(1, 6, 1),
             "reaching": reaching, "race": reaching, "up": up, "half_up_forward": half_up_forward,
             "up_circle": up_circle, "up_sharp_back_turn": up_sharp_back_turn}
+
+
+MAX_TRACKS = 64
+MAX_BANK_WAYPOINTS = 64
+
+
+class TrackBank:
+    """Several tracks for one fleet (dn_enable_tracks): each episode of a drone flies one of them.
+
+    `tracks`: 1..64 non-circle `Track`s with equal `initial_xyzs` and `aviary_dim` and at most 64 waypoints in all; track 0 is the
+    env's own track.  `weights` (default: uniform): the draw weights, finite, >= 0, not all zero; a zero weight is never drawn.
+    `resample=True`: every episode start draws the drone's track; False: a drone keeps the track `DroneVecEnv.set_tracks` gave it
+    (track 0 until then).  Validates on the CPU what dn_enable_tracks refuses."""
+
+    def __init__(self, tracks, weights=None, resample=True):
+        tracks = list(tracks)
+        if not 1 <= len(tracks) <= MAX_TRACKS:
+            raise ValueError(f"a bank holds 1..{MAX_TRACKS} tracks (got {len(tracks)})")
+        for k, t in enumerate(tracks):
+            if not isinstance(t, Track):
+                raise TypeError(f"tracks[{k}] must be a drl_dronenavigation_amd.tracks.Track")
+            if t.is_circle:
+                raise ValueError(f"tracks[{k}] is a circle track: the bank holds corridor tracks only")
+            if len(t.waypoints) < 1:
+                raise ValueError(f"tracks[{k}] has no waypoints")
+            if not np.all(np.isfinite(t.waypoints)):
+                raise ValueError(f"tracks[{k}] has a waypoint that is not finite")
+            if not (np.array_equal(t.initial_xyzs, tracks[0].initial_xyzs) and np.array_equal(t.aviary_dim, tracks[0].aviary_dim)):
+                raise ValueError(f"tracks[{k}] differs from tracks[0] in initial_xyzs or aviary_dim: a bank shares one spawn and one box")
+        total = sum(len(t.waypoints) for t in tracks)
+        if total > MAX_BANK_WAYPOINTS:
+            raise ValueError(f"the bank has {total} waypoints in all: at most {MAX_BANK_WAYPOINTS}")
+        w = np.ones(len(tracks), np.float32) if weights is None else np.asarray(weights, dtype=np.float32).reshape(-1)
+        if w.shape != (len(tracks),):
+            raise ValueError(f"weights must hold one value per track ({len(tracks)}), got {w.shape[0]}")
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("weights must be finite and >= 0")
+        if not np.any(w > 0):
+            raise ValueError("every weight is zero: no track could be drawn")
+        self.tracks = tracks
+        self.weights = w
+        self.resample = bool(resample)
+
+    def __len__(self):
+        return len(self.tracks)
+
+    @property
+    def num_waypoints(self):
+        return [len(t.waypoints) for t in self.tracks]
+
+    def cdf(self):
+        """The cumulative weights the draw compares u with: float64 partial sums of the float32 weights over their total."""
+        s = np.cumsum(self.weights.astype(np.float64))
+        return s / s[-1]
+
+    @staticmethod
+    def draw(cdf, u):
+        """The track for the uniform u in (0, 1): the number of k in 0..T-2 with u >= cdf[k]."""
+        cdf = np.asarray(cdf, np.float64)
+        return (np.asarray(u, np.float64)[..., None] >= cdf[:-1]).sum(axis=-1).astype(np.int32)
+
+    def to_c(self):
+        from . import _capi
+        c = _capi.DnTrackBankConfig()
+        c.num_tracks = len(self.tracks)
+        flat = np.concatenate([t.waypoints for t in self.tracks]).ravel()
+        for k, t in enumerate(self.tracks):
+            c.num_waypoints[k] = len(t.waypoints)
+            c.weight[k] = float(self.weights[k])
+        for j, v in enumerate(flat):
+            c.waypoints[j] = float(v)
+        c.resample = int(self.resample)
+        c.reserved = 0
+        return c
+
+    @classmethod
+    def from_c(cls, c, initial_xyzs, aviary_dim):
+        pts = np.array(c.waypoints[:], np.float64).reshape(-1, 3)
+        tracks, row = [], 0
+        for k in range(c.num_tracks):
+            tracks.append(Track(pts[row:row + c.num_waypoints[k]].copy(), initial_xyzs, aviary_dim))
+            row += c.num_waypoints[k]
+        return cls(tracks, np.array(c.weight[:c.num_tracks], np.float32), bool(c.resample))

@@ -105,7 +105,8 @@ typedef struct dn_config {
  * checkpointing).  Field names follow the reference's attributes.  It does not carry the body scales of
  * dn_enable_dynamics: a checkpoint of a randomised fleet is dn_get_state + dn_get_dynamics (restore: dn_set_state + dn_set_dynamics),
  * nor the wind of dn_enable_wind (+ dn_get_wind / dn_set_wind), nor the actuator state of dn_enable_actuator (+ dn_get_actuator /
- * dn_set_actuator), nor the sensor state of dn_enable_sensor (+ dn_get_sensor / dn_set_sensor). */
+ * dn_set_actuator), nor the sensor state of dn_enable_sensor (+ dn_get_sensor / dn_set_sensor), nor the track of dn_enable_tracks
+ * (+ dn_get_tracks; restore: dn_set_tracks BEFORE dn_set_state, which holds idx to the drone's own track). */
 typedef struct dn_env_state {
     float pos[3], quat[4], vel[3], ang_v[3];    /* Bullet base state, BaseAviary.py:596-598 (quat = x,y,z,w) */
     float prev_vel[3], prev_ang_v[3];           /* PBDroneEnv.prev_vel / prev_ang_v */
@@ -660,6 +661,65 @@ int32_t dn_get_goal_config(const dn_env *env, dn_goal_config *out);
  * enabled but unbound writes nothing and launches the kernels it would launch without the feature.  DN_ERR_BAD_STATE if the feature is
  * not enabled.  The buffers must outlive the binding; a launch captured in a hipGraph bakes the pointers in. */
 int32_t dn_bind_goal(dn_env *env, float *rows, float *terminal_rows, int64_t capacity_steps);
+
+/* Track bank: each drone of a fleet flies one of several tracks.  A bank is T tracks, 1 <= T <= DN_MAX_TRACKS; track t has W_t >= 1
+ * waypoints, given one track after the other in `waypoints`; the sum of W_t is at most DN_MAX_WAYPOINTS (the 64-entry corridor table the
+ * kernels stage into LDS holds the whole bank, so LDS use and occupancy of no kernel change).  All tracks share the env's spawn,
+ * aviary_dim, threshold and max_steps.  Track 0 must equal the track of dn_config -- the same count and bit-equal waypoints -- so that
+ * enabling the bank on a flying fleet changes nothing for any drone.
+ *   Definition: the table rows of track t are the rows a dn_config with that one track gets (including row 0 of each track, whose base
+ *   point is the spawn); the library builds both with the same function.  For a drone on track t everything the step does with waypoints
+ *   uses t's rows and W_t: the gate row, the corridor of the next segment, the last gate (completion and its +200), observation column
+ *   12, the orientation reward, the fresh episode's distance to waypoint 0, the goal rows (wp[i], wp[i+1], i + 1 < W_t) and the terminal
+ *   goal index min(idx, W_t - 1).  The step of the drone's own track is unchanged in every bit: a bank drone on track t equals the same
+ *   drone (same num_envs, seed, env_id_offset, actions) of an env created with track t alone.  idx in dn_env_state and found_targets stay
+ *   the index within the drone's track.
+ *   Per drone: track (the track of its current episode) and finished (the track of its most recently ended episode, -1 before the
+ *   first), int32, in one allocation of the model's own outside dn_state_bytes.
+ *   Draw (resample = 1): every episode start -- dn_reset and every in-kernel auto-reset -- draws the track with ONE Philox4x32-10 call
+ *   keyed like the other models: (seed; global drone id, the vector step the episode starts on, stream 22).
+ *     u = (r_0 + 0.5) / 2^32 in float64;  cdf_k = S_k / S_{T-1}, S = the float64 partial sums of the float32 weights in index order
+ *     (formed on the host);  t = the number of k in 0..T-2 with u >= cdf_k.  A zero weight is never drawn.
+ *   The new track is the one the reset row, the reset goal row and the fresh d / d_prev are measured on; the terminal observation, the
+ *   terminal goal row, the reward, found_targets and `finished` belong to the track the step was entered with.
+ *   (As in every auto-reset, the fresh distance is measured from the position the reference keeps in _current_position, not from the
+ *   spawn, and the reset row's column 12 shows the ended episode's distance; likewise the first dn_reset after dn_set_tracks shows the
+ *   distance the state held.)
+ *   Checkpoint of a bank fleet: dn_get_state + dn_get_tracks (+ the models' getters); restore as dn_set_tracks, THEN dn_set_state, which
+ *   holds every idx to the waypoint count of the track the drone is on at that moment (DN_ERR_INVALID_ARGUMENT beyond it).  `finished`
+ *   and the counters are reporting state and are not restored.
+ *   resample = 0: a drone keeps its track across episode starts (dn_set_tracks writes it).
+ *   Per-track counters, int64 [T][5], added at episode ends under the entry track, inside fused launches too:
+ *   episodes, completed, truncated, sum of found_targets at episode end, sum of episode lengths.
+ * The bank rides in the goal family of the one-wave option kernels (with the goal rows unbound that family writes none): enabling forces
+ * dn_get_kernel_waves(env, 0 / 1) == 1, and dn_step_sampled, dn_step_squashed, dn_mlp_step_sampled and dn_eval_kinematics refuse the env.
+ * Layout: num_tracks at 0, num_waypoints at 4, waypoints at 264 (8-byte aligned), weight at 1800, resample at 2056, reserved at 2060;
+ * 2064 bytes. */
+#define DN_MAX_TRACKS 64
+typedef struct dn_track_bank_config {
+    int32_t num_tracks;                         /* T, 1..DN_MAX_TRACKS */
+    int32_t num_waypoints[DN_MAX_TRACKS];       /* W_t, each >= 1, sum <= DN_MAX_WAYPOINTS */
+    double  waypoints[DN_MAX_WAYPOINTS * 3];    /* the tracks' waypoints one track after the other, row-major xyz */
+    float   weight[DN_MAX_TRACKS];              /* draw weights, finite and >= 0, not all zero (resample = 1) */
+    int32_t resample, reserved;                 /* resample: 0 or 1; reserved: must be 0 */
+} dn_track_bank_config;
+/* The first call allocates and sets track = 0, finished = -1 and zero counters; a later call with the same geometry (counts and
+ * waypoints) changes weights and resample and keeps the assignment; a later call with another geometry is refused.
+ * DN_ERR_INVALID_ARGUMENT: a circle env; random_spawn (the spawn draw reads track lines); counts out of range or a sum over
+ * DN_MAX_WAYPOINTS; non-finite waypoints; negative or non-finite weights, or all weights zero; track 0 different from the config's;
+ * reserved != 0.  An env created with DN_GROUND_CONTACT_AUTO resolves the term again over every track of the bank (on if any track
+ * needs it); dn_get_config returns the result. */
+int32_t dn_enable_tracks(dn_env *env, const dn_track_bank_config *cfg);
+/* track: int32[N] on the device.  Writes the assignment and does not touch the state: reset afterwards.  Values are not validated (the
+ * kernels hold an index to the bank).  DN_ERR_BAD_STATE before dn_enable_tracks. */
+int32_t dn_set_tracks(dn_env *env, const int32_t *track, void *stream);
+/* track, finished: int32[N] on the device; either may be NULL.  DN_ERR_BAD_STATE before dn_enable_tracks. */
+int32_t dn_get_tracks(dn_env *env, int32_t *track, int32_t *finished, void *stream);
+/* out: int64[T][5] on the host (synchronises the device); reset != 0 zeroes the counters afterwards.  DN_ERR_BAD_STATE before
+ * dn_enable_tracks. */
+int32_t dn_get_track_stats(dn_env *env, int64_t *out, int32_t reset);
+/* *out = the configuration last given to dn_enable_tracks.  DN_ERR_BAD_STATE before dn_enable_tracks (*out untouched). */
+int32_t dn_get_track_bank_config(const dn_env *env, dn_track_bank_config *out);
 
 #ifdef __cplusplus
 }

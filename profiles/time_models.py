@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of the step kernels with and without one of the per-drone models, interleaved A/B:
-    python3 profiles/time_models.py MODEL [reps] [configs]    (MODEL: dynamics, wind, actuator, sensor, privileged or goal; configs: a comma
+    python3 profiles/time_models.py MODEL [reps] [configs]    (MODEL: dynamics, wind, actuator, sensor, privileged, goal or tracks; configs: a comma
                                                                list of the model's configuration names below; default all of them)
 The A/B against another tree (without the model) runs the configurations that tree knows from a checkout of each tree in turn.
 Each launch is timed by the two events dn_set_launch_events attaches to its own dispatch (the kernel alone, as a kernel trace sees it);
@@ -46,6 +46,13 @@ goal (dn_enable_goal)
   goal-world     the same with GoalObservation(frame="world"): the goal family, 32 bytes stored per drone-step
   goal-body      the same with frame="body": three float32 sin / cos pairs and two rotations per row as well
   The fused launch binds step rows only (no want_terminal); the single steps are step_tensor's default, both row buffers bound.
+tracks (dn_enable_tracks)
+  goal-world     the goal configuration of that name, no bank: the goal family as a fleet on one track runs it (and the configuration a tree
+                 without the bank knows, under `goal`: the A/B of the goal family with the bank off against that tree)
+  bank-fixed     the same with TrackBank(T = 6, uniform weights, resample=False): the race track and its first 7, 6, 5, 4 and 3 gates, 33
+                 table rows; every drone stays on track 0 (no assignment is written), so the same trajectories as `goal-world`
+  bank-draw      the same with resample=True: one Philox call and two 4-byte stores per episode start, and six tracks flown
+  The fused launch binds step rows only (no want_terminal); the single steps are step_tensor's default, both row buffers bound.
 
 Every model's rows carry <config>_over_<baseline>_<kind> for each of its own configurations against its baseline (the first
 configuration; `opt` for wind); dynamics keeps the names it was first measured under (dr_over_opt, dr_over_ref, dr1_over_opt).
@@ -76,7 +83,12 @@ def configs(model):
     gust = dict(wind=pkg.WindDisturbance(**STEADY, **GUST))
     act = dict(dr, **gust, actuator=pkg.ActuatorModel(latency=(0, 8)))
     sens = dict(act, sensor=pkg.SensorModel(latency=(0, 8), bias=0.02))
+    race = tracks.reaching()
+    bank = [race] + [tracks.Track(race.waypoints[:k], race.initial_xyzs, race.aviary_dim) for k in (7, 6, 5, 4, 3)]
+    goal = dict(sens, goal=pkg.GoalObservation(frame="world"))
     return {
+        "tracks": {"goal-world": goal, "bank-fixed": dict(goal, tracks=pkg.TrackBank(bank, resample=False)),
+                   "bank-draw": dict(goal, tracks=pkg.TrackBank(bank, resample=True))},
         "dynamics": {"opt": {}, "opt+dr": dr, "opt+dr1": dict(dynamics=pkg.DynamicsRandomization(resample=True)), "ref": REF},
         "wind": {"opt": {}, "opt+wind": dict(wind=pkg.WindDisturbance(**STEADY)), "opt+gust": gust, "opt+dr+gust": dict(dr, **gust), "ref": REF},
         "actuator": {"dr+gust": dict(dr, **gust), "act-off": dict(dr, **gust, actuator=pkg.ActuatorModel()), "act+lat": act,
@@ -90,7 +102,7 @@ def configs(model):
     }[model]
 
 
-BASELINE = {"wind": "opt", "actuator": "dr+gust", "sensor": "act", "privileged": "sens", "goal": "sens"}
+BASELINE = {"wind": "opt", "actuator": "dr+gust", "sensor": "act", "privileged": "sens", "goal": "sens", "tracks": "goal-world"}
 # (key, numerator, denominator) of the ratio columns; dynamics keeps the names of its committed results
 RATIOS = {m: [(f"{nm}_over_{b}", nm, b) for nm in configs(m) if nm not in (b, "opt", "ref")] for m, b in BASELINE.items()}
 RATIOS["dynamics"] = [("dr_over_opt", "opt+dr", "opt"), ("dr_over_ref", "opt+dr", "ref"), ("dr1_over_opt", "opt+dr1", "opt")]
