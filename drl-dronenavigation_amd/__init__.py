@@ -18,6 +18,7 @@ from .goal import GoalObservation, GOAL_DIM, GOAL_FRAMES, GOAL_SLICES  # noqa: F
 
 __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
            "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor",
+           "FusedMlpPolicy", "MlpValue", "FusedMlpValue",
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
            "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES"]
@@ -33,12 +34,12 @@ def __getattr__(name):
                 "FusedRolloutCollector"):
         collector = importlib.import_module(__name__ + ".collector")
         return collector if name == "collector" else getattr(collector, name)
-    if name in ("policy_mfma", "FusedMlpPolicy", "FusedSacActor"):
+    if name in ("policy_mfma", "FusedMlpPolicy", "FusedSacActor", "FusedMlpValue"):
         pm = importlib.import_module(__name__ + ".policy_mfma")
         return pm if name == "policy_mfma" else getattr(pm, name)
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
-    if name in ("policy", "MlpActorCritic", "SacActor"):
+    if name in ("policy", "MlpActorCritic", "SacActor", "MlpValue"):
         policy = importlib.import_module(__name__ + ".policy")
         return policy if name == "policy" else getattr(policy, name)
     raise AttributeError(name)

@@ -103,10 +103,11 @@ class RolloutGather:
 
 
 def _refuse_privileged(env, who):
-    """The collectors built on the 16-input policy kernels (dn_mlp_forward takes obs_dim <= 16) cannot feed a critic the 52-wide rows."""
+    """The fused collectors evaluate actor and critic in one launch over one input, the 13-column observation their step path hands on:
+    they cannot feed a critic the 52-wide rows."""
     if getattr(env, "privileged", None) is not None:
-        raise ValueError(f"{who} does not carry privileged observations (its critic kernel, dn_mlp_forward, takes at most 16 inputs); "
-                         "use RolloutCollector(..., value_input='privileged') with a torch value_fn")
+        raise ValueError(f"{who} does not carry privileged observations (its step path shows actor and critic the same 13-column observation); "
+                         "use RolloutCollector(..., value_input='privileged') with value_fn=FusedMlpValue(MlpValue(52), ...) or a torch value_fn")
 
 
 def _refuse_tracks(env, who):
@@ -121,7 +122,8 @@ def _refuse_goal(env, who):
     written by another kernel family, which carries no sampling-fused entry point."""
     if getattr(env, "goal", None) is not None:
         raise ValueError(f"{who} does not carry goal observations (its policy kernels read the 13-column observation); "
-                         "use RolloutCollector(..., policy_input='observation+goal') with a torch policy")
+                         "use RolloutCollector(..., policy_input='observation+goal') with FusedMlpPolicy(MlpActorCritic(obs_dim=21), ...) "
+                         "or a torch policy")
 
 
 class RolloutCollector:
@@ -528,6 +530,9 @@ class FusedRolloutCollector:
             raise TypeError("FusedRolloutCollector needs a DroneVecEnv and a FusedMlpPolicy (HIP); there is no CPU path")
         if env.num_envs % 4 or env.obs_dim != OBS_DIM:
             raise ValueError("num_envs must be a multiple of 4 and the observation the full 13 columns")
+        if policy.pi["obs_dim"] != OBS_DIM or policy.vf["obs_dim"] != OBS_DIM:      # dn_mlp_step_sampled takes the pointers without the widths
+            raise ValueError(f"FusedRolloutCollector feeds its policy the {OBS_DIM}-column observation; the policy was packed for "
+                             f"{policy.pi['obs_dim']} (actor) / {policy.vf['obs_dim']} (critic) columns")
         self.env, self.policy = env, policy
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
         self.bootstrap_truncated, self.gather, self.group, self.use_graph = bool(bootstrap_truncated), bool(gather), group, bool(use_graph)

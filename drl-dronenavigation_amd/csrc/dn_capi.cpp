@@ -1649,11 +1649,14 @@ int32_t dn_mlp_forward(const dn_mlp_net *nets, int32_t num_nets, const float *ob
     if (!nets || !obs) return fail(DN_ERR_INVALID_ARGUMENT, "nets and obs are required");
     if (num_nets < 1 || num_nets > 2) return fail(DN_ERR_INVALID_ARGUMENT, "num_nets must be 1 or 2 (got %d)", num_nets);
     if (num_envs < 1) return fail(DN_ERR_INVALID_ARGUMENT, "num_envs must be >= 1");
-    if (obs_dim < 1 || obs_dim > 16) return fail(DN_ERR_INVALID_ARGUMENT, "obs_dim must be in 1..16 (got %d)", obs_dim);
     for (int k = 0; k < num_nets; ++k) {
         const dn_mlp_net &n = nets[k];
         if (n.arch != DN_MLP_ARCH_PPO && n.arch != DN_MLP_ARCH_SAC)
             return fail(DN_ERR_INVALID_ARGUMENT, "net %d: arch must be 0 (PPO 512-512-256 Tanh) or 1 (SAC actor 256-256 ReLU)", k);
+        // rows of up to 64 columns for the PPO networks (dn_mlp_wide.hip beyond 16), of up to 16 for the SAC actor
+        if (n.arch == DN_MLP_ARCH_PPO ? dn_mlp_ks1(obs_dim) == 0 : dn_mlp_ks1(obs_dim) != 1)
+            return fail(DN_ERR_INVALID_ARGUMENT, "obs_dim must be in 1..%d for %s (got %d)", n.arch == DN_MLP_ARCH_PPO ? 64 : 16,
+                        n.arch == DN_MLP_ARCH_PPO ? "the PPO networks" : "the SAC actor", obs_dim);
         const bool three = n.arch == DN_MLP_ARCH_PPO;
         if (!n.w1 || !n.w2 || (three && !n.w3) || !n.wh || !n.b1 || !n.b2 || (three && !n.b3) || !n.bh || !n.out)
             return fail(DN_ERR_INVALID_ARGUMENT, "net %d: every weight, bias and output pointer is required", k);

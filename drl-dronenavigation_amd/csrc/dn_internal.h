@@ -283,6 +283,12 @@ hipError_t dn_launch_add_bootstrap(float *reward, const float *terminal_value, c
 hipError_t dn_launch_set_step_count(DnStatSlot *slots, long long blocks, unsigned long long value, hipStream_t stream);
 hipError_t dn_launch_mlp(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                          hipStream_t stream);
+// Layer-1 K-steps (of 16 inputs) a PPO policy kernel runs for rows of obs_dim columns: 1 (the kernels of dn_mlp.hip), 2 or 4 (those of
+// dn_mlp_wide.hip; there is no 3: 33..48 columns run 4 with zero fragments for the padding), 0 = refuse.  The SAC actor and
+// dn_mlp_step_sampled take rows of KS1 = 1 only.
+inline int dn_mlp_ks1(int obs_dim) { return obs_dim < 1 || obs_dim > 64 ? 0 : obs_dim <= 16 ? 1 : obs_dim <= 32 ? 2 : 4; }
+hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
+                              hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,
                               hipStream_t stream);                                                                             // dn_fused.hip
 hipError_t dn_launch_compact_pack(const unsigned long long *mask, long long n, const float *terminal_obs, const float *ep_return,

@@ -1406,6 +1406,8 @@ hipError_t dn_launch_mlp(const dn_mlp_net *nets, int num_nets, const float *obs,
         }
         return hipGetLastError();
     }
+    // rows of 17 .. 64 columns: the wide forms of the two default kernels (dn_mlp_wide.hip); DN_MLP_SHAPE is a knob of the 16-column shapes only
+    if (dn_mlp_ks1(obs_dim) > 1) return dn_launch_mlp_wide(nets, num_nets, obs, row_mask, n, obs_dim, stream);
     if (nets[0].grade == 1) {                                // fp32-grade networks (split-bf16 x3): their own kernel and packing
         hipLaunchKernelGGL(dn_mlp_x3_kernel<NoTail>, dim3((tiles + 1) / 2, num_nets), dim3(64 * XWAVES), 0, stream, a, NoTail());
         dump_stamps("x3");

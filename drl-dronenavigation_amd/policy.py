@@ -69,6 +69,28 @@ class MlpActorCritic(nn.Module):
         return self.predict_values(obs), self._log_prob(actions, mean, log_std), entropy
 
 
+class MlpValue(nn.Module):
+    """A critic of its own over `in_dim` inputs, in the shape of MlpActorCritic's value side (`vf` trunk, Tanh, and `value_net`; the same
+    orthogonal initialisation): the value function of an asymmetric actor-critic, which reads other rows than the actor -- e.g. the
+    52-column privileged rows, RolloutCollector(..., value_fn=..., value_input="privileged").  policy_mfma.FusedMlpValue runs it on the
+    fused kernel (in_dim <= 64)."""
+
+    def __init__(self, in_dim, vf=(512, 512, 256), ortho_init=True):
+        super().__init__()
+        self.vf = _mlp((in_dim,) + tuple(vf), nn.Tanh)
+        self.value_net = nn.Linear(vf[-1], 1)
+        if ortho_init:
+            for mod, gain in ((self.vf, math.sqrt(2)), (self.value_net, 1.0)):
+                for m in mod.modules():
+                    if isinstance(m, nn.Linear):
+                        nn.init.orthogonal_(m.weight, gain=gain)
+                        nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        """x [N, in_dim] -> values [N]."""
+        return self.value_net(self.vf(x)).squeeze(-1)
+
+
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0          # SB3 sac/policies.py [3P-recall]
 
 

@@ -18,10 +18,21 @@ from . import _capi
 HIDDEN = (512, 512, 256)
 
 
+MAX_INPUTS, MAX_INPUTS_SAC = 64, 16
+
+
+def first_ksteps(in_features):
+    """K-steps of 16 inputs that layer 1 runs for rows of `in_features` columns (dn_mlp_ks1 in csrc/dn_internal.h): 1, 2 or 4 --
+    33..48 columns run 4, their padding slots hold zeros."""
+    if not 1 <= in_features <= MAX_INPUTS:
+        raise ValueError(f"the fused kernels take 1..{MAX_INPUTS} input columns (got {in_features})")
+    return 1 if in_features <= 16 else 2 if in_features <= 32 else 4
+
+
 def _k_order(in_features, first):
     """Input-feature index read by (K-step kk, lane group g, slot s) -> [KS, 2, 8]."""
     if first:
-        ks = 1
+        ks = first_ksteps(in_features)
         f = 16 * np.arange(ks)[:, None, None] + 8 * np.arange(2)[None, :, None] + np.arange(8)[None, None, :]
         return np.where(f < in_features, f, -1)
     ks = in_features // 16
@@ -79,6 +90,8 @@ def pack_mlp(layers, device, grade="bf16"):
     if [tuple(w.shape) for w, _ in layers[1:3]] != [(HIDDEN[1], HIDDEN[0]), (HIDDEN[2], HIDDEN[1])] or \
             layers[0][0].shape[0] != HIDDEN[0] or layers[3][0].shape[1] != HIDDEN[2]:
         raise ValueError("the fused kernel is built for obs -> 512 -> 512 -> 256 -> out (PBDroneSimulator.py:251-258)")
+    if not 1 <= layers[0][0].shape[1] <= MAX_INPUTS:
+        raise ValueError(f"the fused PPO kernels take 1..{MAX_INPUTS} input columns (got {layers[0][0].shape[1]})")
     out = {}
     for name, (w, b), first in zip(("1", "2", "3", "h"), layers, (True, False, False, False)):
         pw, pb = pack_layer(w, b, first, scale=1.0 if name == "h" else TANH_PRESCALE, grade=grade)
@@ -103,6 +116,8 @@ def pack_sac_actor(layers, device, grade="bf16"):
     if w1.shape[0] != SAC_HIDDEN[0] or tuple(w2.shape) != (SAC_HIDDEN[1], SAC_HIDDEN[0]) or wm.shape[1] != SAC_HIDDEN[1] \
             or tuple(ws.shape) != tuple(wm.shape):
         raise ValueError("the SAC actor kernel is built for obs -> 256 -> 256 -> (mu, log_std) (PBDroneSimulator.py:297-303)")
+    if not 1 <= w1.shape[1] <= MAX_INPUTS_SAC:
+        raise ValueError(f"the SAC actor kernel takes 1..{MAX_INPUTS_SAC} input columns (got {w1.shape[1]})")
     f = lambda t: t.detach().cpu().float()          # noqa: E731
     wh, bh = torch.cat((f(wm), f(ws)), 0), torch.cat((f(bm), f(bs)), 0)
     out = {}
@@ -148,6 +163,9 @@ def mlp_forward(packs, obs, outs=None, row_mask=None):
         raise ValueError("obs must be a float32 CUDA tensor [N, obs_dim]; there is no CPU fallback")
     obs = obs.contiguous()
     n, dev = obs.shape[0], obs.device
+    for p in packs:                                 # the kernel is told the rows' width only: a w1 packed for another one would be read wrongly, or past its end
+        if "obs_dim" in p and p["obs_dim"] != obs.shape[1]:
+            raise ValueError(f"obs has {obs.shape[1]} columns, the network was packed for {p['obs_dim']}")
     if outs is None:
         outs = [torch.empty((n, p["out_dim"]), dtype=torch.float32, device=dev) for p in packs]
     arr = (_capi.DnMlpNet * len(packs))(*[_net_struct(p, o) for p, o in zip(packs, outs)])
@@ -194,6 +212,30 @@ class FusedMlpPolicy:
         out = self._value if out is None else out
         mlp_forward([self.vf], obs, [out], row_mask=row_mask)
         return out.squeeze(-1)
+
+
+class FusedMlpValue:
+    """value_fn(x, row_mask=None) -> [N] for RolloutCollector(value_fn=..., value_input=...) on the fused kernel, from a policy.MlpValue's
+    weights: a critic that reads other rows than the actor (e.g. the privileged rows, 52 columns).  The kernel reads the rows as they
+    are: scale or select (groups=) what is far from unit size.  Re-pack with `refresh()` after every optimiser step; static output buffer
+    and in-place re-packing: hipGraph-capture safe."""
+
+    def __init__(self, module, num_envs, device, grade="bf16"):
+        self.module, self.device, self.grade = module, torch.device(device), grade
+        self._value = torch.empty((num_envs, 1), dtype=torch.float32, device=self.device)
+        self.vf = None
+        self.refresh()
+
+    def refresh(self):
+        """Re-pack the module's current weights into the SAME device tensors (captured graphs keep working)."""
+        m = self.module
+        vf = [(l.weight, l.bias) for l in m.vf if isinstance(l, torch.nn.Linear)] + [(m.value_net.weight, m.value_net.bias)]
+        self.vf = _repack_into(self.vf, pack_mlp(vf, self.device, self.grade))
+
+    def __call__(self, x, row_mask=None):
+        """V(x); with row_mask (uint8 [N]) only tiles that contain a flagged drone are evaluated, the rest read 0."""
+        mlp_forward([self.vf], x, [self._value], row_mask=row_mask)
+        return self._value.squeeze(-1)
 
 
 class FusedSacActor:

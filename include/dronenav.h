@@ -301,7 +301,11 @@ int32_t dn_gae(const float *rewards, const float *values, const uint8_t *dones,
  *                        into one [8, 256] matrix (rows 0..3 mu, 4..7 log_std); w3 / b3 are unused and may be NULL.
  * Weights are bfloat16 in the fragment order of the kernel (drl-dronenavigation_amd/policy_mfma.py::pack_mlp / pack_sac_actor
  * produce it from the [out, in] float32 matrices), biases float32 padded to a multiple of 32 (the head's to 32).  All pointers
- * are device pointers. */
+ * are device pointers.
+ * w1 for input rows of more than 16 columns (DN_MLP_ARCH_PPO only): layer 1 runs KS1 = 2 (obs_dim <= 32) or 4 (obs_dim <= 64) K-steps of
+ * 16 inputs -- input k sits in K-step k >> 4, lane group (k >> 3) & 1, slot k & 7, columns at and beyond obs_dim are zero -- and w1 holds,
+ * per M-tile of 32 output rows, the KS1 fragments (64 lanes x 8 values) in K-step order; in the float32 grade the KS1 hi fragments and then
+ * the KS1 lo fragments, the rule of the other layers.  obs_dim <= 16 is KS1 = 1: the layout it always had. */
 #define DN_MLP_ARCH_PPO 0
 #define DN_MLP_ARCH_SAC 1
 typedef struct dn_mlp_net {
@@ -322,7 +326,10 @@ typedef struct dn_mlp_net {
 
 /* Forward pass of one or two such networks over the same observations in one launch (replaces the mlp_extractor +
  * action_net / value_net part of SB3's ActorCriticPolicy.forward / predict_values): a fused MFMA kernel, one wavefront
- * per 32 drones, activations resident in registers.  obs: device float[num_envs * obs_dim], obs_dim <= 16.
+ * per 32 drones, activations resident in registers.  obs: device float[num_envs * obs_dim], ONE tensor per call (a caller with two sources
+ * concatenates them), read as it is (no rescaling); obs_dim in 1..64 for DN_MLP_ARCH_PPO, in 1..16 for DN_MLP_ARCH_SAC, anything else is
+ * DN_ERR_INVALID_ARGUMENT.  Every w1 of the call must be packed for that obs_dim's KS1.  Rows of 17..64 columns run wide forms of the
+ * default four-wave kernel (grades 0 and 2) and of the float32-grade kernel, whatever DN_MLP_SHAPE says.
  * row_mask: device uint8[num_envs] or NULL; with a mask, a 32-drone tile without a flagged drone writes zeros and
  * skips the network (V(terminal_observation) is needed only where an episode hit the time limit). */
 int32_t dn_mlp_forward(const dn_mlp_net *nets, int32_t num_nets, const float *obs, const uint8_t *row_mask,

@@ -1,0 +1,112 @@
+"""What the policy-kernel tests for wide inputs share (tests/test_mlp_wide_cpu.py, tests/test_gpu_mlp_wide.py): the fragment layout of
+layer 1 written out independently of policy_mfma.pack_layer, the two reference evaluations, and the networks.  A plain module like
+tests/gpu_support.py -- pytest does not collect it."""
+import numpy as np
+import torch
+
+GRADES = ("bf16", "fp16", "fp32")
+FLEETS = (1, 33, 129, 300)              # one lane, a tile edge, a workgroup edge of both kernels (128 / 64 drones), a ragged tail
+
+
+def ksteps(in_f):
+    """K-steps of 16 inputs in layer 1: the rule of the C ABI (dn_mlp_ks1), restated."""
+    return 1 if in_f <= 16 else 2 if in_f <= 32 else 4
+
+
+def unpack_first(packed, grade):
+    """The packed w1 of pack_layer(first=True) -> (the [32 MT, 16 KS1] float32 matrix it stands for, or the (hi, lo) pair of them in the
+    float32 grade).  The rule: input k of output row 32 mo + (lane & 31) sits in K-step k >> 4, lane group (k >> 3) & 1 = lane >> 5,
+    slot k & 7; per M-tile the KS1 fragments in K-step order, in the float32 grade the KS1 hi fragments and then the KS1 lo fragments."""
+    p = packed.float().numpy()
+    parts = [p[:, 0], p[:, 1]] if grade == "fp32" else [p]            # [MT, KS1, 64, 8] each
+    out = []
+    for q in parts:
+        mt, ks1 = q.shape[:2]
+        w = np.zeros((32 * mt, 16 * ks1), np.float32)
+        for mo in range(mt):
+            for kk in range(ks1):
+                for lane in range(64):
+                    for s in range(8):
+                        w[32 * mo + (lane & 31), 16 * kk + 8 * (lane >> 5) + s] = q[mo, kk, lane, s]
+        out.append(w)
+    return tuple(out) if grade == "fp32" else out[0]
+
+
+def parent_pack_first(w, scale, grade):
+    """The layer-1 fragments as the packer formed them when layer 1 was one K-step (in_f <= 16), written out: [MT, 1, 64, 8] with
+    element (mo, 0, lane, s) = scale * W[32 mo + (lane & 31), 8 (lane >> 5) + s], zero beyond in_f; bf16 / fp16, or stacked (hi, lo)."""
+    w = (np.asarray(w, np.float32) * np.float32(scale)).astype(np.float32)
+    out_f, in_f = w.shape
+    assert in_f <= 16
+    mt = (out_f + 31) // 32
+    p = np.zeros((mt, 1, 64, 8), np.float32)
+    for mo in range(mt):
+        for lane in range(64):
+            r = 32 * mo + (lane & 31)
+            for s in range(8):
+                k = 8 * (lane >> 5) + s
+                if r < out_f and k < in_f:
+                    p[mo, 0, lane, s] = w[r, k]
+    pt = torch.from_numpy(p)
+    if grade == "fp32":
+        hi = pt.to(torch.bfloat16)
+        return torch.stack((hi, (pt - hi.float()).to(torch.bfloat16)), dim=1)
+    return pt.to(torch.float16 if grade == "fp16" else torch.bfloat16)
+
+
+def mlp_reference(layers, x):
+    """The bf16 grade's arithmetic spelled out in torch: bf16 weights and activations, float32 accumulation and bias, tanh in float32,
+    float32 head output."""
+    from drl_dronenavigation_amd.policy_mfma import TANH_PRESCALE as c      # folded into the hidden layers before bf16
+    h = x.to(torch.bfloat16).float()
+    for k, (w, b) in enumerate(layers):
+        if k < len(layers) - 1:
+            z = h @ (w.float() * c).to(torch.bfloat16).float().t() + b.float() * c
+            h = torch.tanh(z / c).to(torch.bfloat16).float()
+        else:
+            h = h @ w.to(torch.bfloat16).float().t() + b.float()
+    return h
+
+
+def f64(layers, x):
+    """The float32 network's exact value, evaluated in float64."""
+    h = x.double()
+    for k, (w, b) in enumerate(layers):
+        h = h @ w.double().t() + b.double()
+        if k < len(layers) - 1:
+            h = torch.tanh(h)
+    return h
+
+
+def layers_of(net):
+    """(pi, vf): the [(W, b)] lists of an MlpActorCritic, heads last."""
+    lin = lambda seq: [l for l in seq if isinstance(l, torch.nn.Linear)]      # noqa: E731
+    pi = [(l.weight.detach(), l.bias.detach()) for l in lin(net.pi)] + [(net.action_net.weight.detach(), net.action_net.bias.detach())]
+    vf = [(l.weight.detach(), l.bias.detach()) for l in lin(net.vf)] + [(net.value_net.weight.detach(), net.value_net.bias.detach())]
+    return pi, vf
+
+
+def perturbed_net(pkg, obs_dim, seed, dev):
+    """MlpActorCritic(obs_dim) with non-zero biases and not-quite-orthogonal weights, as test_fused_mfma_mlp_matches_torch perturbs it."""
+    torch.manual_seed(seed)
+    net = pkg.MlpActorCritic(obs_dim=obs_dim).to(dev)
+    with torch.no_grad():
+        for p_ in net.parameters():
+            p_.add_(0.05 * torch.randn_like(p_))
+    return net
+
+
+def random_layers(in_f, out_dim, seed):
+    """A random in_f-512-512-256-out_dim network on the CPU (float32), weights of the size SB3's initialisation gives."""
+    g = torch.Generator().manual_seed(seed)
+    sizes = (in_f, 512, 512, 256, out_dim)
+    return [(torch.randn((b, a), generator=g) * (1.4 / max(a, 16) ** 0.5), 0.1 * torch.randn((b,), generator=g))
+            for a, b in zip(sizes[:-1], sizes[1:])]
+
+
+def tiles_with_a_flag(mask):
+    """bool [N]: the drone's 32-drone tile holds a flagged drone."""
+    n = mask.numel()
+    t = torch.zeros((n + 31) // 32 * 32, dtype=torch.bool, device=mask.device)
+    t[:n] = mask.bool()
+    return t.view(-1, 32).any(1).repeat_interleave(32)[:n]
