@@ -15,13 +15,14 @@ from .actuator import ActuatorModel  # noqa: F401
 from .sensor import SensorModel  # noqa: F401
 from .privileged import PrivilegedObservation, PRIV_DIM, PRIV_GROUPS, PRIV_SLICES  # noqa: F401
 from .goal import GoalObservation, GOAL_DIM, GOAL_FRAMES, GOAL_SLICES  # noqa: F401
+from .history import HistoryObservation  # noqa: F401
 
 __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError", "DroneNavLibraryError", "make_config",
            "RolloutCollector", "ShardPlan", "all_gather_rollout", "preprocess_action", "stream_copy", "MlpActorCritic", "SacActor", "FusedSacActor",
            "FusedMlpPolicy", "MlpValue", "FusedMlpValue",
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
-           "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES"]
+           "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation"]
 
 
 def __getattr__(name):

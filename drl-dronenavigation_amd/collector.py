@@ -126,6 +126,14 @@ def _refuse_goal(env, who):
                          "or a torch policy")
 
 
+def _refuse_history(env, who):
+    """The fused collectors feed the policy kernels the 13 observation columns from the step kernel's own output; the history rows are
+    stacked by a kernel of their own, after the step."""
+    if getattr(env, "history", None) is not None:
+        raise ValueError(f"{who} does not carry history rows (its policy kernels read the 13-column observation); "
+                         "use RolloutCollector(..., policy_input='history') with FusedMlpPolicy(MlpActorCritic(obs_dim=W), ...) or a torch policy")
+
+
 class RolloutCollector:
     """n_steps x (policy -> dn_step) on one GPU's shard, then GAE (+ optional all-gather).
 
@@ -151,14 +159,18 @@ class RolloutCollector:
     `value_input="privileged"` -- sees cat(obs, goal), [N, obs_dim + 8]; the truncation bootstrap is evaluated on
     cat(terminal_obs, terminal_goal), and the buffer dict gains `goal` [n_steps, N, 8] (`obs` stays the observation alone).
 
+    `policy_input="history"` (the env needs history=HistoryObservation(...)): the policy -- and the value function, unless
+    `value_input="privileged"` -- sees `env.history`, [N, W]; the truncation bootstrap is evaluated on `terminal_history` where done, and
+    the buffer dict gains `history` [n_steps, N, W] (`obs` stays the 13 columns).
+
     An env with a track bank (tracks=TrackBank(...)): the buffer dict gains `track` [n_steps, N] int32, the track each drone is on
     when `obs[t]` is observed."""
 
     def __init__(self, env, policy, n_steps, *, value_fn=None, gamma=0.99, gae_lambda=0.95, bootstrap_truncated=True,
                  gather=False, group=None, use_graph=False, value_input="observation", policy_input="observation"):
         from .vec_env import ACT_DIM, DroneVecEnv
-        if policy_input not in ("observation", "observation+goal"):       # a misspelt mode is wrong whatever the env
-            raise ValueError(f"policy_input must be 'observation' or 'observation+goal', got {policy_input!r}")
+        if policy_input not in ("observation", "observation+goal", "history"):       # a misspelt mode is wrong whatever the env
+            raise ValueError(f"policy_input must be 'observation', 'observation+goal' or 'history', got {policy_input!r}")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("RolloutCollector drives a DroneVecEnv (HIP); there is no CPU path")
         if value_input not in ("observation", "privileged"):
@@ -172,6 +184,9 @@ class RolloutCollector:
         self.policy_goal = policy_input == "observation+goal"
         if self.policy_goal and env.goal is None:
             raise ValueError("policy_input='observation+goal' needs an env built with goal=GoalObservation(...)")
+        self.policy_history = policy_input == "history"
+        if self.policy_history and env.history is None:
+            raise ValueError("policy_input='history' needs an env built with history=HistoryObservation(...)")
         self.env, self.policy, self.value_fn = env, policy, value_fn
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
         self.bootstrap_truncated, self.gather, self.group = bool(bootstrap_truncated), bool(gather), group
@@ -198,6 +213,9 @@ class RolloutCollector:
         if self.policy_goal:
             self.buf["goal"] = torch.empty((T, n, env.goal.shape[1]), dtype=f32, device=dev)
             self._last_goal = env.goal.clone()
+        if self.policy_history:
+            self.buf["history"] = torch.empty((T, n, env.history.shape[1]), dtype=f32, device=dev)
+            self._last_hist = env.history.clone()
         self.has_tracks = env.track_ids is not None
         if self.has_tracks:         # the track each drone is on when obs[t] is observed
             self.buf["track"] = torch.empty((T, n), dtype=torch.int32, device=dev)
@@ -222,14 +240,19 @@ class RolloutCollector:
         obs, done = self._last_obs, self._last_done
         priv = self._last_priv if self.value_privileged else None
         goal = self._last_goal if self.policy_goal else None
+        hist = self._last_hist if self.policy_history else None
 
-        def seen(o, g):         # what the policy (and the value function on observations) is shown
+        def seen(o, g, h=None):         # what the policy (and the value function on observations) is shown
+            if hist is not None:
+                return h
             return o if goal is None else torch.cat((o, g), dim=1)
 
         for t in range(self.n_steps):
-            actions, values, log_probs = self.policy(seen(obs, goal))
+            actions, values, log_probs = self.policy(seen(obs, goal, hist))
             if goal is not None:
                 b["goal"][t].copy_(goal)
+            if hist is not None:
+                b["history"][t].copy_(hist)
             if self.has_tracks:
                 b["track"][t].copy_(self._last_track)
             if priv is not None:
@@ -248,8 +271,9 @@ class RolloutCollector:
                     tv = self._values(torch.where(next_done.bool()[:, None], info["terminal_privileged"], info["privileged"]),
                                       row_mask=info["truncated"])
                 else:
-                    tv = self._values(torch.where(next_done.bool()[:, None], seen(info["terminal_obs"], info.get("terminal_goal")),
-                                                  seen(next_obs, info.get("goal"))), row_mask=info["truncated"])
+                    tv = self._values(torch.where(next_done.bool()[:, None],
+                                                  seen(info["terminal_obs"], info.get("terminal_goal"), info.get("terminal_history")),
+                                                  seen(next_obs, info.get("goal"), info.get("history"))), row_mask=info["truncated"])
                 reward = reward + self.gamma * tv * info["truncated"].to(reward.dtype)
             b["rewards"][t].copy_(reward)
             obs.copy_(next_obs)
@@ -258,9 +282,11 @@ class RolloutCollector:
                 priv.copy_(info["privileged"])
             if goal is not None:
                 goal.copy_(info["goal"])
+            if hist is not None:
+                hist.copy_(info["history"])
             if self.has_tracks:
                 self._last_track.copy_(info["track"])
-        b["last_values"].copy_(self._values(seen(obs, goal) if priv is None else priv))
+        b["last_values"].copy_(self._values(seen(obs, goal, hist) if priv is None else priv))
         b["last_dones"].copy_(done)
         dev = env.device
         _capi.check(_capi.load().dn_gae(
@@ -408,6 +434,7 @@ class OffPolicyCollector:
         _refuse_privileged(env, "OffPolicyCollector")
         _refuse_goal(env, "OffPolicyCollector")
         _refuse_tracks(env, "OffPolicyCollector")
+        _refuse_history(env, "OffPolicyCollector")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("OffPolicyCollector drives a DroneVecEnv (HIP); there is no CPU path")
         self.env, self.actor = env, actor
@@ -526,6 +553,7 @@ class FusedRolloutCollector:
         _refuse_privileged(env, "FusedRolloutCollector")
         _refuse_goal(env, "FusedRolloutCollector")
         _refuse_tracks(env, "FusedRolloutCollector")
+        _refuse_history(env, "FusedRolloutCollector")
         if not isinstance(env, DroneVecEnv) or not isinstance(policy, FusedMlpPolicy):
             raise TypeError("FusedRolloutCollector needs a DroneVecEnv and a FusedMlpPolicy (HIP); there is no CPU path")
         if env.num_envs % 4 or env.obs_dim != OBS_DIM:

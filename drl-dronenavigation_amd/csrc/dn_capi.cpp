@@ -1686,4 +1686,38 @@ int32_t dn_gae(const float *rewards, const float *values, const uint8_t *dones, 
     return DN_OK;
 }
 
+int32_t dn_history_width(const dn_history_config *cfg)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "dn_history_config.reserved must be 0 (got %d)", cfg->reserved);
+    if (cfg->frames < 1 || cfg->frames > 4) return fail(DN_ERR_INVALID_ARGUMENT, "frames must be in 1..4 (got %d)", cfg->frames);
+    if (cfg->actions < 0 || cfg->actions > 4) return fail(DN_ERR_INVALID_ARGUMENT, "actions must be in 0..4 (got %d)", cfg->actions);
+    if (cfg->extra_dim < 0) return fail(DN_ERR_INVALID_ARGUMENT, "extra_dim must be >= 0 (got %d)", cfg->extra_dim);
+    const int w = dn_history_row_width(cfg->frames, cfg->actions, cfg->extra_dim);
+    if (w == 0)
+        return fail(DN_ERR_INVALID_ARGUMENT, "the row of 13 x %d + 4 x %d + %d columns is wider than 64, the policy kernels' limit", cfg->frames,
+                    cfg->actions, cfg->extra_dim);
+    return w;
+}
+
+int32_t dn_stack_history(const dn_history_config *cfg, int64_t k, int64_t n, const float *prev, const float *obs, const float *actions,
+                         const uint8_t *done, const float *terminal_obs, const float *extra, const float *terminal_extra, float *rows,
+                         float *terminal_rows, int32_t device_id, void *stream)
+{
+    const int32_t w = dn_history_width(cfg);
+    if (w < 0) return w;
+    if (k < 1 || n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 (got %lld, %lld)", (long long)k, (long long)n);
+    if (k > 1 && n % 4) return fail(DN_ERR_INVALID_ARGUMENT, "n must be a multiple of 4 for k > 1, as for dn_step_many (got %lld)", (long long)n);
+    if (!obs || !rows) return fail(DN_ERR_INVALID_ARGUMENT, "obs and rows are required");
+    if (((uintptr_t)rows | (uintptr_t)terminal_rows | (uintptr_t)prev) & 15u)
+        return fail(DN_ERR_INVALID_ARGUMENT, "prev, rows and terminal_rows must be 16-byte aligned");
+    if (terminal_rows && !terminal_obs) return fail(DN_ERR_INVALID_ARGUMENT, "terminal_rows needs terminal_obs");
+    if (done && !actions)
+        return fail(DN_ERR_INVALID_ARGUMENT, "done needs actions (actions = NULL is the reset call, in which no episode ends)");
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_history(cfg->frames, cfg->actions, cfg->extra_dim, k, n, prev, obs, actions, done, terminal_obs, extra, terminal_extra,
+                             rows, terminal_rows, (hipStream_t)stream));
+    return DN_OK;
+}
+
 }  // extern "C"

@@ -287,6 +287,17 @@ hipError_t dn_launch_mlp(const dn_mlp_net *nets, int num_nets, const float *obs,
 // dn_mlp_wide.hip; there is no 3: 33..48 columns run 4 with zero fragments for the padding), 0 = refuse.  The SAC actor and
 // dn_mlp_step_sampled take rows of KS1 = 1 only.
 inline int dn_mlp_ks1(int obs_dim) { return obs_dim < 1 || obs_dim > 64 ? 0 : obs_dim <= 16 ? 1 : obs_dim <= 32 ? 2 : 4; }
+// Width W of a history row (dn_stack_history): F observation frames of 13 columns, A action frames of 4 and E extra columns, padded with
+// zeros to whole 16-byte quads; 0 = refuse (1 <= F <= 4, 0 <= A <= 4, E >= 0, and W <= 64, the widest row the policy kernels take).
+inline int dn_history_row_width(int frames, int actions, int extra_dim)
+{
+    if (frames < 1 || frames > 4 || actions < 0 || actions > 4 || extra_dim < 0 || extra_dim > 64) return 0;
+    const int w = (13 * frames + 4 * actions + extra_dim + 3) / 4 * 4;
+    return w <= 64 ? w : 0;
+}
+hipError_t dn_launch_history(int frames, int actions, int extra_dim, long long k, long long n, const float *prev, const float *obs,
+                             const float *act, const uint8_t *done, const float *term_obs, const float *extra, const float *term_extra,
+                             float *rows, float *term_rows, hipStream_t stream);                                               // dn_history.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

@@ -728,6 +728,47 @@ int32_t dn_get_track_stats(dn_env *env, int64_t *out, int32_t reset);
 /* *out = the configuration last given to dn_enable_tracks.  DN_ERR_BAD_STATE before dn_enable_tracks (*out untouched). */
 int32_t dn_get_track_bank_config(const dn_env *env, dn_track_bank_config *out);
 
+/* Observation and action history rows, stacked on the device (what SB3's VecFrameStack does for the reference's VecEnv, plus the policy's
+ * own previous actions): under command latency, motor lag and observation latency the 13 columns of one instant are no Markov state.  One
+ * row of W float32 per drone and step, W = 4 ceil((13 F + 4 A + E) / 4) <= 64 (the widest row dn_mlp_forward takes):
+ *   columns [0, 13 F)              F observation frames, oldest first, newest last (SB3's order)
+ *   columns [13 F, 13 F + 4 A)     A action frames, oldest first; the newest is the action of the step that produced the newest observation
+ *   the next E columns             the `extra` columns of the step, copied through (the 8 goal columns, for instance)
+ *   the rest                       zero
+ * Step rule, per drone, with P the row before the step, o the step's `obs` row (already the reset row where done), a its action, d its done
+ * flag, tau its `terminal_obs` row, x / xtau its extras, and shift(P) = P without its oldest observation frame and its oldest action frame:
+ *   d = 0:  row = shift(P) with o and a as the newest frames, then x
+ *   d = 1:  terminal row = shift(P) with tau and a as the newest frames, then xtau -- written only where done, like terminal_obs, and only
+ *           when terminal_rows is given;  row = zero frames with o as the newest observation frame, zero action frames, then x
+ *           (VecFrameStack at an episode boundary).
+ * Every word is a copy of a float32 word the caller holds (NaN payloads and -0.0 included) or zero; nothing is normalised or rescaled, so
+ * with normalize_obs a frame carries the statistics of its own step.
+ * A kernel of its own, run after the step, on buffers every step kernel already writes: no dn_env, no state in the library, no model level,
+ * dn_get_kernel_waves unchanged.  All buffers are step-major like dn_step_many's:
+ *   prev           const float[N][W]     the row before step 0; NULL = every episode starts (all zero).  May alias any step slot of `rows`
+ *                                        (the caller's current rows, updated in place): a drone's previous row is read before any of its
+ *                                        rows is written
+ *   obs            const float[k][N][13]
+ *   actions        const float[k][N][4]  NULL = zero action frames (the reset call); required when `done` is given
+ *   done           const uint8[k][N]     NULL = no episode ended
+ *   terminal_obs   const float[k][N][13] read where done; required when terminal_rows is given
+ *   extra, terminal_extra  const float[k][N][E] or NULL (then zero)
+ *   rows           float[k][N][W];  terminal_rows  float[k][N][W] or NULL
+ * prev, rows and terminal_rows 16-byte aligned; for k > 1, N a multiple of 4 as for dn_step_many.  A reset is k = 1 with
+ * prev = actions = done = NULL.  Validates before the first device call; enqueues one launch on `stream` (capturable).
+ * Layout of dn_history_config: frames at 0, actions at 4, extra_dim at 8, reserved at 12; 16 bytes. */
+typedef struct dn_history_config {
+    int32_t frames;       /* F, 1..4 */
+    int32_t actions;      /* A, 0..4 */
+    int32_t extra_dim;    /* E >= 0 */
+    int32_t reserved;     /* must be 0 */
+} dn_history_config;
+/* W, or a negative dn_status (DN_ERR_INVALID_ARGUMENT: NULL, a range out of bounds, W > 64, reserved != 0). */
+int32_t dn_history_width(const dn_history_config *cfg);
+int32_t dn_stack_history(const dn_history_config *cfg, int64_t k, int64_t n, const float *prev, const float *obs, const float *actions,
+                         const uint8_t *done, const float *terminal_obs, const float *extra, const float *terminal_extra, float *rows,
+                         float *terminal_rows, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
