@@ -1036,6 +1036,11 @@ __global__ __launch_bounds__(64 * XWAVES) __attribute__((amdgpu_waves_per_eu(1, 
 constexpr int S1 = 256, S2 = 256;
 constexpr int SAC_RING = 8;
 
+// ReLU as torch computes it: a NaN stays a NaN.  fmaxf(x, 0) returns its OTHER operand for a NaN (IEEE maxNum), so a drone whose observation
+// held a NaN left layer 1 with all-zero activations and the actor answered it with a finite (mu | log_std), where the float32
+// network gives NaN (tests/test_gpu_mlp_shapes.py::test_a_non_finite_row_stays_in_its_column).  IEEE 754-2019 maximum is one v_maximum3_f32
+// on gfx950; every other value, -0 included, comes out as before.
+MLP_DEV float relu(const float x) { return __builtin_elementwise_maximum(x, 0.0f); }
 MLP_DEV void split_pair(const float a, const float b, unsigned &hi, unsigned &lo)
 {   // two float32 values -> one dword of the hi operand and one of the lo operand (v = hi + lo to 16 mantissa bits)
     bf16x2 h, l;
@@ -1083,7 +1088,7 @@ MLP_DEV void sac_layer(const uint4 *__restrict__ w, const float *__restrict__ bi
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {                       // ReLU, pack (and split) into the next layer's K-steps 2m, 2m + 1
-            const float v0 = fmaxf(acc[2 * q], 0.0f), v1 = fmaxf(acc[2 * q + 1], 0.0f);
+            const float v0 = relu(acc[2 * q]), v1 = relu(acc[2 * q + 1]);
             unsigned hi, lo = 0u;
             if (X3) split_pair(v0, v1, hi, lo); else hi = pack2(v0, v1);
             if (q < 4) { outh[2 * m][q] = hi; if (X3) outl[2 * m][q] = lo; }
@@ -1174,7 +1179,7 @@ MLP_DEV void sac_epilogue(const f32x16 &acc, u32x4 &h0, u32x4 &h1, u32x4 &l0, u3
 {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-        const float v0 = fmaxf(acc[2 * q], 0.0f), v1 = fmaxf(acc[2 * q + 1], 0.0f);
+        const float v0 = relu(acc[2 * q]), v1 = relu(acc[2 * q + 1]);
         unsigned hi, lo = 0u;
         if (X3) split_pair(v0, v1, hi, lo); else hi = pack2t<F16>(v0, v1);
         if (q < 4) { h0[q] = hi; if (X3) l0[q] = lo; }
@@ -1277,7 +1282,7 @@ MLP_DEV f32x16 sac_stream(const MlpNetDev &net, const float *lbias, uint4 *lds, 
             acc = mfma16<F16>(ah, bh, acc);
             if (t > 0 && kk < 8) {                                         // the previous tile's ReLU / pack / split, one pair a K-step
                 const int q = kk, m = t - 1;
-                const float v0 = fmaxf(prev[2 * q], 0.0f), v1 = fmaxf(prev[2 * q + 1], 0.0f);
+                const float v0 = relu(prev[2 * q]), v1 = relu(prev[2 * q + 1]);
                 unsigned hi, lo = 0u;
                 if (X3) split_pair(v0, v1, hi, lo); else hi = pack2t<F16>(v0, v1);
                 if (q < 4) { h2h[2 * m][q] = hi; if (X3) h2l[2 * m][q] = lo; }

@@ -1,6 +1,6 @@
-"""What the policy-kernel tests for wide inputs share (tests/test_mlp_wide_cpu.py, tests/test_gpu_mlp_wide.py): the fragment layout of
-layer 1 written out independently of policy_mfma.pack_layer, the two reference evaluations, and the networks.  A plain module like
-tests/gpu_support.py -- pytest does not collect it."""
+"""What the policy-kernel tests share (tests/test_mlp_wide_cpu.py, tests/test_gpu_mlp_wide.py, tests/test_mlp_shapes_cpu.py,
+tests/test_gpu_mlp_shapes.py): the fragment layouts written out independently of policy_mfma.pack_layer, the reference evaluations, the
+networks, and output buffers with guard rows.  A plain module like tests/gpu_support.py -- pytest does not collect it."""
 import numpy as np
 import torch
 
@@ -110,3 +110,55 @@ def tiles_with_a_flag(mask):
     t = torch.zeros((n + 31) // 32 * 32, dtype=torch.bool, device=mask.device)
     t[:n] = mask.bool()
     return t.view(-1, 32).any(1).repeat_interleave(32)[:n]
+
+
+def random_sac_layers(obs_dim, act_dim, seed):
+    """A random obs_dim-256-256-(act_dim, act_dim) SAC actor on the CPU (float32): [(W1, b1), (W2, b2), (Wmu, bmu), (Wls, bls)], by
+    random_layers' rule."""
+    g = torch.Generator().manual_seed(seed)
+    shapes = ((obs_dim, 256), (256, 256), (256, act_dim), (256, act_dim))
+    return [(torch.randn((b, a), generator=g) * (1.4 / max(a, 16) ** 0.5), 0.1 * torch.randn((b,), generator=g)) for a, b in shapes]
+
+
+def sac_f64(layers, x):
+    """The float32 SAC actor's exact value, evaluated in float64: [N, 2 act_dim] = (mu | log_std), ReLU trunk, no clamp."""
+    (w1, b1), (w2, b2), (wm, bm), (ws, bs) = layers
+    h = torch.relu(x.double() @ w1.double().t() + b1.double())
+    h = torch.relu(h @ w2.double().t() + b2.double())
+    return torch.cat((h @ wm.double().t() + bm.double(), h @ ws.double().t() + bs.double()), 1)
+
+
+def unpack_hidden(packed, grade):
+    """The packed weights of pack_layer(first=False) -> (the [32 MT, 16 KS] float32 matrix they stand for, or the (hi, lo) pair of them in
+    the float32 grade).  The rule, from the C/D map of the 32x32 MFMA that wrote the layer's input: K-step kk, lane group g = lane >> 5,
+    slot s of output row 32 mo + (lane & 31) reads input feature 32 (kk >> 1) + 4 g + (r & 3) + 8 (r >> 2) with r = 8 (kk & 1) + s."""
+    p = packed.float().numpy()
+    parts = [p[:, 0], p[:, 1]] if grade == "fp32" else [p]            # [MT, KS, 64, 8] each
+    out = []
+    for q in parts:
+        mt, ks = q.shape[:2]
+        w = np.full((32 * mt, 16 * ks), np.nan, np.float32)           # every entry is written once: a NaN left over fails the comparison
+        for kk in range(ks):
+            for lane in range(64):
+                for s in range(8):
+                    r = 8 * (kk & 1) + s
+                    f = 32 * (kk >> 1) + 4 * (lane >> 5) + (r & 3) + 8 * (r >> 2)
+                    w[(lane & 31) + 32 * np.arange(mt), f] = q[:, kk, lane, s]
+        out.append(w)
+    return tuple(out) if grade == "fp32" else out[0]
+
+
+PATTERN = 0x7FC12345                    # a quiet NaN no kernel here produces (tests/test_gpu_history.py's)
+
+
+def guarded_out(n, width, device):
+    """(buf, out): out [n, width] float32 inside a sentinel-filled buffer with one guard row in front of it and one behind."""
+    buf = torch.full(((n + 2) * width,), PATTERN, dtype=torch.int32, device=device)
+    return buf, buf.view(torch.float32)[width:(n + 1) * width].view(n, width)
+
+
+def check_guards(buf, n, width, tag=""):
+    """The guard rows keep their bits, and every word between them was written."""
+    b = buf.view(n + 2, width)
+    assert bool((b[0] == PATTERN).all()) and bool((b[-1] == PATTERN).all()), f"{tag}: a store left the fleet's rows"
+    assert not bool((b[1:-1] == PATTERN).any()), f"{tag}: an output word was never written"

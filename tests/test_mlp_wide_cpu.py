@@ -22,7 +22,7 @@ def pkg():
 
 
 @pytest.mark.parametrize("grade", S.GRADES)
-@pytest.mark.parametrize("in_f", [13, 16, 17, 21, 32, 33, 52, 64])
+@pytest.mark.parametrize("in_f", [1, 7, 8, 9, 13, 15, 16, 17, 21, 32, 33, 52, 64])
 def test_layer1_fragments_unpack_to_the_weights(pkg, in_f, grade):
     """pack_layer(first=True) read back with the stated rule (mlp_support.unpack_first) gives W: every column where its K-step, lane
     group and slot say, zeros in the padding; in the float32 grade hi + lo gives W to the precision of the bf16 split.  Up to 16 inputs
