@@ -22,7 +22,7 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "FusedMlpPolicy", "MlpValue", "FusedMlpValue",
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
-           "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation"]
+           "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer"]
 
 
 def __getattr__(name):
@@ -38,6 +38,9 @@ def __getattr__(name):
     if name in ("policy_mfma", "FusedMlpPolicy", "FusedSacActor", "FusedMlpValue"):
         pm = importlib.import_module(__name__ + ".policy_mfma")
         return pm if name == "policy_mfma" else getattr(pm, name)
+    if name in ("rownorm", "RowNormalizer"):
+        rownorm = importlib.import_module(__name__ + ".rownorm")
+        return rownorm if name == "rownorm" else rownorm.RowNormalizer
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
     if name in ("policy", "MlpActorCritic", "SacActor", "MlpValue"):

@@ -98,6 +98,10 @@ class DnHistoryConfig(C.Structure):
     _fields_ = [("frames", C.c_int32), ("actions", C.c_int32), ("extra_dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DnRownormConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("clip", C.c_float), ("epsilon", C.c_double)]
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -142,6 +146,10 @@ PROTOTYPES = {
     "dn_gae": (_I32, [_VP] * 5 + [_I64, _I64, C.c_double, C.c_double, _VP, _VP, _I32, _VP]),
     "dn_history_width": (_I32, [C.POINTER(DnHistoryConfig)]),
     "dn_stack_history": (_I32, [C.POINTER(DnHistoryConfig), _I64, _I64] + [_VP] * 9 + [_I32, _VP]),
+    "dn_rownorm_state_doubles": (_I64, [_I32]),
+    "dn_rownorm_scratch_bytes": (_I64, [_I64, _I64, _I32]),
+    "dn_rownorm_init": (_I32, [C.POINTER(DnRownormConfig), _VP, _I32, _VP]),
+    "dn_rownorm": (_I32, [C.POINTER(DnRownormConfig), _VP, _I64, _I64, _VP, _VP, _I32, _VP, _I64, _I32, _VP]),
     "dn_set_launch_events": (_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

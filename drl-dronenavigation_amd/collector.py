@@ -164,13 +164,33 @@ class RolloutCollector:
     the buffer dict gains `history` [n_steps, N, W] (`obs` stays the 13 columns).
 
     An env with a track bank (tracks=TrackBank(...)): the buffer dict gains `track` [n_steps, N] int32, the track each drone is on
-    when `obs[t]` is observed."""
+    when `obs[t]` is observed.
+
+    `policy_norm=RowNormalizer(W, device)`: what the policy is shown -- `obs`, cat(obs, goal) or the history rows, and the value function
+    too when it reads observations -- passes through a fleet-wide running normaliser (rownorm.py), in SB3's VecNormalize order [from
+    recall]: the reset rows and, after each step, the next rows update the statistics and are normalised with the updated ones; the rows
+    of the truncation bootstrap, where(done, terminal, next), are normalised with the same statistics and do not move them.  The buffer
+    dict gains `policy_rows` [n_steps, N, W], the rows the policy saw -- what a learner trains on; `obs`, `goal` and `history` stay raw.
+    `value_norm=RowNormalizer(52, device)` (needs value_input="privileged"): the same three rules for the privileged rows, and the buffer
+    dict gains `value_rows` [n_steps, N, 52].  A width that does not match the rows is a ValueError.  Both work under `use_graph`: the
+    statistics live on the device and keep moving under replay.  Each rank keeps its own statistics."""
 
     def __init__(self, env, policy, n_steps, *, value_fn=None, gamma=0.99, gae_lambda=0.95, bootstrap_truncated=True,
-                 gather=False, group=None, use_graph=False, value_input="observation", policy_input="observation"):
+                 gather=False, group=None, use_graph=False, value_input="observation", policy_input="observation",
+                 policy_norm=None, value_norm=None):
         from .vec_env import ACT_DIM, DroneVecEnv
         if policy_input not in ("observation", "observation+goal", "history"):       # a misspelt mode is wrong whatever the env
             raise ValueError(f"policy_input must be 'observation', 'observation+goal' or 'history', got {policy_input!r}")
+        if value_norm is not None and value_input != "privileged":
+            raise ValueError("value_norm needs value_input='privileged' (a value function on observations sees the policy's rows: "
+                             "use policy_norm)")
+        if policy_norm is not None or value_norm is not None:
+            from .rownorm import RowNormalizer
+            for name, v in (("policy_norm", policy_norm), ("value_norm", value_norm)):
+                if v is not None and not isinstance(v, RowNormalizer):
+                    raise TypeError(f"{name} must be a RowNormalizer or None, got {type(v).__name__}")
+            if policy_norm is value_norm:
+                raise ValueError("policy_norm and value_norm must be two normalisers: each keeps the statistics of one kind of row")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("RolloutCollector drives a DroneVecEnv (HIP); there is no CPU path")
         if value_input not in ("observation", "privileged"):
@@ -221,9 +241,27 @@ class RolloutCollector:
             self.buf["track"] = torch.empty((T, n), dtype=torch.int32, device=dev)
             self._last_track = env.track_ids.clone()
         self._last_done = torch.ones(n, dtype=torch.uint8, device=dev)       # SB3: _last_episode_starts = True
+        self.policy_norm, self.value_norm = policy_norm, value_norm
+        for name, norm, rows in (("policy_norm", policy_norm, self._seen(self._last_obs, getattr(self, "_last_goal", None),
+                                                                         getattr(self, "_last_hist", None))),
+                                 ("value_norm", value_norm, getattr(self, "_last_priv", None))):
+            if norm is None:
+                continue
+            if norm.width != rows.shape[1] or norm.device != dev:
+                raise ValueError(f"{name} is of width {norm.width} on {norm.device}; the rows it is to normalise are "
+                                 f"{rows.shape[1]} columns wide on {dev}")
+            key = "policy_rows" if norm is policy_norm else "value_rows"
+            self.buf[key] = torch.empty((T, n, norm.width), dtype=f32, device=dev)
+            setattr(self, "_" + key, norm.update_normalize(rows))          # the reset rows: VecNormalize.reset updates, then normalises
         self.num_timesteps = 0
         self._graph = None
         self._calls = 0
+
+    def _seen(self, o, g, h=None):
+        """The raw rows the policy (and the value function on observations) is shown."""
+        if self.policy_history:
+            return h
+        return torch.cat((o, g), dim=1) if self.policy_goal else o
 
     def _values(self, obs, row_mask=None):
         if self.value_fn is not None:
@@ -241,14 +279,14 @@ class RolloutCollector:
         priv = self._last_priv if self.value_privileged else None
         goal = self._last_goal if self.policy_goal else None
         hist = self._last_hist if self.policy_history else None
-
-        def seen(o, g, h=None):         # what the policy (and the value function on observations) is shown
-            if hist is not None:
-                return h
-            return o if goal is None else torch.cat((o, g), dim=1)
+        seen = self._seen
+        # with a normaliser the policy / the critic read its static buffer, the normalised image of the current raw rows
+        pn, vn = self.policy_norm, self.value_norm
 
         for t in range(self.n_steps):
-            actions, values, log_probs = self.policy(seen(obs, goal, hist))
+            actions, values, log_probs = self.policy(seen(obs, goal, hist) if pn is None else self._policy_rows)
+            if pn is not None:
+                b["policy_rows"][t].copy_(self._policy_rows)
             if goal is not None:
                 b["goal"][t].copy_(goal)
             if hist is not None:
@@ -257,7 +295,9 @@ class RolloutCollector:
                 b["track"][t].copy_(self._last_track)
             if priv is not None:
                 b["privileged"][t].copy_(priv)
-                values = self._values(priv)
+                if vn is not None:
+                    b["value_rows"][t].copy_(self._value_rows)
+                values = self._values(priv if vn is None else self._value_rows)
             b["obs"][t].copy_(obs)
             b["episode_starts"][t].copy_(done)
             b["values"][t].copy_(values.reshape(-1))
@@ -265,15 +305,21 @@ class RolloutCollector:
             b["actions"][t].copy_(actions)
             torch.clamp(b["actions"][t], -1.0, 1.0, out=self._clipped)
             next_obs, reward, next_done, info = env.step_tensor(self._clipped, want_terminal=self.bootstrap_truncated)
+            # VecNormalize.step_wait: the next rows update the statistics and are normalised; the terminal rows below see the same statistics
+            if pn is not None:
+                pn.update_normalize(seen(next_obs, info.get("goal"), info.get("history")), out=self._policy_rows)
+            if vn is not None:
+                vn.update_normalize(info["privileged"], out=self._value_rows)
             if self.bootstrap_truncated:
                 # rows of terminal_obs are valid only where done; `truncated` is zero elsewhere
                 if priv is not None:
-                    tv = self._values(torch.where(next_done.bool()[:, None], info["terminal_privileged"], info["privileged"]),
-                                      row_mask=info["truncated"])
+                    rows = torch.where(next_done.bool()[:, None], info["terminal_privileged"], info["privileged"])
+                    tv = self._values(rows if vn is None else vn.normalize(rows, out=rows), row_mask=info["truncated"])
                 else:
-                    tv = self._values(torch.where(next_done.bool()[:, None],
-                                                  seen(info["terminal_obs"], info.get("terminal_goal"), info.get("terminal_history")),
-                                                  seen(next_obs, info.get("goal"), info.get("history"))), row_mask=info["truncated"])
+                    rows = torch.where(next_done.bool()[:, None],
+                                       seen(info["terminal_obs"], info.get("terminal_goal"), info.get("terminal_history")),
+                                       seen(next_obs, info.get("goal"), info.get("history")))
+                    tv = self._values(rows if pn is None else pn.normalize(rows, out=rows), row_mask=info["truncated"])
                 reward = reward + self.gamma * tv * info["truncated"].to(reward.dtype)
             b["rewards"][t].copy_(reward)
             obs.copy_(next_obs)
@@ -286,7 +332,10 @@ class RolloutCollector:
                 hist.copy_(info["history"])
             if self.has_tracks:
                 self._last_track.copy_(info["track"])
-        b["last_values"].copy_(self._values(seen(obs, goal, hist) if priv is None else priv))
+        if priv is not None:
+            b["last_values"].copy_(self._values(priv if vn is None else self._value_rows))
+        else:
+            b["last_values"].copy_(self._values(seen(obs, goal, hist) if pn is None else self._policy_rows))
         b["last_dones"].copy_(done)
         dev = env.device
         _capi.check(_capi.load().dn_gae(

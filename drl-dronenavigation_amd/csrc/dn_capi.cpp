@@ -1720,4 +1720,72 @@ int32_t dn_stack_history(const dn_history_config *cfg, int64_t k, int64_t n, con
     return DN_OK;
 }
 
+// ---- dn_rownorm: one RunningMeanStd over the fleet per row kind (Sol/Model/Environments/normalize.py:10-47) ---------------------------
+static int32_t rownorm_config_ok(const dn_rownorm_config *cfg)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (cfg->width < 1 || cfg->width > DN_ROWNORM_MAX_WIDTH)
+        return fail(DN_ERR_INVALID_ARGUMENT, "width must be in 1..%d (got %d)", DN_ROWNORM_MAX_WIDTH, cfg->width);
+    if (!(cfg->clip > 0.0f)) return fail(DN_ERR_INVALID_ARGUMENT, "clip must be > 0, +inf for no clip (got %g)", (double)cfg->clip);
+    if (!(cfg->epsilon >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "epsilon must be >= 0 (got %g)", cfg->epsilon);
+    return DN_OK;
+}
+
+/* normalize.py:10-47: the state of one RunningMeanStd of `width` columns -- count, mean[width], var[width] */
+int64_t dn_rownorm_state_doubles(int32_t width)
+{
+    if (width < 1 || width > DN_ROWNORM_MAX_WIDTH) return fail(DN_ERR_INVALID_ARGUMENT, "width must be in 1..%d (got %d)", DN_ROWNORM_MAX_WIDTH, width);
+    return 1 + 2 * (int64_t)width;
+}
+
+/* normalize.py:10-47 in batch form: what dn_rownorm keeps between its launches (dn_internal.h dn_rownorm_scratch_doubles) */
+int64_t dn_rownorm_scratch_bytes(int64_t k, int64_t n, int32_t width)
+{
+    const long long d = dn_rownorm_scratch_doubles(k, n, width);
+    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "width must be in 1..%d and k, n >= 1 (got width %d, k %lld, n %lld)", DN_ROWNORM_MAX_WIDTH,
+                            width, (long long)k, (long long)n);
+    return (d * 8 + 15) / 16 * 16;
+}
+
+/* RunningMeanStd.__init__ (normalize.py:10-17): count 1e-4, mean 0, var 1 */
+int32_t dn_rownorm_init(const dn_rownorm_config *cfg, double *stats, int32_t device_id, void *stream)
+{
+    const int32_t rc = rownorm_config_ok(cfg);
+    if (rc != DN_OK) return rc;
+    if (!stats) return fail(DN_ERR_INVALID_ARGUMENT, "stats is required");
+    if ((uintptr_t)stats & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats must be 8-byte aligned");
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_rownorm_init(cfg->width, stats, (hipStream_t)stream));
+    return DN_OK;
+}
+
+/* RunningMeanStd.update + update_mean_var_count_from_moments (normalize.py:10-47) with the N rows of a step as the batch, then the
+ * normalised rows */
+int32_t dn_rownorm(const dn_rownorm_config *cfg, double *stats, int64_t k, int64_t n, const float *rows, float *out, int32_t update,
+                   void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    const int32_t rc = rownorm_config_ok(cfg);
+    if (rc != DN_OK) return rc;
+    if (!stats || !rows || !scratch) return fail(DN_ERR_INVALID_ARGUMENT, "stats, rows and scratch are required");
+    if (k < 1 || n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 (got %lld, %lld)", (long long)k, (long long)n);
+    if (update != 0 && update != 1) return fail(DN_ERR_INVALID_ARGUMENT, "update must be 0 or 1 (got %d)", update);
+    if (!update && !out) return fail(DN_ERR_INVALID_ARGUMENT, "out is required with update = 0 (there is nothing else to do)");
+    const int64_t need = dn_rownorm_scratch_bytes(k, n, cfg->width);
+    if (need <= 0) return fail(DN_ERR_INVALID_ARGUMENT, "k x n = %lld x %lld rows are more than one call takes", (long long)k, (long long)n);
+    if (scratch_bytes < need)
+        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_rownorm_scratch_bytes gives %lld", (long long)scratch_bytes,
+                    (long long)need);
+    if (((uintptr_t)stats | (uintptr_t)scratch) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats and scratch must be 8-byte aligned");
+    if (((uintptr_t)rows | (uintptr_t)out) & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "rows and out must be 4-byte aligned");
+    if (out && out != rows) {
+        const uintptr_t bytes = (uintptr_t)k * (uintptr_t)n * (uintptr_t)cfg->width * sizeof(float);
+        const uintptr_t r0 = (uintptr_t)rows, o0 = (uintptr_t)out;
+        if (r0 < o0 + bytes && o0 < r0 + bytes)
+            return fail(DN_ERR_INVALID_ARGUMENT, "out overlaps rows: it must be rows itself (in place) or apart from it");
+    }
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_rownorm(cfg->width, cfg->clip, cfg->epsilon, stats, k, n, rows, out, update, (double *)scratch, (hipStream_t)stream));
+    return DN_OK;
+}
+
 }  // extern "C"

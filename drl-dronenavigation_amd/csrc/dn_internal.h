@@ -298,6 +298,25 @@ inline int dn_history_row_width(int frames, int actions, int extra_dim)
 hipError_t dn_launch_history(int frames, int actions, int extra_dim, long long k, long long n, const float *prev, const float *obs,
                              const float *act, const uint8_t *done, const float *term_obs, const float *extra, const float *term_extra,
                              float *rows, float *term_rows, hipStream_t stream);                                               // dn_history.hip
+// Fleet-wide running normaliser of rows (dn_rownorm, dn_rownorm.hip).  The batch moments of a step are formed per block of
+// DN_ROWNORM_BLOCK_ROWS consecutive rows -- a constant: the order of every float64 sum, and so every bit of the statistics, depends on
+// (k, n, width) alone, never on the device or the launch shape.  The scratch is doubles only:
+//   partials   [k][blocks(n)][2][width]   mean and sum of squared deviations of the block's rows, per column
+//   snapshots  [k][2][width]              per step: the mean after the step's update and (a float32 held in a double) 1 / sqrt(var + eps)
+// blocks(n) = ceil(n / DN_ROWNORM_BLOCK_ROWS).  0 = refuse (width outside 1..64, k or n < 1, or a size beyond 2^62 bytes).
+constexpr long long DN_ROWNORM_BLOCK_ROWS = 1024;
+constexpr int DN_ROWNORM_MAX_WIDTH = 64;
+inline long long dn_rownorm_blocks(long long n) { return n < 1 ? 0 : (n - 1) / DN_ROWNORM_BLOCK_ROWS + 1; }
+inline long long dn_rownorm_scratch_doubles(long long k, long long n, int width)
+{
+    if (width < 1 || width > DN_ROWNORM_MAX_WIDTH || k < 1 || n < 1) return 0;
+    if (dn_rownorm_blocks(n) > (1ll << 50)) return 0;
+    const long long per_step = (dn_rownorm_blocks(n) + 1) * 2 * width;         // < 2^58
+    return k > (1ll << 59) / per_step ? 0 : k * per_step;
+}
+hipError_t dn_launch_rownorm_init(int width, double *stats, hipStream_t stream);                                             // dn_rownorm.hip
+hipError_t dn_launch_rownorm(int width, float clip, double epsilon, double *stats, long long k, long long n, const float *rows, float *out,
+                             int update, double *scratch, hipStream_t stream);                                                  // dn_rownorm.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

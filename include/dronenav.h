@@ -769,6 +769,46 @@ int32_t dn_stack_history(const dn_history_config *cfg, int64_t k, int64_t n, con
                          const uint8_t *done, const float *terminal_obs, const float *extra, const float *terminal_extra, float *rows,
                          float *terminal_rows, int32_t device_id, void *stream);
 
+/* A fleet-wide running normaliser for policy and critic input rows (what SB3's VecNormalize is to the reference's VecEnv [from recall]):
+ * the privileged rows, cat(obs, goal) and the history rows reach the networks raw otherwise -- rotor speeds of order 1e4 beside columns
+ * of order 1.  One RunningMeanStd per row kind over the WHOLE fleet, the arithmetic of Sol/Model/Environments/normalize.py:10-47
+ * (RunningMeanStd, update_mean_var_count_from_moments) with the N rows of a step as the batch (the per-drone NormalizeObservation calls
+ * it with a batch of one).  State, float64 on the device, dn_rownorm_state_doubles(width) = 1 + 2 width doubles:
+ *   stats[0] = count (starts at 1e-4), stats[1 .. width] = mean (0), stats[1 + width .. 2 width] = var (1) -- the variance itself, not
+ *   a second moment: a copy of the state is the state.
+ * Update with a batch of n rows, per column, bm / bv the batch mean and population variance:
+ *   delta = bm - mean; tot = count + n; mean += delta n / tot; var = (var count + bv n + delta^2 count n / tot) / tot; count = tot
+ * Output: out = clip((x - mean) / sqrt(var + epsilon), -clip, +clip) as float32; a NaN stays a NaN in its own cell (np.clip), clip = +inf
+ * is no clip.  x - mean is formed in float64 and rounded to float32, then multiplied by the float32 reciprocal square root of
+ * float32(var + epsilon): within 3 float32 ulp of the float64 evaluation, the output stage of the step kernels' normaliser.
+ * Order within a step, SB3's VecNormalize.step_wait [from recall]: update with the step's N rows (reset rows included), then normalise
+ * those rows with the updated statistics; terminal rows are normalised with update = 0 and do not move the statistics.
+ *   update = 1   k times in sequence: step t's rows are normalised with the statistics after steps 0 .. t.  out may be NULL (update only).
+ *   update = 0   all k n rows are normalised with `stats` as they are; `stats` is not written.  out is required.
+ *   rows         const float[k][n][width], dense and step-major like dn_step_many's buffers, 4-byte aligned
+ *   out          float[k][n][width]: rows itself (in place) or apart from it; 16-byte loads and stores when width % 4 == 0 and both
+ *                pointers are 16-byte aligned, 4-byte ones otherwise
+ *   scratch      the caller's device memory, 8-byte aligned, at least dn_rownorm_scratch_bytes(k, n, width): the per-block moments and
+ *                the per-step snapshots.  The library allocates nothing and keeps nothing between calls.
+ * Bit-reproducible: the batch moments are formed in float64 per block of 1024 consecutive rows (a constant) in a shifted form and merged
+ * in ascending block order; no atomics, no workgroup waits for another: three ordinary launches on `stream` (one with update = 0),
+ * capturable.  K steps in one call equal K calls of one step bit for bit.  Validates before the first device call.
+ * Each rank keeps its own statistics (no collective).  Layout of dn_rownorm_config: width at 0, clip at 4, epsilon at 8; 16 bytes. */
+typedef struct dn_rownorm_config {
+    int32_t width;        /* W, 1..64 */
+    float clip;           /* > 0; +inf = no clip.  VecNormalize's clip_obs is 10 */
+    double epsilon;       /* >= 0; the reference's is 1e-8 */
+} dn_rownorm_config;
+/* normalize.py:10-47.  1 + 2 width; a negative dn_status for a width outside 1..64. */
+int64_t dn_rownorm_state_doubles(int32_t width);
+/* normalize.py:10-47.  Bytes of scratch for k steps of n rows; a negative dn_status for a width outside 1..64 or k, n < 1. */
+int64_t dn_rownorm_scratch_bytes(int64_t k, int64_t n, int32_t width);
+/* normalize.py:10-47 (RunningMeanStd.__init__, lines 13-17).  stats <- 1e-4, 0, 1, on `stream`. */
+int32_t dn_rownorm_init(const dn_rownorm_config *cfg, double *stats, int32_t device_id, void *stream);
+/* normalize.py:10-47 (update and update_mean_var_count_from_moments, lines 19-47) and the normalised rows. */
+int32_t dn_rownorm(const dn_rownorm_config *cfg, double *stats, int64_t k, int64_t n, const float *rows, float *out, int32_t update,
+                   void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,435 @@
+"""The fleet-wide row normaliser (include/dronenav.h dn_rownorm, csrc/dn_rownorm.hip, rownorm.py) on the HIP path.
+
+ 1. the statistics after three successive updates against the NumPy float64 reference of tests/rownorm_support.py;
+ 2. the output against the float64 evaluation of the output expression fed the device's OWN statistics: 3 float32 ulp, cells beyond
+    the clip exactly +-clip, the zero column exactly 0;
+ 3. in place = out of place, guard rows and guard columns, a 4-byte-aligned W = 52 view = its dense copy, bit for bit;
+ 4. K = 3 in one launch = three launches of K = 1; the same call twice from the same state = the same bits;
+ 5. update = 0 leaves the bytes of `stats` alone; a NaN and an infinite cell stay in their own cells;
+ 6. state_dict -> a fresh RowNormalizer -> load_state_dict continues bit-identically;
+ 7. RolloutCollector(value_norm=...) and (policy_norm=...) against a RowNormalizer driven by the test, eager and graph-replayed.
+
+Shapes: W in {1, 13, 21, 52, 64}; N in {1, 63, 64, 65, 1000} and 2049, just above two blocks of DN_ROWNORM_BLOCK_ROWS = 1024 rows (three
+blocks, the last of one row); K in {1, 3}.
+
+Where this file departs from the letter of its issue, and why.  The issue asks for variance "exactly 0" in the constant and the zero
+column and for the constant column to come out "exactly 0".  The reference's own arithmetic does not give that: RunningMeanStd starts at
+count = 1e-4 with mean 0 and var 1, and that prior never leaves -- after n rows of a constant c the reference holds
+mean = c n / (n + 1e-4) and var = (1e-4 + c^2 1e-4 n / (n + 1e-4)) / (n + 1e-4) > 0 (tests/test_rownorm_cpu.py checks this on the
+reference alone).  What the claim is after is that a column without spread picks up no rounding noise, and that is asserted here in the
+strictest form there is: in those two columns the batch moments are exact (mean c, variance 0), so the device runs the reference's update
+on the reference's operands, and its mean and var must equal the reference's BIT FOR BIT; the zero column's output is exactly 0 (its mean
+stays 0), and the constant column's output is exactly 0 under statistics that hold its mean exactly (loaded with load_state_dict)."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import rownorm_support as R  # noqa: E402
+from gpu_support import DEV  # noqa: E402
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import NOISE  # noqa: E402
+
+PATTERN = 0x7FC12345                    # a quiet NaN nothing here produces
+WIDTHS = (1, 13, 21, 52, 64)
+FLEETS = (1, 63, 64, 65, 1000, 2 * R.BLOCK_ROWS + 1)
+CLIP = 2.5                              # N(0, 1) columns: about 1 % of the cells lie beyond it
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+
+
+def _same(a, b, tag):
+    assert a.shape == b.shape and torch.equal(_bits(a), _bits(b)), tag
+
+
+# ---- 1. the statistics ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W", WIDTHS)
+def test_statistics_match_the_reference_after_three_updates(W):
+    """count exact; |mean - ref| <= 1e-9 (|ref mean| + ref std); |var - ref| <= 1e-9 ref var: a fixed-order float64 reduction of n float32
+    values is within ~4 n 2^-53 of any other, far below 1e-9 at these sizes (the reference in two summation orders agrees to 1e-12:
+    tests/test_rownorm_cpu.py), where a raw-moment form misses the rotor-speed column by ~1e-5.  The constant and the zero column: bit for
+    bit (the module docstring says why, and why not "exactly 0")."""
+    pkg = _pkg()
+    rotor, const, zero = R.special_columns(W)
+    worst_m = worst_v = 0.0
+    for K in (1, 3):
+        for N in FLEETS:
+            rng = np.random.default_rng(1000 * W + 10 * N + K)
+            norm, ref = pkg.RowNormalizer(W, DEV), R.RunningMeanStd(W)
+            for call in range(3):
+                x = R.make_rows(rng, K, N, W)
+                norm.update(_dev(x if K > 1 else x[0]))
+                for t in range(K):
+                    ref.update(x[t])
+            got, want = norm.stats.cpu().numpy(), ref.stats()
+            tag = (W, K, N)
+            assert got[0] == want[0] and abs(got[0] - (1e-4 + 3 * K * N)) < 1e-9, tag       # the reference's own sum of counts, exactly
+            gm, gv, rm, rv = got[1:1 + W], got[1 + W:], want[1:1 + W], want[1 + W:]
+            em = np.abs(gm - rm) / (np.abs(rm) + np.sqrt(rv))
+            ev = np.abs(gv - rv) / rv
+            worst_m, worst_v = max(worst_m, em.max()), max(worst_v, ev.max())
+            assert (em <= 1e-9).all(), tag + ("mean", int(em.argmax()), em.max())
+            assert (ev <= 1e-9).all(), tag + ("var", int(ev.argmax()), ev.max())
+            for c in (const, zero):
+                if c is not None:
+                    assert gm[c].tobytes() == rm[c].tobytes() and gv[c].tobytes() == rv[c].tobytes(), tag + ("column without spread", c)
+            if zero is not None:
+                assert gm[zero] == 0.0
+    print(f"W={W}: worst relative error of the mean {worst_m:.3e} (of |mean| + std), of the variance {worst_v:.3e}; bars 1e-9")
+
+
+# ---- 2. the output --------------------------------------------------------------------------------------------------------------------
+def _check_output(got, x, stats, W, clip, tag):
+    """got, x: numpy [..., W].  Returns the largest ulp distance."""
+    mean, var = stats[1:1 + W], stats[1 + W:]
+    want = R.normalize(x, mean, var, 1e-8, clip)
+    assert np.isfinite(got).all(), tag
+    d = R.ulp_distance(got, want)
+    assert d.max() <= 3, tag + ("ulp", int(d.max()))
+    raw = R.normalize(x, mean, var, 1e-8, np.inf)
+    hi, lo = raw > clip * (1 + 1e-6), raw < -clip * (1 + 1e-6)
+    assert (got[hi] == np.float32(clip)).all() and (got[lo] == np.float32(-clip)).all(), tag + ("clip",)
+    return int(d.max()), int(hi.sum() + lo.sum())
+
+
+@pytest.mark.parametrize("W", WIDTHS)
+def test_output_is_within_three_ulp_of_the_float64_expression(W):
+    """Against the float64 evaluation of clip((x - mean) / sqrt(var + eps)) on the device's own statistics, read back: the statistics'
+    error does not enter.  update = 1 (the rows of the last step see the statistics that are read back) and update = 0 (all rows do)."""
+    pkg = _pkg()
+    rotor, const, zero = R.special_columns(W)
+    worst, clipped = 0, 0
+    for K in (1, 3):
+        for N in FLEETS:
+            rng = np.random.default_rng(2000 * W + 10 * N + K)
+            norm = pkg.RowNormalizer(W, DEV, clip=CLIP)
+            norm.update(_dev(R.make_rows(rng, 1, max(N, 64), W)[0]))         # away from the prior
+            x = R.make_rows(rng, K, N, W)
+            out = norm.update_normalize(_dev(x)).cpu().numpy()
+            stats = norm.stats.cpu().numpy()
+            u, c = _check_output(out[K - 1], x[K - 1], stats, W, CLIP, (W, K, N, "update"))
+            worst, clipped = max(worst, u), clipped + c
+            y = R.make_rows(rng, K, N, W)
+            out0 = norm.normalize(_dev(y)).cpu().numpy()
+            _same(norm.stats, _dev(stats), (W, K, N, "normalize moved the statistics"))
+            u, c = _check_output(out0, y, stats, W, CLIP, (W, K, N, "normalize"))
+            worst, clipped = max(worst, u), clipped + c
+            if zero is not None:
+                assert not out[..., zero].any() and not out0[..., zero].any(), (W, K, N, "the zero column")
+    assert clipped > 0 or W == 1, "no cell beyond the clip: the clip was not exercised"
+    # the constant column under statistics that hold its mean exactly: 0 times 1 / sqrt(0 + eps)
+    if const is not None:
+        norm = pkg.RowNormalizer(W, DEV)
+        s = norm.state_dict()
+        s["stats"][1 + const] = R.CONSTANT
+        s["stats"][1 + W + const] = 0.0
+        norm.load_state_dict(s)
+        out = norm.normalize(_dev(R.make_rows(np.random.default_rng(W), 1, 65, W)[0]))
+        assert not bool(out[:, const].any())
+    print(f"W={W}: largest distance from the float64 expression {worst} float32 ulp (bar 3); {clipped} cells beyond the clip")
+
+
+# ---- 3. in place, guards, alignment ---------------------------------------------------------------------------------------------------
+def _guarded(shape_rows, W):
+    b = torch.empty((shape_rows + 2, W), dtype=torch.float32, device=DEV)
+    b.view(torch.int32).fill_(PATTERN)
+    return b
+
+
+@pytest.mark.parametrize("W", WIDTHS)
+def test_in_place_equals_out_of_place_between_guard_rows(W):
+    pkg = _pkg()
+    for K, N in ((1, 1), (1, 65), (3, 63), (1, 1000), (3, 2 * R.BLOCK_ROWS + 1)):
+        x = _dev(R.make_rows(np.random.default_rng(W + N), K, N, W))
+        for update in (True, False):
+            a, b = pkg.RowNormalizer(W, DEV, clip=CLIP), pkg.RowNormalizer(W, DEV, clip=CLIP)
+            buf = _guarded(K * N, W)
+            out = buf[1:-1].view(K, N, W)
+            run = (lambda n, r, o: n.update_normalize(r, out=o)) if update else (lambda n, r, o: n.normalize(r, out=o))
+            assert run(a, x, out) is out
+            assert bool((buf.view(torch.int32)[[0, -1]] == PATTERN).all()), (W, K, N, "a store left the rows")
+            buf2 = _guarded(K * N, W)
+            inp = buf2[1:-1].view(K, N, W)
+            inp.copy_(x)
+            run(b, inp, inp)
+            assert bool((buf2.view(torch.int32)[[0, -1]] == PATTERN).all()), (W, K, N, "in place: a store left the rows")
+            _same(inp, out, (W, K, N, update, "in place"))
+            _same(a.stats, b.stats, (W, K, N, update, "statistics"))
+
+
+@pytest.mark.parametrize("W", (52, 64, 13))
+def test_four_byte_aligned_rows_equal_their_aligned_copy(W):
+    """Dense rows that start 4 bytes past a 16-byte boundary take the 4-byte loads and stores although W % 4 == 0: the choice is made from
+    the pointers.  Same bits as the aligned copy, the words around them untouched."""
+    pkg = _pkg()
+    for K, N in ((1, 65), (3, 1000)):
+        x = _dev(R.make_rows(np.random.default_rng(W * N), K, N, W))
+        a, b = pkg.RowNormalizer(W, DEV, clip=CLIP), pkg.RowNormalizer(W, DEV, clip=CLIP)
+        want = a.update_normalize(x)
+        assert x.data_ptr() % 16 == 0 and want.data_ptr() % 16 == 0
+        m = K * N * W
+        flat_in = torch.zeros(m + 8, dtype=torch.float32, device=DEV)
+        flat_out = torch.empty(m + 8, dtype=torch.float32, device=DEV)
+        flat_out.view(torch.int32).fill_(PATTERN)
+        rows, out = flat_in[1:1 + m].view(K, N, W), flat_out[1:1 + m].view(K, N, W)
+        assert rows.data_ptr() % 16 == 4 and out.data_ptr() % 16 == 4 and rows.is_contiguous()
+        rows.copy_(x)
+        b.update_normalize(rows, out=out)
+        _same(out, want, (W, K, N))
+        _same(a.stats, b.stats, (W, K, N, "statistics"))
+        edge = flat_out.view(torch.int32)
+        assert int(edge[0]) == PATTERN and bool((edge[1 + m:] == PATTERN).all())
+
+
+def test_column_slice_of_a_wider_buffer_equals_its_dense_copy():
+    """A [:, 1:53] view of 64-column buffers (W = 52, 4-byte aligned, strided): the result of the dense copy bit for bit, out of place
+    between guard rows and guard columns and in place, and the guards keep their words."""
+    pkg = _pkg()
+    W, N = 52, 1000
+    x = _dev(R.make_rows(np.random.default_rng(52), 1, N, W)[0])
+    a, b, c = (pkg.RowNormalizer(W, DEV, clip=CLIP) for _ in range(3))
+    want = a.update_normalize(x)
+    wide_in = torch.zeros((N, 64), dtype=torch.float32, device=DEV)
+    wide_in[:, 1:53].copy_(x)
+    wide_out = torch.empty((N + 2, 64), dtype=torch.float32, device=DEV)
+    wide_out.view(torch.int32).fill_(PATTERN)
+    rows, out = wide_in[:, 1:53], wide_out[1:-1, 1:53]
+    assert not rows.is_contiguous() and rows.data_ptr() % 16 == 4
+    b.update_normalize(rows, out=out)
+    _same(out, want, "out of place")
+    _same(a.stats, b.stats, "statistics")
+    guards = wide_out.view(torch.int32).clone()
+    guards[1:-1, 1:53] = PATTERN
+    assert bool((guards == PATTERN).all()), "a store left the view"
+    _same(wide_in[:, 1:53], x, "the input view changed")
+    wide_in.view(torch.int32)[:, 0] = PATTERN
+    wide_in.view(torch.int32)[:, 53:] = PATTERN
+    c.update_normalize(rows, out=rows)
+    _same(wide_in[:, 1:53], want, "in place")
+    assert bool((wide_in.view(torch.int32)[:, 0] == PATTERN).all() and (wide_in.view(torch.int32)[:, 53:] == PATTERN).all())
+
+
+# ---- 4. one launch of K steps = K launches --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W", WIDTHS)
+def test_three_steps_in_one_launch_equal_three_launches(W):
+    pkg = _pkg()
+    for N in (1, 65, 1000, 2 * R.BLOCK_ROWS + 1):
+        x = _dev(R.make_rows(np.random.default_rng(7 * W + N), 3, N, W))
+        one, three, again = (pkg.RowNormalizer(W, DEV, clip=CLIP) for _ in range(3))
+        whole = one.update_normalize(x)
+        for t in range(3):
+            _same(three.update_normalize(x[t]), whole[t], (W, N, t))
+        _same(one.stats, three.stats, (W, N, "statistics"))
+        _same(again.update_normalize(x), whole, (W, N, "the same call from the same state"))
+        _same(again.stats, one.stats, (W, N, "statistics of the same call"))
+        # update only (out = NULL) moves the statistics the same way
+        silent = pkg.RowNormalizer(W, DEV, clip=CLIP)
+        silent.update(x)
+        _same(silent.stats, one.stats, (W, N, "update without an output"))
+
+
+# ---- 5. update = 0 --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W", (13, 52))
+def test_normalize_leaves_the_statistics_and_keeps_nan_and_inf_in_their_cells(W):
+    pkg = _pkg()
+    N = 65
+    rng = np.random.default_rng(W)
+    norm = pkg.RowNormalizer(W, DEV)
+    norm.update(_dev(R.make_rows(rng, 3, 1000, W)))
+    before = norm.stats.clone()
+    x = R.make_rows(rng, 1, N, W)[0]
+    clean = norm.normalize(_dev(x))
+    y = x.copy()
+    y[3, 2], y[17, 0], y[40, 5] = np.nan, np.inf, -np.inf
+    got = norm.normalize(_dev(y))
+    _same(norm.stats, before, "normalize wrote the statistics")
+    assert bool(torch.isnan(got[3, 2])) and float(got[17, 0]) == 10.0 and float(got[40, 5]) == -10.0
+    mask = torch.ones((N, W), dtype=torch.bool, device=DEV)
+    mask[3, 2] = mask[17, 0] = mask[40, 5] = False
+    assert torch.equal(_bits(got)[mask], _bits(clean)[mask]), "a NaN or an infinity reached another cell"
+    # no clip at all: clip = +inf
+    free = pkg.RowNormalizer(W, DEV, clip=float("inf"))
+    free.load_state_dict(norm.state_dict())
+    far = x.copy()
+    far[:, 1] *= 1e6
+    out = free.normalize(_dev(far)).cpu().numpy()
+    s = before.cpu().numpy()
+    assert np.abs(out[:, 1]).max() > 1e3
+    assert R.ulp_distance(out, R.normalize(far, s[1:1 + W], s[1 + W:], 1e-8, np.inf)).max() <= 3
+
+
+# ---- 6. checkpoints -------------------------------------------------------------------------------------------------------------------
+def test_state_dict_round_trip_continues_bit_identically():
+    pkg = _pkg()
+    W, N = 52, 1000
+    rng = np.random.default_rng(6)
+    a = pkg.RowNormalizer(W, DEV)
+    a.update_normalize(_dev(R.make_rows(rng, 3, N, W)))
+    state = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in a.state_dict().items()}       # through the host, as a checkpoint goes
+    b = pkg.RowNormalizer(W, DEV)
+    b.load_state_dict(state)
+    assert torch.equal(a.stats, b.stats)
+    x = _dev(R.make_rows(rng, 3, N, W))
+    assert torch.equal(a.update_normalize(x), b.update_normalize(x)) and torch.equal(a.stats, b.stats)
+    with pytest.raises(ValueError, match="width"):
+        pkg.RowNormalizer(13, DEV).load_state_dict(state)
+    b.reset()
+    assert torch.equal(b.stats, pkg.RowNormalizer(W, DEV).stats) and float(b.count) == 1e-4
+    with pytest.raises(ValueError, match="no CPU path"):
+        a.normalize(torch.zeros((4, W)))
+    with pytest.raises(ValueError, match=r"\[N, 52\]"):
+        a.normalize(torch.zeros((4, 13), device=DEV))
+
+
+# ---- 7. the collector -----------------------------------------------------------------------------------------------------------------
+def _priv_env(pkg, n):
+    from drl_dronenavigation_amd import tracks
+    from model_support import AMPS, BODY
+    return pkg.DroneVecEnv(tracks.circle(1, 4, 1), n, max_steps=3, seed=17, device=DEV, normalize_obs=True,
+                           dynamics=pkg.DynamicsRandomization(**BODY), sensor=pkg.SensorModel(latency=(0, 8), bias=AMPS),
+                           privileged=pkg.PrivilegedObservation(), **NOISE)
+
+
+def _policy(width):
+    g = torch.Generator(device="cpu").manual_seed(3)
+    Wa, Wv = (0.05 * torch.randn((width, 4), generator=g)).to(DEV), (0.1 * torch.randn((width,), generator=g)).to(DEV)
+
+    def policy(rows):
+        x = torch.nan_to_num(rows).clamp(-5, 5)
+        return 0.0922 + 0.01 * torch.tanh(x @ Wa), x @ Wv, -(x * x).sum(dim=1)
+    return policy
+
+
+def _critic(width):
+    g = torch.Generator(device="cpu").manual_seed(4)
+    W1, W2 = (0.2 * torch.randn((width, 32), generator=g)).to(DEV), (0.2 * torch.randn((32,), generator=g)).to(DEV)
+    return lambda rows: torch.tanh(rows @ W1) @ W2
+
+
+def test_collector_normalises_the_privileged_rows_for_the_critic():
+    pkg = _pkg()
+    from drl_dronenavigation_amd.collector import RolloutCollector
+    n, T, gamma = 192, 4, 0.99
+    A, twin = _priv_env(pkg, n), _priv_env(pkg, n)
+    with pytest.raises(ValueError, match="52 columns wide"):
+        RolloutCollector(A, _policy(13), T, value_fn=_critic(52), value_input="privileged", value_norm=pkg.RowNormalizer(13, DEV))
+    with pytest.raises(ValueError, match="13 columns wide"):
+        RolloutCollector(A, _policy(13), T, policy_norm=pkg.RowNormalizer(52, DEV))
+    critic, calls = _critic(52), []
+    vn, mine = pkg.RowNormalizer(52, DEV), pkg.RowNormalizer(52, DEV)
+
+    def value_fn(rows):
+        calls.append((rows.clone(), vn.stats.clone()))
+        return critic(rows)
+
+    col = RolloutCollector(A, _policy(13), T, value_fn=value_fn, value_input="privileged", value_norm=vn, gamma=gamma)
+    twin.reset_tensor()
+    _same(col._last_priv, twin.privileged, "reset rows")
+    cur = mine.update_normalize(twin.privileged)                       # the reset rows update, then are normalised
+    truncated = 0
+    for rollout in range(3):
+        del calls[:]
+        buf = col.collect()
+        assert tuple(buf["value_rows"].shape) == (T, n, 52) and len(calls) == 2 * T + 1
+        for t in range(T):
+            _same(buf["value_rows"][t], cur, (rollout, t, "value_rows"))
+            _same(calls[2 * t][0], cur, (rollout, t, "value_fn was shown other rows"))
+            assert torch.equal(buf["values"][t], critic(cur).reshape(-1)), (rollout, t)
+            _, reward, done, info = twin.step_tensor(buf["actions"][t].clamp(-1.0, 1.0))
+            if t + 1 < T:
+                _same(buf["privileged"][t + 1], info["privileged"], (rollout, t, "the twin left the collector's env"))
+            cur = mine.update_normalize(info["privileged"])             # the next rows update, then are normalised
+            after = mine.stats.clone()
+            boot = mine.normalize(torch.where(done.bool()[:, None], info["terminal_privileged"], info["privileged"]))
+            _same(calls[2 * t + 1][0], boot, (rollout, t, "bootstrap rows"))
+            _same(calls[2 * t + 1][1], after, (rollout, t, "statistics at the bootstrap"))
+            _same(calls[2 * t + 2][1], after, (rollout, t, "the bootstrap call moved the statistics"))
+            want = reward + gamma * critic(boot).reshape(-1) * info["truncated"].to(reward.dtype)
+            assert torch.equal(buf["rewards"][t], want), (rollout, t)
+            truncated += int(info["truncated"].sum())
+        _same(calls[2 * T][0], cur, (rollout, "last_values rows"))
+        _same(vn.stats, mine.stats, (rollout, "statistics"))
+        # the raw rows stay raw (slots 1 .. T - 1 were held against the twin's above); the critic's rows are the clipped ones
+        assert not torch.equal(buf["privileged"], buf["value_rows"]) and float(buf["value_rows"].abs().max()) <= 10.0
+    assert truncated > 0, "no truncation: the bootstrap was not exercised"
+    A.close()
+    twin.close()
+
+
+def _graph_against_eager(make):
+    """The third collect() of a use_graph collector against an eager twin: every buffer and the statistics, bit for bit."""
+    runs = []
+    for use_graph in (False, True):
+        env, col, norms = make(use_graph)
+        for _ in range(3):
+            out = col.collect()
+        torch.cuda.synchronize()
+        assert (col._graph is not None) == use_graph
+        runs.append(({k: v.clone() for k, v in out.items()}, [m.stats.clone() for m in norms]))
+        env.close()
+    for k in runs[0][0]:
+        assert torch.equal(_bits(runs[0][0][k]) if runs[0][0][k].dtype == torch.float32 else runs[0][0][k],
+                           _bits(runs[1][0][k]) if runs[1][0][k].dtype == torch.float32 else runs[1][0][k]), k
+    for a, b in zip(runs[0][1], runs[1][1]):
+        _same(a, b, "statistics under replay")
+    return runs[0][0]
+
+
+def test_collector_with_value_norm_replays_as_a_graph():
+    pkg = _pkg()
+    from drl_dronenavigation_amd.collector import RolloutCollector
+    n, T = 192, 4
+
+    def make(use_graph):
+        env, vn = _priv_env(pkg, n), pkg.RowNormalizer(52, DEV)
+        return env, RolloutCollector(env, _policy(13), T, value_fn=_critic(52), value_input="privileged", value_norm=vn,
+                                     use_graph=use_graph), [vn]
+    buf = _graph_against_eager(make)
+    assert int(buf["episode_starts"].sum()) > 0 and float(buf["value_rows"].abs().max()) <= 10.0
+
+
+def test_collector_normalises_the_history_rows_for_the_policy():
+    pkg = _pkg()
+    from drl_dronenavigation_amd import tracks
+    from drl_dronenavigation_amd.collector import RolloutCollector
+    n, T = 192, 4
+    hist = pkg.HistoryObservation(frames=3, actions=2)
+    W = hist.width()
+
+    def env_():
+        return pkg.DroneVecEnv(tracks.circle(1, 4, 1), n, max_steps=3, seed=17, device=DEV, normalize_obs=False, history=hist, **NOISE)
+
+    A = env_()
+    pol, calls = _policy(W), []
+
+    def policy(rows):
+        calls.append(rows.clone())
+        return pol(rows)
+
+    pn, mine = pkg.RowNormalizer(W, DEV), pkg.RowNormalizer(W, DEV)
+    col = RolloutCollector(A, policy, T, policy_input="history", policy_norm=pn)
+    cur = mine.update_normalize(col._last_hist)
+    for rollout in range(2):
+        del calls[:]
+        buf = col.collect()
+        assert tuple(buf["policy_rows"].shape) == (T, n, W) and tuple(buf["history"].shape) == (T, n, W) and len(calls) == 2 * T + 1
+        for t in range(T):
+            _same(buf["policy_rows"][t], cur, (rollout, t, "policy_rows"))
+            _same(calls[2 * t], cur, (rollout, t, "the policy was shown other rows"))      # calls[2 t + 1]: the bootstrap's values
+            cur = mine.update_normalize(buf["history"][t + 1] if t + 1 < T else col._last_hist)
+        _same(pn.stats, mine.stats, (rollout, "statistics"))
+    assert int(buf["episode_starts"].sum()) > 0
+    A.close()
+
+    def make(use_graph):
+        env, pn = env_(), pkg.RowNormalizer(W, DEV)
+        return env, RolloutCollector(env, _policy(W), T, policy_input="history", policy_norm=pn, use_graph=use_graph), [pn]
+    _graph_against_eager(make)
