@@ -22,7 +22,8 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "FusedMlpPolicy", "MlpValue", "FusedMlpValue",
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
-           "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer"]
+           "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer",
+           "ReturnNormalizer"]
 
 
 def __getattr__(name):
@@ -41,6 +42,9 @@ def __getattr__(name):
     if name in ("rownorm", "RowNormalizer"):
         rownorm = importlib.import_module(__name__ + ".rownorm")
         return rownorm if name == "rownorm" else rownorm.RowNormalizer
+    if name in ("retnorm", "ReturnNormalizer"):
+        retnorm = importlib.import_module(__name__ + ".retnorm")
+        return retnorm if name == "retnorm" else retnorm.ReturnNormalizer
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
     if name in ("policy", "MlpActorCritic", "SacActor", "MlpValue"):

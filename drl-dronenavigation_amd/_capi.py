@@ -102,6 +102,10 @@ class DnRownormConfig(C.Structure):
     _fields_ = [("width", C.c_int32), ("clip", C.c_float), ("epsilon", C.c_double)]
 
 
+class DnRetnormConfig(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("epsilon", C.c_double), ("clip", C.c_float), ("reserved", C.c_int32)]
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -150,6 +154,9 @@ PROTOTYPES = {
     "dn_rownorm_scratch_bytes": (_I64, [_I64, _I64, _I32]),
     "dn_rownorm_init": (_I32, [C.POINTER(DnRownormConfig), _VP, _I32, _VP]),
     "dn_rownorm": (_I32, [C.POINTER(DnRownormConfig), _VP, _I64, _I64, _VP, _VP, _I32, _VP, _I64, _I32, _VP]),
+    "dn_retnorm_scratch_bytes": (_I64, [_I64, _I64]),
+    "dn_retnorm_init": (_I32, [_VP, _VP, _I64, _I32, _VP]),
+    "dn_retnorm": (_I32, [C.POINTER(DnRetnormConfig), _VP, _VP, _I64, _I64, _VP, _VP, _VP, _I32, _VP, _I64, _I32, _VP]),
     "dn_set_launch_events": (_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

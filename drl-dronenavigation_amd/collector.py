@@ -173,11 +173,18 @@ class RolloutCollector:
     dict gains `policy_rows` [n_steps, N, W], the rows the policy saw -- what a learner trains on; `obs`, `goal` and `history` stay raw.
     `value_norm=RowNormalizer(52, device)` (needs value_input="privileged"): the same three rules for the privileged rows, and the buffer
     dict gains `value_rows` [n_steps, N, 52].  A width that does not match the rows is a ValueError.  Both work under `use_graph`: the
-    statistics live on the device and keep moving under replay.  Each rank keeps its own statistics."""
+    statistics live on the device and keep moving under replay.  Each rank keeps its own statistics.
+
+    `reward_norm=ReturnNormalizer(N, device)` (retnorm.py): the reward half of VecNormalize [from recall].  After the step the raw reward
+    goes to the new buffer key `raw_rewards` [n_steps, N]; the reward is scaled with `update_normalize(reward, next_done)` (the fleet's
+    discounted returns update one RunningMeanStd, the reward is divided by their standard deviation and clipped); THEN the truncation
+    bootstrap gamma * V(terminal) * truncated is added, SB3's order: VecNormalize sits inside the algorithm's TimeLimit handling, so the
+    critic lives in the normalised scale.  `rewards` is what GAE reads.  The normaliser's gamma is its own, not the collector's.  A
+    normaliser of another num_envs or device is a ValueError.  Works under `use_graph`.  The Monitor episode returns stay raw."""
 
     def __init__(self, env, policy, n_steps, *, value_fn=None, gamma=0.99, gae_lambda=0.95, bootstrap_truncated=True,
                  gather=False, group=None, use_graph=False, value_input="observation", policy_input="observation",
-                 policy_norm=None, value_norm=None):
+                 policy_norm=None, value_norm=None, reward_norm=None):
         from .vec_env import ACT_DIM, DroneVecEnv
         if policy_input not in ("observation", "observation+goal", "history"):       # a misspelt mode is wrong whatever the env
             raise ValueError(f"policy_input must be 'observation', 'observation+goal' or 'history', got {policy_input!r}")
@@ -191,8 +198,15 @@ class RolloutCollector:
                     raise TypeError(f"{name} must be a RowNormalizer or None, got {type(v).__name__}")
             if policy_norm is value_norm:
                 raise ValueError("policy_norm and value_norm must be two normalisers: each keeps the statistics of one kind of row")
+        if reward_norm is not None:
+            from .retnorm import ReturnNormalizer
+            if not isinstance(reward_norm, ReturnNormalizer):
+                raise TypeError(f"reward_norm must be a ReturnNormalizer or None, got {type(reward_norm).__name__}")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("RolloutCollector drives a DroneVecEnv (HIP); there is no CPU path")
+        if reward_norm is not None and (reward_norm.num_envs != env.num_envs or reward_norm.device != env.device):
+            raise ValueError(f"reward_norm is of {reward_norm.num_envs} envs on {reward_norm.device}; the env has {env.num_envs} on "
+                             f"{env.device}")
         if value_input not in ("observation", "privileged"):
             raise ValueError(f"value_input must be 'observation' or 'privileged', got {value_input!r}")
         self.value_privileged = value_input == "privileged"
@@ -253,6 +267,10 @@ class RolloutCollector:
             key = "policy_rows" if norm is policy_norm else "value_rows"
             self.buf[key] = torch.empty((T, n, norm.width), dtype=f32, device=dev)
             setattr(self, "_" + key, norm.update_normalize(rows))          # the reset rows: VecNormalize.reset updates, then normalises
+        self.reward_norm = reward_norm
+        if reward_norm is not None:
+            self.buf["raw_rewards"] = torch.empty((T, n), dtype=f32, device=dev)
+            self._norm_reward = torch.empty(n, dtype=f32, device=dev)
         self.num_timesteps = 0
         self._graph = None
         self._calls = 0
@@ -310,6 +328,9 @@ class RolloutCollector:
                 pn.update_normalize(seen(next_obs, info.get("goal"), info.get("history")), out=self._policy_rows)
             if vn is not None:
                 vn.update_normalize(info["privileged"], out=self._value_rows)
+            if self.reward_norm is not None:    # before the bootstrap below: the critic's values are in the normalised scale already
+                b["raw_rewards"][t].copy_(reward)
+                reward = self.reward_norm.update_normalize(reward, next_done, out=self._norm_reward)
             if self.bootstrap_truncated:
                 # rows of terminal_obs are valid only where done; `truncated` is zero elsewhere
                 if priv is not None:

@@ -1788,4 +1788,72 @@ int32_t dn_rownorm(const dn_rownorm_config *cfg, double *stats, int64_t k, int64
     return DN_OK;
 }
 
+// ---- dn_retnorm: one discounted return per drone, one RunningMeanStd of the returns over the fleet (normalize.py:10-47) ----------------
+static int32_t retnorm_config_ok(const dn_retnorm_config *cfg)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (!(cfg->gamma >= 0.0 && cfg->gamma <= 1.0)) return fail(DN_ERR_INVALID_ARGUMENT, "gamma must be in [0, 1] (got %g)", cfg->gamma);
+    if (!(cfg->clip > 0.0f)) return fail(DN_ERR_INVALID_ARGUMENT, "clip must be > 0, +inf for no clip (got %g)", (double)cfg->clip);
+    if (!(cfg->epsilon >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "epsilon must be >= 0 (got %g)", cfg->epsilon);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    return DN_OK;
+}
+
+/* normalize.py:10-47 in batch form: what dn_retnorm keeps between its launches (dn_internal.h dn_retnorm_scratch_doubles) */
+int64_t dn_retnorm_scratch_bytes(int64_t k, int64_t n)
+{
+    const long long d = dn_retnorm_scratch_doubles(k, n);
+    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 and k x n within one call (got k %lld, n %lld)", (long long)k, (long long)n);
+    return d * 8;
+}
+
+/* RunningMeanStd.__init__ (normalize.py:10-17): count 1e-4, mean 0, var 1; the returns start at 0 */
+int32_t dn_retnorm_init(double *stats, double *returns, int64_t n, int32_t device_id, void *stream)
+{
+    if (!stats && !returns) return fail(DN_ERR_INVALID_ARGUMENT, "stats or returns is required (there is nothing else to do)");
+    if (returns && n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "n must be >= 1 (got %lld)", (long long)n);
+    if (returns && n > (1ll << 38)) return fail(DN_ERR_INVALID_ARGUMENT, "n = %lld returns are more than one call takes", (long long)n);
+    if (((uintptr_t)stats | (uintptr_t)returns) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats and returns must be 8-byte aligned");
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_retnorm_init(stats, returns, n, (hipStream_t)stream));
+    return DN_OK;
+}
+
+/* The discounted returns, RunningMeanStd.update + update_mean_var_count_from_moments (normalize.py:10-47) with the N returns of a step as
+ * the batch, then the scaled rewards */
+int32_t dn_retnorm(const dn_retnorm_config *cfg, double *stats, double *returns, int64_t k, int64_t n, const float *rewards,
+                   const uint8_t *done, float *out, int32_t update, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    const int32_t rc = retnorm_config_ok(cfg);
+    if (rc != DN_OK) return rc;
+    if (update != 0 && update != 1) return fail(DN_ERR_INVALID_ARGUMENT, "update must be 0 or 1 (got %d)", update);
+    if (!stats || !rewards) return fail(DN_ERR_INVALID_ARGUMENT, "stats and rewards are required");
+    if (update && (!returns || !done || !scratch))
+        return fail(DN_ERR_INVALID_ARGUMENT, "returns, done and scratch are required with update = 1");
+    if (!update && !out) return fail(DN_ERR_INVALID_ARGUMENT, "out is required with update = 0 (there is nothing else to do)");
+    if (k < 1 || n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 (got %lld, %lld)", (long long)k, (long long)n);
+    if ((uintptr_t)stats & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats must be 8-byte aligned");
+    if (update) {
+        const int64_t need = dn_retnorm_scratch_bytes(k, n);
+        if (need <= 0) return fail(DN_ERR_INVALID_ARGUMENT, "k x n = %lld x %lld rewards are more than one call takes", (long long)k, (long long)n);
+        if (scratch_bytes < need)
+            return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_retnorm_scratch_bytes gives %lld", (long long)scratch_bytes,
+                        (long long)need);
+        if (((uintptr_t)returns | (uintptr_t)scratch) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "returns and scratch must be 8-byte aligned");
+    }
+    if (!dn_retnorm_grids_ok(k, n))
+        return fail(DN_ERR_INVALID_ARGUMENT, "k x n = %lld x %lld rewards need a grid of more than 2^31 - 1 workgroups", (long long)k, (long long)n);
+    if (out && out != rewards) {
+        const uintptr_t bytes = (uintptr_t)k * (uintptr_t)n * sizeof(float);
+        const uintptr_t r0 = (uintptr_t)rewards, o0 = (uintptr_t)out;
+        if (r0 < o0 + bytes && o0 < r0 + bytes)
+            return fail(DN_ERR_INVALID_ARGUMENT, "out overlaps rewards: it must be rewards itself (in place) or apart from it");
+    }
+    if (((uintptr_t)rewards | (uintptr_t)out) & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "rewards and out must be 4-byte aligned");
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_retnorm(cfg->gamma, cfg->epsilon, cfg->clip, stats, update ? returns : nullptr, k, n, rewards, update ? done : nullptr, out,
+                             update, update ? (double *)scratch : nullptr, (hipStream_t)stream));
+    return DN_OK;
+}
+
 }  // extern "C"

@@ -317,6 +317,31 @@ inline long long dn_rownorm_scratch_doubles(long long k, long long n, int width)
 hipError_t dn_launch_rownorm_init(int width, double *stats, hipStream_t stream);                                             // dn_rownorm.hip
 hipError_t dn_launch_rownorm(int width, float clip, double epsilon, double *stats, long long k, long long n, const float *rows, float *out,
                              int update, double *scratch, hipStream_t stream);                                                  // dn_rownorm.hip
+// Fleet-wide running return normaliser of rewards (dn_retnorm, dn_retnorm.hip): one discounted return per drone and one RunningMeanStd of
+// the returns over the fleet.  The batch moments of a step are formed per block of DN_ROWNORM_BLOCK_ROWS consecutive drones, the row
+// normaliser's constant, so every bit of the statistics depends on (k, n) alone.  The scratch is doubles only:
+//   partials   [k][blocks(n)][2]   mean and sum of squared deviations of the block's returns at that step
+//   snapshots  [k][2]              per step: (a float32 held in a double) 1 / sqrt(var + eps) after the step's update, and one spare word
+//                                  (between the merge's two passes the pair holds the step's batch mean and sum of squared deviations)
+// 0 = refuse (k or n < 1, or a size beyond 2^62 bytes).  The scale launch takes DN_RETNORM_CHUNK rewards of one step per workgroup;
+// dn_retnorm_grids_ok: both grids, blocks(n) and k chunks(n) workgroups, fit the 2^31 - 1 of a launch.
+constexpr long long DN_RETNORM_CHUNK = 4096;
+inline long long dn_retnorm_chunks(long long n) { return n < 1 ? 0 : (n - 1) / DN_RETNORM_CHUNK + 1; }
+inline long long dn_retnorm_scratch_doubles(long long k, long long n)
+{
+    if (k < 1 || n < 1) return 0;
+    const long long per_step = (dn_rownorm_blocks(n) + 1) * 2;                 // <= 2^54
+    return k > (1ll << 59) / per_step ? 0 : k * per_step;
+}
+inline bool dn_retnorm_grids_ok(long long k, long long n)
+{
+    if (k < 1 || n < 1 || dn_rownorm_blocks(n) > 0x7fffffffll) return false;
+    return k <= 0x7fffffffll / dn_retnorm_chunks(n);
+}
+hipError_t dn_launch_retnorm_init(double *stats, double *returns, long long n, hipStream_t stream);                           // dn_retnorm.hip
+hipError_t dn_launch_retnorm(double gamma, double epsilon, float clip, double *stats, double *returns, long long k, long long n,
+                             const float *rewards, const uint8_t *done, float *out, int update, double *scratch,
+                             hipStream_t stream);                                                                               // dn_retnorm.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

@@ -809,6 +809,52 @@ int32_t dn_rownorm_init(const dn_rownorm_config *cfg, double *stats, int32_t dev
 int32_t dn_rownorm(const dn_rownorm_config *cfg, double *stats, int64_t k, int64_t n, const float *rows, float *out, int32_t update,
                    void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
 
+/* A fleet-wide running return normaliser for rewards: the reward half of SB3's VecNormalize (norm_reward=True) [from recall].  One
+ * discounted return per drone and ONE RunningMeanStd of those returns over the WHOLE fleet -- the arithmetic of
+ * Sol/Model/Environments/normalize.py:10-47 (RunningMeanStd, update_mean_var_count_from_moments) with the N returns of a step as the
+ * batch -- and the reward divided by the returns' standard deviation.  (The reference's NormalizeReward, dn_config.norm_rew, keeps one
+ * statistic per drone, a batch of one, inside the one-wave option kernel.)  State, the caller's, float64 on the device:
+ *   stats[3]     count (starts at 1e-4), mean (0), var (1) -- the variance itself, not a second moment: a copy of the state is the state
+ *   returns[n]   the discounted return of every drone's running episode, 0 at the start
+ * Per vector step, r[n] the float32 rewards and d[n] the done flags (truncations included), in this order:
+ *   1. returns = returns * gamma + r      the reward widened to float64, product and sum unfused as numpy evaluates them: bit-exact
+ *   2. the update of normalize.py:32-47 with the n returns as the batch, bm / bv their np.mean / np.var:
+ *        delta = bm - mean; tot = count + n; mean += delta n / tot; var = (var count + bv n + delta^2 count n / tot) / tot; count = tot
+ *   3. out = clip(r / sqrt(var + epsilon), -clip, +clip) as float32, with the updated variance.  No mean is subtracted.  Formed as
+ *      r times the float32 reciprocal square root of float32(var + epsilon), the output stage of dn_rownorm: within 3 float32 ulp of the
+ *      float64 evaluation.  A NaN stays a NaN in its own cell (np.clip); clip = +inf is no clip.
+ *   4. returns = 0 where d
+ * A NaN reward poisons its drone's return and the statistics, as it does in the reference.
+ *   update = 1   k times in sequence: step t is scaled with the statistics after steps 0 .. t.  done, returns and scratch are required;
+ *                out may be NULL (update only).
+ *   update = 0   step 3 alone on `stats` as they are (normalize_reward for evaluation): reads no done and no returns, writes neither stats
+ *                nor returns; out is required; done, returns and scratch are ignored.
+ *   rewards      const float[k][n], step-major like dn_step_many's buffers, 4-byte aligned
+ *   done         const uint8_t[k][n]
+ *   out          float[k][n]: rewards itself (in place) or apart from it; 16-byte loads and stores when both pointers are 16-byte aligned
+ *                and n is a multiple of 4, 4-byte ones otherwise, with the same bits
+ *   scratch      the caller's device memory, 8-byte aligned, at least dn_retnorm_scratch_bytes(k, n): the per-block moments and the
+ *                per-step snapshots.  The library allocates nothing and keeps nothing between calls.
+ * Bit-reproducible: the batch moments are formed in float64 per block of 1024 consecutive drones (a constant) in a shifted form and merged
+ * in ascending block order; no atomics, no workgroup waits for another: three ordinary launches on `stream` (one with update = 0),
+ * capturable.  K steps in one call equal K calls of one step bit for bit, in out, stats and returns.  Validates before the first device
+ * call.  Each rank keeps its own statistics (no collective).
+ * Layout of dn_retnorm_config: gamma at 0, epsilon at 8, clip at 16, reserved at 20; 24 bytes. */
+typedef struct dn_retnorm_config {
+    double gamma;         /* in [0, 1]; VecNormalize's is 0.99 */
+    double epsilon;       /* >= 0; 1e-8 */
+    float clip;           /* > 0; +inf = no clip.  VecNormalize's clip_reward is 10 */
+    int32_t reserved;     /* 0 */
+} dn_retnorm_config;
+/* normalize.py:10-47.  Bytes of scratch for k steps of n drones; a negative dn_status for k or n < 1. */
+int64_t dn_retnorm_scratch_bytes(int64_t k, int64_t n);
+/* normalize.py:10-47 (RunningMeanStd.__init__, lines 13-17).  stats <- 1e-4, 0, 1 and returns[n] <- 0, on `stream`.  Either may be NULL
+ * and is then left alone: stats = NULL resets the returns only, which is what VecNormalize.reset() does [from recall]. */
+int32_t dn_retnorm_init(double *stats, double *returns, int64_t n, int32_t device_id, void *stream);
+/* normalize.py:10-47 (update and update_mean_var_count_from_moments, lines 19-47) on the discounted returns, and the scaled rewards. */
+int32_t dn_retnorm(const dn_retnorm_config *cfg, double *stats, double *returns, int64_t k, int64_t n, const float *rewards,
+                   const uint8_t *done, float *out, int32_t update, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

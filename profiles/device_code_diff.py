@@ -29,7 +29,8 @@ import subprocess
 import sys
 import tempfile
 
-OBJECTS = ["dn_kernels.o", "dn_kernels.exact.o", "dn_kernels_mw.o", "dn_kernels_mw.exact.o", "dn_fused.o", "dn_fused.exact.o", "dn_mlp.o"]
+OBJECTS = ["dn_kernels.o", "dn_kernels.exact.o", "dn_kernels_mw.o", "dn_kernels_mw.exact.o", "dn_fused.o", "dn_fused.exact.o", "dn_mlp.o",
+           "dn_mlp_wide.o", "dn_history.o", "dn_rownorm.o"]
 
 
 def tool(name):

@@ -1,0 +1,428 @@
+"""The fleet-wide return normaliser (include/dronenav.h dn_retnorm, csrc/dn_retnorm.hip, retnorm.py) on the HIP path.
+
+ 1. the discounted returns after three calls against the NumPy float64 reference of tests/retnorm_support.py, bit for bit;
+ 2. the statistics against the reference: count exact, mean and variance within the row normaliser's 1e-9 bars;
+ 3. a batch without spread (gamma = 0.5, reward 0.5, no dones): the statistics bit for bit after each of 20 single-step calls;
+ 4. the output against the float64 evaluation of the output expression fed the device's OWN variance: 3 float32 ulp; cells beyond the
+    clip exactly +-clip;
+ 5. K steps in one call = K calls of one step; the same call twice from the same state = the same bits;
+ 6. in place = out of place, guard cells around `out` and `returns`, a 4-byte-aligned view = its aligned copy, bit for bit;
+ 7. update = 0 leaves the bytes of `stats` and `returns` alone; a NaN and an infinite reward stay in their own cells;
+ 8. state_dict -> a fresh ReturnNormalizer -> load_state_dict continues bit-identically; reset_returns;
+ 9. RolloutCollector(reward_norm=...) against a ReturnNormalizer driven by the test, eager and graph-replayed.
+
+Shapes: N in {1, 63, 64, 65, 1000} and 2049, just above two blocks of DN_ROWNORM_BLOCK_ROWS = 1024 drones (three blocks, the last of one
+drone); K in {1, 3, 9, 17}: 9 is one past the 8 steps whose rewards the scan loads ahead, 17 one past two of the merge's 8-deep prefetch
+batches; and K = 65 in test 5, one past the 64 steps the merge takes side by side."""
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import retnorm_support as R  # noqa: E402
+from gpu_support import DEV  # noqa: E402
+from gpu_support import pkg as _pkg  # noqa: E402
+from model_support import NOISE  # noqa: E402
+
+PATTERN = 0x7FC12345                    # a quiet NaN nothing here produces
+PATTERN64 = 0x7FF8123456789ABC
+FLEETS, STEPS = R.FLEETS, R.STEPS
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+def _bits(t):
+    return t.contiguous().view({torch.float32: torch.int32, torch.float64: torch.int64}.get(t.dtype, t.dtype))
+
+
+def _same(a, b, tag):
+    assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b)), tag
+
+
+@functools.lru_cache(maxsize=None)
+def _case(N, K):
+    """Three calls of K steps on N drones and the reference's results, computed once: ([(r, d)], the reference's out [3][K, N] float64,
+    its statistics after every step [3][K, 3], its returns after every call [3][N]).  On top of the 5 % done flags, the last drone is done
+    on the last step of the first call and the first drone on the first step of the second."""
+    rng = np.random.default_rng(100 * N + K)
+    ref = R.ReturnNormalizer(N)
+    calls, outs, stats, rets = [], [], [], []
+    for call in range(3):
+        r, d = R.make_rewards(rng, K, N)
+        if call == 0:
+            d[K - 1, N - 1] = 1
+        if call == 1:
+            d[0, 0] = 1
+        o, s = np.empty((K, N)), np.empty((K, 3))
+        for t in range(K):
+            o[t] = ref.step(r[t], d[t])
+            s[t] = ref.stats()
+        calls.append((r, d))
+        outs.append(o)
+        stats.append(s)
+        rets.append(ref.returns.copy())
+    return calls, outs, stats, rets
+
+
+def _rows(x, K):
+    """[K, N] -> what the Python surface takes: [N] for one step."""
+    return _dev(x if K > 1 else x[0])
+
+
+# ---- 1. the returns, 2. the statistics ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", FLEETS)
+def test_returns_match_the_reference_bit_for_bit(N):
+    """returns = returns * gamma + r in float64, unfused, then 0 where done: every drone's own chain, so the bits are the reference's --
+    the reset at done, a drone done on a call's last step (the next call starts it from 0) and one done on its first included."""
+    pkg = _pkg()
+    for K in STEPS:
+        calls, _, _, rets = _case(N, K)
+        norm = pkg.ReturnNormalizer(N, DEV)
+        for call, (r, d) in enumerate(calls):
+            norm.update(_rows(r, K), _rows(d, K))
+            got = norm.returns.cpu().numpy()
+            assert got.tobytes() == rets[call].tobytes(), (N, K, call, int((got != rets[call]).sum()))
+        assert rets[0][N - 1] == 0.0 and (N == 1 or (rets[2] != 0.0).any())
+
+
+@pytest.mark.parametrize("N", FLEETS)
+def test_statistics_match_the_reference(N):
+    """count exact; |mean - ref| <= 1e-9 (|ref mean| + ref std); |var - ref| <= 1e-9 ref var, after every call: a fixed-order float64
+    reduction of a few thousand values is within ~4 n 2^-53 of any other (the reference in two summation orders agrees to 1e-12:
+    tests/test_retnorm_cpu.py)."""
+    pkg = _pkg()
+    worst_m = worst_v = 0.0
+    for K in STEPS:
+        calls, _, stats, _ = _case(N, K)
+        norm = pkg.ReturnNormalizer(N, DEV)
+        for call, (r, d) in enumerate(calls):
+            norm.update(_rows(r, K), _rows(d, K))
+            got, want = norm.stats.cpu().numpy(), stats[call][K - 1]
+            assert got[0] == want[0] and abs(got[0] - (1e-4 + (call + 1) * K * N)) < 1e-9, (N, K, call)
+            em = abs(got[1] - want[1]) / (abs(want[1]) + np.sqrt(want[2]))
+            ev = abs(got[2] - want[2]) / want[2]
+            worst_m, worst_v = max(worst_m, em), max(worst_v, ev)
+            assert em <= 1e-9 and ev <= 1e-9, (N, K, call, em, ev)
+            assert float(norm.count) == got[0] and float(norm.mean) == got[1] and float(norm.var) == got[2]
+    print(f"N={N}: worst relative error of the mean {worst_m:.3e} (of |mean| + std), of the variance {worst_v:.3e}; bars 1e-9")
+
+
+# ---- 3. a batch without spread ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", FLEETS)
+def test_a_batch_without_spread_gives_the_reference_statistics_bit_for_bit(N):
+    """gamma = 0.5, reward 0.5, no dones: every return of a step is the same short dyadic number, the reference's batch mean is exact and
+    its batch variance 0 (tests/test_retnorm_cpu.py), and so are the shifted block moments and their merge: the device runs the
+    reference's update on the reference's operands."""
+    pkg = _pkg()
+    norm, ref = pkg.ReturnNormalizer(N, DEV, gamma=0.5), R.ReturnNormalizer(N, gamma=0.5)
+    r, d = np.full(N, 0.5, np.float32), np.zeros(N, np.uint8)
+    rd, dd = _dev(r), _dev(d)
+    for call in range(20):
+        norm.update(rd, dd)
+        ref.step(r, d)
+        assert norm.stats.cpu().numpy().tobytes() == ref.stats().tobytes(), (N, call, norm.stats.cpu().numpy(), ref.stats())
+    assert norm.returns.cpu().numpy().tobytes() == ref.returns.tobytes()
+
+
+# ---- 4. the output ----------------------------------------------------------------------------------------------------------------------
+def _check_output(got, r, var, clip, tag):
+    want = R.scale(r, var, 1e-8, clip)
+    assert np.isfinite(got).all(), tag
+    dist = R.ulp_distance(got, want)
+    assert dist.max() <= 3, tag + ("ulp", int(dist.max()))
+    raw = R.scale(r, var, 1e-8, np.inf)
+    hi, lo = raw > clip * (1 + 1e-6), raw < -clip * (1 + 1e-6)
+    assert (got[hi] == np.float32(clip)).all() and (got[lo] == np.float32(-clip)).all(), tag + ("clip",)
+    return int(dist.max()), int(hi.sum() + lo.sum())
+
+
+@pytest.mark.parametrize("N", FLEETS)
+def test_output_is_within_three_ulp_of_the_float64_expression(N):
+    """K = 1 calls, so that the variance every step was scaled with can be read back: out against clip(r / sqrt(var + eps)) in float64 on
+    the device's own variance -- the statistics' error does not enter.  update = 1 and update = 0."""
+    pkg = _pkg()
+    worst = 0
+    for K in STEPS:
+        calls, _, _, _ = _case(N, K)
+        norm = pkg.ReturnNormalizer(N, DEV)
+        for call, (r, d) in enumerate(calls):
+            for t in range(K):
+                out = norm.update_normalize(_dev(r[t]), _dev(d[t])).cpu().numpy()
+                var = float(norm.stats.cpu().numpy()[2])
+                worst = max(worst, _check_output(out, r[t], var, 10.0, (N, K, call, t, "update"))[0])
+            out0 = norm.normalize(_rows(r, K)).cpu().numpy()
+            worst = max(worst, _check_output(out0, r if K > 1 else r[0], var, 10.0, (N, K, call, "normalize"))[0])
+    print(f"N={N}: largest distance from the float64 expression {worst} float32 ulp (bar 3)")
+
+
+def test_cells_beyond_the_clip_are_exactly_the_clip():
+    """N = 1000, three calls of three single steps, clip = 1: between 1 % and 50 % of the cells of calls two and three lie beyond the
+    clip on the reference, so both branches are exercised and neither swallows the other."""
+    pkg = _pkg()
+    calls, frac = R.clip_case()
+    assert 0.01 <= frac <= 0.5, frac
+    norm = pkg.ReturnNormalizer(1000, DEV, clip=1.0)
+    worst = clipped = inside = 0
+    for call, (r, d) in enumerate(calls):
+        for t in range(3):
+            out = norm.update_normalize(_dev(r[t]), _dev(d[t])).cpu().numpy()
+            var = float(norm.stats.cpu().numpy()[2])
+            u, c = _check_output(out, r[t], var, 1.0, (call, t))
+            worst = max(worst, u)
+            if call >= 1:
+                clipped += c
+                inside += int((np.abs(out) < 1.0).sum())
+            assert np.abs(out).max() == 1.0
+    assert 0.01 * 6000 <= clipped <= 0.5 * 6000 and inside >= 0.5 * 6000, (clipped, inside)
+    print(f"clip = 1: {clipped} of 6000 cells beyond the clip ({100 * frac:.1f} % on the reference), {inside} inside; {worst} ulp")
+
+
+# ---- 5. one call of K steps = K calls ---------------------------------------------------------------------------------------------------
+def _started(pkg, N, **kw):
+    """A normaliser away from the prior, with returns under way."""
+    norm = pkg.ReturnNormalizer(N, DEV, **kw)
+    r, d = R.make_rewards(np.random.default_rng(N), 2, N)
+    norm.update(_dev(r), _dev(d))
+    return norm
+
+
+def _copy_of(pkg, norm, **kw):
+    other = pkg.ReturnNormalizer(norm.num_envs, DEV, **kw)
+    other.load_state_dict(norm.state_dict())
+    return other
+
+
+@pytest.mark.parametrize("K,fleets", [(3, FLEETS), (9, FLEETS), (17, FLEETS), (65, (65, 2049))], ids=["K3", "K9", "K17", "K65"])
+def test_k_steps_in_one_call_equal_k_calls(K, fleets):
+    pkg = _pkg()
+    for N in fleets:
+        first = _started(pkg, N, clip=2.5)
+        one, many, again, silent = (_copy_of(pkg, first, clip=2.5) for _ in range(4))
+        r, d = R.make_rewards(np.random.default_rng(1000 * K + N), K, N)
+        r, d = _dev(r), _dev(d)
+        whole = one.update_normalize(r, d)
+        for t in range(K):
+            _same(many.update_normalize(r[t], d[t]), whole[t], (K, N, t))
+        _same(one.stats, many.stats, (K, N, "statistics"))
+        _same(one.returns, many.returns, (K, N, "returns"))
+        _same(again.update_normalize(r, d), whole, (K, N, "the same call from the same state"))
+        _same(again.stats, one.stats, (K, N, "statistics of the same call"))
+        _same(again.returns, one.returns, (K, N, "returns of the same call"))
+        silent.update(r, d)                            # update only (out = NULL) moves the state the same way
+        _same(silent.stats, one.stats, (K, N, "update without an output"))
+        _same(silent.returns, one.returns, (K, N, "update without an output: returns"))
+        assert not torch.equal(one.stats, first.stats)
+
+
+# ---- 6. in place, guards, alignment -----------------------------------------------------------------------------------------------------
+def _guarded(cells, dtype=torch.float32):
+    b = torch.empty(cells + 8, dtype=dtype, device=DEV)
+    b.view(torch.int32 if dtype == torch.float32 else torch.int64).fill_(PATTERN if dtype == torch.float32 else PATTERN64)
+    return b
+
+
+def _guards_intact(b, cells, lead):
+    w = b.view(torch.int32 if b.dtype == torch.float32 else torch.int64)
+    p = PATTERN if b.dtype == torch.float32 else PATTERN64
+    return bool((w[:lead] == p).all()) and bool((w[lead + cells:] == p).all())
+
+
+def _with_guarded_returns(norm):
+    buf = _guarded(norm.num_envs, torch.float64)
+    buf[4:4 + norm.num_envs].copy_(norm.returns)
+    norm.returns = buf[4:4 + norm.num_envs]
+    return buf
+
+
+@pytest.mark.parametrize("K,N", [(1, 1), (1, 65), (3, 63), (9, 64), (1, 1000), (17, 1000), (3, 2049)])
+def test_in_place_equals_out_of_place_between_guard_cells(K, N):
+    """`out` lies 16 bytes (4 floats) into a guarded buffer, so N % 4 == 0 takes the 16-byte stores; `returns` between guard doubles."""
+    pkg = _pkg()
+    r, d = R.make_rewards(np.random.default_rng(K + N), K, N)
+    first = _started(pkg, N, clip=2.5)
+    for update in (True, False):
+        a, b = _copy_of(pkg, first, clip=2.5), _copy_of(pkg, first, clip=2.5)
+        ra, rb = _with_guarded_returns(a), _with_guarded_returns(b)
+        run = (lambda n, x, o: n.update_normalize(x, _rows(d, K), out=o)) if update else (lambda n, x, o: n.normalize(x, out=o))
+        buf = _guarded(K * N)
+        out = buf[4:4 + K * N].view((K, N) if K > 1 else (N,))
+        assert run(a, _rows(r, K), out) is out
+        assert _guards_intact(buf, K * N, 4), (K, N, update, "a store left out")
+        buf2 = _guarded(K * N)
+        inp = buf2[4:4 + K * N].view((K, N) if K > 1 else (N,))
+        inp.copy_(_rows(r, K))
+        run(b, inp, inp)
+        assert _guards_intact(buf2, K * N, 4), (K, N, update, "in place: a store left the rewards")
+        _same(inp, out, (K, N, update, "in place"))
+        _same(a.stats, b.stats, (K, N, update, "statistics"))
+        _same(a.returns, b.returns, (K, N, update, "returns"))
+        assert _guards_intact(ra, N, 4) and _guards_intact(rb, N, 4), (K, N, update, "a store left returns")
+        assert torch.equal(a.returns, first.returns) == (not update)
+
+
+@pytest.mark.parametrize("K,N", [(1, 64), (3, 1000), (9, 65), (3, 2048)])
+def test_four_byte_aligned_rewards_equal_their_aligned_copy(K, N):
+    """Rewards and out that start 4 bytes past a 16-byte boundary take the 4-byte loads and stores: the choice is made from the pointers
+    and N % 4.  Same bits as the aligned copy, the words around them untouched."""
+    pkg = _pkg()
+    r, d = R.make_rewards(np.random.default_rng(7 * K + N), K, N)
+    first = _started(pkg, N, clip=2.5)
+    a, b = _copy_of(pkg, first, clip=2.5), _copy_of(pkg, first, clip=2.5)
+    x = _rows(r, K)
+    want = a.update_normalize(x, _rows(d, K))
+    assert x.data_ptr() % 16 == 0 and want.data_ptr() % 16 == 0
+    m = K * N
+    flat_in, flat_out = torch.zeros(m + 8, dtype=torch.float32, device=DEV), _guarded(m)
+    rows, out = flat_in[1:1 + m].view(x.shape), flat_out[1:1 + m].view(x.shape)
+    assert rows.data_ptr() % 16 == 4 and out.data_ptr() % 16 == 4 and rows.is_contiguous()
+    rows.copy_(x)
+    b.update_normalize(rows, _rows(d, K), out=out)
+    _same(out, want, (K, N))
+    _same(a.stats, b.stats, (K, N, "statistics"))
+    _same(a.returns, b.returns, (K, N, "returns"))
+    assert _guards_intact(flat_out, m, 1)
+    _same(b.normalize(rows), a.normalize(x), (K, N, "update = 0"))
+
+
+# ---- 7. update = 0 ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", (65, 1000))
+def test_normalize_leaves_the_state_and_keeps_nan_and_inf_in_their_cells(N):
+    pkg = _pkg()
+    norm = _started(pkg, N)
+    stats, returns = norm.stats.clone(), norm.returns.clone()
+    r = R.make_rewards(np.random.default_rng(N + 1), 3, N)[0]
+    clean = norm.normalize(_dev(r))
+    y = r.copy()
+    y[0, 3], y[1, 17], y[2, 40] = np.nan, np.inf, -np.inf
+    got = norm.normalize(_dev(y))
+    _same(norm.stats, stats, "normalize wrote the statistics")
+    _same(norm.returns, returns, "normalize wrote the returns")
+    assert bool(torch.isnan(got[0, 3])) and float(got[1, 17]) == 10.0 and float(got[2, 40]) == -10.0
+    mask = torch.ones((3, N), dtype=torch.bool, device=DEV)
+    mask[0, 3] = mask[1, 17] = mask[2, 40] = False
+    assert torch.equal(_bits(got)[mask], _bits(clean)[mask]), "a NaN or an infinity reached another cell"
+    var = float(stats[2])
+    assert R.ulp_distance(clean.cpu().numpy(), R.scale(r, var)).max() <= 3
+    # no clip at all: clip = +inf
+    free = _copy_of(pkg, norm, clip=float("inf"))
+    far = r.copy()
+    far[1] *= 1e6
+    out = free.normalize(_dev(far)).cpu().numpy()
+    assert np.abs(out[1]).max() > 1e3
+    assert R.ulp_distance(out, R.scale(far, var, 1e-8, np.inf)).max() <= 3
+    # a NaN reward with update = 1 poisons its drone's return and the statistics, as in the reference, and no other drone's return
+    bad = _copy_of(pkg, norm)
+    y[1, 17], y[2, 40] = 0.0, 0.0
+    bad.update(_dev(y), torch.zeros((3, N), dtype=torch.uint8, device=DEV))
+    assert bool(torch.isnan(bad.returns[3])) and int(torch.isnan(bad.returns).sum()) == 1 and bool(torch.isnan(bad.stats[1:]).all())
+
+
+# ---- 8. checkpoints ---------------------------------------------------------------------------------------------------------------------
+def test_state_dict_round_trip_continues_bit_identically():
+    pkg = _pkg()
+    N = 1000
+    a = _started(pkg, N)
+    state = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in a.state_dict().items()}       # through the host, as a checkpoint goes
+    b = pkg.ReturnNormalizer(N, DEV)
+    b.load_state_dict(state)
+    _same(a.stats, b.stats, "statistics")
+    _same(a.returns, b.returns, "returns")
+    r, d = R.make_rewards(np.random.default_rng(8), 3, N)
+    _same(a.update_normalize(_dev(r), _dev(d)), b.update_normalize(_dev(r), _dev(d)), "continued")
+    _same(a.stats, b.stats, "statistics, continued")
+    _same(a.returns, b.returns, "returns, continued")
+    with pytest.raises(ValueError, match="envs"):
+        pkg.ReturnNormalizer(64, DEV).load_state_dict(state)
+    stats = b.stats.clone()
+    assert bool(b.returns.any())
+    b.reset_returns()
+    assert not bool(b.returns.any())
+    _same(b.stats, stats, "reset_returns moved the statistics")
+    b.reset()
+    fresh = pkg.ReturnNormalizer(N, DEV)
+    _same(b.stats, fresh.stats, "reset")
+    assert float(b.count) == 1e-4 and float(b.mean) == 0.0 and float(b.var) == 1.0 and not bool(fresh.returns.any())
+    with pytest.raises(ValueError, match="no CPU path"):
+        a.normalize(torch.zeros(N))
+    with pytest.raises(ValueError, match=r"\[K, 1000\]"):
+        a.normalize(torch.zeros(64, device=DEV))
+    with pytest.raises(ValueError, match="dones"):
+        a.update_normalize(torch.zeros(N, device=DEV), torch.zeros(N, device=DEV))
+
+
+# ---- 9. the collector -------------------------------------------------------------------------------------------------------------------
+def _env(pkg, n):
+    from drl_dronenavigation_amd import tracks
+    return pkg.DroneVecEnv(tracks.circle(1, 4, 1), n, max_steps=3, seed=17, device=DEV, normalize_obs=True, **NOISE)
+
+
+def _policy():
+    g = torch.Generator(device="cpu").manual_seed(3)
+    Wa, Wv = (0.05 * torch.randn((13, 4), generator=g)).to(DEV), (0.1 * torch.randn((13,), generator=g)).to(DEV)
+
+    def policy(rows):
+        x = torch.nan_to_num(rows).clamp(-5, 5)
+        return 0.0922 + 0.01 * torch.tanh(x @ Wa), x @ Wv, -(x * x).sum(dim=1)
+    return policy
+
+
+VALUE = 0.75
+
+
+def _constant_value(rows):
+    return torch.full((rows.shape[0],), VALUE, dtype=torch.float32, device=rows.device)
+
+
+@pytest.mark.parametrize("use_graph", [False, True], ids=["eager", "graph"])
+@pytest.mark.parametrize("bootstrap", [False, True], ids=["plain", "bootstrap"])
+def test_collector_normalises_the_rewards(bootstrap, use_graph):
+    """Three collect() calls against a second ReturnNormalizer driven from buf["raw_rewards"] and the rollout's done flags.  Without the
+    bootstrap buf["rewards"] is the normaliser's output bit for bit; with it and a constant value function, the same float32 expression
+    evaluated here: normalised reward + gamma * V * truncated -- the bootstrap is added after the normalisation.  raw_rewards equals the
+    rewards of a twin collector without reward_norm and without bootstrap; a twin env gives the truncation flags."""
+    pkg = _pkg()
+    from drl_dronenavigation_amd.collector import RolloutCollector
+    n, T, gamma = 192, 4, 0.97                     # the collector's gamma; the normaliser keeps its own 0.99
+    A, B, twin = _env(pkg, n), _env(pkg, n), _env(pkg, n)
+    with pytest.raises(ValueError, match="reward_norm is of 64 envs"):
+        RolloutCollector(A, _policy(), T, reward_norm=pkg.ReturnNormalizer(64, DEV))
+    with pytest.raises(TypeError, match="reward_norm must be a ReturnNormalizer"):
+        RolloutCollector(A, _policy(), T, reward_norm=pkg.RowNormalizer(1, DEV))
+    rn, mine = pkg.ReturnNormalizer(n, DEV), pkg.ReturnNormalizer(n, DEV)
+    col = RolloutCollector(A, _policy(), T, value_fn=_constant_value if bootstrap else None, bootstrap_truncated=bootstrap,
+                           reward_norm=rn, use_graph=use_graph, gamma=gamma)
+    plain = RolloutCollector(B, _policy(), T, bootstrap_truncated=False, gamma=gamma)
+    assert "raw_rewards" not in plain.buf and plain.reward_norm is None and rn.gamma == 0.99
+    twin.reset_tensor()
+    truncated = ended = 0
+    tv = torch.full((n,), VALUE, dtype=torch.float32, device=DEV)
+    seen = []
+    for rollout in range(3):
+        buf, ref = col.collect(), plain.collect()
+        torch.cuda.synchronize()
+        assert (col._graph is not None) == (use_graph and rollout >= 1)
+        assert tuple(buf["raw_rewards"].shape) == (T, n)
+        _same(buf["raw_rewards"], ref["rewards"], (rollout, "raw_rewards against the twin collector's rewards"))
+        for t in range(T):
+            _, reward, done, info = twin.step_tensor(buf["actions"][t].clamp(-1.0, 1.0))
+            _same(reward, buf["raw_rewards"][t], (rollout, t, "the twin env left the collector's"))
+            _same(done, buf["episode_starts"][t + 1] if t + 1 < T else buf["last_dones"], (rollout, t, "done flags"))
+            scaled = mine.update_normalize(buf["raw_rewards"][t], done)
+            want = scaled + gamma * tv * info["truncated"].to(scaled.dtype) if bootstrap else scaled
+            _same(buf["rewards"][t], want, (rollout, t, "rewards"))
+            truncated += int(info["truncated"].sum())
+            ended += int(done.sum())
+        _same(rn.stats, mine.stats, (rollout, "statistics"))
+        _same(rn.returns, mine.returns, (rollout, "returns"))
+        seen.append(rn.stats.clone())
+        assert not torch.equal(buf["rewards"], buf["raw_rewards"])
+    assert truncated > 0 and ended >= truncated, "no truncation: the bootstrap was not exercised"
+    assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2]), "the statistics stood still under replay"
+    for e in (A, B, twin):
+        e.close()

@@ -1,0 +1,257 @@
+"""The fleet-wide return normaliser (include/dronenav.h dn_retnorm), the part that needs no GPU: the three entry points are declared,
+exported and bound; the layout of dn_retnorm_config, compiled from the header; every refusal of dn_retnorm / dn_retnorm_init, which
+validate before their first device call, so the pointers here are never followed; the Python surface's and the collector's own refusals;
+the reference against itself; and the scratch-size rule as a stand-alone host program, plainly and under the address and
+undefined-behaviour sanitizers."""
+import ctypes as C
+import json
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+import retnorm_support as R  # noqa: E402
+from test_model_level import rocm_include  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("dn_retnorm_scratch_bytes", "dn_retnorm_init", "dn_retnorm")
+INVALID = -1
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import drl_dronenavigation_amd as p
+    p.build.build_library()
+    return p
+
+
+def test_the_three_names_are_declared_exported_and_bound(pkg):
+    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    assert re.search(r"typedef struct dn_retnorm_config \{\s*double gamma;\s*double epsilon;\s*float clip;\s*int32_t reserved;\s*\} "
+                     r"dn_retnorm_config;", code)
+    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
+    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
+    for name in NAMES:
+        assert re.search(r"\b%s\s*\(" % name, code), name
+        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    text = header[header.index("A fleet-wide running return normaliser"):]
+    assert "normalize.py:10-47" in text and text.count("normalize.py:") >= 4        # every entry point cites the reference
+    assert "[from recall]" in text
+    assert pkg.ReturnNormalizer is pkg.retnorm.ReturnNormalizer and "ReturnNormalizer" in pkg.__all__
+    assert pkg._capi.load().dn_abi_version() == 9
+
+
+def test_config_layout_compiled_from_the_header(pkg, tmp_path):
+    """sizeof(dn_retnorm_config) = 24 with gamma at 0, epsilon at 8, clip at 16 and reserved at 20: by the C compiler from the header
+    itself, and the ctypes mirror agrees."""
+    prog = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "dronenav.h"
+int main(void) {
+    printf("%zu %zu %zu %zu %zu %d\n", sizeof(dn_retnorm_config), offsetof(dn_retnorm_config, gamma), offsetof(dn_retnorm_config, epsilon),
+           offsetof(dn_retnorm_config, clip), offsetof(dn_retnorm_config, reserved), DN_ABI_VERSION);
+    return 0;
+}
+'''
+    src, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
+    with open(src, "w") as f:
+        f.write(prog)
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
+    got = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert got == [24, 0, 8, 16, 20, 9], got
+    K = pkg._capi.DnRetnormConfig
+    assert [C.sizeof(K), K.gamma.offset, K.epsilon.offset, K.clip.offset, K.reserved.offset] == got[:5]
+
+
+def test_scratch_sizes(pkg):
+    lib = pkg._capi.load()
+    blocks = lambda n: -(-n // R.BLOCK_ROWS)       # noqa: E731
+    for k, n in ((1, 1), (1, 1024), (1, 1025), (32, 32768), (1, 1 << 21), (17, 2049)):
+        assert lib.dn_retnorm_scratch_bytes(k, n) == 8 * k * (blocks(n) + 1) * 2, (k, n)
+    for k, n in ((0, 1), (1, 0), (-1, 5), (1 << 62, 1 << 62)):
+        assert lib.dn_retnorm_scratch_bytes(k, n) <= 0, (k, n)
+        assert b"k and n must be >= 1" in lib.dn_last_error()
+
+
+CFG = (0.99, 1e-8, 10.0, 0)         # gamma, epsilon, clip, reserved
+
+
+def _call(lib, K, *, cfg=CFG, stats=0x10000, returns=0x100000, k=1, n=64, rewards=0x20000, done=0x30000, out=0x40000, update=1,
+          scratch=0x80000, scratch_bytes=None):
+    c = None if cfg is None else C.byref(K.DnRetnormConfig(*cfg))
+    if scratch_bytes is None:
+        scratch_bytes = 1 << 62
+    rc = lib.dn_retnorm(c, stats, returns, k, n, rewards, done, out, update, scratch, scratch_bytes, 0, None)
+    return rc, lib.dn_last_error().decode()
+
+
+def _cfg(**kw):
+    d = dict(gamma=CFG[0], epsilon=CFG[1], clip=CFG[2], reserved=CFG[3])
+    d.update(kw)
+    return dict(cfg=(d["gamma"], d["epsilon"], d["clip"], d["reserved"]))
+
+
+STEP_BYTES = 64 * 4
+REFUSALS = [
+    ("null_cfg", dict(cfg=None), "cfg is required"),
+    ("null_stats", dict(stats=None), "stats and rewards are required"),
+    ("null_rewards", dict(rewards=None), "stats and rewards are required"),
+    ("null_returns", dict(returns=None), "returns, done and scratch are required with update = 1"),
+    ("null_done", dict(done=None), "returns, done and scratch are required with update = 1"),
+    ("null_scratch", dict(scratch=None), "returns, done and scratch are required with update = 1"),
+    ("no_out_without_update", dict(out=None, update=0), "out is required with update = 0"),
+    ("update_2", dict(update=2), "update must be 0 or 1"),
+    ("k_0", dict(k=0), "k and n must be >= 1"),
+    ("n_0", dict(n=0), "k and n must be >= 1"),
+    ("n_negative", dict(n=-5), "k and n must be >= 1"),
+    ("gamma_negative", _cfg(gamma=-0.01), "gamma must be in [0, 1]"),
+    ("gamma_above_1", _cfg(gamma=1.0000001), "gamma must be in [0, 1]"),
+    ("gamma_nan", _cfg(gamma=math.nan), "gamma must be in [0, 1]"),
+    ("clip_0", _cfg(clip=0.0), "clip must be > 0"),
+    ("clip_negative", _cfg(clip=-1.0), "clip must be > 0"),
+    ("clip_nan", _cfg(clip=math.nan), "clip must be > 0"),
+    ("epsilon_negative", _cfg(epsilon=-1e-8), "epsilon must be >= 0"),
+    ("epsilon_nan", _cfg(epsilon=math.nan), "epsilon must be >= 0"),
+    ("reserved_1", _cfg(reserved=1), "reserved must be 0 (got 1)"),
+    ("scratch_one_byte_short", dict(scratch_bytes="short"), "scratch_bytes is too small"),
+    ("scratch_0", dict(scratch_bytes=0), "scratch_bytes is too small"),
+    ("stats_misaligned", dict(stats=0x10004), "stats must be 8-byte aligned"),
+    ("returns_misaligned", dict(returns=0x100004), "returns and scratch must be 8-byte aligned"),
+    ("scratch_misaligned", dict(scratch=0x80004), "returns and scratch must be 8-byte aligned"),
+    ("grid_of_scale_workgroups", dict(k=1 << 20, n=1 << 23, rewards=1 << 50, out=1 << 50), "a grid of more than 2^31 - 1 workgroups"),
+    ("grid_of_blocks", dict(k=1, n=1 << 41, rewards=1 << 50, out=1 << 50), "a grid of more than 2^31 - 1 workgroups"),
+    ("grid_without_update", dict(k=1 << 20, n=1 << 23, rewards=1 << 50, out=1 << 50, update=0), "a grid of more than 2^31 - 1 workgroups"),
+    ("out_overlaps_from_above", dict(out=0x20000 + 4), "out overlaps rewards"),
+    ("out_overlaps_last_word", dict(out=0x20000 + STEP_BYTES - 4), "out overlaps rewards"),
+    ("out_overlaps_from_below", dict(rewards=0x40000, out=0x40000 - STEP_BYTES + 4), "out overlaps rewards"),
+    ("rewards_misaligned", dict(rewards=0x20002), "rewards and out must be 4-byte aligned"),
+    ("out_misaligned", dict(out=0x40001), "rewards and out must be 4-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("kw,message", [pytest.param(*r[1:], id=r[0]) for r in REFUSALS])
+def test_dn_retnorm_refuses(pkg, kw, message):
+    """Every case returns DN_ERR_INVALID_ARGUMENT with its own text on dummy pointers: none gets as far as a device call."""
+    K = pkg._capi
+    lib = K.load()
+    kw = dict(kw)
+    if kw.get("scratch_bytes") == "short":
+        kw["scratch_bytes"] = lib.dn_retnorm_scratch_bytes(1, 64) - 1
+    rc, msg = _call(lib, K, **kw)
+    assert rc == INVALID, msg
+    assert message in msg, msg
+
+
+def test_the_refusals_are_not_the_dummies_own(pkg):
+    """The unchanged dummy call -- also in place, with out exactly behind the rewards, with gamma 0 and 1, an infinite clip and epsilon 0,
+    without an output, with the exact scratch size, and with update = 0 and nothing but stats, rewards and out -- passes every check but
+    one chosen here, the last one validation makes: each refusal above is caused by what it changes."""
+    K = pkg._capi
+    lib = K.load()
+    for kw in (dict(), dict(out=0x20002), dict(out=0x20002 + STEP_BYTES), _cfg(gamma=0.0), _cfg(gamma=1.0, clip=math.inf, epsilon=0.0),
+               dict(out=None), dict(scratch_bytes=lib.dn_retnorm_scratch_bytes(1, 64)),
+               dict(update=0, returns=None, done=None, scratch=None, scratch_bytes=0),
+               dict(update=0, returns=0x100004, done=None, scratch=0x80004, scratch_bytes=0)):
+        rc, msg = _call(lib, K, rewards=0x20002, **kw)
+        assert rc == INVALID and "rewards and out must be 4-byte aligned" in msg, (kw, msg)
+
+
+def test_dn_retnorm_init_refuses(pkg):
+    lib = pkg._capi.load()
+    assert lib.dn_retnorm_init(None, None, 64, 0, None) == INVALID and b"stats or returns is required" in lib.dn_last_error()
+    assert lib.dn_retnorm_init(0x1000, 0x2000, 0, 0, None) == INVALID and b"n must be >= 1" in lib.dn_last_error()
+    assert lib.dn_retnorm_init(None, 0x2000, -3, 0, None) == INVALID and b"n must be >= 1" in lib.dn_last_error()
+    assert lib.dn_retnorm_init(0x1004, 0x2000, 64, 0, None) == INVALID and b"8-byte aligned" in lib.dn_last_error()
+    assert lib.dn_retnorm_init(0x1000, 0x2004, 64, 0, None) == INVALID and b"8-byte aligned" in lib.dn_last_error()
+    assert lib.dn_retnorm_init(None, 0x2000, 1 << 39, 0, None) == INVALID and b"more than one call takes" in lib.dn_last_error()
+
+
+def test_python_surface_refuses_without_a_device(pkg):
+    from drl_dronenavigation_amd import collector
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        pkg.ReturnNormalizer(64, "cpu")
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        pkg.ReturnNormalizer(64, torch.device("cpu"), gamma=0.9, clip=5.0)
+    for bad in (0, -1, 64.0, True):
+        with pytest.raises(ValueError, match="num_envs"):
+            pkg.ReturnNormalizer(bad, "cpu")
+    for kw, word in ((dict(gamma=-0.1), "gamma"), (dict(gamma=1.5), "gamma"), (dict(gamma=math.nan), "gamma"), (dict(clip=0.0), "clip"),
+                     (dict(clip=math.nan), "clip"), (dict(epsilon=-1.0), "epsilon"), (dict(epsilon=math.nan), "epsilon")):
+        with pytest.raises(ValueError, match=word):
+            pkg.ReturnNormalizer(64, "cpu", **kw)
+    # RolloutCollector: what it can say about the argument before it looks at the env
+    for bad in (object(), (64, 0.99), "vecnormalize", 0.99):
+        with pytest.raises(TypeError, match="reward_norm must be a ReturnNormalizer or None"):
+            collector.RolloutCollector(None, None, 4, reward_norm=bad)
+    with pytest.raises(TypeError, match="DroneVecEnv"):                # left at None the first complaint is the old one
+        collector.RolloutCollector(None, None, 4, reward_norm=None)
+
+
+def test_reference_agrees_with_itself_in_two_summation_orders():
+    """The 1e-9 bars of the GPU test on the reference alone: the same returns with the batch moments taken by np.mean / np.var and from
+    sums in reversed drone order agree to 1e-12 in mean and variance, on the fleets and step counts of the GPU test."""
+    worst_m = worst_v = 0.0
+    for n in R.FLEETS:
+        for k in R.STEPS:
+            rng = np.random.default_rng(10 * n + k)
+            a, b = R.ReturnNormalizer(n), R.ReturnNormalizer(n)
+            b._update = lambda x, b=b: R.ReturnNormalizer._update(b, x[::-1].copy())
+            for call in range(3):
+                r, d = R.make_rewards(rng, k, n)
+                for t in range(k):
+                    a.step(r[t], d[t])
+                    b.step(r[t], d[t])
+            assert a.count == b.count and abs(a.count - (1e-4 + 3 * k * n)) < 1e-9
+            assert np.array_equal(a.returns, b.returns)
+            em, ev = abs(a.mean - b.mean) / (abs(a.mean) + math.sqrt(a.var)), abs(a.var - b.var) / a.var
+            worst_m, worst_v = max(worst_m, em), max(worst_v, ev)
+            assert em <= 1e-12 and ev <= 1e-12, (n, k, em, ev)
+    print(f"worst relative difference between the two orders: mean {worst_m:.1e}, variance {worst_v:.1e}")
+
+
+@pytest.mark.parametrize("n", R.FLEETS)
+def test_reference_is_exact_on_a_batch_without_spread(n):
+    """gamma = 0.5, reward 0.5, no dones, 20 steps: every return is a short dyadic number (1 - 2^-t), so numpy's batch mean is that number
+    exactly and its batch variance 0 -- the premise of the GPU test that asks for the statistics bit for bit."""
+    ref = R.ReturnNormalizer(n, gamma=0.5)
+    r, d = np.full(n, 0.5, np.float32), np.zeros(n, np.uint8)
+    for t in range(20):
+        want = 1.0 - 0.5 ** (t + 1)
+        nxt = ref.returns * ref.gamma + r
+        assert (nxt == want).all() and np.mean(nxt) == want and np.var(nxt) == 0.0, (n, t)
+        ref.step(r, d)
+        assert (ref.returns == want).all()
+    assert abs(ref.count - (1e-4 + 20 * n)) < 1e-9 and 0.0 < ref.var < 1.0
+
+
+def test_clip_case_of_the_gpu_test_exercises_both_branches():
+    """N = 1000, three calls of three single steps, clip = 1: between 1 % and 50 % of the cells of calls two and three lie beyond the clip
+    on the reference (the GPU test repeats the assertion before it runs the same data)."""
+    calls, frac = R.clip_case()
+    print(f"clipped cells of calls two and three: {100 * frac:.1f} %")
+    assert len(calls) == 3 and 0.01 <= frac <= 0.5
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_scratch_size_rule_as_a_host_program(tmp_path, sanitize):
+    """tests/tools/check_retnorm_sizes.cpp walks k {1, 2, 64} x n {1, 63, 64, 65, 1000, 2^21}, six refusals of the size rule and eight
+    grid cases; built with the host compiler against the HIP headers, plainly and under the address and undefined-behaviour sanitizers,
+    and run as its own process."""
+    inc = rocm_include()
+    if inc is None:
+        pytest.skip("the HIP headers are not installed")
+    exe = str(tmp_path / "check_retnorm_sizes")
+    src = os.path.join(ROOT, "tests", "tools", "check_retnorm_sizes.cpp")
+    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + csrc] + flags + [src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert json.loads(out.stdout) == {"cases": 3 * 6 + 6 + 8, "bad": 0}
