@@ -1,0 +1,69 @@
+"""What the two fleet-wide normalisers share on the Python side (rownorm.RowNormalizer, retnorm.ReturnNormalizer): the device, the clip
+and epsilon checks, the stream, the scratch with its capture guard, and the staging of tensors that are not dense.  Shapes, state and the
+C calls are the classes' own."""
+import ctypes as C
+import math
+
+import torch
+
+from . import _capi
+
+
+class FleetNormalizer:
+    _NAME = _NOUN = None        # the class and its input tensor as the messages name them: "RowNormalizer", "rows"
+
+    def __init__(self, device, clip, epsilon):
+        clip, epsilon = float(clip), float(epsilon)
+        if not clip > 0.0:
+            raise ValueError(f"{self._NAME}.clip must be > 0 (math.inf for no clip), got {clip!r}")
+        if not epsilon >= 0.0:
+            raise ValueError(f"{self._NAME}.epsilon must be >= 0, got {epsilon!r}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"{self._NAME} needs a GPU device, got {device}; there is no CPU path")
+        self.device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
+        self.clip, self.epsilon = clip, epsilon
+        self._lib = _capi.load()
+        self._scratch = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _scratch_for(self, need):
+        """The scratch tensor of at least `need` bytes (what dn_*_scratch_bytes answered: <= 0 is its refusal)."""
+        if need <= 0:
+            _capi.check(int(need))
+        if self._scratch is None or self._scratch.numel() * 8 < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._NAME}: the scratch would have to grow inside a graph capture; call it once with {self._NOUN} of "
+                                   "this size before capturing")
+            self._scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        return self._scratch
+
+    def _check_source(self, x):
+        if not isinstance(x, torch.Tensor) or x.device != self.device or x.dtype != torch.float32:
+            raise ValueError(f"{self._NOUN} must be a float32 tensor on {self.device}; there is no CPU path")
+
+    def _stage(self, x, out, want_out):
+        """(out, the dense source, the dense destination): `out` is made when None and wanted; the kernels take dense tensors, so a
+        strided source goes through a dense copy, and a strided `out` is written in that copy (or a dense buffer) and filled by _finish."""
+        if want_out:
+            if out is None:
+                out = torch.empty(x.shape, dtype=torch.float32, device=self.device)
+            elif not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or out.shape != x.shape:
+                raise ValueError(f"out must be a float32 tensor of the shape of {self._NOUN} on the same device")
+        src = x if x.is_contiguous() else x.contiguous()
+        if out is None or out.is_contiguous():
+            dst = out
+        else:
+            dst = src if src is not x else torch.empty(x.shape, dtype=torch.float32, device=self.device)
+        return out, src, dst
+
+    @staticmethod
+    def _finish(out, dst):
+        if out is not None and dst is not out:
+            out.copy_(dst)
+        return out
+
+    def _clip_text(self):
+        return "inf" if math.isinf(self.clip) else f"{self.clip:g}"

@@ -12,16 +12,17 @@
 //                        first drone at that step; never E[x^2] - E[x]^2): across the lanes of a wave by a fixed tree, then the waves in
 //                        ascending order.  Rewards and done flags are loaded RT_STEPS steps ahead of the scan.  Writes one (mean, m2) per
 //                        (step, block) and the final returns.
-//   2. rt_merge_kernel   ONE wave, dn_rownorm's merge at width 1 with the steps side by side in the lanes (a row normaliser's lanes are
-//                        its columns; here there is one): each lane merges the blocks of a step in ascending block order into the step's
-//                        batch moments; then lane 0 applies the K steps in sequence with the reference's update, leaving per step a
-//                        snapshot of 1 / sqrt(var + eps), and the statistics after step K - 1 in `stats`.
+//   2. rt_merge_kernel   ONE wave, the merge of dn_fleet_rms.h with a lane per step (a row normaliser's lanes are its columns; here there
+//                        is one column, so the steps lie side by side in the lanes): each lane merges the blocks of a step in ascending
+//                        block order into the step's batch moments; then lane 0 applies the K steps in sequence with the reference's
+//                        update, leaving per step a snapshot of 1 / sqrt(var + eps), and the statistics after step K - 1 in `stats`.
 //   3. rt_scale_kernel   every reward of step t times the snapshot of step t, clipped: 16-byte loads and stores when both pointers are
 //                        16-byte aligned and N is a multiple of 4 (every step then starts on a 16-byte boundary), 4-byte ones otherwise.
 // The order of every float64 operation is a function of (K, N) alone, not of the CU count or a launch shape: the same call gives the same
 // bits every time, K steps in one call equal K calls of one step, and a captured graph replays it.
 // update = 0 is launch 3 alone, every workgroup taking 1 / sqrt(var + eps) from `stats` itself (which is never written).
 #include "dn_internal.h"
+#include "dn_fleet_rms.h"
 
 namespace {
 
@@ -31,7 +32,6 @@ constexpr int RT_STEPS = 8;                            // launch 1: steps whose 
 constexpr int RT_MERGE_THREADS = 64;                   // launch 2: one wave, 64 steps side by side
 constexpr int RT_SCALE_THREADS = 256;                  // launch 3
 constexpr int RT_CHUNK = (int)DN_RETNORM_CHUNK;        // floats per workgroup of launch 3
-constexpr int RT_BATCH = 8;                            // partials in flight ahead of the sequential merges
 
 typedef float rt_v4f __attribute__((ext_vector_type(4)));
 
@@ -45,27 +45,6 @@ struct RtArgs {
     double *stats, *returns, *part, *snap;             // snap == nullptr (update = 0): `stats`
     long long chunks;                                  // launch 3: workgroups per step
 };
-
-// 1 / x as dn_rownorm.hip's merge forms it (v_rcp_f64 and two Newton steps): the counts it is applied to do not depend on the data
-__device__ __forceinline__ double rt_rcp(const double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-x, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
-
-// dn_rownorm.hip rn_merge: (count, mean, m2) <- merged with the next block of nb values, mean bm, sum of squared deviations b2
-__device__ __forceinline__ void rt_merge(double &count, double &mean, double &m2, const double nb, const double bm, const double b2)
-{
-    const double tot = count + nb;
-    const double r = nb * rt_rcp(tot);
-    const double delta = bm - mean;
-    mean = mean + delta * r;
-    m2 = m2 + b2 + delta * delta * (count * r);
-    count = tot;
-}
 
 // the sum over the 64 lanes of a wave in a fixed tree (lane i + lane i + 32, then + 16, ... + 1); lane 0 holds it
 __device__ __forceinline__ double rt_wave_sum(double v)
@@ -139,81 +118,21 @@ __global__ __launch_bounds__(RT_THREADS) void rt_scan_kernel(const RtArgs a)
 __global__ __launch_bounds__(RT_MERGE_THREADS) void rt_merge_kernel(const RtArgs a)
 {
     const int tid = (int)threadIdx.x;
-    const long long last_rows = a.n - (a.nblk - 1) * DN_ROWNORM_BLOCK_ROWS;
 
-    // the batch moments of every step: its blocks in ascending order; 64 steps side by side
+    // the batch moments of every step: a lane per step, 64 steps side by side
     for (long long t = tid; t < a.k; t += RT_MERGE_THREADS) {
-        const double *p = a.part + t * a.nblk * 2;
-        double count = 0.0, mean = 0.0, m2 = 0.0;
-        double pm[RT_BATCH], p2[RT_BATCH], qm[RT_BATCH], q2[RT_BATCH];
-#pragma unroll
-        for (int j = 0; j < RT_BATCH; ++j) {
-            const bool in = j < a.nblk;
-            pm[j] = in ? p[2 * j] : 0.0;
-            p2[j] = in ? p[2 * j + 1] : 0.0;
-        }
-        for (long long b0 = 0; b0 < a.nblk; b0 += RT_BATCH) {
-#pragma unroll
-            for (int j = 0; j < RT_BATCH; ++j) {       // the next batch is on its way while this one is merged
-                const long long b = b0 + RT_BATCH + j;
-                const bool in = b < a.nblk;
-                qm[j] = in ? p[2 * b] : 0.0;
-                q2[j] = in ? p[2 * b + 1] : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < RT_BATCH; ++j) {
-                const long long b = b0 + j;
-                if (b < a.nblk) {
-                    const double nb = (double)(b == a.nblk - 1 ? last_rows : DN_ROWNORM_BLOCK_ROWS);
-                    if (b == 0) { count = nb; mean = pm[j]; m2 = p2[j]; }
-                    else rt_merge(count, mean, m2, nb, pm[j], p2[j]);
-                }
-                pm[j] = qm[j];
-                p2[j] = q2[j];
-            }
-        }
+        double mean, m2;
+        fr_merge_blocks(a.part + t * a.nblk * 2, 2, 1, a.nblk, a.n, mean, m2);
         a.snap[2 * t] = mean;                          // parked in the step's snapshot until the sequential pass below
         a.snap[2 * t + 1] = m2;
     }
     __syncthreads();
 
-    // the K updates in sequence (normalize.py:32-47 with the step's N returns as the batch)
+    // the K updates in sequence on lane 0: the snapshot of step t becomes 1 / sqrt(var + eps)
     if (tid == 0) {
         double count = a.stats[0], mean = a.stats[1], var = a.stats[2];
-        const double nn = (double)a.n;
         double *s = a.snap;
-        double pm[RT_BATCH], p2[RT_BATCH], qm[RT_BATCH], q2[RT_BATCH];
-#pragma unroll
-        for (int j = 0; j < RT_BATCH; ++j) {
-            const bool in = j < a.k;
-            pm[j] = in ? s[2 * j] : 0.0;
-            p2[j] = in ? s[2 * j + 1] : 0.0;
-        }
-        for (long long t0 = 0; t0 < a.k; t0 += RT_BATCH) {
-#pragma unroll
-            for (int j = 0; j < RT_BATCH; ++j) {
-                const long long t = t0 + RT_BATCH + j;
-                const bool in = t < a.k;
-                qm[j] = in ? s[2 * t] : 0.0;
-                q2[j] = in ? s[2 * t + 1] : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < RT_BATCH; ++j) {
-                const long long t = t0 + j;
-                if (t < a.k) {
-                    const double batch_var = p2[j] / nn;                       // np.var: the population variance
-                    const double delta = pm[j] - mean;
-                    const double tot = count + nn;
-                    mean = mean + delta * nn / tot;
-                    const double m_a = var * count, m_b = batch_var * nn;
-                    var = (m_a + m_b + delta * delta * count * nn / tot) / tot;
-                    count = tot;
-                    s[2 * t] = (double)__builtin_amdgcn_rsqf((float)(var + a.eps));
-                }
-                pm[j] = qm[j];
-                p2[j] = q2[j];
-            }
-        }
+        fr_update_steps(s, 2, 1, a.k, a.n, a.eps, count, mean, var, [s](const long long t, const double, const double rstd) { s[2 * t] = rstd; });
         a.stats[0] = count;
         a.stats[1] = mean;
         a.stats[2] = var;

@@ -9,15 +9,17 @@
 //                          sum of squared deviations in float64, in the SHIFTED form (sums of x - x0 and (x - x0)^2 with x0 the
 //                          block's first row; never E[x^2] - E[x]^2 of the raw values).  4-byte loads, a wave reading whole rows side by
 //                          side (rows are 4-byte aligned only, and the pass is a reduction: a row's words go to different columns).
-//   2. rn_merge_kernel     ONE workgroup: 8 steps at a time, each step's blocks merged in ascending block order into the step's batch
-//                          moments; then the K steps in sequence with the reference's update, leaving per step a snapshot of the mean
-//                          and of 1 / sqrt(var + eps), and the statistics after step K - 1 in `stats`.
+//   2. rn_merge_kernel     ONE workgroup, the merge of dn_fleet_rms.h with a lane per column: 8 steps at a time (one per wave), each
+//                          step's blocks merged in ascending block order into the step's batch moments; then the lanes of wave 0 take the
+//                          K steps in sequence with the reference's update, leaving per step a snapshot of the mean and of
+//                          1 / sqrt(var + eps), and the statistics after step K - 1 in `stats`.
 //   3. rn_normalize_kernel every row of step t with the snapshot of step t: 16-byte loads and stores when the width is a multiple of 4 and
 //                          both pointers are 16-byte aligned (decided from the pointers at run time), 4-byte ones otherwise.
 // The order of every float64 operation is a function of (K, N, W) alone, not of the CU count or a launch shape: the same call gives the
 // same bits every time, K steps in one call equal K calls of one step, and a captured graph replays it.
 // update = 0 is launch 3 alone, every workgroup taking mean and 1 / sqrt(var + eps) from `stats` itself (which is never written).
 #include "dn_internal.h"
+#include "dn_fleet_rms.h"
 
 namespace {
 
@@ -27,7 +29,6 @@ constexpr int RN_MERGE_THREADS = 512;                  // launch 2: 8 steps side
 constexpr int RN_MERGE_STEPS = RN_MERGE_THREADS / 64;
 constexpr int RN_NORM_THREADS = 256;                   // launch 3
 constexpr int RN_CHUNK = 4096;                         // floats per workgroup of launch 3
-constexpr int RN_BATCH = 8;                            // partials in flight ahead of the sequential merges
 
 typedef float rn_v4f __attribute__((ext_vector_type(4)));
 
@@ -42,30 +43,6 @@ struct RnArgs {
     long long snap_stride;                             // doubles between the snapshots of two steps; snap == nullptr (update = 0): `stats`
     long long chunks;                                  // launch 3: workgroups per step
 };
-
-// 1 / x as the step kernels form it (dn_kernels.hip rcp_f64): v_rcp_f64 and two Newton steps, 5 instructions where an IEEE division is ~35
-__device__ __forceinline__ double rn_rcp(const double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-x, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
-
-// (count, mean, m2) <- merged with the next block: nb values of mean bm and sum of squared deviations b2.  The formula of
-// update_mean_var_count_from_moments (normalize.py:32-47) on sums of squared deviations, with nb / tot taken once, by reciprocal: the
-// counts do not depend on the data, so it stays off the chain mean -> delta -> mean that one wave walks block by block (a step of
-// 2 M rows is 2048 blocks).  The reference has no blocks to be literal about; the K updates below are literal.
-__device__ __forceinline__ void rn_merge(double &count, double &mean, double &m2, const double nb, const double bm, const double b2)
-{
-    const double tot = count + nb;
-    const double r = nb * rn_rcp(tot);
-    const double delta = bm - mean;
-    mean = mean + delta * r;
-    m2 = m2 + b2 + delta * delta * (count * r);
-    count = tot;
-}
 
 __global__ __launch_bounds__(RN_THREADS) void rn_partial_kernel(const RnArgs a)
 {
@@ -114,84 +91,26 @@ __global__ __launch_bounds__(RN_MERGE_THREADS) void rn_merge_kernel(const RnArgs
 {
     const int w = a.w, tid = (int)threadIdx.x, c = tid & 63, sl = tid >> 6;
     const bool on = c < w;
-    const long long last_rows = a.n - (a.nblk - 1) * DN_ROWNORM_BLOCK_ROWS;
 
-    // the batch moments of every step: its blocks in ascending order; 8 steps side by side
+    // the batch moments of every step: a lane per column, 8 steps side by side
     for (long long t = sl; t < a.k; t += RN_MERGE_STEPS) {
         if (on) {
-            const double *p = a.part + t * a.nblk * (2 * w) + c;
-            double count = 0.0, mean = 0.0, m2 = 0.0;
-            double pm[RN_BATCH], p2[RN_BATCH], qm[RN_BATCH], q2[RN_BATCH];
-#pragma unroll
-            for (int j = 0; j < RN_BATCH; ++j) {
-                const bool in = j < a.nblk;
-                pm[j] = in ? p[(long long)j * (2 * w)] : 0.0;
-                p2[j] = in ? p[(long long)j * (2 * w) + w] : 0.0;
-            }
-            for (long long b0 = 0; b0 < a.nblk; b0 += RN_BATCH) {
-#pragma unroll
-                for (int j = 0; j < RN_BATCH; ++j) {   // the next batch is on its way while this one is merged
-                    const long long b = b0 + RN_BATCH + j;
-                    const bool in = b < a.nblk;
-                    qm[j] = in ? p[b * (2 * w)] : 0.0;
-                    q2[j] = in ? p[b * (2 * w) + w] : 0.0;
-                }
-#pragma unroll
-                for (int j = 0; j < RN_BATCH; ++j) {
-                    const long long b = b0 + j;
-                    if (b < a.nblk) {
-                        const double nb = (double)(b == a.nblk - 1 ? last_rows : DN_ROWNORM_BLOCK_ROWS);
-                        if (b == 0) { count = nb; mean = pm[j]; m2 = p2[j]; }
-                        else rn_merge(count, mean, m2, nb, pm[j], p2[j]);
-                    }
-                    pm[j] = qm[j];
-                    p2[j] = q2[j];
-                }
-            }
+            double mean, m2;
+            fr_merge_blocks(a.part + t * a.nblk * (2 * w) + c, 2 * w, w, a.nblk, a.n, mean, m2);
             a.snap[t * (2 * w) + c] = mean;            // parked in the step's snapshot until the sequential pass below
             a.snap[t * (2 * w) + w + c] = m2;
         }
     }
     __syncthreads();
 
-    // the K updates in sequence (normalize.py:32-47 with the step's N rows as the batch), one lane per column
+    // the K updates in sequence, one lane per column: the snapshot of step t becomes its mean and 1 / sqrt(var + eps)
     if (sl == 0 && on) {
         double count = a.stats[0], mean = a.stats[1 + c], var = a.stats[1 + w + c];
-        const double nn = (double)a.n;
         double *s = a.snap + c;
-        double pm[RN_BATCH], p2[RN_BATCH], qm[RN_BATCH], q2[RN_BATCH];
-#pragma unroll
-        for (int j = 0; j < RN_BATCH; ++j) {
-            const bool in = j < a.k;
-            pm[j] = in ? s[(long long)j * (2 * w)] : 0.0;
-            p2[j] = in ? s[(long long)j * (2 * w) + w] : 0.0;
-        }
-        for (long long t0 = 0; t0 < a.k; t0 += RN_BATCH) {
-#pragma unroll
-            for (int j = 0; j < RN_BATCH; ++j) {
-                const long long t = t0 + RN_BATCH + j;
-                const bool in = t < a.k;
-                qm[j] = in ? s[t * (2 * w)] : 0.0;
-                q2[j] = in ? s[t * (2 * w) + w] : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < RN_BATCH; ++j) {
-                const long long t = t0 + j;
-                if (t < a.k) {
-                    const double batch_var = p2[j] / nn;                       // np.var: the population variance
-                    const double delta = pm[j] - mean;
-                    const double tot = count + nn;
-                    mean = mean + delta * nn / tot;
-                    const double m_a = var * count, m_b = batch_var * nn;
-                    var = (m_a + m_b + delta * delta * count * nn / tot) / tot;
-                    count = tot;
-                    s[t * (2 * w)] = mean;
-                    s[t * (2 * w) + w] = (double)__builtin_amdgcn_rsqf((float)(var + a.eps));
-                }
-                pm[j] = qm[j];
-                p2[j] = q2[j];
-            }
-        }
+        fr_update_steps(s, 2 * w, w, a.k, a.n, a.eps, count, mean, var, [s, w](const long long t, const double m, const double rstd) {
+            s[t * (2 * w)] = m;
+            s[t * (2 * w) + w] = rstd;
+        });
         if (c == 0) a.stats[0] = count;
         a.stats[1 + c] = mean;
         a.stats[1 + w + c] = var;

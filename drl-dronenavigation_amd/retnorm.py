@@ -9,14 +9,14 @@ per-drone NormalizeReward (norm_rew) keeps one statistic per drone and runs insi
 kernels alone.  Each rank keeps its own statistics: there is no collective.
 """
 import ctypes as C
-import math
 
 import torch
 
 from . import _capi
+from ._fleetnorm import FleetNormalizer
 
 
-class ReturnNormalizer:
+class ReturnNormalizer(FleetNormalizer):
     """num_envs: the fleet; device: a GPU (there is no CPU path); gamma: the discount of the returns, the normaliser's own (SB3's default
     0.99); clip: +-clip bounds the output (math.inf: none); epsilon: added to the variance.
 
@@ -27,6 +27,7 @@ class ReturnNormalizer:
 
     stats: the device float64 tensor [3]: count, mean, var.  returns: the device float64 tensor [N].  state_dict() / load_state_dict()
     copy both, so a round trip is exact.  reset() is RunningMeanStd.__init__ and zero returns; reset_returns() zeroes the returns only."""
+    _NAME, _NOUN = "ReturnNormalizer", "rewards"
 
     def __init__(self, num_envs, device, *, gamma=0.99, clip=10.0, epsilon=1e-8):
         if isinstance(num_envs, bool) or not isinstance(num_envs, int) or num_envs < 1:
@@ -34,24 +35,12 @@ class ReturnNormalizer:
         gamma, clip, epsilon = float(gamma), float(clip), float(epsilon)
         if not 0.0 <= gamma <= 1.0:
             raise ValueError(f"ReturnNormalizer.gamma must be in [0, 1], got {gamma!r}")
-        if not clip > 0.0:
-            raise ValueError(f"ReturnNormalizer.clip must be > 0 (math.inf for no clip), got {clip!r}")
-        if not epsilon >= 0.0:
-            raise ValueError(f"ReturnNormalizer.epsilon must be >= 0, got {epsilon!r}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"ReturnNormalizer needs a GPU device, got {device}; there is no CPU path")
-        self.device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
-        self.num_envs, self.gamma, self.clip, self.epsilon = num_envs, gamma, clip, epsilon
+        super().__init__(device, clip, epsilon)
+        self.num_envs, self.gamma = num_envs, gamma
         self._cfg = _capi.DnRetnormConfig(gamma, epsilon, clip, 0)
-        self._lib = _capi.load()
         self.stats = torch.empty(3, dtype=torch.float64, device=self.device)
         self.returns = torch.empty(num_envs, dtype=torch.float64, device=self.device)
-        self._scratch = None
         self.reset()
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _init(self, stats):
         with torch.cuda.device(self.device):
@@ -84,49 +73,26 @@ class ReturnNormalizer:
         self.stats.copy_(torch.as_tensor(state["stats"]))
         self.returns.copy_(torch.as_tensor(state["returns"]))
 
-    def _scratch_for(self, k, n):
-        need = self._lib.dn_retnorm_scratch_bytes(k, n)
-        if need <= 0:
-            _capi.check(int(need))
-        if self._scratch is None or self._scratch.numel() * 8 < need:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("ReturnNormalizer: the scratch would have to grow inside a graph capture; call it once with rewards of "
-                                   "this size before capturing")
-            self._scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
-        return self._scratch
-
     def _run(self, rewards, dones, out, update, want_out=True):
         n = self.num_envs
-        if not isinstance(rewards, torch.Tensor) or rewards.device != self.device or rewards.dtype != torch.float32:
-            raise ValueError(f"rewards must be a float32 tensor on {self.device}; there is no CPU path")
+        self._check_source(rewards)
         if rewards.dim() not in (1, 2) or rewards.shape[-1] != n or rewards.numel() == 0:
             raise ValueError(f"rewards must be [{n}] or [K, {n}] with K >= 1, got {tuple(rewards.shape)}")
         k = 1 if rewards.dim() == 1 else rewards.shape[0]
         if update and (not isinstance(dones, torch.Tensor) or dones.device != self.device or dones.dtype != torch.uint8
                        or dones.shape != rewards.shape):
             raise ValueError("dones must be a uint8 tensor of the shape of rewards on the same device")
-        if want_out:
-            if out is None:
-                out = torch.empty(rewards.shape, dtype=torch.float32, device=self.device)
-            elif not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or out.shape != rewards.shape:
-                raise ValueError("out must be a float32 tensor of the shape of rewards on the same device")
-        src = rewards if rewards.is_contiguous() else rewards.contiguous()
-        if out is None or out.is_contiguous():
-            dst = out
-        else:                   # a strided `out`: scale in the dense copy of the rewards (or a dense buffer) and copy the cells across
-            dst = src if src is not rewards else torch.empty(rewards.shape, dtype=torch.float32, device=self.device)
+        out, src, dst = self._stage(rewards, out, want_out)
         flags = scratch = None
         if update:
             flags = dones if dones.is_contiguous() else dones.contiguous()
-            scratch = self._scratch_for(k, n)
+            scratch = self._scratch_for(self._lib.dn_retnorm_scratch_bytes(k, n))
         with torch.cuda.device(self.device):
             _capi.check(self._lib.dn_retnorm(C.byref(self._cfg), self.stats.data_ptr(), self.returns.data_ptr(), k, n, src.data_ptr(),
                                              None if flags is None else flags.data_ptr(), None if dst is None else dst.data_ptr(),
                                              int(update), None if scratch is None else scratch.data_ptr(),
                                              0 if scratch is None else scratch.numel() * 8, self.device.index, self._stream()))
-        if out is not None and dst is not out:
-            out.copy_(dst)
-        return out
+        return self._finish(out, dst)
 
     def update_normalize(self, rewards, dones, out=None):
         return self._run(rewards, dones, out, True)
@@ -138,6 +104,5 @@ class ReturnNormalizer:
         self._run(rewards, dones, None, True, want_out=False)
 
     def __repr__(self):
-        clip = "inf" if math.isinf(self.clip) else f"{self.clip:g}"
-        return (f"ReturnNormalizer(num_envs={self.num_envs}, device={str(self.device)!r}, gamma={self.gamma:g}, clip={clip}, "
+        return (f"ReturnNormalizer(num_envs={self.num_envs}, device={str(self.device)!r}, gamma={self.gamma:g}, clip={self._clip_text()}, "
                 f"epsilon={self.epsilon:g})")

@@ -9,16 +9,16 @@ device, so a captured graph keeps them moving.  Each rank keeps its own statisti
 they agree closely; a delta-tracking merge is a later change).
 """
 import ctypes as C
-import math
 
 import torch
 
 from . import _capi
+from ._fleetnorm import FleetNormalizer
 
 MAX_WIDTH = 64
 
 
-class RowNormalizer:
+class RowNormalizer(FleetNormalizer):
     """width: columns of a row, 1..64; device: a GPU (there is no CPU path); clip: +-clip bounds the output (math.inf: none); epsilon:
     added to the variance.
 
@@ -28,28 +28,16 @@ class RowNormalizer:
     are staged through a dense copy: the kernels take dense rows.
 
     stats: the device float64 tensor [1 + 2 W]: count, mean[W], var[W].  state_dict() / load_state_dict() copy it, so a round trip is exact."""
+    _NAME, _NOUN = "RowNormalizer", "rows"
 
     def __init__(self, width, device, *, clip=10.0, epsilon=1e-8):
         if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= MAX_WIDTH:
             raise ValueError(f"RowNormalizer.width must be an integer in 1..{MAX_WIDTH}, got {width!r}")
-        clip, epsilon = float(clip), float(epsilon)
-        if not clip > 0.0:
-            raise ValueError(f"RowNormalizer.clip must be > 0 (math.inf for no clip), got {clip!r}")
-        if not epsilon >= 0.0:
-            raise ValueError(f"RowNormalizer.epsilon must be >= 0, got {epsilon!r}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"RowNormalizer needs a GPU device, got {device}; there is no CPU path")
-        self.device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
-        self.width, self.clip, self.epsilon = width, clip, epsilon
-        self._cfg = _capi.DnRownormConfig(width, clip, epsilon)
-        self._lib = _capi.load()
+        super().__init__(device, clip, epsilon)
+        self.width = width
+        self._cfg = _capi.DnRownormConfig(width, self.clip, self.epsilon)
         self.stats = torch.empty(1 + 2 * width, dtype=torch.float64, device=self.device)
-        self._scratch = None
         self.reset()
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def reset(self):
         """count = 1e-4, mean = 0, var = 1 (RunningMeanStd.__init__)."""
@@ -71,41 +59,18 @@ class RowNormalizer:
             raise ValueError(f"stats must be float64 [{self.stats.shape[0]}], got {s.dtype} {tuple(s.shape)}")
         self.stats.copy_(s)
 
-    def _scratch_for(self, k, n):
-        need = self._lib.dn_rownorm_scratch_bytes(k, n, self.width)
-        if need <= 0:
-            _capi.check(int(need))
-        if self._scratch is None or self._scratch.numel() * 8 < need:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("RowNormalizer: the scratch would have to grow inside a graph capture; call it once with rows of this "
-                                   "size before capturing")
-            self._scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
-        return self._scratch
-
     def _run(self, rows, out, update, want_out=True):
-        if not isinstance(rows, torch.Tensor) or rows.device != self.device or rows.dtype != torch.float32:
-            raise ValueError(f"rows must be a float32 tensor on {self.device}; there is no CPU path")
+        self._check_source(rows)
         if rows.dim() not in (2, 3) or rows.shape[-1] != self.width or rows.numel() == 0:
             raise ValueError(f"rows must be [N, {self.width}] or [K, N, {self.width}] with N >= 1, got {tuple(rows.shape)}")
         k, n = (1, rows.shape[0]) if rows.dim() == 2 else (rows.shape[0], rows.shape[1])
-        if want_out:
-            if out is None:
-                out = torch.empty(rows.shape, dtype=torch.float32, device=self.device)
-            elif not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32 or out.shape != rows.shape:
-                raise ValueError("out must be a float32 tensor of the shape of rows on the same device")
-        src = rows if rows.is_contiguous() else rows.contiguous()
-        if out is None or out.is_contiguous():
-            dst = out
-        else:                   # a strided `out`: normalise in the dense copy of the rows (or a dense buffer) and copy the cells across
-            dst = src if src is not rows else torch.empty(rows.shape, dtype=torch.float32, device=self.device)
-        scratch = self._scratch_for(k, n)
+        out, src, dst = self._stage(rows, out, want_out)
+        scratch = self._scratch_for(self._lib.dn_rownorm_scratch_bytes(k, n, self.width))
         with torch.cuda.device(self.device):
             _capi.check(self._lib.dn_rownorm(C.byref(self._cfg), self.stats.data_ptr(), k, n, src.data_ptr(),
                                              None if dst is None else dst.data_ptr(), int(update), scratch.data_ptr(), scratch.numel() * 8,
                                              self.device.index, self._stream()))
-        if out is not None and dst is not out:
-            out.copy_(dst)
-        return out
+        return self._finish(out, dst)
 
     def update_normalize(self, rows, out=None):
         return self._run(rows, out, True)
@@ -117,5 +82,4 @@ class RowNormalizer:
         self._run(rows, None, True, want_out=False)
 
     def __repr__(self):
-        clip = "inf" if math.isinf(self.clip) else f"{self.clip:g}"
-        return f"RowNormalizer(width={self.width}, device={str(self.device)!r}, clip={clip}, epsilon={self.epsilon:g})"
+        return f"RowNormalizer(width={self.width}, device={str(self.device)!r}, clip={self._clip_text()}, epsilon={self.epsilon:g})"

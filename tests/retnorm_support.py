@@ -4,7 +4,8 @@ Sol/Model/Environments/normalize.py:10-47 with np.mean / np.var of a step's retu
 module like tests/rownorm_support.py: pytest does not collect it.  NumPy only."""
 import numpy as np
 
-from rownorm_support import BLOCK_ROWS, ulp_distance  # noqa: F401  (csrc/dn_internal.h DN_ROWNORM_BLOCK_ROWS; the float32 ulp distance)
+# csrc/dn_internal.h DN_ROWNORM_BLOCK_ROWS; the float32 ulp distance; the literal update, which both references share
+from rownorm_support import BLOCK_ROWS, ulp_distance, update_from_moments  # noqa: F401
 
 FLEETS = (1, 63, 64, 65, 1000, 2 * BLOCK_ROWS + 1)      # the last: three blocks, the third of one drone
 STEPS = (1, 3, 9, 17)
@@ -20,14 +21,7 @@ class ReturnNormalizer:
 
     def _update(self, x):
         """normalize.py:19-47, batch form, on a vector of scalars."""
-        batch_mean, batch_var, batch_count = np.mean(x), np.var(x), x.shape[0]
-        delta = batch_mean - self.mean
-        tot_count = self.count + batch_count
-        new_mean = self.mean + delta * batch_count / tot_count
-        m_a = self.var * self.count
-        m_b = batch_var * batch_count
-        M2 = m_a + m_b + np.square(delta) * self.count * batch_count / tot_count
-        self.mean, self.var, self.count = new_mean, M2 / tot_count, tot_count
+        self.mean, self.var, self.count = update_from_moments(self.mean, self.var, self.count, np.mean(x), np.var(x), x.shape[0])
 
     def step(self, r, d):
         """r float32 [n], d uint8 [n] -> the scaled, clipped reward in float64."""

@@ -8,6 +8,18 @@ CONSTANT = 3.25
 BLOCK_ROWS = 1024           # csrc/dn_internal.h DN_ROWNORM_BLOCK_ROWS
 
 
+def update_from_moments(mean, var, count, batch_mean, batch_var, batch_count):
+    """update_mean_var_count_from_moments, normalize.py:19-47, literally: (mean, var, count) after the batch.  The caller forms the batch
+    moments, np.mean / np.var in its own shape, so that NumPy sums in the order it always has."""
+    delta = batch_mean - mean
+    tot_count = count + batch_count
+    new_mean = mean + delta * batch_count / tot_count
+    m_a = var * count
+    m_b = batch_var * batch_count
+    M2 = m_a + m_b + np.square(delta) * count * batch_count / tot_count
+    return new_mean, M2 / tot_count, tot_count
+
+
 class RunningMeanStd:
     """normalize.py:10-47, batch form."""
 
@@ -18,14 +30,7 @@ class RunningMeanStd:
 
     def update(self, x):
         x = np.asarray(x, np.float64)
-        batch_mean, batch_var, batch_count = np.mean(x, axis=0), np.var(x, axis=0), x.shape[0]
-        delta = batch_mean - self.mean
-        tot_count = self.count + batch_count
-        new_mean = self.mean + delta * batch_count / tot_count
-        m_a = self.var * self.count
-        m_b = batch_var * batch_count
-        M2 = m_a + m_b + np.square(delta) * self.count * batch_count / tot_count
-        self.mean, self.var, self.count = new_mean, M2 / tot_count, tot_count
+        self.mean, self.var, self.count = update_from_moments(self.mean, self.var, self.count, np.mean(x, axis=0), np.var(x, axis=0), x.shape[0])
 
     def stats(self):
         return np.concatenate(([self.count], self.mean, self.var))

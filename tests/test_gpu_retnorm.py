@@ -9,11 +9,13 @@
  6. in place = out of place, guard cells around `out` and `returns`, a 4-byte-aligned view = its aligned copy, bit for bit;
  7. update = 0 leaves the bytes of `stats` and `returns` alone; a NaN and an infinite reward stay in their own cells;
  8. state_dict -> a fresh ReturnNormalizer -> load_state_dict continues bit-identically; reset_returns;
- 9. RolloutCollector(reward_norm=...) against a ReturnNormalizer driven by the test, eager and graph-replayed.
+ 9. 1, 2, 4 and 5 at (K, N) = (9, 8 blocks), (17, 8 blocks + 1 drone), (9, 16 blocks + 1 drone): the merge launch beyond one batch of 8
+    blocks;
+10. RolloutCollector(reward_norm=...) against a ReturnNormalizer driven by the test, eager and graph-replayed.
 
 Shapes: N in {1, 63, 64, 65, 1000} and 2049, just above two blocks of DN_ROWNORM_BLOCK_ROWS = 1024 drones (three blocks, the last of one
 drone); K in {1, 3, 9, 17}: 9 is one past the 8 steps whose rewards the scan loads ahead, 17 one past two of the merge's 8-deep prefetch
-batches; and K = 65 in test 5, one past the 64 steps the merge takes side by side."""
+batches; and K = 65 in test 5, one past the 64 steps the merge takes side by side; and those of 9."""
 import functools
 
 import numpy as np
@@ -31,6 +33,9 @@ from model_support import NOISE  # noqa: E402
 PATTERN = 0x7FC12345                    # a quiet NaN nothing here produces
 PATTERN64 = 0x7FF8123456789ABC
 FLEETS, STEPS = R.FLEETS, R.STEPS
+# (K, N) past one batch of 8 blocks in the merge launch: 8 blocks; 9 blocks, the last of one drone (a second pass of the block loop whose
+# prefetch had one block in range); 17 blocks (the prefetch full once and partial once)
+MERGE_CASES = ((9, 8 * R.BLOCK_ROWS), (17, 8 * R.BLOCK_ROWS + 1), (9, 16 * R.BLOCK_ROWS + 1))
 
 
 def _dev(x):
@@ -91,6 +96,23 @@ def test_returns_match_the_reference_bit_for_bit(N):
         assert rets[0][N - 1] == 0.0 and (N == 1 or (rets[2] != 0.0).any())
 
 
+def _check_statistics(pkg, N, K):
+    """Three calls of _case(N, K) against the reference after every call.  Returns the worst relative error of the mean and the variance."""
+    worst_m = worst_v = 0.0
+    calls, _, stats, _ = _case(N, K)
+    norm = pkg.ReturnNormalizer(N, DEV)
+    for call, (r, d) in enumerate(calls):
+        norm.update(_rows(r, K), _rows(d, K))
+        got, want = norm.stats.cpu().numpy(), stats[call][K - 1]
+        assert got[0] == want[0] and abs(got[0] - (1e-4 + (call + 1) * K * N)) < 1e-9, (N, K, call)
+        em = abs(got[1] - want[1]) / (abs(want[1]) + np.sqrt(want[2]))
+        ev = abs(got[2] - want[2]) / want[2]
+        worst_m, worst_v = max(worst_m, em), max(worst_v, ev)
+        assert em <= 1e-9 and ev <= 1e-9, (N, K, call, em, ev)
+        assert float(norm.count) == got[0] and float(norm.mean) == got[1] and float(norm.var) == got[2]
+    return worst_m, worst_v
+
+
 @pytest.mark.parametrize("N", FLEETS)
 def test_statistics_match_the_reference(N):
     """count exact; |mean - ref| <= 1e-9 (|ref mean| + ref std); |var - ref| <= 1e-9 ref var, after every call: a fixed-order float64
@@ -99,17 +121,8 @@ def test_statistics_match_the_reference(N):
     pkg = _pkg()
     worst_m = worst_v = 0.0
     for K in STEPS:
-        calls, _, stats, _ = _case(N, K)
-        norm = pkg.ReturnNormalizer(N, DEV)
-        for call, (r, d) in enumerate(calls):
-            norm.update(_rows(r, K), _rows(d, K))
-            got, want = norm.stats.cpu().numpy(), stats[call][K - 1]
-            assert got[0] == want[0] and abs(got[0] - (1e-4 + (call + 1) * K * N)) < 1e-9, (N, K, call)
-            em = abs(got[1] - want[1]) / (abs(want[1]) + np.sqrt(want[2]))
-            ev = abs(got[2] - want[2]) / want[2]
-            worst_m, worst_v = max(worst_m, em), max(worst_v, ev)
-            assert em <= 1e-9 and ev <= 1e-9, (N, K, call, em, ev)
-            assert float(norm.count) == got[0] and float(norm.mean) == got[1] and float(norm.var) == got[2]
+        em, ev = _check_statistics(pkg, N, K)
+        worst_m, worst_v = max(worst_m, em), max(worst_v, ev)
     print(f"N={N}: worst relative error of the mean {worst_m:.3e} (of |mean| + std), of the variance {worst_v:.3e}; bars 1e-9")
 
 
@@ -142,22 +155,28 @@ def _check_output(got, r, var, clip, tag):
     return int(dist.max()), int(hi.sum() + lo.sum())
 
 
+def _check_output_of_case(pkg, N, K):
+    """The three calls of _case(N, K) as calls of one step, so that the variance every step was scaled with can be read back; after each
+    call its K steps again with update = 0.  Returns the largest ulp distance."""
+    worst = 0
+    calls, _, _, _ = _case(N, K)
+    norm = pkg.ReturnNormalizer(N, DEV)
+    for call, (r, d) in enumerate(calls):
+        for t in range(K):
+            out = norm.update_normalize(_dev(r[t]), _dev(d[t])).cpu().numpy()
+            var = float(norm.stats.cpu().numpy()[2])
+            worst = max(worst, _check_output(out, r[t], var, 10.0, (N, K, call, t, "update"))[0])
+        out0 = norm.normalize(_rows(r, K)).cpu().numpy()
+        worst = max(worst, _check_output(out0, r if K > 1 else r[0], var, 10.0, (N, K, call, "normalize"))[0])
+    return worst
+
+
 @pytest.mark.parametrize("N", FLEETS)
 def test_output_is_within_three_ulp_of_the_float64_expression(N):
     """K = 1 calls, so that the variance every step was scaled with can be read back: out against clip(r / sqrt(var + eps)) in float64 on
     the device's own variance -- the statistics' error does not enter.  update = 1 and update = 0."""
     pkg = _pkg()
-    worst = 0
-    for K in STEPS:
-        calls, _, _, _ = _case(N, K)
-        norm = pkg.ReturnNormalizer(N, DEV)
-        for call, (r, d) in enumerate(calls):
-            for t in range(K):
-                out = norm.update_normalize(_dev(r[t]), _dev(d[t])).cpu().numpy()
-                var = float(norm.stats.cpu().numpy()[2])
-                worst = max(worst, _check_output(out, r[t], var, 10.0, (N, K, call, t, "update"))[0])
-            out0 = norm.normalize(_rows(r, K)).cpu().numpy()
-            worst = max(worst, _check_output(out0, r if K > 1 else r[0], var, 10.0, (N, K, call, "normalize"))[0])
+    worst = max(_check_output_of_case(pkg, N, K) for K in STEPS)
     print(f"N={N}: largest distance from the float64 expression {worst} float32 ulp (bar 3)")
 
 
@@ -198,26 +217,30 @@ def _copy_of(pkg, norm, **kw):
     return other
 
 
+def _check_one_call_equals_k_calls(pkg, K, N):
+    first = _started(pkg, N, clip=2.5)
+    one, many, again, silent = (_copy_of(pkg, first, clip=2.5) for _ in range(4))
+    r, d = R.make_rewards(np.random.default_rng(1000 * K + N), K, N)
+    r, d = _dev(r), _dev(d)
+    whole = one.update_normalize(r, d)
+    for t in range(K):
+        _same(many.update_normalize(r[t], d[t]), whole[t], (K, N, t))
+    _same(one.stats, many.stats, (K, N, "statistics"))
+    _same(one.returns, many.returns, (K, N, "returns"))
+    _same(again.update_normalize(r, d), whole, (K, N, "the same call from the same state"))
+    _same(again.stats, one.stats, (K, N, "statistics of the same call"))
+    _same(again.returns, one.returns, (K, N, "returns of the same call"))
+    silent.update(r, d)                            # update only (out = NULL) moves the state the same way
+    _same(silent.stats, one.stats, (K, N, "update without an output"))
+    _same(silent.returns, one.returns, (K, N, "update without an output: returns"))
+    assert not torch.equal(one.stats, first.stats)
+
+
 @pytest.mark.parametrize("K,fleets", [(3, FLEETS), (9, FLEETS), (17, FLEETS), (65, (65, 2049))], ids=["K3", "K9", "K17", "K65"])
 def test_k_steps_in_one_call_equal_k_calls(K, fleets):
     pkg = _pkg()
     for N in fleets:
-        first = _started(pkg, N, clip=2.5)
-        one, many, again, silent = (_copy_of(pkg, first, clip=2.5) for _ in range(4))
-        r, d = R.make_rewards(np.random.default_rng(1000 * K + N), K, N)
-        r, d = _dev(r), _dev(d)
-        whole = one.update_normalize(r, d)
-        for t in range(K):
-            _same(many.update_normalize(r[t], d[t]), whole[t], (K, N, t))
-        _same(one.stats, many.stats, (K, N, "statistics"))
-        _same(one.returns, many.returns, (K, N, "returns"))
-        _same(again.update_normalize(r, d), whole, (K, N, "the same call from the same state"))
-        _same(again.stats, one.stats, (K, N, "statistics of the same call"))
-        _same(again.returns, one.returns, (K, N, "returns of the same call"))
-        silent.update(r, d)                            # update only (out = NULL) moves the state the same way
-        _same(silent.stats, one.stats, (K, N, "update without an output"))
-        _same(silent.returns, one.returns, (K, N, "update without an output: returns"))
-        assert not torch.equal(one.stats, first.stats)
+        _check_one_call_equals_k_calls(pkg, K, N)
 
 
 # ---- 6. in place, guards, alignment -----------------------------------------------------------------------------------------------------
@@ -356,7 +379,36 @@ def test_state_dict_round_trip_continues_bit_identically():
         a.update_normalize(torch.zeros(N, device=DEV), torch.zeros(N, device=DEV))
 
 
-# ---- 9. the collector -------------------------------------------------------------------------------------------------------------------
+# ---- 9. more than one batch of blocks ---------------------------------------------------------------------------------------------------
+merge_cases = pytest.mark.parametrize("K,N", MERGE_CASES, ids=["K%d-N%d" % c for c in MERGE_CASES])
+
+
+@merge_cases
+def test_merge_batches_statistics_and_returns_match_the_reference(K, N):
+    """The bars of test 2 (count exact, mean and variance within 1e-9) and the returns of test 1, bit for bit.  The bars hold on the
+    reference's side at these shapes too: a NumPy emulation of the blocked, shifted merge on this data stays within 3e-14 of the
+    reference there."""
+    pkg = _pkg()
+    em, ev = _check_statistics(pkg, N, K)
+    norm = pkg.ReturnNormalizer(N, DEV)
+    for call, (r, d) in enumerate(_case(N, K)[0]):
+        norm.update(_rows(r, K), _rows(d, K))
+        assert norm.returns.cpu().numpy().tobytes() == _case(N, K)[3][call].tobytes(), (N, K, call)
+    print(f"K={K} N={N}: relative error of the mean {em:.3e} (of |mean| + std), of the variance {ev:.3e}; bars 1e-9")
+
+
+@merge_cases
+def test_merge_batches_one_call_equals_k_calls(K, N):
+    _check_one_call_equals_k_calls(_pkg(), K, N)
+
+
+@merge_cases
+def test_merge_batches_output_is_within_three_ulp_of_the_float64_expression(K, N):
+    worst = _check_output_of_case(_pkg(), N, K)
+    print(f"K={K} N={N}: largest distance from the float64 expression {worst} float32 ulp (bar 3)")
+
+
+# ---- 10. the collector -------------------------------------------------------------------------------------------------------------------
 def _env(pkg, n):
     from drl_dronenavigation_amd import tracks
     return pkg.DroneVecEnv(tracks.circle(1, 4, 1), n, max_steps=3, seed=17, device=DEV, normalize_obs=True, **NOISE)
