@@ -4,12 +4,14 @@
 // validates its arguments, turns HIP failures into dn_status codes + a thread-local message, and
 // never falls back to a CPU implementation.
 #include "dn_internal.h"
+#include "dn_shapes.h"
 
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -36,15 +38,6 @@ int32_t fail(dn_status st, const char *fmt, ...)
 
 inline double norm3d(const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 
-// Shape crossovers, measured on the 256-CU MI355X and kept as TILES PER CU (a 64-drone tile is one workgroup): what decides a
-// shape is how many waves meet on a SIMD, so a partitioned (CPX) or smaller device scales the fleet sizes with its own
-// hipDeviceProp_t.multiProcessorCount (dn_create) instead of inheriting the 256-CU figures.
-constexpr long long DN_CALIBRATION_CUS = 256;
-constexpr long long DN_TWO_WAVE_TILES_PER_CU = 4;   // 1024 tiles = 65536 drones on 256 CUs: one tile per SIMD
-constexpr long long DN_PQX_TILES_PER_CU = 4;        // three-wave single step: while the tiles alone leave SIMDs idle
-constexpr long long DN_FIVE_WAVE_TILES_PER_CU = 2;  // the same with the normaliser on a fifth wave: up to two tiles per CU (round 6: beyond, the four-wave kernel's X wave carries the normaliser -- 149 registers since its statistics are addressed from a walked pair -- and wins: dn_create)
-constexpr long long DN_ROLE_PIPE_TILES_PER_CU = 6;  // role-pipelined fused step (eight roles per tile): up to one tile per CU and from three to six, see dn_create
-constexpr long long DN_FOUR_WAVE_TILES_PER_CU = 3;  // four-wave fused step: up to three tiles per CU (768 tiles on 256 CUs)
 constexpr double DN_CONTACT_MARGIN = 0.02;          // Bullet's contact-breaking threshold (dn_kernels.hip collision_common)
 constexpr double DN_COLL_R = 0.06, DN_COLL_H = 0.025;   // base_link collision cylinder, cf2x.urdf:34
 
@@ -89,8 +82,7 @@ struct dn_env {
     float *tab32 = nullptr;
     long long blocks = 0;
     int num_cus = (int)DN_CALIBRATION_CUS;   // hipDeviceProp_t.multiProcessorCount of cfg.device_id
-    int waves_fused = 2;        // kernel shape of dn_step_many (k > 1), see dn_launch_step_many
-    int waves_single = 1;       // kernel shape of dn_step (k == 1)
+    DnShapes picked = {2, 1};   // dn_create's pick (dn_shapes.h); what a launch takes is kernel_shapes(env), which the models overrule
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // dn_set_launch_events: attached to the next step kernel's dispatch, then cleared
     // dn_enable_*: each model's arrays are one allocation of its own, outside the arena (dn_state_bytes is unchanged): 16 bytes per drone
     // for the dynamics, 32 for the wind, 152 for the actuator, 1092 for the sensor model.  MODELS below names the pointer that owns each.
@@ -357,6 +349,16 @@ int32_t refuse_models(dn_env *env, const char *who, const char *instead)
     return DN_OK;
 }
 
+// The kernel shapes a launch of this env takes: dn_create's pick, unless a model is on -- the models live in the one-wave option kernels
+// only (as the random spawn does).  On by the row's own predicate, not by dn_model_level: privileged or goal rows that are enabled but
+// unbound write nothing and still fly the one-wave kernels.
+DnShapes kernel_shapes(const dn_env *env)
+{
+    for (const ModelRow &r : MODELS)
+        if (r.on(env->m)) return {1, 1};
+    return env->picked;
+}
+
 // The DnStepIO of every step-family entry point, every field set.  Without a sampler (mean, act_out and logp_out null) the kernels read
 // `actions`; dn_mlp_step_sampled draws from the mean its policy kernel holds in registers, so it passes act_out / logp_out without `mean`.
 DnStepIO make_io(const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets, float *terminal_obs,
@@ -373,6 +375,48 @@ DnStepIO make_io(const float *actions, float *obs, float *reward, uint8_t *done,
     return io;
 }
 
+// dn_step_sampled and dn_step_squashed: one body.  The caller names what differs: the rows the sampler reads (`src`: the means, or the
+// mu | log_std rows, which carry log_std themselves and ask for the squashed action: make_io), whether every pointer ITS signature
+// requires is there, and the words of its refusals.
+struct SamplerWords { const char *who, *src, *required, *instead; };     // the entry point, its name for `src`, its required pointers as its message lists them, the calls that serve what it refuses
+int32_t sampler_step(dn_env *env, const SamplerWords &w, bool given, const float *src, const float *log_std, int squash, uint64_t seed,
+                     int32_t deterministic, float *actions_out, float *log_prob_out, float *obs, float *reward, uint8_t *done, uint8_t *truncated,
+                     int32_t *found_targets, float *terminal_obs, float *ep_return, int32_t *ep_length, uint64_t *done_mask, void *stream)
+{
+    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
+    const LaunchEvents armed(env);                         // dn_set_launch_events: this launch takes the hook as well
+    if (!given) return fail(DN_ERR_INVALID_ARGUMENT, "%s are required", w.required);
+    if (((uintptr_t)src & 15u) || ((uintptr_t)actions_out & 15u) || ((uintptr_t)obs & 15u))
+        return fail(DN_ERR_INVALID_ARGUMENT, "%s, actions_out and obs must be 16-byte aligned", w.src);
+    if (!dn_config_is_plain(env->cfg))
+        return fail(DN_ERR_INVALID_ARGUMENT, "%s is built for the configuration without reward wrappers / extra physics terms / RPM actions / random spawn / zero damping; "
+                                             "%s", w.who, w.instead);
+    if (const int32_t rc = refuse_models(env, w.who, w.instead)) return rc;
+    const DnStepIO io = make_io(nullptr, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask,
+                                src, actions_out, log_prob_out, log_std, seed, deterministic, squash);
+    // the sampling lives in the single-step kernels (one wave, or three waves cut by dependency)
+    DN_REFUSE_ARMED_CAPTURE(stream);
+    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, kernel_shapes(env).single == 3 ? 3 : 1, (hipStream_t)stream));
+    return DN_OK;
+}
+
+// dn_bind_privileged and dn_bind_goal: the binding of an enabled row writer.  rows = NULL unbinds both buffers.
+int32_t bind_rows(float *&rows_slot, float *&term_slot, long long &cap_slot, float *rows, float *terminal_rows, int64_t capacity_steps)
+{
+    if (!rows) {
+        if (terminal_rows) return fail(DN_ERR_INVALID_ARGUMENT, "terminal_rows without rows: rows = NULL unbinds both");
+        rows_slot = term_slot = nullptr;
+        cap_slot = 0;
+        return DN_OK;
+    }
+    if (((uintptr_t)rows & 15u) || ((uintptr_t)terminal_rows & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "rows and terminal_rows must be 16-byte aligned");
+    if (capacity_steps < 1) return fail(DN_ERR_INVALID_ARGUMENT, "capacity_steps must be >= 1 (got %lld)", (long long)capacity_steps);
+    rows_slot = rows;
+    term_slot = terminal_rows;
+    cap_slot = capacity_steps;
+    return DN_OK;
+}
+
 // The checks every dn_*_config shares.
 int32_t check_resample_reserved(int32_t resample, int32_t reserved)
 {
@@ -382,10 +426,9 @@ int32_t check_resample_reserved(int32_t resample, int32_t reserved)
 }
 
 // The tail of every dn_enable_* once its configuration is valid: on the first call, the model's allocation (`bytes`, handed to
-// init(float4 *) to fill on the null stream, freed again if that fails); on every call, the kernel shape -- the models live in the
-// one-wave option kernels only (as the random spawn does).  `what` names the allocation in messages.
+// init(float4 *) to fill on the null stream, freed again if that fails).  `what` names the allocation in messages.
 template <typename Init>
-int32_t model_storage(dn_env *env, float4 *&slot, size_t bytes, const char *what, Init init)
+int32_t model_storage(float4 *&slot, size_t bytes, const char *what, Init init)
 {
     if (!slot) {
         float4 *d = nullptr;
@@ -397,7 +440,6 @@ int32_t model_storage(dn_env *env, float4 *&slot, size_t bytes, const char *what
         }
         slot = d;
     }
-    env->waves_fused = env->waves_single = 1;
     return DN_OK;
 }
 
@@ -468,7 +510,10 @@ int32_t dn_create(const dn_config *cfg, dn_env **out)
         return fail(DN_ERR_INVALID_ARGUMENT, "device_id %d out of range (%d devices)", cfg->device_id, ndev);
     DN_HIP(hipSetDevice(cfg->device_id));
 
-    dn_env *e = new (std::nothrow) dn_env();
+    // the half-built env: freed, arena included, on every early return below; released into *out at the end
+    struct Unbuild { void operator()(dn_env *h) const { if (h->arena) (void)hipFree(h->arena); delete h; } };
+    std::unique_ptr<dn_env, Unbuild> owner(new (std::nothrow) dn_env());
+    dn_env *e = owner.get();
     if (!e) return fail(DN_ERR_OUT_OF_MEMORY, "host allocation failed");
     e->cfg = *cfg;
     e->ground_contact_auto = e->cfg.ground_contact == DN_GROUND_CONTACT_AUTO;
@@ -480,100 +525,12 @@ int32_t dn_create(const dn_config *cfg, dn_env **out)
     }
     const long long n = cfg->num_envs;
     e->blocks = (n + DN_BLOCK - 1) / DN_BLOCK;
-    const long long DN_TWO_WAVE_MAX_TILES = DN_TWO_WAVE_TILES_PER_CU * e->num_cus;
-    const long long DN_PQX_MAX_TILES = DN_PQX_TILES_PER_CU * e->num_cus;
-    const long long DN_FOUR_WAVE_MAX_TILES = DN_FOUR_WAVE_TILES_PER_CU * e->num_cus;
-    // Measured on MI355X (profiles/r01_r_sweep_shapes.txt): the fused K-step kernel is bound by the dependent
-    // instruction stream of a wave, and two or three waves per tile win while the tiles alone leave SIMDs idle
-    // (<= 1024 tiles = 65536 drones on 1024 SIMDs); the single-step launch is latency bound (launch + load round
-    // trip) and one wave is never slower.  DN_WAVES=1|2|3 forces a shape (A/B measurements, the bit-identity test).
-    // The three-wave shape (flight / report / aux) exists for fused launches.  Measured (profiles/r01_r_sweep_shapes.txt,
-    // profiles/r01_r_sweep_options.txt, with the report wave yielding to the other two by s_setprio): without the
-    // normaliser it wins wherever more than one wave per tile wins, i.e. up to 1024 tiles (65536 drones: 2.3 us per step
-    // against 2.5 with two waves and 2.9 with one); with the normaliser (27 more float64 per drone in a wave) up to 512
-    // tiles (32768 drones: 1.8 us against 2.1 with two waves), one wave beyond (49152 drones: 3.3 us against 3.5).
-    // The option kernels are wider in registers (the three-wave kernels are compiled for three waves per SIMD, two with
-    // the normaliser: __launch_bounds__), so their crossovers sit lower (profiles/r01_r_sweep_options.txt, us per step):
-    //   XOPT options (reward wrappers, force terms, rpm actions), all on: 32768 drones 2.15 (3w) / 2.97 (2w) / 3.70 (1w);
-    //     49152: 2.43 / 2.99 / 3.66; 65536: 4.48 / 3.14 / 3.72  -> three waves up to 768 tiles, two up to 1024;
-    //     with the normaliser 32768: 2.43 / 2.80 / 4.50; 65536: 4.74 / 5.42 / 4.56 -> three up to 512 tiles, one beyond;
-    //   noise (Philox + Box-Muller per observation column): 16384 drones 3.51 / 4.63 / 5.86; 32768: 4.86 / 4.78 / 6.02;
-    //     49152: 5.36 / 4.88 / 6.04 -> three waves up to 256 tiles, two beyond (same with the normaliser, up to 512);
-    //     noise + XOPT without the normaliser follows the XOPT row (49152: 5.75 / 6.23 / 6.99).
-    const bool plain = !cfg->clip_rew && !cfg->norm_rew && cfg->physics == 0 && cfg->action_type == 0 && !cfg->random_spawn && !cfg->zero_damping;
-    const bool noisy = cfg->act_noise_sigma > 0.0f || cfg->obs_noise_sigma > 0.0f;
-    const long long max_multi = cfg->normalize_obs ? DN_TWO_WAVE_MAX_TILES / 2 : DN_TWO_WAVE_MAX_TILES;
-    long long max_three = max_multi;
-    if (!plain && !cfg->normalize_obs) max_three = DN_TWO_WAVE_MAX_TILES * 3 / 4;
-    else if (noisy) max_three = DN_TWO_WAVE_MAX_TILES / 4;
-    e->waves_fused = e->blocks <= max_multi ? (e->blocks <= max_three ? 3 : 2) : 1;
-    // Four waves (dn_step_many_4w_kernel: the recurrence itself on two waves; plain configuration without the ground-contact term,
-    // us per step against the three- / two- / one-wave pick of the table above):
-    //   normaliser off   8 192 / 16 384 / 24 576 / 32 768 / 49 152 drones   1.01 / 1.02 / 1.23 / 1.23 / 1.66   against 1.28 / 1.29 / 1.29 / 1.28 / 1.71
-    //                    65 536: 2.58 against 1.92 -> up to 768 tiles
-    //   normaliser on    8 192 / 16 384 / 24 576 / 32 768 / 49 152           1.37 / 1.39 / 1.73 / 1.76 / 3.27   against 1.48 / 1.50 / 1.87 / 1.89 / 3.36 -> up to 768 tiles
-    //   with noise       16 384 / 32 768 / 49 152                            2.99 / 4.47 / 4.84   against 3.75 / 4.85 / 4.84 (normaliser on: 3.43 / 3.75 / 7.44 against
-    //                    3.62 / 5.73 / 6.98) -> up to 512 tiles
-    if (plain && !cfg->ground_contact && e->blocks <= (noisy ? DN_FOUR_WAVE_MAX_TILES * 2 / 3 : DN_FOUR_WAVE_MAX_TILES)) e->waves_fused = 4;
-    // Five waves (normaliser on; round 3): the four-wave kernel with the normaliser on a wave of its own (NW = 5), where the report wave set
-    // the pace.  DN_WAVES=4 keeps the four-wave shape for A/B runs; see profiles/r03_notes.md.
-    if (e->waves_fused == 4 && cfg->normalize_obs && e->blocks <= DN_FIVE_WAVE_TILES_PER_CU * e->num_cus) e->waves_fused = 5;
-    // Role-pipelined kernel (round 4, dn_step_many_rp8_kernel: eight roles per tile; plain configuration with the normaliser, no noise).
-    // Fleet sweep, 64-step launches, us per step (five waves | eight roles; profiles/r04_sweep_rp.txt): 4 096 drones 1.08 | 0.93, 8 192
-    // 1.11 | 0.99, 16 384 1.18 | 1.05, 20 480 1.52 | 1.53, 24 576 1.53 | 1.57, 32 768 1.63 | 1.66, 40 960 2.79 | 2.37, 49 152 2.98 | 2.47
-    // -> eight roles up to one tile per CU and from two to three tiles per CU (where two of its workgroups fit a CU and the third tile
-    // follows), five waves in between, where sixteen waves saturate the vector ALUs either way.  Without the normaliser the six-role form
-    // lost to the four-wave kernel at every size (32 768 drones: 1.68 against 1.40) and was removed in round 5.
-    // Round 6, beyond three tiles per CU (one wave | eight roles, 64-step launches, the one-wave kernel 27 % faster than it was:
-    // profiles/r06_sweep_large.txt): 57 344 drones 3.41 | 2.53, 65 536 3.53 | 2.70, 81 920 4.56 | 3.37, 98 304 4.67 | 3.93, 114 688
-    // 4.76 | 4.58 (K = 20: 5.07 | 5.22), 131 072 4.86 | 5.16 -> eight roles up to six tiles per CU, one wave beyond.
-    const bool rp_ok = plain && !cfg->ground_contact && !noisy;
-    // ... and from two to three tiles per CU the four-wave kernel WITH the normaliser on its X wave, once its statistics are addressed from a walked
-    // scalar pair (195 -> 149 registers: three tiles = twelve waves per CU resident; four waves | five | eight roles, profiles/r06_sweep_4wnorm.txt):
-    // 34 816 drones 1.80 | 2.06 | 1.93, 40 960 1.83 | 2.13 | 1.96, 49 152 1.95 | 2.23 | 2.06, 53 248 2.66 | 3.14 | 2.44 -> four waves in (2, 3] tiles per CU.
-    if (rp_ok && cfg->normalize_obs && (e->blocks <= e->num_cus || (e->blocks > 3 * e->num_cus && e->blocks <= DN_ROLE_PIPE_TILES_PER_CU * e->num_cus)))
-        e->waves_fused = 8;
-    // dn_step (one control step per launch) is latency bound: 1.65 us of kernel boundary that an empty kernel already pays
-    // (profiles/r03_dispatch_floor.txt; the 2.9 us of round 2 was the host's eager launch cadence), a ~1.2 us memory round trip
-    // with nothing to overlap it, plus the dependent instruction stream of the step.  Cutting the step
-    // by dependency over three waves (dn_step_pqx_kernel) shortens that stream while the chip has idle SIMDs; built for the
-    // plain configuration without the ground-contact term.  DN_WAVES_SINGLE=1|3 overrides the pick (sweeps).
-    // Measured (profiles/r02_sweep_single.txt, us per step, one wave / three waves): 32768 drones 6.4 / 4.7, 65536: 7.7 / 6.8,
-    // 98304: 9.5 / 9.8; with the normaliser 32768: 8.7 / 6.8, 49152: 9.5 / 10.9 -> three waves up to 1024 tiles, 512 with the
-    // normaliser's statistics (27 float64 per drone through one wave's loads and stores).
-    const bool pqx_ok = plain && !cfg->ground_contact;
-    e->waves_single = (pqx_ok && e->blocks <= (cfg->normalize_obs ? DN_PQX_MAX_TILES / 2 : DN_PQX_MAX_TILES)) ? 3 : 1;
-    if (const char *w = getenv("DN_WAVES")) {
-        if (w[0] == '1') e->waves_fused = e->waves_single = 1;
-        else if (w[0] == '2') e->waves_fused = e->waves_single = 2;
-        else if (w[0] == '3') {
-            e->waves_fused = 3;
-            e->waves_single = pqx_ok ? 3 : 1;
-        } else if (w[0] == '4') {                              // the recurrence itself on two waves (dn_step_many_4w_kernel): plain configuration only
-            e->waves_fused = pqx_ok ? 4 : 3;
-            e->waves_single = pqx_ok ? 3 : 1;
-        } else if (w[0] == '5') {                              // + the normaliser on a fifth wave (normaliser on only)
-            e->waves_fused = pqx_ok ? (cfg->normalize_obs ? 5 : 4) : 3;
-            e->waves_single = pqx_ok ? 3 : 1;
-        } else if (w[0] == '8') {                              // the role-pipelined kernel (eight roles; normaliser on, no noise)
-            e->waves_fused = rp_ok && cfg->normalize_obs ? 8 : (pqx_ok ? (cfg->normalize_obs ? 5 : 4) : 3);
-            e->waves_single = pqx_ok ? 3 : 1;
-        }
-    }
-    if (const char *w = getenv("DN_WAVES_SINGLE")) {
-        if (w[0] == '1') e->waves_single = 1;
-        else if (w[0] == '3' && pqx_ok) e->waves_single = 3;
-    }
+    e->picked = dn_pick_shapes(*cfg, e->num_cus, getenv("DN_WAVES"), getenv("DN_WAVES_SINGLE"));
     const int drag = cfg->physics == 2 || cfg->physics == 4;
     const int pid_mode = (cfg->action_type == 2 || cfg->action_type == 3 || cfg->action_type == 5) ? cfg->action_type : 0;
-    if (pid_mode) e->waves_fused = e->waves_single = 1;      // the controller reads the step's entry state: one-wave kernels (dn_kernels.hip, PidCtx)
-    if (cfg->random_spawn) e->waves_fused = e->waves_single = 1;   // the spawn draw lives in the one-wave option kernels only
     const Layout L = make_layout(n, cfg->normalize_obs, cfg->norm_rew, drag, pid_mode);
-    hipError_t he = hipMalloc(&e->arena, L.total);
-    if (he != hipSuccess) {
-        delete e;
-        return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for %lld drones failed: %s", L.total, n, hipGetErrorString(he));
-    }
+    const hipError_t he = hipMalloc(&e->arena, L.total);
+    if (he != hipSuccess) return fail(DN_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) for %lld drones failed: %s", L.total, n, hipGetErrorString(he));
     e->arena_bytes = L.total;
     char *base = (char *)e->arena;
     DnParams &p = e->p;
@@ -610,15 +567,13 @@ int32_t dn_create(const dn_config *cfg, dn_env **out)
         // compile-time form (dn_kernels.hip, normalize_obs_cols) that lives in libdronenav_exact.so: here the request is only CHECKED against the build.
         // Both are readable back through dn_get_exact_flags; a value that is neither a yes nor a no fails the create.
         int v = env_switch("DN_EXACT_OBS_NOISE");
-        if (v < 0) { (void)hipFree(e->arena); delete e; return fail(DN_ERR_INVALID_ARGUMENT, "DN_EXACT_OBS_NOISE=%s: expected 1 | true | on | yes or 0 | false | off | no", getenv("DN_EXACT_OBS_NOISE")); }
+        if (v < 0) return fail(DN_ERR_INVALID_ARGUMENT, "DN_EXACT_OBS_NOISE=%s: expected 1 | true | on | yes or 0 | false | off | no", getenv("DN_EXACT_OBS_NOISE"));
         p.exact_obs_noise = v;
         v = env_switch("DN_EXACT_NORM");
-        if (v < 0) { (void)hipFree(e->arena); delete e; return fail(DN_ERR_INVALID_ARGUMENT, "DN_EXACT_NORM=%s: expected 1 | true | on | yes or 0 | false | off | no", getenv("DN_EXACT_NORM")); }
-        if (v == 1 && !dn_norm_exact_compiled_in()) {
-            (void)hipFree(e->arena); delete e;
+        if (v < 0) return fail(DN_ERR_INVALID_ARGUMENT, "DN_EXACT_NORM=%s: expected 1 | true | on | yes or 0 | false | off | no", getenv("DN_EXACT_NORM"));
+        if (v == 1 && !dn_norm_exact_compiled_in())
             return fail(DN_ERR_INVALID_ARGUMENT, "DN_EXACT_NORM=1 asks for the normaliser's float64 output stage, which is a build of its own: load "
                                                  "libdronenav_exact.so (the Python package does when the variable is set) instead of this library");
-        }
     }
     p.act_noise_sigma = cfg->act_noise_sigma; p.obs_noise_sigma = cfg->obs_noise_sigma;
     p.seed = cfg->seed; p.env_id_offset = cfg->env_id_offset;
@@ -629,34 +584,25 @@ int32_t dn_create(const dn_config *cfg, dn_env **out)
     std::vector<float> t32(DN_MAX_WAYPOINTS * DN_T_STRIDE, 0.0f);
     build_table(*cfg, t64.data());
     for (size_t j = 0; j < t64.size(); ++j) t32[j] = (float)t64[j];
-    int32_t st = DN_OK;
-    do {
-        if (hipMemcpy(e->tab64, t64.data(), t64.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(e->tab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            st = fail(DN_ERR_HIP, "uploading the waypoint table failed");
-            break;
+    if (hipMemcpy(e->tab64, t64.data(), t64.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->tab32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DN_ERR_HIP, "uploading the waypoint table failed");
+
+    rc = init_state(e, nullptr);
+    if (rc != DN_OK) return rc;
+    if (cfg->random_spawn) {                // make_env's env.reset(seed=...) (PBDroneSimulator.py:173) already draws a spawn point
+        float *scratch = nullptr;
+        if (hipMalloc(&scratch, (size_t)n * DN_OBS_DIM * sizeof(float)) != hipSuccess) return fail(DN_ERR_OUT_OF_MEMORY, "scratch observation buffer");
+        const bool launched = dn_launch_reset(e->p, scratch, cfg->compute_f32 != 0, nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
+        (void)hipFree(scratch);
+        if (!launched) return fail(DN_ERR_HIP, "initial random spawn failed");
+        if (cfg->normalize_obs) {           // that reset happens BEFORE the NormalizeObservation wrapper exists: statistics stay pristine
+            rc = init_state_rms(e, nullptr);
+            if (rc != DN_OK) return rc;
         }
-        st = init_state(e, nullptr);
-        if (st != DN_OK) break;
-        if (cfg->random_spawn) {                // make_env's env.reset(seed=...) (PBDroneSimulator.py:173) already draws a spawn point
-            float *scratch = nullptr;
-            if (hipMalloc(&scratch, (size_t)n * DN_OBS_DIM * sizeof(float)) != hipSuccess) { st = fail(DN_ERR_OUT_OF_MEMORY, "scratch observation buffer"); break; }
-            const bool launched = dn_launch_reset(e->p, scratch, cfg->compute_f32 != 0, nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
-            (void)hipFree(scratch);
-            if (!launched) { st = fail(DN_ERR_HIP, "initial random spawn failed"); break; }
-            if (cfg->normalize_obs) {           // that reset happens BEFORE the NormalizeObservation wrapper exists: statistics stay pristine
-                st = init_state_rms(e, nullptr);
-                if (st != DN_OK) break;
-            }
-        }
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { st = fail(DN_ERR_HIP, "state initialisation failed"); break; }
-    } while (0);
-    if (st != DN_OK) {
-        (void)hipFree(e->arena);
-        delete e;
-        return st;
     }
-    *out = e;
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(DN_ERR_HIP, "state initialisation failed");
+    *out = owner.release();
     return DN_OK;
 }
 
@@ -725,7 +671,7 @@ int32_t dn_step(dn_env *env, const float *actions, float *obs, float *reward, ui
         return fail(DN_ERR_INVALID_ARGUMENT, "actions and obs must be 16-byte aligned");
     DN_REFUSE_ARMED_CAPTURE(stream);
     const DnStepIO io = make_io(actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask);
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single, (hipStream_t)stream, &env->m));
+    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, kernel_shapes(env).single, (hipStream_t)stream, &env->m));
     return DN_OK;
 }
 
@@ -734,43 +680,22 @@ int32_t dn_step_sampled(dn_env *env, const float *mean, const float *log_std, ui
                         int32_t *found_targets, float *terminal_obs, float *ep_return, int32_t *ep_length,
                         uint64_t *done_mask, void *stream)
 {
-    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
-    const LaunchEvents armed(env);                         // dn_set_launch_events: this launch takes the hook as well
-    if (!mean || !log_std || !actions_out || !log_prob_out || !obs || !reward || !done || !truncated || !found_targets)
-        return fail(DN_ERR_INVALID_ARGUMENT, "mean, log_std, actions_out, log_prob_out, obs, reward, done, truncated and found_targets are required");
-    if (((uintptr_t)mean & 15u) || ((uintptr_t)actions_out & 15u) || ((uintptr_t)obs & 15u))
-        return fail(DN_ERR_INVALID_ARGUMENT, "mean, actions_out and obs must be 16-byte aligned");
-    if (env->cfg.clip_rew || env->cfg.norm_rew || env->cfg.physics != 0 || env->cfg.action_type != 0 || env->cfg.random_spawn || env->cfg.zero_damping)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_sampled is built for the configuration without reward wrappers / extra physics terms / RPM actions / random spawn / zero damping; "
-                                             "use dn_policy_sample + dn_step there");
-    if (const int32_t rc = refuse_models(env, "dn_step_sampled", "use dn_policy_sample + dn_step there")) return rc;
-    const DnStepIO io = make_io(nullptr, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask,
-                                mean, actions_out, log_prob_out, log_std, seed, deterministic, 0);
-    // the sampling lives in the single-step kernels (one wave, or three waves cut by dependency)
-    DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single == 3 ? 3 : 1, (hipStream_t)stream));
-    return DN_OK;
+    const SamplerWords w = {"dn_step_sampled", "mean", "mean, log_std, actions_out, log_prob_out, obs, reward, done, truncated and found_targets",
+                            "use dn_policy_sample + dn_step there"};
+    const bool given = mean && log_std && actions_out && log_prob_out && obs && reward && done && truncated && found_targets;
+    return sampler_step(env, w, given, mean, log_std, 0, seed, deterministic, actions_out, log_prob_out, obs, reward, done, truncated, found_targets,
+                        terminal_obs, ep_return, ep_length, done_mask, stream);
 }
 
 int32_t dn_step_squashed(dn_env *env, const float *mu_log_std, uint64_t seed, int32_t deterministic, float *actions_out,
                          float *log_prob_out, float *obs, float *reward, uint8_t *done, uint8_t *truncated, int32_t *found_targets,
                          float *terminal_obs, float *ep_return, int32_t *ep_length, uint64_t *done_mask, void *stream)
 {
-    if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
-    const LaunchEvents armed(env);                         // dn_set_launch_events: this launch takes the hook as well
-    if (!mu_log_std || !actions_out || !obs || !reward || !done || !truncated || !found_targets)
-        return fail(DN_ERR_INVALID_ARGUMENT, "mu_log_std, actions_out, obs, reward, done, truncated and found_targets are required");
-    if (((uintptr_t)mu_log_std & 15u) || ((uintptr_t)actions_out & 15u) || ((uintptr_t)obs & 15u))
-        return fail(DN_ERR_INVALID_ARGUMENT, "mu_log_std, actions_out and obs must be 16-byte aligned");
-    if (env->cfg.clip_rew || env->cfg.norm_rew || env->cfg.physics != 0 || env->cfg.action_type != 0 || env->cfg.random_spawn || env->cfg.zero_damping)
-        return fail(DN_ERR_INVALID_ARGUMENT, "dn_step_squashed is built for the configuration without reward wrappers / extra physics terms / RPM actions / random spawn / zero damping; "
-                                             "use dn_squashed_sample + dn_step there");
-    if (const int32_t rc = refuse_models(env, "dn_step_squashed", "use dn_squashed_sample + dn_step there")) return rc;
-    const DnStepIO io = make_io(nullptr, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask,
-                                mu_log_std, actions_out, log_prob_out, nullptr, seed, deterministic, 1);     // the rows carry log_std
-    DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, 1, env->cfg.compute_f32 != 0, env->waves_single == 3 ? 3 : 1, (hipStream_t)stream));
-    return DN_OK;
+    const SamplerWords w = {"dn_step_squashed", "mu_log_std", "mu_log_std, actions_out, obs, reward, done, truncated and found_targets",
+                            "use dn_squashed_sample + dn_step there"};
+    const bool given = mu_log_std && actions_out && obs && reward && done && truncated && found_targets;
+    return sampler_step(env, w, given, mu_log_std, nullptr, 1, seed, deterministic, actions_out, log_prob_out, obs, reward, done, truncated,
+                        found_targets, terminal_obs, ep_return, ep_length, done_mask, stream);      // the rows carry log_std
 }
 
 int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_nets, const float *policy_obs, int32_t obs_dim,
@@ -813,8 +738,7 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
     }
     // the tail is the three-wave single step: the plain configuration dn_step_sampled covers, without noise and without the
     // ground-contact term, on fleets for which dn_create picked that shape; whole workgroups of the policy kernel only
-    if (c.clip_rew || c.norm_rew || c.physics != 0 || c.action_type != 0 || c.random_spawn || c.zero_damping || c.ground_contact ||
-        c.act_noise_sigma > 0.0f || c.obs_noise_sigma > 0.0f || c.compute_f32 || env->waves_single != 3)
+    if (!dn_config_is_plain(c) || c.ground_contact || dn_config_is_noisy(c) || c.compute_f32 || kernel_shapes(env).single != 3)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_mlp_step_sampled is built for the float64 reference configuration without noise / reward wrappers / extra "
                                              "physics / ground contact on fleets that take the three-wave single step; use dn_mlp_forward + dn_step_sampled");
     const long long per_wg = nets[0].grade == 1 ? 64 : 128;
@@ -837,6 +761,7 @@ int32_t dn_eval_kinematics(dn_env *env, const double *kinematics, float *obs, fl
     if (((uintptr_t)kinematics & 7u) || ((uintptr_t)obs & 15u))
         return fail(DN_ERR_INVALID_ARGUMENT, "kinematics must be 8-byte and obs 16-byte aligned");
     const dn_config &c = env->cfg;
+    // deliberately not dn_config_is_plain: a replayed transition never meets zero_damping, and noise is refused here as well
     if (c.act_noise_sigma > 0.0f || c.obs_noise_sigma > 0.0f || c.clip_rew || c.norm_rew || c.physics != 0 || c.action_type != 0 || c.random_spawn)
         return fail(DN_ERR_INVALID_ARGUMENT, "dn_eval_kinematics is built for the reference configuration (no noise, no reward wrappers, "
                                              "Physics.PYB, ActionType.THRUST, fixed spawn)");
@@ -872,7 +797,7 @@ int32_t dn_step_many(dn_env *env, int64_t k, const float *actions, float *obs, f
     // one fused launch: the state stays in registers for all k steps (dn_step_many_kernel)
     const DnStepIO io = make_io(actions, obs, reward, done, truncated, found_targets, terminal_obs, ep_return, ep_length, done_mask);
     DN_REFUSE_ARMED_CAPTURE(stream);
-    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, env->waves_fused, (hipStream_t)stream, &env->m));
+    DN_HIP(dn_launch_step_many(env->p, io, (int)k, env->cfg.compute_f32 != 0, kernel_shapes(env).fused, (hipStream_t)stream, &env->m));
     return DN_OK;
 }
 
@@ -1102,7 +1027,11 @@ int32_t dn_reset_stats(dn_env *env, void *stream)
     return DN_OK;
 }
 
-int32_t dn_get_kernel_waves(const dn_env *env, int32_t fused) { return env ? (fused ? env->waves_fused : env->waves_single) : 0; }
+int32_t dn_get_kernel_waves(const dn_env *env, int32_t fused)
+{
+    if (!env) return 0;
+    return fused ? kernel_shapes(env).fused : kernel_shapes(env).single;
+}
 
 int32_t dn_enable_dynamics(dn_env *env, const dn_dynamics_config *cfg)
 {
@@ -1119,7 +1048,7 @@ int32_t dn_enable_dynamics(dn_env *env, const dn_dynamics_config *cfg)
     const long long n = env->cfg.num_envs;
     DnDyn &d = env->m.dyn;
     // first call: the per-drone scales, all 1 (the nominal body) until a reset draws or dn_set_dynamics writes
-    if (const int32_t rc = model_storage(env, d.dyn, (size_t)n * sizeof(float4), "the dynamics scales", [&](float4 *mem) {
+    if (const int32_t rc = model_storage(d.dyn, (size_t)n * sizeof(float4), "the dynamics scales", [&](float4 *mem) {
             return dn_launch_fill4(mem, make_float4(1.0f, 1.0f, 1.0f, 1.0f), n, nullptr) == hipSuccess;
         }))
         return rc;
@@ -1171,7 +1100,7 @@ int32_t dn_enable_wind(dn_env *env, const dn_wind_config *cfg)
     const long long n = env->cfg.num_envs;
     DnWind &w = env->m.wind;
     // first call: wbar and g of every drone, 0 (still air) until an episode start draws or dn_set_wind writes
-    if (const int32_t rc = model_storage(env, w.mean, (size_t)(2 * n) * sizeof(float4), "the wind", [&](float4 *mem) {
+    if (const int32_t rc = model_storage(w.mean, (size_t)(2 * n) * sizeof(float4), "the wind", [&](float4 *mem) {
             return dn_launch_fill4(mem, make_float4(0.0f, 0.0f, 0.0f, 0.0f), 2 * n, nullptr) == hipSuccess;
         }))
         return rc;
@@ -1244,7 +1173,7 @@ int32_t dn_enable_actuator(dn_env *env, const dn_actuator_config *cfg)
     const long long n = env->cfg.num_envs;
     DnAct &a = env->m.act;
     // first call: d = 0, a = 0, r = rpm_fill, the history holds `fill`
-    if (const int32_t rc = model_storage(env, a.hist, (size_t)n * (9 * sizeof(float4) + sizeof(float) + sizeof(int)), "the actuator", [&](float4 *mem) {
+    if (const int32_t rc = model_storage(a.hist, (size_t)n * (9 * sizeof(float4) + sizeof(float) + sizeof(int)), "the actuator", [&](float4 *mem) {
             return dn_launch_fill4(mem, fill, 8 * n, nullptr) == hipSuccess && dn_launch_fill4(mem + 8 * n, rpm_fill, n, nullptr) == hipSuccess
                    && hipMemsetAsync(mem + 9 * n, 0, (size_t)n * (sizeof(float) + sizeof(int)), nullptr) == hipSuccess;
         }))
@@ -1312,7 +1241,7 @@ int32_t dn_enable_sensor(dn_env *env, const dn_sensor_config *cfg)
     if (s.ring) DN_HIP(hipDeviceSynchronize());     // launches in flight carry the previous configuration
     else s.base = 0;
     // first call: d = 0, b = 0, an all-zero ring
-    if (const int32_t rc = model_storage(env, s.ring, bytes, "the sensor model", [&](float4 *mem) { return hipMemsetAsync(mem, 0, bytes, nullptr) == hipSuccess; }))
+    if (const int32_t rc = model_storage(s.ring, bytes, "the sensor model", [&](float4 *mem) { return hipMemsetAsync(mem, 0, bytes, nullptr) == hipSuccess; }))
         return rc;
     s.bias = s.ring + (size_t)n * DN_SENS_SLOTS * 4;
     s.lat = reinterpret_cast<int *>(s.ring + quads);
@@ -1369,7 +1298,6 @@ int32_t dn_enable_privileged(dn_env *env, const dn_privileged_config *cfg)
     }
     env->m.priv.groups = cfg->groups;
     env->priv_cfg = *cfg;
-    env->waves_fused = env->waves_single = 1;       // the rows are written by the one-wave option kernels only
     return DN_OK;
 }
 
@@ -1386,18 +1314,7 @@ int32_t dn_bind_privileged(dn_env *env, float *rows, float *terminal_rows, int64
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
     DnPriv &pv = env->m.priv;
     if (!pv.groups) return fail(DN_ERR_BAD_STATE, "the privileged observations are not enabled (dn_enable_privileged)");
-    if (!rows) {
-        if (terminal_rows) return fail(DN_ERR_INVALID_ARGUMENT, "terminal_rows without rows: rows = NULL unbinds both");
-        pv.rows = pv.term = nullptr;
-        pv.cap = 0;
-        return DN_OK;
-    }
-    if (((uintptr_t)rows & 15u) || ((uintptr_t)terminal_rows & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "rows and terminal_rows must be 16-byte aligned");
-    if (capacity_steps < 1) return fail(DN_ERR_INVALID_ARGUMENT, "capacity_steps must be >= 1 (got %lld)", (long long)capacity_steps);
-    pv.rows = rows;
-    pv.term = terminal_rows;
-    pv.cap = capacity_steps;
-    return DN_OK;
+    return bind_rows(pv.rows, pv.term, pv.cap, rows, terminal_rows, capacity_steps);
 }
 
 int32_t dn_enable_goal(dn_env *env, const dn_goal_config *cfg)
@@ -1415,7 +1332,6 @@ int32_t dn_enable_goal(dn_env *env, const dn_goal_config *cfg)
     env->m.goal.on = 1;
     env->m.goal.frame = cfg->frame;
     env->goal_cfg = *cfg;
-    env->waves_fused = env->waves_single = 1;       // the rows are written by the one-wave option kernels only
     return DN_OK;
 }
 
@@ -1432,18 +1348,7 @@ int32_t dn_bind_goal(dn_env *env, float *rows, float *terminal_rows, int64_t cap
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is required");
     DnGoal &g = env->m.goal;
     if (!g.on) return fail(DN_ERR_BAD_STATE, "the goal observations are not enabled (dn_enable_goal)");
-    if (!rows) {
-        if (terminal_rows) return fail(DN_ERR_INVALID_ARGUMENT, "terminal_rows without rows: rows = NULL unbinds both");
-        g.rows = g.term = nullptr;
-        g.cap = 0;
-        return DN_OK;
-    }
-    if (((uintptr_t)rows & 15u) || ((uintptr_t)terminal_rows & 15u)) return fail(DN_ERR_INVALID_ARGUMENT, "rows and terminal_rows must be 16-byte aligned");
-    if (capacity_steps < 1) return fail(DN_ERR_INVALID_ARGUMENT, "capacity_steps must be >= 1 (got %lld)", (long long)capacity_steps);
-    g.rows = rows;
-    g.term = terminal_rows;
-    g.cap = capacity_steps;
-    return DN_OK;
+    return bind_rows(g.rows, g.term, g.cap, rows, terminal_rows, capacity_steps);
 }
 
 // ---- track bank ----
@@ -1493,7 +1398,7 @@ int32_t dn_enable_tracks(dn_env *env, const dn_track_bank_config *cfg)
     const bool first = tk.track == nullptr;
     float4 *mem = reinterpret_cast<float4 *>(tk.track);
     // first call: every drone on track 0, no episode finished yet, zero counters
-    if (const int32_t rc = model_storage(env, mem, bytes, "the track bank", [&](float4 *d) {
+    if (const int32_t rc = model_storage(mem, bytes, "the track bank", [&](float4 *d) {
             char *b = reinterpret_cast<char *>(d);
             return hipMemsetAsync(b, 0, bytes, nullptr) == hipSuccess &&
                    hipMemsetAsync(b + (size_t)n * sizeof(int), 0xFF, (size_t)n * sizeof(int), nullptr) == hipSuccess;
