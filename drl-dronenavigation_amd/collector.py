@@ -102,36 +102,34 @@ class RolloutGather:
         return self.recv[:, 0].permute(1, 0, 2), self.recv[:, 1].permute(1, 0, 2)      # [T, R, n] views, no copy
 
 
-def _refuse_privileged(env, who):
-    """The fused collectors evaluate actor and critic in one launch over one input, the 13-column observation their step path hands on:
-    they cannot feed a critic the 52-wide rows."""
-    if getattr(env, "privileged", None) is not None:
-        raise ValueError(f"{who} does not carry privileged observations (its step path shows actor and critic the same 13-column observation); "
-                         "use RolloutCollector(..., value_input='privileged') with value_fn=FusedMlpValue(MlpValue(52), ...) or a torch value_fn")
+# What the fused collectors do not carry: (env attribute, the rest of the message), refused in this order.  They evaluate actor and critic
+# in one launch over the 13-column observation their step path hands on, straight from the step kernel's own output: the privileged and
+# goal rows are written by other kernel families, which carry no sampling-fused entry point (a track bank rides in the goal family), and
+# the history rows are stacked by a kernel of their own, after the step.
+_EXTRA_ROWS = (
+    ("privileged", "privileged observations (its step path shows actor and critic the same 13-column observation); "
+                   "use RolloutCollector(..., value_input='privileged') with value_fn=FusedMlpValue(MlpValue(52), ...) or a torch value_fn"),
+    ("goal", "goal observations (its policy kernels read the 13-column observation); "
+             "use RolloutCollector(..., policy_input='observation+goal') with FusedMlpPolicy(MlpActorCritic(obs_dim=21), ...) "
+             "or a torch policy"),
+    ("track_ids", "a track bank (its sampling-fused step kernels fly the one track of the env); "
+                  "use RolloutCollector with a torch policy"),
+    ("history", "history rows (its policy kernels read the 13-column observation); "
+                "use RolloutCollector(..., policy_input='history') with FusedMlpPolicy(MlpActorCritic(obs_dim=W), ...) or a torch policy"))
 
 
-def _refuse_tracks(env, who):
-    """A track bank rides in the goal family of the step kernels, which carries no sampling-fused entry point."""
-    if getattr(env, "track_ids", None) is not None:
-        raise ValueError(f"{who} does not carry a track bank (its sampling-fused step kernels fly the one track of the env); "
-                         "use RolloutCollector with a torch policy")
+def _refuse_extra_rows(env, who):
+    for attr, what in _EXTRA_ROWS:
+        if getattr(env, attr, None) is not None:
+            raise ValueError(f"{who} does not carry {what}")
 
 
-def _refuse_goal(env, who):
-    """The fused collectors feed the policy kernels the 13 observation columns from the step kernel's own output; the goal rows are
-    written by another kernel family, which carries no sampling-fused entry point."""
-    if getattr(env, "goal", None) is not None:
-        raise ValueError(f"{who} does not carry goal observations (its policy kernels read the 13-column observation); "
-                         "use RolloutCollector(..., policy_input='observation+goal') with FusedMlpPolicy(MlpActorCritic(obs_dim=21), ...) "
-                         "or a torch policy")
-
-
-def _refuse_history(env, who):
-    """The fused collectors feed the policy kernels the 13 observation columns from the step kernel's own output; the history rows are
-    stacked by a kernel of their own, after the step."""
-    if getattr(env, "history", None) is not None:
-        raise ValueError(f"{who} does not carry history rows (its policy kernels read the 13-column observation); "
-                         "use RolloutCollector(..., policy_input='history') with FusedMlpPolicy(MlpActorCritic(obs_dim=W), ...) or a torch policy")
+def _sampling_fused_scope(env):
+    """Whether the sampling-fused step kernels (dn_step_sampled, dn_step_squashed) are built for this env: no reward wrappers, extra
+    physics terms, RPM / PID actions, random spawn or per-drone models.  Outside it a collector samples and steps in two launches."""
+    cfg = env.cfg
+    return not (cfg.clip_rew or cfg.norm_rew or cfg.physics or cfg.action_type or cfg.random_spawn or cfg.zero_damping
+                or env.dynamics is not None or env.wind is not None or env.actuator is not None or env.sensor is not None)
 
 
 class RolloutCollector:
@@ -241,24 +239,18 @@ class RolloutCollector:
             last_values=torch.empty(n, dtype=f32, device=dev), last_dones=torch.empty(n, dtype=torch.uint8, device=dev))
         self._clipped = torch.empty((n, ACT_DIM), dtype=f32, device=dev)
         self._last_obs = env.reset_tensor().clone()
-        if self.value_privileged:
-            self.buf["privileged"] = torch.empty((T, n, env.privileged.shape[1]), dtype=f32, device=dev)
-            self._last_priv = env.privileged.clone()
-        if self.policy_goal:
-            self.buf["goal"] = torch.empty((T, n, env.goal.shape[1]), dtype=f32, device=dev)
-            self._last_goal = env.goal.clone()
-        if self.policy_history:
-            self.buf["history"] = torch.empty((T, n, env.history.shape[1]), dtype=f32, device=dev)
-            self._last_hist = env.history.clone()
-        self.has_tracks = env.track_ids is not None
-        if self.has_tracks:         # the track each drone is on when obs[t] is observed
-            self.buf["track"] = torch.empty((T, n), dtype=torch.int32, device=dev)
-            self._last_track = env.track_ids.clone()
+        # the rows carried beside the observation, by the key they have in `info` and in the buffer dict: a static tensor each, which
+        # holds what goes with `_last_obs` (the track: the one each drone is on when obs[t] is observed)
+        self._last = {}
+        for wanted, key, rows in ((self.value_privileged, "privileged", env.privileged), (self.policy_goal, "goal", env.goal),
+                                  (self.policy_history, "history", env.history), (env.track_ids is not None, "track", env.track_ids)):
+            if wanted:
+                self.buf[key] = torch.empty((T,) + tuple(rows.shape), dtype=rows.dtype, device=dev)
+                self._last[key] = rows.clone()
         self._last_done = torch.ones(n, dtype=torch.uint8, device=dev)       # SB3: _last_episode_starts = True
         self.policy_norm, self.value_norm = policy_norm, value_norm
-        for name, norm, rows in (("policy_norm", policy_norm, self._seen(self._last_obs, getattr(self, "_last_goal", None),
-                                                                         getattr(self, "_last_hist", None))),
-                                 ("value_norm", value_norm, getattr(self, "_last_priv", None))):
+        for name, norm, rows in (("policy_norm", policy_norm, self._seen(self._last_obs, self._last)),
+                                 ("value_norm", value_norm, self._last.get("privileged"))):
             if norm is None:
                 continue
             if norm.width != rows.shape[1] or norm.device != dev:
@@ -275,11 +267,12 @@ class RolloutCollector:
         self._graph = None
         self._calls = 0
 
-    def _seen(self, o, g, h=None):
-        """The raw rows the policy (and the value function on observations) is shown."""
+    def _seen(self, o, rows, terminal=""):
+        """The raw rows the policy (and the value function on observations) is shown: `rows` maps the carried keys to the rows that go
+        with observation `o` -- the collector's own, or a step's `info`, whose terminal rows are the keys behind "terminal_"."""
         if self.policy_history:
-            return h
-        return torch.cat((o, g), dim=1) if self.policy_goal else o
+            return rows[terminal + "history"]
+        return torch.cat((o, rows[terminal + "goal"]), dim=1) if self.policy_goal else o
 
     def _values(self, obs, row_mask=None):
         if self.value_fn is not None:
@@ -292,27 +285,20 @@ class RolloutCollector:
         """One rollout on the current stream, in place in the static buffers (eager or under graph capture)."""
         from . import _capi
         import ctypes as C
-        env, b = self.env, self.buf
+        env, b, last = self.env, self.buf, self._last
         obs, done = self._last_obs, self._last_done
-        priv = self._last_priv if self.value_privileged else None
-        goal = self._last_goal if self.policy_goal else None
-        hist = self._last_hist if self.policy_history else None
+        priv = last.get("privileged")
         seen = self._seen
         # with a normaliser the policy / the critic read its static buffer, the normalised image of the current raw rows
         pn, vn = self.policy_norm, self.value_norm
 
         for t in range(self.n_steps):
-            actions, values, log_probs = self.policy(seen(obs, goal, hist) if pn is None else self._policy_rows)
+            actions, values, log_probs = self.policy(seen(obs, last) if pn is None else self._policy_rows)
             if pn is not None:
                 b["policy_rows"][t].copy_(self._policy_rows)
-            if goal is not None:
-                b["goal"][t].copy_(goal)
-            if hist is not None:
-                b["history"][t].copy_(hist)
-            if self.has_tracks:
-                b["track"][t].copy_(self._last_track)
+            for key, rows in last.items():
+                b[key][t].copy_(rows)
             if priv is not None:
-                b["privileged"][t].copy_(priv)
                 if vn is not None:
                     b["value_rows"][t].copy_(self._value_rows)
                 values = self._values(priv if vn is None else self._value_rows)
@@ -325,7 +311,7 @@ class RolloutCollector:
             next_obs, reward, next_done, info = env.step_tensor(self._clipped, want_terminal=self.bootstrap_truncated)
             # VecNormalize.step_wait: the next rows update the statistics and are normalised; the terminal rows below see the same statistics
             if pn is not None:
-                pn.update_normalize(seen(next_obs, info.get("goal"), info.get("history")), out=self._policy_rows)
+                pn.update_normalize(seen(next_obs, info), out=self._policy_rows)
             if vn is not None:
                 vn.update_normalize(info["privileged"], out=self._value_rows)
             if self.reward_norm is not None:    # before the bootstrap below: the critic's values are in the normalised scale already
@@ -337,26 +323,18 @@ class RolloutCollector:
                     rows = torch.where(next_done.bool()[:, None], info["terminal_privileged"], info["privileged"])
                     tv = self._values(rows if vn is None else vn.normalize(rows, out=rows), row_mask=info["truncated"])
                 else:
-                    rows = torch.where(next_done.bool()[:, None],
-                                       seen(info["terminal_obs"], info.get("terminal_goal"), info.get("terminal_history")),
-                                       seen(next_obs, info.get("goal"), info.get("history")))
+                    rows = torch.where(next_done.bool()[:, None], seen(info["terminal_obs"], info, "terminal_"), seen(next_obs, info))
                     tv = self._values(rows if pn is None else pn.normalize(rows, out=rows), row_mask=info["truncated"])
                 reward = reward + self.gamma * tv * info["truncated"].to(reward.dtype)
             b["rewards"][t].copy_(reward)
             obs.copy_(next_obs)
             done.copy_(next_done)
-            if priv is not None:
-                priv.copy_(info["privileged"])
-            if goal is not None:
-                goal.copy_(info["goal"])
-            if hist is not None:
-                hist.copy_(info["history"])
-            if self.has_tracks:
-                self._last_track.copy_(info["track"])
+            for key, rows in last.items():
+                rows.copy_(info[key])
         if priv is not None:
             b["last_values"].copy_(self._values(priv if vn is None else self._value_rows))
         else:
-            b["last_values"].copy_(self._values(seen(obs, goal, hist) if pn is None else self._policy_rows))
+            b["last_values"].copy_(self._values(seen(obs, last) if pn is None else self._policy_rows))
         b["last_dones"].copy_(done)
         dev = env.device
         _capi.check(_capi.load().dn_gae(
@@ -501,10 +479,7 @@ class OffPolicyCollector:
     def __init__(self, env, actor, buffer_size, *, seed=0, deterministic=False, fused_sample=True):
         from .policy_mfma import FusedSacActor
         from .vec_env import ACT_DIM, DroneVecEnv
-        _refuse_privileged(env, "OffPolicyCollector")
-        _refuse_goal(env, "OffPolicyCollector")
-        _refuse_tracks(env, "OffPolicyCollector")
-        _refuse_history(env, "OffPolicyCollector")
+        _refuse_extra_rows(env, "OffPolicyCollector")
         if not isinstance(env, DroneVecEnv):
             raise TypeError("OffPolicyCollector drives a DroneVecEnv (HIP); there is no CPU path")
         self.env, self.actor = env, actor
@@ -516,11 +491,7 @@ class OffPolicyCollector:
             self.buffer = RingReplayBuffer(buffer_size, env.num_envs, env.obs_dim, ACT_DIM, env.device)
             self.buffer.obs_ring[0].copy_(env.reset_tensor())
             self._found = torch.zeros(env.num_envs, dtype=torch.int32, device=env.device)
-            cfg = env.cfg
-            self._fused_sample = fused_sample and not (cfg.clip_rew or cfg.norm_rew or cfg.physics or cfg.action_type or cfg.random_spawn
-                                                       or cfg.zero_damping or env.dynamics is not None
-                                                       or env.wind is not None or env.actuator is not None
-                                                       or env.sensor is not None)       # dn_step_squashed's scope
+            self._fused_sample = fused_sample and _sampling_fused_scope(env)      # dn_step_squashed's scope
         else:
             self.buffer = ReplayBuffer(buffer_size, env.num_envs, env.obs_dim, ACT_DIM, env.device)
             self._obs = env.reset_tensor().clone()
@@ -620,10 +591,7 @@ class FusedRolloutCollector:
                  group=None, use_graph=True, seed=0, one_launch=False):
         from .policy_mfma import FusedMlpPolicy
         from .vec_env import ACT_DIM, OBS_DIM, DroneVecEnv
-        _refuse_privileged(env, "FusedRolloutCollector")
-        _refuse_goal(env, "FusedRolloutCollector")
-        _refuse_tracks(env, "FusedRolloutCollector")
-        _refuse_history(env, "FusedRolloutCollector")
+        _refuse_extra_rows(env, "FusedRolloutCollector")
         if not isinstance(env, DroneVecEnv) or not isinstance(policy, FusedMlpPolicy):
             raise TypeError("FusedRolloutCollector needs a DroneVecEnv and a FusedMlpPolicy (HIP); there is no CPU path")
         if env.num_envs % 4 or env.obs_dim != OBS_DIM:
@@ -651,10 +619,7 @@ class FusedRolloutCollector:
             self.buf["advantages"], self.buf["returns"] = torch.empty((T, n), dtype=f32, device=dev), torch.empty((T, n), dtype=f32, device=dev)
         self._mean = torch.empty((n, ACT_DIM), dtype=f32, device=dev)
         cfg = env.cfg
-        self._sampled_step = not (cfg.clip_rew or cfg.norm_rew or cfg.physics or cfg.action_type or cfg.random_spawn or cfg.zero_damping
-                                  or env.dynamics is not None or env.wind is not None
-                                  or env.actuator is not None
-                                  or env.sensor is not None)   # dn_step_sampled's scope (randomised dynamics, wind, actuator, sensor: sample + dn_step)
+        self._sampled_step = _sampling_fused_scope(env)       # dn_step_sampled's scope (outside it: sample + dn_step)
         self._clipped = None if self._sampled_step else torch.empty((n, ACT_DIM), dtype=f32, device=dev)
         # ONE launch per step (dn_mlp_step_sampled: the actor's workgroups step the drones they evaluated) where that kernel is built:
         # the float64 reference configuration without noise / ground contact, fleets on the three-wave single step, whole workgroups

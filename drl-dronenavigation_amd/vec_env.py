@@ -103,6 +103,21 @@ class _SparseInfo(dict):
         return (dict, (self.copy(),))
 
 
+class _RowFamily:
+    """One family of extra rows beside the observation.  `rows` [N, width] are the env's current ones (env.privileged, env.goal or
+    env.history; info[key]) and `terminal_rows` those of the single-step calls (info["terminal_" + key]).  `bind` is the C entry point
+    that points the step kernels at a pair of buffers -- None for the history rows, which a kernel of their own stacks after the
+    step -- and `slot` the env attribute that remembers the binding that stands (`_priv_bound`, `_goal_bound`).  `runs` are the (start, stop) runs of columns the kernels write, which is what
+    rollout_tensor copies back from the caller's buffers: None = the whole row."""
+    __slots__ = ("key", "width", "rows", "terminal_rows", "bind", "slot", "runs")
+
+    def __init__(self, key, width, bind, slot, runs, n, device):
+        self.key, self.width, self.bind, self.slot = key, width, bind, slot
+        self.runs = ((0, width),) if runs is None else runs
+        self.rows = torch.zeros((n, width), dtype=torch.float32, device=device)
+        self.terminal_rows = torch.zeros((n, width), dtype=torch.float32, device=device)
+
+
 # enums.Physics / enums.ActionType values of the reference (Sol/PyBullet/enums.py:12-21, :36-44) -> dn_config codes.
 # The reference only ever runs "pyb" + "thrust" (BaseAviary.py:411 pins the physics); the others are its dormant options.
 PHYSICS = {"pyb": 0, "pyb_gnd": 1, "pyb_drag": 2, "pyb_dw": 3, "pyb_gnd_drag_dw": 4}
@@ -192,20 +207,12 @@ class DroneVecEnv(_VecEnvBase):
             given = np.asarray(track.targets(target_factor) if target_points is None else target_points, dtype=np.float64).reshape(-1, 3)
             if not np.array_equal(given, first.waypoints):
                 raise ValueError("track / target_points must be absent or equal to track 0 of the bank")
-        if dynamics is not None and not isinstance(dynamics, DynamicsRandomization):
-            raise TypeError("dynamics must be a drl_dronenavigation_amd.DynamicsRandomization (or None)")
-        if wind is not None and not isinstance(wind, WindDisturbance):
-            raise TypeError("wind must be a drl_dronenavigation_amd.WindDisturbance (or None)")
-        if actuator is not None and not isinstance(actuator, ActuatorModel):
-            raise TypeError("actuator must be a drl_dronenavigation_amd.ActuatorModel (or None)")
-        if sensor is not None and not isinstance(sensor, SensorModel):
-            raise TypeError("sensor must be a drl_dronenavigation_amd.SensorModel (or None)")
-        if privileged is not None and not isinstance(privileged, PrivilegedObservation):
-            raise TypeError("privileged must be a drl_dronenavigation_amd.PrivilegedObservation (or None)")
-        if goal is not None and not isinstance(goal, GoalObservation):
-            raise TypeError("goal must be a drl_dronenavigation_amd.GoalObservation (or None)")
-        if history is not None and not isinstance(history, HistoryObservation):
-            raise TypeError("history must be a drl_dronenavigation_amd.HistoryObservation (or None)")
+        for keyword, value, cls in (("dynamics", dynamics, DynamicsRandomization), ("wind", wind, WindDisturbance),
+                                    ("actuator", actuator, ActuatorModel), ("sensor", sensor, SensorModel),
+                                    ("privileged", privileged, PrivilegedObservation), ("goal", goal, GoalObservation),
+                                    ("history", history, HistoryObservation)):
+            if value is not None and not isinstance(value, cls):
+                raise TypeError(f"{keyword} must be a drl_dronenavigation_amd.{cls.__name__} (or None)")
         if history is not None and history.goal and goal is None:
             raise ValueError("history=HistoryObservation(goal=True) needs an env built with goal=GoalObservation(...)")
         if track is not None:
@@ -252,12 +259,14 @@ class DroneVecEnv(_VecEnvBase):
         self.actuator = actuator
         self.sensor = sensor
         self.privileged_obs = privileged
-        self.privileged = None                 # the [N, 52] step rows (reset_tensor / step_tensor fill them), with privileged=... only
         self.goal_obs = goal
-        self.goal = None                       # the [N, 8] goal rows (reset_tensor / step_tensor fill them), with goal=... only
         # the history rows are stacked by a kernel of their own after the step (dn_stack_history): nothing to enable on the dn_env
         self.history_obs = history
-        self.history = None                    # the [N, W] history rows (reset_tensor / step_tensor update them in place), with history=... only
+        # the [N, 52] step rows, the [N, 8] goal rows and the [N, W] history rows (reset_tensor / step_tensor fill them, the history rows
+        # in place) and the terminal rows of the single-step calls: each with its keyword only
+        self.privileged = self.goal = self.history = None
+        self._term_priv = self._term_goal = self._term_hist = None
+        self._priv_bound = self._goal_bound = None
         # before the first reset: dn_reset draws the first episode's bodies, winds, actuators and sensors; the privileged rows come after
         # the four models they report
         self.track_bank = tracks
@@ -328,24 +337,21 @@ class DroneVecEnv(_VecEnvBase):
             self._packed_off = offs["_packed"]
             self._mirror_i = 0
             self._done_mask = torch.zeros((n + 63) // 64, dtype=torch.int64, device=dev)
-            self._priv_bound = None
+            # the row families that are on, in the fixed order privileged, goal, history: every method below that handles rows loops over
+            # this tuple, so a new kind of row is one more entry here (a privileged group that is not selected stays 0)
+            families = []
             if privileged is not None:
-                # the step rows and the terminal rows of the single-step calls; a group that is not selected stays 0
-                self.privileged = torch.zeros((n, PRIV_DIM), dtype=f32, device=dev)
-                self._term_priv = torch.zeros((n, PRIV_DIM), dtype=f32, device=dev)
-                self._bind_privileged(self.privileged, self._term_priv, 1)
-                self._priv_runs = privileged.column_runs()
-            self._goal_bound = None
+                families.append((_RowFamily("privileged", PRIV_DIM, self._lib.dn_bind_privileged, "_priv_bound", privileged.column_runs(), n, dev), "_term_priv"))
             if goal is not None:
-                # the step rows and the terminal rows of the single-step calls
-                self.goal = torch.zeros((n, GOAL_DIM), dtype=f32, device=dev)
-                self._term_goal = torch.zeros((n, GOAL_DIM), dtype=f32, device=dev)
-                self._bind_goal(self.goal, self._term_goal, 1)
+                families.append((_RowFamily("goal", GOAL_DIM, self._lib.dn_bind_goal, "_goal_bound", None, n, dev), "_term_goal"))
             if history is not None:
-                # the current rows and the terminal rows of the single-step calls
                 self._hist_cfg = history.to_c()
-                self.history = torch.zeros((n, history.width()), dtype=f32, device=dev)
-                self._term_hist = torch.zeros((n, history.width()), dtype=f32, device=dev)
+                families.append((_RowFamily("history", history.width(), None, None, None, n, dev), "_term_hist"))
+            self._families = tuple(f for f, _ in families)
+            for f, terminal_name in families:
+                setattr(self, f.key, f.rows)
+                setattr(self, terminal_name, f.terminal_rows)
+                self._bind(f, f.rows, f.terminal_rows, 1)
             if tracks is not None:
                 # each drone's current track and the track of its most recently ended episode (-1 before the first)
                 self.track_ids = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -400,23 +406,25 @@ class DroneVecEnv(_VecEnvBase):
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _bind_rows(self, bind, slot, rows, terminal_rows, capacity):
-        """dn_bind_privileged / dn_bind_goal, skipped when the binding already stands (host-side state only: no launch, no
-        synchronisation).  `slot` names the attribute that remembers the binding."""
+    def _bind(self, family, rows, terminal_rows, capacity):
+        """dn_bind_privileged / dn_bind_goal for a family the step kernels write, skipped when the binding already stands (host-side
+        state only: no launch, no synchronisation)."""
+        if family.bind is None:
+            return
         key = (rows.data_ptr(), terminal_rows.data_ptr() if terminal_rows is not None else None, int(capacity))
-        if key != getattr(self, slot):
-            _capi.check(bind(self._handle, key[0], key[1], key[2]))
-            setattr(self, slot, key)
+        if key != getattr(self, family.slot):
+            _capi.check(family.bind(self._handle, key[0], key[1], key[2]))
+            setattr(self, family.slot, key)
 
-    def _bind_privileged(self, rows, terminal_rows, capacity):
-        self._bind_rows(self._lib.dn_bind_privileged, "_priv_bound", rows, terminal_rows, capacity)
-
-    def _bind_goal(self, rows, terminal_rows, capacity):
-        self._bind_rows(self._lib.dn_bind_goal, "_goal_bound", rows, terminal_rows, capacity)
-
-    def _stack_history(self, k, prev, obs, actions, done, terminal_obs, extra, terminal_extra, rows, terminal_rows):
-        """One dn_stack_history launch on the current stream (tensors or None, step-major)."""
-        ptr = [None if x is None else x.data_ptr() for x in (prev, obs, actions, done, terminal_obs, extra, terminal_extra, rows, terminal_rows)]
+    def _stack_history(self, k, prev, obs, actions, done, terminal_obs, goal, terminal_goal, rows, terminal_rows):
+        """One dn_stack_history launch on the current stream (tensors or None, step-major).  Callers hand over what they have; which of it
+        the stack gets is decided here: terminal inputs only where there are terminal observations AND terminal rows to write, the goal
+        columns only where the rows end with them."""
+        if terminal_obs is None or terminal_rows is None:
+            terminal_obs = terminal_goal = terminal_rows = None
+        if not self.history_obs.goal:
+            goal = terminal_goal = None
+        ptr = [None if x is None else x.data_ptr() for x in (prev, obs, actions, done, terminal_obs, goal, terminal_goal, rows, terminal_rows)]
         rc = self._lib.dn_stack_history(C.byref(self._hist_cfg), k, self.num_envs, *ptr, self._dev_index, self._stream())
         if rc:
             _capi.check(rc)
@@ -426,15 +434,13 @@ class DroneVecEnv(_VecEnvBase):
         internal buffer that the next reset/step overwrites).  With privileged=..., `env.privileged` holds the fresh episodes' rows;
         with goal=..., `env.goal` does; with history=..., `env.history` holds the rows of a fresh stack (zero frames, the reset
         observation newest)."""
-        if self.privileged is not None:
-            self._bind_privileged(self.privileged, self._term_priv, 1)
-        if self.goal is not None:
-            self._bind_goal(self.goal, self._term_goal, 1)
+        for f in self._families:
+            self._bind(f, f.rows, f.terminal_rows, 1)
         with torch.cuda.device(self.device):
             _capi.check(self._lib.dn_reset(self._handle, self._obs.data_ptr(), self._stream()))
             self._fetch_tracks()
-            if self.history_obs is not None:
-                self._stack_history(1, None, self._obs, None, None, None, self.goal if self.history_obs.goal else None, None, self.history, None)
+            if self.history is not None:
+                self._stack_history(1, None, self._obs, None, None, None, self.goal, None, self.history, None)
         return self._views[0]
 
     def _fetch_tracks(self):
@@ -455,20 +461,15 @@ class DroneVecEnv(_VecEnvBase):
             raise ValueError(f"actions must be a float32 [{self.num_envs}, {ACT_DIM}] tensor on {self.device}")
         if not actions.is_contiguous():
             actions = actions.contiguous()
-        if self.privileged is not None:
-            self._bind_privileged(self.privileged, self._term_priv if want_terminal else None, 1)
-        if self.goal is not None:
-            self._bind_goal(self.goal, self._term_goal if want_terminal else None, 1)
+        for f in self._families:
+            self._bind(f, f.rows, f.terminal_rows if want_terminal else None, 1)
         self._launch(actions, want_terminal)
         v = self._views
         info = dict(truncated=self._trunc, found_targets=self._found, terminal_obs=v[1],
                     ep_return=self._ep_ret, ep_length=self._ep_len, done_mask=self._done_mask)
-        if self.privileged is not None:
-            info.update(privileged=self.privileged, terminal_privileged=self._term_priv if want_terminal else None)
-        if self.goal is not None:
-            info.update(goal=self.goal, terminal_goal=self._term_goal if want_terminal else None)
-        if self.history_obs is not None:
-            info.update(history=self.history, terminal_history=self._term_hist if want_terminal else None)
+        for f in self._families:
+            info[f.key] = f.rows
+            info["terminal_" + f.key] = f.terminal_rows if want_terminal else None
         if self.track_ids is not None:
             # track: the track of the episode the drone is in after the step; terminal_track: that of its most recently ended episode
             # (the one `terminal_obs` belongs to where done; -1 before the first)
@@ -490,12 +491,10 @@ class DroneVecEnv(_VecEnvBase):
         if self.track_ids is not None:         # every step path (step_tensor, and step_async of the NumPy surface) leaves env.track_ids current
             with torch.cuda.device(self.device):
                 self._fetch_tracks()
-        if self.history_obs is not None:       # likewise env.history: stacked in place (a drone's previous row is read before it is written)
-            ext = self.history_obs.goal
+        if self.history is not None:           # likewise env.history: stacked in place (a drone's previous row is read before it is written)
             with torch.cuda.device(self.device):
                 self._stack_history(1, self.history, self._obs, actions, self._done, self._term_obs if want_terminal else None,
-                                    self.goal if ext else None, self._term_goal if ext and want_terminal else None, self.history,
-                                    self._term_hist if want_terminal else None)
+                                    self.goal, self._term_goal, self.history, self._term_hist)
 
     def eval_kinematics_tensor(self, kinematics):
         """Rows A5-A9 of one control step with the rigid-body transition given (dn_eval_kinematics): `kinematics` is a
@@ -538,28 +537,14 @@ class DroneVecEnv(_VecEnvBase):
                            ep_return=torch.zeros((k, n), dtype=torch.float32, device=dev),
                            ep_length=torch.zeros((k, n), dtype=torch.int32, device=dev),
                            done_mask=torch.zeros((k, (n + 63) // 64), dtype=torch.int64, device=dev))
-            if self.privileged is not None:
-                out["privileged"] = torch.zeros((k, n, PRIV_DIM), dtype=torch.float32, device=dev)
+            for f in self._families:
+                out[f.key] = torch.zeros((k, n, f.width), dtype=torch.float32, device=dev)
                 if want_terminal:
-                    out["terminal_privileged"] = torch.zeros((k, n, PRIV_DIM), dtype=torch.float32, device=dev)
-            if self.goal is not None:
-                out["goal"] = torch.zeros((k, n, GOAL_DIM), dtype=torch.float32, device=dev)
-                if want_terminal:
-                    out["terminal_goal"] = torch.zeros((k, n, GOAL_DIM), dtype=torch.float32, device=dev)
-            if self.history_obs is not None:
-                out["history"] = torch.zeros((k, n, self.history.shape[1]), dtype=torch.float32, device=dev)
-                if want_terminal:
-                    out["terminal_history"] = torch.zeros((k, n, self.history.shape[1]), dtype=torch.float32, device=dev)
-        if self.privileged is not None:
-            if "privileged" not in out:
-                raise ValueError("out has no 'privileged' buffer: pass a dict rollout_tensor returned for this env")
-            self._bind_privileged(out["privileged"], out.get("terminal_privileged"), k)
-        if self.goal is not None:
-            if "goal" not in out:
-                raise ValueError("out has no 'goal' buffer: pass a dict rollout_tensor returned for this env")
-            self._bind_goal(out["goal"], out.get("terminal_goal"), k)
-        if self.history_obs is not None and "history" not in out:
-            raise ValueError("out has no 'history' buffer: pass a dict rollout_tensor returned for this env")
+                    out["terminal_" + f.key] = torch.zeros((k, n, f.width), dtype=torch.float32, device=dev)
+        for f in self._families:
+            if f.key not in out:
+                raise ValueError(f"out has no '{f.key}' buffer: pass a dict rollout_tensor returned for this env")
+            self._bind(f, out[f.key], out.get("terminal_" + f.key), k)
 
         def ptr(name):
             return out[name].data_ptr() if name in out else None
@@ -569,27 +554,18 @@ class DroneVecEnv(_VecEnvBase):
                 ptr("found_targets"), ptr("terminal_obs"), ptr("ep_return"), ptr("ep_length"), ptr("done_mask"),
                 self._stream()))
             self._fetch_tracks()
-            if self.history_obs is not None:
-                # all K steps in one launch, from the env's current rows; the last slot becomes the env's current rows
-                ext = self.history_obs.goal
-                term = out.get("terminal_history") if "terminal_obs" in out else None
-                self._stack_history(k, self.history, out["obs"], actions, out["done"], out.get("terminal_obs") if term is not None else None,
-                                    out["goal"] if ext else None, out.get("terminal_goal") if ext and term is not None else None,
-                                    out["history"], term)
-                self.history.copy_(out["history"][k - 1])
+            if self.history is not None:         # all K steps in one launch, from the env's current rows
+                self._stack_history(k, self.history, out["obs"], actions, out["done"], out.get("terminal_obs"), out.get("goal"),
+                                    out.get("terminal_goal"), out["history"], out.get("terminal_history"))
         if self.track_ids is not None:       # the tracks after the launch (env.track_ids and the finished tracks)
             out["track"], out["terminal_track"] = self.track_ids, self._finished_ids
-        if self.privileged is not None:
+        for f in self._families:
             # the last step's rows are the env's current ones (the columns the kernels wrote: the rest of `out` is the caller's bytes);
             # the caller's buffers must not stay bound beyond their lifetime
-            last = out["privileged"][k - 1]
-            for a, b in self._priv_runs:
-                self.privileged[:, a:b].copy_(last[:, a:b])
-            self._bind_privileged(self.privileged, self._term_priv, 1)
-        if self.goal is not None:
-            # likewise: the last step's rows are the env's current ones, and the caller's buffers do not stay bound
-            self.goal.copy_(out["goal"][k - 1])
-            self._bind_goal(self.goal, self._term_goal, 1)
+            last = out[f.key][k - 1]
+            for a, b in f.runs:
+                f.rows[:, a:b].copy_(last[:, a:b])
+            self._bind(f, f.rows, f.terminal_rows, 1)
         return out
 
     def done_indices(self):

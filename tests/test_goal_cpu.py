@@ -123,9 +123,9 @@ def test_collectors_judge_policy_input_and_refuse_goal_envs_without_a_device(pkg
         pkg.RolloutCollector(object(), None, 4, policy_input="observation+goal")
     # what FusedRolloutCollector and OffPolicyCollector call first
     with pytest.raises(ValueError, match="FusedRolloutCollector does not carry goal observations"):
-        collector._refuse_goal(types.SimpleNamespace(goal=object()), "FusedRolloutCollector")
-    collector._refuse_goal(types.SimpleNamespace(goal=None), "OffPolicyCollector")
-    collector._refuse_goal(object(), "OffPolicyCollector")
+        collector._refuse_extra_rows(types.SimpleNamespace(goal=object()), "FusedRolloutCollector")
+    collector._refuse_extra_rows(types.SimpleNamespace(goal=None), "OffPolicyCollector")
+    collector._refuse_extra_rows(object(), "OffPolicyCollector")
 
 
 # ---- the reference itself ------------------------------------------------------------------------------------------------------------

@@ -632,7 +632,7 @@ def test_collector_feeds_the_policy_observation_and_goal():
     col = RolloutCollector(A, policy, T, policy_input="observation+goal", gamma=gamma)
     obs = R.reset_tensor().clone()
     goal = R.goal.clone()
-    assert torch.equal(col._last_obs, obs) and torch.equal(col._last_goal, goal)
+    assert torch.equal(col._last_obs, obs) and torch.equal(col._last["goal"], goal)
     trunc = ahead_boot = 0
     rng, seen = np.random.default_rng(12), Seen()
     for e in (A, R):

@@ -392,7 +392,7 @@ def test_collector_normalises_the_privileged_rows_for_the_critic():
 
     col = RolloutCollector(A, _policy(13), T, value_fn=value_fn, value_input="privileged", value_norm=vn, gamma=gamma)
     twin.reset_tensor()
-    _same(col._last_priv, twin.privileged, "reset rows")
+    _same(col._last["privileged"], twin.privileged, "reset rows")
     cur = mine.update_normalize(twin.privileged)                       # the reset rows update, then are normalised
     truncated = 0
     for rollout in range(3):
@@ -476,7 +476,7 @@ def test_collector_normalises_the_history_rows_for_the_policy():
 
     pn, mine = pkg.RowNormalizer(W, DEV), pkg.RowNormalizer(W, DEV)
     col = RolloutCollector(A, policy, T, policy_input="history", policy_norm=pn)
-    cur = mine.update_normalize(col._last_hist)
+    cur = mine.update_normalize(col._last["history"])
     for rollout in range(2):
         del calls[:]
         buf = col.collect()
@@ -484,7 +484,7 @@ def test_collector_normalises_the_history_rows_for_the_policy():
         for t in range(T):
             _same(buf["policy_rows"][t], cur, (rollout, t, "policy_rows"))
             _same(calls[2 * t], cur, (rollout, t, "the policy was shown other rows"))      # calls[2 t + 1]: the bootstrap's values
-            cur = mine.update_normalize(buf["history"][t + 1] if t + 1 < T else col._last_hist)
+            cur = mine.update_normalize(buf["history"][t + 1] if t + 1 < T else col._last["history"])
         _same(pn.stats, mine.stats, (rollout, "statistics"))
     assert int(buf["episode_starts"].sum()) > 0
     A.close()

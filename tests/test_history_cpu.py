@@ -193,6 +193,6 @@ def test_collectors_know_the_history_mode_and_refuse_history_envs(pkg):
     with pytest.raises(TypeError, match="DroneVecEnv"):                   # the known mode gets as far as the env check
         pkg.RolloutCollector(object(), None, 4, policy_input="history")
     with pytest.raises(ValueError, match="FusedRolloutCollector does not carry history rows"):
-        collector._refuse_history(types.SimpleNamespace(history=object()), "FusedRolloutCollector")
-    collector._refuse_history(types.SimpleNamespace(history=None), "OffPolicyCollector")
-    collector._refuse_history(object(), "OffPolicyCollector")
+        collector._refuse_extra_rows(types.SimpleNamespace(history=object()), "FusedRolloutCollector")
+    collector._refuse_extra_rows(types.SimpleNamespace(history=None), "OffPolicyCollector")
+    collector._refuse_extra_rows(object(), "OffPolicyCollector")
