@@ -106,6 +106,17 @@ class DnRetnormConfig(C.Structure):
     _fields_ = [("gamma", C.c_double), ("epsilon", C.c_double), ("clip", C.c_float), ("reserved", C.c_int32)]
 
 
+class DnMinibatchField(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("normalize", C.c_int32)]
+
+
+class DnMinibatchConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("epoch", C.c_uint64), ("epsilon", C.c_double), ("num_fields", C.c_int32), ("reserved", C.c_int32)]
+
+
+MINIBATCH_MAX_FIELDS = 8
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -157,6 +168,10 @@ PROTOTYPES = {
     "dn_retnorm_scratch_bytes": (_I64, [_I64, _I64]),
     "dn_retnorm_init": (_I32, [_VP, _VP, _I64, _I32, _VP]),
     "dn_retnorm": (_I32, [C.POINTER(DnRetnormConfig), _VP, _VP, _I64, _I64, _VP, _VP, _VP, _I32, _VP, _I64, _I32, _VP]),
+    "dn_minibatch_scratch_bytes": (_I64, [_I64]),
+    "dn_minibatch_permutation": (_I32, [C.c_uint64, C.c_uint64, _I64, _I64, _I64, _VP]),
+    "dn_minibatch": (_I32, [C.POINTER(DnMinibatchConfig), C.POINTER(DnMinibatchField), _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _I64, _I32,
+                            _VP]),
     "dn_set_launch_events": (_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

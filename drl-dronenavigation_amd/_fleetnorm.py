@@ -1,6 +1,7 @@
-"""What the two fleet-wide normalisers share on the Python side (rownorm.RowNormalizer, retnorm.ReturnNormalizer): the device, the clip
-and epsilon checks, the stream, the scratch with its capture guard, and the staging of tensors that are not dense.  Shapes, state and the
-C calls are the classes' own."""
+"""What the classes that call the env-free kernels share on the Python side.  DeviceScratch (rownorm.RowNormalizer,
+retnorm.ReturnNormalizer, minibatch.MinibatchSampler): the device, the stream and the scratch with its capture guard.  FleetNormalizer, what
+the two fleet-wide normalisers share beyond that: the clip and epsilon checks and the staging of tensors that are not dense.  Shapes, state
+and the C calls are the classes' own."""
 import ctypes as C
 import math
 
@@ -9,20 +10,14 @@ import torch
 from . import _capi
 
 
-class FleetNormalizer:
-    _NAME = _NOUN = None        # the class and its input tensor as the messages name them: "RowNormalizer", "rows"
+class DeviceScratch:
+    _NAME = _NOUN = None        # the class and its input as the messages name them: "RowNormalizer", "rows"
 
-    def __init__(self, device, clip, epsilon):
-        clip, epsilon = float(clip), float(epsilon)
-        if not clip > 0.0:
-            raise ValueError(f"{self._NAME}.clip must be > 0 (math.inf for no clip), got {clip!r}")
-        if not epsilon >= 0.0:
-            raise ValueError(f"{self._NAME}.epsilon must be >= 0, got {epsilon!r}")
+    def __init__(self, device):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(f"{self._NAME} needs a GPU device, got {device}; there is no CPU path")
         self.device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
-        self.clip, self.epsilon = clip, epsilon
         self._lib = _capi.load()
         self._scratch = None
 
@@ -39,6 +34,17 @@ class FleetNormalizer:
                                    "this size before capturing")
             self._scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
         return self._scratch
+
+
+class FleetNormalizer(DeviceScratch):
+    def __init__(self, device, clip, epsilon):
+        clip, epsilon = float(clip), float(epsilon)
+        if not clip > 0.0:
+            raise ValueError(f"{self._NAME}.clip must be > 0 (math.inf for no clip), got {clip!r}")
+        if not epsilon >= 0.0:
+            raise ValueError(f"{self._NAME}.epsilon must be >= 0, got {epsilon!r}")
+        super().__init__(device)
+        self.clip, self.epsilon = clip, epsilon
 
     def _check_source(self, x):
         if not isinstance(x, torch.Tensor) or x.device != self.device or x.dtype != torch.float32:

@@ -4,6 +4,7 @@
 // validates its arguments, turns HIP failures into dn_status codes + a thread-local message, and
 // never falls back to a CPU implementation.
 #include "dn_internal.h"
+#include "dn_permute.h"
 #include "dn_shapes.h"
 
 #include <cmath>
@@ -1758,6 +1759,83 @@ int32_t dn_retnorm(const dn_retnorm_config *cfg, double *stats, double *returns,
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_retnorm(cfg->gamma, cfg->epsilon, cfg->clip, stats, update ? returns : nullptr, k, n, rewards, update ? done : nullptr, out,
                              update, update ? (double *)scratch : nullptr, (hipStream_t)stream));
+    return DN_OK;
+}
+
+// ---- dn_minibatch: SB3 RolloutBuffer.get and PPO's advantage normalisation [from recall] on the step-major buffers ----------------------
+int64_t dn_minibatch_scratch_bytes(int64_t batch)
+{
+    const long long d = dn_minibatch_scratch_doubles(batch);
+    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
+    return d * 8;
+}
+
+/* the keyed permutation of csrc/dn_permute.h on the host: no device, no HIP call */
+int32_t dn_minibatch_permutation(uint64_t seed, uint64_t epoch, int64_t m, int64_t start, int64_t count, int64_t *out)
+{
+    if (m < 1 || m > DN_PERMUTE_MAX) return fail(DN_ERR_INVALID_ARGUMENT, "m must be in 1..2^31 - 1 (got %lld)", (long long)m);
+    if (start < 0 || count < 0 || start > m || count > m - start)
+        return fail(DN_ERR_INVALID_ARGUMENT, "start and count must be >= 0 with start + count <= m (got %lld, %lld, m %lld)", (long long)start,
+                    (long long)count, (long long)m);
+    if (!out) return fail(DN_ERR_INVALID_ARGUMENT, "out is required");
+    const DnPermutation p = dn_permute_make(seed, epoch, (uint32_t)m);
+    for (int64_t i = 0; i < count; ++i) out[i] = (int64_t)dn_permute_at(p, (uint32_t)(start + i));
+    return DN_OK;
+}
+
+int32_t dn_minibatch(const dn_minibatch_config *cfg, const dn_minibatch_field *fields, int64_t n_steps, int64_t n_envs, int64_t start,
+                     int64_t batch, const int64_t *indices, const int64_t *epoch_offset, int64_t *indices_out, void *scratch,
+                     int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (!cfg || !fields) return fail(DN_ERR_INVALID_ARGUMENT, "cfg and fields are required");
+    if (cfg->num_fields < 1 || cfg->num_fields > DN_MINIBATCH_MAX_FIELDS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "num_fields must be in 1..%d (got %d)", DN_MINIBATCH_MAX_FIELDS, cfg->num_fields);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (!(cfg->epsilon >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "epsilon must be >= 0 (got %g)", cfg->epsilon);
+    if (n_steps < 1 || n_envs < 1) return fail(DN_ERR_INVALID_ARGUMENT, "n_steps and n_envs must be >= 1 (got %lld, %lld)", (long long)n_steps, (long long)n_envs);
+    if (n_steps > DN_PERMUTE_MAX || n_envs > DN_PERMUTE_MAX / n_steps)
+        return fail(DN_ERR_INVALID_ARGUMENT, "n_steps x n_envs = %lld x %lld samples are more than the 2^31 - 1 of a buffer", (long long)n_steps,
+                    (long long)n_envs);
+    const int64_t m = n_steps * n_envs;
+    // batch <= m <= 2^31 - 1: the grids, blocks(batch) x num_fields and ceil(batch / 256) workgroups, are far below the 2^31 - 1 of a launch
+    if (batch < 1 || start < 0 || start > m || batch > m - start)
+        return fail(DN_ERR_INVALID_ARGUMENT, "start must be >= 0 and batch >= 1 with start + batch <= n_steps x n_envs = %lld (got %lld, %lld)",
+                    (long long)m, (long long)start, (long long)batch);
+    if (indices && start != 0) return fail(DN_ERR_INVALID_ARGUMENT, "start must be 0 with indices (got %lld)", (long long)start);
+    DnMinibatchArgs a;
+    a.num_fields = cfg->num_fields;
+    a.norm_field = -1;
+    for (int f = 0; f < cfg->num_fields; ++f) {
+        const dn_minibatch_field &fd = fields[f];
+        if (!fd.src || !fd.dst) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: src and dst are required", f);
+        if (fd.width < 1 || fd.width > DN_ROWNORM_MAX_WIDTH)
+            return fail(DN_ERR_INVALID_ARGUMENT, "field %d: width must be in 1..%d (got %d)", f, DN_ROWNORM_MAX_WIDTH, fd.width);
+        if (fd.normalize != 0 && fd.normalize != 1) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: normalize must be 0 or 1 (got %d)", f, fd.normalize);
+        if (fd.normalize) {
+            if (a.norm_field >= 0) return fail(DN_ERR_INVALID_ARGUMENT, "fields %d and %d: at most one field is normalised", a.norm_field, f);
+            if (fd.width != 1) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: the normalised field must be of width 1 (got %d)", f, fd.width);
+            a.norm_field = f;
+        }
+        if (fd.dst == fd.src) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: dst must not be src", f);
+        if (((uintptr_t)fd.src | (uintptr_t)fd.dst) & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: src and dst must be 4-byte aligned", f);
+        a.fields[f] = fd;
+    }
+    for (int f = cfg->num_fields; f < DN_MINIBATCH_MAX_FIELDS; ++f) a.fields[f] = dn_minibatch_field{nullptr, nullptr, 0, 0};
+    if (!scratch) return fail(DN_ERR_INVALID_ARGUMENT, "scratch is required");
+    const int64_t need = dn_minibatch_scratch_bytes(batch);
+    if (scratch_bytes < need)
+        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_minibatch_scratch_bytes gives %lld", (long long)scratch_bytes,
+                    (long long)need);
+    if (((uintptr_t)scratch | (uintptr_t)indices | (uintptr_t)epoch_offset | (uintptr_t)indices_out) & 7u)
+        return fail(DN_ERR_INVALID_ARGUMENT, "scratch, indices, epoch_offset and indices_out must be 8-byte aligned");
+    if (batch == 1) a.norm_field = -1;                 // SB3 skips the normalisation of a minibatch of one
+    a.seed = cfg->seed; a.epoch = cfg->epoch; a.eps = cfg->epsilon;
+    a.n_steps = (unsigned)n_steps; a.n_envs = (unsigned)n_envs; a.m = (unsigned)m; a.start = (unsigned)start; a.batch = (unsigned)batch;
+    a.nblk = (unsigned)dn_rownorm_blocks(batch);
+    a.indices = (const long long *)indices; a.epoch_offset = (const long long *)epoch_offset; a.indices_out = (long long *)indices_out;
+    a.part = (double *)scratch;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_minibatch(a, (hipStream_t)stream));
     return DN_OK;
 }
 

@@ -1,6 +1,7 @@
-// dn_fleet_rms.h -- the running-moments merge of the fleet-wide normalisers (dn_rownorm.hip, dn_retnorm.hip): device code only, and the
-// only place that holds it.  Every bit of both normalisers' statistics depends on the order of the float64 operations below (the build
-// uses -ffp-contract=off); the two merge kernels choose which lane takes which column or step and where its moments lie, nothing else.
+// dn_fleet_rms.h -- the running-moments merge of the fleet-wide normalisers (dn_rownorm.hip, dn_retnorm.hip), which dn_minibatch.hip uses for
+// the blocks of a minibatch: device code only, and the only place that holds it.  Every bit of the statistics depends on the order of the
+// float64 operations below (the build uses -ffp-contract=off); the merge kernels choose which lane takes which column or step and where
+// its moments lie, nothing else.
 //
 // One lane works on one sequence of (mean, m2) pairs in global memory: the pair of item i has its mean at p[i * stride] and its sum of
 // squared deviations (or, after the update, whatever the caller stores) at p[i * stride + off2].  Both walks are sequential chains, so
@@ -10,6 +11,15 @@
 #include "dn_internal.h"
 
 constexpr int FR_BATCH = 8;                            // pairs in flight ahead of the sequential chain
+
+// The sum over the 64 lanes of a wave in a fixed tree (lane i + lane i + 32, then + 16, ... + 1); lane 0 holds it.  The lane order of the
+// block moments that are formed a row per lane (dn_retnorm.hip, dn_minibatch.hip).
+__device__ __forceinline__ double fr_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
 
 // 1 / x as the step kernels form it (dn_kernels.hip rcp_f64): v_rcp_f64 and two Newton steps, 5 instructions where an IEEE division is ~35
 __device__ __forceinline__ double fr_rcp(const double x)

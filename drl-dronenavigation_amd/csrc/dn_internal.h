@@ -342,6 +342,27 @@ hipError_t dn_launch_retnorm_init(double *stats, double *returns, long long n, h
 hipError_t dn_launch_retnorm(double gamma, double epsilon, float clip, double *stats, double *returns, long long k, long long n,
                              const float *rewards, const uint8_t *done, float *out, int update, double *scratch,
                              hipStream_t stream);                                                                               // dn_retnorm.hip
+// PPO minibatches (dn_minibatch, dn_minibatch.hip): the gather of one minibatch's rows and the advantage normalisation.  The moments of
+// the normalised field are formed per block of DN_ROWNORM_BLOCK_ROWS consecutive OUTPUT rows, the normalisers' constant, so every bit of
+// them depends on `batch` alone.  The scratch is doubles only:
+//   partials   [blocks(batch)][2]   mean and sum of squared deviations of the block's gathered values
+//   result     [2]                  the minibatch's mean and std + epsilon
+// 0 = refuse (batch < 1 or beyond the 2^31 - 1 samples of a buffer).
+struct DnMinibatchArgs {
+    dn_minibatch_field fields[DN_MINIBATCH_MAX_FIELDS];
+    int num_fields, norm_field;                        // norm_field: the field to normalise, -1 = none (or batch == 1)
+    unsigned long long seed, epoch;
+    double eps;
+    unsigned n_steps, n_envs, m, start, batch, nblk;    // nblk = blocks(batch)
+    const long long *indices, *epoch_offset;
+    long long *indices_out;
+    double *part;
+};
+inline long long dn_minibatch_scratch_doubles(long long batch)
+{
+    return batch < 1 || batch > 0x7fffffffll ? 0 : (dn_rownorm_blocks(batch) + 1) * 2;
+}
+hipError_t dn_launch_minibatch(const DnMinibatchArgs &a, hipStream_t stream);                                                  // dn_minibatch.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

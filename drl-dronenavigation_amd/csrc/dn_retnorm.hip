@@ -46,14 +46,6 @@ struct RtArgs {
     long long chunks;                                  // launch 3: workgroups per step
 };
 
-// the sum over the 64 lanes of a wave in a fixed tree (lane i + lane i + 32, then + 16, ... + 1); lane 0 holds it
-__device__ __forceinline__ double rt_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(RT_THREADS) void rt_scan_kernel(const RtArgs a)
 {
     __shared__ double l1[2][RT_STEPS][RT_WAVES], l2[2][RT_STEPS][RT_WAVES], lx[2][RT_STEPS];
@@ -85,7 +77,7 @@ __global__ __launch_bounds__(RT_THREADS) void rt_scan_kernel(const RtArgs a)
                 ret = ret * gamma + (double)r[j];      // unfused (-ffp-contract=off), as numpy evaluates it
                 ret0 = ret0 * gamma + (double)r0[j];
                 const double dv = on ? ret - ret0 : 0.0;
-                const double s1 = rt_wave_sum(dv), s2 = rt_wave_sum(dv * dv);
+                const double s1 = fr_wave_sum(dv), s2 = fr_wave_sum(dv * dv);
                 if (lane == 0) {
                     l1[buf][j][wave] = s1;
                     l2[buf][j][wave] = s2;

@@ -855,6 +855,62 @@ int32_t dn_retnorm_init(double *stats, double *returns, int64_t n, int32_t devic
 int32_t dn_retnorm(const dn_retnorm_config *cfg, double *stats, double *returns, int64_t k, int64_t n, const float *rewards,
                    const uint8_t *done, float *out, int32_t update, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
 
+/* PPO minibatches on the device: the reading half of SB3's RolloutBuffer, get(batch_size) [from recall] -- swap-and-flatten, one random
+ * permutation per epoch, the gathered minibatches, and the per-minibatch advantage normalisation of PPO.train [from recall] -- on the
+ * step-major [n_steps][n_envs] buffers that dn_step_many, dn_gae and the collectors leave, without a flattened copy and with pinned
+ * bits.  Env-free; the learner itself stays the caller's.
+ * Sample numbering: M = n_steps n_envs <= 2^31 - 1; sample s is drone s / n_steps at step s % n_steps, SB3's swap_and_flatten order
+ *   [from recall] (a caller who passes SB3's own np.random.permutation as `indices` gets SB3's minibatches); its source row is
+ *   (s % n_steps) n_envs + s / n_steps.
+ * Sample selection: output row j of the call, 0 <= j < batch, is sample indices[j] when `indices` (device int64[batch]) is not NULL; a
+ *   value outside [0, M) is clamped into it, so no read ever leaves the source.  With NULL indices row j is sample pi(start + j), pi the
+ *   keyed bijection of [0, M) under (seed, epoch + (epoch_offset ? *epoch_offset : 0)), the sum mod 2^64.
+ *   pi: b = max(1, bit_length(M - 1)), h = max(1, (b + 1) / 2), mask = 2^h - 1; six round keys k_r = the high 32 bits of six successive
+ *   splitmix64 outputs from the state seed ^ (epoch * 0xD1342543DE82EF95); one pass over v: L = (v >> h) & mask, R = v & mask, six times
+ *   F = fmix32(R + k_r) >> (32 - h), (L, R) = (R, (L ^ F) & mask) (fmix32: murmur3's finaliser), v' = L << h | R; pi(i) repeats the pass
+ *   from v = i until v' < M.  Evaluated per element: no permutation array, no sort (csrc/dn_permute.h, host and device).
+ *   epoch_offset   device int64[1] or NULL: lets a captured graph reshuffle on every replay, the way the environment's device-side step
+ *                  counter keeps the noise moving
+ *   indices_out    device int64[batch] or NULL: receives the samples taken
+ *   start          0 <= start and start + batch <= M; with `indices`, start must be 0
+ * Copies: every field's rows are copied bit for bit (32-bit words, float32 or int32), dst row j from the source row of sample j.
+ * Advantage normalisation: the `normalize` field is then out = (a - mean) / (std + epsilon), mean over the batch gathered values and std
+ *   their unbiased standard deviation (torch.std: divide by batch - 1); skipped when batch == 1, as SB3 skips it.  Moments, the
+ *   subtraction and a true division are float64, rounded once to float32.  A NaN advantage makes the minibatch's output NaN, as in torch.
+ * Bit-reproducible: the moments are float64 per block of 1024 consecutive output rows (the normalisers' constant) in dn_retnorm's shifted
+ *   form (shift = the block's first gathered value; lanes by a fixed tree, waves ascending), the blocks merged in ascending order by the
+ *   normalisers' merge.  The order of every float64 operation is a function of `batch` alone.
+ *   scratch        the caller's device memory, 8-byte aligned, at least dn_minibatch_scratch_bytes(batch): the per-block pairs, the mean
+ *                  and the denominator.  The library allocates nothing and keeps nothing between calls.
+ * At most three ordinary launches on `stream`: gather + block moments, a one-wave merge, the division; one launch when no field is
+ * normalised or batch == 1.  No workgroup waits for another, no atomics, capturable.  Validates before the first device call:
+ * DN_ERR_INVALID_ARGUMENT with a dn_last_error text.
+ * Layout of dn_minibatch_field: src at 0, dst at 8, width at 16, normalize at 20; 24 bytes.
+ * Layout of dn_minibatch_config: seed at 0, epoch at 8, epsilon at 16, num_fields at 24, reserved at 28; 32 bytes. */
+#define DN_MINIBATCH_MAX_FIELDS 8
+typedef struct dn_minibatch_field {
+    const void *src;      /* device, 32-bit words [n_steps][n_envs][width], dense, step-major (float32 or int32: copied bit for bit) */
+    void *dst;            /* device, [batch][width], dense; never src */
+    int32_t width;        /* 1..64 */
+    int32_t normalize;    /* 1 on at most one field, which must be width 1 and float32: the advantages */
+} dn_minibatch_field;
+typedef struct dn_minibatch_config {
+    uint64_t seed;
+    uint64_t epoch;
+    double epsilon;       /* >= 0; SB3's 1e-8 */
+    int32_t num_fields;   /* 1..8 */
+    int32_t reserved;     /* 0 */
+} dn_minibatch_config;
+/* Bytes of scratch for a minibatch of `batch` rows; a negative dn_status for batch < 1. */
+int64_t dn_minibatch_scratch_bytes(int64_t batch);
+/* Host only: needs no device and makes no HIP call.  out[0 .. count) <- pi(start) .. pi(start + count - 1) of [0, m) under (seed, epoch),
+ * in HOST memory, by the code the kernel runs.  1 <= m <= 2^31 - 1, 0 <= start, 0 <= count, start + count <= m. */
+int32_t dn_minibatch_permutation(uint64_t seed, uint64_t epoch, int64_t m, int64_t start, int64_t count, int64_t *out);
+/* SB3 RolloutBuffer.get [from recall] for one minibatch, and PPO.train's advantage normalisation [from recall]. */
+int32_t dn_minibatch(const dn_minibatch_config *cfg, const dn_minibatch_field *fields, int64_t n_steps, int64_t n_envs, int64_t start,
+                     int64_t batch, const int64_t *indices, const int64_t *epoch_offset, int64_t *indices_out, void *scratch,
+                     int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
