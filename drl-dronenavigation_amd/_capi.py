@@ -117,6 +117,14 @@ class DnMinibatchConfig(C.Structure):
 MINIBATCH_MAX_FIELDS = 8
 
 
+class DnPpoLossConfig(C.Structure):
+    _fields_ = [("clip_range", C.c_double), ("clip_range_vf", C.c_double), ("ent_coef", C.c_double), ("vf_coef", C.c_double),
+                ("act_dim", C.c_int32), ("reserved", C.c_int32)]
+
+
+PPO_MAX_ACT = 8
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -172,6 +180,8 @@ PROTOTYPES = {
     "dn_minibatch_permutation": (_I32, [C.c_uint64, C.c_uint64, _I64, _I64, _I64, _VP]),
     "dn_minibatch": (_I32, [C.POINTER(DnMinibatchConfig), C.POINTER(DnMinibatchField), _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _I64, _I32,
                             _VP]),
+    "dn_ppo_loss_scratch_bytes": (_I64, [_I64, _I32]),
+    "dn_ppo_loss": (_I32, [C.POINTER(DnPpoLossConfig), _I64] + [_VP] * 15 + [_I64, _I32, _VP]),
     "dn_set_launch_events": (_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

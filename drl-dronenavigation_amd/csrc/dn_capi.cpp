@@ -1839,4 +1839,77 @@ int32_t dn_minibatch(const dn_minibatch_config *cfg, const dn_minibatch_field *f
     return DN_OK;
 }
 
+// ---- dn_ppo_loss: SB3 PPO.train's loss, statistics and the gradients with respect to the head outputs [from recall] ---------------------
+int64_t dn_ppo_loss_scratch_bytes(int64_t batch, int32_t act_dim)
+{
+    if (act_dim < 1 || act_dim > DN_PPO_MAX_ACT) return fail(DN_ERR_INVALID_ARGUMENT, "act_dim must be in 1..%d (got %d)", DN_PPO_MAX_ACT, act_dim);
+    const long long d = dn_ppo_loss_scratch_doubles(batch, act_dim);
+    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
+    return d * 8;
+}
+
+int32_t dn_ppo_loss(const dn_ppo_loss_config *cfg, int64_t batch, const float *mean, const float *log_std, const float *value,
+                    const float *actions, const float *old_log_prob, const float *advantages, const float *returns,
+                    const float *old_values, float *d_mean, float *d_log_std, float *d_value, float *log_prob_out, float *loss,
+                    double *stats, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (cfg->act_dim < 1 || cfg->act_dim > DN_PPO_MAX_ACT)
+        return fail(DN_ERR_INVALID_ARGUMENT, "act_dim must be in 1..%d (got %d)", DN_PPO_MAX_ACT, cfg->act_dim);
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
+    if (batch < 1 || batch > 0x7fffffffll) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
+    if (!std::isfinite(cfg->clip_range) || !(cfg->clip_range > 0.0))
+        return fail(DN_ERR_INVALID_ARGUMENT, "clip_range must be finite and > 0 (got %g)", cfg->clip_range);
+    if (!std::isfinite(cfg->clip_range_vf))
+        return fail(DN_ERR_INVALID_ARGUMENT, "clip_range_vf must be finite: > 0 clips the value step, <= 0 does not (got %g)", cfg->clip_range_vf);
+    if (!std::isfinite(cfg->ent_coef) || !(cfg->ent_coef >= 0.0))
+        return fail(DN_ERR_INVALID_ARGUMENT, "ent_coef must be finite and >= 0 (got %g)", cfg->ent_coef);
+    if (!std::isfinite(cfg->vf_coef) || !(cfg->vf_coef >= 0.0))
+        return fail(DN_ERR_INVALID_ARGUMENT, "vf_coef must be finite and >= 0 (got %g)", cfg->vf_coef);
+    const bool vclip = cfg->clip_range_vf > 0.0;
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float), cells = rows * (uintptr_t)cfg->act_dim, cols = (uintptr_t)cfg->act_dim * sizeof(float);
+    struct Span { const char *name; const void *p; uintptr_t bytes; bool optional; };
+    const Span in[] = {{"mean", mean, cells, false}, {"log_std", log_std, cols, false}, {"value", value, rows, false}, {"actions", actions, cells, false},
+                       {"old_log_prob", old_log_prob, rows, false}, {"advantages", advantages, rows, false}, {"returns", returns, rows, false},
+                       {"old_values", old_values, rows, true}};
+    const Span out[] = {{"d_mean", d_mean, cells, false}, {"d_log_std", d_log_std, cols, false}, {"d_value", d_value, rows, false},
+                        {"loss", loss, sizeof(float), false},
+                        {"stats", stats, 8 * sizeof(double), false}, {"scratch", scratch, 0, false}, {"log_prob_out", log_prob_out, rows, true}};
+    for (const Span &s : in)
+        if (!s.p && !s.optional) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", s.name);
+    if (vclip && !old_values) return fail(DN_ERR_INVALID_ARGUMENT, "old_values is required with clip_range_vf > 0 (got %g)", cfg->clip_range_vf);
+    if (!vclip && old_values) return fail(DN_ERR_INVALID_ARGUMENT, "old_values must be NULL without a value clip (clip_range_vf %g <= 0)", cfg->clip_range_vf);
+    for (const Span &s : out)
+        if (!s.p && !s.optional) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", s.name);
+    const int64_t need = dn_ppo_loss_scratch_bytes(batch, cfg->act_dim);
+    if (scratch_bytes < need)
+        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_ppo_loss_scratch_bytes gives %lld", (long long)scratch_bytes,
+                    (long long)need);
+    if (((uintptr_t)stats | (uintptr_t)scratch) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats and scratch must be 8-byte aligned");
+    for (const Span &s : in)
+        if ((uintptr_t)s.p & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", s.name);
+    for (const Span &s : out)
+        if ((uintptr_t)s.p & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", s.name);
+    for (const Span &o : out) {
+        if (!o.p) continue;
+        const uintptr_t o0 = (uintptr_t)o.p, obytes = o.p == scratch ? (uintptr_t)need : o.bytes;
+        for (const Span &i : in) {
+            const uintptr_t i0 = (uintptr_t)i.p;
+            if (i.p && i0 < o0 + obytes && o0 < i0 + i.bytes) return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no output may alias an input", o.name, i.name);
+        }
+    }
+    DnPpoLossArgs a;
+    a.mean = mean; a.log_std = log_std; a.value = value; a.actions = actions; a.old_log_prob = old_log_prob; a.advantages = advantages;
+    a.returns = returns; a.old_values = old_values;
+    a.d_mean = d_mean; a.d_log_std = d_log_std; a.d_value = d_value; a.log_prob_out = log_prob_out; a.loss = loss;
+    a.stats = stats; a.part = (double *)scratch;
+    a.clip_range = cfg->clip_range; a.clip_range_vf = cfg->clip_range_vf; a.ent_coef = cfg->ent_coef; a.vf_coef = cfg->vf_coef;
+    a.batch = batch; a.nblk = dn_rownorm_blocks(batch);
+    a.act_dim = cfg->act_dim;
+    a.vec = cfg->act_dim % 4 == 0 && (((uintptr_t)mean | (uintptr_t)actions | (uintptr_t)d_mean) & 15u) == 0;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_ppo_loss(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
 }  // extern "C"

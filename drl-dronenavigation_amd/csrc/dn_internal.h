@@ -363,6 +363,25 @@ inline long long dn_minibatch_scratch_doubles(long long batch)
     return batch < 1 || batch > 0x7fffffffll ? 0 : (dn_rownorm_blocks(batch) + 1) * 2;
 }
 hipError_t dn_launch_minibatch(const DnMinibatchArgs &a, hipStream_t stream);                                                  // dn_minibatch.hip
+// The PPO loss head (dn_ppo_loss, dn_ppo_loss.hip): per-row terms and gradients, and 4 + act_dim float64 sums formed per block of
+// DN_ROWNORM_BLOCK_ROWS consecutive rows, the normalisers' constant, so every bit depends on (batch, act_dim) alone.  The scratch is
+// doubles only:
+//   part   [blocks(batch)][4 + act_dim]   the block's sums of min(p1, p2), (returns - vpred)^2, (ratio - 1) - lr, the clip indicator, and
+//                                         g (z_j^2 - 1) per column
+// 0 = refuse (act_dim outside 1..DN_PPO_MAX_ACT, batch < 1 or beyond 2^31 - 1 rows: the grid of a launch).
+struct DnPpoLossArgs {
+    const float *mean, *log_std, *value, *actions, *old_log_prob, *advantages, *returns, *old_values;   // old_values: NULL = no value clip
+    float *d_mean, *d_log_std, *d_value, *log_prob_out, *loss;                                          // log_prob_out: NULL = not wanted
+    double *stats, *part;
+    double clip_range, clip_range_vf, ent_coef, vf_coef;
+    long long batch, nblk;                             // nblk = blocks(batch)
+    int act_dim, vec;                                  // vec: act_dim % 4 == 0 and mean, actions, d_mean are 16-byte aligned
+};
+inline long long dn_ppo_loss_scratch_doubles(long long batch, int act_dim)
+{
+    return act_dim < 1 || act_dim > DN_PPO_MAX_ACT || batch < 1 || batch > 0x7fffffffll ? 0 : dn_rownorm_blocks(batch) * (4 + act_dim);
+}
+hipError_t dn_launch_ppo_loss(const DnPpoLossArgs &a, hipStream_t stream);                                                     // dn_ppo_loss.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

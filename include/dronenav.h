@@ -911,6 +911,59 @@ int32_t dn_minibatch(const dn_minibatch_config *cfg, const dn_minibatch_field *f
                      int64_t batch, const int64_t *indices, const int64_t *epoch_offset, int64_t *indices_out, void *scratch,
                      int64_t scratch_bytes, int32_t device_id, void *stream);
 
+/* The PPO loss head on the device: SB3's PPO.train body [from recall] between the three head outputs of a diagonal-Gaussian actor-critic
+ * (action_net, log_std, value_net of MlpActorCritic) and the scalar loss -- the clipped surrogate, the value loss, the entropy term, SB3's
+ * logged statistics, and the gradients of the loss with respect to the three head outputs.  Env-free; the networks' own forward and
+ * backward, the optimiser and the learner loop stay the caller's.
+ * Inputs (device float32, dense), row b < batch, column j < A = act_dim: mean[batch][A], log_std[A], value[batch]; of the minibatch
+ *   actions[batch][A], old_log_prob[batch], advantages[batch], returns[batch], and old_values[batch], which is read when the value clip
+ *   is on and must be NULL when it is off.
+ * Scalars: clip_range c > 0, finite; clip_range_vf cv: > 0 and finite = clip the value step, any finite value <= 0 = no value clip (NaN and
+ *   the infinities are refused); ent_coef and vf_coef >= 0, finite.  They are host arguments: a captured graph keeps the values it was captured with.
+ * Arithmetic: every input is widened to float64 once; everything below is float64.  ratio = exp(lr) is the float64 library function;
+ *   inv_j = exp(-log_std_j) is rounded correctly (csrc/dn_exp_cr.h): every bit of logp hangs on it, and in the first epoch, lr ~ 1e-7,
+ *   approx_kl's term (ratio - 1) - lr ~ lr^2 / 2 hangs on the last bit of lr.
+ *   inv_j = exp(-log_std_j)                       z_bj = (actions_bj - mean_bj) inv_j
+ *   logp_b = sum_j (-0.5 z_bj^2 - log_std_j - 0.5 log(2 pi)), j ascending
+ *   lr_b = logp_b - old_log_prob_b                ratio_b = exp(lr_b)
+ *   p1 = adv ratio, p2 = adv clamp(ratio, 1 - c, 1 + c)
+ *   policy_loss = -mean_b min(p1, p2)             clip_fraction = mean_b [|ratio - 1| > c]        approx_kl = mean_b ((ratio - 1) - lr)
+ *   vpred_b = value_b, or with the value clip old_b + clamp(value_b - old_b, -cv, cv)             value_loss = mean_b (returns_b - vpred_b)^2
+ *   entropy_loss = -sum_j (0.5 + 0.5 log(2 pi) + log_std_j)
+ *   loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ * Gradients of loss (what torch's autograd gives for the composition above):
+ *   w_b = 1 if p1 < p2, 0 if p1 > p2; on p1 == p2: 1 if 1 - c <= ratio <= 1 + c, else 0.5 (torch.min splits a tie, torch.clamp passes its
+ *   bounds);  g_b = -adv_b w_b ratio_b / batch;  d_mean_bj = g_b z_bj inv_j;  d_log_std_j = sum_b g_b (z_bj^2 - 1) - ent_coef;
+ *   d_value_b = vf_coef (-2) (returns_b - vpred_b) [no value clip, or -cv <= value_b - old_b <= cv] / batch.
+ *   NaN and infinity are not special-cased: a NaN advantage gives NaN in loss and policy_loss, a NaN d_log_std, and NaN in d_mean of
+ *   its own row only.
+ * Outputs, each rounded once: float32 d_mean[batch][A], d_log_std[A], d_value[batch], log_prob_out[batch] (logp; may be NULL), loss[1];
+ *   float64 stats[8] = loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, 0, 0.  No output may overlap an input.
+ * Bit-reproducible: the means are float64 sums per block of 1024 consecutive rows (the normalisers' constant; lanes by a fixed tree,
+ *   waves ascending), the blocks added in ascending order.  The order of every float64 operation is a function of (batch, act_dim) alone.
+ *   scratch        the caller's device memory, 8-byte aligned, at least dn_ppo_loss_scratch_bytes(batch, act_dim): the block sums.  The
+ *                  library allocates nothing and keeps nothing between calls.
+ * Two ordinary launches on `stream`: rows + block sums, a one-wave merge.  No workgroup waits for another, no atomics, capturable.
+ * Validates before the first device call: DN_ERR_INVALID_ARGUMENT with a dn_last_error text that names the argument.
+ * Layout of dn_ppo_loss_config: clip_range at 0, clip_range_vf at 8, ent_coef at 16, vf_coef at 24, act_dim at 32, reserved at 36;
+ * 40 bytes. */
+#define DN_PPO_MAX_ACT 8
+typedef struct dn_ppo_loss_config {
+    double clip_range;      /* > 0, finite; SB3's 0.2 */
+    double clip_range_vf;   /* > 0: clip the value step; <= 0: no value clip (SB3's None) */
+    double ent_coef;        /* >= 0, finite */
+    double vf_coef;         /* >= 0, finite */
+    int32_t act_dim;        /* 1..8 */
+    int32_t reserved;       /* 0 */
+} dn_ppo_loss_config;
+/* Bytes of scratch for `batch` rows of `act_dim` columns; a negative dn_status for batch < 1 or beyond 2^31 - 1, or act_dim outside 1..8. */
+int64_t dn_ppo_loss_scratch_bytes(int64_t batch, int32_t act_dim);
+/* SB3 PPO.train [from recall]: the loss of one minibatch, its statistics and its gradients with respect to the head outputs. */
+int32_t dn_ppo_loss(const dn_ppo_loss_config *cfg, int64_t batch, const float *mean, const float *log_std, const float *value,
+                    const float *actions, const float *old_log_prob, const float *advantages, const float *returns,
+                    const float *old_values, float *d_mean, float *d_log_std, float *d_value, float *log_prob_out, float *loss,
+                    double *stats, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,323 @@
+"""The PPO loss head (include/dronenav.h dn_ppo_loss), the part that needs no GPU: the two entry points are declared, exported and bound;
+the layout of dn_ppo_loss_config, compiled from the header; the scratch-size rule; every refusal of dn_ppo_loss, which validates before
+its first device call, so the pointers here are never followed; the correctly rounded exp of csrc/dn_exp_cr.h as a stand-alone host
+program, plainly and under the address and undefined-behaviour sanitizers; the refusals of PpoLoss; and the reference of tests/ppo_loss_support.py
+-- the float64 torch composition with autograd -- against the closed forms of the header restated in NumPy, its coverage of both branches
+of every clamp, and its stability under the order of the rows."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+import ppo_loss_support as P  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("dn_ppo_loss_scratch_bytes", "dn_ppo_loss")
+INVALID = -1
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import drl_dronenavigation_amd as p
+    p.build.build_library()
+    return p
+
+
+def test_the_names_are_declared_exported_and_bound(pkg):
+    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    assert re.search(r"#define DN_PPO_MAX_ACT 8\b", code)
+    assert re.search(r"typedef struct dn_ppo_loss_config \{\s*double clip_range;\s*double clip_range_vf;\s*double ent_coef;\s*double vf_coef;\s*"
+                     r"int32_t act_dim;\s*int32_t reserved;\s*\} dn_ppo_loss_config;", code)
+    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
+    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
+    for name in NAMES:
+        assert re.search(r"\b%s\s*\(" % name, code), name
+        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    assert pkg.PpoLoss is pkg.ppo.PpoLoss and "PpoLoss" in pkg.__all__
+    assert pkg._capi.load().dn_abi_version() == 9
+
+
+def test_struct_layout_compiled_from_the_header(pkg, tmp_path):
+    """dn_ppo_loss_config: 40 bytes, clip_range 0, clip_range_vf 8, ent_coef 16, vf_coef 24, act_dim 32, reserved 36 -- by the C compiler
+    from the header itself, and the ctypes mirror agrees."""
+    prog = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "dronenav.h"
+int main(void) {
+    printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(dn_ppo_loss_config), offsetof(dn_ppo_loss_config, clip_range),
+           offsetof(dn_ppo_loss_config, clip_range_vf), offsetof(dn_ppo_loss_config, ent_coef), offsetof(dn_ppo_loss_config, vf_coef),
+           offsetof(dn_ppo_loss_config, act_dim), offsetof(dn_ppo_loss_config, reserved));
+    printf("%d %d\n", DN_ABI_VERSION, DN_PPO_MAX_ACT);
+    return 0;
+}
+'''
+    src, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
+    with open(src, "w") as f:
+        f.write(prog)
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
+    config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
+    assert config == [40, 0, 8, 16, 24, 32, 36] and consts == [9, 8]
+    K = pkg._capi.DnPpoLossConfig
+    assert [C.sizeof(K), K.clip_range.offset, K.clip_range_vf.offset, K.ent_coef.offset, K.vf_coef.offset, K.act_dim.offset, K.reserved.offset] == config
+    assert pkg._capi.PPO_MAX_ACT == 8
+
+
+def test_scratch_sizes(pkg):
+    """4 + act_dim float64 sums per block of 1024 rows."""
+    lib = pkg._capi.load()
+    for batch in (1, 2, 1024, 1025, 2048, 2049, 65536, (1 << 31) - 1):
+        for act_dim in range(1, 9):
+            assert lib.dn_ppo_loss_scratch_bytes(batch, act_dim) == 8 * (4 + act_dim) * -(-batch // P.BLOCK_ROWS), (batch, act_dim)
+    for batch in (0, -1, 1 << 31, 1 << 62):
+        assert lib.dn_ppo_loss_scratch_bytes(batch, 4) == INVALID, batch
+        assert b"batch must be in 1..2^31 - 1" in lib.dn_last_error()
+    for act_dim in (0, -1, 9, 1 << 30):
+        assert lib.dn_ppo_loss_scratch_bytes(100, act_dim) == INVALID, act_dim
+        assert b"act_dim must be in 1..8" in lib.dn_last_error()
+
+
+# ---- the refusals of dn_ppo_loss ----------------------------------------------------------------------------------------------------------
+CFG = dict(clip_range=0.2, clip_range_vf=0.2, ent_coef=0.01, vf_coef=0.5, act_dim=4, reserved=0)
+# dummy addresses 1 MiB apart: 100 rows of 4 columns are 1600 bytes, so nothing overlaps unless a case makes it
+PTRS = dict(mean=0x100000, log_std=0x200000, value=0x300000, actions=0x400000, old_log_prob=0x500000, advantages=0x600000, returns=0x700000,
+            old_values=0x800000, d_mean=0x900000, d_log_std=0xA00000, d_value=0xB00000, log_prob_out=0xC00000, loss=0xD00000, stats=0xE00000,
+            scratch=0xF00000)
+ORDER = tuple(PTRS)
+
+
+def _call(lib, K, *, cfg=CFG, batch=100, scratch_bytes=1 << 40, **kw):
+    c = None
+    if cfg is not None:
+        d = dict(cfg, **{k: kw.pop(k) for k in list(kw) if k in CFG})
+        c = C.byref(K.DnPpoLossConfig(d["clip_range"], d["clip_range_vf"], d["ent_coef"], d["vf_coef"], d["act_dim"], d["reserved"]))
+    p = dict(PTRS, **kw)
+    # device 2^20 does not exist: should a case ever pass validation, hipSetDevice refuses it (DN_ERR_HIP) and no kernel sees a dummy pointer
+    rc = lib.dn_ppo_loss(c, batch, *[p[k] for k in ORDER], scratch_bytes, 1 << 20, None)
+    return rc, lib.dn_last_error().decode()
+
+
+NO_VCLIP = dict(clip_range_vf=0.0, old_values=None)
+REFUSALS = [
+    ("null_cfg", dict(cfg=None), "cfg is required"),
+    ("act_dim_0", dict(act_dim=0), "act_dim must be in 1..8 (got 0)"),
+    ("act_dim_9", dict(act_dim=9), "act_dim must be in 1..8 (got 9)"),
+    ("reserved_1", dict(reserved=1), "reserved must be 0 (got 1)"),
+    ("batch_0", dict(batch=0), "batch must be in 1..2^31 - 1 (got 0)"),
+    ("batch_negative", dict(batch=-100), "batch must be in 1..2^31 - 1"),
+    ("batch_2_to_31", dict(batch=1 << 31), "batch must be in 1..2^31 - 1"),
+    ("clip_range_0", dict(clip_range=0.0), "clip_range must be finite and > 0"),
+    ("clip_range_negative", dict(clip_range=-0.2), "clip_range must be finite and > 0"),
+    ("clip_range_nan", dict(clip_range=math.nan), "clip_range must be finite and > 0"),
+    ("clip_range_inf", dict(clip_range=math.inf), "clip_range must be finite and > 0"),
+    ("clip_range_vf_nan", dict(clip_range_vf=math.nan), "clip_range_vf must be finite"),
+    ("clip_range_vf_inf", dict(clip_range_vf=math.inf), "clip_range_vf must be finite"),
+    ("ent_coef_negative", dict(ent_coef=-0.01), "ent_coef must be finite and >= 0"),
+    ("ent_coef_nan", dict(ent_coef=math.nan), "ent_coef must be finite and >= 0"),
+    ("ent_coef_inf", dict(ent_coef=math.inf), "ent_coef must be finite and >= 0"),
+    ("vf_coef_negative", dict(vf_coef=-0.5), "vf_coef must be finite and >= 0"),
+    ("vf_coef_nan", dict(vf_coef=math.nan), "vf_coef must be finite and >= 0"),
+    ("vf_coef_inf", dict(vf_coef=math.inf), "vf_coef must be finite and >= 0"),
+] + [("null_" + k, {k: None}, k + " is required") for k in ORDER if k not in ("old_values", "log_prob_out")] + [
+    ("old_values_missing_with_the_clip", dict(old_values=None), "old_values is required with clip_range_vf > 0"),
+    ("old_values_given_without_the_clip", dict(clip_range_vf=0.0), "old_values must be NULL without a value clip"),
+    ("old_values_given_with_a_negative_clip", dict(clip_range_vf=-1.0), "old_values must be NULL without a value clip"),
+    ("scratch_one_byte_short", dict(scratch_bytes="short"), "scratch_bytes is too small"),
+    ("scratch_0", dict(scratch_bytes=0), "scratch_bytes is too small"),
+    ("scratch_misaligned", dict(scratch=0xF00004), "stats and scratch must be 8-byte aligned"),
+    ("stats_misaligned", dict(stats=0xE00004), "stats and scratch must be 8-byte aligned"),
+    ("mean_misaligned", dict(mean=0x100002), "mean must be 4-byte aligned"),
+    ("d_value_misaligned", dict(d_value=0xB00001), "d_value must be 4-byte aligned"),
+    ("d_mean_is_mean", dict(d_mean=PTRS["mean"]), "d_mean overlaps mean"),
+    ("d_mean_ends_in_actions", dict(d_mean=PTRS["actions"] - 1596), "d_mean overlaps actions"),
+    ("d_value_is_value", dict(d_value=PTRS["value"]), "d_value overlaps value"),
+    ("d_value_in_advantages", dict(d_value=PTRS["advantages"] + 396), "d_value overlaps advantages"),
+    ("d_log_std_is_log_std", dict(d_log_std=PTRS["log_std"] + 12), "d_log_std overlaps log_std"),
+    ("log_prob_out_is_old_log_prob", dict(log_prob_out=PTRS["old_log_prob"]), "log_prob_out overlaps old_log_prob"),
+    ("loss_in_returns", dict(loss=PTRS["returns"] + 200), "loss overlaps returns"),
+    ("stats_in_old_values", dict(stats=PTRS["old_values"] + 336), "stats overlaps old_values"),
+    ("scratch_ends_in_mean", dict(scratch=PTRS["mean"] - 56), "scratch overlaps mean"),
+]
+
+
+@pytest.mark.parametrize("kw,message", [pytest.param(*r[1:], id=r[0]) for r in REFUSALS])
+def test_dn_ppo_loss_refuses(pkg, kw, message):
+    """Every case returns DN_ERR_INVALID_ARGUMENT with a text that names the argument, on dummy pointers: none gets as far as a device
+    call."""
+    K = pkg._capi
+    lib = K.load()
+    kw = dict(kw)
+    if kw.get("scratch_bytes") == "short":
+        kw["scratch_bytes"] = lib.dn_ppo_loss_scratch_bytes(100, 4) - 1
+    rc, msg = _call(lib, K, **kw)
+    assert rc == INVALID, msg
+    assert message in msg, msg
+
+
+def test_the_refusals_are_not_the_dummies_own(pkg):
+    """The unchanged dummy call -- also without the value clip, without log_prob_out, with zero coefficients, every act_dim, a batch of one
+    and the largest, the exact scratch size, and outputs that end where an input begins -- passes every check but one chosen here, the last
+    one validation makes: each refusal above is caused by what it changes.  (A batch of 2^31 - 1 rows passes too, but no set of dummy
+    addresses this file could name keeps 32 GB spans apart, so the size limit is test_scratch_sizes' to hold.)"""
+    K = pkg._capi
+    lib = K.load()
+    for kw in [dict(), NO_VCLIP, dict(NO_VCLIP, clip_range_vf=-1.0), dict(log_prob_out=None), dict(ent_coef=0.0, vf_coef=0.0), dict(batch=1),
+               dict(scratch_bytes=lib.dn_ppo_loss_scratch_bytes(100, 4)), dict(d_mean=PTRS["actions"] - 1600), dict(d_value=PTRS["advantages"] + 400),
+               dict(scratch=PTRS["mean"] - 64)] + [dict(act_dim=a) for a in range(1, 9)]:
+        rc, msg = _call(lib, K, **dict(kw, loss=PTRS["returns"]))
+        assert rc == INVALID and "loss overlaps returns" in msg, (kw, msg)
+
+
+# ---- the correctly rounded exp of exp(-log_std) ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_exp_cr_as_a_host_program(tmp_path, sanitize):
+    """tests/tools/check_exp_cr.cpp includes csrc/dn_exp_cr.h alone: built with the host compiler without contraction, as the library is,
+    plainly and under the address and undefined-behaviour sanitizers, and run as its own process.  Every value it prints -- 12 000
+    arguments over [-6, 6], half of them float32 values as -log_std is, powers of two down to 2^-52, the ends of the range -- is the
+    nearest double to exp(x) by 50-digit arithmetic; outside |x| <= 700 and for NaN it answers nothing and leaves the library's exp."""
+    import decimal
+    exe = str(tmp_path / "check_exp_cr")
+    src = os.path.join(ROOT, "tests", "tools", "check_exp_cr.cpp")
+    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-ffp-contract=off", "-I" + csrc] + flags + [src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = out.stdout.splitlines()
+    answered, refused = 0, []
+    with decimal.localcontext() as ctx:
+        ctx.prec = 50
+        for line in lines[:-1]:
+            xs, ys, ok = line.split()
+            x = float.fromhex(xs) if "0x" in xs else float(xs)
+            if ok == "0":
+                refused.append(x)
+                continue
+            answered += 1
+            assert float.fromhex(ys) == float(decimal.Decimal(x).exp()), (xs, ys)
+    assert answered > 12000 and lines[-1] == '{"answered": %d}' % answered
+    assert len(refused) == 8 and all(not abs(x) <= 700.0 for x in refused), refused
+
+
+# ---- the Python surface ---------------------------------------------------------------------------------------------------------------------
+def test_python_surface_refuses(pkg):
+    L = pkg.PpoLoss
+    with pytest.raises(RuntimeError, match="PpoLoss needs a GPU device, got cpu; there is no CPU path"):
+        L(256, 4, "cpu")
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        L(256, 8, torch.device("cpu"), clip_range=0.1, clip_range_vf=0.2, ent_coef=0.01, vf_coef=1.0)
+    for bad in (dict(batch_size=0), dict(batch_size=-1), dict(batch_size=2.0), dict(batch_size=True), dict(batch_size=1 << 31), dict(act_dim=0),
+                dict(act_dim=9), dict(act_dim=4.0)):
+        args = dict(dict(batch_size=256, act_dim=4), **bad)
+        with pytest.raises(ValueError, match="PpoLoss." + next(iter(bad))):
+            L(args["batch_size"], args["act_dim"], "cpu")
+    for kw in (dict(clip_range=0.0), dict(clip_range=-0.2), dict(clip_range=math.nan), dict(clip_range=math.inf), dict(clip_range_vf=0.0),
+               dict(clip_range_vf=-0.2), dict(clip_range_vf=math.nan), dict(clip_range_vf=math.inf), dict(ent_coef=-0.01), dict(ent_coef=math.nan),
+               dict(vf_coef=-0.5), dict(vf_coef=math.inf)):
+        with pytest.raises(ValueError, match="PpoLoss." + next(iter(kw)) + " must be"):
+            L(256, 4, "cpu", **kw)
+
+
+def test_python_call_refuses_its_tensors(pkg):
+    """The checks of a call need no device: they run on an object whose device is set by hand, before anything reaches the library."""
+    L = pkg.PpoLoss
+    ppo = L.__new__(L)
+    ppo.device, ppo.batch_size, ppo.act_dim, ppo.clip_range_vf = torch.device("cpu"), 8, 4, 0.2
+    z = torch.zeros
+    good = dict(mean=z(6, 4), log_std=z(4), values=z(6))
+    mb = dict(actions=z(6, 4), log_probs=z(6), advantages=z(6), returns=z(6), values=z(6))
+
+    def refuses(match, mb=mb, **kw):
+        a = dict(good, **kw)
+        with pytest.raises(ValueError, match=match):
+            ppo(a["mean"], a["log_std"], a["values"], mb)
+
+    refuses("mean must be a tensor", mean=None)
+    refuses("mean must be a tensor", mean=z(6))
+    refuses("mean has 9 rows; a call takes 1..8", mean=z(9, 4))
+    refuses("mean has 0 rows", mean=z(0, 4))
+    refuses("mean must be torch.float32 \\[6, 4\\]", mean=z(6, 3))
+    refuses("mean must be torch.float32", mean=z(6, 4, dtype=torch.float64))
+    refuses("mean must be dense", mean=z(6, 8)[:, :4])
+    refuses("log_std must be torch.float32 \\[4\\]", log_std=z(6, 4))
+    refuses("log_std must be dense", log_std=z(8)[::2])
+    refuses("log_std must be a tensor", log_std=[0.0] * 4)
+    refuses("values must be torch.float32 \\[6\\]", values=z(6, 1))
+    refuses("values must be dense", values=z(12)[::2])
+    refuses("mb\\['actions'\\] must be torch.float32 \\[6, 4\\]", mb=dict(mb, actions=z(6, 3)))
+    refuses("mb\\['log_probs'\\] must be torch.float32 \\[6\\]", mb=dict(mb, log_probs=z(7)))
+    refuses("mb\\['advantages'\\] must be torch.float32", mb=dict(mb, advantages=z(6, dtype=torch.float16)))
+    refuses("mb\\['returns'\\] must be dense", mb=dict(mb, returns=z(12)[::2]))
+    refuses("mb\\['values'\\] is missing", mb={k: v for k, v in mb.items() if k != "values"})
+    refuses("mb\\['actions'\\] is missing", mb=None)
+    if torch.cuda.is_available():
+        refuses("mean must be torch.float32 \\[6, 4\\] on cpu", mean=z(6, 4, device="cuda"))
+
+
+# ---- the reference ------------------------------------------------------------------------------------------------------------------------
+ISSUE_BATCHES, ISSUE_ACT_DIMS = (1, 2, 65, 1025, 2049, 65536), (1, 4, 8)
+VARIANTS = [(vc, co) for vc in (False, True) for co in P.COEFS]
+
+
+@pytest.mark.parametrize("spread", list(P.SPREADS))
+@pytest.mark.parametrize("batch", ISSUE_BATCHES)
+def test_reference_is_the_closed_forms(batch, spread):
+    """torch's float64 autograd on the composition against the hand-derived forms of the header in NumPy: two float64 evaluations of the
+    same expressions, which differ in the order of their sums and the last bits of exp.  Outputs held to a float32 ulp must agree to 1e-4
+    of that tolerance (2^-53 against 2^-24 leaves five orders of magnitude).  The float64 statistics: NumPy's pairwise sum is within about
+    log2(B) 2^-53 <= 2^-49 of the mean absolute term of the reference's exactly rounded one, and the two exp differ by a few 2^-53 of
+    their value: a quarter of the 2^-40 of the tolerance leaves two orders of magnitude over both.  Both take the ratio from the same correctly rounded
+    exp (ppo_loss_support.exp_correctly_rounded): what is compared is the forms, not two exp routines."""
+    worst = {}
+    for act_dim in ISSUE_ACT_DIMS:
+        d = P.data(batch, act_dim, spread)
+        for value_clip, (ent_coef, vf_coef) in VARIANTS:
+            kw = dict(clip_range_vf=P.CLIP_RANGE_VF if value_clip else None, ent_coef=ent_coef, vf_coef=vf_coef)
+            ref, forms = P.reference(d, **kw), P.closed_forms(d, **kw)
+            tol = P.tolerances(ref)
+            for k, t in tol.items():
+                dist, same = P.distance(forms[k], ref[k], t)
+                bar = 0.25 if k == "stats" else 1e-4
+                assert same and dist <= bar, (batch, act_dim, spread, value_clip, k, dist)
+                worst[k] = max(worst.get(k, 0.0), dist)
+            assert abs(ref["torch_loss"] - ref["loss"]) <= tol["stats"][0], "torch's own sum of the loss against the exactly rounded one"
+    print(f"B {batch}, {spread}: closed forms from autograd, in units of the tolerance: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("spread", list(P.SPREADS))
+def test_reference_covers_both_branches_and_is_stable_under_the_order_of_its_sums(spread):
+    """At every shape of the GPU test: the clip fraction and the share of rows inside the value clip lie strictly inside (0.05, 0.95) and
+    (0.2, 0.8) from 63 rows on (a batch of one or two cannot promise either), and the reference with its rows reversed stays within 1e-5
+    of its own tolerances."""
+    worst = 0.0
+    for batch in P.BATCHES:
+        for act_dim in P.ACT_DIMS:
+            for value_clip, coefs in VARIANTS:
+                if batch >= P.COVERED_FROM:
+                    ref = P.reference(P.data(batch, act_dim, spread), clip_range_vf=P.CLIP_RANGE_VF if value_clip else None)
+                    P.check_coverage(ref, spread, value_clip, (batch, act_dim, spread))
+                worst = max(worst, P.check_order_stability(batch, act_dim, spread, value_clip, coefs))
+    print(f"{spread}: the two orders differ by at most {worst:.2e} of the tolerance")
+
+
+def test_reference_edge_values():
+    """All advantages zero: policy gradients of value 0 and a finite loss.  One NaN advantage: NaN in loss, policy_loss, d_log_std and the
+    d_mean of its own row only; the other statistics, d_value and every other row stay finite.  The closed forms say the same."""
+    d = {k: v.copy() for k, v in P.data(65, 4, "near").items()}
+    d["advantages"][:] = 0.0
+    for got in (P.reference(d, ent_coef=0.0, vf_coef=0.5), P.closed_forms(d, ent_coef=0.0, vf_coef=0.5)):
+        assert (got["d_mean"] == 0.0).all() and (got["d_log_std"] == 0.0).all() and math.isfinite(got["loss"]) and got["stats"][1] == 0.0
+    d = {k: v.copy() for k, v in P.data(65, 4, "near").items()}
+    d["advantages"][17] = np.nan
+    for got in (P.reference(d, clip_range_vf=0.2), P.closed_forms(d, clip_range_vf=0.2)):
+        assert np.isnan(got["stats"][:2]).all() and np.isfinite(got["stats"][2:]).all() and np.isnan(got["loss"])
+        assert np.isnan(got["d_log_std"]).all() and np.isfinite(got["d_value"]).all() and np.isfinite(got["log_probs"]).all()
+        bad = np.isnan(got["d_mean"])
+        assert bad[17].all() and not np.delete(bad, 17, axis=0).any()
