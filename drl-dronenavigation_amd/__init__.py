@@ -23,7 +23,7 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
            "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer",
-           "ReturnNormalizer", "MinibatchSampler", "PpoLoss"]
+           "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam"]
 
 
 def __getattr__(name):
@@ -51,6 +51,9 @@ def __getattr__(name):
     if name in ("ppo", "PpoLoss"):
         ppo = importlib.import_module(__name__ + ".ppo")
         return ppo if name == "ppo" else ppo.PpoLoss
+    if name in ("optim", "ClippedAdam"):
+        optim = importlib.import_module(__name__ + ".optim")
+        return optim if name == "optim" else optim.ClippedAdam
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
     if name in ("policy", "MlpActorCritic", "SacActor", "MlpValue"):

@@ -125,6 +125,19 @@ class DnPpoLossConfig(C.Structure):
 PPO_MAX_ACT = 8
 
 
+class DnAdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("count", C.c_int64)]
+
+
+class DnAdamConfig(C.Structure):
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_grad_norm", C.c_double),
+                ("n_tensors", C.c_int32), ("flags", C.c_int32)]
+
+
+ADAM_MAX_TENSORS = 32
+ADAM_ZERO_GRADS = 1
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -182,6 +195,8 @@ PROTOTYPES = {
                             _VP]),
     "dn_ppo_loss_scratch_bytes": (_I64, [_I64, _I32]),
     "dn_ppo_loss": (_I32, [C.POINTER(DnPpoLossConfig), _I64] + [_VP] * 15 + [_I64, _I32, _VP]),
+    "dn_adam_scratch_bytes": (_I64, [C.POINTER(C.c_int64), _I32]),
+    "dn_adam_step": (_I32, [C.POINTER(DnAdamConfig), C.POINTER(DnAdamTensor), _VP, _VP, _VP, _VP, _I64, _I32, _VP]),
     "dn_set_launch_events": (_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

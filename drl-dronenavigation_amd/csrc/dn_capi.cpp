@@ -1912,4 +1912,67 @@ int32_t dn_ppo_loss(const dn_ppo_loss_config *cfg, int64_t batch, const float *m
     return DN_OK;
 }
 
+// ---- dn_adam_step: SB3 PPO.train's clip_grad_norm_ + Adam.step [from recall] ---------------------------------------------------------------
+int64_t dn_adam_scratch_bytes(const int64_t *counts, int32_t n_tensors)
+{
+    if (!counts) return fail(DN_ERR_INVALID_ARGUMENT, "counts is required");
+    if (n_tensors < 1 || n_tensors > DN_ADAM_MAX_TENSORS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "n_tensors must be in 1..%d (got %d)", DN_ADAM_MAX_TENSORS, n_tensors);
+    long long chunks = 0;                              // at most 32 x 2^53: no overflow
+    for (int i = 0; i < n_tensors; ++i) {
+        if (counts[i] < 1) return fail(DN_ERR_INVALID_ARGUMENT, "counts[%d] must be >= 1 (got %lld)", i, (long long)counts[i]);
+        chunks += dn_adam_chunks(counts[i]);
+    }
+    if (chunks > 0x7fffffffll)
+        return fail(DN_ERR_INVALID_ARGUMENT, "the counts make %lld chunks of %d elements; a call takes at most 2^31 - 1", chunks, DN_ADAM_CHUNK);
+    return chunks * 8;
+}
+
+int32_t dn_adam_step(const dn_adam_config *cfg, const dn_adam_tensor *tensors, const double *lr, double *state, double *stats,
+                     void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (!tensors) return fail(DN_ERR_INVALID_ARGUMENT, "tensors is required");
+    const struct { const char *name; const void *p; } doubles[] = {{"lr", lr}, {"state", state}, {"stats", stats}, {"scratch", scratch}};
+    for (const auto &d : doubles)
+        if (!d.p) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", d.name);
+    if (cfg->n_tensors < 1 || cfg->n_tensors > DN_ADAM_MAX_TENSORS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "n_tensors must be in 1..%d (got %d)", DN_ADAM_MAX_TENSORS, cfg->n_tensors);
+    if (cfg->flags & ~DN_ADAM_ZERO_GRADS) return fail(DN_ERR_INVALID_ARGUMENT, "flags has unknown bits: 0x%x (bit 0 zeroes the gradients)", cfg->flags);
+    if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0)) return fail(DN_ERR_INVALID_ARGUMENT, "beta1 must be in [0, 1) (got %g)", cfg->beta1);
+    if (!(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0)) return fail(DN_ERR_INVALID_ARGUMENT, "beta2 must be in [0, 1) (got %g)", cfg->beta2);
+    if (!std::isfinite(cfg->eps) || !(cfg->eps >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "eps must be finite and >= 0 (got %g)", cfg->eps);
+    if (!std::isfinite(cfg->max_grad_norm))
+        return fail(DN_ERR_INVALID_ARGUMENT, "max_grad_norm must be finite: > 0 clips the global norm, <= 0 does not (got %g)", cfg->max_grad_norm);
+    int64_t counts[DN_ADAM_MAX_TENSORS];
+    for (int i = 0; i < cfg->n_tensors; ++i) {
+        const dn_adam_tensor &t = tensors[i];
+        const struct { const char *name; const void *p; } fields[] = {{"param", t.param}, {"grad", t.grad}, {"exp_avg", t.exp_avg},
+                                                                      {"exp_avg_sq", t.exp_avg_sq}};
+        for (const auto &f : fields) {
+            if (!f.p) return fail(DN_ERR_INVALID_ARGUMENT, "tensors[%d].%s is required", i, f.name);
+            if ((uintptr_t)f.p & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "tensors[%d].%s must be 4-byte aligned", i, f.name);
+        }
+        if (t.count < 1) return fail(DN_ERR_INVALID_ARGUMENT, "tensors[%d].count must be >= 1 (got %lld)", i, (long long)t.count);
+        counts[i] = t.count;
+    }
+    const int64_t need = dn_adam_scratch_bytes(counts, cfg->n_tensors);
+    if (need < 0) return (int32_t)need;                // more than 2^31 - 1 chunks: the text is dn_adam_scratch_bytes'
+    if (scratch_bytes < need)
+        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_adam_scratch_bytes gives %lld", (long long)scratch_bytes,
+                    (long long)need);
+    for (const auto &d : doubles)
+        if ((uintptr_t)d.p & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 8-byte aligned", d.name);
+    DnAdamArgs a;
+    std::memset(&a, 0, sizeof a);
+    for (int i = 0; i < cfg->n_tensors; ++i) a.t[i] = tensors[i];
+    a.lr = lr; a.state = state; a.stats = stats; a.part = (double *)scratch;
+    a.beta1 = cfg->beta1; a.beta2 = cfg->beta2; a.eps = cfg->eps; a.max_grad_norm = cfg->max_grad_norm;
+    a.nchunks = need / 8;
+    a.n_tensors = cfg->n_tensors; a.flags = cfg->flags;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_adam(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
 }  // extern "C"

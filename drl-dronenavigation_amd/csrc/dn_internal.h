@@ -382,6 +382,22 @@ inline long long dn_ppo_loss_scratch_doubles(long long batch, int act_dim)
     return act_dim < 1 || act_dim > DN_PPO_MAX_ACT || batch < 1 || batch > 0x7fffffffll ? 0 : dn_rownorm_blocks(batch) * (4 + act_dim);
 }
 hipError_t dn_launch_ppo_loss(const DnPpoLossArgs &a, hipStream_t stream);                                                     // dn_ppo_loss.hip
+// The PPO optimiser step (dn_adam_step, dn_adam.hip): the global gradient norm, SB3's clip and Adam over up to DN_ADAM_MAX_TENSORS
+// tensors.  Each tensor is cut into chunks of DN_ADAM_CHUNK consecutive elements (its last chunk is short: no chunk straddles two
+// tensors), numbered tensor by tensor; a chunk is one workgroup.  The tensor table travels by value as a kernel argument.  The scratch is
+// doubles only:
+//   part   [chunks]   the chunk's float64 sum of g * g
+// so the order of every float64 operation depends on the tensor counts alone.
+struct DnAdamArgs {
+    dn_adam_tensor t[DN_ADAM_MAX_TENSORS];
+    const double *lr;                                  // device [1]
+    double *state, *stats, *part;                      // device {step, c1, c2, 0}, {total, coef, lr, step'}, [nchunks]
+    double beta1, beta2, eps, max_grad_norm;
+    long long nchunks;                                 // sum over the tensors of dn_adam_chunks(count), <= 2^31 - 1: the grid of a launch
+    int n_tensors, flags;                              // flags bit 0: zero the gradients after they are read
+};
+inline long long dn_adam_chunks(long long count) { return count < 1 ? 0 : (count - 1) / DN_ADAM_CHUNK + 1; }
+hipError_t dn_launch_adam(const DnAdamArgs &a, hipStream_t stream);                                                            // dn_adam.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

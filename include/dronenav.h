@@ -964,6 +964,65 @@ int32_t dn_ppo_loss(const dn_ppo_loss_config *cfg, int64_t batch, const float *m
                     const float *old_values, float *d_mean, float *d_log_std, float *d_value, float *log_prob_out, float *loss,
                     double *stats, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
 
+/* The PPO optimiser step on the device: what SB3's PPO.train [from recall] puts between loss.backward() and the next minibatch --
+ * torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) and torch.optim.Adam(eps=1e-5).step() -- over n_tensors <= 32 tensors in one
+ * call.  Env-free; the networks' backward and the learner loop stay the caller's.
+ * Inputs: `tensors`, a HOST array of n_tensors entries, each four device pointers to `count` dense float32 -- the parameter, its
+ *   gradient and the two moments exp_avg (m) and exp_avg_sq (v); `lr`, one device float64, read by the kernel, so a schedule or a replayed
+ *   graph changes the rate by writing it; `state`, device float64 [4] = {step, c1, c2, 0}, initially {0, 1, 1, 0}: c1 = beta1^step and
+ *   c2 = beta2^step as running products, so no pow is taken.  beta1, beta2 in [0, 1), eps >= 0 and max_grad_norm, finite, are host
+ *   arguments: a captured graph keeps the values it was captured with.
+ * Arithmetic: every input is widened to float64 once; everything below is an IEEE float64 basic operation (true division and square
+ *   root, no reciprocal shortcuts, no contraction); every output is rounded once.
+ *   total = sqrt(sum over all elements of all tensors of g g)           the order of the sum is fixed, see below
+ *   c = max_grad_norm / (total + 1e-6);  coef = c > 1 ? 1 : c            clip_grad_norm_; a NaN stays a NaN
+ *                                                                        max_grad_norm <= 0 is SB3's None: coef = 1
+ *   step' = step + 1;  c1' = c1 beta1;  c2' = c2 beta2;  bc1 = 1 - c1';  bc2 = 1 - c2'
+ *   gs = g coef
+ *   m' = m + (gs - m) (1 - beta1)                                        torch's lerp_
+ *   v' = v beta2 + (1 - beta2) gs gs
+ *   p' = p - (lr / bc1) (m' / (sqrt(v') / sqrt(bc2) + eps))              from the unrounded m', v'
+ *   NaN and infinity are not special-cased: one NaN gradient makes total, coef and with them every parameter NaN, as in torch.  No
+ *   weight decay, amsgrad or maximize, one parameter group, and a non-finite step is not skipped.
+ * Outputs: float32 p', m', v' in place; float64 state <- {step', c1', c2', 0}; float64 stats[4] <- {total, coef, lr, step'}.  The scaled
+ *   gradients are not written back.  With flags bit 0 every gradient is zeroed after it is read (zero_grad(set_to_none=False)); the other
+ *   bits must be 0.  Overlap between tensors, or of a tensor with lr, state, stats or scratch, is the caller's business: it is not checked.
+ * Bit-reproducible: each tensor is cut into chunks of DN_ADAM_CHUNK consecutive elements (the last chunk of a tensor is short; no chunk
+ *   straddles two tensors), numbered tensor by tensor.  A chunk's sum of g g: each of 256 lanes adds its four consecutive elements in
+ *   ascending order, the 64 lanes of a wave by a fixed tree, the four waves ascending.  The chunk sums: lane l of one wave adds sums l,
+ *   l + 64, ... ascending, then the same tree.  The order of every float64 operation is a function of the tensor counts alone; a tensor
+ *   whose four pointers are 16-byte aligned moves as 16-byte words, any other as 4-byte words, with the same bits.
+ *   scratch        the caller's device memory, 8-byte aligned, at least dn_adam_scratch_bytes(counts, n_tensors): the chunk sums.  The
+ *                  library allocates nothing and keeps nothing between calls.
+ * Two ordinary launches on `stream`: chunk sums + the state's advance, the update.  No workgroup waits for another, no atomics,
+ *   capturable: the pointers of the table are captured with it, so the gradients must be the same tensors at replay.
+ * Validates before the first device call: DN_ERR_INVALID_ARGUMENT with a dn_last_error text that names the argument.
+ * Layouts: dn_adam_tensor param at 0, grad at 8, exp_avg at 16, exp_avg_sq at 24, count at 32; 40 bytes.  dn_adam_config beta1 at 0,
+ *   beta2 at 8, eps at 16, max_grad_norm at 24, n_tensors at 32, flags at 36; 40 bytes. */
+#define DN_ADAM_MAX_TENSORS 32
+#define DN_ADAM_CHUNK 1024
+#define DN_ADAM_ZERO_GRADS 1
+typedef struct dn_adam_tensor {
+    float *param;           /* device, count float32, 4-byte aligned; updated in place */
+    float *grad;            /* read; zeroed with DN_ADAM_ZERO_GRADS */
+    float *exp_avg;         /* m, updated in place */
+    float *exp_avg_sq;      /* v, updated in place */
+    int64_t count;          /* >= 1 */
+} dn_adam_tensor;
+typedef struct dn_adam_config {
+    double beta1, beta2;    /* in [0, 1); SB3's 0.9, 0.999 */
+    double eps;             /* >= 0, finite; SB3's 1e-5 */
+    double max_grad_norm;   /* finite; > 0: clip the global norm; <= 0: no clip (SB3's None) */
+    int32_t n_tensors;      /* 1..32 */
+    int32_t flags;          /* bit 0 = DN_ADAM_ZERO_GRADS */
+} dn_adam_config;
+/* Bytes of scratch for tensors of these element counts (a host array): 8 * sum ceil(count / DN_ADAM_CHUNK); a negative dn_status for a
+ * NULL list, n_tensors outside 1..32, a count below 1, or more than 2^31 - 1 chunks. */
+int64_t dn_adam_scratch_bytes(const int64_t *counts, int32_t n_tensors);
+/* clip_grad_norm_ + Adam.step [from recall] over the tensors of the table, on the device. */
+int32_t dn_adam_step(const dn_adam_config *cfg, const dn_adam_tensor *tensors, const double *lr, double *state, double *stats,
+                     void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ import sys
 import tempfile
 
 OBJECTS = ["dn_kernels.o", "dn_kernels.exact.o", "dn_kernels_mw.o", "dn_kernels_mw.exact.o", "dn_fused.o", "dn_fused.exact.o", "dn_mlp.o",
-           "dn_mlp_wide.o", "dn_history.o", "dn_rownorm.o", "dn_retnorm.o", "dn_minibatch.o"]
+           "dn_mlp_wide.o", "dn_history.o", "dn_rownorm.o", "dn_retnorm.o", "dn_minibatch.o", "dn_ppo_loss.o"]
 
 
 def tool(name):
