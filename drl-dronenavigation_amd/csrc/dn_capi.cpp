@@ -3,8 +3,9 @@
 // Owns the device arena, the waypoint/corridor tables and the launch parameters; every entry point
 // validates its arguments, turns HIP failures into dn_status codes + a thread-local message, and
 // never falls back to a CPU implementation.
+#include "dn_argcheck.h"
+#include "dn_capi_fail.h"
 #include "dn_internal.h"
-#include "dn_permute.h"
 #include "dn_shapes.h"
 
 #include <cmath>
@@ -20,6 +21,8 @@ namespace {
 
 thread_local char g_err[512] = "";
 
+}  // namespace
+
 int32_t fail(dn_status st, const char *fmt, ...)
 {
     va_list ap;
@@ -29,13 +32,7 @@ int32_t fail(dn_status st, const char *fmt, ...)
     return (int32_t)st;
 }
 
-#define DN_HIP(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(e_ == hipErrorOutOfMemory ? DN_ERR_OUT_OF_MEMORY : DN_ERR_HIP, "%s failed: %s", #expr, \
-                        hipGetErrorString(e_));                                                   \
-    } while (0)
+namespace {
 
 inline double norm3d(const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 
@@ -727,13 +724,12 @@ int32_t dn_mlp_step_sampled(dn_env *env, const dn_mlp_net *nets, int32_t num_net
     if (nets[0].out_dim != DN_ACT_DIM) return fail(DN_ERR_INVALID_ARGUMENT, "nets[0] must be the actor (out_dim 4)");
     {   // one launch: the critic's workgroups and later actor workgroups still READ policy_obs while earlier actor tails already WRITE obs
         // and the networks' outputs -- overlapping buffers would be a silent data race, so they are refused
-        const long long nn = c.num_envs;
-        const uintptr_t pb = (uintptr_t)policy_obs, pe = pb + (uintptr_t)nn * obs_dim * sizeof(float);
-        const uintptr_t ob = (uintptr_t)obs, oe = ob + (uintptr_t)nn * DN_OBS_DIM * sizeof(float);
-        if (pb < oe && ob < pe) return fail(DN_ERR_INVALID_ARGUMENT, "policy_obs must not overlap obs (the launch reads one while it writes the other)");
+        const uintptr_t nn = (uintptr_t)c.num_envs, pbytes = nn * obs_dim * sizeof(float), obytes = nn * DN_OBS_DIM * sizeof(float);
+        if (dn_ranges_overlap(policy_obs, pbytes, obs, obytes))
+            return fail(DN_ERR_INVALID_ARGUMENT, "policy_obs must not overlap obs (the launch reads one while it writes the other)");
         for (int k = 0; k < num_nets; ++k) {
-            const uintptr_t nb = (uintptr_t)nets[k].out, ne = nb + (uintptr_t)nn * nets[k].out_dim * sizeof(float);
-            if ((nb < pe && pb < ne) || (nb < oe && ob < ne))
+            const uintptr_t nbytes = nn * nets[k].out_dim * sizeof(float);
+            if (dn_ranges_overlap(nets[k].out, nbytes, policy_obs, pbytes) || dn_ranges_overlap(nets[k].out, nbytes, obs, obytes))
                 return fail(DN_ERR_INVALID_ARGUMENT, "net %d: out must not overlap policy_obs or obs", k);
         }
     }
@@ -807,39 +803,6 @@ int32_t dn_set_launch_events(dn_env *env, void *start_event, void *stop_event)
     if (!env) return fail(DN_ERR_INVALID_ARGUMENT, "env is NULL");
     env->ev_start = (hipEvent_t)start_event;
     env->ev_stop = (hipEvent_t)stop_event;
-    return DN_OK;
-}
-
-int32_t dn_compact_done(const uint64_t *done_mask, int64_t num_envs, int32_t *indices, int32_t *count,
-                        int32_t device_id, void *stream)
-{
-    if (!done_mask || !indices || !count || num_envs < 1)
-        return fail(DN_ERR_INVALID_ARGUMENT, "done_mask, indices, count are required and num_envs >= 1");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_compact((const unsigned long long *)done_mask, num_envs, indices, count, (hipStream_t)stream));
-    return DN_OK;
-}
-
-int32_t dn_pack_done(const uint64_t *done_mask, int64_t num_envs, const float *terminal_obs, const float *ep_return, const int32_t *ep_length,
-                     const uint8_t *truncated, const int32_t *found_targets, int32_t *indices, int32_t *count, float *packed,
-                     int32_t device_id, void *stream)
-{
-    if (!done_mask || !terminal_obs || !ep_return || !ep_length || !truncated || !found_targets || !indices || !count || !packed || num_envs < 1)
-        return fail(DN_ERR_INVALID_ARGUMENT, "every pointer is required and num_envs >= 1");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_compact_pack((const unsigned long long *)done_mask, num_envs, terminal_obs, ep_return, ep_length, truncated, found_targets,
-                                  indices, count, packed, (hipStream_t)stream));
-    return DN_OK;
-}
-
-int32_t dn_stream_copy(void *dst, const void *src, int64_t bytes, int32_t device_id, void *stream)
-{
-    if (!dst || !src || bytes < 16 || (bytes & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15))
-        return fail(DN_ERR_INVALID_ARGUMENT, "dst, src: 16-byte aligned device pointers; bytes: a positive multiple of 16");
-    DN_HIP(hipSetDevice(device_id));
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || cus < 1) cus = 256;
-    DN_HIP(dn_launch_stream_copy(dst, src, bytes / 16, cus, (hipStream_t)stream));
     return DN_OK;
 }
 
@@ -1506,18 +1469,6 @@ int32_t dn_set_step_count(dn_env *env, uint64_t value)
     return DN_OK;
 }
 
-int32_t dn_preprocess_action(const float *actions, int64_t num_envs, int32_t normalize_actions, float *rpm, float *forces,
-                             float *z_torque, int32_t device_id, void *stream)
-{
-    if (!actions || num_envs < 1) return fail(DN_ERR_INVALID_ARGUMENT, "actions is required and num_envs >= 1");
-    if (!rpm && !forces && !z_torque) return fail(DN_ERR_INVALID_ARGUMENT, "at least one output buffer is required");
-    if (((uintptr_t)actions & 15u) || ((uintptr_t)rpm & 15u) || ((uintptr_t)forces & 15u))
-        return fail(DN_ERR_INVALID_ARGUMENT, "actions, rpm and forces must be 16-byte aligned");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_action_chain(actions, num_envs, normalize_actions, rpm, forces, z_torque, (hipStream_t)stream));
-    return DN_OK;
-}
-
 int32_t dn_policy_sample(dn_env *env, const float *mean, const float *log_std, uint64_t seed, int32_t deterministic, float *actions,
                          float *clipped, float *log_prob, void *stream)
 {
@@ -1536,442 +1487,6 @@ int32_t dn_squashed_sample(dn_env *env, const float *mu_log_std, uint64_t seed, 
     if (((uintptr_t)mu_log_std | (uintptr_t)actions) & 15u)
         return fail(DN_ERR_INVALID_ARGUMENT, "mu_log_std and actions must be 16-byte aligned");
     DN_HIP(dn_launch_squashed_sample(env->p, mu_log_std, seed, deterministic, actions, log_prob, (hipStream_t)stream));
-    return DN_OK;
-}
-
-int32_t dn_add_bootstrap(float *reward, const float *terminal_value, const uint8_t *truncated, double gamma, int64_t num_envs,
-                         int32_t device_id, void *stream)
-{
-    if (!reward || !terminal_value || !truncated || num_envs < 1)
-        return fail(DN_ERR_INVALID_ARGUMENT, "reward, terminal_value, truncated are required and num_envs >= 1");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_add_bootstrap(reward, terminal_value, truncated, (float)gamma, num_envs, (hipStream_t)stream));
-    return DN_OK;
-}
-
-int32_t dn_mlp_forward(const dn_mlp_net *nets, int32_t num_nets, const float *obs, const uint8_t *row_mask, int64_t num_envs,
-                       int32_t obs_dim, int32_t device_id, void *stream)
-{
-    if (!nets || !obs) return fail(DN_ERR_INVALID_ARGUMENT, "nets and obs are required");
-    if (num_nets < 1 || num_nets > 2) return fail(DN_ERR_INVALID_ARGUMENT, "num_nets must be 1 or 2 (got %d)", num_nets);
-    if (num_envs < 1) return fail(DN_ERR_INVALID_ARGUMENT, "num_envs must be >= 1");
-    for (int k = 0; k < num_nets; ++k) {
-        const dn_mlp_net &n = nets[k];
-        if (n.arch != DN_MLP_ARCH_PPO && n.arch != DN_MLP_ARCH_SAC)
-            return fail(DN_ERR_INVALID_ARGUMENT, "net %d: arch must be 0 (PPO 512-512-256 Tanh) or 1 (SAC actor 256-256 ReLU)", k);
-        // rows of up to 64 columns for the PPO networks (dn_mlp_wide.hip beyond 16), of up to 16 for the SAC actor
-        if (n.arch == DN_MLP_ARCH_PPO ? dn_mlp_ks1(obs_dim) == 0 : dn_mlp_ks1(obs_dim) != 1)
-            return fail(DN_ERR_INVALID_ARGUMENT, "obs_dim must be in 1..%d for %s (got %d)", n.arch == DN_MLP_ARCH_PPO ? 64 : 16,
-                        n.arch == DN_MLP_ARCH_PPO ? "the PPO networks" : "the SAC actor", obs_dim);
-        const bool three = n.arch == DN_MLP_ARCH_PPO;
-        if (!n.w1 || !n.w2 || (three && !n.w3) || !n.wh || !n.b1 || !n.b2 || (three && !n.b3) || !n.bh || !n.out)
-            return fail(DN_ERR_INVALID_ARGUMENT, "net %d: every weight, bias and output pointer is required", k);
-        if (n.out_dim < 1 || n.out_dim > 32) return fail(DN_ERR_INVALID_ARGUMENT, "net %d: out_dim must be in 1..32", k);
-        if (n.grade < 0 || n.grade > 2) return fail(DN_ERR_INVALID_ARGUMENT, "net %d: grade must be 0 (bf16), 1 (fp32 grade) or 2 (fp16)", k);
-        if (n.grade != nets[0].grade || n.arch != nets[0].arch)
-            return fail(DN_ERR_INVALID_ARGUMENT, "all networks of one call must share grade and arch");
-        if (((uintptr_t)n.w1 | (uintptr_t)n.w2 | (three ? (uintptr_t)n.w3 : 0) | (uintptr_t)n.wh) & 15u)
-            return fail(DN_ERR_INVALID_ARGUMENT, "net %d: packed weights must be 16-byte aligned", k);
-    }
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_mlp(nets, num_nets, obs, row_mask, num_envs, obs_dim, (hipStream_t)stream));
-    return DN_OK;
-}
-
-int32_t dn_gae(const float *rewards, const float *values, const uint8_t *dones, const float *last_values,
-               const uint8_t *last_dones, int64_t n_steps, int64_t n_envs, double gamma, double gae_lambda,
-               float *advantages, float *returns, int32_t device_id, void *stream)
-{
-    if (!rewards || !values || !dones || !last_values || !last_dones || !advantages || !returns)
-        return fail(DN_ERR_INVALID_ARGUMENT, "all buffers are required");
-    if (n_steps < 1 || n_envs < 1) return fail(DN_ERR_INVALID_ARGUMENT, "n_steps and n_envs must be >= 1");
-    DN_HIP(hipSetDevice(device_id));
-    // gamma and gamma*gae_lambda are Python floats multiplied into float32 tensors (cleanRLPPO.py:245-246)
-    DN_HIP(dn_launch_gae(rewards, values, dones, last_values, last_dones, n_steps, n_envs, (float)gamma,
-                         (float)(gamma * gae_lambda), advantages, returns, (hipStream_t)stream));
-    return DN_OK;
-}
-
-int32_t dn_history_width(const dn_history_config *cfg)
-{
-    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "dn_history_config.reserved must be 0 (got %d)", cfg->reserved);
-    if (cfg->frames < 1 || cfg->frames > 4) return fail(DN_ERR_INVALID_ARGUMENT, "frames must be in 1..4 (got %d)", cfg->frames);
-    if (cfg->actions < 0 || cfg->actions > 4) return fail(DN_ERR_INVALID_ARGUMENT, "actions must be in 0..4 (got %d)", cfg->actions);
-    if (cfg->extra_dim < 0) return fail(DN_ERR_INVALID_ARGUMENT, "extra_dim must be >= 0 (got %d)", cfg->extra_dim);
-    const int w = dn_history_row_width(cfg->frames, cfg->actions, cfg->extra_dim);
-    if (w == 0)
-        return fail(DN_ERR_INVALID_ARGUMENT, "the row of 13 x %d + 4 x %d + %d columns is wider than 64, the policy kernels' limit", cfg->frames,
-                    cfg->actions, cfg->extra_dim);
-    return w;
-}
-
-int32_t dn_stack_history(const dn_history_config *cfg, int64_t k, int64_t n, const float *prev, const float *obs, const float *actions,
-                         const uint8_t *done, const float *terminal_obs, const float *extra, const float *terminal_extra, float *rows,
-                         float *terminal_rows, int32_t device_id, void *stream)
-{
-    const int32_t w = dn_history_width(cfg);
-    if (w < 0) return w;
-    if (k < 1 || n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 (got %lld, %lld)", (long long)k, (long long)n);
-    if (k > 1 && n % 4) return fail(DN_ERR_INVALID_ARGUMENT, "n must be a multiple of 4 for k > 1, as for dn_step_many (got %lld)", (long long)n);
-    if (!obs || !rows) return fail(DN_ERR_INVALID_ARGUMENT, "obs and rows are required");
-    if (((uintptr_t)rows | (uintptr_t)terminal_rows | (uintptr_t)prev) & 15u)
-        return fail(DN_ERR_INVALID_ARGUMENT, "prev, rows and terminal_rows must be 16-byte aligned");
-    if (terminal_rows && !terminal_obs) return fail(DN_ERR_INVALID_ARGUMENT, "terminal_rows needs terminal_obs");
-    if (done && !actions)
-        return fail(DN_ERR_INVALID_ARGUMENT, "done needs actions (actions = NULL is the reset call, in which no episode ends)");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_history(cfg->frames, cfg->actions, cfg->extra_dim, k, n, prev, obs, actions, done, terminal_obs, extra, terminal_extra,
-                             rows, terminal_rows, (hipStream_t)stream));
-    return DN_OK;
-}
-
-// ---- dn_rownorm: one RunningMeanStd over the fleet per row kind (Sol/Model/Environments/normalize.py:10-47) ---------------------------
-static int32_t rownorm_config_ok(const dn_rownorm_config *cfg)
-{
-    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
-    if (cfg->width < 1 || cfg->width > DN_ROWNORM_MAX_WIDTH)
-        return fail(DN_ERR_INVALID_ARGUMENT, "width must be in 1..%d (got %d)", DN_ROWNORM_MAX_WIDTH, cfg->width);
-    if (!(cfg->clip > 0.0f)) return fail(DN_ERR_INVALID_ARGUMENT, "clip must be > 0, +inf for no clip (got %g)", (double)cfg->clip);
-    if (!(cfg->epsilon >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "epsilon must be >= 0 (got %g)", cfg->epsilon);
-    return DN_OK;
-}
-
-/* normalize.py:10-47: the state of one RunningMeanStd of `width` columns -- count, mean[width], var[width] */
-int64_t dn_rownorm_state_doubles(int32_t width)
-{
-    if (width < 1 || width > DN_ROWNORM_MAX_WIDTH) return fail(DN_ERR_INVALID_ARGUMENT, "width must be in 1..%d (got %d)", DN_ROWNORM_MAX_WIDTH, width);
-    return 1 + 2 * (int64_t)width;
-}
-
-/* normalize.py:10-47 in batch form: what dn_rownorm keeps between its launches (dn_internal.h dn_rownorm_scratch_doubles) */
-int64_t dn_rownorm_scratch_bytes(int64_t k, int64_t n, int32_t width)
-{
-    const long long d = dn_rownorm_scratch_doubles(k, n, width);
-    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "width must be in 1..%d and k, n >= 1 (got width %d, k %lld, n %lld)", DN_ROWNORM_MAX_WIDTH,
-                            width, (long long)k, (long long)n);
-    return (d * 8 + 15) / 16 * 16;
-}
-
-/* RunningMeanStd.__init__ (normalize.py:10-17): count 1e-4, mean 0, var 1 */
-int32_t dn_rownorm_init(const dn_rownorm_config *cfg, double *stats, int32_t device_id, void *stream)
-{
-    const int32_t rc = rownorm_config_ok(cfg);
-    if (rc != DN_OK) return rc;
-    if (!stats) return fail(DN_ERR_INVALID_ARGUMENT, "stats is required");
-    if ((uintptr_t)stats & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats must be 8-byte aligned");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_rownorm_init(cfg->width, stats, (hipStream_t)stream));
-    return DN_OK;
-}
-
-/* RunningMeanStd.update + update_mean_var_count_from_moments (normalize.py:10-47) with the N rows of a step as the batch, then the
- * normalised rows */
-int32_t dn_rownorm(const dn_rownorm_config *cfg, double *stats, int64_t k, int64_t n, const float *rows, float *out, int32_t update,
-                   void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
-{
-    const int32_t rc = rownorm_config_ok(cfg);
-    if (rc != DN_OK) return rc;
-    if (!stats || !rows || !scratch) return fail(DN_ERR_INVALID_ARGUMENT, "stats, rows and scratch are required");
-    if (k < 1 || n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 (got %lld, %lld)", (long long)k, (long long)n);
-    if (update != 0 && update != 1) return fail(DN_ERR_INVALID_ARGUMENT, "update must be 0 or 1 (got %d)", update);
-    if (!update && !out) return fail(DN_ERR_INVALID_ARGUMENT, "out is required with update = 0 (there is nothing else to do)");
-    const int64_t need = dn_rownorm_scratch_bytes(k, n, cfg->width);
-    if (need <= 0) return fail(DN_ERR_INVALID_ARGUMENT, "k x n = %lld x %lld rows are more than one call takes", (long long)k, (long long)n);
-    if (scratch_bytes < need)
-        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_rownorm_scratch_bytes gives %lld", (long long)scratch_bytes,
-                    (long long)need);
-    if (((uintptr_t)stats | (uintptr_t)scratch) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats and scratch must be 8-byte aligned");
-    if (((uintptr_t)rows | (uintptr_t)out) & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "rows and out must be 4-byte aligned");
-    if (out && out != rows) {
-        const uintptr_t bytes = (uintptr_t)k * (uintptr_t)n * (uintptr_t)cfg->width * sizeof(float);
-        const uintptr_t r0 = (uintptr_t)rows, o0 = (uintptr_t)out;
-        if (r0 < o0 + bytes && o0 < r0 + bytes)
-            return fail(DN_ERR_INVALID_ARGUMENT, "out overlaps rows: it must be rows itself (in place) or apart from it");
-    }
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_rownorm(cfg->width, cfg->clip, cfg->epsilon, stats, k, n, rows, out, update, (double *)scratch, (hipStream_t)stream));
-    return DN_OK;
-}
-
-// ---- dn_retnorm: one discounted return per drone, one RunningMeanStd of the returns over the fleet (normalize.py:10-47) ----------------
-static int32_t retnorm_config_ok(const dn_retnorm_config *cfg)
-{
-    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
-    if (!(cfg->gamma >= 0.0 && cfg->gamma <= 1.0)) return fail(DN_ERR_INVALID_ARGUMENT, "gamma must be in [0, 1] (got %g)", cfg->gamma);
-    if (!(cfg->clip > 0.0f)) return fail(DN_ERR_INVALID_ARGUMENT, "clip must be > 0, +inf for no clip (got %g)", (double)cfg->clip);
-    if (!(cfg->epsilon >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "epsilon must be >= 0 (got %g)", cfg->epsilon);
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
-    return DN_OK;
-}
-
-/* normalize.py:10-47 in batch form: what dn_retnorm keeps between its launches (dn_internal.h dn_retnorm_scratch_doubles) */
-int64_t dn_retnorm_scratch_bytes(int64_t k, int64_t n)
-{
-    const long long d = dn_retnorm_scratch_doubles(k, n);
-    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 and k x n within one call (got k %lld, n %lld)", (long long)k, (long long)n);
-    return d * 8;
-}
-
-/* RunningMeanStd.__init__ (normalize.py:10-17): count 1e-4, mean 0, var 1; the returns start at 0 */
-int32_t dn_retnorm_init(double *stats, double *returns, int64_t n, int32_t device_id, void *stream)
-{
-    if (!stats && !returns) return fail(DN_ERR_INVALID_ARGUMENT, "stats or returns is required (there is nothing else to do)");
-    if (returns && n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "n must be >= 1 (got %lld)", (long long)n);
-    if (returns && n > (1ll << 38)) return fail(DN_ERR_INVALID_ARGUMENT, "n = %lld returns are more than one call takes", (long long)n);
-    if (((uintptr_t)stats | (uintptr_t)returns) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats and returns must be 8-byte aligned");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_retnorm_init(stats, returns, n, (hipStream_t)stream));
-    return DN_OK;
-}
-
-/* The discounted returns, RunningMeanStd.update + update_mean_var_count_from_moments (normalize.py:10-47) with the N returns of a step as
- * the batch, then the scaled rewards */
-int32_t dn_retnorm(const dn_retnorm_config *cfg, double *stats, double *returns, int64_t k, int64_t n, const float *rewards,
-                   const uint8_t *done, float *out, int32_t update, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
-{
-    const int32_t rc = retnorm_config_ok(cfg);
-    if (rc != DN_OK) return rc;
-    if (update != 0 && update != 1) return fail(DN_ERR_INVALID_ARGUMENT, "update must be 0 or 1 (got %d)", update);
-    if (!stats || !rewards) return fail(DN_ERR_INVALID_ARGUMENT, "stats and rewards are required");
-    if (update && (!returns || !done || !scratch))
-        return fail(DN_ERR_INVALID_ARGUMENT, "returns, done and scratch are required with update = 1");
-    if (!update && !out) return fail(DN_ERR_INVALID_ARGUMENT, "out is required with update = 0 (there is nothing else to do)");
-    if (k < 1 || n < 1) return fail(DN_ERR_INVALID_ARGUMENT, "k and n must be >= 1 (got %lld, %lld)", (long long)k, (long long)n);
-    if ((uintptr_t)stats & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats must be 8-byte aligned");
-    if (update) {
-        const int64_t need = dn_retnorm_scratch_bytes(k, n);
-        if (need <= 0) return fail(DN_ERR_INVALID_ARGUMENT, "k x n = %lld x %lld rewards are more than one call takes", (long long)k, (long long)n);
-        if (scratch_bytes < need)
-            return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_retnorm_scratch_bytes gives %lld", (long long)scratch_bytes,
-                        (long long)need);
-        if (((uintptr_t)returns | (uintptr_t)scratch) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "returns and scratch must be 8-byte aligned");
-    }
-    if (!dn_retnorm_grids_ok(k, n))
-        return fail(DN_ERR_INVALID_ARGUMENT, "k x n = %lld x %lld rewards need a grid of more than 2^31 - 1 workgroups", (long long)k, (long long)n);
-    if (out && out != rewards) {
-        const uintptr_t bytes = (uintptr_t)k * (uintptr_t)n * sizeof(float);
-        const uintptr_t r0 = (uintptr_t)rewards, o0 = (uintptr_t)out;
-        if (r0 < o0 + bytes && o0 < r0 + bytes)
-            return fail(DN_ERR_INVALID_ARGUMENT, "out overlaps rewards: it must be rewards itself (in place) or apart from it");
-    }
-    if (((uintptr_t)rewards | (uintptr_t)out) & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "rewards and out must be 4-byte aligned");
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_retnorm(cfg->gamma, cfg->epsilon, cfg->clip, stats, update ? returns : nullptr, k, n, rewards, update ? done : nullptr, out,
-                             update, update ? (double *)scratch : nullptr, (hipStream_t)stream));
-    return DN_OK;
-}
-
-// ---- dn_minibatch: SB3 RolloutBuffer.get and PPO's advantage normalisation [from recall] on the step-major buffers ----------------------
-int64_t dn_minibatch_scratch_bytes(int64_t batch)
-{
-    const long long d = dn_minibatch_scratch_doubles(batch);
-    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
-    return d * 8;
-}
-
-/* the keyed permutation of csrc/dn_permute.h on the host: no device, no HIP call */
-int32_t dn_minibatch_permutation(uint64_t seed, uint64_t epoch, int64_t m, int64_t start, int64_t count, int64_t *out)
-{
-    if (m < 1 || m > DN_PERMUTE_MAX) return fail(DN_ERR_INVALID_ARGUMENT, "m must be in 1..2^31 - 1 (got %lld)", (long long)m);
-    if (start < 0 || count < 0 || start > m || count > m - start)
-        return fail(DN_ERR_INVALID_ARGUMENT, "start and count must be >= 0 with start + count <= m (got %lld, %lld, m %lld)", (long long)start,
-                    (long long)count, (long long)m);
-    if (!out) return fail(DN_ERR_INVALID_ARGUMENT, "out is required");
-    const DnPermutation p = dn_permute_make(seed, epoch, (uint32_t)m);
-    for (int64_t i = 0; i < count; ++i) out[i] = (int64_t)dn_permute_at(p, (uint32_t)(start + i));
-    return DN_OK;
-}
-
-int32_t dn_minibatch(const dn_minibatch_config *cfg, const dn_minibatch_field *fields, int64_t n_steps, int64_t n_envs, int64_t start,
-                     int64_t batch, const int64_t *indices, const int64_t *epoch_offset, int64_t *indices_out, void *scratch,
-                     int64_t scratch_bytes, int32_t device_id, void *stream)
-{
-    if (!cfg || !fields) return fail(DN_ERR_INVALID_ARGUMENT, "cfg and fields are required");
-    if (cfg->num_fields < 1 || cfg->num_fields > DN_MINIBATCH_MAX_FIELDS)
-        return fail(DN_ERR_INVALID_ARGUMENT, "num_fields must be in 1..%d (got %d)", DN_MINIBATCH_MAX_FIELDS, cfg->num_fields);
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
-    if (!(cfg->epsilon >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "epsilon must be >= 0 (got %g)", cfg->epsilon);
-    if (n_steps < 1 || n_envs < 1) return fail(DN_ERR_INVALID_ARGUMENT, "n_steps and n_envs must be >= 1 (got %lld, %lld)", (long long)n_steps, (long long)n_envs);
-    if (n_steps > DN_PERMUTE_MAX || n_envs > DN_PERMUTE_MAX / n_steps)
-        return fail(DN_ERR_INVALID_ARGUMENT, "n_steps x n_envs = %lld x %lld samples are more than the 2^31 - 1 of a buffer", (long long)n_steps,
-                    (long long)n_envs);
-    const int64_t m = n_steps * n_envs;
-    // batch <= m <= 2^31 - 1: the grids, blocks(batch) x num_fields and ceil(batch / 256) workgroups, are far below the 2^31 - 1 of a launch
-    if (batch < 1 || start < 0 || start > m || batch > m - start)
-        return fail(DN_ERR_INVALID_ARGUMENT, "start must be >= 0 and batch >= 1 with start + batch <= n_steps x n_envs = %lld (got %lld, %lld)",
-                    (long long)m, (long long)start, (long long)batch);
-    if (indices && start != 0) return fail(DN_ERR_INVALID_ARGUMENT, "start must be 0 with indices (got %lld)", (long long)start);
-    DnMinibatchArgs a;
-    a.num_fields = cfg->num_fields;
-    a.norm_field = -1;
-    for (int f = 0; f < cfg->num_fields; ++f) {
-        const dn_minibatch_field &fd = fields[f];
-        if (!fd.src || !fd.dst) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: src and dst are required", f);
-        if (fd.width < 1 || fd.width > DN_ROWNORM_MAX_WIDTH)
-            return fail(DN_ERR_INVALID_ARGUMENT, "field %d: width must be in 1..%d (got %d)", f, DN_ROWNORM_MAX_WIDTH, fd.width);
-        if (fd.normalize != 0 && fd.normalize != 1) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: normalize must be 0 or 1 (got %d)", f, fd.normalize);
-        if (fd.normalize) {
-            if (a.norm_field >= 0) return fail(DN_ERR_INVALID_ARGUMENT, "fields %d and %d: at most one field is normalised", a.norm_field, f);
-            if (fd.width != 1) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: the normalised field must be of width 1 (got %d)", f, fd.width);
-            a.norm_field = f;
-        }
-        if (fd.dst == fd.src) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: dst must not be src", f);
-        if (((uintptr_t)fd.src | (uintptr_t)fd.dst) & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "field %d: src and dst must be 4-byte aligned", f);
-        a.fields[f] = fd;
-    }
-    for (int f = cfg->num_fields; f < DN_MINIBATCH_MAX_FIELDS; ++f) a.fields[f] = dn_minibatch_field{nullptr, nullptr, 0, 0};
-    if (!scratch) return fail(DN_ERR_INVALID_ARGUMENT, "scratch is required");
-    const int64_t need = dn_minibatch_scratch_bytes(batch);
-    if (scratch_bytes < need)
-        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_minibatch_scratch_bytes gives %lld", (long long)scratch_bytes,
-                    (long long)need);
-    if (((uintptr_t)scratch | (uintptr_t)indices | (uintptr_t)epoch_offset | (uintptr_t)indices_out) & 7u)
-        return fail(DN_ERR_INVALID_ARGUMENT, "scratch, indices, epoch_offset and indices_out must be 8-byte aligned");
-    if (batch == 1) a.norm_field = -1;                 // SB3 skips the normalisation of a minibatch of one
-    a.seed = cfg->seed; a.epoch = cfg->epoch; a.eps = cfg->epsilon;
-    a.n_steps = (unsigned)n_steps; a.n_envs = (unsigned)n_envs; a.m = (unsigned)m; a.start = (unsigned)start; a.batch = (unsigned)batch;
-    a.nblk = (unsigned)dn_rownorm_blocks(batch);
-    a.indices = (const long long *)indices; a.epoch_offset = (const long long *)epoch_offset; a.indices_out = (long long *)indices_out;
-    a.part = (double *)scratch;
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_minibatch(a, (hipStream_t)stream));
-    return DN_OK;
-}
-
-// ---- dn_ppo_loss: SB3 PPO.train's loss, statistics and the gradients with respect to the head outputs [from recall] ---------------------
-int64_t dn_ppo_loss_scratch_bytes(int64_t batch, int32_t act_dim)
-{
-    if (act_dim < 1 || act_dim > DN_PPO_MAX_ACT) return fail(DN_ERR_INVALID_ARGUMENT, "act_dim must be in 1..%d (got %d)", DN_PPO_MAX_ACT, act_dim);
-    const long long d = dn_ppo_loss_scratch_doubles(batch, act_dim);
-    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
-    return d * 8;
-}
-
-int32_t dn_ppo_loss(const dn_ppo_loss_config *cfg, int64_t batch, const float *mean, const float *log_std, const float *value,
-                    const float *actions, const float *old_log_prob, const float *advantages, const float *returns,
-                    const float *old_values, float *d_mean, float *d_log_std, float *d_value, float *log_prob_out, float *loss,
-                    double *stats, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
-{
-    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
-    if (cfg->act_dim < 1 || cfg->act_dim > DN_PPO_MAX_ACT)
-        return fail(DN_ERR_INVALID_ARGUMENT, "act_dim must be in 1..%d (got %d)", DN_PPO_MAX_ACT, cfg->act_dim);
-    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %d)", cfg->reserved);
-    if (batch < 1 || batch > 0x7fffffffll) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
-    if (!std::isfinite(cfg->clip_range) || !(cfg->clip_range > 0.0))
-        return fail(DN_ERR_INVALID_ARGUMENT, "clip_range must be finite and > 0 (got %g)", cfg->clip_range);
-    if (!std::isfinite(cfg->clip_range_vf))
-        return fail(DN_ERR_INVALID_ARGUMENT, "clip_range_vf must be finite: > 0 clips the value step, <= 0 does not (got %g)", cfg->clip_range_vf);
-    if (!std::isfinite(cfg->ent_coef) || !(cfg->ent_coef >= 0.0))
-        return fail(DN_ERR_INVALID_ARGUMENT, "ent_coef must be finite and >= 0 (got %g)", cfg->ent_coef);
-    if (!std::isfinite(cfg->vf_coef) || !(cfg->vf_coef >= 0.0))
-        return fail(DN_ERR_INVALID_ARGUMENT, "vf_coef must be finite and >= 0 (got %g)", cfg->vf_coef);
-    const bool vclip = cfg->clip_range_vf > 0.0;
-    const uintptr_t rows = (uintptr_t)batch * sizeof(float), cells = rows * (uintptr_t)cfg->act_dim, cols = (uintptr_t)cfg->act_dim * sizeof(float);
-    struct Span { const char *name; const void *p; uintptr_t bytes; bool optional; };
-    const Span in[] = {{"mean", mean, cells, false}, {"log_std", log_std, cols, false}, {"value", value, rows, false}, {"actions", actions, cells, false},
-                       {"old_log_prob", old_log_prob, rows, false}, {"advantages", advantages, rows, false}, {"returns", returns, rows, false},
-                       {"old_values", old_values, rows, true}};
-    const Span out[] = {{"d_mean", d_mean, cells, false}, {"d_log_std", d_log_std, cols, false}, {"d_value", d_value, rows, false},
-                        {"loss", loss, sizeof(float), false},
-                        {"stats", stats, 8 * sizeof(double), false}, {"scratch", scratch, 0, false}, {"log_prob_out", log_prob_out, rows, true}};
-    for (const Span &s : in)
-        if (!s.p && !s.optional) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", s.name);
-    if (vclip && !old_values) return fail(DN_ERR_INVALID_ARGUMENT, "old_values is required with clip_range_vf > 0 (got %g)", cfg->clip_range_vf);
-    if (!vclip && old_values) return fail(DN_ERR_INVALID_ARGUMENT, "old_values must be NULL without a value clip (clip_range_vf %g <= 0)", cfg->clip_range_vf);
-    for (const Span &s : out)
-        if (!s.p && !s.optional) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", s.name);
-    const int64_t need = dn_ppo_loss_scratch_bytes(batch, cfg->act_dim);
-    if (scratch_bytes < need)
-        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_ppo_loss_scratch_bytes gives %lld", (long long)scratch_bytes,
-                    (long long)need);
-    if (((uintptr_t)stats | (uintptr_t)scratch) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats and scratch must be 8-byte aligned");
-    for (const Span &s : in)
-        if ((uintptr_t)s.p & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", s.name);
-    for (const Span &s : out)
-        if ((uintptr_t)s.p & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", s.name);
-    for (const Span &o : out) {
-        if (!o.p) continue;
-        const uintptr_t o0 = (uintptr_t)o.p, obytes = o.p == scratch ? (uintptr_t)need : o.bytes;
-        for (const Span &i : in) {
-            const uintptr_t i0 = (uintptr_t)i.p;
-            if (i.p && i0 < o0 + obytes && o0 < i0 + i.bytes) return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no output may alias an input", o.name, i.name);
-        }
-    }
-    DnPpoLossArgs a;
-    a.mean = mean; a.log_std = log_std; a.value = value; a.actions = actions; a.old_log_prob = old_log_prob; a.advantages = advantages;
-    a.returns = returns; a.old_values = old_values;
-    a.d_mean = d_mean; a.d_log_std = d_log_std; a.d_value = d_value; a.log_prob_out = log_prob_out; a.loss = loss;
-    a.stats = stats; a.part = (double *)scratch;
-    a.clip_range = cfg->clip_range; a.clip_range_vf = cfg->clip_range_vf; a.ent_coef = cfg->ent_coef; a.vf_coef = cfg->vf_coef;
-    a.batch = batch; a.nblk = dn_rownorm_blocks(batch);
-    a.act_dim = cfg->act_dim;
-    a.vec = cfg->act_dim % 4 == 0 && (((uintptr_t)mean | (uintptr_t)actions | (uintptr_t)d_mean) & 15u) == 0;
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_ppo_loss(a, (hipStream_t)stream));
-    return DN_OK;
-}
-
-// ---- dn_adam_step: SB3 PPO.train's clip_grad_norm_ + Adam.step [from recall] ---------------------------------------------------------------
-int64_t dn_adam_scratch_bytes(const int64_t *counts, int32_t n_tensors)
-{
-    if (!counts) return fail(DN_ERR_INVALID_ARGUMENT, "counts is required");
-    if (n_tensors < 1 || n_tensors > DN_ADAM_MAX_TENSORS)
-        return fail(DN_ERR_INVALID_ARGUMENT, "n_tensors must be in 1..%d (got %d)", DN_ADAM_MAX_TENSORS, n_tensors);
-    long long chunks = 0;                              // at most 32 x 2^53: no overflow
-    for (int i = 0; i < n_tensors; ++i) {
-        if (counts[i] < 1) return fail(DN_ERR_INVALID_ARGUMENT, "counts[%d] must be >= 1 (got %lld)", i, (long long)counts[i]);
-        chunks += dn_adam_chunks(counts[i]);
-    }
-    if (chunks > 0x7fffffffll)
-        return fail(DN_ERR_INVALID_ARGUMENT, "the counts make %lld chunks of %d elements; a call takes at most 2^31 - 1", chunks, DN_ADAM_CHUNK);
-    return chunks * 8;
-}
-
-int32_t dn_adam_step(const dn_adam_config *cfg, const dn_adam_tensor *tensors, const double *lr, double *state, double *stats,
-                     void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
-{
-    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
-    if (!tensors) return fail(DN_ERR_INVALID_ARGUMENT, "tensors is required");
-    const struct { const char *name; const void *p; } doubles[] = {{"lr", lr}, {"state", state}, {"stats", stats}, {"scratch", scratch}};
-    for (const auto &d : doubles)
-        if (!d.p) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", d.name);
-    if (cfg->n_tensors < 1 || cfg->n_tensors > DN_ADAM_MAX_TENSORS)
-        return fail(DN_ERR_INVALID_ARGUMENT, "n_tensors must be in 1..%d (got %d)", DN_ADAM_MAX_TENSORS, cfg->n_tensors);
-    if (cfg->flags & ~DN_ADAM_ZERO_GRADS) return fail(DN_ERR_INVALID_ARGUMENT, "flags has unknown bits: 0x%x (bit 0 zeroes the gradients)", cfg->flags);
-    if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0)) return fail(DN_ERR_INVALID_ARGUMENT, "beta1 must be in [0, 1) (got %g)", cfg->beta1);
-    if (!(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0)) return fail(DN_ERR_INVALID_ARGUMENT, "beta2 must be in [0, 1) (got %g)", cfg->beta2);
-    if (!std::isfinite(cfg->eps) || !(cfg->eps >= 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "eps must be finite and >= 0 (got %g)", cfg->eps);
-    if (!std::isfinite(cfg->max_grad_norm))
-        return fail(DN_ERR_INVALID_ARGUMENT, "max_grad_norm must be finite: > 0 clips the global norm, <= 0 does not (got %g)", cfg->max_grad_norm);
-    int64_t counts[DN_ADAM_MAX_TENSORS];
-    for (int i = 0; i < cfg->n_tensors; ++i) {
-        const dn_adam_tensor &t = tensors[i];
-        const struct { const char *name; const void *p; } fields[] = {{"param", t.param}, {"grad", t.grad}, {"exp_avg", t.exp_avg},
-                                                                      {"exp_avg_sq", t.exp_avg_sq}};
-        for (const auto &f : fields) {
-            if (!f.p) return fail(DN_ERR_INVALID_ARGUMENT, "tensors[%d].%s is required", i, f.name);
-            if ((uintptr_t)f.p & 3u) return fail(DN_ERR_INVALID_ARGUMENT, "tensors[%d].%s must be 4-byte aligned", i, f.name);
-        }
-        if (t.count < 1) return fail(DN_ERR_INVALID_ARGUMENT, "tensors[%d].count must be >= 1 (got %lld)", i, (long long)t.count);
-        counts[i] = t.count;
-    }
-    const int64_t need = dn_adam_scratch_bytes(counts, cfg->n_tensors);
-    if (need < 0) return (int32_t)need;                // more than 2^31 - 1 chunks: the text is dn_adam_scratch_bytes'
-    if (scratch_bytes < need)
-        return fail(DN_ERR_INVALID_ARGUMENT, "scratch_bytes is too small: %lld, dn_adam_scratch_bytes gives %lld", (long long)scratch_bytes,
-                    (long long)need);
-    for (const auto &d : doubles)
-        if ((uintptr_t)d.p & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 8-byte aligned", d.name);
-    DnAdamArgs a;
-    std::memset(&a, 0, sizeof a);
-    for (int i = 0; i < cfg->n_tensors; ++i) a.t[i] = tensors[i];
-    a.lr = lr; a.state = state; a.stats = stats; a.part = (double *)scratch;
-    a.beta1 = cfg->beta1; a.beta2 = cfg->beta2; a.eps = cfg->eps; a.max_grad_norm = cfg->max_grad_norm;
-    a.nchunks = need / 8;
-    a.n_tensors = cfg->n_tensors; a.flags = cfg->flags;
-    DN_HIP(hipSetDevice(device_id));
-    DN_HIP(dn_launch_adam(a, (hipStream_t)stream));
     return DN_OK;
 }
 

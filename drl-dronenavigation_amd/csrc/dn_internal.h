@@ -1,4 +1,4 @@
-// dn_internal.h -- shared between the HIP kernels (dn_kernels.hip) and the C-ABI host side (dn_capi.cpp).
+// dn_internal.h -- shared between the HIP kernels (dn_kernels.hip) and the C-ABI host side (dn_capi.cpp, dn_capi_envfree.cpp).
 #ifndef DN_INTERNAL_H
 #define DN_INTERNAL_H
 

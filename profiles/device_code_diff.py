@@ -29,8 +29,17 @@ import subprocess
 import sys
 import tempfile
 
-OBJECTS = ["dn_kernels.o", "dn_kernels.exact.o", "dn_kernels_mw.o", "dn_kernels_mw.exact.o", "dn_fused.o", "dn_fused.exact.o", "dn_mlp.o",
-           "dn_mlp_wide.o", "dn_history.o", "dn_rownorm.o", "dn_retnorm.o", "dn_minibatch.o", "dn_ppo_loss.o"]
+
+def objects():
+    """Every object of the build with a device code object: one per .hip source, and the .exact.o of each step source (build.py)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "drl-dronenavigation_amd"))
+    import build
+    out = []
+    for src in build.SOURCES:
+        stem, ext = os.path.splitext(src)
+        if ext == ".hip":                                           # the .cpp units are host code only
+            out += [stem + ".o"] + ([stem + ".exact.o"] if src in build.STEP_SOURCES else [])
+    return out
 
 
 def tool(name):
@@ -138,7 +147,7 @@ def masked(text):
 
 def main(old, new, new_template_arg=False, model_level=False):
     bad = 0
-    for name in OBJECTS:
+    for name in objects():
         with tempfile.TemporaryDirectory() as work:
             (a, na, ma), (b, nb, mb) = functions(os.path.join(old, name), work), functions(os.path.join(new, name), work)
         if new_template_arg:

@@ -1,23 +1,12 @@
 """tests/tools/check_kernel_shapes.cpp for the tests that use it: the host program over csrc/dn_shapes.h, built with the host compiler
 and run as its own process."""
-import json
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]
+import host_program_support
 
 
 def build_program(directory, sanitize=False):
-    exe = os.path.join(str(directory), "check_kernel_shapes")
-    src = os.path.join(ROOT, "tests", "tools", "check_kernel_shapes.cpp")
-    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + csrc] + (SANITIZE if sanitize else []) + [src, "-o", exe])
-    return exe
+    return host_program_support.build("check_kernel_shapes", directory, sanitize=sanitize)
 
 
 def run_program(exe, **keys):
     """Without keys: the walk's {"cases", "digest", "bad"}.  With keys (num_cus, num_envs, configuration fields): {"fused", "single"}."""
-    out = subprocess.run([exe] + ["%s=%s" % kv for kv in keys.items()], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return json.loads(out.stdout)
+    return host_program_support.run(exe, *["%s=%s" % kv for kv in keys.items()], timeout=120)

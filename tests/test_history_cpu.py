@@ -2,7 +2,6 @@
 case, HistoryObservation's validation and width rule, the refusals of the C ABI (dn_stack_history validates before its first device call),
 the exported symbols, the inline width rule as a stand-alone host program, and the collectors' refusals."""
 import ctypes as C
-import json
 import os
 import subprocess
 import types
@@ -11,7 +10,8 @@ import numpy as np
 import pytest
 
 import history_support as H
-from test_model_level import ROOT, rocm_include
+import host_program_support
+from host_program_support import ROOT
 
 INVALID = -1
 P = C.c_void_p(0x1000)           # a non-null, 16-byte aligned pointer that is never followed
@@ -172,17 +172,10 @@ def test_width_rule_as_a_host_program(tmp_path, sanitize):
     """tests/tools/check_history_width.cpp walks F = -1 .. 6, A = -2 .. 6, E = -1 .. 70 against the rule written out independently of the
     function; built with the host compiler against the HIP headers, plainly and under the address and undefined-behaviour sanitizers,
     and run as its own process."""
-    inc = rocm_include()
-    if inc is None:
+    exe = host_program_support.build("check_history_width", tmp_path, sanitize=sanitize, hip_headers=True)
+    if exe is None:
         pytest.skip("the HIP headers are not installed")
-    exe = str(tmp_path / "check_history_width")
-    src = os.path.join(ROOT, "tests", "tools", "check_history_width.cpp")
-    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + csrc] + flags + [src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert json.loads(out.stdout) == {"cases": 8 * 9 * 72 + 3, "bad": 0}
+    assert host_program_support.run(exe) == {"cases": 8 * 9 * 72 + 3, "bad": 0}
 
 
 # ---- the collectors ---------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,6 @@ permutation through the real library against the NumPy reference of tests/miniba
 plainly and under the address and undefined-behaviour sanitizers; every refusal of dn_minibatch, which validates before its first device
 call, so the pointers here are never followed; the Python surface's own refusals; and the reference normalisation against itself."""
 import ctypes as C
-import json
 import math
 import os
 import re
@@ -15,6 +14,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import host_program_support  # noqa: E402
 import minibatch_support as M  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,15 +140,9 @@ def test_permutation_as_a_host_program(tmp_path, sanitize):
     """tests/tools/check_minibatch_permutation.cpp includes csrc/dn_permute.h alone: built with the host compiler, plainly and under the
     address and undefined-behaviour sanitizers, and run as its own process; its bitmap finds every pi a bijection, and every pi it prints
     is the NumPy reference's."""
-    exe = str(tmp_path / "check_minibatch_permutation")
-    src = os.path.join(ROOT, "tests", "tools", "check_minibatch_permutation.cpp")
-    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + csrc] + flags + [src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    lines = out.stdout.splitlines()
-    assert json.loads(lines[-1]) == {"cases": len(M.SIZES) * len(M.SEEDS) * len(M.EPOCHS), "bad": 0}
+    exe = host_program_support.build("check_minibatch_permutation", tmp_path, sanitize=sanitize, extra_flags=("-Wall", "-Werror"))
+    result, lines = host_program_support.run_lines(exe, timeout=120)
+    assert result == {"cases": len(M.SIZES) * len(M.SEEDS) * len(M.EPOCHS), "bad": 0}
     seen = set()
     for line in lines[:-1]:
         key, values = line.split(":")

@@ -1,9 +1,6 @@
 """The policy kernels' wide inputs (17 .. 64 columns), the part that needs no GPU: the packed layout of layer 1, the refusals of the
 packers and of the C ABI (dn_mlp_forward validates before its first device call), and dn_mlp_ks1 as a stand-alone host program."""
 import ctypes as C
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +8,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import mlp_support as S  # noqa: E402
-from test_model_level import ROOT, rocm_include  # noqa: E402
+import host_program_support  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -112,14 +109,7 @@ def test_dn_mlp_step_sampled_keeps_its_sixteen_columns(pkg):
 def test_ks1_of_every_width(tmp_path, sanitize):
     """tests/tools/check_mlp_ks1.cpp walks obs_dim = -1 .. 70; built with the host compiler against the HIP headers, once plainly and once
     under the address and undefined-behaviour sanitizers, and run as its own process."""
-    inc = rocm_include()
-    if inc is None:
+    exe = host_program_support.build("check_mlp_ks1", tmp_path, sanitize=sanitize, hip_headers=True)
+    if exe is None:
         pytest.skip("the HIP headers are not installed")
-    exe = str(tmp_path / "check_mlp_ks1")
-    src = os.path.join(ROOT, "tests", "tools", "check_mlp_ks1.cpp")
-    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + csrc] + flags + [src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert json.loads(out.stdout) == {"cases": 72, "bad": 0}
+    assert host_program_support.run(exe) == {"cases": 72, "bad": 0}

@@ -2,35 +2,14 @@
 and goal rows counting only when enabled AND bound.  tests/tools/check_model_level.cpp walks all 144 combinations against that rule, written
 out independently of the function.  Host code only: built with the host compiler against the HIP headers, once plainly and once under the
 address and undefined-behaviour sanitizers, and run as its own process.  No GPU."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rocm_include():
-    hipcc = shutil.which("hipcc")
-    roots = [os.environ.get("ROCM_PATH"), os.path.dirname(os.path.dirname(os.path.realpath(hipcc))) if hipcc else None, "/opt/rocm"]
-    for r in roots:
-        if r and os.path.exists(os.path.join(r, "include", "hip", "hip_runtime.h")):
-            return os.path.join(r, "include")
-    return None
+import host_program_support
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_model_level_is_the_deepest_model_that_counts(tmp_path, sanitize):
-    inc = rocm_include()
-    if inc is None:
+    exe = host_program_support.build("check_model_level", tmp_path, sanitize=sanitize, hip_headers=True)
+    if exe is None:
         pytest.skip("the HIP headers are not installed")
-    exe = str(tmp_path / "check_model_level")
-    src = os.path.join(ROOT, "tests", "tools", "check_model_level.cpp")
-    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + csrc] + flags + [src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert json.loads(out.stdout) == {"cases": 144, "bad": 0}
+    assert host_program_support.run(exe) == {"cases": 144, "bad": 0}

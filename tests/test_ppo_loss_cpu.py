@@ -15,6 +15,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import host_program_support  # noqa: E402
 import ppo_loss_support as P  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -183,14 +184,8 @@ def test_exp_cr_as_a_host_program(tmp_path, sanitize):
     arguments over [-6, 6], half of them float32 values as -log_std is, powers of two down to 2^-52, the ends of the range -- is the
     nearest double to exp(x) by 50-digit arithmetic; outside |x| <= 700 and for NaN it answers nothing and leaves the library's exp."""
     import decimal
-    exe = str(tmp_path / "check_exp_cr")
-    src = os.path.join(ROOT, "tests", "tools", "check_exp_cr.cpp")
-    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-ffp-contract=off", "-I" + csrc] + flags + [src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    lines = out.stdout.splitlines()
+    exe = host_program_support.build("check_exp_cr", tmp_path, sanitize=sanitize, extra_flags=("-Wall", "-Werror", "-ffp-contract=off"))
+    _, lines = host_program_support.run_lines(exe, timeout=120)
     answered, refused = 0, []
     with decimal.localcontext() as ctx:
         ctx.prec = 50

@@ -3,7 +3,6 @@ exported and bound; the state and scratch sizes; every refusal of dn_rownorm / d
 call, so the pointers here are never followed; the Python surface's own refusals; and the scratch-size rule as a stand-alone host
 program, plainly and under the address and undefined-behaviour sanitizers."""
 import ctypes as C
-import json
 import math
 import os
 import re
@@ -15,7 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import rownorm_support as R  # noqa: E402
-from test_model_level import rocm_include  # noqa: E402
+import host_program_support  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dn_rownorm_config", "dn_rownorm_state_doubles", "dn_rownorm_scratch_bytes", "dn_rownorm_init", "dn_rownorm")
@@ -182,14 +181,7 @@ def test_scratch_size_rule_as_a_host_program(tmp_path, sanitize):
     """tests/tools/check_rownorm_sizes.cpp walks width 1 .. 64 x k {1, 2, 64} x n {1, 63, 64, 65, 1000, 2^21} and ten refusals; built
     with the host compiler against the HIP headers, plainly and under the address and undefined-behaviour sanitizers, and run as its own
     process."""
-    inc = rocm_include()
-    if inc is None:
+    exe = host_program_support.build("check_rownorm_sizes", tmp_path, sanitize=sanitize, hip_headers=True)
+    if exe is None:
         pytest.skip("the HIP headers are not installed")
-    exe = str(tmp_path / "check_rownorm_sizes")
-    src = os.path.join(ROOT, "tests", "tools", "check_rownorm_sizes.cpp")
-    csrc = os.path.join(ROOT, "drl-dronenavigation_amd", "csrc")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + csrc] + flags + [src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert json.loads(out.stdout) == {"cases": 64 * 3 * 6 + 10, "bad": 0}
+    assert host_program_support.run(exe) == {"cases": 64 * 3 * 6 + 10, "bad": 0}
