@@ -23,7 +23,7 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
            "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer",
-           "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam"]
+           "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam", "ReplaySampler"]
 
 
 def __getattr__(name):
@@ -54,6 +54,9 @@ def __getattr__(name):
     if name in ("optim", "ClippedAdam"):
         optim = importlib.import_module(__name__ + ".optim")
         return optim if name == "optim" else optim.ClippedAdam
+    if name in ("replay", "ReplaySampler"):
+        replay = importlib.import_module(__name__ + ".replay")
+        return replay if name == "replay" else replay.ReplaySampler
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
     if name in ("policy", "MlpActorCritic", "SacActor", "MlpValue"):

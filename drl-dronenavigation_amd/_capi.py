@@ -138,6 +138,20 @@ ADAM_MAX_TENSORS = 32
 ADAM_ZERO_GRADS = 1
 
 
+class DnReplayConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("draw", C.c_uint64), ("buffer_size", C.c_int64), ("n_envs", C.c_int64), ("valid", C.c_int64),
+                ("skip", C.c_int64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DnReplaySource(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("next_obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+                ("timeouts", C.c_void_p)]
+
+
+REPLAY_PLAIN, REPLAY_RING = 0, 1
+REPLAY_MAX_OBS, REPLAY_MAX_ACT = 64, 8
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -197,7 +211,9 @@ PROTOTYPES = {
     "dn_ppo_loss": (_I32, [C.POINTER(DnPpoLossConfig), _I64] + [_VP] * 15 + [_I64, _I32, _VP]),
     "dn_adam_scratch_bytes": (_I64, [C.POINTER(C.c_int64), _I32]),
     "dn_adam_step": (_I32, [C.POINTER(DnAdamConfig), C.POINTER(DnAdamTensor), _VP, _VP, _VP, _VP, _I64, _I32, _VP]),
-    "dn_set_launch_events": (_I32, [_VP, _VP, _VP]),
+    "dn_replay_indices": (_I32, [C.c_uint64, C.c_uint64, _I64, _I64, _I64, _I64, _I64, _VP]),
+    "dn_replay_sample": (_I32, [C.POINTER(DnReplayConfig), C.POINTER(DnReplaySource), _I64] + [_VP] * 8 + [_I32, _VP]),
+    "dn_set_launch_events":(_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),
     "dn_set_dynamics": (_I32, [_VP, _VP, _VP]),

@@ -1,5 +1,5 @@
 // dn_capi_envfree.cpp -- the entry points of include/dronenav.h that take a device_id and no dn_env: the rollout glue, the history rows,
-// the two fleet normalisers, the minibatches, the PPO loss and the optimiser step.
+// the two fleet normalisers, the minibatches, the PPO loss, the optimiser step and the replay minibatches.
 //
 // Every entry point validates its arguments, turns HIP failures into dn_status codes + the thread-local message of dn_capi.cpp
 // (dn_capi_fail.h), and never falls back to a CPU implementation.
@@ -7,6 +7,7 @@
 #include "dn_capi_fail.h"
 #include "dn_internal.h"
 #include "dn_permute.h"
+#include "dn_replay_draw.h"
 
 #include <cmath>
 #include <cstring>
@@ -481,6 +482,90 @@ int32_t dn_adam_step(const dn_adam_config *cfg, const dn_adam_tensor *tensors, c
     a.n_tensors = cfg->n_tensors; a.flags = cfg->flags;
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_adam(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+// ---- dn_replay_sample: SB3 ReplayBuffer.sample [from recall] on either replay layout ------------------------------------------------------
+/* what dn_replay_indices and dn_replay_sample both ask of the window the draw covers */
+static int32_t replay_window_ok(int64_t valid, int64_t n_envs, int64_t skip)
+{
+    if (valid < 1 || valid > DN_REPLAY_MAX || n_envs < 1 || n_envs > DN_REPLAY_MAX)
+        return fail(DN_ERR_INVALID_ARGUMENT, "valid and n_envs must be in 1..2^31 - 1 (got %lld, %lld)", (long long)valid, (long long)n_envs);
+    if (skip < -1 || skip > valid)
+        return fail(DN_ERR_INVALID_ARGUMENT, "skip must be -1 or in 0..valid = %lld (got %lld)", (long long)valid, (long long)skip);
+    return DN_OK;
+}
+
+/* the keyed draw of csrc/dn_replay_draw.h on the host: no device, no HIP call */
+int32_t dn_replay_indices(uint64_t seed, uint64_t draw, int64_t valid, int64_t n_envs, int64_t skip, int64_t start, int64_t count, int64_t *out)
+{
+    if (const int32_t rc = replay_window_ok(valid, n_envs, skip)) return rc;
+    if (start < 0 || count < 0 || start > DN_REPLAY_MAX || count > DN_REPLAY_MAX - start)
+        return fail(DN_ERR_INVALID_ARGUMENT, "start and count must be >= 0 with start + count <= 2^31 - 1 (got %lld, %lld)", (long long)start,
+                    (long long)count);
+    if (!out) return fail(DN_ERR_INVALID_ARGUMENT, "out is required");
+    const uint64_t key = dn_replay_key(seed, draw);
+    for (int64_t i = 0; i < count; ++i)
+        out[i] = dn_replay_flat(dn_replay_draw_at(key, (uint64_t)(start + i), (uint32_t)valid, (uint32_t)n_envs, skip), (uint32_t)n_envs);
+    return DN_OK;
+}
+
+/* cells x per bytes, held at 2^62 where the product is larger than any allocation: the overlap walk needs no more */
+static uintptr_t replay_bytes(int64_t cells, int64_t per)
+{
+    return cells > (1ll << 62) / per ? (uintptr_t)1 << 62 : (uintptr_t)cells * (uintptr_t)per;
+}
+
+int32_t dn_replay_sample(const dn_replay_config *cfg, const dn_replay_source *src, int64_t batch, const int64_t *indices,
+                         const int64_t *draw_offset, float *obs, float *next_obs, float *actions, float *rewards, float *dones,
+                         int64_t *indices_out, int32_t device_id, void *stream)
+{
+    if (!cfg || !src) return fail(DN_ERR_INVALID_ARGUMENT, "cfg and src are required");
+    if (const int32_t rc = reserved_ok(cfg->reserved)) return rc;
+    if (cfg->layout != DN_REPLAY_PLAIN && cfg->layout != DN_REPLAY_RING)
+        return fail(DN_ERR_INVALID_ARGUMENT, "layout must be 0 (DN_REPLAY_PLAIN) or 1 (DN_REPLAY_RING) (got %d)", cfg->layout);
+    if (cfg->obs_dim < 1 || cfg->obs_dim > DN_REPLAY_MAX_OBS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "obs_dim must be in 1..%d (got %d)", DN_REPLAY_MAX_OBS, cfg->obs_dim);
+    if (cfg->act_dim < 1 || cfg->act_dim > DN_REPLAY_MAX_ACT)
+        return fail(DN_ERR_INVALID_ARGUMENT, "act_dim must be in 1..%d (got %d)", DN_REPLAY_MAX_ACT, cfg->act_dim);
+    if (batch < 1 || batch > DN_REPLAY_MAX) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
+    const int64_t T = cfg->buffer_size, N = cfg->n_envs, S = cfg->valid;
+    if (T < 1 || T > DN_REPLAY_MAX) return fail(DN_ERR_INVALID_ARGUMENT, "buffer_size must be in 1..2^31 - 1 (got %lld)", (long long)T);
+    if (const int32_t rc = replay_window_ok(S, N, cfg->skip)) return rc;
+    // T, N <= 2^31 - 1: T N < 2^62 transitions, which the kernel's 64-bit offsets hold
+    if (S + (cfg->skip >= 0) > T)
+        return fail(DN_ERR_INVALID_ARGUMENT, "valid%s must be <= buffer_size = %lld (got valid %lld, skip %lld)", cfg->skip >= 0 ? " + 1 (the skipped slot)" : "",
+                    (long long)T, (long long)S, (long long)cfg->skip);
+    const bool ring = cfg->layout == DN_REPLAY_RING;
+    if (!ring && cfg->skip != -1)
+        return fail(DN_ERR_INVALID_ARGUMENT, "skip must be -1 with DN_REPLAY_PLAIN: every slot below valid is whole (got %lld)", (long long)cfg->skip);
+    if (indices && draw_offset) return fail(DN_ERR_INVALID_ARGUMENT, "draw_offset must be NULL with indices: the draw plays no part");
+    const int64_t cells = T * N, D = cfg->obs_dim, A = cfg->act_dim, flag = ring ? 1 : 4;
+    const DnArg in[] = {{"src.obs", src->obs, replay_bytes(cells + (ring ? N : 0), 4 * D), false}, {"src.next_obs", src->next_obs, replay_bytes(cells, 4 * D), false},
+                        {"src.actions", src->actions, replay_bytes(cells, 4 * A), false}, {"src.rewards", src->rewards, replay_bytes(cells, 4), false},
+                        {"src.dones", src->dones, replay_bytes(cells, flag), false}, {"src.timeouts", src->timeouts, replay_bytes(cells, flag), false}};
+    const DnArg floats[] = {in[0], in[1], in[2], in[3], {"src.dones", ring ? nullptr : src->dones, 0, true}, {"src.timeouts", ring ? nullptr : src->timeouts, 0, true}};
+    const DnArg out[] = {{"obs", obs, (uintptr_t)batch * 4u * (uintptr_t)D, false}, {"next_obs", next_obs, (uintptr_t)batch * 4u * (uintptr_t)D, false},
+                         {"actions", actions, (uintptr_t)batch * 4u * (uintptr_t)A, false}, {"rewards", rewards, (uintptr_t)batch * 4u, false},
+                         {"dones", dones, (uintptr_t)batch * 4u, false}};
+    const DnArg longs[] = {{"indices", indices, 0, true}, {"draw_offset", draw_offset, 0, true}, {"indices_out", indices_out, (uintptr_t)batch * 8u, true}};
+    if (const DnArg *a = dn_first_missing(in)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_missing(out)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_misaligned(floats, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    if (const DnArg *a = dn_first_misaligned(out, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    if (const DnArg *a = dn_first_misaligned(longs, 7u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 8-byte aligned", a->name);
+    const DnArg *o, *i;
+    if (dn_first_overlap(out, in, &o, &i) || dn_first_overlap(&longs[2], 1, in, 6, &o, &i))
+        return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no output may be a source", o->name, i->name);
+    DnReplayArgs a;
+    a.src = *src;
+    a.obs = obs; a.next_obs = next_obs; a.actions = actions; a.rewards = rewards; a.dones = dones;
+    a.indices = (const long long *)indices; a.draw_offset = (const long long *)draw_offset; a.indices_out = (long long *)indices_out;
+    a.seed = cfg->seed; a.draw = cfg->draw; a.skip = cfg->skip;
+    a.t = (unsigned)T; a.n = (unsigned)N; a.s = (unsigned)S; a.batch = (unsigned)batch;
+    a.obs_dim = cfg->obs_dim; a.act_dim = cfg->act_dim; a.ring = ring;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_replay(a, (hipStream_t)stream));
     return DN_OK;
 }
 }  // extern "C"

@@ -398,6 +398,20 @@ struct DnAdamArgs {
 };
 inline long long dn_adam_chunks(long long count) { return count < 1 ? 0 : (count - 1) / DN_ADAM_CHUNK + 1; }
 hipError_t dn_launch_adam(const DnAdamArgs &a, hipStream_t stream);                                                            // dn_adam.hip
+// SAC replay minibatches (dn_replay_sample, dn_replay.hip): one launch, grid (blocks of DN_REPLAY_BLOCK_ROWS output rows, 3 parts: obs,
+// next_obs, and actions | reward | dones).  Everything is checked by the C ABI: 1 <= s, s + (skip >= 0) <= t, n, batch <= 2^31 - 1.
+constexpr int DN_REPLAY_BLOCK_ROWS = 16;
+struct DnReplayArgs {
+    dn_replay_source src;
+    float *obs, *next_obs, *actions, *rewards, *dones;
+    const long long *indices, *draw_offset;            // NULL = the keyed draw; NULL = no offset
+    long long *indices_out;                            // NULL = not wanted
+    unsigned long long seed, draw;
+    long long skip;                                    // -1 = none
+    unsigned t, n, s, batch;
+    int obs_dim, act_dim, ring;                        // ring: DN_REPLAY_RING
+};
+hipError_t dn_launch_replay(const DnReplayArgs &a, hipStream_t stream);                                                        // dn_replay.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

@@ -1023,6 +1023,74 @@ int64_t dn_adam_scratch_bytes(const int64_t *counts, int32_t n_tensors);
 int32_t dn_adam_step(const dn_adam_config *cfg, const dn_adam_tensor *tensors, const double *lr, double *state, double *stats,
                      void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
 
+/* SAC replay minibatches on the device: SB3's ReplayBuffer.sample(batch_size) [from recall] -- a slot and a drone drawn uniformly with
+ * replacement per row, the gathered transition, the terminal observation where the episode ended, and dones * (1 - timeouts) -- in one
+ * ordinary launch, from either of the two buffer layouts, with a keyed draw whose bits are pinned.  Env-free; the SAC losses, the target
+ * update and the learner loop stay the caller's.
+ * The window: T = buffer_size slots of N = n_envs drones; S = valid of them hold a whole transition.  skip = -1: they are slots 0 .. S - 1.
+ *   skip in 0 .. S: slot `skip` is the one being replaced (a full ring mid-cycle has lost its observation row) and the valid slots are
+ *   0 .. S without it.  1 <= S, S + (skip >= 0) <= T <= 2^31 - 1, 1 <= N <= 2^31 - 1, T N <= 2^62.
+ * The draw: row j (0-based) under (seed, draw + (draw_offset ? *draw_offset : 0)), the sum mod 2^64 (csrc/dn_replay_draw.h, host and
+ *   device):
+ *     x = seed ^ (draw * 0xD1342543DE82EF95); z = the (j + 1)-th splitmix64 output from the state x
+ *     raw = ((z >> 32) * S) >> 32;  env = ((z & 0xFFFFFFFF) * N) >> 32;  slot = raw + (skip >= 0 && raw >= skip)
+ *   With replacement; not rejection sampled: each value's probability is within 2^-32 of uniform.  Row j does not depend on `batch`: a
+ *   call for G B rows is G independent batches of B (SAC's gradient_steps).  The flat index of a transition is slot * N + env.
+ *   indices        device int64[batch] or NULL.  Not NULL: row j is the transition indices[j] instead -- slot = indices[j] / N and
+ *                  env = indices[j] % N by C's division, the slot then clamped into [0, T) and the drone into [0, N), so no read ever
+ *                  leaves the buffers; the draw plays no part and draw_offset must be NULL.
+ *   draw_offset    device int64[1] or NULL: lets a captured graph draw afresh on every replay, as epoch_offset does for dn_minibatch
+ *   indices_out    device int64[batch] or NULL: receives the flat indices of the transitions taken (after the clamp)
+ * Sources (dn_replay_source; all device, dense):
+ *   DN_REPLAY_PLAIN  float32 obs[T][N][D], next_obs[T][N][D], actions[T][N][A], rewards[T][N], dones[T][N], timeouts[T][N];
+ *                    skip must be -1.  out dones_j = dones * (1.0f - timeouts), float32.
+ *   DN_REPLAY_RING   float32 obs = the ring [T + 1][N][D] (row t + 1 is both what the step of slot t produced and the input of slot
+ *                    t + 1; row T is the spare row), next_obs = terminal_obs[T][N][D], actions, rewards; uint8 dones = done_flags[T][N],
+ *                    timeouts = timeout_flags[T][N] (non-zero = set).  out obs_j = ring[slot][env];
+ *                    next_obs_j = done ? terminal_obs[slot][env] : ring[slot + 1][env]; dones_j = done && !timeout ? 1.0f : 0.0f.
+ * Outputs (device, dense): float32 obs[batch][D], next_obs[batch][D], actions[batch][A], rewards[batch], dones[batch].  Observation,
+ *   action and reward words are copied bit for bit (32-bit words: NaN payloads survive).  D = obs_dim in 1..64, A = act_dim in 1..8.  No
+ *   output may be a source pointer.
+ * One ordinary launch on `stream`: every output word is written once, by a vector store; no atomics, no workgroup waits for another,
+ *   nothing is allocated or kept between calls; capturable.  Validates before the first device call: DN_ERR_INVALID_ARGUMENT with a
+ *   dn_last_error text.
+ * Layout of dn_replay_config: seed at 0, draw at 8, buffer_size at 16, n_envs at 24, valid at 32, skip at 40, obs_dim at 48, act_dim at
+ *   52, layout at 56, reserved at 60; 64 bytes.
+ * Layout of dn_replay_source: obs at 0, next_obs at 8, actions at 16, rewards at 24, dones at 32, timeouts at 40; 48 bytes. */
+#define DN_REPLAY_PLAIN 0
+#define DN_REPLAY_RING 1
+#define DN_REPLAY_MAX_OBS 64
+#define DN_REPLAY_MAX_ACT 8
+typedef struct dn_replay_config {
+    uint64_t seed;
+    uint64_t draw;
+    int64_t buffer_size;  /* T */
+    int64_t n_envs;       /* N */
+    int64_t valid;        /* S */
+    int64_t skip;         /* -1, or the slot being replaced, in 0..S */
+    int32_t obs_dim;      /* D, 1..64 */
+    int32_t act_dim;      /* A, 1..8 */
+    int32_t layout;       /* DN_REPLAY_PLAIN or DN_REPLAY_RING */
+    int32_t reserved;     /* 0 */
+} dn_replay_config;
+typedef struct dn_replay_source {
+    const void *obs;       /* PLAIN: obs; RING: the ring of T + 1 rows */
+    const void *next_obs;  /* PLAIN: next_obs; RING: terminal_obs */
+    const void *actions;
+    const void *rewards;
+    const void *dones;     /* PLAIN: float32 dones; RING: uint8 done_flags */
+    const void *timeouts;  /* PLAIN: float32 timeouts; RING: uint8 timeout_flags */
+} dn_replay_source;
+/* Host only: needs no device and makes no HIP call.  out[0 .. count) <- the flat indices slot * N + env of rows start .. start + count - 1
+ * under (seed, draw), in HOST memory, by the code the kernel runs.  1 <= valid, n_envs <= 2^31 - 1, skip -1 or in 0..valid, 0 <= start,
+ * 0 <= count, start + count <= 2^31 - 1. */
+int32_t dn_replay_indices(uint64_t seed, uint64_t draw, int64_t valid, int64_t n_envs, int64_t skip, int64_t start, int64_t count,
+                          int64_t *out);
+/* SB3 ReplayBuffer.sample [from recall] for `batch` rows, 1 <= batch <= 2^31 - 1. */
+int32_t dn_replay_sample(const dn_replay_config *cfg, const dn_replay_source *src, int64_t batch, const int64_t *indices,
+                         const int64_t *draw_offset, float *obs, float *next_obs, float *actions, float *rewards, float *dones,
+                         int64_t *indices_out, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
