@@ -23,7 +23,8 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
            "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer",
-           "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam", "ReplaySampler"]
+           "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam", "ReplaySampler", "SacPolicyHead", "SacCriticLoss", "SacActorLoss",
+           "SacCritic"]
 
 
 def __getattr__(name):
@@ -57,9 +58,12 @@ def __getattr__(name):
     if name in ("replay", "ReplaySampler"):
         replay = importlib.import_module(__name__ + ".replay")
         return replay if name == "replay" else replay.ReplaySampler
+    if name in ("sac", "SacPolicyHead", "SacCriticLoss", "SacActorLoss"):
+        sac = importlib.import_module(__name__ + ".sac")
+        return sac if name == "sac" else getattr(sac, name)
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
-    if name in ("policy", "MlpActorCritic", "SacActor", "MlpValue"):
+    if name in ("policy", "MlpActorCritic", "SacActor", "SacCritic", "MlpValue"):
         policy = importlib.import_module(__name__ + ".policy")
         return policy if name == "policy" else getattr(policy, name)
     raise AttributeError(name)

@@ -152,6 +152,14 @@ REPLAY_PLAIN, REPLAY_RING = 0, 1
 REPLAY_MAX_OBS, REPLAY_MAX_ACT = 64, 8
 
 
+class DnSacConfig(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("target_entropy", C.c_double), ("ent_coef", C.c_double), ("log_std_min", C.c_double),
+                ("log_std_max", C.c_double), ("act_dim", C.c_int32), ("n_critics", C.c_int32), ("reserved", C.c_int64)]
+
+
+SAC_MAX_ACT, SAC_MAX_CRITICS = 8, 4
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -213,6 +221,11 @@ PROTOTYPES = {
     "dn_adam_step": (_I32, [C.POINTER(DnAdamConfig), C.POINTER(DnAdamTensor), _VP, _VP, _VP, _VP, _I64, _I32, _VP]),
     "dn_replay_indices": (_I32, [C.c_uint64, C.c_uint64, _I64, _I64, _I64, _I64, _I64, _VP]),
     "dn_replay_sample": (_I32, [C.POINTER(DnReplayConfig), C.POINTER(DnReplaySource), _I64] + [_VP] * 8 + [_I32, _VP]),
+    "dn_sac_loss_scratch_bytes": (_I64, [_I64, _I32]),
+    "dn_sac_policy": (_I32, [C.POINTER(DnSacConfig), _I64] + [_VP] * 5 + [_I32, _VP]),
+    "dn_sac_policy_backward": (_I32, [C.POINTER(DnSacConfig), _I64] + [_VP] * 7 + [_I32, _VP]),
+    "dn_sac_critic_loss": (_I32, [C.POINTER(DnSacConfig), _I64] + [_VP] * 11 + [_I64, _I32, _VP]),
+    "dn_sac_actor_loss": (_I32, [C.POINTER(DnSacConfig), _I64] + [_VP] * 10 + [_I64, _I32, _VP]),
     "dn_set_launch_events":(_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

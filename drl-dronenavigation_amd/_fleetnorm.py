@@ -1,5 +1,5 @@
 """What the classes that call the env-free kernels share on the Python side.  DeviceScratch (rownorm.RowNormalizer,
-retnorm.ReturnNormalizer, minibatch.MinibatchSampler, ppo.PpoLoss, optim.ClippedAdam): the device, the stream and the scratch with its capture guard.  FleetNormalizer, what
+retnorm.ReturnNormalizer, minibatch.MinibatchSampler, ppo.PpoLoss, optim.ClippedAdam, replay.ReplaySampler, the three heads of sac): the device, the stream and the scratch with its capture guard.  FleetNormalizer, what
 the two fleet-wide normalisers share beyond that: the clip and epsilon checks and the staging of tensors that are not dense.  Shapes, state
 and the C calls are the classes' own."""
 import ctypes as C

@@ -1,5 +1,5 @@
 // dn_capi_envfree.cpp -- the entry points of include/dronenav.h that take a device_id and no dn_env: the rollout glue, the history rows,
-// the two fleet normalisers, the minibatches, the PPO loss, the optimiser step and the replay minibatches.
+// the two fleet normalisers, the minibatches, the PPO loss, the optimiser step, the replay minibatches and the SAC loss heads.
 //
 // Every entry point validates its arguments, turns HIP failures into dn_status codes + the thread-local message of dn_capi.cpp
 // (dn_capi_fail.h), and never falls back to a CPU implementation.
@@ -566,6 +566,192 @@ int32_t dn_replay_sample(const dn_replay_config *cfg, const dn_replay_source *sr
     a.obs_dim = cfg->obs_dim; a.act_dim = cfg->act_dim; a.ring = ring;
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_replay(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+// ---- the SAC loss heads: SB3 SAC.train's squashed policy, critic, actor and entropy-coefficient losses [from recall] ------------------------
+/* what all four entry points ask of cfg and batch */
+static int32_t sac_call_ok(const dn_sac_config *cfg, int64_t batch)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (cfg->reserved != 0) return fail(DN_ERR_INVALID_ARGUMENT, "reserved must be 0 (got %lld)", (long long)cfg->reserved);
+    if (batch < 1 || batch > 0x7fffffffll) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
+    return DN_OK;
+}
+static int32_t sac_critics_ok(int32_t n_critics)
+{
+    return n_critics < 1 || n_critics > DN_SAC_MAX_CRITICS
+               ? fail(DN_ERR_INVALID_ARGUMENT, "n_critics must be in 1..%d (got %d)", DN_SAC_MAX_CRITICS, n_critics) : DN_OK;
+}
+/* the policy head's fields */
+static int32_t sac_policy_ok(const dn_sac_config *cfg, int64_t batch)
+{
+    if (const int32_t rc = sac_call_ok(cfg, batch)) return rc;
+    if (cfg->act_dim < 1 || cfg->act_dim > DN_SAC_MAX_ACT)
+        return fail(DN_ERR_INVALID_ARGUMENT, "act_dim must be in 1..%d (got %d)", DN_SAC_MAX_ACT, cfg->act_dim);
+    if (!std::isfinite(cfg->log_std_min) || !std::isfinite(cfg->log_std_max) || !(cfg->log_std_min < cfg->log_std_max))
+        return fail(DN_ERR_INVALID_ARGUMENT, "log_std_min and log_std_max must be finite with log_std_min < log_std_max (got %g, %g)", cfg->log_std_min,
+                    cfg->log_std_max);
+    return DN_OK;
+}
+/* the coefficient both losses read: the device's log_ent_coef, or the host's ent_coef */
+static int32_t sac_ent_coef_ok(const dn_sac_config *cfg, const float *log_ent_coef)
+{
+    if (!log_ent_coef && (!std::isfinite(cfg->ent_coef) || !(cfg->ent_coef >= 0.0)))
+        return fail(DN_ERR_INVALID_ARGUMENT, "ent_coef must be finite and >= 0 when log_ent_coef is NULL (got %g)", cfg->ent_coef);
+    return DN_OK;
+}
+/* required, aligned, and no output on an input or on another output; scratch takes its size first */
+static int32_t sac_pointers_ok(const DnArg *in, size_t n_in, DnArg *out, size_t n_out, const void *stats, const void *scratch, int64_t need)
+{
+    if (const DnArg *a = dn_first_missing(in, n_in)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_missing(out, n_out)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (((uintptr_t)stats | (uintptr_t)scratch) & 7u) return fail(DN_ERR_INVALID_ARGUMENT, "stats and scratch must be 8-byte aligned");
+    if (const DnArg *a = dn_first_misaligned(in, n_in, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    if (const DnArg *a = dn_first_misaligned(out, n_out, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    for (size_t k = 0; k < n_out; ++k)
+        if (scratch && out[k].p == scratch) out[k].bytes = (uintptr_t)need;
+    const DnArg *o, *i;
+    if (dn_first_overlap(out, n_out, in, n_in, &o, &i)) return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no output may alias an input", o->name, i->name);
+    for (size_t k = 0; k + 1 < n_out; ++k)
+        if (dn_first_overlap(&out[k], 1, &out[k + 1], n_out - k - 1, &o, &i))
+            return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no two outputs may share memory", o->name, i->name);
+    return DN_OK;
+}
+static const char *const SAC_Q[] = {"q[0]", "q[1]", "q[2]", "q[3]"}, *const SAC_NEXT_Q[] = {"next_q[0]", "next_q[1]", "next_q[2]", "next_q[3]"},
+                  *const SAC_D_Q[] = {"d_q[0]", "d_q[1]", "d_q[2]", "d_q[3]"}, *const SAC_Q_PI[] = {"q_pi[0]", "q_pi[1]", "q_pi[2]", "q_pi[3]"},
+                  *const SAC_D_Q_PI[] = {"d_q_pi[0]", "d_q_pi[1]", "d_q_pi[2]", "d_q_pi[3]"};
+
+int64_t dn_sac_loss_scratch_bytes(int64_t batch, int32_t n_critics)
+{
+    if (const int32_t rc = sac_critics_ok(n_critics)) return rc;
+    const long long d = dn_sac_loss_scratch_doubles(batch, n_critics);
+    if (d == 0) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^31 - 1 (got %lld)", (long long)batch);
+    return d * 8;
+}
+
+int32_t dn_sac_policy(const dn_sac_config *cfg, int64_t batch, const float *mean, const float *log_std, const float *noise, float *actions,
+                      float *log_prob, int32_t device_id, void *stream)
+{
+    if (const int32_t rc = sac_policy_ok(cfg, batch)) return rc;
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float), cells = rows * (uintptr_t)cfg->act_dim;
+    const DnArg in[] = {{"mean", mean, cells, false}, {"log_std", log_std, cells, false}, {"noise", noise, cells, false}};
+    DnArg out[] = {{"actions", actions, cells, false}, {"log_prob", log_prob, rows, false}};
+    if (const int32_t rc = sac_pointers_ok(in, 3, out, 2, nullptr, nullptr, 0)) return rc;
+    DnSacPolicyArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.mean = mean; a.raw = log_std; a.eps = noise; a.actions = actions; a.log_prob = log_prob;
+    a.lo = cfg->log_std_min; a.hi = cfg->log_std_max; a.batch = batch; a.act_dim = cfg->act_dim;
+    a.vec = cfg->act_dim % 4 == 0 && (((uintptr_t)mean | (uintptr_t)log_std | (uintptr_t)noise | (uintptr_t)actions) & 15u) == 0;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_sac_policy(a, false, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_sac_policy_backward(const dn_sac_config *cfg, int64_t batch, const float *mean, const float *log_std, const float *noise,
+                               const float *g_actions, const float *g_log_prob, float *d_mean, float *d_log_std, int32_t device_id,
+                               void *stream)
+{
+    if (const int32_t rc = sac_policy_ok(cfg, batch)) return rc;
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float), cells = rows * (uintptr_t)cfg->act_dim;
+    const DnArg in[] = {{"mean", mean, cells, false}, {"log_std", log_std, cells, false}, {"noise", noise, cells, false},
+                        {"g_actions", g_actions, cells, true}, {"g_log_prob", g_log_prob, rows, true}};
+    DnArg out[] = {{"d_mean", d_mean, cells, false}, {"d_log_std", d_log_std, cells, false}};
+    if (const int32_t rc = sac_pointers_ok(in, 5, out, 2, nullptr, nullptr, 0)) return rc;
+    DnSacPolicyArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.mean = mean; a.raw = log_std; a.eps = noise; a.g_a = g_actions; a.g_lp = g_log_prob; a.d_mean = d_mean; a.d_raw = d_log_std;
+    a.lo = cfg->log_std_min; a.hi = cfg->log_std_max; a.batch = batch; a.act_dim = cfg->act_dim;
+    a.vec = cfg->act_dim % 4 == 0
+            && (((uintptr_t)mean | (uintptr_t)log_std | (uintptr_t)noise | (uintptr_t)g_actions | (uintptr_t)d_mean | (uintptr_t)d_log_std) & 15u) == 0;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_sac_policy(a, true, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_sac_critic_loss(const dn_sac_config *cfg, int64_t batch, const float *const *q, const float *const *next_q,
+                           const float *next_log_prob, const float *rewards, const float *dones, const float *log_ent_coef,
+                           float *const *d_q, float *target_q, float *loss, double *stats, void *scratch, int64_t scratch_bytes,
+                           int32_t device_id, void *stream)
+{
+    if (const int32_t rc = sac_call_ok(cfg, batch)) return rc;
+    if (const int32_t rc = sac_critics_ok(cfg->n_critics)) return rc;
+    if (!std::isfinite(cfg->gamma) || !(cfg->gamma >= 0.0 && cfg->gamma <= 1.0))
+        return fail(DN_ERR_INVALID_ARGUMENT, "gamma must be finite and in [0, 1] (got %g)", cfg->gamma);
+    if (const int32_t rc = sac_ent_coef_ok(cfg, log_ent_coef)) return rc;
+    if (!q) return fail(DN_ERR_INVALID_ARGUMENT, "q is required");
+    if (!next_q) return fail(DN_ERR_INVALID_ARGUMENT, "next_q is required");
+    if (!d_q) return fail(DN_ERR_INVALID_ARGUMENT, "d_q is required");
+    const int C = cfg->n_critics;
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float);
+    DnArg in[2 * DN_SAC_MAX_CRITICS + 4], out[DN_SAC_MAX_CRITICS + 4];
+    size_t ni = 0, no = 0;
+    for (int c = 0; c < C; ++c) in[ni++] = DnArg{SAC_Q[c], q[c], rows, false};
+    for (int c = 0; c < C; ++c) in[ni++] = DnArg{SAC_NEXT_Q[c], next_q[c], rows, false};
+    in[ni++] = DnArg{"next_log_prob", next_log_prob, rows, false};
+    in[ni++] = DnArg{"rewards", rewards, rows, false};
+    in[ni++] = DnArg{"dones", dones, rows, false};
+    in[ni++] = DnArg{"log_ent_coef", log_ent_coef, sizeof(float), true};
+    for (int c = 0; c < C; ++c) out[no++] = DnArg{SAC_D_Q[c], d_q[c], rows, false};
+    out[no++] = DnArg{"target_q", target_q, rows, false};
+    out[no++] = DnArg{"loss", loss, sizeof(float), false};
+    out[no++] = DnArg{"stats", stats, 8 * sizeof(double), false};
+    out[no++] = DnArg{"scratch", scratch, 0, false};
+    const int64_t need = dn_sac_loss_scratch_bytes(batch, C);
+    if (scratch && dn_scratch_short(scratch_bytes, need)) return scratch_too_small(scratch_bytes, need, "dn_sac_loss_scratch_bytes");
+    if (const int32_t rc = sac_pointers_ok(in, ni, out, no, stats, scratch, need)) return rc;
+    DnSacLossArgs a;
+    std::memset(&a, 0, sizeof a);
+    for (int c = 0; c < C; ++c) { a.q[c] = q[c]; a.next_q[c] = next_q[c]; a.d_q[c] = d_q[c]; }
+    a.next_log_prob = next_log_prob; a.rewards = rewards; a.dones = dones; a.log_ent_coef = log_ent_coef;
+    a.target_q = target_q; a.loss = loss; a.stats = stats; a.part = (double *)scratch;
+    a.gamma = cfg->gamma; a.ent_coef = cfg->ent_coef;
+    a.batch = batch; a.nblk = dn_rownorm_blocks(batch); a.n_critics = C; a.mode = DN_SAC_CRITIC;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_sac_loss(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_sac_actor_loss(const dn_sac_config *cfg, int64_t batch, const float *log_prob, const float *const *q_pi,
+                          const float *log_ent_coef, float *d_log_prob, float *const *d_q_pi, float *d_log_ent_coef, float *actor_loss,
+                          float *ent_coef_loss, double *stats, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (const int32_t rc = sac_call_ok(cfg, batch)) return rc;
+    if (const int32_t rc = sac_critics_ok(cfg->n_critics)) return rc;
+    if (!std::isfinite(cfg->target_entropy)) return fail(DN_ERR_INVALID_ARGUMENT, "target_entropy must be finite (got %g)", cfg->target_entropy);
+    if (const int32_t rc = sac_ent_coef_ok(cfg, log_ent_coef)) return rc;
+    if (!q_pi) return fail(DN_ERR_INVALID_ARGUMENT, "q_pi is required");
+    if (!d_q_pi) return fail(DN_ERR_INVALID_ARGUMENT, "d_q_pi is required");
+    if (log_ent_coef && !d_log_ent_coef) return fail(DN_ERR_INVALID_ARGUMENT, "d_log_ent_coef is required with log_ent_coef");
+    if (!log_ent_coef && d_log_ent_coef)
+        return fail(DN_ERR_INVALID_ARGUMENT, "d_log_ent_coef must be NULL without log_ent_coef: a fixed coefficient has no gradient");
+    const int C = cfg->n_critics;
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float);
+    DnArg in[DN_SAC_MAX_CRITICS + 2], out[DN_SAC_MAX_CRITICS + 6];
+    size_t ni = 0, no = 0;
+    in[ni++] = DnArg{"log_prob", log_prob, rows, false};
+    for (int c = 0; c < C; ++c) in[ni++] = DnArg{SAC_Q_PI[c], q_pi[c], rows, false};
+    in[ni++] = DnArg{"log_ent_coef", log_ent_coef, sizeof(float), true};
+    out[no++] = DnArg{"d_log_prob", d_log_prob, rows, false};
+    for (int c = 0; c < C; ++c) out[no++] = DnArg{SAC_D_Q_PI[c], d_q_pi[c], rows, false};
+    out[no++] = DnArg{"d_log_ent_coef", d_log_ent_coef, sizeof(float), true};
+    out[no++] = DnArg{"actor_loss", actor_loss, sizeof(float), false};
+    out[no++] = DnArg{"ent_coef_loss", ent_coef_loss, sizeof(float), false};
+    out[no++] = DnArg{"stats", stats, 8 * sizeof(double), false};
+    out[no++] = DnArg{"scratch", scratch, 0, false};
+    const int64_t need = dn_sac_loss_scratch_bytes(batch, C);
+    if (scratch && dn_scratch_short(scratch_bytes, need)) return scratch_too_small(scratch_bytes, need, "dn_sac_loss_scratch_bytes");
+    if (const int32_t rc = sac_pointers_ok(in, ni, out, no, stats, scratch, need)) return rc;
+    DnSacLossArgs a;
+    std::memset(&a, 0, sizeof a);
+    for (int c = 0; c < C; ++c) { a.q[c] = q_pi[c]; a.d_q[c] = d_q_pi[c]; }
+    a.log_prob = log_prob; a.log_ent_coef = log_ent_coef;
+    a.d_log_prob = d_log_prob; a.d_log_ent_coef = d_log_ent_coef; a.loss = actor_loss; a.ent_coef_loss = ent_coef_loss;
+    a.stats = stats; a.part = (double *)scratch;
+    a.target_entropy = cfg->target_entropy; a.ent_coef = cfg->ent_coef;
+    a.batch = batch; a.nblk = dn_rownorm_blocks(batch); a.n_critics = C; a.mode = DN_SAC_ACTOR;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_sac_loss(a, (hipStream_t)stream));
     return DN_OK;
 }
 }  // extern "C"

@@ -412,6 +412,44 @@ struct DnReplayArgs {
     int obs_dim, act_dim, ring;                        // ring: DN_REPLAY_RING
 };
 hipError_t dn_launch_replay(const DnReplayArgs &a, hipStream_t stream);                                                        // dn_replay.hip
+// The SAC loss heads (dn_sac_policy, dn_sac_policy_backward, dn_sac_critic_loss, dn_sac_actor_loss; dn_sac_loss.hip).  The squashed
+// policy head and its backward are one launch each, a row per lane, nothing reduced.  The two losses form float64 sums per block of
+// DN_ROWNORM_BLOCK_ROWS consecutive rows, the normalisers' constant, so every bit depends on (batch, n_critics) alone.  The scratch is
+// doubles only, and one size serves both losses:
+//   part   [blocks(batch)][2 n_critics + 2]   critic: e_c^2 per critic, y, q_c per critic (2 n_critics + 1 used)
+//                                             actor:  alpha lp - qmin, lp + target_entropy, lp, qmin (4 used)
+// 0 = refuse (n_critics outside 1..DN_SAC_MAX_CRITICS, batch < 1 or beyond 2^31 - 1 rows).
+struct DnSacPolicyArgs {
+    const float *mean, *raw, *eps;                     // [batch][act_dim]; raw: the log_std head before the clamp
+    const float *g_a, *g_lp;                           // backward: [batch][act_dim], [batch]; NULL = zero
+    float *actions, *log_prob;                         // forward outputs
+    float *d_mean, *d_raw;                             // backward outputs
+    double lo, hi;                                     // log_std_min, log_std_max
+    long long batch;
+    int act_dim, vec;                                  // vec: act_dim % 4 == 0 and every [batch][act_dim] pointer of the call is 16-byte aligned
+};
+constexpr int DN_SAC_CRITIC = 0, DN_SAC_ACTOR = 1;
+struct DnSacLossArgs {
+    const float *q[DN_SAC_MAX_CRITICS];                // critic: q_c; actor: q_pi_c
+    const float *next_q[DN_SAC_MAX_CRITICS];           // critic only
+    float *d_q[DN_SAC_MAX_CRITICS];
+    const float *next_log_prob, *rewards, *dones;      // critic only
+    const float *log_prob;                             // actor only
+    const float *log_ent_coef;                         // device [1]; NULL = the fixed ent_coef
+    float *target_q;                                   // critic only
+    float *d_log_prob, *d_log_ent_coef, *ent_coef_loss;   // actor only; d_log_ent_coef NULL with a fixed coefficient
+    float *loss;                                       // critic_loss or actor_loss
+    double *stats, *part;
+    double gamma, target_entropy, ent_coef;
+    long long batch, nblk;                             // nblk = blocks(batch)
+    int n_critics, mode;                               // mode: DN_SAC_CRITIC or DN_SAC_ACTOR
+};
+inline long long dn_sac_loss_scratch_doubles(long long batch, int n_critics)
+{
+    return n_critics < 1 || n_critics > DN_SAC_MAX_CRITICS || batch < 1 || batch > 0x7fffffffll ? 0 : dn_rownorm_blocks(batch) * (2 * n_critics + 2);
+}
+hipError_t dn_launch_sac_policy(const DnSacPolicyArgs &a, bool backward, hipStream_t stream);                                  // dn_sac_loss.hip
+hipError_t dn_launch_sac_loss(const DnSacLossArgs &a, hipStream_t stream);                                                     // dn_sac_loss.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

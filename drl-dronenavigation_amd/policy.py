@@ -124,3 +124,19 @@ class SacActor(nn.Module):
     def forward(self, obs, deterministic=False):
         mean, log_std = self.mean_log_std(obs)
         return self.squash(mean, log_std, None if deterministic else torch.randn_like(mean))[0]
+
+
+class SacCritic(nn.Module):
+    """The critics of the reference's SAC agent (Sol/Model/PBDroneSimulator.py:297-338, net_arch qf=[256, 256, 128], n_critics = 2): SB3's
+    ContinuousCritic [3P-recall] -- n_critics independent MLPs over cat(obs, actions), ReLU, one linear output each, default torch
+    initialisation.  forward(obs, actions) returns a tuple of n_critics tensors [N]: what sac.SacCriticLoss and sac.SacActorLoss take.
+    The target critics are a second instance that the caller keeps by Polyak averaging."""
+
+    def __init__(self, obs_dim=13, act_dim=4, qf=(256, 256, 128), n_critics=2):
+        super().__init__()
+        self.q_networks = nn.ModuleList(nn.Sequential(*_mlp((obs_dim + act_dim,) + tuple(qf), nn.ReLU), nn.Linear(qf[-1], 1))
+                                        for _ in range(n_critics))
+
+    def forward(self, obs, actions):
+        x = torch.cat((obs, actions), dim=-1)
+        return tuple(q(x).squeeze(-1) for q in self.q_networks)

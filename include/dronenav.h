@@ -1091,6 +1091,90 @@ int32_t dn_replay_sample(const dn_replay_config *cfg, const dn_replay_source *sr
                          const int64_t *draw_offset, float *obs, float *next_obs, float *actions, float *rewards, float *dones,
                          int64_t *indices_out, int32_t device_id, void *stream);
 
+/* The SAC loss heads on the device: SB3's SAC.train body [from recall] between the networks' head outputs and the scalar losses -- the
+ * squashed Gaussian's reparametrised sample with its log-probability, the TD target and the critic loss, the actor loss, the
+ * entropy-coefficient loss, and the gradients with respect to every head output.  Env-free; the networks' own forward and backward, the
+ * optimisers (dn_adam_step with eps 1e-8 and no clip), the Polyak update and the learner loop stay the caller's.  One gradient step of
+ * SB3, for a replay batch (obs, next_obs, actions, rewards, dones), an actor with heads mu and log_std, C critics and log_ent_coef:
+ *   a_pi, lp      = squash(mu(obs), log_std(obs), eps)                      dn_sac_policy; backward dn_sac_policy_backward
+ *   a_n, lp_n     = squash(mu(next_obs), log_std(next_obs), eps_n)          dn_sac_policy, no gradient
+ *   critic_loss   from Q_c(obs, actions), Qtarget_c(next_obs, a_n), lp_n    dn_sac_critic_loss
+ *   actor_loss, ent_coef_loss from lp, Q_c(obs, a_pi)                       dn_sac_actor_loss
+ * Arithmetic (csrc/dn_sac_math.h, which host and device both run): every float32 input is widened to float64 once; every operation below
+ *   is an IEEE float64 operation, no contraction; exp, tanh and log are the float64 library functions; every output is rounded once.  NaN
+ *   and infinity are not special-cased.
+ * The squashed policy head, row b < batch, column j < A = act_dim, raw = the log_std head's output, eps = the caller's N(0, 1) draw:
+ *   ls = clamp(raw, log_std_min, log_std_max)     torch.clamp: a NaN stays, the gradient passes at the bounds
+ *   std = exp(ls)            pre = mean + std eps            a = tanh(pre)
+ *   t = exp(-2 |pre|)        J = 4 t / ((1 + t)(1 + t))      sech^2(pre); never formed as 1 - a a, which is lost once |pre| > 9
+ *   term_j = -0.5 eps^2 - ls - 0.5 log(2 pi) - log(J + 1e-6)      eps itself, not (pre - mean) / std, which loses eps at a small std
+ *   log_prob_b = term_0 + term_1 + ..., j ascending;  actions_bj = a
+ *   Where the literal float32 expression of SB3 is well conditioned the two agree (|pre| <= 6, log_std >= -5: to 2^-40 of the terms plus
+ *   the literal form's own cancellation 2^-51 / (J + 1e-6)).
+ * Its backward, given g_a[batch][A] = d L / d actions and g_lp[batch] = d L / d log_prob (NULL = zero), recomputed from mean, raw, eps:
+ *   K = 2 a J / (J + 1e-6);  d_pre = g_a J + g_lp K;  d_mean = d_pre;  d_ls = d_pre std eps - g_lp;
+ *   d_log_std = d_ls where log_std_min <= raw <= log_std_max, else 0.
+ * The critic loss, row b, critic c < C = n_critics:
+ *   alpha = exp(log_ent_coef[0]), read from device memory when the kernel runs and rounded correctly (csrc/dn_exp_cr.h); with
+ *           log_ent_coef NULL the host value ent_coef (SB3's fixed coefficient)
+ *   nq = min_c next_q_c                           c ascending; a NaN on either side wins, as in torch.min
+ *   y = rewards + (1 - dones) gamma (nq - alpha next_log_prob)
+ *   e_c = q_c - y;  critic_loss = 0.5 (S_0 / batch + S_1 / batch + ...), S_c = sum_b e_c^2, c ascending;  d_q_c = e_c / batch
+ *   target_q = (float) y: for the caller's logging; the loss uses the unrounded y.
+ *   stats[8] = critic_loss, alpha, mean_b y, mean_b q_0 .. mean_b q_3 (0 from n_critics on), 0.
+ * The actor and entropy-coefficient loss, row b:
+ *   qmin = min_c q_pi_c                           c ascending; a tie picks the lowest c, the first NaN wins
+ *   actor_loss = sum_b (alpha log_prob - qmin) / batch;  d_log_prob = alpha / batch;  d_q_pi_c = -[c is the pick] / batch
+ *   with log_ent_coef: ent_coef_loss = -(log_ent_coef m), d_log_ent_coef = -m, m = sum_b (log_prob + target_entropy) / batch
+ *   with a fixed coefficient ent_coef_loss = 0, d_log_ent_coef must be NULL and is not written.
+ *   stats[8] = actor_loss, ent_coef_loss, alpha, mean_b log_prob, mean_b qmin, d_log_ent_coef (0 when fixed), 0, 0.
+ *   Both losses read log_ent_coef when they run: a caller who steps the coefficient's optimiser after the actor loss reproduces SB3's order.
+ * Per-critic inputs and outputs (q, next_q, d_q, q_pi, d_q_pi) are HOST arrays of n_critics device pointers, each to `batch` dense
+ *   float32.  gamma, target_entropy, ent_coef, log_std_min, log_std_max are host values: a captured graph keeps the ones it was
+ *   captured with.  Each entry point reads the fields of dn_sac_config that its arithmetic names, and `reserved`.
+ * Bit-reproducible: the policy head is a row per lane with nothing reduced; [batch][A] tensors move as 16-byte words when A % 4 == 0 and
+ *   all of them are 16-byte aligned, else as 4-byte words, with the same bits.  The sums over b are float64 sums per block of 1024
+ *   consecutive rows (lanes by a fixed tree, waves ascending), the blocks added in ascending order: the order of every float64 operation
+ *   is a function of (batch, act_dim, n_critics) alone.
+ *   scratch        the caller's device memory, 8-byte aligned, at least dn_sac_loss_scratch_bytes(batch, n_critics): the block sums.  One
+ *                  size serves both losses.  The library allocates nothing and keeps nothing between calls.
+ * Launches on `stream`: one for dn_sac_policy, one for dn_sac_policy_backward, two for each loss (rows + block sums, a one-wave merge).  No
+ *   workgroup waits for another, no atomics, capturable.  No output may overlap an input or another output.
+ * Validates before the first device call: DN_ERR_INVALID_ARGUMENT with a dn_last_error text that names the argument and the value.
+ * Layout of dn_sac_config: gamma at 0, target_entropy at 8, ent_coef at 16, log_std_min at 24, log_std_max at 32, act_dim at 40,
+ *   n_critics at 44, reserved at 48; 56 bytes. */
+#define DN_SAC_MAX_ACT 8
+#define DN_SAC_MAX_CRITICS 4
+typedef struct dn_sac_config {
+    double gamma;           /* in [0, 1]; SB3's 0.99 (critic loss) */
+    double target_entropy;  /* finite; SB3's "auto" is -act_dim (actor loss) */
+    double ent_coef;        /* >= 0, finite: alpha when log_ent_coef is NULL (both losses) */
+    double log_std_min;     /* finite, < log_std_max; SB3's -20 (policy head) */
+    double log_std_max;     /* finite; SB3's 2 (policy head) */
+    int32_t act_dim;        /* 1..8 (policy head) */
+    int32_t n_critics;      /* 1..4 (both losses) */
+    int64_t reserved;       /* 0 */
+} dn_sac_config;
+/* Bytes of scratch for either loss over `batch` rows and `n_critics` critics: 8 (2 n_critics + 2) per block of 1024 rows; a negative
+ * dn_status for batch < 1 or beyond 2^31 - 1, or n_critics outside 1..4. */
+int64_t dn_sac_loss_scratch_bytes(int64_t batch, int32_t n_critics);
+/* SB3 SquashedDiagGaussianDistribution [from recall]: actions[batch][A] and log_prob[batch] from mean, log_std (raw), noise [batch][A]. */
+int32_t dn_sac_policy(const dn_sac_config *cfg, int64_t batch, const float *mean, const float *log_std, const float *noise, float *actions,
+                      float *log_prob, int32_t device_id, void *stream);
+/* Its backward: d_mean[batch][A], d_log_std[batch][A] from g_actions[batch][A] and g_log_prob[batch], either of which may be NULL (zero). */
+int32_t dn_sac_policy_backward(const dn_sac_config *cfg, int64_t batch, const float *mean, const float *log_std, const float *noise,
+                               const float *g_actions, const float *g_log_prob, float *d_mean, float *d_log_std, int32_t device_id,
+                               void *stream);
+/* SB3 SAC.train [from recall]: the TD target, the critic loss, its statistics and d_q_c. */
+int32_t dn_sac_critic_loss(const dn_sac_config *cfg, int64_t batch, const float *const *q, const float *const *next_q,
+                           const float *next_log_prob, const float *rewards, const float *dones, const float *log_ent_coef,
+                           float *const *d_q, float *target_q, float *loss, double *stats, void *scratch, int64_t scratch_bytes,
+                           int32_t device_id, void *stream);
+/* SB3 SAC.train [from recall]: the actor loss and the entropy-coefficient loss, their statistics and gradients. */
+int32_t dn_sac_actor_loss(const dn_sac_config *cfg, int64_t batch, const float *log_prob, const float *const *q_pi,
+                          const float *log_ent_coef, float *d_log_prob, float *const *d_q_pi, float *d_log_ent_coef, float *actor_loss,
+                          float *ent_coef_loss, double *stats, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

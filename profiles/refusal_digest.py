@@ -3,7 +3,7 @@
 
     python profiles/refusal_digest.py LIBRARY
 
-Walks the 23 entry points of include/dronenav.h that take a device_id and no env.  Each starts from one valid call; then every argument
+Walks the 28 entry points of include/dronenav.h that take a device_id and no env.  Each starts from one valid call; then every argument
 -- a config field and a field of a host table count as arguments -- takes each value of its FULL set alone, and every pair of arguments
 takes each pair of values of their SHORT sets, so that a caller's two mistakes meet and the order of the checks shows.
 
@@ -46,6 +46,9 @@ T.DnMinibatchConfig = T.make("DnMinibatchConfig", [("seed", _U64), ("epoch", _U6
 T.DnPpoLossConfig = T.make("DnPpoLossConfig", [(n, _F64) for n in ("clip_range", "clip_range_vf", "ent_coef", "vf_coef")]
                            + [("act_dim", _I32), ("reserved", _I32)])
 T.DnAdamTensor = T.make("DnAdamTensor", [(n, _VP) for n in ("param", "grad", "exp_avg", "exp_avg_sq")] + [("count", _I64)])
+T.DnSacConfig = T.make("DnSacConfig", [(n, _F64) for n in ("gamma", "target_entropy", "ent_coef", "log_std_min", "log_std_max")]
+                       + [("act_dim", _I32), ("n_critics", _I32), ("reserved", _I64)])
+T.DnSacPointer = T.make("DnSacPointer", [("p", _VP)])        # one entry of a host array of device pointers
 T.DnAdamConfig = T.make("DnAdamConfig", [(n, _F64) for n in ("beta1", "beta2", "eps", "max_grad_norm")] + [("n_tensors", _I32), ("flags", _I32)])
 
 DEVICE_ID = 1 << 20
@@ -69,6 +72,9 @@ NET = [p("w1"), p("w2"), p("w3"), p("wh"), p("b1"), p("b2"), p("b3"), p("bh"), p
 HISTORY = struct("cfg", T.DnHistoryConfig, [i32("frames", 2), i32("actions", 1), i32("extra_dim", 0), i32("reserved", 0)])
 ROWNORM = struct("cfg", T.DnRownormConfig, [i32("width", 13), f32("clip", 10.0), f64("epsilon", 1e-8)])
 RETNORM = struct("cfg", T.DnRetnormConfig, [f64("gamma", 0.99), f64("epsilon", 1e-8), f32("clip", 10.0), i32("reserved", 0)])
+SAC = struct("cfg", T.DnSacConfig, [f64("gamma", 0.99), f64("target_entropy", -4.0), f64("ent_coef", 0.2), f64("log_std_min", -20.0),
+                                    f64("log_std_max", 2.0), i32("act_dim", 4), i32("n_critics", 2), i64("reserved", 0)])
+def sac_table(name): return struct(name, T.DnSacPointer, [p("p")], count=2, room=4)
 SCRATCH = i64("scratch_bytes", None)         # None: what the entry point's dn_X_scratch_bytes gives for the valid call
 
 # entry point -> (arguments in order, the call that sizes its scratch or None)
@@ -115,6 +121,16 @@ ENTRY_POINTS = {
                              room=T.ADAM_MAX_TENSORS),
                       p("lr"), p("state"), p("stats"), p("scratch"), SCRATCH, DEV, STREAM],
                      ("dn_adam_scratch_bytes", (lambda v: (_I64 * 2)(*v), _I32), ((100, 5000), 2))),
+    "dn_sac_loss_scratch_bytes": ([i64("batch", 8), i32("n_critics", 2)], None),
+    "dn_sac_policy": ([SAC, i64("batch", 8)] + [p(n) for n in ("mean", "log_std", "noise", "actions", "log_prob")] + [DEV, STREAM], None),
+    "dn_sac_policy_backward": ([SAC, i64("batch", 8)] + [p(n) for n in ("mean", "log_std", "noise", "g_actions", "g_log_prob", "d_mean", "d_log_std")]
+                               + [DEV, STREAM], None),
+    "dn_sac_critic_loss": ([SAC, i64("batch", 8), sac_table("q"), sac_table("next_q")] + [p(n) for n in ("next_log_prob", "rewards", "dones", "log_ent_coef")]
+                           + [sac_table("d_q")] + [p(n) for n in ("target_q", "loss", "stats", "scratch")] + [SCRATCH, DEV, STREAM],
+                           ("dn_sac_loss_scratch_bytes", (_I64, _I32), (8, 2))),
+    "dn_sac_actor_loss": ([SAC, i64("batch", 8), p("log_prob"), sac_table("q_pi"), p("log_ent_coef"), p("d_log_prob"), sac_table("d_q_pi")]
+                          + [p(n) for n in ("d_log_ent_coef", "actor_loss", "ent_coef_loss", "stats", "scratch")] + [SCRATCH, DEV, STREAM],
+                          ("dn_sac_loss_scratch_bytes", (_I64, _I32), (8, 2))),
 }
 
 
