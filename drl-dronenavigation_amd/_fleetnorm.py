@@ -1,7 +1,9 @@
 """What the classes that call the env-free kernels share on the Python side.  DeviceScratch (rownorm.RowNormalizer,
-retnorm.ReturnNormalizer, minibatch.MinibatchSampler, ppo.PpoLoss, optim.ClippedAdam, replay.ReplaySampler, the three heads of sac): the device, the stream and the scratch with its capture guard.  FleetNormalizer, what
-the two fleet-wide normalisers share beyond that: the clip and epsilon checks and the staging of tensors that are not dense.  Shapes, state
-and the C calls are the classes' own."""
+retnorm.ReturnNormalizer, minibatch.MinibatchSampler, optim.ClippedAdam, replay.ReplaySampler, and through LossHead ppo.PpoLoss and the
+three heads of sac): the device, the stream and the scratch with its capture guard.  FleetNormalizer, what the two fleet-wide normalisers
+share beyond that: the clip and epsilon checks and the staging of tensors that are not dense.  LossHead, what the four loss heads share
+beyond it: the checks of a constructor count, of the rows of a call and of a tensor by argument name, and the call counter with its
+stale-backward refusal.  Shapes, state and the C calls are the classes' own."""
 import ctypes as C
 import math
 
@@ -34,6 +36,46 @@ class DeviceScratch:
                                    "this size before capturing")
             self._scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
         return self._scratch
+
+
+class LossHead(DeviceScratch):
+    """A head keeps batch_size (the most rows of a call) and counts its forward calls in _calls: the autograd functions note the count at
+    forward, and _stale refuses a backward that comes after a later forward."""
+
+    def __init__(self, device):
+        super().__init__(device)
+        self._calls = 0
+
+    def _count(self, name, v, top):
+        """A constructor argument that is an integer in 1..top; usable before __init__."""
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
+            raise ValueError(f"{self._NAME}.{name} must be an integer in 1..{top}, got {v!r}")
+
+    def _check(self, name, t, shapes):
+        """t: a dense float32 tensor on the device of `shapes`, one shape or a list of them."""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{self._NAME}: {name} must be a tensor, got {type(t).__name__}")
+        shapes = shapes if isinstance(shapes, list) else [shapes]
+        if tuple(t.shape) not in shapes or t.dtype != torch.float32 or t.device != self.device:
+            want = " or ".join(str(list(s)) for s in shapes)
+            raise ValueError(f"{self._NAME}: {name} must be torch.float32 {want} on {self.device}, got {t.dtype} {list(t.shape)} on {t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{self._NAME}: {name} must be dense (strides {t.stride()}); the kernel reads it in place and stages nothing")
+
+    def _rows(self, name, t, *cols):
+        """count, the rows of a call, from its leading tensor t [count, *cols]: 1..batch_size of them, and t passes _check."""
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 + len(cols):
+            raise ValueError(f"{self._NAME}: {name} must be a tensor [{', '.join(['count'] + [str(c) for c in cols])}]")
+        count = int(t.shape[0])
+        if not 1 <= count <= self.batch_size:
+            raise ValueError(f"{self._NAME}: {name} has {count} rows; a call takes 1..{self.batch_size} (batch_size)")
+        self._check(name, t, (count,) + cols)
+        return count
+
+    def _stale(self, ctx):
+        if ctx.call != self._calls:
+            raise RuntimeError(f"{self._NAME}: backward of call {ctx.call} after call {self._calls}: the gradients live in static buffers that the "
+                               "later forward has overwritten; call backward() before the next forward")
 
 
 class FleetNormalizer(DeviceScratch):

@@ -8,6 +8,7 @@
 #include "dn_internal.h"
 #include "dn_permute.h"
 #include "dn_replay_draw.h"
+#include "dn_row_sums.h"
 
 #include <cmath>
 #include <cstring>
@@ -420,7 +421,7 @@ int32_t dn_ppo_loss(const dn_ppo_loss_config *cfg, int64_t batch, const float *m
     a.clip_range = cfg->clip_range; a.clip_range_vf = cfg->clip_range_vf; a.ent_coef = cfg->ent_coef; a.vf_coef = cfg->vf_coef;
     a.batch = batch; a.nblk = dn_rownorm_blocks(batch);
     a.act_dim = cfg->act_dim;
-    a.vec = cfg->act_dim % 4 == 0 && (((uintptr_t)mean | (uintptr_t)actions | (uintptr_t)d_mean) & 15u) == 0;
+    a.vec = dn_rows_vec16(cfg->act_dim, mean, actions, d_mean);
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_ppo_loss(a, (hipStream_t)stream));
     return DN_OK;
@@ -642,7 +643,7 @@ int32_t dn_sac_policy(const dn_sac_config *cfg, int64_t batch, const float *mean
     std::memset(&a, 0, sizeof a);
     a.mean = mean; a.raw = log_std; a.eps = noise; a.actions = actions; a.log_prob = log_prob;
     a.lo = cfg->log_std_min; a.hi = cfg->log_std_max; a.batch = batch; a.act_dim = cfg->act_dim;
-    a.vec = cfg->act_dim % 4 == 0 && (((uintptr_t)mean | (uintptr_t)log_std | (uintptr_t)noise | (uintptr_t)actions) & 15u) == 0;
+    a.vec = dn_rows_vec16(cfg->act_dim, mean, log_std, noise, actions);
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_sac_policy(a, false, (hipStream_t)stream));
     return DN_OK;
@@ -662,8 +663,7 @@ int32_t dn_sac_policy_backward(const dn_sac_config *cfg, int64_t batch, const fl
     std::memset(&a, 0, sizeof a);
     a.mean = mean; a.raw = log_std; a.eps = noise; a.g_a = g_actions; a.g_lp = g_log_prob; a.d_mean = d_mean; a.d_raw = d_log_std;
     a.lo = cfg->log_std_min; a.hi = cfg->log_std_max; a.batch = batch; a.act_dim = cfg->act_dim;
-    a.vec = cfg->act_dim % 4 == 0
-            && (((uintptr_t)mean | (uintptr_t)log_std | (uintptr_t)noise | (uintptr_t)g_actions | (uintptr_t)d_mean | (uintptr_t)d_log_std) & 15u) == 0;
+    a.vec = dn_rows_vec16(cfg->act_dim, mean, log_std, noise, g_actions, d_mean, d_log_std);
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_sac_policy(a, true, (hipStream_t)stream));
     return DN_OK;

@@ -13,7 +13,7 @@
 constexpr int FR_BATCH = 8;                            // pairs in flight ahead of the sequential chain
 
 // The sum over the 64 lanes of a wave in a fixed tree (lane i + lane i + 32, then + 16, ... + 1); lane 0 holds it.  The lane order of the
-// block moments that are formed a row per lane (dn_retnorm.hip, dn_minibatch.hip).
+// block moments that are formed a row per lane (dn_retnorm.hip, dn_minibatch.hip) and of the loss heads' block sums (dn_row_sums.h).
 __device__ __forceinline__ double fr_wave_sum(double v)
 {
 #pragma unroll

@@ -7,18 +7,17 @@
 // Two ordinary launches on the caller's stream; no workgroup ever waits for another, nothing is allocated, no atomics:
 //   1. pl_rows_kernel   one workgroup per block of DN_ROWNORM_BLOCK_ROWS consecutive rows, one row per lane.  Lanes 0 .. A - 1 first
 //                       widen log_std and form exp(-log_std) (dn_exp_cr.h) into LDS; after one barrier every lane loads its row (16-byte words when
-//                       A % 4 == 0 and mean, actions and d_mean are 16-byte aligned: the same values into the same registers, so the same
-//                       bits; else 4-byte words, a wave's A loads of a field covering its contiguous 256 A bytes between them), evaluates
+//                       dn_rows_vec16 holds of mean, actions and d_mean, else 4-byte words: dn_load_row of dn_row_sums.h), evaluates
 //                       the expressions of the header and stores d_mean, d_value and log_prob_out.  The block then forms 4 + A float64
 //                       sums -- min(p1, p2), (returns - vpred)^2, (ratio - 1) - lr, the clip indicator, and g (z_j^2 - 1) per column --
-//                       across the lanes of a wave by the fixed tree of dn_fleet_rms.h, then the waves in ascending order through LDS;
-//                       lanes past the end contribute +0.0.  The sums go to part[block][4 + A].
-//   2. pl_merge_kernel  ONE wave: lane q < 4 + A adds column q of the block sums in ascending block order (plain sums, FR_BATCH loads in
-//                       flight ahead of the chain); lane 0 then writes stats[8] and the float32 loss, lanes 4 .. 4 + A - 1 d_log_std.
-// The order of every float64 operation is a function of (batch, act_dim) alone: the same call gives the same bits every time, and a
-// captured graph replays it.  ratio = exp(lr) is the float64 library function; exp(-log_std) is the correctly rounded one of dn_exp_cr.h.
+//                       by fr_block_sums; lanes past the end contribute +0.0.  The sums go to part[block][4 + A].
+//   2. pl_merge_kernel  ONE wave: lane q < 4 + A adds column q of the block sums by fr_sum_column; lane 0 then writes stats[8] and the
+//                       float32 loss, lanes 4 .. 4 + A - 1 d_log_std.
+// The order of every float64 sum is that of dn_row_sums.h, a function of (batch, act_dim) alone: the same call gives the same bits every
+// time, and a captured graph replays it.  ratio = exp(lr) is the float64 library function; exp(-log_std) is the correctly rounded one of
+// dn_exp_cr.h.
 #include "dn_internal.h"
-#include "dn_fleet_rms.h"
+#include "dn_row_sums.h"
 #include "dn_exp_cr.h"
 
 namespace {
@@ -27,39 +26,6 @@ constexpr int PL_THREADS = (int)DN_ROWNORM_BLOCK_ROWS;  // launch 1: one row per
 constexpr int PL_WAVES = PL_THREADS / 64;
 constexpr double PL_HALF_LOG_2PI = 0.9189385332046727;  // 0.5 log(2 pi)
 constexpr double PL_ENTROPY_0 = 1.4189385332046727;     // 0.5 + 0.5 log(2 pi)
-
-// One row of A float32 columns into registers: 16-byte words (A % 4 == 0, p 16-byte aligned) or 4-byte words, the same values either way.
-template <int A>
-__device__ __forceinline__ void pl_load_row(const float *__restrict__ p, const long long row, const bool vec, float (&x)[A])
-{
-    if constexpr (A % 4 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < A / 4; ++q) {
-                const float4 v = reinterpret_cast<const float4 *>(p)[row * (A / 4) + q];
-                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < A; ++j) x[j] = p[row * A + j];
-}
-
-template <int A>
-__device__ __forceinline__ void pl_store_row(float *__restrict__ p, const long long row, const bool vec, const float (&x)[A])
-{
-    if constexpr (A % 4 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < A / 4; ++q)
-                reinterpret_cast<float4 *>(p)[row * (A / 4) + q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < A; ++j) p[row * A + j] = x[j];
-}
 
 template <int A>
 __global__ __launch_bounds__(PL_THREADS) void pl_rows_kernel(const DnPpoLossArgs a)
@@ -89,8 +55,8 @@ __global__ __launch_bounds__(PL_THREADS) void pl_rows_kernel(const DnPpoLossArgs
     if (tid < nrows) {
         const long long row = row0 + tid;
         float mu[A], ac[A], dm[A];
-        pl_load_row<A>(a.mean, row, a.vec != 0, mu);
-        pl_load_row<A>(a.actions, row, a.vec != 0, ac);
+        dn_load_row<A>(a.mean, row, a.vec != 0, mu);
+        dn_load_row<A>(a.actions, row, a.vec != 0, ac);
         const double adv = (double)a.advantages[row], olp = (double)a.old_log_prob[row], ret = (double)a.returns[row];
         const double val = (double)a.value[row];
 
@@ -124,7 +90,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_rows_kernel(const DnPpoLossArgs
             dm[j] = (float)(g * z[j] * inv_s[j]);
             s[4 + j] = g * (z[j] * z[j] - 1.0);
         }
-        pl_store_row<A>(a.d_mean, row, a.vec != 0, dm);
+        dn_store_row<A>(a.d_mean, row, a.vec != 0, dm);
         a.d_value[row] = (float)(a.vf_coef * -2.0 * e * inside / nb);
         if (a.log_prob_out) a.log_prob_out[row] = (float)logp;
 
@@ -134,17 +100,11 @@ __global__ __launch_bounds__(PL_THREADS) void pl_rows_kernel(const DnPpoLossArgs
         s[3] = fabs(ratio - 1.0) > a.clip_range ? 1.0 : 0.0;
     }
 
+    // fr_block_sums, step by step: handed on as an array, the 12 sums of A = 8 cost the kernel 68 VGPRs for 61, 7 waves per SIMD for 8
 #pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        const double t = fr_wave_sum(s[q]);
-        if ((tid & 63) == 0) wsum[tid >> 6][q] = t;
-    }
+    for (int q = 0; q < NS; ++q) fr_wave_to_lds<NS, PL_WAVES>(q, s[q], wsum);
     __syncthreads();
-    if (tid < NS) {
-        double t = 0.0;
-        for (int wv = 0; wv < PL_WAVES; ++wv) t += wsum[wv][tid];
-        a.part[(long long)blockIdx.x * NS + tid] = t;
-    }
+    if (tid < NS) a.part[(long long)blockIdx.x * NS + tid] = fr_waves_sum<NS, PL_WAVES>(wsum, tid);
 }
 
 __global__ __launch_bounds__(64) void pl_merge_kernel(const DnPpoLossArgs a)
@@ -152,24 +112,7 @@ __global__ __launch_bounds__(64) void pl_merge_kernel(const DnPpoLossArgs a)
     const int q = (int)threadIdx.x, A = a.act_dim, ns = 4 + A;
     const long long nblk = a.nblk;
     double t = 0.0;
-    if (q < ns) {
-        const double *p = a.part + q;
-        double cur[FR_BATCH], nxt[FR_BATCH];
-#pragma unroll
-        for (int j = 0; j < FR_BATCH; ++j) cur[j] = j < nblk ? p[(long long)j * ns] : 0.0;
-        for (long long b0 = 0; b0 < nblk; b0 += FR_BATCH) {
-#pragma unroll
-            for (int j = 0; j < FR_BATCH; ++j) {       // the next batch is on its way while this one is added
-                const long long b = b0 + FR_BATCH + j;
-                nxt[j] = b < nblk ? p[b * ns] : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < FR_BATCH; ++j) {
-                if (b0 + j < nblk) t += cur[j];
-                cur[j] = nxt[j];
-            }
-        }
-    }
+    if (q < ns) t = fr_sum_column(a.part + q, ns, nblk);
     const double s0 = __shfl(t, 0, 64), s1 = __shfl(t, 1, 64), s2 = __shfl(t, 2, 64), s3 = __shfl(t, 3, 64);
     const double nb = (double)a.batch;
     if (q == 0) {

@@ -8,22 +8,20 @@
 // are added, nothing else.
 //
 // Ordinary launches on the caller's stream; no workgroup ever waits for another, nothing is allocated, no atomics:
-//   sl_policy_kernel<A, BWD>  one row per lane, 256 rows per workgroup, the row's A columns in registers (16-byte words when A % 4 == 0 and
-//                             every [batch][A] pointer is 16-byte aligned: the same values into the same registers, so the same bits; else
-//                             4-byte words).  Forward stores actions and log_prob; backward recomputes the element from mean, log_std and
-//                             noise and stores d_mean and d_log_std.  No reduction, no scratch.
+//   sl_policy_kernel<A, BWD>  one row per lane, 256 rows per workgroup, the row's A columns in registers (16-byte words when dn_rows_vec16
+//                             holds of every [batch][A] pointer of the call, else 4-byte words: dn_load_row of dn_row_sums.h).  Forward
+//                             stores actions and log_prob; backward recomputes the element from mean, log_std and noise and stores d_mean
+//                             and d_log_std.  No reduction, no scratch.
 //   sl_critic_rows_kernel<C>  one workgroup per block of DN_ROWNORM_BLOCK_ROWS consecutive rows, one row per lane.  Lane 0 first forms alpha
 //   sl_actor_rows_kernel<C>   into LDS; after one barrier every lane loads its row, evaluates the expressions of the header and stores its
-//                             per-row outputs.  The block then forms its float64 sums across the lanes of a wave by the fixed tree of
-//                             dn_fleet_rms.h, then the waves in ascending order through LDS; lanes past the end contribute +0.0.  The sums
-//                             go to part[block][ns]: ns = 2 C + 1 (critic) or 4 (actor).
-//   sl_merge_kernel           ONE wave, both losses: lane q < ns adds column q of the block sums in ascending block order (plain sums,
-//                             FR_BATCH loads in flight ahead of the chain); lane 0 then writes stats[8], the float32 losses and
-//                             d_log_ent_coef.
-// The order of every float64 operation is a function of (batch, act_dim, n_critics) alone: the same call gives the same bits every time,
-// and a captured graph replays it.
+//                             per-row outputs.  The block then forms its float64 sums by fr_block_sums; lanes past the end contribute
+//                             +0.0.  The sums go to part[block][ns]: ns = 2 C + 1 (critic) or 4 (actor).
+//   sl_merge_kernel           ONE wave, both losses: lane q < ns adds column q of the block sums by fr_sum_column; lane 0 then writes
+//                             stats[8], the float32 losses and d_log_ent_coef.
+// The order of every float64 sum is that of dn_row_sums.h, a function of (batch, act_dim, n_critics) alone: the same call gives the same
+// bits every time, and a captured graph replays it.
 #include "dn_internal.h"
-#include "dn_fleet_rms.h"
+#include "dn_row_sums.h"
 #include "dn_sac_math.h"
 
 namespace {
@@ -33,39 +31,6 @@ constexpr int SL_THREADS = (int)DN_ROWNORM_BLOCK_ROWS;   // the losses: one row 
 constexpr int SL_WAVES = SL_THREADS / 64;
 constexpr int SL_MAX_SUMS = 2 * DN_SAC_MAX_CRITICS + 1;
 
-// One row of A float32 columns into registers: 16-byte words (A % 4 == 0, p 16-byte aligned) or 4-byte words, the same values either way.
-template <int A>
-__device__ __forceinline__ void sl_load_row(const float *__restrict__ p, const long long row, const bool vec, float (&x)[A])
-{
-    if constexpr (A % 4 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < A / 4; ++q) {
-                const float4 v = reinterpret_cast<const float4 *>(p)[row * (A / 4) + q];
-                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < A; ++j) x[j] = p[row * A + j];
-}
-
-template <int A>
-__device__ __forceinline__ void sl_store_row(float *__restrict__ p, const long long row, const bool vec, const float (&x)[A])
-{
-    if constexpr (A % 4 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < A / 4; ++q)
-                reinterpret_cast<float4 *>(p)[row * (A / 4) + q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < A; ++j) p[row * A + j] = x[j];
-}
-
 template <int A, bool BWD>
 __global__ __launch_bounds__(SP_THREADS) void sl_policy_kernel(const DnSacPolicyArgs a)
 {
@@ -73,9 +38,9 @@ __global__ __launch_bounds__(SP_THREADS) void sl_policy_kernel(const DnSacPolicy
     if (row >= a.batch) return;
     const bool vec = a.vec != 0;
     float mu[A], raw[A], eps[A];
-    sl_load_row<A>(a.mean, row, vec, mu);
-    sl_load_row<A>(a.raw, row, vec, raw);
-    sl_load_row<A>(a.eps, row, vec, eps);
+    dn_load_row<A>(a.mean, row, vec, mu);
+    dn_load_row<A>(a.raw, row, vec, raw);
+    dn_load_row<A>(a.eps, row, vec, eps);
     if constexpr (!BWD) {
         float act[A];
         double lp = 0.0;
@@ -85,12 +50,12 @@ __global__ __launch_bounds__(SP_THREADS) void sl_policy_kernel(const DnSacPolicy
             act[j] = (float)e.a;
             lp = j == 0 ? e.term : lp + e.term;
         }
-        sl_store_row<A>(a.actions, row, vec, act);
+        dn_store_row<A>(a.actions, row, vec, act);
         a.log_prob[row] = (float)lp;
     } else {
         float ga[A], dm[A], dr[A];
         if (a.g_a) {
-            sl_load_row<A>(a.g_a, row, vec, ga);
+            dn_load_row<A>(a.g_a, row, vec, ga);
         } else {
 #pragma unroll
             for (int j = 0; j < A; ++j) ga[j] = 0.0f;
@@ -105,26 +70,8 @@ __global__ __launch_bounds__(SP_THREADS) void sl_policy_kernel(const DnSacPolicy
             dm[j] = (float)d_mean;
             dr[j] = (float)d_raw;
         }
-        sl_store_row<A>(a.d_mean, row, vec, dm);
-        sl_store_row<A>(a.d_raw, row, vec, dr);
-    }
-}
-
-// The block's NS sums: lanes by the fixed tree, waves ascending through LDS, into part[block][NS].
-template <int NS>
-__device__ __forceinline__ void sl_block_sums(const double (&s)[NS], double (&wsum)[SL_WAVES][NS], double *__restrict__ part)
-{
-    const int tid = (int)threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        const double t = fr_wave_sum(s[q]);
-        if ((tid & 63) == 0) wsum[tid >> 6][q] = t;
-    }
-    __syncthreads();
-    if (tid < NS) {
-        double t = 0.0;
-        for (int wv = 0; wv < SL_WAVES; ++wv) t += wsum[wv][tid];
-        part[(long long)blockIdx.x * NS + tid] = t;
+        dn_store_row<A>(a.d_mean, row, vec, dm);
+        dn_store_row<A>(a.d_raw, row, vec, dr);
     }
 }
 
@@ -169,7 +116,7 @@ __global__ __launch_bounds__(SL_THREADS) void sl_critic_rows_kernel(const DnSacL
         s[C] = y;
         a.target_q[row] = (float)y;
     }
-    sl_block_sums<NS>(s, wsum, a.part);
+    fr_block_sums<NS, SL_WAVES>(s, wsum, a.part);
 }
 
 template <int C>
@@ -207,7 +154,7 @@ __global__ __launch_bounds__(SL_THREADS) void sl_actor_rows_kernel(const DnSacLo
         s[2] = lp;
         s[3] = qmin;
     }
-    sl_block_sums<NS>(s, wsum, a.part);
+    fr_block_sums<NS, SL_WAVES>(s, wsum, a.part);
 }
 
 __global__ __launch_bounds__(64) void sl_merge_kernel(const DnSacLossArgs a)
@@ -215,26 +162,7 @@ __global__ __launch_bounds__(64) void sl_merge_kernel(const DnSacLossArgs a)
     __shared__ double tot[SL_MAX_SUMS];
     const int q = (int)threadIdx.x, C = a.n_critics, ns = a.mode == DN_SAC_CRITIC ? 2 * C + 1 : 4;
     const long long nblk = a.nblk;
-    if (q < ns) {
-        double t = 0.0;
-        const double *p = a.part + q;
-        double cur[FR_BATCH], nxt[FR_BATCH];
-#pragma unroll
-        for (int j = 0; j < FR_BATCH; ++j) cur[j] = j < nblk ? p[(long long)j * ns] : 0.0;
-        for (long long b0 = 0; b0 < nblk; b0 += FR_BATCH) {
-#pragma unroll
-            for (int j = 0; j < FR_BATCH; ++j) {       // the next batch is on its way while this one is added
-                const long long b = b0 + FR_BATCH + j;
-                nxt[j] = b < nblk ? p[b * ns] : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < FR_BATCH; ++j) {
-                if (b0 + j < nblk) t += cur[j];
-                cur[j] = nxt[j];
-            }
-        }
-        tot[q] = t;
-    }
+    if (q < ns) tot[q] = fr_sum_column(a.part + q, ns, nblk);
     __syncthreads();
     if (q != 0) return;
     const double nb = (double)a.batch, alpha = sl_alpha(a);

@@ -13,7 +13,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _capi
-from ._fleetnorm import DeviceScratch
+from ._fleetnorm import LossHead
 
 STAT_NAMES = ("loss", "policy_gradient_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")      # SB3's logger keys; stats[6:8] are 0
 
@@ -31,13 +31,11 @@ class _PpoLossFunction(torch.autograd.Function):
     @once_differentiable                               # the stored gradients are plain buffers: there is no double backward
     def backward(ctx, grad_output):
         owner, n = ctx.owner, ctx.count
-        if ctx.call != owner._calls:
-            raise RuntimeError(f"PpoLoss: backward of call {ctx.call} after call {owner._calls}: the gradients live in static buffers that the "
-                               "later forward has overwritten; call backward() before the next forward")
+        owner._stale(ctx)
         return grad_output * owner.d_mean[:n], grad_output * owner.d_log_std, grad_output * owner.d_value[:n], None, None, None
 
 
-class PpoLoss(DeviceScratch):
+class PpoLoss(LossHead):
     """batch_size: the most rows of a call (SB3's batch_size); act_dim: 1..8 action columns; device: a GPU (there is no CPU path);
     clip_range > 0; clip_range_vf: None (no value clip, SB3's default) or > 0; ent_coef, vf_coef >= 0.  All four are host values: a
     captured graph keeps the ones it was captured with.
@@ -53,9 +51,8 @@ class PpoLoss(DeviceScratch):
     _NAME, _NOUN = "PpoLoss", "a minibatch"
 
     def __init__(self, batch_size, act_dim, device, *, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5):
-        for name, v, top in (("batch_size", batch_size, (1 << 31) - 1), ("act_dim", act_dim, _capi.PPO_MAX_ACT)):
-            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
-                raise ValueError(f"PpoLoss.{name} must be an integer in 1..{top}, got {v!r}")
+        self._count("batch_size", batch_size, (1 << 31) - 1)
+        self._count("act_dim", act_dim, _capi.PPO_MAX_ACT)
         clip_range = float(clip_range)
         if not (math.isfinite(clip_range) and clip_range > 0.0):
             raise ValueError(f"PpoLoss.clip_range must be finite and > 0, got {clip_range!r}")
@@ -73,23 +70,9 @@ class PpoLoss(DeviceScratch):
         self.d_mean, self.d_log_std = torch.zeros((batch_size, act_dim), **f32), torch.zeros(act_dim, **f32)
         self.d_value, self.log_probs, self.loss = torch.zeros(batch_size, **f32), torch.zeros(batch_size, **f32), torch.zeros(1, **f32)
         self.stats = torch.zeros(8, dtype=torch.float64, device=self.device)
-        self._calls = 0
-
-    def _check(self, name, t, shape):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"PpoLoss: {name} must be a tensor, got {type(t).__name__}")
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device:
-            raise ValueError(f"PpoLoss: {name} must be torch.float32 {list(shape)} on {self.device}, got {t.dtype} {list(t.shape)} on {t.device}")
-        if not t.is_contiguous():
-            raise ValueError(f"PpoLoss: {name} must be dense (strides {t.stride()}); the kernel reads it in place and stages nothing")
 
     def __call__(self, mean, log_std, values, mb):
-        if not isinstance(mean, torch.Tensor) or mean.dim() != 2:
-            raise ValueError(f"PpoLoss: mean must be a tensor [count, {self.act_dim}]")
-        count = int(mean.shape[0])
-        if not 1 <= count <= self.batch_size:
-            raise ValueError(f"PpoLoss: mean has {count} rows; a call takes 1..{self.batch_size} (batch_size)")
-        self._check("mean", mean, (count, self.act_dim))
+        count = self._rows("mean", mean, self.act_dim)
         self._check("log_std", log_std, (self.act_dim,))
         self._check("values", values, (count,))
         need = ("actions", "log_probs", "advantages", "returns") + (("values",) if self.clip_range_vf is not None else ())

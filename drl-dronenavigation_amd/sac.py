@@ -14,16 +14,10 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _capi
-from ._fleetnorm import DeviceScratch
+from ._fleetnorm import LossHead
 
 CRITIC_STAT_NAMES = ("critic_loss", "ent_coef", "target_q_mean")       # then q_mean_0 .. q_mean_{n_critics - 1}; SB3's logger keys first
 ACTOR_STAT_NAMES = ("actor_loss", "ent_coef_loss", "ent_coef", "log_prob_mean", "q_pi_min_mean")
-
-
-def _count(cls, name, v, top):
-    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
-        raise ValueError(f"{cls}.{name} must be an integer in 1..{top}, got {v!r}")
-    return v
 
 
 def _ent_coef(cls, v):
@@ -36,19 +30,9 @@ def _ent_coef(cls, v):
     return v
 
 
-class _SacHead(DeviceScratch):
-    """What the three heads share: the checks of a tensor by argument name, the call counter, and the table of per-critic pointers."""
-
-    def _check(self, name, t, shapes):
-        """t: a dense float32 tensor on the device of one of `shapes`."""
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{self._NAME}: {name} must be a tensor, got {type(t).__name__}")
-        shapes = shapes if isinstance(shapes, list) else [shapes]
-        if tuple(t.shape) not in shapes or t.dtype != torch.float32 or t.device != self.device:
-            want = " or ".join(str(list(s)) for s in shapes)
-            raise ValueError(f"{self._NAME}: {name} must be torch.float32 {want} on {self.device}, got {t.dtype} {list(t.shape)} on {t.device}")
-        if not t.is_contiguous():
-            raise ValueError(f"{self._NAME}: {name} must be dense (strides {t.stride()}); the kernel reads it in place and stages nothing")
+class _SacHead(LossHead):
+    """What the three heads share beyond LossHead: the checks of a list of per-critic tensors and of log_ent_coef, and the table of
+    per-critic pointers."""
 
     def _check_list(self, name, ts, count):
         if not isinstance(ts, (list, tuple)) or len(ts) != self.n_critics:
@@ -64,11 +48,6 @@ class _SacHead(DeviceScratch):
             self._check("log_ent_coef", log_ent_coef, [(1,), ()])
         elif log_ent_coef is not None:
             raise ValueError(f"{self._NAME}: log_ent_coef must be None with the fixed ent_coef={self.ent_coef:g}")
-
-    def _stale(self, ctx):
-        if ctx.call != self._calls:
-            raise RuntimeError(f"{self._NAME}: backward of call {ctx.call} after call {self._calls}: the gradients live in static buffers that the "
-                               "later forward has overwritten; call backward() before the next forward")
 
     @staticmethod
     def _table(tensors):
@@ -113,8 +92,8 @@ class SacPolicyHead(_SacHead):
     _NAME, _NOUN = "SacPolicyHead", "a batch"
 
     def __init__(self, batch_size, act_dim, device, *, log_std_min=-20.0, log_std_max=2.0):
-        _count("SacPolicyHead", "batch_size", batch_size, (1 << 31) - 1)
-        _count("SacPolicyHead", "act_dim", act_dim, _capi.SAC_MAX_ACT)
+        self._count("batch_size", batch_size, (1 << 31) - 1)
+        self._count("act_dim", act_dim, _capi.SAC_MAX_ACT)
         log_std_min, log_std_max = float(log_std_min), float(log_std_max)
         if not (math.isfinite(log_std_min) and math.isfinite(log_std_max) and log_std_min < log_std_max):
             raise ValueError(f"SacPolicyHead.log_std_min and log_std_max must be finite with log_std_min < log_std_max, got {log_std_min!r}, {log_std_max!r}")
@@ -123,18 +102,13 @@ class SacPolicyHead(_SacHead):
         f32 = dict(dtype=torch.float32, device=self.device)
         self.actions, self.log_prob = torch.zeros((batch_size, act_dim), **f32), torch.zeros(batch_size, **f32)
         self.d_mean, self.d_log_std = torch.zeros((batch_size, act_dim), **f32), torch.zeros((batch_size, act_dim), **f32)
-        self._calls = 0
 
     def _cfg(self):
         return _capi.DnSacConfig(0.0, 0.0, 0.0, self.log_std_min, self.log_std_max, self.act_dim, 1, 0)
 
     def __call__(self, mean, log_std, noise):
-        if not isinstance(mean, torch.Tensor) or mean.dim() != 2:
-            raise ValueError(f"SacPolicyHead: mean must be a tensor [count, {self.act_dim}]")
-        count = int(mean.shape[0])
-        if not 1 <= count <= self.batch_size:
-            raise ValueError(f"SacPolicyHead: mean has {count} rows; a call takes 1..{self.batch_size} (batch_size)")
-        for name, t in (("mean", mean), ("log_std", log_std), ("noise", noise)):
+        count = self._rows("mean", mean, self.act_dim)
+        for name, t in (("log_std", log_std), ("noise", noise)):
             self._check(name, t, (count, self.act_dim))
         return _SacPolicyFunction.apply(mean, log_std, noise, self, count)
 
@@ -194,8 +168,8 @@ class SacCriticLoss(_SacHead):
     _NAME, _NOUN = "SacCriticLoss", "a batch"
 
     def __init__(self, batch_size, device, *, n_critics=2, gamma=0.99, ent_coef=None):
-        _count("SacCriticLoss", "batch_size", batch_size, (1 << 31) - 1)
-        _count("SacCriticLoss", "n_critics", n_critics, _capi.SAC_MAX_CRITICS)
+        self._count("batch_size", batch_size, (1 << 31) - 1)
+        self._count("n_critics", n_critics, _capi.SAC_MAX_CRITICS)
         gamma = float(gamma)
         if not (math.isfinite(gamma) and 0.0 <= gamma <= 1.0):
             raise ValueError(f"SacCriticLoss.gamma must be finite and in [0, 1], got {gamma!r}")
@@ -205,15 +179,9 @@ class SacCriticLoss(_SacHead):
         f32 = dict(dtype=torch.float32, device=self.device)
         self.d_q, self.target_q, self.loss = torch.zeros((n_critics, batch_size), **f32), torch.zeros(batch_size, **f32), torch.zeros(1, **f32)
         self.stats = torch.zeros(8, dtype=torch.float64, device=self.device)
-        self._calls = 0
 
     def __call__(self, q_list, next_q_list, next_log_prob, batch, log_ent_coef=None):
-        if not isinstance(next_log_prob, torch.Tensor) or next_log_prob.dim() != 1:
-            raise ValueError("SacCriticLoss: next_log_prob must be a tensor [count]")
-        count = int(next_log_prob.shape[0])
-        if not 1 <= count <= self.batch_size:
-            raise ValueError(f"SacCriticLoss: next_log_prob has {count} rows; a call takes 1..{self.batch_size} (batch_size)")
-        self._check("next_log_prob", next_log_prob, (count,))
+        count = self._rows("next_log_prob", next_log_prob)
         self._check_list("q_list", q_list, count)
         self._check_list("next_q_list", next_q_list, count)
         for key in ("rewards", "dones"):
@@ -293,8 +261,8 @@ class SacActorLoss(_SacHead):
     _NAME, _NOUN = "SacActorLoss", "a batch"
 
     def __init__(self, batch_size, device, *, n_critics=2, target_entropy, ent_coef=None):
-        _count("SacActorLoss", "batch_size", batch_size, (1 << 31) - 1)
-        _count("SacActorLoss", "n_critics", n_critics, _capi.SAC_MAX_CRITICS)
+        self._count("batch_size", batch_size, (1 << 31) - 1)
+        self._count("n_critics", n_critics, _capi.SAC_MAX_CRITICS)
         target_entropy = float(target_entropy)
         if not math.isfinite(target_entropy):
             raise ValueError(f"SacActorLoss.target_entropy must be finite, got {target_entropy!r}")
@@ -305,15 +273,9 @@ class SacActorLoss(_SacHead):
         self.d_log_prob, self.d_q_pi = torch.zeros(batch_size, **f32), torch.zeros((n_critics, batch_size), **f32)
         self.d_log_ent_coef, self.actor_loss, self.ent_coef_loss = torch.zeros(1, **f32), torch.zeros(1, **f32), torch.zeros(1, **f32)
         self.stats = torch.zeros(8, dtype=torch.float64, device=self.device)
-        self._calls = 0
 
     def __call__(self, log_prob, q_pi_list, log_ent_coef=None):
-        if not isinstance(log_prob, torch.Tensor) or log_prob.dim() != 1:
-            raise ValueError("SacActorLoss: log_prob must be a tensor [count]")
-        count = int(log_prob.shape[0])
-        if not 1 <= count <= self.batch_size:
-            raise ValueError(f"SacActorLoss: log_prob has {count} rows; a call takes 1..{self.batch_size} (batch_size)")
-        self._check("log_prob", log_prob, (count,))
+        count = self._rows("log_prob", log_prob)
         self._check_list("q_pi_list", q_pi_list, count)
         self._check_log_ent_coef(log_ent_coef)
         return _SacActorFunction.apply(self, count, log_prob, log_ent_coef, *q_pi_list)

@@ -8,16 +8,12 @@ import math
 import numpy as np
 import torch
 
-BLOCK_ROWS = 1024                       # DN_ROWNORM_BLOCK_ROWS
-BATCHES = (1, 2, 63, 65, 1024, 1025, 2049)
-ACT_DIMS = (1, 3, 4, 8)
+from loss_support import ACT_DIMS, BATCHES, BLOCK_ROWS, COVERED_FROM, EPS40, HALF_LOG_2PI, distance, ulp32  # noqa: F401  (handed on to the tests)
+
 SPREADS = {"first": 0.0, "near": 0.15, "far": 0.5}      # the standard deviation of new - old log-probability: the first epoch, near, far
 CLIP_RANGE, CLIP_RANGE_VF = 0.2, 0.2
 COEFS = ((0.0, 0.0), (0.01, 0.5))       # (ent_coef, vf_coef): both zero, both nonzero
-HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
-COVERED_FROM = 63                       # below this many rows a data set cannot promise both branches (a batch of one has one)
-EPS40 = 2.0 ** -40
 
 
 _EXP = {}
@@ -170,13 +166,6 @@ def closed_forms(d, clip_range=CLIP_RANGE, clip_range_vf=None, ent_coef=0.0, vf_
 
 
 # ---- tolerances, against reference() only ---------------------------------------------------------------------------------------------------
-def ulp32(want):
-    """One float32 ulp at the reference value."""
-    w32 = np.abs(np.asarray(want, np.float64)).astype(np.float32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        return (np.nextafter(w32, np.float32(np.inf)) - w32).astype(np.float64)
-
-
 def tolerances(ref):
     """Per output of reference(): d_mean, d_value, log_probs one float32 ulp of the reference value or 2^-40 absolute, whichever is larger
     (the single rounding to float32, and near zero the last float64 bits of exp and 1 / B); d_log_std one float32 ulp or 2^-40 times the
@@ -189,20 +178,6 @@ def tolerances(ref):
         tol["stats"] = EPS40 * np.fmax(ref["stats_terms"], np.abs(ref["stats"]))
     tol["loss"] = np.fmax(ulp32(ref["loss"]), tol["stats"][0])
     return tol
-
-
-def distance(got, want, tol):
-    """The largest |got - want| / tol over the cells where the reference is finite; where it is not, got must be NaN in the same cells.
-    Returns (distance, the NaN patterns agree)."""
-    got, want, tol = (np.asarray(x, np.float64) for x in (got, want, tol))
-    got, want, tol = np.broadcast_arrays(got, want, tol)
-    fin = np.isfinite(want)
-    same = bool(np.array_equal(np.isnan(got), np.isnan(want)))
-    if not fin.any():
-        return 0.0, same
-    err = np.abs(got[fin] - want[fin])
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return float(np.max(np.where(err == 0.0, 0.0, err / tol[fin]))), same             # a bound of 0 (a clip fraction of 0) asks for equality
 
 
 def check_outputs(got, ref, tag):

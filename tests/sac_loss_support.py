@@ -16,16 +16,12 @@ import math
 import numpy as np
 import torch
 
-BLOCK_ROWS = 1024                       # DN_ROWNORM_BLOCK_ROWS
-BATCHES = (1, 2, 63, 65, 1024, 1025, 2049)
-ACT_DIMS = (1, 3, 4, 8)
+from loss_support import ACT_DIMS, BATCHES, BLOCK_ROWS, COVERED_FROM, EPS40, HALF_LOG_2PI, distance, ulp32  # noqa: F401  (handed on to the tests)
+
 CRITICS = (1, 2, 4)
 GAMMAS = (0.0, 0.99)
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
-HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 LOG_EPS = 1e-6
-COVERED_FROM = 63                       # below this many rows a data set cannot promise its shares
-EPS40 = 2.0 ** -40
 FIXED_ENT_COEF = 0.2
 TARGET_ENTROPY = -4.0
 
@@ -274,13 +270,6 @@ def actor_closed_forms(d, learned, target_entropy=TARGET_ENTROPY):
 
 
 # ---- tolerances, against the references only ------------------------------------------------------------------------------------------------
-def ulp32(want):
-    """One float32 ulp at the reference value."""
-    w32 = np.abs(np.asarray(want, np.float64)).astype(np.float32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        return (np.nextafter(w32, np.float32(np.inf)) - w32).astype(np.float64)
-
-
 def row_tolerance(ref, key):
     """A per-row float32 output: one float32 ulp of the reference value or 2^-40 of the sum of its absolute terms, whichever is larger.
     The second bound also carries the reference's own error where it has one (`<key>_own`): torch's autograd takes d tanh / d pre as
@@ -297,20 +286,6 @@ def stats_tolerance(ref):
 
 def loss_tolerance(ref, key, index):
     return float(np.fmax(ulp32(ref[key]), stats_tolerance(ref)[index]))
-
-
-def distance(got, want, tol):
-    """The largest |got - want| / tol over the cells where the reference is finite; where it is not, got must be NaN in the same cells.
-    Returns (distance, the NaN patterns agree)."""
-    got, want, tol = (np.asarray(x, np.float64) for x in (got, want, tol))
-    got, want, tol = np.broadcast_arrays(got, want, tol)
-    fin = np.isfinite(want)
-    same = bool(np.array_equal(np.isnan(got), np.isnan(want)))
-    if not fin.any():
-        return 0.0, same
-    err = np.abs(got[fin] - want[fin])
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return float(np.max(np.where(err == 0.0, 0.0, err / tol[fin]))), same             # a bound of 0 asks for equality
 
 
 def _held(worst, tag, key, got, want, tol):
