@@ -1,5 +1,5 @@
 /* dn_action_sat.h -- the saturation constants of the float32 action chain (A1-A3), shared by the HIP kernels
- * (dn_kernels.hip: rotor_force_sat) and by the exhaustive checker tests/tools/check_action_chain_exact.c, which
+ * (dn_action_chain.h: rotor_force_sat) and by the exhaustive checker tests/tools/check_action_chain_exact.c, which
  * PROVES them against the literal numpy-order chain for every float32 action (all 2^32 bit patterns but the NaNs).
  *
  * PBDroneEnv._preprocessAction clips the (rescaled) action to [a_low, a_high] (PBDroneEnv.py:889) before anything

@@ -1,4 +1,4 @@
-// dn_internal.h -- shared between the HIP kernels (dn_kernels.hip) and the C-ABI host side (dn_capi.cpp, dn_capi_envfree.cpp).
+// dn_internal.h -- shared between the HIP kernels (dn_kernels.hip, dn_glue.hip) and the C-ABI host side (dn_capi.cpp, dn_capi_envfree.cpp).
 #ifndef DN_INTERNAL_H
 #define DN_INTERNAL_H
 
@@ -15,6 +15,9 @@
 // workgroup is one wave (all phases) or two (flight wave + report wave over the same 64 drones).  Every
 // wave-level idiom below (ballot, LDS tile transpose) assumes DN_BLOCK == 64.
 #define DN_BLOCK 64
+
+// Every device function of the step and glue units and of the headers they share (dn_action_chain.h, dn_philox.h, dn_policy_draw.h)
+#define DN_DEV __device__ __forceinline__
 
 // Layout of one waypoint-table entry (entry k describes waypoint k and the corridor segment that ends
 // at it), staged into LDS once per workgroup.  Precomputed on the host in float64 with the reference's
@@ -269,18 +272,18 @@ hipError_t dn_launch_sensor_bias(const DnSens &sn, long long n, float *bias, int
 hipError_t dn_launch_eval_kinematics(const DnParams &p, const DnStepIO &io, const double *kin, bool f32, hipStream_t stream);
 hipError_t dn_launch_gae(const float *rewards, const float *values, const uint8_t *dones,
                          const float *last_values, const uint8_t *last_dones, long long T, long long N,
-                         float gamma, float gl, float *adv, float *ret, hipStream_t stream);
+                         float gamma, float gl, float *adv, float *ret, hipStream_t stream);   // dn_glue.hip
 hipError_t dn_launch_action_chain(const float *actions, long long n, int normalize_actions, float *rpm, float *forces,
-                                  float *z_torque, hipStream_t stream);
-hipError_t dn_launch_fill4(float4 *dst, float4 v, long long n, hipStream_t stream);
-hipError_t dn_launch_filld(double *dst, double v, long long n, hipStream_t stream);
+                                  float *z_torque, hipStream_t stream);   // dn_glue.hip
+hipError_t dn_launch_fill4(float4 *dst, float4 v, long long n, hipStream_t stream);   // dn_glue.hip
+hipError_t dn_launch_filld(double *dst, double v, long long n, hipStream_t stream);   // dn_glue.hip
 hipError_t dn_launch_squashed_sample(const DnParams &p, const float *mu_log_std, unsigned long long seed, int deterministic,
-                                     float *actions, float *log_prob, hipStream_t stream);
+                                     float *actions, float *log_prob, hipStream_t stream);   // dn_glue.hip
 hipError_t dn_launch_policy_sample(const DnParams &p, const float *mean, const float *log_std4, unsigned long long seed, int deterministic,
-                                   float *actions, float *clipped, float *log_prob, hipStream_t stream);
+                                   float *actions, float *clipped, float *log_prob, hipStream_t stream);   // dn_glue.hip
 hipError_t dn_launch_add_bootstrap(float *reward, const float *terminal_value, const uint8_t *truncated, float gamma, long long n,
-                                   hipStream_t stream);
-hipError_t dn_launch_set_step_count(DnStatSlot *slots, long long blocks, unsigned long long value, hipStream_t stream);
+                                   hipStream_t stream);   // dn_glue.hip
+hipError_t dn_launch_set_step_count(DnStatSlot *slots, long long blocks, unsigned long long value, hipStream_t stream);   // dn_glue.hip
 hipError_t dn_launch_mlp(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                          hipStream_t stream);
 // Layer-1 K-steps (of 16 inputs) a PPO policy kernel runs for rows of obs_dim columns: 1 (the kernels of dn_mlp.hip), 2 or 4 (those of
@@ -456,9 +459,9 @@ hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_ml
                               hipStream_t stream);                                                                             // dn_fused.hip
 hipError_t dn_launch_compact_pack(const unsigned long long *mask, long long n, const float *terminal_obs, const float *ep_return,
                                   const int32_t *ep_length, const uint8_t *truncated, const int32_t *found, int32_t *indices, int32_t *count,
-                                  float *packed, hipStream_t stream);
-hipError_t dn_launch_stream_copy(void *dst, const void *src, long long n16, int num_cus, hipStream_t stream);
+                                  float *packed, hipStream_t stream);   // dn_glue.hip
+hipError_t dn_launch_stream_copy(void *dst, const void *src, long long n16, int num_cus, hipStream_t stream);   // dn_glue.hip
 hipError_t dn_launch_compact(const unsigned long long *mask, long long n, int32_t *indices, int32_t *count,
-                             hipStream_t stream);
+                             hipStream_t stream);   // dn_glue.hip
 
 #endif

@@ -21,7 +21,9 @@
 //   PBDroneEnv.py = Sol/Model/Environments/PBDroneEnv.py, BaseAviary.py = Sol/PyBullet/BaseAviary.py,
 //   env_utils.py = Sol/Model/env_utils.py, normalize.py = Sol/Model/Environments/normalize.py.
 #include "dn_internal.h"
-#include "dn_action_sat.h"
+#include "dn_action_chain.h"    // A1-A3: the float32 action chain and its constants (KF32 ... A_HIGH32)
+#include "dn_philox.h"          // philox4x32, the two Box-Muller forms, noise4
+#include "dn_policy_draw.h"     // clipv, gaussian_draw, tanh_squash, squashed_draw
 
 #ifndef DN_TU
 #define DN_TU 1      // see dn_launch_step_many: 1 = this file as such, 2 = through dn_kernels_mw.hip
@@ -29,8 +31,6 @@
 
 #include <float.h>
 #include <type_traits>
-
-#define DN_DEV __device__ __forceinline__
 
 namespace {
 
@@ -57,107 +57,7 @@ template <typename R> struct K {
     static constexpr R INV_25 = R(1.0 / 25.0);
     static constexpr R COS_10DEG = R(0.98480775301220805936674302458952);   // cos(np.radians(10))
 };
-constexpr float KF32 = (float)3.16e-10, KM32 = (float)7.94e-12;
-constexpr float PWM2RPM_SCALE32 = (float)0.2685, PWM2RPM_CONST32 = (float)4070.3;
-constexpr float MIN_PWM32 = 20000.0f, MAX_PWM32 = 65535.0f;
-// a_low / a_high = float32(KF * (SCALE * PWM + CONST)**2), PBDroneEnv.py:113-116
-constexpr float A_LOW32 = (float)(3.16e-10 * ((0.2685 * 20000.0 + 4070.3) * (0.2685 * 20000.0 + 4070.3)));
-constexpr float A_HIGH32 = (float)(3.16e-10 * ((0.2685 * 65535.0 + 4070.3) * (0.2685 * 65535.0 + 4070.3)));
-
-template <typename T> DN_DEV T clipv(T x, T lo, T hi)
-{   // np.clip = minimum(maximum(x, lo), hi); NaN propagates (both compares false)
-    return x < lo ? lo : (x > hi ? hi : x);
-}
 template <typename R> DN_DEV R norm3(R a, R b, R c) { return sqrt(a * a + b * b + c * c); }
-
-// ---- A1-A3: float32 action chain ------------------------------------------------------------------
-// Bit-exact against numpy float32 (golden actions.npz).  IEEE divide and sqrt expand to 10 and 23 instructions on
-// gfx950 (scaling, fix-up); every divisor here is a constant and every operand range is known, so the chain uses
-//   a / c  =  q0 + fma(-q0, c, a) * RN(1/c),  q0 = a * RN(1/c)        (Markstein's correction, 3 instructions)
-//   sqrt   =  v_sqrt_f32 (1 ulp) + a one-ulp-down / one-ulp-up test with fma residuals
-// which tests/tools/check_action_chain_exact.c proves identical to the correctly rounded results for EVERY float32
-// input that can reach them (2.1e9 actions, 2e7 thrusts, 1e7 roots; exhaustive).  Clips are v_med3_f32; np.clip's
-// NaN propagation is restored by the final select.
-constexpr float DEN32 = A_HIGH32 - A_LOW32;
-constexpr float INV_DEN32 = 1.0f / DEN32, INV_KF32 = 1.0f / KF32, INV_SCALE32 = 1.0f / PWM2RPM_SCALE32;
-DN_DEV float div_const32(float a, float c, float inv_c)
-{
-    const float q0 = a * inv_c;
-    const float r = __builtin_fmaf(-q0, c, a);
-    return __builtin_fmaf(r, inv_c, q0);
-}
-DN_DEV float sqrt_rn32(float x)
-{
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
-    const float rm = __builtin_fmaf(-sm, s, x), rp = __builtin_fmaf(-sp, s, x);
-    float out = rm <= 0.0f ? sm : s;
-    out = rp > 0.0f ? sp : out;
-    return out;
-}
-DN_DEV float rescale_unclipped32(float a)
-{   // PBDroneEnv.rescale_action, PBDroneEnv.py:949-971, before its final clip to [-1, 1]
-    const float ac = __builtin_amdgcn_fmed3f(a, -2.0f, 2.0f);   // beyond +-2 the result is saturated anyway
-    const float num = ac - A_LOW32;
-    const float q = div_const32(num, DEN32, INV_DEN32);
-    const float m = 2.0f * q;                // (high - low) = 1 - (-1)
-    return -1.0f + m;
-}
-DN_DEV float rescale_action32(float a) { return __builtin_amdgcn_fmed3f(rescale_unclipped32(a), -1.0f, 1.0f); }
-// cmd: the (rescaled) action.  rescale_action's own clip to [-1, 1] may be left out by the caller: the thrust clip below
-// is to [a_low, a_high], a sub-interval, and clip(clip(x, -1, 1), lo, hi) = clip(x, lo, hi).  a: the raw action (NaN test).
-DN_DEV float rotor_force_from_cmd(float cmd, float a, float &torque, float *rpm_out = nullptr, bool nan_check = true)
-{
-    // PBDroneEnv._preprocessAction, PBDroneEnv.py:889.  The clip makes thrust >= a_low > 0, so cmd2pwm's
-    // maximum(thrust, 0) (env_utils.py:29) is the identity.
-    const float thrust = __builtin_amdgcn_fmed3f(cmd, A_LOW32, A_HIGH32);
-    const float t = div_const32(thrust, KF32, INV_KF32);             // env_utils.py:30 (n_motor = 1)
-    const float s = sqrt_rn32(t);
-    float pwm = div_const32(s - PWM2RPM_CONST32, PWM2RPM_SCALE32, INV_SCALE32);
-    pwm = __builtin_amdgcn_fmed3f(pwm, MIN_PWM32, MAX_PWM32);        // env_utils.py:39
-    const float r0 = PWM2RPM_SCALE32 * pwm;
-    const float rpm = r0 + PWM2RPM_CONST32;          // pwm2rpm, env_utils.py:58
-    const float sq = rpm * rpm;                      // BaseAviary._physics, BaseAviary.py:776-777
-    const bool nan = nan_check && a != a;            // np.clip / sqrt propagate NaN
-    if (rpm_out) *rpm_out = nan ? a : rpm;
-    torque = nan ? a : sq * KM32;
-    return nan ? a : sq * KF32;
-}
-DN_DEV float rotor_force_from_action(float a, bool normalize_actions, float &torque, float *rpm_out = nullptr, bool nan_check = true)
-{
-    return rotor_force_from_cmd(normalize_actions ? rescale_unclipped32(a) : a, a, torque, rpm_out, nan_check);
-}
-// The saturation fast path (round 6).  The thrust clip of rotor_force_from_cmd is the chain's ONLY read of the command, so every
-// command <= a_low yields the force / torque of a_low and every command >= a_high those of a_high; rescale_action is monotone in
-// the action, so in raw-action space that is two float32 thresholds (csrc/dn_action_sat.h; tests/tools/check_action_chain_exact.c
-// proves thresholds and constants against the literal numpy-order chain for all 2^32 - 2^24 non-NaN actions).  99.6 % of U(-1,1)
-// actions -- and of a sigma = 1 Gaussian policy's -- lie outside the 0.0072-wide band in between: per rotor the WAVE takes the chain
-// only if one of its lanes is inside the band (or NaN: both compares false), 21 % of rotor evaluations at U(-1,1); then every
-// lane takes it, and a saturated lane's chain returns the same two constants: bit-exact by construction either way.
-constexpr float ACT_SAT_LO32 = __builtin_bit_cast(float, DN_ACT_SAT_LO_BITS), ACT_SAT_HI32 = __builtin_bit_cast(float, DN_ACT_SAT_HI_BITS);
-constexpr float F_LO32 = __builtin_bit_cast(float, DN_F_LO_BITS), F_HI32 = __builtin_bit_cast(float, DN_F_HI_BITS);
-constexpr float TQ_LO32 = __builtin_bit_cast(float, DN_TQ_LO_BITS), TQ_HI32 = __builtin_bit_cast(float, DN_TQ_HI_BITS);
-static_assert(__builtin_bit_cast(unsigned, A_LOW32) == DN_A_LOW_BITS && __builtin_bit_cast(unsigned, A_HIGH32) == DN_A_HIGH_BITS,
-              "dn_action_sat.h was derived for other action bounds");
-DN_DEV float rotor_force_sat(const float a, const bool normalize_actions, float &torque)
-{
-    const float t_lo = normalize_actions ? ACT_SAT_LO32 : A_LOW32, t_hi = normalize_actions ? ACT_SAT_HI32 : A_HIGH32;   // wave-uniform
-    const bool hi = a >= t_hi, lo = a <= t_lo;
-    float f = hi ? F_HI32 : F_LO32;
-    torque = hi ? TQ_HI32 : TQ_LO32;
-    if (__ballot(!(hi || lo)) != 0ull)            // wave-uniform: a lane inside the band, or a NaN (np.clip / sqrt propagate it: the chain's own select)
-        f = rotor_force_from_cmd(normalize_actions ? rescale_unclipped32(a) : a, a, torque, nullptr, true);
-    return f;
-}
-
-DN_DEV float z_torque32(const float tq[4])
-{   // z_torque = -t0 + t1 - t2 + t3, left to right in float32 (BaseAviary.py:780)
-    float z = -tq[0];
-    z = z + tq[1];
-    z = z - tq[2];
-    z = z + tq[3];
-    return z;
-}
 
 // ---- N4: options that are present but unreachable in the reference (BaseAviary.step pins Physics.PYB,
 // BaseAviary.py:411; PBDroneEnv overrides _preprocessAction).  Compiled only into the XOPT kernels.  These helpers
@@ -207,120 +107,6 @@ DN_DEV double drag_omega_sum(const float4 last, bool rpm_f32)
     return sum + w[3];
 }
 
-// ---- noise (BASELINE config 5; sigma = 0 is the reference): Philox4x32-10 + float64 Box-Muller ------
-DN_DEV void philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-        unsigned n1 = (unsigned)p1;
-        unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        unsigned n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// The EXACT form (draws that feed the dynamics: action noise, the policies' sampling, random spawn): Box-Muller on one pair of Philox words, float64 throughout, every operation spelled out (no libm call: the device
-// library's log / sin / cos carry argument-reduction paths for inputs that cannot occur here and cost ~300 instructions
-// a pair; this is ~80).  u = (r + 0.5) / 2^32 lies strictly inside (0, 1).
-//   ln u1:  u1 = m 2^e, m in [sqrt(1/2), sqrt(2)),  ln m = 2 atanh(s) = 2 s (1 + s^2/3 + ... + s^14/15),  s = (m-1)/(m+1),
-//           |s| <= 0.1716: truncation 3e-14 relative, and no cancellation as u1 -> 1 (e = 0, m - 1 exact);
-//   angle:  2 pi u2 = k pi/2 + theta, k = rint(4 u2), theta = 2 pi (u2 - k/4) in [-pi/4, pi/4] (the subtraction is
-//           exact), sin / cos Taylor to theta^13 / theta^14 (2e-14), quadrant fix-up by k.
-// Equal to the libm form (log, sqrt, cos, sin of the C library) to ~1e-13 before the float32 cast.
-DN_DEV void box_muller_pair64(unsigned ra, unsigned rb, float &z0, float &z1)
-{
-    const double u1 = ((double)ra + 0.5) * (1.0 / 4294967296.0);
-    const double u2 = ((double)rb + 0.5) * (1.0 / 4294967296.0);
-    double m = __builtin_amdgcn_frexp_mant(u1);            // [0.5, 1)
-    int e = __builtin_amdgcn_frexp_exp(u1);
-    if (m < 0.70710678118654752440) { m = m + m; e = e - 1; }
-    const double num = m - 1.0, den = m + 1.0;
-    double r = __builtin_amdgcn_rcp(den);
-    double q = __builtin_fma(-den, r, 1.0);
-    r = __builtin_fma(r, q, r);
-    q = __builtin_fma(-den, r, 1.0);
-    r = __builtin_fma(r, q, r);
-    const double sv = num * r, s2 = sv * sv;
-    double pl = 1.0 / 15.0;
-    pl = __builtin_fma(pl, s2, 1.0 / 13.0);
-    pl = __builtin_fma(pl, s2, 1.0 / 11.0);
-    pl = __builtin_fma(pl, s2, 1.0 / 9.0);
-    pl = __builtin_fma(pl, s2, 1.0 / 7.0);
-    pl = __builtin_fma(pl, s2, 1.0 / 5.0);
-    pl = __builtin_fma(pl, s2, 1.0 / 3.0);
-    pl = __builtin_fma(pl, s2, 1.0);
-    const double ln_u1 = __builtin_fma((double)e, 0.69314718055994530942, (sv + sv) * pl);
-    const double t = -2.0 * ln_u1;                         // > 0
-    double y = __builtin_amdgcn_rsq(t);
-    y = y * __builtin_fma(-0.5 * t * y, y, 1.5);
-    y = y * __builtin_fma(-0.5 * t * y, y, 1.5);
-    const double rad = t * y;
-    const double k4 = __builtin_rint(u2 * 4.0);
-    const double th = (2.0 * 3.14159265358979323846) * __builtin_fma(k4, -0.25, u2);
-    const double t2 = th * th;
-    double ps = 1.0 / 6227020800.0;                        //  1/13!
-    ps = __builtin_fma(ps, t2, -1.0 / 39916800.0);         // -1/11!
-    ps = __builtin_fma(ps, t2, 1.0 / 362880.0);
-    ps = __builtin_fma(ps, t2, -1.0 / 5040.0);
-    ps = __builtin_fma(ps, t2, 1.0 / 120.0);
-    ps = __builtin_fma(ps, t2, -1.0 / 6.0);
-    const double sn = __builtin_fma(th * t2, ps, th);
-    double pc = -1.0 / 87178291200.0;                      // -1/14!
-    pc = __builtin_fma(pc, t2, 1.0 / 479001600.0);         //  1/12!
-    pc = __builtin_fma(pc, t2, -1.0 / 3628800.0);
-    pc = __builtin_fma(pc, t2, 1.0 / 40320.0);
-    pc = __builtin_fma(pc, t2, -1.0 / 720.0);
-    pc = __builtin_fma(pc, t2, 1.0 / 24.0);
-    pc = __builtin_fma(pc, t2, -0.5);
-    const double cs = __builtin_fma(pc, t2, 1.0);
-    const int k = (int)k4 & 3;
-    const double c = (k & 1) ? sn : cs, d = (k & 1) ? cs : sn;          // odd quadrants swap the two ...
-    const double cosv = (k == 1 || k == 2) ? -c : c;                    // ... and the signs follow cos(a + pi/2) = -sin a
-    const double sinv = (k >= 2) ? -d : d;
-    z0 = (float)(rad * cosv);
-    z1 = (float)(rad * sinv);
-}
-// The FLOAT32 form (observation noise: 13 of the 17 draws of a config-5 step, 26 when an episode ends): the same Box-Muller on the
-// hardware transcendentals, ~25 instructions a pair instead of ~80.  Observation noise is added to a float32 output and feeds nothing
-// back inside the environment, so an error of 1e-6 in z is 1e-8 in the observation; the draws that DO feed the dynamics keep the exact
-// form above, because the action chain rounds in float32 and the near-cancelling rotor torques of a hovering drone turn a last-bit
-// difference in one thrust into 1e-4 in the unit angular-velocity columns (seen when the action noise was tried in this form).
-// Care is taken where float32 would lose the draw:
-//   ln u1:  for u1 < 1/2 the float32 value of u1 carries it to 2^-24 relative; for u1 >= 1/2 it does not (u1 -> 1 rounds to 1 and the
-//           radius to 0), so the COMPLEMENT w = 1 - u1 = (~word + 0.5) / 2^32 is formed from the integer (exact to 2^-24 relative)
-//           and -ln(1 - w) taken as w (1 + w/2 + w^2/3) below w = 2^-9 (next term: 2e-9 relative) and as -ln2 log2(1 - w) above;
-//   angle:  v_sin_f32 / v_cos_f32 take their argument in revolutions, i.e. u2 itself: no 2 pi product to round.
-// Against the float64 libm evaluation of the same formula the draws differ by at most 1.2e-6 absolute (mean 7e-8; measured over 3.3e7 draws:
-// tests/test_gpu_parity.py::test_observation_noise_draws_match_their_definition); sigma z enters the state at sigma <= 1e-2.
-DN_DEV void box_muller_pair32(unsigned ra, unsigned rb, float &z0, float &z1)
-{
-    const bool upper = ra >= 0x80000000u;
-    const float u1 = __builtin_fmaf((float)ra, 2.3283064365386963e-10f, 1.1641532182693481e-10f);          // (ra + 0.5) 2^-32
-    const float w = __builtin_fmaf((float)(~ra), 2.3283064365386963e-10f, 1.1641532182693481e-10f);        // 1 - u1, exact to 2^-24 relative
-    const float arg = upper ? 1.0f - w : u1;
-    float L = -0.69314718055994530942f * __builtin_amdgcn_logf(arg);                                          // -ln(arg); v_log_f32 = log2
-    const float series = w * __builtin_fmaf(w, __builtin_fmaf(w, 0.33333333333333333f, 0.5f), 1.0f);
-    L = (upper && w < 0.001953125f) ? series : L;
-    const float rad = __builtin_amdgcn_sqrtf(L + L);
-    const float u2 = __builtin_fmaf((float)rb, 2.3283064365386963e-10f, 1.1641532182693481e-10f);
-    z0 = rad * __builtin_amdgcn_cosf(u2);                                                                    // cos(2 pi u2)
-    z1 = rad * __builtin_amdgcn_sinf(u2);
-}
-// Philox counter = (drone id lo, drone id hi, vector step lo, stream | vector step hi << 8): the 64-bit vector-step counter
-// enters whole, so the streams do not repeat when its low word wraps (2^32 vector steps = hours of fused stepping);
-// stream ids are below 256.
-template <bool EXACT = true>
-DN_DEV void noise4(unsigned long long seed, unsigned long long gid, unsigned long long step, unsigned stream, float z[4])
-{
-    unsigned r[4];
-    philox4x32((unsigned)gid, (unsigned)(gid >> 32), (unsigned)step, stream | ((unsigned)(step >> 32) << 8), (unsigned)seed, (unsigned)(seed >> 32), r);
-    if (EXACT) { box_muller_pair64(r[0], r[1], z[0], z[1]); box_muller_pair64(r[2], r[3], z[2], z[3]); }
-    else { box_muller_pair32(r[0], r[1], z[0], z[1]); box_muller_pair32(r[2], r[3], z[2], z[3]); }
-}
 // The observation noise's draws: the float32 form, or -- DN_EXACT_OBS_NOISE=1, for runs that must replay bit for bit on another GPU generation
 // or against the CPU definition -- the exact form the dynamics-feeding draws always use (one wave-uniform branch; ~3x the instructions a pair).
 DN_DEV void obs_pair(const DnParams &p, const unsigned ra, const unsigned rb, float &z0, float &z1)
@@ -2529,27 +2315,7 @@ DN_DEV Flight<R> fly(const DnParams &p, unsigned long long gid, unsigned long lo
 // dn_step_sampled: SB3 DiagGaussianDistribution.sample / log_prob and the np.clip of collect_rollouts [3P-recall], drawn
 // where the action is consumed: action = mean + exp(log_std) z, z ~ N(0,1) from the environment's Philox stream (seed,
 // global drone id, the tile's vector-step counter, stream 9); the unclipped action and its log-probability go to the
-// rollout buffer, the clipped one into the step.  Same expressions as dn_policy_sample_kernel (same bits).
-// tanh(x) = 1 - 2 / (1 + e^{2x}): v_exp_f32 + v_rcp_f32 (absolute error ~1e-7; +-1 exactly once e^{2x} over- or underflows)
-DN_DEV float tanh_squash(const float x)
-{
-    const float e = __builtin_amdgcn_exp2f(x * 2.88539008177792681472f);        // 2 log2(e)
-    return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-}
-// One drone's squashed-Gaussian draw (SB3 SAC Actor [3P-recall]): shared by dn_squashed_sample_kernel and the step kernels
-// (dn_step_squashed), so that the two produce the same bits.  The log-probability costs four logf: only on request.
-DN_DEV void squashed_draw(const float4 m, const float4 l, const float z[4], const bool want_lp, float a[4], float &lp)
-{
-    const float mu[4] = {m.x, m.y, m.z, m.w};
-    const float ls[4] = {clipv(l.x, -20.0f, 2.0f), clipv(l.y, -20.0f, 2.0f), clipv(l.z, -20.0f, 2.0f), clipv(l.w, -20.0f, 2.0f)};
-    lp = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] = tanh_squash(mu[j] + expf(ls[j]) * z[j]);
-    if (want_lp) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) lp += (-0.5f * z[j] * z[j] - ls[j] - 0.91893853320467274178f) - logf(1.0f - a[j] * a[j] + 1e-6f);
-    }
-}
+// rollout buffer, the clipped one into the step.  The draw is dn_policy_sample_kernel's (gaussian_draw, dn_policy_draw.h).
 // m = the policy's mean row (PPO) or its mu row with l = the log_std row (SAC, io.sample_squash); taken by value so that a kernel
 // that has just COMPUTED them (the fused policy + step launch, dn_fused.hip) hands them over without a trip through memory
 DN_DEV float4 sample_action_from(const DnStepIO &io, const float4 m, const float4 l, const unsigned long long gid, const unsigned long long step,
@@ -2559,16 +2325,12 @@ DN_DEV float4 sample_action_from(const DnStepIO &io, const float4 m, const float
     if (!io.sample_deterministic) noise4(io.sample_seed, gid, step, 9u, z);
     float a[4], lp = 0.0f;
     if (io.sample_squash) {
-        // dn_step_squashed: SAC's Actor on the (mu | log_std) rows of dn_mlp_forward(arch = SAC) -- the expressions of
-        // dn_squashed_sample_kernel (same bits); the squashed action is already inside the action box
+        // dn_step_squashed: SAC's Actor on the (mu | log_std) rows of dn_mlp_forward(arch = SAC) -- the draw of
+        // dn_squashed_sample_kernel; the squashed action is already inside the action box
         squashed_draw(m, l, z, io.logp_out != nullptr, a, lp);
     } else {
         const float mu[4] = {m.x, m.y, m.z, m.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = mu[j] + expf(io.log_std[j]) * z[j];
-            lp += -0.5f * z[j] * z[j] - io.log_std[j] - 0.91893853320467274178f;
-        }
+        gaussian_draw(mu, io.log_std, z, a, lp);
     }
     if (active) {
         reinterpret_cast<float4 *>(io.act_out)[i] = make_float4(a[0], a[1], a[2], a[3]);
@@ -4537,303 +4299,10 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_reset_kernel(const DnParams p, fl
     store_obs_tile(s_tile, obs + tile_base * DN_OBS_DIM, rows, lane, o);
 }
 
-// =====================================================================================================
-// N1: GAE, one lane per drone, time-reversed scan (cleanRLPPO.py:234-248).  float32, unfused, in the
-// reference's operation order so the result is bit-identical to the torch float32 loop.
-// =====================================================================================================
-__global__ __launch_bounds__(256) void dn_gae_kernel(const float *__restrict__ rewards, const float *__restrict__ values,
-                                                     const uint8_t *__restrict__ dones, const float *__restrict__ last_values,
-                                                     const uint8_t *__restrict__ last_dones, long long T, long long N,
-                                                     float gamma, float gl, float *__restrict__ adv, float *__restrict__ ret)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    float last = 0.0f;
-    float nnt = 1.0f - (float)last_dones[i];
-    float nv = last_values[i];
-    for (long long t = T - 1; t >= 0; --t) {
-        const float v = values[t * N + i];
-        float gv = gamma * nv;
-        float delta = rewards[t * N + i] + gv * nnt;
-        delta = delta - v;
-        float k = gl * nnt;
-        last = delta + k * last;
-        adv[t * N + i] = last;
-        ret[t * N + i] = last + v;
-        nnt = 1.0f - (float)dones[t * N + i];
-        nv = v;
-    }
-}
-
-// =====================================================================================================
-// Episode-done compaction: ballot words -> ordered index list (popcount + block-wide exclusive scan).
-// One workgroup of 1024 lanes per 1024 words (65 536 drones), one word per lane.  A workgroup's place in the list is the
-// number of set bits in all earlier words, which it counts itself (coalesced popcount sweep + reduction: at 2 M drones the
-// last of 32 workgroups re-reads 256 KB out of L2) -- no second launch, no scratch buffer, no atomics, and the list stays in
-// ascending order whatever order the workgroups run in.
-// =====================================================================================================
-__global__ __launch_bounds__(1024) void dn_compact_kernel(const unsigned long long *__restrict__ mask, long long n,
-                                                          int32_t *__restrict__ indices, int32_t *__restrict__ count)
-{
-    __shared__ int s_wave[16], s_before[16];
-    const long long words = (n + 63) / 64;
-    const long long w_base = (long long)blockIdx.x * 1024;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int before = 0;
-    for (long long w = threadIdx.x; w < w_base; w += 1024) before += __popcll(mask[w]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
-    const long long w = w_base + threadIdx.x;
-    unsigned long long mword = w < words ? mask[w] : 0ull;
-    const int mine = __popcll(mword);
-    // exclusive scan: within the wave by shuffles, across the 16 waves through LDS
-    int incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    if (lane == 0) s_before[wave] = before;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < 16; ++k) base += s_before[k];
-    for (int k = 0; k < wave; ++k) base += s_wave[k];
-    int pos = base + incl - mine;
-    while (mword) {
-        int b = __ffsll((long long)mword) - 1;
-        indices[pos++] = (int32_t)(w * 64 + b);
-        mword &= mword - 1;
-    }
-    if (threadIdx.x == 1023 && blockIdx.x == gridDim.x - 1) *count = base + incl;
-}
-
-// dn_pack_done: the compaction above with, next to every index, the episode-end record of that drone as ONE 64-byte row --
-// terminal_observation (13), Monitor return, Monitor length (int bits), TimeLimit.truncated | found_targets << 8 (int bits) -- so that
-// the NumPy step() brings the few finished drones' records to the host in one short copy instead of four whole per-drone arrays.
-__global__ __launch_bounds__(1024) void dn_compact_pack_kernel(const unsigned long long *__restrict__ mask, long long n,
-                                                               const float *__restrict__ terminal_obs, const float *__restrict__ ep_return,
-                                                               const int32_t *__restrict__ ep_length, const uint8_t *__restrict__ truncated,
-                                                               const int32_t *__restrict__ found, int32_t *__restrict__ indices,
-                                                               int32_t *__restrict__ count, float *__restrict__ packed)
-{
-    __shared__ int s_wave[16], s_before[16];
-    const long long words = (n + 63) / 64;
-    const long long w_base = (long long)blockIdx.x * 1024;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int before = 0;
-    for (long long w = threadIdx.x; w < w_base; w += 1024) before += __popcll(mask[w]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
-    const long long w = w_base + threadIdx.x;
-    unsigned long long mword = w < words ? mask[w] : 0ull;
-    const int mine = __popcll(mword);
-    int incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    if (lane == 0) s_before[wave] = before;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < 16; ++k) base += s_before[k];
-    for (int k = 0; k < wave; ++k) base += s_wave[k];
-    int pos = base + incl - mine;
-    while (mword) {
-        const int b = __ffsll((long long)mword) - 1;
-        const long long i = w * 64 + b;
-        indices[pos] = (int32_t)i;
-        float *row = packed + (long long)pos * 16;
-#pragma unroll
-        for (int k = 0; k < DN_OBS_DIM; ++k) row[k] = terminal_obs[i * DN_OBS_DIM + k];
-        row[13] = ep_return[i];
-        row[14] = __int_as_float(ep_length[i]);
-        row[15] = __int_as_float((int)truncated[i] | (found[i] << 8));
-        ++pos;
-        mword &= mword - 1;
-    }
-    if (threadIdx.x == 1023 && blockIdx.x == gridDim.x - 1) *count = base + incl;
-}
-
-// A1-A3 on their own (dn_preprocess_action): N x PBDroneEnv._preprocessAction + the force/torque lines of
-// BaseAviary._physics, so the float32 chain can be checked bit for bit against the reference's golden vectors.
-__global__ __launch_bounds__(256) void dn_action_chain_kernel(const float4 *__restrict__ actions, long long n, int normalize_actions,
-                                                              float4 *__restrict__ rpm, float4 *__restrict__ forces,
-                                                              float *__restrict__ z_torque)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 A = actions[i];
-    const float a[4] = {A.x, A.y, A.z, A.w};
-    float tq[4], f[4], r[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float tq_chain;
-        rotor_force_from_action(a[j], normalize_actions != 0, tq_chain, &r[j]);          // the rpm output: the chain itself
-        f[j] = rotor_force_sat(a[j], normalize_actions != 0, tq[j]);                     // forces / torque: the path the step kernels take
-    }
-    if (rpm) rpm[i] = make_float4(r[0], r[1], r[2], r[3]);
-    if (forces) forces[i] = make_float4(f[0], f[1], f[2], f[3]);
-    if (z_torque) z_torque[i] = z_torque32(tq);
-}
-
-// Rollout-step glue around the policy network (the host loop's small element-wise kernels, fused):
-//   dn_policy_sample_kernel  -- SB3 DiagGaussianDistribution.sample / log_prob and the np.clip of collect_rollouts
-//                               [3P-recall]: actions = mean + exp(log_std) z, z ~ N(0,1) from the environment's Philox
-//                               stream (seed, global drone id, the tile's vector-step counter, stream 9), the clipped copy
-//                               that goes to dn_step, and log N(actions; mean, std) summed over the four action dims.
-//   dn_add_bootstrap_kernel  -- reward += gamma * V(terminal_observation) where TimeLimit.truncated (SB3's
-//                               collect_rollouts bootstrap) [3P-recall].
-__global__ __launch_bounds__(256) void dn_policy_sample_kernel(const DnParams p, const float4 *__restrict__ mean,
-                                                               const float4 log_std, const unsigned long long seed,
-                                                               const int deterministic, float4 *__restrict__ actions,
-                                                               float4 *__restrict__ clipped, float *__restrict__ log_prob)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p.n) return;
-    const float4 m = mean[i];
-    const float mu[4] = {m.x, m.y, m.z, m.w};
-    const float ls[4] = {log_std.x, log_std.y, log_std.z, log_std.w};
-    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (!deterministic)
-        noise4(seed, (unsigned long long)(p.env_id_offset + i), p.st.stats[i / DN_BLOCK].step_count, 9u, z);
-    float a[4], lp = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        a[j] = mu[j] + expf(ls[j]) * z[j];
-        // log N(a; mu, sigma) with (a - mu)/sigma = z
-        lp += -0.5f * z[j] * z[j] - ls[j] - 0.91893853320467274178f;
-    }
-    actions[i] = make_float4(a[0], a[1], a[2], a[3]);
-    clipped[i] = make_float4(clipv(a[0], -1.0f, 1.0f), clipv(a[1], -1.0f, 1.0f), clipv(a[2], -1.0f, 1.0f), clipv(a[3], -1.0f, 1.0f));
-    log_prob[i] = lp;
-}
-
-// dn_squashed_sample_kernel -- SB3 SAC's Actor on top of the (mu | log_std) rows of dn_mlp_forward(arch = SAC) [3P-recall of
-// sac/policies.py and SquashedDiagGaussianDistribution]: log_std clamped to [-20, 2], pre = mu + exp(log_std) z with z ~ N(0,1)
-// from the environment's Philox stream (seed, global drone id, the tile's vector-step counter, stream 9: as dn_policy_sample),
-// action = tanh(pre) -- already inside dn_step's [-1, 1] --, log_prob = sum_j log N(pre_j; mu_j, sigma_j) - log(1 - a_j^2 + 1e-6).
-__global__ __launch_bounds__(256) void dn_squashed_sample_kernel(const DnParams p, const float4 *__restrict__ mu_log_std,
-                                                                 const unsigned long long seed, const int deterministic,
-                                                                 float4 *__restrict__ actions, float *__restrict__ log_prob)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p.n) return;
-    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (!deterministic)
-        noise4(seed, (unsigned long long)(p.env_id_offset + i), p.st.stats[i / DN_BLOCK].step_count, 9u, z);
-    float a[4], lp;
-    squashed_draw(mu_log_std[2 * i], mu_log_std[2 * i + 1], z, log_prob != nullptr, a, lp);
-    actions[i] = make_float4(a[0], a[1], a[2], a[3]);
-    if (log_prob) log_prob[i] = lp;
-}
-
-__global__ __launch_bounds__(256) void dn_add_bootstrap_kernel(float *__restrict__ reward, const float *__restrict__ terminal_value,
-                                                               const uint8_t *__restrict__ truncated, float gamma, long long n)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && truncated[i]) reward[i] = reward[i] + gamma * terminal_value[i];
-}
-
-__global__ __launch_bounds__(256) void dn_set_step_count_kernel(DnStatSlot *slots, long long blocks, unsigned long long value)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < blocks; i += (long long)gridDim.x * blockDim.x)
-        slots[i].step_count = value;
-}
-
-// dn_set_sensor / dn_get_sensor: history[i][j] (the pre-bias row of j control steps ago, j = 0..8) <-> the ring.  The last vector step run
-// is the tile's counter - 1, so the row of j steps ago sits in the slot of vector step counter - 1 - j.  One thread per (drone, j).
-__global__ __launch_bounds__(256) void dn_sensor_history_kernel(const DnStatSlot *slots, const long long n, const DnSens sn, float *history,
-                                                                const int to_ring)
-{
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * (DN_MAX_LATENCY + 1)) return;
-    const long long i = t / (DN_MAX_LATENCY + 1);
-    const int j = (int)(t - i * (DN_MAX_LATENCY + 1));
-    const unsigned long long sc = slots[i / DN_BLOCK].step_count;
-    float4 *row = sens_ring(sn, n, sens_slot(sn, sc - 1ull - (unsigned long long)j));
-    float *h = history + t * DN_OBS_DIM;
-    float o[DN_OBS_DIM];
-    if (to_ring) {
-#pragma unroll
-        for (int c = 0; c < DN_OBS_DIM; ++c) o[c] = h[c];
-        sens_store_quads(row, n, i, o);
-    } else {
-        sens_load_quads(row, n, i, o);
-#pragma unroll
-        for (int c = 0; c < DN_OBS_DIM; ++c) h[c] = o[c];
-    }
-}
-// bias[i][13] <-> the four quads of drone i
-__global__ __launch_bounds__(256) void dn_sensor_bias_kernel(const DnSens sn, const long long n, float *bias, const int to_dev)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float o[DN_OBS_DIM];
-    if (to_dev) {
-#pragma unroll
-        for (int c = 0; c < DN_OBS_DIM; ++c) o[c] = bias[i * DN_OBS_DIM + c];
-        sens_store_quads(sn.bias, n, i, o);
-    } else {
-        sens_load_quads(sn.bias, n, i, o);
-#pragma unroll
-        for (int c = 0; c < DN_OBS_DIM; ++c) bias[i * DN_OBS_DIM + c] = o[c];
-    }
-}
-
-__global__ __launch_bounds__(256) void dn_fill4_kernel(float4 *dst, float4 v, long long n)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dst[i] = v;
-}
-// The copy ceiling of the box (dn_stream_copy): ONE 16-byte load and one 16-byte store per lane, no loop -- the form that measured
-// fastest on MI355X (profiles/r04_copy_sweep.txt: 6 237 GB/s read + write over 1 GiB, against 4 100-5 200 for grid-stride loops of
-// 4-64 workgroups per CU with or without non-temporal hints, 5 300-5 750 for a contiguous chunk per workgroup, 4 689 for hipMemcpyAsync
-// and ~5 500 for torch's copy_): the dispatcher streams workgroups onto CUs as they drain, and every wave has exactly one load in flight.
-typedef float dn_v4f __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void dn_stream_copy_kernel(const float4 *__restrict__ src4, float4 *__restrict__ dst4, long long n16)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n16) reinterpret_cast<dn_v4f *>(dst4)[i] = reinterpret_cast<const dn_v4f *>(src4)[i];
-}
-__global__ __launch_bounds__(256) void dn_filld_kernel(double *dst, double v, long long n)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dst[i] = v;
-}
-
 }  // namespace
 
 #if DN_TU == 1
 int dn_norm_exact_compiled_in() { return DN_NORM_EXACT; }
-
-hipError_t dn_launch_fill4(float4 *dst, float4 v, long long n, hipStream_t stream)
-{
-    if (n <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(dn_fill4_kernel, dim3(grid), dim3(256), 0, stream, dst, v, n);
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_stream_copy(void *dst, const void *src, long long n16, int num_cus, hipStream_t stream)
-{
-    (void)num_cus;
-    const long long per = 256ll * 0x40000000ll;                  // grid.x <= 2^30 workgroups per launch
-    for (long long off = 0; off < n16; off += per) {
-        const long long m = n16 - off < per ? n16 - off : per;
-        hipLaunchKernelGGL(dn_stream_copy_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, (const float4 *)src + off, (float4 *)dst + off, m);
-    }
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_filld(double *dst, double v, long long n, hipStream_t stream)
-{
-    if (n <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(dn_filld_kernel, dim3(grid), dim3(256), 0, stream, dst, v, n);
-    return hipGetLastError();
-}
-
 #endif
 
 // Kernel shape: two or three waves per 64 drones where the chip would otherwise idle (the step is bound by one wave's
@@ -4990,6 +4459,49 @@ hipError_t dn_launch_reset(const DnParams &p, float *obs, bool f32, hipStream_t 
     return hipGetLastError();
 }
 
+// The two sensor transfer kernels are not templates: they sit here, in the one unit that launches them, so that no other unit emits them.
+namespace {
+// dn_set_sensor / dn_get_sensor: history[i][j] (the pre-bias row of j control steps ago, j = 0..8) <-> the ring.  The last vector step run
+// is the tile's counter - 1, so the row of j steps ago sits in the slot of vector step counter - 1 - j.  One thread per (drone, j).
+__global__ __launch_bounds__(256) void dn_sensor_history_kernel(const DnStatSlot *slots, const long long n, const DnSens sn, float *history,
+                                                                const int to_ring)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * (DN_MAX_LATENCY + 1)) return;
+    const long long i = t / (DN_MAX_LATENCY + 1);
+    const int j = (int)(t - i * (DN_MAX_LATENCY + 1));
+    const unsigned long long sc = slots[i / DN_BLOCK].step_count;
+    float4 *row = sens_ring(sn, n, sens_slot(sn, sc - 1ull - (unsigned long long)j));
+    float *h = history + t * DN_OBS_DIM;
+    float o[DN_OBS_DIM];
+    if (to_ring) {
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) o[c] = h[c];
+        sens_store_quads(row, n, i, o);
+    } else {
+        sens_load_quads(row, n, i, o);
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) h[c] = o[c];
+    }
+}
+// bias[i][13] <-> the four quads of drone i
+__global__ __launch_bounds__(256) void dn_sensor_bias_kernel(const DnSens sn, const long long n, float *bias, const int to_dev)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float o[DN_OBS_DIM];
+    if (to_dev) {
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) o[c] = bias[i * DN_OBS_DIM + c];
+        sens_store_quads(sn.bias, n, i, o);
+    } else {
+        sens_load_quads(sn.bias, n, i, o);
+#pragma unroll
+        for (int c = 0; c < DN_OBS_DIM; ++c) bias[i * DN_OBS_DIM + c] = o[c];
+    }
+}
+}  // namespace
+
 hipError_t dn_launch_sensor_history(const DnParams &p, const DnSens &sn, float *history, int to_ring, hipStream_t stream)
 {
     const long long m = p.n * (DN_MAX_LATENCY + 1);
@@ -5017,75 +4529,6 @@ hipError_t dn_launch_eval_kinematics(const DnParams &p, const DnStepIO &io, cons
     return hipGetLastError();
 }
 
-hipError_t dn_launch_gae(const float *rewards, const float *values, const uint8_t *dones, const float *last_values,
-                         const uint8_t *last_dones, long long T, long long N, float gamma, float gl, float *adv,
-                         float *ret, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(dn_gae_kernel, dim3(grid), dim3(256), 0, stream, rewards, values, dones, last_values,
-                       last_dones, T, N, gamma, gl, adv, ret);
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_action_chain(const float *actions, long long n, int normalize_actions, float *rpm, float *forces,
-                                  float *z_torque, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(dn_action_chain_kernel, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4 *>(actions), n,
-                       normalize_actions, reinterpret_cast<float4 *>(rpm), reinterpret_cast<float4 *>(forces), z_torque);
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_squashed_sample(const DnParams &p, const float *mu_log_std, unsigned long long seed, int deterministic,
-                                     float *actions, float *log_prob, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((p.n + 255) / 256);
-    hipLaunchKernelGGL(dn_squashed_sample_kernel, dim3(grid), dim3(256), 0, stream, p, reinterpret_cast<const float4 *>(mu_log_std),
-                       seed, deterministic, reinterpret_cast<float4 *>(actions), log_prob);
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_policy_sample(const DnParams &p, const float *mean, const float *log_std4, unsigned long long seed, int deterministic,
-                                   float *actions, float *clipped, float *log_prob, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((p.n + 255) / 256);
-    hipLaunchKernelGGL(dn_policy_sample_kernel, dim3(grid), dim3(256), 0, stream, p, reinterpret_cast<const float4 *>(mean),
-                       make_float4(log_std4[0], log_std4[1], log_std4[2], log_std4[3]), seed, deterministic,
-                       reinterpret_cast<float4 *>(actions), reinterpret_cast<float4 *>(clipped), log_prob);
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_add_bootstrap(float *reward, const float *terminal_value, const uint8_t *truncated, float gamma, long long n,
-                                   hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(dn_add_bootstrap_kernel, dim3(grid), dim3(256), 0, stream, reward, terminal_value, truncated, gamma, n);
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_set_step_count(DnStatSlot *slots, long long blocks, unsigned long long value, hipStream_t stream)
-{
-    const unsigned grid = (unsigned)((blocks + 255) / 256 < 1024 ? (blocks + 255) / 256 : 1024);
-    hipLaunchKernelGGL(dn_set_step_count_kernel, dim3(grid), dim3(256), 0, stream, slots, blocks, value);
-    return hipGetLastError();
-}
-
-hipError_t dn_launch_compact(const unsigned long long *mask, long long n, int32_t *indices, int32_t *count,
-                             hipStream_t stream)
-{
-    const unsigned blocks = (unsigned)(((n + 63) / 64 + 1023) / 1024);
-    hipLaunchKernelGGL(dn_compact_kernel, dim3(blocks), dim3(1024), 0, stream, mask, n, indices, count);
-    return hipGetLastError();
-}
-hipError_t dn_launch_compact_pack(const unsigned long long *mask, long long n, const float *terminal_obs, const float *ep_return,
-                                  const int32_t *ep_length, const uint8_t *truncated, const int32_t *found, int32_t *indices, int32_t *count,
-                                  float *packed, hipStream_t stream)
-{
-    const unsigned blocks = (unsigned)(((n + 63) / 64 + 1023) / 1024);
-    hipLaunchKernelGGL(dn_compact_pack_kernel, dim3(blocks), dim3(1024), 0, stream, mask, n, terminal_obs, ep_return, ep_length, truncated, found,
-                       indices, count, packed);
-    return hipGetLastError();
-}
 #ifdef DN_PQX_STAMP
 extern "C" int dn_debug_pqx_stamps(long long *out)
 {

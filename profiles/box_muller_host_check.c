@@ -1,4 +1,4 @@
-/* Host check of the series behind box_muller_pair (drl-dronenavigation_amd/csrc/dn_kernels.hip): the same operation sequence in
+/* Host check of the series behind box_muller_pair (drl-dronenavigation_amd/csrc/dn_philox.h): the same operation sequence in
  * C (frexp + 2 atanh series, Taylor sine / cosine after the quadrant reduction; the IEEE division and sqrt stand in for
  * the device's v_rcp_f64 / v_rsq_f64 + Newton steps) against the libm form log / sqrt / cos / sin, over 2*10^7 random
  * word pairs plus the edge words.   gcc -O2 -o /tmp/bm profiles/box_muller_host_check.c -lm && /tmp/bm

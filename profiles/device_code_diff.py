@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the device code of two builds the same?  For a host-only change (launchers, the C ABI) the answer must be yes.
 
-    python profiles/device_code_diff.py OLD/csrc NEW/csrc [--new-template-arg | --model-level]
+    python profiles/device_code_diff.py OLD/csrc NEW/csrc [--new-template-arg | --model-level | --by-library]
 
 For every object with a gfx950 code object in both directories: extracts the code object (llvm-objdump --offloading), lists its FUNC
 symbols (llvm-readelf -s --wide), disassembles it (llvm-objdump -d), splits the text by symbol and strips the address and encoding
@@ -19,7 +19,19 @@ SAMPLE, DYN, WIND, ACT, SENS, PRIV, GOAL> is compared with the new kernel <R, NO
 `true`s in DYN ... GOAL; it is an error if they are not a prefix of that run.  The StepArg<...>::type inside the name maps likewise.
 Every other function pairs by identical name; both sides are masked as above.
 
-With either pairing, and without one, the entries of the code object's metadata note are compared for every paired kernel as well: VGPR,
+--by-library: for a change that moves functions between objects.  Functions pair by name over all objects of a library as build.py links
+it (the default library: every .o; the exact library: the .exact.o where there is one and the .o otherwise; an object that one side does
+not have is skipped on that side).  A function pairs with the one of the same object where both sides have it there, else with the first
+object in link order that holds it on the old side.  A further copy of a function that is paired (the old build emitted it in more
+objects, or the new one does) is listed as dropped or added and is not a difference; a NAME on one side only is.  Both sides are masked
+as under --new-template-arg: an object that lost or gained functions has another layout.  The per-object function counts are printed as
+before, then one summary per library, every moved function, and for every function whose text differs the number of differing lines.
+
+In every mode the padding lines at a function's very end are dropped (trailing s_nop / s_code_end lines and the disassembler's `...`):
+they fill up to the next function's alignment or the section's end, so they depend on the function's neighbour, not on the function.
+Nothing else is dropped: code that the compiler placed behind the last s_endpgm is compared like the rest.
+
+With any pairing, and without one, the entries of the code object's metadata note are compared for every paired kernel as well: VGPR,
 AGPR and SGPR counts, both spill counts, LDS size, private segment size and kernarg segment size.
 """
 import os
@@ -75,6 +87,9 @@ def functions(obj, work):
     for f in os.listdir(work):
         os.remove(os.path.join(work, f))
     assert set(text) == syms, (len(text), len(syms))
+    for t in text.values():                                         # the padding at a function's end depends on what follows it
+        while t and (t[-1].startswith(("s_nop", "s_code_end")) or t[-1] == "..."):
+            t.pop()
     return {s: "\n".join(t) for s, t in text.items()}, listed, meta
 
 
@@ -145,6 +160,76 @@ def masked(text):
     return "\n".join(out)
 
 
+def library_objects(exact):
+    """The objects with device code that build.py links into the default (exact: the exact) library, in link order."""
+    objs = objects()
+    if not exact:
+        return [o for o in objs if not o.endswith(".exact.o")]
+    return [o for o in objs if o.endswith(".exact.o") or o[:-2] + ".exact.o" not in objs]       # the .exact.o where there is one
+
+
+def by_library(old, new):
+    """--by-library: pairs by name over all objects of a library, so that a function that moved between objects is compared."""
+    bad, cache = 0, {}
+
+    def load(d, name):
+        if (d, name) not in cache:
+            path = os.path.join(d, name)
+            with tempfile.TemporaryDirectory() as work:
+                cache[d, name] = functions(path, work) if os.path.exists(path) else None
+        return cache[d, name]
+
+    for lib, exact in (("libdronenav.so", False), ("libdronenav_exact.so", True)):
+        print(f"{lib}:")
+        a, b, ma, mb = {}, {}, {}, {}                               # {(object, symbol): text}, {(object, kernel): metadata}
+        for name in library_objects(exact):
+            sides = [load(old, name), load(new, name)]
+            for got, text, meta in zip(sides, (a, b), (ma, mb)):
+                if got:
+                    text.update({(name, s): masked(t) for s, t in got[0].items()})      # an object that lost functions has another layout
+                    meta.update({(name, s): v for s, v in got[2].items()})
+            print(f"    {name}: " + " | ".join("absent" if not g else f"{len(g[0])} functions ({g[1]} FUNC entries)" for g in sides))
+        pairs = [(k, k) for k in a if k in b]                       # same object first ...
+        left_a, left_b = [k for k in a if k not in b], [k for k in b if k not in a]
+        moved = []
+        for kb in left_b:                                           # ... then by name: the first holder in link order
+            ka = next((k for k in left_a if k[1] == kb[1]), None)
+            if ka:
+                moved.append((ka, kb))
+                left_a.remove(ka)
+        names_a, names_b = {k[1] for k in a}, {k[1] for k in b}
+        dropped = [k for k in left_a if k[1] in names_b]            # further old copies of a function that the new build emits in fewer objects
+        extra = [k for k in left_b if k[1] in names_a and k not in {kb for _, kb in moved}]      # ... and in more
+        only_a, only_b = [k for k in left_a if k[1] not in names_b], [k for k in left_b if k[1] not in names_a]
+        differ = [(ka, kb) for ka, kb in pairs + moved if a[ka] != b[kb]]
+        kernels = [(ka, kb) for ka, kb in pairs + moved if ka in ma and kb in mb]
+        meta_differ = [(ka, kb) for ka, kb in kernels if ma[ka] != mb[kb]]
+        print(f"    {len(a)} | {len(b)} functions, {len(pairs)} paired in the same object, {len(moved)} moved, {len(dropped)} | {len(extra)} further "
+              f"copies of functions that are paired, {len(only_a)} only old, {len(only_b)} only new, {len(differ)} with different text; "
+              f"{len(kernels)} paired kernels ({len(ma)} | {len(mb)}), {len(meta_differ)} with different metadata")
+        for tag, group in (("old copy dropped", dropped), ("new copy added", extra)):
+            for obj, s in group:
+                print(f"    {tag}: {obj}: {s}")
+        for ka, kb in moved:
+            print(f"    moved: {kb[1]}: {ka[0]} -> {kb[0]}")
+        for tag, group in (("only old", only_a), ("only new", only_b)):
+            for obj, s in group:
+                print(f"    {tag}: {obj}: {s}")
+        for ka, kb in differ:
+            la, lb = a[ka].split("\n"), b[kb].split("\n")
+            n = sum(x != y for x, y in zip(la, lb)) + abs(len(la) - len(lb))
+            print(f"    differs: {kb[0]}: {kb[1]}: {n} lines of {len(la)} | {len(lb)}")
+            if len(la) == len(lb) and n <= 40:                      # few enough to read: the lines themselves
+                for i, (x, y) in enumerate(zip(la, lb)):
+                    if x != y:
+                        print(f"        {i}: {x}  |  {y}")
+        for ka, kb in meta_differ:
+            print(f"    metadata: {kb[0]}: {kb[1]}: " + ", ".join(f"{k} {ma[ka][k]} | {mb[kb][k]}" for k in META_KEYS if ma[ka][k] != mb[kb][k]))
+        bad += len(only_a) + len(only_b) + len(differ) + len(meta_differ)
+    print("device code identical" if not bad else f"{bad} differences")
+    return 1 if bad else 0
+
+
 def main(old, new, new_template_arg=False, model_level=False):
     bad = 0
     for name in objects():
@@ -180,4 +265,6 @@ def main(old, new, new_template_arg=False, model_level=False):
 
 if __name__ == "__main__":
     args = [x for x in sys.argv[1:] if not x.startswith("--")]
+    if "--by-library" in sys.argv[1:]:
+        sys.exit(by_library(args[0], args[1]))
     sys.exit(main(args[0], args[1], "--new-template-arg" in sys.argv[1:], "--model-level" in sys.argv[1:]))

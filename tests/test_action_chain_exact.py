@@ -1,5 +1,5 @@
 """The short float32 sequences of the HIP action chain (Markstein division by a constant, one-ulp sqrt fix-up;
-csrc/dn_kernels.hip rotor_force_from_action) are proven bit-identical to IEEE divide / sqrt by enumerating every
+csrc/dn_action_chain.h rotor_force_from_action) are proven bit-identical to IEEE divide / sqrt by enumerating every
 float32 input that can reach them (tests/tools/check_action_chain_exact.c), and the saturation fast path's constants
 (csrc/dn_action_sat.h: two raw-action thresholds, two force / torque pairs) are proven against the literal chain for
 EVERY float32 action, with and without rescale_action.  CPU only; the exhaustive run takes a few seconds on 8 cores."""

@@ -54,7 +54,7 @@ def chain_numpy(a, normalize):
 
 
 def test_saturation_fast_path_is_the_chain_bit_for_bit():
-    """rotor_force_sat (csrc/dn_kernels.hip): a wave takes the chain for a rotor only if one of its 64 lanes is inside the unsaturated band
+    """rotor_force_sat (csrc/dn_action_chain.h): a wave takes the chain for a rotor only if one of its 64 lanes is inside the unsaturated band
     (or NaN); otherwise every lane selects one of two constant pairs.  Waves built to take each path -- all lanes saturated, one lane inside
     the band, lanes exactly ON the two thresholds and one float32 inside them, infinities, a NaN among saturated lanes -- against the
     reference's chain evaluated literally in numpy float32: forces and yaw torque bit for bit, both action modes."""

@@ -8,7 +8,7 @@
  *   square root:                s = approx;  one ulp below / above tested with fma residuals          vs   sqrtf
  *
  *   saturation fast path:       raw action <= DN_ACT_SAT_LO -> (F_LO, TQ_LO),  >= DN_ACT_SAT_HI -> (F_HI, TQ_HI)
- *                               (csrc/dn_action_sat.h, rotor_force_sat in csrc/dn_kernels.hip)                 vs   the literal chain
+ *                               (csrc/dn_action_sat.h, rotor_force_sat in csrc/dn_action_chain.h)              vs   the literal chain
  *   for EVERY float32 action (all 2^32 bit patterns but the NaNs), with and without rescale_action.
  *
  * Usage: check_action_chain_exact [stride]   (stride 1 = exhaustive, default; larger = subsample for quick runs)
