@@ -24,6 +24,7 @@
 #include "dn_action_chain.h"    // A1-A3: the float32 action chain and its constants (KF32 ... A_HIGH32)
 #include "dn_philox.h"          // philox4x32, the two Box-Muller forms, noise4
 #include "dn_policy_draw.h"     // clipv, gaussian_draw, tanh_squash, squashed_draw
+#include "dn_role_place.h"      // which wave of a five-wave tile runs which role, from the SIMDs the waves landed on
 
 #ifndef DN_TU
 #define DN_TU 1      // see dn_launch_step_many: 1 = this file as such, 2 = through dn_kernels_mw.hip
@@ -3178,6 +3179,25 @@ __device__ long long g_mw_edge[16][8];    // per role: cycles at entry, after ba
 #else
 #define MW_EDGE(k) do { } while (0)
 #endif
+// Placement census (-DDN_PLACE_CENSUS; never shipped): every wave of every workgroup of a five-wave launch leaves its HW_ID and XCC_ID
+// (read-only s_getreg; one plain store from lane 0), read back through dn_debug_place (profiles/placement_census.py).
+#ifdef DN_PLACE_CENSUS
+#define DN_CENSUS_TILES 1024
+__device__ unsigned g_place[DN_CENSUS_TILES][8][2];
+#define MW_CENSUS(wave) do { if (NW == 5 && lane == 0 && blockIdx.x < DN_CENSUS_TILES) { \
+        g_place[blockIdx.x][wave][0] = __builtin_amdgcn_s_getreg(63492);     /* HW_REG_HW_ID, all 32 bits */ \
+        g_place[blockIdx.x][wave][1] = __builtin_amdgcn_s_getreg(63508); } } while (0)  /* HW_REG_XCC_ID */
+#else
+#define MW_CENSUS(wave) do { } while (0)
+#endif
+// Sweep build (-DDN_5W_ROLE_SWEEP; never shipped): the role table and the static priorities of the five-wave kernel come from a device
+// buffer that dn_debug_role_sweep fills from the environment variable DN_5W_ROLE_SWEEP (profiles/sweep_5w_roles.py), so that one library
+// serves a whole sweep.  Value: the eight table rows ([second tile][doubled SIMD], five letters each) and the priorities of L A Q X N,
+// nine words joined by ','.
+#ifdef DN_5W_ROLE_SWEEP
+struct DnRoleSweep { DnRoleTable table; char prio[8]; };
+__device__ DnRoleSweep g_role_sweep;
+#endif
 
 template <typename R, bool NORM, bool NOISE, int NW>
 DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int k_steps)
@@ -3199,21 +3219,27 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
     // 4.47 us per step against 4.74; with the normaliser, which also lives on the report wave, 3.85 against 3.75)
     constexpr bool THRUST_ON_Q = !NOISE || NORM;
     const int wv0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    MW_CENSUS(wv0);
     const int second_tile = (int)((blockIdx.x / (unsigned)p.num_cus) & 1u);      // the workgroup that lands beside tile blockIdx.x - num_cus on its CU
     const int wv = (!NORM && second_tile) ? (wv0 ^ 2) : wv0;
-#ifndef DN_5W_ORDER_A
-#define DN_5W_ORDER_A "LQANX"
-#define DN_5W_ORDER_B "ANLQX"
-#endif
     int role;
-    if (NW == 5) {
-        // five waves land on four SIMDs as 0 1 2 3 0; the second tile of a CU (tiles 256 .. 511 beside 0 .. 255) takes another order, so
-        // that the heavy waves of the two tiles pair with light ones of the other: SIMD 0: L1 X1 A2 X2, 1: Q1 N2, 2: A1 L2, 3: N1 Q2.
-        // Swept at 32 768 drones (us per step): this order 1.43, X L A N Q | Q N A L X 1.45, the same order in both tiles 1.56-1.80
-        // (profiles/r03_notes.md); the four-wave kernel 1.76.
-        constexpr char oa[6] = DN_5W_ORDER_A, ob[6] = DN_5W_ORDER_B;
-        const char ch = second_tile ? ob[wv0] : oa[wv0];
-        role = ch == 'L' ? 0 : ch == 'A' ? 1 : ch == 'Q' ? 2 : ch == 'X' ? 3 : 4;
+    if constexpr (NW == 5) {
+        // five waves land on four SIMDs in the cyclic order 0 2 1 3 from a start that differs from CU to CU (waves 0 and 4 share the start
+        // SIMD), and the second tile of a CU (tiles 256 .. 511 beside 0 .. 255) starts one place further on (profiles/role_placement.md).
+        // Each wave publishes the SIMD it sits on, and dn_role_place.h gives the roles from the five ids: SIMD p: X1 N1 L2, p + 1:
+        // L1 A2 X2, p + 2: Q1 N2, p + 3: A1 Q2 -- swept over all pairs of orders at 32 768 drones (us per step): this one 1.22, round 3's
+        // L Q A N X | A N L Q X 1.27, the worst 2.22.  Roles only say which wave runs which function: no result depends on them.
+        __shared__ unsigned char s_simd[8];
+        if (lane == 0) s_simd[wv0] = (unsigned char)__builtin_amdgcn_s_getreg(2308);  // HW_REG_HW_ID bits [5:4]: the SIMD this wave sits on (read-only)
+        block_lds_barrier();
+        int simd[DN_ROLES];
+#pragma unroll
+        for (int w = 0; w < DN_ROLES; ++w) simd[w] = __builtin_amdgcn_readfirstlane(s_simd[w]);
+#ifdef DN_5W_ROLE_SWEEP
+        role = __builtin_amdgcn_readfirstlane(dn_place_role_with(g_role_sweep.table, simd, second_tile != 0, wv0));
+#else
+        role = __builtin_amdgcn_readfirstlane(dn_place_role(simd, second_tile != 0, wv0));
+#endif
     } else
         role = NORM ? (wv == 0 ? 0 : (wv == 1 ? 3 : (wv == 2 ? 1 : 2)))            // L X A Q
                     : (wv == 0 ? 0 : (wv == 1 ? 1 : (wv == 2 ? 3 : 2)));           // L A X Q
@@ -3236,7 +3262,11 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
 #define DN_5W_PRIO "22311"               // s_setprio of the roles L A Q X N: Q, the role every barrier waits for, first (round 6: 33200 -> 22311 is 3 % of the step)
 #endif
     {
+#ifdef DN_5W_ROLE_SWEEP
+        const char *pr = g_role_sweep.prio;
+#else
         constexpr char pr[6] = DN_5W_PRIO;
+#endif
         switch (pr[role] - '0') {                                          // s_setprio takes an immediate
         case 1: __builtin_amdgcn_s_setprio(1); break;
         case 2: __builtin_amdgcn_s_setprio(2); break;
@@ -4368,6 +4398,9 @@ template <bool NORM> void launch_1w_2w(const StepLaunch &L, bool two_wave)
 }  // namespace
 
 #if DN_TU == 2
+#ifdef DN_5W_ROLE_SWEEP
+extern "C" int dn_debug_role_sweep();
+#endif
 hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, bool f32, int waves, hipStream_t stream)
 {
     const StepLaunch L(p, io, k, f32, stream);
@@ -4375,11 +4408,15 @@ hipError_t dn_launch_step_many_mw(const DnParams &p, const DnStepIO &io, int k, 
         dn_bools([&](auto F32) {
             DN_KLAUNCH((dn_step_many_rp8_kernel<real_t<decltype(F32)>>), L.grid, dim3(8 * DN_BLOCK), 0, stream, p, io, k);
         }, f32);
-    else if (waves == 5 && k > 1)       // four waves + the normaliser's: fused launches of the plain configuration, normaliser on
+    else if (waves == 5 && k > 1) {     // four waves + the normaliser's: fused launches of the plain configuration, normaliser on
+#ifdef DN_5W_ROLE_SWEEP
+        static const int sweep_filled = dn_debug_role_sweep();              // once, before the first launch (never under a stream capture)
+        if (sweep_filled != 0) return hipErrorInvalidValue;
+#endif
         dn_bools([&](auto F32, auto NOISE) {
             DN_KLAUNCH((dn_step_many_5w_kernel<real_t<decltype(F32)>, NOISE>), L.grid, dim3(5 * DN_BLOCK), 0, stream, p, io, k);
         }, f32, L.noise);
-    else if (waves == 4 && k > 1)       // four waves per tile: fused launches of the plain configuration (the caller checked)
+    } else if (waves == 4 && k > 1)     // four waves per tile: fused launches of the plain configuration (the caller checked)
         dn_bools([&](auto F32, auto NORM, auto NOISE) {
             DN_KLAUNCH((dn_step_many_4w_kernel<real_t<decltype(F32)>, NORM, NOISE>), L.grid, dim3(4 * DN_BLOCK), 0, stream, p, io, k);
         }, f32, L.norm, L.noise);
@@ -4400,6 +4437,42 @@ extern "C" int dn_debug_mw_stamps(long long *out)
 {
     if (hipDeviceSynchronize() != hipSuccess) return 1;
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mw_stamp), sizeof(long long) * 8 * 48 * 2) == hipSuccess ? 0 : 1;
+}
+#endif
+#ifdef DN_PLACE_CENSUS
+extern "C" int dn_debug_place(unsigned *out)        // DN_CENSUS_TILES x 8 waves x {HW_ID, XCC_ID} of the last five-wave launch
+{
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_place), sizeof(unsigned) * DN_CENSUS_TILES * 8 * 2) == hipSuccess ? 0 : 1;
+}
+#endif
+#ifdef DN_5W_ROLE_SWEEP
+// Reads DN_5W_ROLE_SWEEP (see g_role_sweep) into the device buffer: the launcher calls it before its first five-wave launch, the sweep
+// script after every change of the variable.  A malformed value is refused (1) and leaves the buffer as it was.
+extern "C" int dn_debug_role_sweep()
+{
+    const char *s = getenv("DN_5W_ROLE_SWEEP");
+    if (!s) s = "-----,-----,-----,-----,-----,-----,-----,-----," DN_5W_PRIO;
+    DnRoleSweep h = {};
+    for (int word = 0; word < 9; ++word) {
+        char *dst = word < 8 ? h.table.row[word / 4][word % 4] : h.prio;
+        for (int k = 0; k < 5; ++k) {
+            const char ch = s[word * 6 + k];
+            const bool ok = word < 8 ? (ch == 'L' || ch == 'A' || ch == 'Q' || ch == 'X' || ch == 'N' || ch == '-') : (ch >= '0' && ch <= '3');
+            if (!ok) return 1;
+            dst[k] = ch;
+        }
+        if (s[word * 6 + 5] != (word < 8 ? ',' : '\0')) return 1;
+    }
+    for (int word = 0; word < 8; ++word) {                  // a named row is a permutation of the five roles
+        const char *row = h.table.row[word / 4][word % 4];
+        if (row[0] == '-') continue;
+        unsigned seen = 0;
+        for (int k = 0; k < 5; ++k) seen |= row[k] == '-' ? 32u : 1u << dn_role_of_letter(row[k]);
+        if (seen != 31u) return 1;
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_role_sweep), &h, sizeof(h)) == hipSuccess ? 0 : 1;
 }
 #endif
 #elif DN_TU == 1
