@@ -12,7 +12,7 @@ MAX_WAYPOINTS = 64
 MAX_TRACKS = 64
 OBS_DIM = 13
 ACT_DIM = 4
-ABI_VERSION = 9
+ABI_VERSION = 10
 GROUND_CONTACT_AUTO = 2
 
 DN_OK = 0
@@ -51,7 +51,7 @@ class DnEnvState(C.Structure):
         ("ep_ret", C.c_float), ("ep_len", C.c_int32),
         ("rms_mean", C.c_double * OBS_DIM), ("rms_var", C.c_double * OBS_DIM), ("rms_count", C.c_double),
         ("rr_returns", C.c_double), ("rr_mean", C.c_double), ("rr_var", C.c_double), ("rr_count", C.c_double),
-        ("last_rpm", C.c_float * 4), ("pid", C.c_double * 9), ("ep_ret_lo", C.c_float),
+        ("last_rpm", C.c_float * 4), ("pid", C.c_double * 9), ("ep_ret_lo", C.c_float), ("rms_m2", C.c_double * OBS_DIM),
     ]
 
 

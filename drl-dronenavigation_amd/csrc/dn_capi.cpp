@@ -6,6 +6,7 @@
 #include "dn_argcheck.h"
 #include "dn_capi_fail.h"
 #include "dn_internal.h"
+#include "dn_second_moment.h"
 #include "dn_shapes.h"
 
 #include <cmath>
@@ -40,19 +41,6 @@ constexpr double DN_CONTACT_MARGIN = 0.02;          // Bullet's contact-breaking
 constexpr double DN_COLL_R = 0.06, DN_COLL_H = 0.025;   // base_link collision cylinder, cf2x.urdf:34
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// dn_set_state: the second moment the device carries for a given RunningMeanStd.var / .count -- the double m nearest to var x count
-// with m / count == var where one exists (so that dn_get_state of what was just set returns the var it was given, and a blob taken
-// with dn_get_state restores to statistics that read back identically).
-double second_moment(double var, double count)
-{
-    const double m = var * count;
-    if (!(count > 0.0) || !std::isfinite(m) || m / count == var) return m;
-    const double lo = std::nextafter(m, -HUGE_VAL), hi = std::nextafter(m, HUGE_VAL);
-    if (lo / count == var) return lo;
-    if (hi / count == var) return hi;
-    return m;
-}
 
 // An on / off environment switch read by dn_create: 1 / 0, or -1 for a value that is neither (the create then fails: a typo
 // must not silently select the other arithmetic).  Unset or empty = off.
@@ -883,7 +871,7 @@ int32_t dn_get_state(dn_env *env, dn_env_state *states, int64_t count)
         if (s.steps > 0) { s.cur_pos[0] = s.pos[0]; s.cur_pos[1] = s.pos[1]; s.cur_pos[2] = s.pos[2]; }
         else { s.cur_pos[0] = g[6][i].x; s.cur_pos[1] = g[6][i].y; s.cur_pos[2] = g[6][i].z; }
         if (env->cfg.normalize_obs) {
-            for (int k = 0; k < DN_OBS_DIM; ++k) { s.rms_mean[k] = mean[(size_t)k * n + i]; s.rms_var[k] = var[(size_t)k * n + i] / cnt[(size_t)i]; }      // the device holds the second moment var x count
+            for (int k = 0; k < DN_OBS_DIM; ++k) { s.rms_mean[k] = mean[(size_t)k * n + i]; s.rms_m2[k] = var[(size_t)k * n + i]; s.rms_var[k] = s.rms_m2[k] / cnt[(size_t)i]; }      // the device holds the second moment var x count: verbatim, and as var
             s.rms_count = cnt[(size_t)i];
         }
     }
@@ -942,8 +930,8 @@ int32_t dn_set_state(dn_env *env, const dn_env_state *states, int64_t count)
         g[5][i] = make_float4(s.prev_ang_v[0], s.prev_ang_v[1], s.prev_ang_v[2], flen);
         g[6][i] = make_float4(s.cur_pos[0], s.cur_pos[1], s.cur_pos[2], 0.0f);
         if (env->cfg.normalize_obs) {
-            if (!(s.rms_count > 0.0)) return fail(DN_ERR_INVALID_ARGUMENT, "state %lld: rms_count must be > 0 (RunningMeanStd starts at 1e-4)", i);
-            for (int k = 0; k < DN_OBS_DIM; ++k) { mean[(size_t)k * n + i] = s.rms_mean[k]; var[(size_t)k * n + i] = second_moment(s.rms_var[k], s.rms_count); }
+            if (!dn_rms_count_ok(s.rms_count)) return fail(DN_ERR_INVALID_ARGUMENT, "state %lld: rms_count must be > 0 and finite (RunningMeanStd starts at 1e-4)", i);
+            for (int k = 0; k < DN_OBS_DIM; ++k) { mean[(size_t)k * n + i] = s.rms_mean[k]; var[(size_t)k * n + i] = dn_restore_second_moment(s.rms_var[k], s.rms_count, s.rms_m2[k]); }
             cnt[(size_t)i] = s.rms_count;
         }
     }

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DN_ABI_VERSION 9
+#define DN_ABI_VERSION 10
 #define DN_MAX_WAYPOINTS 64
 #define DN_OBS_DIM 13      /* 12 kinematic + distance, PBDroneEnv._computeObs, PBDroneEnv.py:296-336 */
 #define DN_ACT_DIM 4       /* four rotor thrust commands, PBDroneEnv._actionSpace, PBDroneEnv.py:225-243 */
@@ -106,7 +106,10 @@ typedef struct dn_config {
  * dn_enable_dynamics: a checkpoint of a randomised fleet is dn_get_state + dn_get_dynamics (restore: dn_set_state + dn_set_dynamics),
  * nor the wind of dn_enable_wind (+ dn_get_wind / dn_set_wind), nor the actuator state of dn_enable_actuator (+ dn_get_actuator /
  * dn_set_actuator), nor the sensor state of dn_enable_sensor (+ dn_get_sensor / dn_set_sensor), nor the track of dn_enable_tracks
- * (+ dn_get_tracks; restore: dn_set_tracks BEFORE dn_set_state, which holds idx to the drone's own track). */
+ * (+ dn_get_tracks; restore: dn_set_tracks BEFORE dn_set_state, which holds idx to the drone's own track).
+ * A record written by dn_get_state and handed back to dn_set_state restores every device word bit for bit, the observation normaliser's
+ * included (rms_m2, ABI 10): a restored, resharded or set_attr-edited fleet continues with the bits of the uninterrupted one.  With
+ * normalize_obs dn_set_state refuses an rms_count that is not positive and finite. */
 typedef struct dn_env_state {
     float pos[3], quat[4], vel[3], ang_v[3];    /* Bullet base state, BaseAviary.py:596-598 (quat = x,y,z,w) */
     float prev_vel[3], prev_ang_v[3];           /* PBDroneEnv.prev_vel / prev_ang_v */
@@ -118,7 +121,7 @@ typedef struct dn_env_state {
     float ep_ret;                               /* Monitor: running episode return (high word, see ep_ret_lo) */
     int32_t ep_len;                             /* Monitor: running episode length */
     double rms_mean[DN_OBS_DIM];                /* normalize.RunningMeanStd.mean  (normalize_obs only) */
-    double rms_var[DN_OBS_DIM];                 /*                         .var  (the device carries the second moment var x count; these calls convert) */
+    double rms_var[DN_OBS_DIM];                 /*                         .var  (the device carries the second moment var x count: rms_m2 below) */
     double rms_count;                           /*                         .count                     */
     double rr_returns;                          /* NormalizeReward.returns (discounted return, norm_rew only)  */
     double rr_mean, rr_var, rr_count;           /* NormalizeReward.return_rms                                  */
@@ -127,6 +130,12 @@ typedef struct dn_env_state {
     float ep_ret_lo;                            /* Monitor: low part of the running return -- the return is ep_ret + ep_ret_lo, ep_ret_lo a multiple k/256
                                                    (k a signed byte) of ep_ret's ulp, so that the float64 sum SB3's Monitor keeps is not re-rounded to
                                                    24 bits every step; dn_set_state rounds what it is given to that grid */
+    double rms_m2[DN_OBS_DIM];                  /* the device's own words M2 = .var x .count (normalize_obs only; ABI 10, appended: no earlier offset moved).
+                                                   dn_get_state fills them verbatim beside rms_var = M2 / count.  dn_set_state takes rms_m2[k] as it is while
+                                                   rms_count > 0, rms_m2[k] is finite and rms_m2[k] / rms_count == rms_var[k] -- a blob then restores the
+                                                   statistics bit for bit, which rms_var alone cannot (neighbouring M2 divide to the same var) -- and
+                                                   otherwise rebuilds M2 from rms_var and rms_count: an edited var or count is honoured with rms_m2 left
+                                                   stale, and a producer that does not know the field leaves it zero */
 } dn_env_state;
 
 /* Wave-reduced episode statistics accumulated on the device since dn_create / dn_reset_stats. */

@@ -24,7 +24,7 @@ from oracle import oracle as O  # noqa: E402
 DT = 1.0 / 240.0
 WIDE = [-1e4, -1e4, -1e4, 1e4, 1e4, 1e4]
 STATE_KEYS = ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev", "idx", "steps", "just_found", "ep_ret",
-              "ep_len", "rms_mean", "rms_var", "rms_count", "last_rpm", "ep_ret_lo")
+              "ep_len", "rms_mean", "rms_var", "rms_count", "rms_m2", "last_rpm", "ep_ret_lo")
 BODY_KEYS = tuple(k for k in STATE_KEYS if not k.startswith("rms_"))       # the state outside the normaliser's statistics
 STATE_F32 = ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev")
 BODY = dict(mass=(0.7, 1.3), inertia=(0.7, 1.3), kf=(0.8, 1.2), km=(0.7, 1.3))

@@ -51,9 +51,9 @@ def test_struct_layouts_match_header(pkg):
 #include <stddef.h>
 #include "dronenav.h"
 int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(dn_config), sizeof(dn_env_state), sizeof(dn_stats), sizeof(dn_mlp_net),
+    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(dn_config), sizeof(dn_env_state), sizeof(dn_stats), sizeof(dn_mlp_net),
            offsetof(dn_config, random_spawn), offsetof(dn_config, seed), offsetof(dn_env_state, pid),
-           offsetof(dn_env_state, rms_mean), DN_ABI_VERSION);
+           offsetof(dn_env_state, rms_mean), offsetof(dn_env_state, ep_ret_lo), offsetof(dn_env_state, rms_m2), DN_ABI_VERSION);
     return 0;
 }
 '''
@@ -66,8 +66,14 @@ int main(void) {
     K = pkg._capi
     assert got == [C.sizeof(K.DnConfig), C.sizeof(K.DnEnvState), C.sizeof(K.DnStats), C.sizeof(K.DnMlpNet),
                    K.DnConfig.random_spawn.offset, K.DnConfig.seed.offset, K.DnEnvState.pid.offset,
-                   K.DnEnvState.rms_mean.offset, K.ABI_VERSION], got
-    assert pkg._capi.load().dn_abi_version() == pkg._capi.ABI_VERSION == 9
+                   K.DnEnvState.rms_mean.offset, K.DnEnvState.ep_ret_lo.offset, K.DnEnvState.rms_m2.offset, K.ABI_VERSION], got
+    # ABI 10 appended rms_m2 (the normaliser's second moment, verbatim) behind ep_ret_lo: every offset of ABI 9 stands, the struct grew by
+    # the field alone, and the numpy view of the blob (vec_env.STATE_DTYPE) places every field where ctypes does
+    assert (got[1], got[8], got[9]) == (568, 456, 464) and got[1] - got[9] == 13 * 8, got
+    from drl_dronenavigation_amd.vec_env import STATE_DTYPE
+    assert STATE_DTYPE.itemsize == got[1] and STATE_DTYPE.names == tuple(f[0] for f in K.DnEnvState._fields_)
+    assert all(STATE_DTYPE.fields[name][1] == getattr(K.DnEnvState, name).offset for name in STATE_DTYPE.names)
+    assert pkg._capi.load().dn_abi_version() == pkg._capi.ABI_VERSION == 10
 
 
 def test_config_defaults_follow_the_driver(pkg):

@@ -42,7 +42,7 @@ def test_the_names_are_declared_exported_and_bound(pkg):
         assert re.search(r"\b%s\s*\(" % name, code), name
         assert name in exported and name in pkg._capi.PROTOTYPES, name
     assert pkg.ClippedAdam is pkg.optim.ClippedAdam and "ClippedAdam" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 9
+    assert pkg._capi.load().dn_abi_version() == 10
     assert "dn_adam.hip" in pkg.build.SOURCES
 
 
@@ -69,7 +69,7 @@ int main(void) {
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
     tensor, config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
     assert tensor == [40, 0, 8, 16, 24, 32] and config == [40, 0, 8, 16, 24, 32, 36]
-    assert consts == [9, 32, A.CHUNK, 1] and A.MAX_TENSORS == 32
+    assert consts == [10, 32, A.CHUNK, 1] and A.MAX_TENSORS == 32
     T, K = pkg._capi.DnAdamTensor, pkg._capi.DnAdamConfig
     assert [C.sizeof(T), T.param.offset, T.grad.offset, T.exp_avg.offset, T.exp_avg_sq.offset, T.count.offset] == tensor
     assert [C.sizeof(K), K.beta1.offset, K.beta2.offset, K.eps.offset, K.max_grad_norm.offset, K.n_tensors.offset, K.flags.offset] == config

@@ -45,7 +45,7 @@ int main(void) {
     from drl_dronenavigation_amd import goal as M
     assert got == [C.sizeof(S), S.frame.offset, S.reserved.offset, pkg._capi.ABI_VERSION, M.GOAL_DIM, M.GOAL_FRAMES["world"],
                    M.GOAL_FRAMES["body"]], got
-    assert got == [8, 0, 4, 9, 8, 0, 1]                         # the layout the header documents; additive: the ABI version stays
+    assert got == [8, 0, 4, 10, 8, 0, 1]                         # the layout the header documents; additive: the ABI version stays
     assert G.GOAL_DIM == M.GOAL_DIM == pkg.GOAL_DIM
     named = sorted(c for s in M.GOAL_SLICES.values() for c in range(s.start, s.stop))
     assert named == list(range(8))                              # the named slices partition the row
@@ -53,7 +53,7 @@ int main(void) {
 
 def test_goal_symbols_are_in_header_exports_and_ctypes_table(pkg):
     lib = pkg._capi.load()
-    assert lib.dn_abi_version() == pkg._capi.ABI_VERSION == 9
+    assert lib.dn_abi_version() == pkg._capi.ABI_VERSION == 10
     P = pkg._capi.PROTOTYPES
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     cfg_p = C.POINTER(pkg._capi.DnGoalConfig)

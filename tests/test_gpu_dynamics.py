@@ -277,11 +277,14 @@ def test_sampling_fused_entry_points_refuse_and_the_collectors_fall_back():
 
 
 # ---- (g) round trip and checkpoint ------------------------------------------------------------------------------------
-def test_set_get_round_trip_and_checkpoint_continuation():
+# normalize_obs: the blob also carries the normaliser's statistics -- mean, count and, since ABI 10, the second moment itself (rms_m2) --
+# and _same_state compares them byte for byte
+@pytest.mark.parametrize("normalize_obs", [False, True], ids=["raw", "norm"])
+def test_set_get_round_trip_and_checkpoint_continuation(normalize_obs):
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
     n, K = 4096, 20
-    kw = dict(normalize_obs=False, max_steps=15, seed=9, device=DEV, dynamics=pkg.DynamicsRandomization(**RANGES))
+    kw = dict(normalize_obs=normalize_obs, max_steps=15, seed=9, device=DEV, dynamics=pkg.DynamicsRandomization(**RANGES))
     track = tracks.reaching()
     a = pkg.DroneVecEnv(track, n, **kw)
     a.reset_tensor()

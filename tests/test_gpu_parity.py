@@ -1221,7 +1221,8 @@ def test_reward_wrappers_match_oracle(clip, norm):
         assert np.array_equal(st["rr_count"], ora.envs["rr_count"]) and float(np.abs(st["rr_var"] - 1.0).min()) > 1e-3
         env.set_state(st)                                   # round trip through the host representation
         st2 = env.get_state()
-        assert np.array_equal(st2["rr_mean"], st["rr_mean"]) and np.array_equal(st2["rr_returns"], st["rr_returns"])
+        for k in ("rr_mean", "rr_returns", "rr_var", "rr_count"):          # all four words are stored verbatim
+            assert np.array_equal(st2[k], st[k]), k
     env.close()
 
 

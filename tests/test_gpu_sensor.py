@@ -308,11 +308,14 @@ def test_two_shards_equal_the_whole_fleet():
 
 
 # ---- 9. set / get, checkpoint -----------------------------------------------------------------------------------------------
-def test_set_get_round_trip_and_checkpoint_continuation():
+# normalize_obs: the blob also carries the normaliser's statistics -- mean, count and, since ABI 10, the second moment itself (rms_m2) --
+# and _same_state compares them byte for byte
+@pytest.mark.parametrize("normalize_obs", [False, True], ids=["raw", "norm"])
+def test_set_get_round_trip_and_checkpoint_continuation(normalize_obs):
     pkg = _pkg()
     from drl_dronenavigation_amd import tracks
     n, K = 2048, 20
-    kw = dict(normalize_obs=False, max_steps=15, seed=9, device=DEV, sensor=_model(pkg), actuator=pkg.ActuatorModel(**FULL),
+    kw = dict(normalize_obs=normalize_obs, max_steps=15, seed=9, device=DEV, sensor=_model(pkg), actuator=pkg.ActuatorModel(**FULL),
               dynamics=pkg.DynamicsRandomization(**BODY), wind=pkg.WindDisturbance(**GUSTY), **NOISE)
     track = tracks.reaching()
     a = pkg.DroneVecEnv(track, n, **kw)

@@ -302,18 +302,20 @@ def test_two_shards_equal_the_whole_fleet():
 
 
 # ---- checkpoint -----------------------------------------------------------------------------------------------------------------------
-def test_a_bank_fleet_round_trips_through_set_state_mid_flight():
+@pytest.mark.parametrize("normalize_obs", [False, True], ids=["raw", "norm"])
+def test_a_bank_fleet_round_trips_through_set_state_mid_flight(normalize_obs):
     """A checkpoint of a bank fleet is get_state + track_ids, restored as set_tracks THEN set_state (include/dronenav.h).  The bank here
     puts the one-waypoint track first, so that every drone on a longer track that passed a gate holds an idx >= W_0: dn_set_state holds
     idx to the drone's OWN track.  After 100 single steps with redraws the fleet is restored into a second env, and both fly 100 more
     steps bit for bit (outputs, goal rows, tracks, state).  In the other direction an idx inside a longer track's count but beyond the
-    drone's own is refused.  Normaliser, noise and the sensor are off, so that dn_set_state round trips exactly.
+    drone's own is refused.  Noise and the sensor are off; with the normaliser on the blob carries its second moment verbatim (rms_m2,
+    ABI 10), so dn_set_state round trips exactly either way (the flight does not depend on the normaliser: the figures below hold for both).
     Measured on one MI355X: at the checkpoint 179 of 191 drones hold an idx >= W_0 = 1 (the largest is 3), after 508 episode ends; 350
     more end after the restore."""
     pkg = _pkg()
     n, order = 191, [4, 3, 0, 5]                                  # bank track 0 = the one-waypoint track, 1 = up_circle, 2 = up, 3 = two waypoints
     Wb = S.W[order]
-    make = lambda: S.bank_env(pkg, n, which=order, resample=True, goal=pkg.GoalObservation("world"))      # noqa: E731
+    make = lambda: S.bank_env(pkg, n, which=order, resample=True, goal=pkg.GoalObservation("world"), normalize_obs=normalize_obs)      # noqa: E731
     acts = S.action_stream(n, 200)
     keys = ("obs", "reward", "done", "truncated", "found_targets", "terminal_obs", "ep_return", "ep_length", "goal", "terminal_goal", "track")
 

@@ -43,7 +43,7 @@ def test_the_names_are_declared_exported_and_bound(pkg):
         assert re.search(r"\b%s\s*\(" % name, code), name
         assert name in exported and name in pkg._capi.PROTOTYPES, name
     assert pkg.MinibatchSampler is pkg.minibatch.MinibatchSampler and "MinibatchSampler" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 9
+    assert pkg._capi.load().dn_abi_version() == 10
 
 
 def test_struct_layouts_compiled_from_the_header(pkg, tmp_path):
@@ -67,7 +67,7 @@ int main(void) {
         f.write(prog)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
     field, config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert field == [24, 0, 8, 16, 20] and config == [32, 0, 8, 16, 24, 28] and consts == [9, 8]
+    assert field == [24, 0, 8, 16, 20] and config == [32, 0, 8, 16, 24, 28] and consts == [10, 8]
     F, K = pkg._capi.DnMinibatchField, pkg._capi.DnMinibatchConfig
     assert [C.sizeof(F), F.src.offset, F.dst.offset, F.width.offset, F.normalize.offset] == field
     assert [C.sizeof(K), K.seed.offset, K.epoch.offset, K.epsilon.offset, K.num_fields.offset, K.reserved.offset] == config

@@ -42,7 +42,7 @@ def test_the_names_are_declared_exported_and_bound(pkg):
         assert re.search(r"\b%s\s*\(" % name, code), name
         assert name in exported and name in pkg._capi.PROTOTYPES, name
     assert pkg.PpoLoss is pkg.ppo.PpoLoss and "PpoLoss" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 9
+    assert pkg._capi.load().dn_abi_version() == 10
 
 
 def test_struct_layout_compiled_from_the_header(pkg, tmp_path):
@@ -65,7 +65,7 @@ int main(void) {
         f.write(prog)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
     config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert config == [40, 0, 8, 16, 24, 32, 36] and consts == [9, 8]
+    assert config == [40, 0, 8, 16, 24, 32, 36] and consts == [10, 8]
     K = pkg._capi.DnPpoLossConfig
     assert [C.sizeof(K), K.clip_range.offset, K.clip_range_vf.offset, K.ent_coef.offset, K.vf_coef.offset, K.act_dim.offset, K.reserved.offset] == config
     assert pkg._capi.PPO_MAX_ACT == 8

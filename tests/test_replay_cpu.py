@@ -44,7 +44,7 @@ def test_the_names_are_declared_exported_and_bound(pkg):
         assert re.search(r"\b%s\s*\(" % name, code), name
         assert name in exported and name in pkg._capi.PROTOTYPES, name
     assert pkg.ReplaySampler is pkg.replay.ReplaySampler and "ReplaySampler" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 9
+    assert pkg._capi.load().dn_abi_version() == 10
     build = pkg.build
     assert "dn_replay.hip" in build.SOURCES and "dn_replay_draw.h" in build.HEADERS
 
@@ -63,7 +63,7 @@ def test_struct_layouts_compiled_from_the_header(pkg, tmp_path):
         f.write(prog)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), path, "-o", exe])
     config, source, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert config == [64, 0, 8, 16, 24, 32, 40, 48, 52, 56, 60] and source == [48, 0, 8, 16, 24, 32, 40] and consts == [9, 0, 1, 64, 8]
+    assert config == [64, 0, 8, 16, 24, 32, 40, 48, 52, 56, 60] and source == [48, 0, 8, 16, 24, 32, 40] and consts == [10, 0, 1, 64, 8]
     K, S = pkg._capi.DnReplayConfig, pkg._capi.DnReplaySource
     assert [C.sizeof(K)] + [getattr(K, f).offset for f in cfg] == config
     assert [C.sizeof(S)] + [getattr(S, f).offset for f in src] == source

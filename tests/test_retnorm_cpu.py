@@ -43,7 +43,7 @@ def test_the_three_names_are_declared_exported_and_bound(pkg):
     assert "normalize.py:10-47" in text and text.count("normalize.py:") >= 4        # every entry point cites the reference
     assert "[from recall]" in text
     assert pkg.ReturnNormalizer is pkg.retnorm.ReturnNormalizer and "ReturnNormalizer" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 9
+    assert pkg._capi.load().dn_abi_version() == 10
 
 
 def test_config_layout_compiled_from_the_header(pkg, tmp_path):
@@ -64,7 +64,7 @@ int main(void) {
         f.write(prog)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
     got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got == [24, 0, 8, 16, 20, 9], got
+    assert got == [24, 0, 8, 16, 20, 10], got
     K = pkg._capi.DnRetnormConfig
     assert [C.sizeof(K), K.gamma.offset, K.epsilon.offset, K.clip.offset, K.reserved.offset] == got[:5]
 

@@ -42,7 +42,7 @@ def test_the_five_names_are_declared_exported_and_bound(pkg):
     assert C.sizeof(K.DnRownormConfig) == 16
     assert (K.DnRownormConfig.width.offset, K.DnRownormConfig.clip.offset, K.DnRownormConfig.epsilon.offset) == (0, 4, 8)
     assert pkg.RowNormalizer is pkg.rownorm.RowNormalizer and "RowNormalizer" in pkg.__all__
-    assert K.load().dn_abi_version() == 9
+    assert K.load().dn_abi_version() == 10
 
 
 def test_state_and_scratch_sizes(pkg):

@@ -50,7 +50,7 @@ def test_the_names_are_declared_exported_and_bound(pkg):
         assert getattr(pkg, name) is getattr(pkg.sac, name) and name in pkg.__all__
     assert pkg.SacCritic is pkg.policy.SacCritic and "SacCritic" in pkg.__all__
     assert "dn_sac_loss.hip" in pkg.build.SOURCES and "dn_sac_math.h" in pkg.build.HEADERS
-    assert pkg._capi.load().dn_abi_version() == 9
+    assert pkg._capi.load().dn_abi_version() == 10
 
 
 def test_struct_layout_compiled_from_the_header(pkg, tmp_path):
@@ -73,7 +73,7 @@ int main(void) {
         f.write(prog)
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
     config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert config == [56, 0, 8, 16, 24, 32, 40, 44, 48] and consts == [9, 8, 4]
+    assert config == [56, 0, 8, 16, 24, 32, 40, 44, 48] and consts == [10, 8, 4]
     K = pkg._capi.DnSacConfig
     assert [C.sizeof(K)] + [getattr(K, n).offset for n in ("gamma", "target_entropy", "ent_coef", "log_std_min", "log_std_max", "act_dim", "n_critics",
                                                            "reserved")] == config

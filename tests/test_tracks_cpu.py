@@ -76,7 +76,7 @@ int main(void) {
     K = _capi.DnTrackBankConfig
     assert got == [C.sizeof(K), K.num_waypoints.offset, K.waypoints.offset, K.weight.offset, K.resample.offset, K.reserved.offset,
                    _capi.MAX_TRACKS, _capi.ABI_VERSION], got
-    assert got == [2064, 4, 264, 1800, 2056, 2060, 64, 9]         # the layout line of the header's comment
+    assert got == [2064, 4, 264, 1800, 2056, 2060, 64, 10]         # the layout line of the header's comment
 
 
 def test_cdf_and_draw_on_hand_cases():
