@@ -1010,13 +1010,8 @@ class DroneVecEnv(_VecEnvBase):
         _capi.check(self._lib.dn_set_step_count(self._handle, int(value)))
 
 
-STATE_DTYPE = np.dtype([
-    ("pos", "f4", 3), ("quat", "f4", 4), ("vel", "f4", 3), ("ang_v", "f4", 3), ("prev_vel", "f4", 3),
-    ("prev_ang_v", "f4", 3), ("cur_pos", "f4", 3), ("d", "f4"), ("d_prev", "f4"), ("idx", "i4"), ("steps", "i4"),
-    ("just_found", "i4"), ("ep_ret", "f4"), ("ep_len", "i4"), ("rms_mean", "f8", OBS_DIM), ("rms_var", "f8", OBS_DIM),
-    ("rms_count", "f8"), ("rr_returns", "f8"), ("rr_mean", "f8"), ("rr_var", "f8"), ("rr_count", "f8"),
-    ("last_rpm", "f4", 4), ("pid", "f8", 9), ("ep_ret_lo", "f4"), ("rms_m2", "f8", OBS_DIM)], align=True)
-assert STATE_DTYPE.itemsize == C.sizeof(_capi.DnEnvState), (STATE_DTYPE.itemsize, C.sizeof(_capi.DnEnvState))
+# the numpy view of the state blob is the ctypes record of dn_env_state: same names, offsets, element types and item size
+STATE_DTYPE = np.dtype(_capi.DnEnvState)
 
 
 def _states_to_numpy(arr, n):

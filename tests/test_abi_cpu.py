@@ -4,10 +4,11 @@ imports the oracle.  No compute calls (there is no GPU here)."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import abi_support as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "drl-dronenavigation_amd")
@@ -20,60 +21,79 @@ def pkg():
     return p
 
 
-def header_symbols():
-    src = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(dn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_library_exports_every_declared_symbol(pkg):
     lib = pkg._capi.load()
-    syms = header_symbols()
+    syms = abi.header_symbols()
     assert len(syms) >= 18
     for s in syms:
         assert hasattr(lib, s), f"libdronenav.so does not export {s}"
-    assert set(syms) == set(pkg._capi.PROTOTYPES), "ctypes prototypes and the header disagree"
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    assert exported == set(syms), exported ^ set(syms)
+    assert syms == set(pkg._capi.PROTOTYPES), "ctypes prototypes and the header disagree"
+    exported = abi.exported(pkg._capi.library_path())
+    assert exported == syms, exported ^ syms
+    abi.check_names(*syms)
+    assert abi.header_arity() == {name: len(args) for name, (_, args) in pkg._capi.PROTOTYPES.items()}
+
+
+def test_every_mirror_matches_the_header_field_by_field(pkg):
+    """Every ctypes.Structure of _capi.py against the header struct its name derives: size, and every field's offset and size."""
+    got, mirrors = abi.compiled(), abi.mirrors()
+    assert len(mirrors) >= 22 and sum(len(c._fields_) for c in mirrors.values()) >= 164       # the structs and fields of ABI 10
+    assert set(mirrors) == set(got.sizes) == set(got.fields)
+    for cls in mirrors.values():
+        abi.check_layout(cls, C.sizeof(cls))
+
+
+def test_every_header_struct_has_a_mirror(pkg):
+    structs = abi.header_structs()
+    assert "dn_config" in structs and "dn_env" not in structs and len(structs) >= 22
+    assert structs == set(abi.mirrors()), structs ^ set(abi.mirrors())
+
+
+MIRRORED_CONSTANTS = {"MAX_WAYPOINTS", "MAX_TRACKS", "OBS_DIM", "ACT_DIM", "ABI_VERSION", "GROUND_CONTACT_AUTO", "MINIBATCH_MAX_FIELDS", "PPO_MAX_ACT",
+                      "ADAM_MAX_TENSORS", "ADAM_ZERO_GRADS", "REPLAY_PLAIN", "REPLAY_RING", "REPLAY_MAX_OBS", "REPLAY_MAX_ACT", "SAC_MAX_ACT",
+                      "SAC_MAX_CRITICS"}
+
+
+def test_every_mirrored_constant_and_status_agrees(pkg):
+    K, got = pkg._capi, abi.compiled()
+    mirrored = {name[3:]: value for name, value in got.constants.items() if hasattr(K, name[3:])}
+    assert set(mirrored) == MIRRORED_CONSTANTS, set(mirrored) ^ MIRRORED_CONSTANTS
+    for name, value in mirrored.items():
+        assert getattr(K, name) == value, name
+    assert len(got.status) == 6 and {v: k for k, v in got.status.items()} == K.STATUS_NAMES
+    abi.check_version()
 
 
 def test_struct_layouts_match_header(pkg):
-    # sizes computed by hand from include/dronenav.h (natural alignment) ...
-    assert C.sizeof(pkg._capi.DnConfig) == 8 + 4 + 4 + 64 * 3 * 8 + 3 * 8 + 6 * 8 + 8 + 8 * 4 + 2 * 4 + 8 + 8 + 4 * 4 + 2 * 4   # ... + random_spawn + zero_damping
-    assert C.sizeof(pkg._capi.DnStats) == 7 * 8
-    # ... and by the C compiler from the header itself: sizes and the offsets of the trailing fields
-    import subprocess
-    import tempfile
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(dn_config), sizeof(dn_env_state), sizeof(dn_stats), sizeof(dn_mlp_net),
-           offsetof(dn_config, random_spawn), offsetof(dn_config, seed), offsetof(dn_env_state, pid),
-           offsetof(dn_env_state, rms_mean), offsetof(dn_env_state, ep_ret_lo), offsetof(dn_env_state, rms_m2), DN_ABI_VERSION);
-    return 0;
-}
-'''
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "abi.c"), os.path.join(td, "abi")
-        with open(src, "w") as f:
-            f.write(prog)
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), src, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
     K = pkg._capi
-    assert got == [C.sizeof(K.DnConfig), C.sizeof(K.DnEnvState), C.sizeof(K.DnStats), C.sizeof(K.DnMlpNet),
-                   K.DnConfig.random_spawn.offset, K.DnConfig.seed.offset, K.DnEnvState.pid.offset,
-                   K.DnEnvState.rms_mean.offset, K.DnEnvState.ep_ret_lo.offset, K.DnEnvState.rms_m2.offset, K.ABI_VERSION], got
+    # sizes computed by hand from include/dronenav.h (natural alignment) ...
+    # ... and by the C compiler from the header itself: sizes and the offsets of the trailing fields
+    abi.check_layout(K.DnConfig, 8 + 4 + 4 + 64 * 3 * 8 + 3 * 8 + 6 * 8 + 8 + 8 * 4 + 2 * 4 + 8 + 8 + 4 * 4 + 2 * 4,   # ... + random_spawn + zero_damping
+                     seed=1672, random_spawn=1704)
+    abi.check_layout(K.DnStats, 7 * 8)
+    abi.check_layout(K.DnMlpNet, 9 * 8 + 4 * 4)
     # ABI 10 appended rms_m2 (the normaliser's second moment, verbatim) behind ep_ret_lo: every offset of ABI 9 stands, the struct grew by
-    # the field alone, and the numpy view of the blob (vec_env.STATE_DTYPE) places every field where ctypes does
-    assert (got[1], got[8], got[9]) == (568, 456, 464) and got[1] - got[9] == 13 * 8, got
+    # the field alone
+    abi.check_layout(K.DnEnvState, 568, rms_mean=120, pid=384, ep_ret_lo=456, rms_m2=464)
+    assert 568 - 464 == 13 * 8
+    abi.check_version()
+
+
+def test_state_dtype_is_the_compiled_record(pkg):
+    """vec_env.STATE_DTYPE, the numpy view of the state blob, against the compiled dn_env_state: names in order, offsets, item size and
+    every field's size; and the element formats, which the compiler's numbers do not tell."""
     from drl_dronenavigation_amd.vec_env import STATE_DTYPE
-    assert STATE_DTYPE.itemsize == got[1] and STATE_DTYPE.names == tuple(f[0] for f in K.DnEnvState._fields_)
-    assert all(STATE_DTYPE.fields[name][1] == getattr(K.DnEnvState, name).offset for name in STATE_DTYPE.names)
-    assert pkg._capi.load().dn_abi_version() == pkg._capi.ABI_VERSION == 10
+    got = abi.compiled()
+    state = got.fields["dn_env_state"]
+    assert STATE_DTYPE.names == tuple(state) and STATE_DTYPE.itemsize == got.sizes["dn_env_state"] == 568
+    assert {n: (STATE_DTYPE.fields[n][1], STATE_DTYPE.fields[n][0].itemsize) for n in STATE_DTYPE.names} == state
+    f4 = ("pos", "quat", "vel", "ang_v", "prev_vel", "prev_ang_v", "cur_pos", "d", "d_prev", "ep_ret", "last_rpm", "ep_ret_lo")
+    i4 = ("idx", "steps", "just_found", "ep_len")
+    f8 = ("rms_mean", "rms_var", "rms_count", "rr_returns", "rr_mean", "rr_var", "rr_count", "pid", "rms_m2")
+    assert set(f4 + i4 + f8) == set(STATE_DTYPE.names)
+    for names, base in ((f4, "<f4"), (i4, "<i4"), (f8, "<f8")):
+        for n in names:
+            assert STATE_DTYPE.fields[n][0].base == np.dtype(base), n
 
 
 def test_config_defaults_follow_the_driver(pkg):

@@ -2,14 +2,12 @@
 symbols, and the host-side validation of ActuatorModel."""
 import ctypes as C
 import dataclasses
-import os
-import subprocess
-import tempfile
 
 import pytest
 
+import abi_support as abi
+
 NEW_SYMBOLS = ("dn_enable_actuator", "dn_set_actuator", "dn_get_actuator", "dn_get_actuator_config")
-FIELDS = ("latency", "motor_tau", "fill", "resample", "reserved")
 
 
 @pytest.fixture(scope="module")
@@ -19,39 +17,16 @@ def pkg():
 
 
 def test_actuator_config_layout_matches_header(pkg):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    offs = ", ".join(f"offsetof(dn_actuator_config, {f})" for f in FIELDS)
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %d %d %zu %zu\n", sizeof(dn_actuator_config), ''' + offs + r''', DN_ABI_VERSION, DN_MAX_LATENCY,
-           sizeof(dn_config), sizeof(dn_env_state));
-    return 0;
-}
-'''
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "act.c"), os.path.join(td, "act")
-        with open(src, "w") as f:
-            f.write(prog)
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), src, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    A = pkg._capi.DnActuatorConfig
     from drl_dronenavigation_amd import actuator
-    assert got == [C.sizeof(A)] + [getattr(A, f).offset for f in FIELDS] + [pkg._capi.ABI_VERSION, actuator.MAX_LATENCY,
-                                                                           C.sizeof(pkg._capi.DnConfig), C.sizeof(pkg._capi.DnEnvState)], got
-    assert C.sizeof(A) == 40 and pkg._capi.ABI_VERSION == 10 and actuator.MAX_LATENCY == 8      # additive: the ABI version stays
+    abi.check_layout(pkg._capi.DnActuatorConfig, 40)
+    abi.check_layout(pkg._capi.DnConfig, C.sizeof(pkg._capi.DnConfig))
+    abi.check_layout(pkg._capi.DnEnvState, C.sizeof(pkg._capi.DnEnvState))
+    assert abi.compiled().constants["DN_MAX_LATENCY"] == actuator.MAX_LATENCY == 8
+    abi.check_version()
 
 
 def test_actuator_symbols_are_exported_and_bound(pkg):
-    lib = pkg._capi.load()
-    for name in NEW_SYMBOLS:
-        assert name in pkg._capi.PROTOTYPES, name
-        assert getattr(lib, name).argtypes == pkg._capi.PROTOTYPES[name][1], name
-    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg._capi.library_path()]).decode()
-    for name in NEW_SYMBOLS:
-        assert f" T {name}\n" in out, name
+    abi.check_names(*NEW_SYMBOLS)
 
 
 NAN, INF = float("nan"), float("inf")

@@ -5,18 +5,16 @@ reference of tests/adam_support.py against an independent statement: torch's own
 tensors."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+import abi_support as abi  # noqa: E402
 import adam_support as A  # noqa: E402
 
-ROOT = A.ROOT
 NAMES = ("dn_adam_scratch_bytes", "dn_adam_step")
 INVALID = -1
 
@@ -29,51 +27,27 @@ def pkg():
 
 
 def test_the_names_are_declared_exported_and_bound(pkg):
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    code = abi.header_text()
     assert re.search(r"#define DN_ADAM_MAX_TENSORS 32\b", code) and re.search(r"#define DN_ADAM_CHUNK \d+\b", code)
     assert re.search(r"typedef struct dn_adam_tensor \{\s*float \*param;\s*float \*grad;\s*float \*exp_avg;\s*float \*exp_avg_sq;\s*"
                      r"int64_t count;\s*\} dn_adam_tensor;", code)
     assert re.search(r"typedef struct dn_adam_config \{\s*double beta1, beta2;\s*double eps;\s*double max_grad_norm;\s*int32_t n_tensors;\s*"
                      r"int32_t flags;\s*\} dn_adam_config;", code)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    abi.check_names(*NAMES)
     assert pkg.ClippedAdam is pkg.optim.ClippedAdam and "ClippedAdam" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 10
+    abi.check_version()
     assert "dn_adam.hip" in pkg.build.SOURCES
 
 
-def test_struct_layouts_compiled_from_the_header(pkg, tmp_path):
+def test_struct_layouts_compiled_from_the_header(pkg):
     """dn_adam_tensor: 40 bytes, param 0, grad 8, exp_avg 16, exp_avg_sq 24, count 32.  dn_adam_config: 40 bytes, beta1 0, beta2 8, eps 16,
     max_grad_norm 24, n_tensors 32, flags 36 -- by the C compiler from the header itself, and the ctypes mirrors agree."""
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu\n", sizeof(dn_adam_tensor), offsetof(dn_adam_tensor, param), offsetof(dn_adam_tensor, grad),
-           offsetof(dn_adam_tensor, exp_avg), offsetof(dn_adam_tensor, exp_avg_sq), offsetof(dn_adam_tensor, count));
-    printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(dn_adam_config), offsetof(dn_adam_config, beta1), offsetof(dn_adam_config, beta2),
-           offsetof(dn_adam_config, eps), offsetof(dn_adam_config, max_grad_norm), offsetof(dn_adam_config, n_tensors),
-           offsetof(dn_adam_config, flags));
-    printf("%d %d %d %d\n", DN_ABI_VERSION, DN_ADAM_MAX_TENSORS, DN_ADAM_CHUNK, DN_ADAM_ZERO_GRADS);
-    return 0;
-}
-'''
-    src, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
-    with open(src, "w") as f:
-        f.write(prog)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    tensor, config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert tensor == [40, 0, 8, 16, 24, 32] and config == [40, 0, 8, 16, 24, 32, 36]
-    assert consts == [10, 32, A.CHUNK, 1] and A.MAX_TENSORS == 32
-    T, K = pkg._capi.DnAdamTensor, pkg._capi.DnAdamConfig
-    assert [C.sizeof(T), T.param.offset, T.grad.offset, T.exp_avg.offset, T.exp_avg_sq.offset, T.count.offset] == tensor
-    assert [C.sizeof(K), K.beta1.offset, K.beta2.offset, K.eps.offset, K.max_grad_norm.offset, K.n_tensors.offset, K.flags.offset] == config
+    abi.check_layout(pkg._capi.DnAdamTensor, 40, param=0, grad=8, exp_avg=16, exp_avg_sq=24, count=32)
+    abi.check_layout(pkg._capi.DnAdamConfig, 40, beta1=0, beta2=8, eps=16, max_grad_norm=24, n_tensors=32, flags=36)
+    consts = abi.compiled().constants
+    assert [consts["DN_ADAM_MAX_TENSORS"], consts["DN_ADAM_CHUNK"], consts["DN_ADAM_ZERO_GRADS"]] == [32, A.CHUNK, 1] and A.MAX_TENSORS == 32
     assert pkg._capi.ADAM_MAX_TENSORS == 32 and pkg._capi.ADAM_ZERO_GRADS == 1
+    abi.check_version()
 
 
 def _scratch_bytes(lib, counts):

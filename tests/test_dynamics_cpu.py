@@ -1,11 +1,9 @@
 """Dynamics randomisation (include/dronenav.h dn_enable_dynamics) without a GPU: the C struct against its ctypes twin, the exported
 symbols, and the host-side validation of DynamicsRandomization."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import pytest
+
+import abi_support as abi
 
 NEW_SYMBOLS = ("dn_enable_dynamics", "dn_set_dynamics", "dn_get_dynamics", "dn_get_dynamics_config")
 
@@ -17,38 +15,12 @@ def pkg():
 
 
 def test_dynamics_config_layout_matches_header(pkg):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(dn_dynamics_config), offsetof(dn_dynamics_config, mass),
-           offsetof(dn_dynamics_config, inertia), offsetof(dn_dynamics_config, kf), offsetof(dn_dynamics_config, km),
-           offsetof(dn_dynamics_config, resample), offsetof(dn_dynamics_config, reserved), DN_ABI_VERSION);
-    return 0;
-}
-'''
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "dyn.c"), os.path.join(td, "dyn")
-        with open(src, "w") as f:
-            f.write(prog)
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), src, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    D = pkg._capi.DnDynamicsConfig
-    assert got == [C.sizeof(D), D.mass.offset, D.inertia.offset, D.kf.offset, D.km.offset, D.resample.offset, D.reserved.offset,
-                   pkg._capi.ABI_VERSION], got
-    assert C.sizeof(D) == 40 and pkg._capi.ABI_VERSION == 10            # additive: the ABI version stays
+    abi.check_layout(pkg._capi.DnDynamicsConfig, 40)
+    abi.check_version()
 
 
 def test_dynamics_symbols_are_exported_and_bound(pkg):
-    lib = pkg._capi.load()
-    for name in NEW_SYMBOLS:
-        assert name in pkg._capi.PROTOTYPES, name
-        assert getattr(lib, name).argtypes == pkg._capi.PROTOTYPES[name][1], name
-    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg._capi.library_path()]).decode()
-    for name in NEW_SYMBOLS:
-        assert f" T {name}\n" in out, name
+    abi.check_names(*NEW_SYMBOLS)
 
 
 @pytest.mark.parametrize("bad", [dict(mass=(1.2, 0.8)), dict(inertia=(0.0, 1.0)), dict(kf=(-0.5, 1.0)), dict(km=(float("nan"), 1.0)),

@@ -4,13 +4,11 @@ tests/goal_support.py against hand-worked rows."""
 import ctypes as C
 import dataclasses
 import math
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import abi_support as abi
 import goal_support as G
 
 NEW_SYMBOLS = ("dn_enable_goal", "dn_get_goal_config", "dn_bind_goal")
@@ -24,28 +22,12 @@ def pkg():
 
 
 def test_goal_config_layout_and_constants_match_header(pkg):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %d %d %d %d\n", sizeof(dn_goal_config), offsetof(dn_goal_config, frame), offsetof(dn_goal_config, reserved),
-           DN_ABI_VERSION, DN_GOAL_DIM, DN_GOAL_FRAME_WORLD, DN_GOAL_FRAME_BODY);
-    return 0;
-}
-'''
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "goal.c"), os.path.join(td, "goal")
-        with open(src, "w") as f:
-            f.write(prog)
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), src, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    S = pkg._capi.DnGoalConfig
     from drl_dronenavigation_amd import goal as M
-    assert got == [C.sizeof(S), S.frame.offset, S.reserved.offset, pkg._capi.ABI_VERSION, M.GOAL_DIM, M.GOAL_FRAMES["world"],
-                   M.GOAL_FRAMES["body"]], got
-    assert got == [8, 0, 4, 10, 8, 0, 1]                         # the layout the header documents; additive: the ABI version stays
+    abi.check_layout(pkg._capi.DnGoalConfig, 8, frame=0, reserved=4)                 # the layout the header documents
+    consts = abi.compiled().constants
+    assert (consts["DN_GOAL_DIM"], consts["DN_GOAL_FRAME_WORLD"], consts["DN_GOAL_FRAME_BODY"]) == (M.GOAL_DIM, M.GOAL_FRAMES["world"],
+                                                                                                  M.GOAL_FRAMES["body"]) == (8, 0, 1)
+    abi.check_version()
     assert G.GOAL_DIM == M.GOAL_DIM == pkg.GOAL_DIM
     named = sorted(c for s in M.GOAL_SLICES.values() for c in range(s.start, s.stop))
     assert named == list(range(8))                              # the named slices partition the row
@@ -53,21 +35,18 @@ int main(void) {
 
 def test_goal_symbols_are_in_header_exports_and_ctypes_table(pkg):
     lib = pkg._capi.load()
-    assert lib.dn_abi_version() == pkg._capi.ABI_VERSION == 10
+    abi.check_version()
     P = pkg._capi.PROTOTYPES
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     cfg_p = C.POINTER(pkg._capi.DnGoalConfig)
     want = {"dn_enable_goal": (i32, [vp, cfg_p]), "dn_get_goal_config": (i32, [vp, cfg_p]), "dn_bind_goal": (i32, [vp, vp, vp, i64])}
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "dronenav.h")).read()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg._capi.library_path()]).decode()
+    abi.check_names(*NEW_SYMBOLS)
     for name in NEW_SYMBOLS:
-        assert f"int32_t {name}(" in header, name
+        assert f"int32_t {name}(" in abi.header_text(), name
         assert name in P, name
         assert (P[name][0], list(P[name][1])) == want[name], name
         fn = getattr(lib, name)
         assert fn.restype == want[name][0] and list(fn.argtypes) == want[name][1], name
-        assert f" T {name}\n" in out, name
 
 
 @pytest.mark.parametrize("bad", ["", "World", "inertial", 0, 1, None, ("world",), b"body"])

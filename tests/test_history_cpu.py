@@ -2,16 +2,14 @@
 case, HistoryObservation's validation and width rule, the refusals of the C ABI (dn_stack_history validates before its first device call),
 the exported symbols, the inline width rule as a stand-alone host program, and the collectors' refusals."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+import abi_support as abi
 import history_support as H
 import host_program_support
-from host_program_support import ROOT
 
 INVALID = -1
 P = C.c_void_p(0x1000)           # a non-null, 16-byte aligned pointer that is never followed
@@ -125,14 +123,11 @@ def test_width_agrees_with_the_c_abi_over_the_grid(pkg):
 
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
 def test_history_symbols_and_layout(pkg):
-    lib = pkg._capi.load()
-    assert lib.dn_abi_version() == pkg._capi.ABI_VERSION == 10         # additive: the ABI version stays
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg._capi.library_path()]).decode()
+    abi.check_version()
+    abi.check_names("dn_history_width", "dn_stack_history")
     for name in ("dn_history_width", "dn_stack_history"):
-        assert f"int32_t {name}(" in header and name in pkg._capi.PROTOTYPES and f" T {name}\n" in out, name
-    S = pkg._capi.DnHistoryConfig
-    assert (C.sizeof(S), S.frames.offset, S.actions.offset, S.extra_dim.offset, S.reserved.offset) == (16, 0, 4, 8, 12)
+        assert f"int32_t {name}(" in abi.header_text(), name
+    abi.check_layout(pkg._capi.DnHistoryConfig, 16, frames=0, actions=4, extra_dim=8, reserved=12)
 
 
 def _call(lib, cfg, k=1, n=64, prev=P, obs=P, actions=P, done=P, terminal_obs=P, extra=None, terminal_extra=None, rows=P,

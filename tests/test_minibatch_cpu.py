@@ -5,19 +5,17 @@ plainly and under the address and undefined-behaviour sanitizers; every refusal 
 call, so the pointers here are never followed; the Python surface's own refusals; and the reference normalisation against itself."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+import abi_support as abi  # noqa: E402
 import host_program_support  # noqa: E402
 import minibatch_support as M  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dn_minibatch_scratch_bytes", "dn_minibatch_permutation", "dn_minibatch")
 INVALID = -1
 
@@ -30,48 +28,24 @@ def pkg():
 
 
 def test_the_names_are_declared_exported_and_bound(pkg):
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    code = abi.header_text()
     assert re.search(r"#define DN_MINIBATCH_MAX_FIELDS 8\b", code)
     assert re.search(r"typedef struct dn_minibatch_field \{\s*const void \*src;\s*void \*dst;\s*int32_t width;\s*int32_t normalize;\s*\} "
                      r"dn_minibatch_field;", code)
     assert re.search(r"typedef struct dn_minibatch_config \{\s*uint64_t seed;\s*uint64_t epoch;\s*double epsilon;\s*int32_t num_fields;\s*"
                      r"int32_t reserved;\s*\} dn_minibatch_config;", code)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    abi.check_names(*NAMES)
     assert pkg.MinibatchSampler is pkg.minibatch.MinibatchSampler and "MinibatchSampler" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 10
+    abi.check_version()
 
 
-def test_struct_layouts_compiled_from_the_header(pkg, tmp_path):
+def test_struct_layouts_compiled_from_the_header(pkg):
     """dn_minibatch_field: 24 bytes, src 0, dst 8, width 16, normalize 20; dn_minibatch_config: 32 bytes, seed 0, epoch 8, epsilon 16,
     num_fields 24, reserved 28 -- by the C compiler from the header itself, and the ctypes mirrors agree."""
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu\n", sizeof(dn_minibatch_field), offsetof(dn_minibatch_field, src), offsetof(dn_minibatch_field, dst),
-           offsetof(dn_minibatch_field, width), offsetof(dn_minibatch_field, normalize));
-    printf("%zu %zu %zu %zu %zu %zu\n", sizeof(dn_minibatch_config), offsetof(dn_minibatch_config, seed), offsetof(dn_minibatch_config, epoch),
-           offsetof(dn_minibatch_config, epsilon), offsetof(dn_minibatch_config, num_fields), offsetof(dn_minibatch_config, reserved));
-    printf("%d %d\n", DN_ABI_VERSION, DN_MINIBATCH_MAX_FIELDS);
-    return 0;
-}
-'''
-    src, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
-    with open(src, "w") as f:
-        f.write(prog)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    field, config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert field == [24, 0, 8, 16, 20] and config == [32, 0, 8, 16, 24, 28] and consts == [10, 8]
-    F, K = pkg._capi.DnMinibatchField, pkg._capi.DnMinibatchConfig
-    assert [C.sizeof(F), F.src.offset, F.dst.offset, F.width.offset, F.normalize.offset] == field
-    assert [C.sizeof(K), K.seed.offset, K.epoch.offset, K.epsilon.offset, K.num_fields.offset, K.reserved.offset] == config
-    assert pkg._capi.MINIBATCH_MAX_FIELDS == 8
+    abi.check_layout(pkg._capi.DnMinibatchField, 24, src=0, dst=8, width=16, normalize=20)
+    abi.check_layout(pkg._capi.DnMinibatchConfig, 32, seed=0, epoch=8, epsilon=16, num_fields=24, reserved=28)
+    assert abi.compiled().constants["DN_MINIBATCH_MAX_FIELDS"] == pkg._capi.MINIBATCH_MAX_FIELDS == 8
+    abi.check_version()
 
 
 def test_scratch_sizes(pkg):

@@ -6,19 +6,17 @@ program, plainly and under the address and undefined-behaviour sanitizers; the r
 of every clamp, and its stability under the order of the rows."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+import abi_support as abi  # noqa: E402
 import host_program_support  # noqa: E402
 import ppo_loss_support as P  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dn_ppo_loss_scratch_bytes", "dn_ppo_loss")
 INVALID = -1
 
@@ -31,44 +29,21 @@ def pkg():
 
 
 def test_the_names_are_declared_exported_and_bound(pkg):
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    code = abi.header_text()
     assert re.search(r"#define DN_PPO_MAX_ACT 8\b", code)
     assert re.search(r"typedef struct dn_ppo_loss_config \{\s*double clip_range;\s*double clip_range_vf;\s*double ent_coef;\s*double vf_coef;\s*"
                      r"int32_t act_dim;\s*int32_t reserved;\s*\} dn_ppo_loss_config;", code)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    abi.check_names(*NAMES)
     assert pkg.PpoLoss is pkg.ppo.PpoLoss and "PpoLoss" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 10
+    abi.check_version()
 
 
-def test_struct_layout_compiled_from_the_header(pkg, tmp_path):
+def test_struct_layout_compiled_from_the_header(pkg):
     """dn_ppo_loss_config: 40 bytes, clip_range 0, clip_range_vf 8, ent_coef 16, vf_coef 24, act_dim 32, reserved 36 -- by the C compiler
     from the header itself, and the ctypes mirror agrees."""
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(dn_ppo_loss_config), offsetof(dn_ppo_loss_config, clip_range),
-           offsetof(dn_ppo_loss_config, clip_range_vf), offsetof(dn_ppo_loss_config, ent_coef), offsetof(dn_ppo_loss_config, vf_coef),
-           offsetof(dn_ppo_loss_config, act_dim), offsetof(dn_ppo_loss_config, reserved));
-    printf("%d %d\n", DN_ABI_VERSION, DN_PPO_MAX_ACT);
-    return 0;
-}
-'''
-    src, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
-    with open(src, "w") as f:
-        f.write(prog)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert config == [40, 0, 8, 16, 24, 32, 36] and consts == [10, 8]
-    K = pkg._capi.DnPpoLossConfig
-    assert [C.sizeof(K), K.clip_range.offset, K.clip_range_vf.offset, K.ent_coef.offset, K.vf_coef.offset, K.act_dim.offset, K.reserved.offset] == config
-    assert pkg._capi.PPO_MAX_ACT == 8
+    abi.check_layout(pkg._capi.DnPpoLossConfig, 40, clip_range=0, clip_range_vf=8, ent_coef=16, vf_coef=24, act_dim=32, reserved=36)
+    assert abi.compiled().constants["DN_PPO_MAX_ACT"] == pkg._capi.PPO_MAX_ACT == 8
+    abi.check_version()
 
 
 def test_scratch_sizes(pkg):

@@ -4,19 +4,17 @@ real library against the NumPy statement of tests/replay_support.py and its know
 under the address and undefined-behaviour sanitizers; its uniformity; every refusal of dn_replay_sample, which validates before its first
 device call, so the pointers here are never followed, and of dn_replay_indices; the Python surface's own refusals."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+import abi_support as abi  # noqa: E402
 import host_program_support  # noqa: E402
 import replay_support as R  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dn_replay_indices", "dn_replay_sample")
 INVALID = -1
 
@@ -30,45 +28,31 @@ def pkg():
 
 # ---- names and layouts ----------------------------------------------------------------------------------------------------------------
 def test_the_names_are_declared_exported_and_bound(pkg):
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    code = abi.header_text()
     for define in ("DN_REPLAY_PLAIN 0", "DN_REPLAY_RING 1", "DN_REPLAY_MAX_OBS 64", "DN_REPLAY_MAX_ACT 8"):
         assert re.search(r"#define %s\b" % define, code), define
     assert re.search(r"typedef struct dn_replay_config \{\s*uint64_t seed;\s*uint64_t draw;\s*int64_t buffer_size;\s*int64_t n_envs;\s*int64_t valid;\s*"
                      r"int64_t skip;\s*int32_t obs_dim;\s*int32_t act_dim;\s*int32_t layout;\s*int32_t reserved;\s*\} dn_replay_config;", code)
     assert re.search(r"typedef struct dn_replay_source \{\s*const void \*obs;\s*const void \*next_obs;\s*const void \*actions;\s*const void \*rewards;\s*"
                      r"const void \*dones;\s*const void \*timeouts;\s*\} dn_replay_source;", code)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    abi.check_names(*NAMES)
     assert pkg.ReplaySampler is pkg.replay.ReplaySampler and "ReplaySampler" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 10
+    abi.check_version()
     build = pkg.build
     assert "dn_replay.hip" in build.SOURCES and "dn_replay_draw.h" in build.HEADERS
 
 
-def test_struct_layouts_compiled_from_the_header(pkg, tmp_path):
+def test_struct_layouts_compiled_from_the_header(pkg):
     """dn_replay_config: 64 bytes, seed 0, draw 8, buffer_size 16, n_envs 24, valid 32, skip 40, obs_dim 48, act_dim 52, layout 56, reserved
     60; dn_replay_source: 48 bytes, six pointers -- by the C compiler from the header itself, and the ctypes mirrors agree."""
-    cfg = ("seed", "draw", "buffer_size", "n_envs", "valid", "skip", "obs_dim", "act_dim", "layout", "reserved")
-    src = ("obs", "next_obs", "actions", "rewards", "dones", "timeouts")
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"dronenav.h\"\nint main(void) {\n"
-    prog += '    printf("%zu", sizeof(dn_replay_config));\n' + "".join(f'    printf(" %zu", offsetof(dn_replay_config, {f}));\n' for f in cfg)
-    prog += '    printf("\\n%zu", sizeof(dn_replay_source));\n' + "".join(f'    printf(" %zu", offsetof(dn_replay_source, {f}));\n' for f in src)
-    prog += '    printf("\\n%d %d %d %d %d\\n", DN_ABI_VERSION, DN_REPLAY_PLAIN, DN_REPLAY_RING, DN_REPLAY_MAX_OBS, DN_REPLAY_MAX_ACT);\n    return 0;\n}\n'
-    path, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
-    with open(path, "w") as f:
-        f.write(prog)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), path, "-o", exe])
-    config, source, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert config == [64, 0, 8, 16, 24, 32, 40, 48, 52, 56, 60] and source == [48, 0, 8, 16, 24, 32, 40] and consts == [10, 0, 1, 64, 8]
-    K, S = pkg._capi.DnReplayConfig, pkg._capi.DnReplaySource
-    assert [C.sizeof(K)] + [getattr(K, f).offset for f in cfg] == config
-    assert [C.sizeof(S)] + [getattr(S, f).offset for f in src] == source
-    assert (pkg._capi.REPLAY_PLAIN, pkg._capi.REPLAY_RING, pkg._capi.REPLAY_MAX_OBS, pkg._capi.REPLAY_MAX_ACT) == (0, 1, 64, 8)
+    K = pkg._capi
+    abi.check_layout(K.DnReplayConfig, 64, seed=0, draw=8, buffer_size=16, n_envs=24, valid=32, skip=40, obs_dim=48, act_dim=52, layout=56, reserved=60)
+    abi.check_layout(K.DnReplaySource, 48, obs=0, next_obs=8, actions=16, rewards=24, dones=32, timeouts=40)
+    consts = abi.compiled().constants
+    assert [consts["DN_REPLAY_" + k] for k in ("PLAIN", "RING", "MAX_OBS", "MAX_ACT")] == [0, 1, 64, 8]
+    assert (K.REPLAY_PLAIN, K.REPLAY_RING, K.REPLAY_MAX_OBS, K.REPLAY_MAX_ACT) == (0, 1, 64, 8)
     assert (R.PLAIN, R.RING) == (0, 1)
+    abi.check_version()
 
 
 # ---- dn_replay_indices ------------------------------------------------------------------------------------------------------------------

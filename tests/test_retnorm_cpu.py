@@ -5,9 +5,7 @@ the reference against itself; and the scratch-size rule as a stand-alone host pr
 undefined-behaviour sanitizers."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +13,9 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import retnorm_support as R  # noqa: E402
+import abi_support as abi  # noqa: E402
 import host_program_support  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dn_retnorm_scratch_bytes", "dn_retnorm_init", "dn_retnorm")
 INVALID = -1
 
@@ -30,43 +28,22 @@ def pkg():
 
 
 def test_the_three_names_are_declared_exported_and_bound(pkg):
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    header, code = abi.header_text(comments=True), abi.header_text()
     assert re.search(r"typedef struct dn_retnorm_config \{\s*double gamma;\s*double epsilon;\s*float clip;\s*int32_t reserved;\s*\} "
                      r"dn_retnorm_config;", code)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    abi.check_names(*NAMES)
     text = header[header.index("A fleet-wide running return normaliser"):]
     assert "normalize.py:10-47" in text and text.count("normalize.py:") >= 4        # every entry point cites the reference
     assert "[from recall]" in text
     assert pkg.ReturnNormalizer is pkg.retnorm.ReturnNormalizer and "ReturnNormalizer" in pkg.__all__
-    assert pkg._capi.load().dn_abi_version() == 10
+    abi.check_version()
 
 
-def test_config_layout_compiled_from_the_header(pkg, tmp_path):
+def test_config_layout_compiled_from_the_header(pkg):
     """sizeof(dn_retnorm_config) = 24 with gamma at 0, epsilon at 8, clip at 16 and reserved at 20: by the C compiler from the header
     itself, and the ctypes mirror agrees."""
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %d\n", sizeof(dn_retnorm_config), offsetof(dn_retnorm_config, gamma), offsetof(dn_retnorm_config, epsilon),
-           offsetof(dn_retnorm_config, clip), offsetof(dn_retnorm_config, reserved), DN_ABI_VERSION);
-    return 0;
-}
-'''
-    src, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
-    with open(src, "w") as f:
-        f.write(prog)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got == [24, 0, 8, 16, 20, 10], got
-    K = pkg._capi.DnRetnormConfig
-    assert [C.sizeof(K), K.gamma.offset, K.epsilon.offset, K.clip.offset, K.reserved.offset] == got[:5]
+    abi.check_layout(pkg._capi.DnRetnormConfig, 24, gamma=0, epsilon=8, clip=16, reserved=20)
+    abi.check_version()
 
 
 def test_scratch_sizes(pkg):

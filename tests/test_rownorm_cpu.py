@@ -4,9 +4,7 @@ call, so the pointers here are never followed; the Python surface's own refusals
 program, plainly and under the address and undefined-behaviour sanitizers."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,9 +12,9 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import rownorm_support as R  # noqa: E402
+import abi_support as abi  # noqa: E402
 import host_program_support  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dn_rownorm_config", "dn_rownorm_state_doubles", "dn_rownorm_scratch_bytes", "dn_rownorm_init", "dn_rownorm")
 INVALID = -1
 
@@ -29,20 +27,13 @@ def pkg():
 
 
 def test_the_five_names_are_declared_exported_and_bound(pkg):
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    header, code = abi.header_text(comments=True), abi.header_text()
     assert re.search(r"typedef struct dn_rownorm_config \{\s*int32_t width;\s*float clip;\s*double epsilon;\s*\} dn_rownorm_config;", code)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    for name in NAMES[1:]:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    abi.check_names(*NAMES[1:])
     assert "normalize.py:10-47" in header and header.count("normalize.py:") >= 5        # every entry point cites the reference
-    K = pkg._capi
-    assert C.sizeof(K.DnRownormConfig) == 16
-    assert (K.DnRownormConfig.width.offset, K.DnRownormConfig.clip.offset, K.DnRownormConfig.epsilon.offset) == (0, 4, 8)
+    abi.check_layout(pkg._capi.DnRownormConfig, 16, width=0, clip=4, epsilon=8)
     assert pkg.RowNormalizer is pkg.rownorm.RowNormalizer and "RowNormalizer" in pkg.__all__
-    assert K.load().dn_abi_version() == 10
+    abi.check_version()
 
 
 def test_state_and_scratch_sizes(pkg):

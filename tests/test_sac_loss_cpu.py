@@ -11,19 +11,17 @@ composition from SacActor.squash 0.13 of the bound (8.9e-12)."""
 import ctypes as C
 import decimal
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+import abi_support as abi  # noqa: E402
 import host_program_support  # noqa: E402
 import sac_loss_support as S  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dn_sac_loss_scratch_bytes", "dn_sac_policy", "dn_sac_policy_backward", "dn_sac_critic_loss", "dn_sac_actor_loss")
 INVALID = -1
 
@@ -36,48 +34,26 @@ def pkg():
 
 
 def test_the_names_are_declared_exported_and_bound(pkg):
-    header = open(os.path.join(ROOT, "include", "dronenav.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    code = abi.header_text()
     assert re.search(r"#define DN_SAC_MAX_ACT 8\b", code) and re.search(r"#define DN_SAC_MAX_CRITICS 4\b", code)
     assert re.search(r"typedef struct dn_sac_config \{\s*double gamma;\s*double target_entropy;\s*double ent_coef;\s*double log_std_min;\s*"
                      r"double log_std_max;\s*int32_t act_dim;\s*int32_t n_critics;\s*int64_t reserved;\s*\} dn_sac_config;", code)
-    out = subprocess.run(["nm", "-D", "--defined-only", pkg._capi.library_path()], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (dn_[a-z_0-9]+)", out))
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in exported and name in pkg._capi.PROTOTYPES, name
+    abi.check_names(*NAMES)
     for name in ("SacPolicyHead", "SacCriticLoss", "SacActorLoss"):
         assert getattr(pkg, name) is getattr(pkg.sac, name) and name in pkg.__all__
     assert pkg.SacCritic is pkg.policy.SacCritic and "SacCritic" in pkg.__all__
     assert "dn_sac_loss.hip" in pkg.build.SOURCES and "dn_sac_math.h" in pkg.build.HEADERS
-    assert pkg._capi.load().dn_abi_version() == 10
+    abi.check_version()
 
 
-def test_struct_layout_compiled_from_the_header(pkg, tmp_path):
+def test_struct_layout_compiled_from_the_header(pkg):
     """dn_sac_config: 56 bytes, gamma 0, target_entropy 8, ent_coef 16, log_std_min 24, log_std_max 32, act_dim 40, n_critics 44, reserved
     48 -- by the C compiler from the header itself, and the ctypes mirror agrees."""
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(dn_sac_config), offsetof(dn_sac_config, gamma), offsetof(dn_sac_config, target_entropy),
-           offsetof(dn_sac_config, ent_coef), offsetof(dn_sac_config, log_std_min), offsetof(dn_sac_config, log_std_max),
-           offsetof(dn_sac_config, act_dim), offsetof(dn_sac_config, n_critics), offsetof(dn_sac_config, reserved));
-    printf("%d %d %d\n", DN_ABI_VERSION, DN_SAC_MAX_ACT, DN_SAC_MAX_CRITICS);
-    return 0;
-}
-'''
-    src, exe = str(tmp_path / "abi.c"), str(tmp_path / "abi")
-    with open(src, "w") as f:
-        f.write(prog)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    config, consts = ([int(v) for v in line.split()] for line in subprocess.check_output([exe], text=True).splitlines())
-    assert config == [56, 0, 8, 16, 24, 32, 40, 44, 48] and consts == [10, 8, 4]
-    K = pkg._capi.DnSacConfig
-    assert [C.sizeof(K)] + [getattr(K, n).offset for n in ("gamma", "target_entropy", "ent_coef", "log_std_min", "log_std_max", "act_dim", "n_critics",
-                                                           "reserved")] == config
-    assert pkg._capi.SAC_MAX_ACT == 8 and pkg._capi.SAC_MAX_CRITICS == 4
+    abi.check_layout(pkg._capi.DnSacConfig, 56, gamma=0, target_entropy=8, ent_coef=16, log_std_min=24, log_std_max=32, act_dim=40, n_critics=44,
+                     reserved=48)
+    consts = abi.compiled().constants
+    assert (consts["DN_SAC_MAX_ACT"], consts["DN_SAC_MAX_CRITICS"]) == (pkg._capi.SAC_MAX_ACT, pkg._capi.SAC_MAX_CRITICS) == (8, 4)
+    abi.check_version()
 
 
 def test_scratch_sizes(pkg):

@@ -1,15 +1,12 @@
 """The track bank (include/dronenav.h dn_enable_tracks) without a GPU: what TrackBank refuses on the CPU, the configuration it hands the
 C ABI, the struct's layout against the header, and the cdf / draw statement on hand cases."""
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_support as abi
 from drl_dronenavigation_amd import Track, TrackBank, _capi, tracks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_trackbank_refuses_what_the_library_refuses():
@@ -56,27 +53,10 @@ def test_to_c_concatenates_the_tracks_and_round_trips():
     assert all(np.array_equal(a.waypoints, b.waypoints) for a, b in zip(back.tracks, bank.tracks))
 
 
-def test_struct_layout_matches_the_header(tmp_path):
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %d %d\n", sizeof(dn_track_bank_config), offsetof(dn_track_bank_config, num_waypoints),
-           offsetof(dn_track_bank_config, waypoints), offsetof(dn_track_bank_config, weight), offsetof(dn_track_bank_config, resample),
-           offsetof(dn_track_bank_config, reserved), DN_MAX_TRACKS, DN_ABI_VERSION);
-    return 0;
-}
-'''
-    src, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    with open(src, "w") as f:
-        f.write(prog)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    got = [int(v) for v in subprocess.check_output([exe]).split()]
-    K = _capi.DnTrackBankConfig
-    assert got == [C.sizeof(K), K.num_waypoints.offset, K.waypoints.offset, K.weight.offset, K.resample.offset, K.reserved.offset,
-                   _capi.MAX_TRACKS, _capi.ABI_VERSION], got
-    assert got == [2064, 4, 264, 1800, 2056, 2060, 64, 10]         # the layout line of the header's comment
+def test_struct_layout_matches_the_header():
+    abi.check_layout(_capi.DnTrackBankConfig, 2064, num_waypoints=4, waypoints=264, weight=1800, resample=2056, reserved=2060)   # the layout line of the header's comment
+    assert abi.compiled().constants["DN_MAX_TRACKS"] == _capi.MAX_TRACKS == 64
+    abi.check_version()
 
 
 def test_cdf_and_draw_on_hand_cases():

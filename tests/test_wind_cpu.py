@@ -1,16 +1,13 @@
 """Per-drone wind (include/dronenav.h dn_enable_wind) without a GPU: the C struct against its ctypes twin, the exported symbols, and the
 host-side validation of WindDisturbance."""
-import ctypes as C
 import dataclasses
 import math
-import os
-import subprocess
-import tempfile
 
 import pytest
 
+import abi_support as abi
+
 NEW_SYMBOLS = ("dn_enable_wind", "dn_set_wind", "dn_get_wind", "dn_get_wind_config")
-FIELDS = ("speed", "azimuth", "vertical", "gust_sigma", "gust_tau", "coeff", "resample", "reserved")
 
 
 @pytest.fixture(scope="module")
@@ -20,36 +17,12 @@ def pkg():
 
 
 def test_wind_config_layout_matches_header(pkg):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    offs = ", ".join(f"offsetof(dn_wind_config, {f})" for f in FIELDS)
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "dronenav.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(dn_wind_config), ''' + offs + r''', DN_ABI_VERSION);
-    return 0;
-}
-'''
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "wind.c"), os.path.join(td, "wind")
-        with open(src, "w") as f:
-            f.write(prog)
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), src, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    W = pkg._capi.DnWindConfig
-    assert got == [C.sizeof(W)] + [getattr(W, f).offset for f in FIELDS] + [pkg._capi.ABI_VERSION], got
-    assert C.sizeof(W) == 52 and pkg._capi.ABI_VERSION == 10            # additive: the ABI version stays
+    abi.check_layout(pkg._capi.DnWindConfig, 52)
+    abi.check_version()
 
 
 def test_wind_symbols_are_exported_and_bound(pkg):
-    lib = pkg._capi.load()
-    for name in NEW_SYMBOLS:
-        assert name in pkg._capi.PROTOTYPES, name
-        assert getattr(lib, name).argtypes == pkg._capi.PROTOTYPES[name][1], name
-    out = subprocess.check_output(["nm", "-D", "--defined-only", pkg._capi.library_path()]).decode()
-    for name in NEW_SYMBOLS:
-        assert f" T {name}\n" in out, name
+    abi.check_names(*NEW_SYMBOLS)
 
 
 NAN, INF = float("nan"), float("inf")
