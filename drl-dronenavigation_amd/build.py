@@ -90,5 +90,37 @@ def build_library(force=False, verbose=False):
     return LIB_PATH
 
 
+def build_variant(dst_dir, tag, defines, sources=("dn_kernels_mw.hip",)):
+    """A library of the same ABI with `sources` compiled under extra `defines` (e.g. ["-DDN_5W_ROLE_SWEEP"]: the sweep build of the
+    five-wave step): dst_dir/libdronenav_<tag>.so.  Every other translation unit is the default build's object, which is brought up to
+    date first; an object that is not there is compiled into dst_dir with the default build's flags.  Nothing of the default build
+    changes, and nothing calls this but the test or script that wants the variant (load it through DN_LIB_PATH)."""
+    unknown = [s for s in sources if s not in SOURCES]
+    if unknown:
+        raise ValueError(f"not translation units of the library: {unknown}")
+    build_library()
+    os.makedirs(dst_dir, exist_ok=True)
+    objs, cmds = [], []
+    for src in SOURCES:
+        stem = os.path.splitext(src)[0]
+        base = [hipcc()] + FLAGS + FLAGS_OF.get(src, NO_LICM) + EXTRA
+        obj = os.path.join(CSRC, stem + ".o")
+        if src in sources:
+            obj = os.path.join(dst_dir, f"{stem}.{tag}.o")
+            cmds.append(base + list(defines) + ["-c", os.path.join(CSRC, src), "-o", obj])
+        elif not os.path.exists(obj):
+            obj = os.path.join(dst_dir, stem + ".o")
+            cmds.append(base + ["-c", os.path.join(CSRC, src), "-o", obj])
+        objs.append(obj)
+    procs = [subprocess.Popen(c) for c in cmds]
+    codes = [p.wait() for p in procs]
+    for c, rc in zip(cmds, codes):
+        if rc != 0:
+            raise subprocess.CalledProcessError(rc, c)
+    lib = os.path.join(dst_dir, f"libdronenav_{tag}.so")
+    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
+    return lib
+
+
 if __name__ == "__main__":
     print(build_library(force=True, verbose=True))

@@ -3193,10 +3193,16 @@ __device__ unsigned g_place[DN_CENSUS_TILES][8][2];
 // Sweep build (-DDN_5W_ROLE_SWEEP; never shipped): the role table and the static priorities of the five-wave kernel come from a device
 // buffer that dn_debug_role_sweep fills from the environment variable DN_5W_ROLE_SWEEP (profiles/sweep_5w_roles.py), so that one library
 // serves a whole sweep.  Value: the eight table rows ([second tile][doubled SIMD], five letters each) and the priorities of L A Q X N,
-// nine words joined by ','.
+// nine words joined by ','; or eleven words, with the two fallback orders (first tile, second tile; DN_ROLE_ORDER in the nine-word form)
+// between the rows and the priorities.  Eight rows "-----" and the orders (pi, sigma) make wave w of a first tile run pi[w] and of a
+// second tile sigma[w] whatever the placement: tests/test_gpu_role_sweep.py holds every such assignment to the bits of one wave.
 #ifdef DN_5W_ROLE_SWEEP
-struct DnRoleSweep { DnRoleTable table; char prio[8]; };
+struct DnRoleSweep { DnRoleTable table; char order[2][6]; char prio[8]; };
 __device__ DnRoleSweep g_role_sweep;
+// What the variant came to: the role every wave of the first DN_SWEEP_TILES workgroups took in the last five-wave launch (one plain store
+// from lane 0), read back through dn_debug_role_seen -- so a test that forces an assignment can see that it was the one that ran.
+#define DN_SWEEP_TILES 1024
+__device__ unsigned char g_role_seen[DN_SWEEP_TILES][8];
 #endif
 
 template <typename R, bool NORM, bool NOISE, int NW>
@@ -3236,7 +3242,8 @@ DN_DEV void step_many_4w_body(const DnParams &p, const DnStepIO &io0, const int 
 #pragma unroll
         for (int w = 0; w < DN_ROLES; ++w) simd[w] = __builtin_amdgcn_readfirstlane(s_simd[w]);
 #ifdef DN_5W_ROLE_SWEEP
-        role = __builtin_amdgcn_readfirstlane(dn_place_role_with(g_role_sweep.table, simd, second_tile != 0, wv0));
+        role = __builtin_amdgcn_readfirstlane(dn_place_role_with(g_role_sweep.table, g_role_sweep.order, simd, second_tile != 0, wv0));
+        if (lane == 0 && blockIdx.x < DN_SWEEP_TILES) g_role_seen[blockIdx.x][wv0] = (unsigned char)role;
 #else
         role = __builtin_amdgcn_readfirstlane(dn_place_role(simd, second_tile != 0, wv0));
 #endif
@@ -4448,24 +4455,31 @@ extern "C" int dn_debug_place(unsigned *out)        // DN_CENSUS_TILES x 8 waves
 #endif
 #ifdef DN_5W_ROLE_SWEEP
 // Reads DN_5W_ROLE_SWEEP (see g_role_sweep) into the device buffer: the launcher calls it before its first five-wave launch, the sweep
-// script after every change of the variable.  A malformed value is refused (1) and leaves the buffer as it was.
+// script and the role tests after every change of the variable.  A malformed value is refused (1) and leaves the buffer as it was.
 extern "C" int dn_debug_role_sweep()
 {
     const char *s = getenv("DN_5W_ROLE_SWEEP");
     if (!s) s = "-----,-----,-----,-----,-----,-----,-----,-----," DN_5W_PRIO;
     DnRoleSweep h = {};
-    for (int word = 0; word < 9; ++word) {
-        char *dst = word < 8 ? h.table.row[word / 4][word % 4] : h.prio;
+    for (int tile = 0; tile < 2; ++tile)
+        for (int k = 0; k < 6; ++k) h.order[tile][k] = DN_ROLE_ORDER[tile][k];
+    // words 0 .. 7: rows; then the priorities (nine words), or two orders and the priorities (eleven).  Read left to right and left at
+    // the first character that does not fit, the terminator included: nothing past the value's end is read.
+    int words = 11;
+    for (int word = 0; word < words; ++word) {
+        if (word == 8 && s[48] >= '0' && s[48] <= '3') words = 9;          // the nine-word form: a digit where an order would begin
+        const bool letters = word < words - 1;
+        char *dst = word < 8 ? h.table.row[word / 4][word % 4] : letters ? h.order[word - 8] : h.prio;
         for (int k = 0; k < 5; ++k) {
             const char ch = s[word * 6 + k];
-            const bool ok = word < 8 ? (ch == 'L' || ch == 'A' || ch == 'Q' || ch == 'X' || ch == 'N' || ch == '-') : (ch >= '0' && ch <= '3');
+            const bool ok = letters ? (ch == 'L' || ch == 'A' || ch == 'Q' || ch == 'X' || ch == 'N' || (ch == '-' && word < 8)) : (ch >= '0' && ch <= '3');
             if (!ok) return 1;
             dst[k] = ch;
         }
-        if (s[word * 6 + 5] != (word < 8 ? ',' : '\0')) return 1;
+        if (s[word * 6 + 5] != (letters ? ',' : '\0')) return 1;
     }
-    for (int word = 0; word < 8; ++word) {                  // a named row is a permutation of the five roles
-        const char *row = h.table.row[word / 4][word % 4];
+    for (int word = 0; word < 10; ++word) {                 // a named row is a permutation of the five roles, and so is an order
+        const char *row = word < 8 ? h.table.row[word / 4][word % 4] : h.order[word - 8];
         if (row[0] == '-') continue;
         unsigned seen = 0;
         for (int k = 0; k < 5; ++k) seen |= row[k] == '-' ? 32u : 1u << dn_role_of_letter(row[k]);
@@ -4473,6 +4487,11 @@ extern "C" int dn_debug_role_sweep()
     }
     if (hipDeviceSynchronize() != hipSuccess) return 1;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_role_sweep), &h, sizeof(h)) == hipSuccess ? 0 : 1;
+}
+extern "C" int dn_debug_role_seen(unsigned char *out)     // DN_SWEEP_TILES x 8 waves: the role numbers (dn_role_place.h) of the last five-wave launch
+{
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_role_seen), sizeof(unsigned char) * DN_SWEEP_TILES * 8) == hipSuccess ? 0 : 1;
 }
 #endif
 #elif DN_TU == 1

@@ -3,8 +3,9 @@
 // Standard C++ only (constexpr functions, which the device compiler takes as they are): the five-wave fused step calls
 // dn_place_role on the device, and tests/tools/check_role_place.cpp walks dn_place_roles over all 4^5 placements on the CPU.
 //
-// The step's results do not depend on the answer: a role only says which wave runs which function.  What depends on it is which
-// roles share a SIMD, i.e. the step time (profiles/role_placement.md).
+// The step's results do not depend on the answer: a role only says which wave runs which function (tests/test_gpu_role_sweep.py runs
+// the kernel under all 120 assignments a tile can get).  What depends on it is which roles share a SIMD, i.e. the step time
+// (profiles/role_placement.md).
 #ifndef DN_ROLE_PLACE_H
 #define DN_ROLE_PLACE_H
 
@@ -51,13 +52,21 @@ constexpr int dn_place_rank(const int simd[DN_ROLES], int w)
     return rank;
 }
 
-// The role of wave w under `table`.
-constexpr int dn_place_role_with(const DnRoleTable &table, const int simd[DN_ROLES], bool second_tile, int w)
+// The role of wave w under `table`, and under the wave-index orders `order` in every placement the table does not name.  With a table of
+// eight rows "-----" wave w runs order[tile][w] whatever the placement: how the sweep build of the kernel forces an assignment
+// (tests/test_gpu_role_sweep.py).
+constexpr int dn_place_role_with(const DnRoleTable &table, const char (&order)[2][6], const int simd[DN_ROLES], bool second_tile, int w)
 {
     const int pattern = dn_place_pattern(simd);
     if (pattern >= 0 && table.row[second_tile ? 1 : 0][pattern][0] != '-')
         return dn_role_of_letter(table.row[second_tile ? 1 : 0][pattern][dn_place_rank(simd, w)]);
-    return dn_role_of_letter(DN_ROLE_ORDER[second_tile ? 1 : 0][w]);
+    return dn_role_of_letter(order[second_tile ? 1 : 0][w]);
+}
+
+// The role of wave w under `table` and the orders above.
+constexpr int dn_place_role_with(const DnRoleTable &table, const int simd[DN_ROLES], bool second_tile, int w)
+{
+    return dn_place_role_with(table, DN_ROLE_ORDER, simd, second_tile, w);
 }
 
 // The role of wave w: what the kernel asks.

@@ -41,13 +41,21 @@ def _run(pkg, track, n, acts, k, singles=False):
     return waves, got
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 640])      # a ragged tile, one tile, two tiles, ten tiles
+SECOND_TILES = "64 (num_cus + 1) + 4"      # one full and one ragged second tile (the workgroups that land beside tiles 0 and 1 on their CUs) beside a full set of first tiles
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 640, pytest.param(SECOND_TILES, id="second_tiles")])      # a ragged tile, one tile, two tiles, ten tiles; the shipped second-tile rows
 def test_five_waves_give_the_bits_of_one_wave_whatever_the_placement(n, monkeypatch):
     """DN_WAVES=5 against DN_WAVES=1 from the same reset, K in {1, 2, 3, 7}, three runs of the five-wave side.  dn_step_many refuses a
     fleet that is no multiple of four drones, so at n in {1, 63, 65} the refusal is asserted, the K steps fly as single steps at n, and
     the launches fly at the nearest fleet the entry point takes with the same tile shape (4, 60, 68: a ragged tile, a ragged tile, one
-    tile and a ragged one)."""
+    tile and a ragged one).  The last fleet, 16 452 drones on 256 CUs, takes its size from the device the env reports."""
     pkg = _gpu()
+    if n == SECOND_TILES:
+        from drl_dronenavigation_amd import tracks
+        env = pkg.DroneVecEnv(tracks.REGISTRY["reaching"](), 4, normalize_obs=True, device="cuda:0")
+        n = 64 * (env.num_cus + 1) + 4
+        env.close()
     if n in LAUNCH_FLEET:
         _compare(pkg, n, monkeypatch, singles=True)
         n = LAUNCH_FLEET[n]
