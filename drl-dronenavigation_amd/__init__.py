@@ -23,7 +23,7 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "DynamicsRandomization", "WindDisturbance", "ActuatorModel", "SensorModel",
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
            "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer",
-           "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam", "ReplaySampler", "SacPolicyHead", "SacCriticLoss", "SacActorLoss",
+           "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam", "MlpTrainer", "ReplaySampler", "SacPolicyHead", "SacCriticLoss", "SacActorLoss",
            "SacCritic"]
 
 
@@ -55,6 +55,9 @@ def __getattr__(name):
     if name in ("optim", "ClippedAdam"):
         optim = importlib.import_module(__name__ + ".optim")
         return optim if name == "optim" else optim.ClippedAdam
+    if name in ("mlp_train", "MlpTrainer"):
+        mlp_train = importlib.import_module(__name__ + ".mlp_train")
+        return mlp_train if name == "mlp_train" else mlp_train.MlpTrainer
     if name in ("replay", "ReplaySampler"):
         replay = importlib.import_module(__name__ + ".replay")
         return replay if name == "replay" else replay.ReplaySampler

@@ -160,6 +160,22 @@ class DnSacConfig(C.Structure):
 SAC_MAX_ACT, SAC_MAX_CRITICS = 8, 4
 
 
+class DnMlpTrainLayer(C.Structure):
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("d_weight", C.c_void_p), ("d_bias", C.c_void_p), ("in_dim", C.c_int32),
+                ("out_dim", C.c_int32)]
+
+
+class DnMlpTrainConfig(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("activation", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# DN_MLP_TRAIN_MAX_LAYERS, DN_MLP_ACT_TANH, DN_MLP_TRAIN_ACCUMULATE, DN_MLP_TRAIN_NO_PARAM_GRADS, DN_MLP_TRAIN_CHUNK (tests/test_mlp_train_cpu.py
+# holds them to the header)
+TRAIN_MAX_LAYERS, TRAIN_ACT_TANH = 4, 0
+TRAIN_ACCUMULATE, TRAIN_NO_PARAM_GRADS = 1, 2
+TRAIN_CHUNK = 1024
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -226,6 +242,9 @@ PROTOTYPES = {
     "dn_sac_policy_backward": (_I32, [C.POINTER(DnSacConfig), _I64] + [_VP] * 7 + [_I32, _VP]),
     "dn_sac_critic_loss": (_I32, [C.POINTER(DnSacConfig), _I64] + [_VP] * 11 + [_I64, _I32, _VP]),
     "dn_sac_actor_loss": (_I32, [C.POINTER(DnSacConfig), _I64] + [_VP] * 10 + [_I64, _I32, _VP]),
+    "dn_mlp_train_scratch_bytes": (_I64, [C.POINTER(DnMlpTrainConfig), C.POINTER(DnMlpTrainLayer), _I64]),
+    "dn_mlp_train_forward": (_I32, [C.POINTER(DnMlpTrainConfig), C.POINTER(DnMlpTrainLayer), _VP, _I64, _VP, _VP, _I64, _I32, _VP]),
+    "dn_mlp_train_backward": (_I32, [C.POINTER(DnMlpTrainConfig), C.POINTER(DnMlpTrainLayer), _VP, _VP, _I64, _VP, _VP, _I64, _I32, _VP]),
     "dn_set_launch_events":(_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

@@ -1,5 +1,6 @@
 // dn_capi_envfree.cpp -- the entry points of include/dronenav.h that take a device_id and no dn_env: the rollout glue, the history rows,
-// the two fleet normalisers, the minibatches, the PPO loss, the optimiser step, the replay minibatches and the SAC loss heads.
+// the two fleet normalisers, the minibatches, the PPO loss, the optimiser step, the replay minibatches, the SAC loss heads and the
+// training pass of the Tanh networks.
 //
 // Every entry point validates its arguments, turns HIP failures into dn_status codes + the thread-local message of dn_capi.cpp
 // (dn_capi_fail.h), and never falls back to a CPU implementation.
@@ -754,4 +755,126 @@ int32_t dn_sac_actor_loss(const dn_sac_config *cfg, int64_t batch, const float *
     DN_HIP(dn_launch_sac_loss(a, (hipStream_t)stream));
     return DN_OK;
 }
+}  // extern "C"
+
+// ---- dn_mlp_train: the training pass of the reference's Tanh networks (forward with saved activations, backward) ---------------------------
+/* what the three entry points ask of cfg, of the dimensions of layers and of batch */
+static int32_t mlp_train_shape_ok(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (!layers) return fail(DN_ERR_INVALID_ARGUMENT, "layers is required");
+    if (cfg->n_layers < 2 || cfg->n_layers > DN_MLP_TRAIN_MAX_LAYERS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "n_layers must be in 2..%d, the head included (got %d)", DN_MLP_TRAIN_MAX_LAYERS, cfg->n_layers);
+    if (cfg->activation != DN_MLP_ACT_TANH)
+        return fail(DN_ERR_INVALID_ARGUMENT, "activation must be DN_MLP_ACT_TANH = %d (got %d)", DN_MLP_ACT_TANH, cfg->activation);
+    if (cfg->flags & ~(DN_MLP_TRAIN_ACCUMULATE | DN_MLP_TRAIN_NO_PARAM_GRADS))
+        return fail(DN_ERR_INVALID_ARGUMENT, "flags has unknown bits: 0x%x (bit 0 accumulates, bit 1 skips the parameter gradients)", cfg->flags);
+    if (const int32_t rc = reserved_ok(cfg->reserved)) return rc;
+    const int L = cfg->n_layers;
+    if (layers[0].in_dim < 1 || layers[0].in_dim > 64)
+        return fail(DN_ERR_INVALID_ARGUMENT, "layers[0].in_dim must be in 1..64 (got %d)", layers[0].in_dim);
+    for (int l = 0; l < L - 1; ++l)
+        if (layers[l].out_dim < 32 || layers[l].out_dim > 512 || layers[l].out_dim % 32)
+            return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d].out_dim, a hidden width, must be a multiple of 32 in 32..512 (got %d)", l, layers[l].out_dim);
+    if (layers[L - 1].out_dim < 1 || layers[L - 1].out_dim > 32)
+        return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d].out_dim, the head's, must be in 1..32 (got %d)", L - 1, layers[L - 1].out_dim);
+    for (int l = 1; l < L; ++l)
+        if (layers[l].in_dim != layers[l - 1].out_dim)
+            return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d].in_dim must be layers[%d].out_dim = %d (got %d)", l, l - 1, layers[l - 1].out_dim,
+                        layers[l].in_dim);
+    if (batch < 1 || batch > (1ll << 24)) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^24 (got %lld)", (long long)batch);
+    return DN_OK;
+}
+
+/* the pointers of a call: `in` and `out` are the call's own besides the layers'; grads: d_weight and d_bias are written */
+static int32_t mlp_train_pointers_ok(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch, const DnArg *in_own,
+                                     size_t n_in_own, const DnArg *out_own, size_t n_out_own, bool grads, void *scratch, int64_t scratch_bytes)
+{
+    static const char *const W[] = {"layers[0].weight", "layers[1].weight", "layers[2].weight", "layers[3].weight"};
+    static const char *const B[] = {"layers[0].bias", "layers[1].bias", "layers[2].bias", "layers[3].bias"};
+    static const char *const DW[] = {"layers[0].d_weight", "layers[1].d_weight", "layers[2].d_weight", "layers[3].d_weight"};
+    static const char *const DB[] = {"layers[0].d_bias", "layers[1].d_bias", "layers[2].d_bias", "layers[3].d_bias"};
+    DnArg in[2 * DN_MLP_TRAIN_MAX_LAYERS + 2], out[2 * DN_MLP_TRAIN_MAX_LAYERS + 3];
+    size_t ni = 0, no = 0;
+    for (size_t i = 0; i < n_in_own; ++i) in[ni++] = in_own[i];
+    for (size_t i = 0; i < n_out_own; ++i) out[no++] = out_own[i];
+    for (int l = 0; l < cfg->n_layers; ++l) {
+        const uintptr_t wb = (uintptr_t)layers[l].out_dim * (uintptr_t)layers[l].in_dim * sizeof(float), bb = (uintptr_t)layers[l].out_dim * sizeof(float);
+        in[ni++] = DnArg{W[l], layers[l].weight, wb, false};
+        in[ni++] = DnArg{B[l], layers[l].bias, bb, false};
+        if (grads) {
+            out[no++] = DnArg{DW[l], layers[l].d_weight, wb, false};
+            out[no++] = DnArg{DB[l], layers[l].d_bias, bb, false};
+        }
+    }
+    const int64_t need = dn_mlp_train_layout(layers, cfg->n_layers, batch).total;
+    out[no++] = DnArg{"scratch", scratch, (uintptr_t)need, false};
+    if (const DnArg *a = dn_first_missing(in, ni)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_missing(out, no)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (dn_scratch_short(scratch_bytes, need)) return scratch_too_small(scratch_bytes, need, "dn_mlp_train_scratch_bytes");
+    if ((uintptr_t)scratch & 15u) return fail(DN_ERR_INVALID_ARGUMENT, "scratch must be 16-byte aligned");
+    if (const DnArg *a = dn_first_misaligned(in, ni, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    if (const DnArg *a = dn_first_misaligned(out, no, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    const DnArg *o, *i;
+    if (dn_first_overlap(out, no, in, ni, &o, &i)) return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no output may alias an input", o->name, i->name);
+    for (size_t a = 0; a + 1 < no; ++a)
+        if (dn_first_overlap(&out[a], 1, &out[a + 1], no - a - 1, &o, &i))
+            return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: every output is a tensor of its own", o->name, i->name);
+    return DN_OK;
+}
+
+static void mlp_train_args(DnMlpTrainArgs &a, const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch, void *scratch)
+{
+    std::memset(&a, 0, sizeof a);
+    for (int l = 0; l < cfg->n_layers; ++l) a.layer[l] = layers[l];
+    a.scratch = (char *)scratch;
+    a.batch = batch;
+    a.n_layers = cfg->n_layers;
+    a.flags = cfg->flags;
+}
+
+extern "C" {
+
+int64_t dn_mlp_train_scratch_bytes(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch)
+{
+    if (const int32_t rc = mlp_train_shape_ok(cfg, layers, batch)) return rc;
+    return dn_mlp_train_layout(layers, cfg->n_layers, batch).total;
+}
+
+int32_t dn_mlp_train_forward(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, const float *x, int64_t batch, float *out,
+                             void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (const int32_t rc = mlp_train_shape_ok(cfg, layers, batch)) return rc;
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float);
+    const DnArg in[] = {{"x", x, rows * (uintptr_t)layers[0].in_dim, false}};
+    const DnArg outs[] = {{"out", out, rows * (uintptr_t)layers[cfg->n_layers - 1].out_dim, false}};
+    if (const int32_t rc = mlp_train_pointers_ok(cfg, layers, batch, in, 1, outs, 1, false, scratch, scratch_bytes)) return rc;
+    DnMlpTrainArgs a;
+    mlp_train_args(a, cfg, layers, batch, scratch);
+    a.x = x; a.out = out;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_mlp_train_forward(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_mlp_train_backward(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, const float *x, const float *d_out,
+                              int64_t batch, float *d_x, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (const int32_t rc = mlp_train_shape_ok(cfg, layers, batch)) return rc;
+    const bool grads = !(cfg->flags & DN_MLP_TRAIN_NO_PARAM_GRADS);
+    if (!grads && !d_x)
+        return fail(DN_ERR_INVALID_ARGUMENT, "d_x is required with DN_MLP_TRAIN_NO_PARAM_GRADS in flags (there is nothing else to do)");
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float);
+    const DnArg in[] = {{"x", x, rows * (uintptr_t)layers[0].in_dim, false},
+                        {"d_out", d_out, rows * (uintptr_t)layers[cfg->n_layers - 1].out_dim, false}};
+    const DnArg outs[] = {{"d_x", d_x, rows * (uintptr_t)layers[0].in_dim, true}};
+    if (const int32_t rc = mlp_train_pointers_ok(cfg, layers, batch, in, 2, outs, 1, grads, scratch, scratch_bytes)) return rc;
+    DnMlpTrainArgs a;
+    mlp_train_args(a, cfg, layers, batch, scratch);
+    a.x = x; a.d_out = d_out; a.d_x = d_x;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_mlp_train_backward(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
 }  // extern "C"

@@ -453,6 +453,37 @@ inline long long dn_sac_loss_scratch_doubles(long long batch, int n_critics)
 }
 hipError_t dn_launch_sac_policy(const DnSacPolicyArgs &a, bool backward, hipStream_t stream);                                  // dn_sac_loss.hip
 hipError_t dn_launch_sac_loss(const DnSacLossArgs &a, hipStream_t stream);                                                     // dn_sac_loss.hip
+// The training pass of the Tanh networks (dn_mlp_train_forward / _backward, dn_mlp_train.hip).  The scratch regions of the header, as
+// byte offsets: h[l] and dz[l] for the hidden layers l < n_layers - 1, wpart[l] and bpart[l] for every layer.  The dimensions have
+// passed the C ABI's checks: in <= 512, out <= 512, batch <= 2^24, so no product here comes near 2^63.
+struct DnMlpTrainLayout {
+    long long h[DN_MLP_TRAIN_MAX_LAYERS], dz[DN_MLP_TRAIN_MAX_LAYERS], wpart[DN_MLP_TRAIN_MAX_LAYERS], bpart[DN_MLP_TRAIN_MAX_LAYERS];
+    long long chunks, total;
+};
+inline long long dn_mlp_train_chunks(long long batch) { return batch < 1 ? 0 : (batch - 1) / DN_MLP_TRAIN_CHUNK + 1; }
+inline DnMlpTrainLayout dn_mlp_train_layout(const dn_mlp_train_layer *layers, int n_layers, long long batch)
+{
+    const auto r = [](long long b) { return (b + 255) / 256 * 256; };
+    DnMlpTrainLayout lay = {};
+    lay.chunks = dn_mlp_train_chunks(batch);
+    long long at = 0;
+    for (int l = 0; l < n_layers - 1; ++l) { lay.h[l] = at; at += r(4 * batch * layers[l].out_dim); }
+    for (int l = 0; l < n_layers - 1; ++l) { lay.dz[l] = at; at += r(4 * batch * layers[l].out_dim); }
+    for (int l = 0; l < n_layers; ++l) { lay.wpart[l] = at; at += r(4 * lay.chunks * layers[l].out_dim * layers[l].in_dim); }
+    for (int l = 0; l < n_layers; ++l) { lay.bpart[l] = at; at += r(8 * lay.chunks * layers[l].out_dim); }
+    lay.total = at;
+    return lay;
+}
+struct DnMlpTrainArgs {
+    dn_mlp_train_layer layer[DN_MLP_TRAIN_MAX_LAYERS];
+    const float *x, *d_out;                            // d_out: backward only
+    float *out, *d_x;                                  // out: forward only; d_x: backward only, NULL = not wanted
+    char *scratch;
+    long long batch;
+    int n_layers, flags;
+};
+hipError_t dn_launch_mlp_train_forward(const DnMlpTrainArgs &a, hipStream_t stream);                                           // dn_mlp_train.hip
+hipError_t dn_launch_mlp_train_backward(const DnMlpTrainArgs &a, hipStream_t stream);                                          // dn_mlp_train.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

@@ -1184,6 +1184,75 @@ int32_t dn_sac_actor_loss(const dn_sac_config *cfg, int64_t batch, const float *
                           const float *log_ent_coef, float *d_log_prob, float *const *d_q_pi, float *d_log_ent_coef, float *actor_loss,
                           float *ent_coef_loss, double *stats, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
 
+/* The training pass of the reference's Tanh networks on the device: a forward that saves what the backward needs, and a backward from
+ * the gradient with respect to the head output (what dn_ppo_loss hands out) to every weight and bias gradient and, where asked, to the
+ * input.  Env-free; the loss head, the optimiser and the learner loop are dn_ppo_loss, dn_adam_step and the caller's.
+ * The network: `layers`, a HOST array of n_layers = 2..4 linear layers, the head last; layer 0 has in_dim 1..64 (any value), every
+ *   hidden width (the out_dim of every layer but the last) is a multiple of 32 in 32..512, the head's out_dim is 1..32, and
+ *   layers[l].in_dim == layers[l - 1].out_dim.  weight and bias are torch's nn.Linear tensors, float32 [out_dim][in_dim] and [out_dim],
+ *   dense, read in place: nothing is packed on the host and no second copy of the weights exists.  batch is 1..2^24 rows, any value.
+ *     h_0 = x;  h_l = tanh(h_{l-1} W_l^T + b_l) for the hidden layers;  out = h_{L-1} W_L^T + b_L
+ *   dn_mlp_train_forward writes out [batch][head out_dim] and saves the hidden activations as float32 in scratch.
+ *   dn_mlp_train_backward must follow a forward with the same config, layers, batch, x and scratch (the caller's business: nothing can
+ *   check it).  With dZ_L = d_out [batch][head out_dim] and dZ_l = dH_l (1 - h_l^2) it forms
+ *     d_bias_l = sum over the rows of dZ_l;  d_weight_l = dZ_l^T h_{l-1};  dH_{l-1} = dZ_l W_l;  d_x = dH_0 where d_x is not NULL.
+ *   flags bit 0 (DN_MLP_TRAIN_ACCUMULATE): each finished float32 gradient is added to the tensor (one float32 add) instead of
+ *   overwriting it.  Bit 1 (DN_MLP_TRAIN_NO_PARAM_GRADS): the backward forms d_x only; d_weight and d_bias are neither read nor
+ *   written and may be NULL.  d_x is always overwritten.  The other bits and `reserved` must be 0; `activation` must be
+ *   DN_MLP_ACT_TANH (the field exists so that ReLU can follow without a new layout).
+ * Arithmetic, float32 grade: every matrix product runs on v_mfma_f32_32x32x16_bf16 with BOTH operands split on the device, as they
+ *   are staged, into two bfloat16 words hi = bf16(v), lo = bf16(v - hi), round to nearest even (csrc/dn_bf16_split.h); a product is
+ *   the three MFMAs lo hi, hi lo, hi hi, in this order, into one float32 accumulator, K-steps of 16 in ascending order.  Bias add,
+ *   tanh(z) = 1 - 2 / (1 + 2^(2 log2(e) z)) (v_exp_f32, v_rcp_f32) and 1 - h h are float32; activations and dZ travel between the
+ *   launches as float32.
+ * Bit-reproducible: no atomics, no workgroup waits for another, and the order of every addition is a function of (batch, the layer
+ *   dimensions) alone.  Row b of out, of the saved activations, of every dZ and of d_x depends on no other row and not on batch.  The
+ *   sums over the batch: the rows are cut into chunks of DN_MLP_TRAIN_CHUNK consecutive rows (the last is short).  One workgroup forms
+ *   each (chunk, output tile) partial of d_weight_l -- the MFMA chain above over the chunk's rows in ascending K-steps of 16 rows, rows
+ *   at and beyond batch staged as exact zeros -- as float32 into scratch.  The chunk's partial of d_bias_l[o] is a float64 sum: lane
+ *   group g = 0..7 adds the rows 4 g .. 4 g + 3 of every 32 rows of the chunk in ascending order, then the eight groups are added in
+ *   ascending order.  One merge launch adds the chunks' partials in ascending chunk order in float64 and rounds once to float32.
+ *   scratch        the caller's device memory, 16-byte aligned, at least dn_mlp_train_scratch_bytes(cfg, layers, batch).  With
+ *                  r(b) = b rounded up to a multiple of 256 and C = ceil(batch / DN_MLP_TRAIN_CHUNK) its regions are, in this order:
+ *                  h_l, r(4 batch out_l) bytes per hidden layer; dZ_l, the same again per hidden layer; the d_weight partials,
+ *                  r(4 C out_l in_l) per layer; the d_bias partials, r(8 C out_l) per layer.  The library allocates nothing and keeps
+ *                  nothing between calls.
+ * Ordinary launches on `stream`, capturable: the forward one per layer; the backward one weight-gradient and one data-gradient launch
+ *   per layer (none for layer 0's data gradient without d_x, no weight-gradient launches with bit 1) and the merge.  Every output word
+ *   is written exactly once by a vector store (read once and written once with bit 0).  No output (out, d_x, d_weight, d_bias,
+ *   scratch) may overlap an input (x, d_out, weight, bias) or, among the gradient tensors, d_x and out, one another.
+ * Validates before the first device call: DN_ERR_INVALID_ARGUMENT with a dn_last_error text that names the argument.
+ * Layouts: dn_mlp_train_layer weight at 0, bias at 8, d_weight at 16, d_bias at 24, in_dim at 32, out_dim at 36; 40 bytes.
+ *   dn_mlp_train_config n_layers at 0, activation at 4, flags at 8, reserved at 12; 16 bytes. */
+#define DN_MLP_TRAIN_MAX_LAYERS 4
+#define DN_MLP_ACT_TANH 0
+#define DN_MLP_TRAIN_ACCUMULATE 1
+#define DN_MLP_TRAIN_NO_PARAM_GRADS 2
+#define DN_MLP_TRAIN_CHUNK 1024
+typedef struct dn_mlp_train_layer {
+    const float *weight;    /* device float32 [out_dim][in_dim], dense, torch's nn.Linear layout, read in place */
+    const float *bias;      /* device float32 [out_dim] */
+    float *d_weight;        /* device float32 [out_dim][in_dim]; may be NULL for dn_mlp_train_forward and with bit 1 */
+    float *d_bias;          /* device float32 [out_dim]; as d_weight */
+    int32_t in_dim;         /* layer 0: 1..64; else the out_dim of the layer before */
+    int32_t out_dim;        /* hidden: a multiple of 32 in 32..512; head: 1..32 */
+} dn_mlp_train_layer;
+typedef struct dn_mlp_train_config {
+    int32_t n_layers;       /* 2..4 linear layers, the head included */
+    int32_t activation;     /* DN_MLP_ACT_TANH */
+    int32_t flags;          /* bit 0 = DN_MLP_TRAIN_ACCUMULATE, bit 1 = DN_MLP_TRAIN_NO_PARAM_GRADS */
+    int32_t reserved;       /* 0 */
+} dn_mlp_train_config;
+/* Bytes of scratch for this network over `batch` rows (the formula above; only the dimensions of `layers` are read): host only, no HIP
+ * call.  A negative dn_status for a NULL argument, a dimension or chain the calls refuse, or batch outside 1..2^24. */
+int64_t dn_mlp_train_scratch_bytes(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch);
+/* out [batch][head out_dim] from x [batch][layers[0].in_dim]; the hidden activations stay in scratch for the backward. */
+int32_t dn_mlp_train_forward(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, const float *x, int64_t batch, float *out,
+                             void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+/* Every d_weight and d_bias, and d_x [batch][layers[0].in_dim] where it is not NULL, from d_out [batch][head out_dim]. */
+int32_t dn_mlp_train_backward(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, const float *x, const float *d_out,
+                              int64_t batch, float *d_x, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
