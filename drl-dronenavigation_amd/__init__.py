@@ -24,7 +24,7 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
            "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer",
            "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam", "MlpTrainer", "ReplaySampler", "SacPolicyHead", "SacCriticLoss", "SacActorLoss",
-           "SacCritic"]
+           "SacCritic", "SacTrainer", "PolyakUpdate"]
 
 
 def __getattr__(name):
@@ -64,6 +64,9 @@ def __getattr__(name):
     if name in ("sac", "SacPolicyHead", "SacCriticLoss", "SacActorLoss"):
         sac = importlib.import_module(__name__ + ".sac")
         return sac if name == "sac" else getattr(sac, name)
+    if name in ("sac_train", "SacTrainer", "PolyakUpdate"):
+        sac_train = importlib.import_module(__name__ + ".sac_train")
+        return sac_train if name == "sac_train" else getattr(sac_train, name)
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
     if name in ("policy", "MlpActorCritic", "SacActor", "SacCritic", "MlpValue"):

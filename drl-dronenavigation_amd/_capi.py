@@ -176,6 +176,16 @@ TRAIN_ACCUMULATE, TRAIN_NO_PARAM_GRADS = 1, 2
 TRAIN_CHUNK = 1024
 
 
+class DnSacTrainConfig(C.Structure):
+    _fields_ = [("n_nets", C.c_int32), ("n_layers", C.c_int32), ("head_parts", C.c_int32), ("activation", C.c_int32), ("in0", C.c_int32),
+                ("in1", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# DN_MLP_ACT_RELU, DN_SAC_TRAIN_MAX_NETS, DN_SAC_TRAIN_MAX_PARTS (tests/test_sac_train_cpu.py holds them to the header)
+TRAIN_ACT_RELU = 1
+TRAIN_MAX_NETS, TRAIN_MAX_PARTS = 4, 2
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -245,6 +255,11 @@ PROTOTYPES = {
     "dn_mlp_train_scratch_bytes": (_I64, [C.POINTER(DnMlpTrainConfig), C.POINTER(DnMlpTrainLayer), _I64]),
     "dn_mlp_train_forward": (_I32, [C.POINTER(DnMlpTrainConfig), C.POINTER(DnMlpTrainLayer), _VP, _I64, _VP, _VP, _I64, _I32, _VP]),
     "dn_mlp_train_backward": (_I32, [C.POINTER(DnMlpTrainConfig), C.POINTER(DnMlpTrainLayer), _VP, _VP, _I64, _VP, _VP, _I64, _I32, _VP]),
+    "dn_sac_train_scratch_bytes": (_I64, [C.POINTER(DnSacTrainConfig), C.POINTER(DnMlpTrainLayer), _I64]),
+    "dn_sac_train_forward": (_I32, [C.POINTER(DnSacTrainConfig), C.POINTER(DnMlpTrainLayer), _VP, _VP, _I64, C.POINTER(_VP), _VP, _I64, _I32, _VP]),
+    "dn_sac_train_backward": (_I32, [C.POINTER(DnSacTrainConfig), C.POINTER(DnMlpTrainLayer), _VP, _VP, C.POINTER(_VP), _I64, _VP, _VP, _VP, _I64,
+                                     _I32, _VP]),
+    "dn_polyak_update": (_I32, [_I32, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I64), C.c_double, _I32, _VP]),
     "dn_set_launch_events":(_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

@@ -1,6 +1,6 @@
 // dn_capi_envfree.cpp -- the entry points of include/dronenav.h that take a device_id and no dn_env: the rollout glue, the history rows,
-// the two fleet normalisers, the minibatches, the PPO loss, the optimiser step, the replay minibatches, the SAC loss heads and the
-// training pass of the Tanh networks.
+// the two fleet normalisers, the minibatches, the PPO loss, the optimiser step, the replay minibatches, the SAC loss heads, the
+// training passes of the Tanh and of the SAC networks and the Polyak update.
 //
 // Every entry point validates its arguments, turns HIP failures into dn_status codes + the thread-local message of dn_capi.cpp
 // (dn_capi_fail.h), and never falls back to a CPU implementation.
@@ -12,6 +12,8 @@
 #include "dn_row_sums.h"
 
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 
 // The refusals that several entry points word alike, each stated once: DN_OK, or the status fail() returns.
@@ -874,6 +876,226 @@ int32_t dn_mlp_train_backward(const dn_mlp_train_config *cfg, const dn_mlp_train
     a.x = x; a.d_out = d_out; a.d_x = d_x;
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_mlp_train_backward(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+}  // extern "C"
+
+// ---- dn_sac_train: the training pass of the SAC networks, and dn_polyak_update --------------------------------------------------------------
+/* a pointer argument whose name is made at run time: layers[c][l].field, out[i] */
+struct SacNamed {
+    char name[40];
+};
+__attribute__((format(printf, 4, 5))) static DnArg sac_named(SacNamed &n, const void *p, uintptr_t bytes, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(n.name, sizeof n.name, fmt, ap);
+    va_end(ap);
+    return DnArg{n.name, p, bytes, false};
+}
+
+/* what the three entry points ask of cfg, of the dimensions of layers and of batch */
+static int32_t sac_train_shape_ok(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (!layers) return fail(DN_ERR_INVALID_ARGUMENT, "layers is required");
+    if (cfg->n_nets < 1 || cfg->n_nets > DN_SAC_TRAIN_MAX_NETS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "n_nets must be in 1..%d (got %d)", DN_SAC_TRAIN_MAX_NETS, cfg->n_nets);
+    if (cfg->n_layers < 2 || cfg->n_layers > DN_MLP_TRAIN_MAX_LAYERS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "n_layers must be in 2..%d, the head counted once (got %d)", DN_MLP_TRAIN_MAX_LAYERS, cfg->n_layers);
+    if (cfg->head_parts < 1 || cfg->head_parts > DN_SAC_TRAIN_MAX_PARTS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "head_parts must be in 1..%d (got %d)", DN_SAC_TRAIN_MAX_PARTS, cfg->head_parts);
+    if (cfg->activation != DN_MLP_ACT_TANH && cfg->activation != DN_MLP_ACT_RELU)
+        return fail(DN_ERR_INVALID_ARGUMENT, "activation must be DN_MLP_ACT_TANH = %d or DN_MLP_ACT_RELU = %d (got %d)", DN_MLP_ACT_TANH,
+                    DN_MLP_ACT_RELU, cfg->activation);
+    if (cfg->in0 < 1 || cfg->in0 > 64) return fail(DN_ERR_INVALID_ARGUMENT, "in0 must be in 1..64 (got %d)", cfg->in0);
+    if (cfg->in1 < 0 || cfg->in1 > 63 || cfg->in0 + cfg->in1 > 64)
+        return fail(DN_ERR_INVALID_ARGUMENT, "in1 must be in 0..63 with in0 + in1 <= 64 (got %d beside in0 = %d)", cfg->in1, cfg->in0);
+    if (cfg->flags & ~(DN_MLP_TRAIN_ACCUMULATE | DN_MLP_TRAIN_NO_PARAM_GRADS))
+        return fail(DN_ERR_INVALID_ARGUMENT, "flags has unknown bits: 0x%x (bit 0 accumulates, bit 1 skips the parameter gradients)", cfg->flags);
+    if (const int32_t rc = reserved_ok(cfg->reserved)) return rc;
+    const int L = cfg->n_layers, P = cfg->head_parts, E = L - 1 + P;
+    for (int c = 0; c < cfg->n_nets; ++c) {
+        const dn_mlp_train_layer *net = layers + c * E;
+        if (net[0].in_dim != cfg->in0 + cfg->in1)
+            return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d][0].in_dim must be in0 + in1 = %d (got %d)", c, cfg->in0 + cfg->in1, net[0].in_dim);
+        for (int l = 0; l < L - 1; ++l)
+            if (net[l].out_dim < 32 || net[l].out_dim > 512 || net[l].out_dim % 32)
+                return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d][%d].out_dim, a hidden width, must be a multiple of 32 in 32..512 (got %d)", c, l,
+                            net[l].out_dim);
+        for (int l = 1; l < E; ++l) {
+            const int before = l < L ? l - 1 : L - 2;                            // every head part reads the last hidden layer
+            if (net[l].in_dim != net[before].out_dim)
+                return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d][%d].in_dim must be layers[%d][%d].out_dim = %d (got %d)", c, l, c, before,
+                            net[before].out_dim, net[l].in_dim);
+        }
+        int head = 0;
+        for (int l = L - 1; l < E; ++l) {
+            if (net[l].out_dim < 1 || net[l].out_dim > 32)
+                return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d][%d].out_dim, a head part's, must be in 1..32 (got %d)", c, l, net[l].out_dim);
+            head += net[l].out_dim;
+        }
+        if (head > 32)
+            return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d][%d].out_dim: the head's parts must have at most 32 outputs together (got %d)", c, E - 1, head);
+        for (int l = 0; l < E; ++l) {
+            if (net[l].in_dim != layers[l].in_dim)
+                return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d][%d].in_dim must be layers[0][%d].in_dim = %d, the networks of a group have one shape (got %d)",
+                            c, l, l, layers[l].in_dim, net[l].in_dim);
+            if (net[l].out_dim != layers[l].out_dim)
+                return fail(DN_ERR_INVALID_ARGUMENT, "layers[%d][%d].out_dim must be layers[0][%d].out_dim = %d, the networks of a group have one shape (got %d)",
+                            c, l, l, layers[l].out_dim, net[l].out_dim);
+        }
+    }
+    if (batch < 1 || batch > (1ll << 24)) return fail(DN_ERR_INVALID_ARGUMENT, "batch must be in 1..2^24 (got %lld)", (long long)batch);
+    return DN_OK;
+}
+
+/* every pointer of a call.  table: out (forward) or d_out (backward), n_nets * head_parts pointers; grads: d_weight and d_bias are written */
+static int32_t sac_train_pointers_ok(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch, const float *x0,
+                                     const float *x1, const void *const *table, const char *table_name, bool table_is_output, float *d_x0,
+                                     float *d_x1, bool backward, bool grads, void *scratch, int64_t scratch_bytes)
+{
+    constexpr int MOST = DN_SAC_TRAIN_MAX_NETS * DN_SAC_TRAIN_MAX_ENTRIES, HEADS = DN_SAC_TRAIN_MAX_NETS * DN_SAC_TRAIN_MAX_PARTS;
+    const int L = cfg->n_layers, P = cfg->head_parts, E = L - 1 + P;
+    const uintptr_t rows = (uintptr_t)batch * sizeof(float);
+    if (!table) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", table_name);
+    if ((x1 != nullptr) != (cfg->in1 > 0)) return fail(DN_ERR_INVALID_ARGUMENT, "x1 must be NULL exactly when in1 = 0 (in1 = %d)", cfg->in1);
+    SacNamed names[4 * MOST + HEADS];
+    DnArg in[2 * MOST + HEADS + 2], out[2 * MOST + HEADS + 3];
+    size_t ni = 0, no = 0, nn = 0;
+    in[ni++] = DnArg{"x0", x0, rows * (uintptr_t)cfg->in0, false};
+    in[ni++] = DnArg{"x1", x1, rows * (uintptr_t)cfg->in1, true};
+    if (backward) {
+        out[no++] = DnArg{"d_x0", d_x0, rows * (uintptr_t)cfg->in0, true};
+        out[no++] = DnArg{"d_x1", d_x1, rows * (uintptr_t)cfg->in1, true};
+    }
+    for (int c = 0; c < cfg->n_nets; ++c) {
+        for (int p = 0; p < P; ++p) {
+            const DnArg a = sac_named(names[nn++], table[c * P + p], rows * (uintptr_t)layers[c * E + L - 1 + p].out_dim, "%s[%d]", table_name, c * P + p);
+            (table_is_output ? out[no++] : in[ni++]) = a;
+        }
+        for (int l = 0; l < E; ++l) {
+            const dn_mlp_train_layer &T = layers[c * E + l];
+            const uintptr_t wb = (uintptr_t)T.out_dim * (uintptr_t)T.in_dim * sizeof(float), bb = (uintptr_t)T.out_dim * sizeof(float);
+            in[ni++] = sac_named(names[nn++], T.weight, wb, "layers[%d][%d].%s", c, l, "weight");
+            in[ni++] = sac_named(names[nn++], T.bias, bb, "layers[%d][%d].%s", c, l, "bias");
+            if (grads) {
+                out[no++] = sac_named(names[nn++], T.d_weight, wb, "layers[%d][%d].%s", c, l, "d_weight");
+                out[no++] = sac_named(names[nn++], T.d_bias, bb, "layers[%d][%d].%s", c, l, "d_bias");
+            }
+        }
+    }
+    const int64_t need = dn_sac_train_layout(layers, cfg->n_nets, L, P, batch).total;
+    out[no++] = DnArg{"scratch", scratch, (uintptr_t)need, false};
+    if (const DnArg *a = dn_first_missing(in, ni)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_missing(out, no)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (dn_scratch_short(scratch_bytes, need)) return scratch_too_small(scratch_bytes, need, "dn_sac_train_scratch_bytes");
+    if ((uintptr_t)scratch & 15u) return fail(DN_ERR_INVALID_ARGUMENT, "scratch must be 16-byte aligned");
+    if (const DnArg *a = dn_first_misaligned(in, ni, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    if (const DnArg *a = dn_first_misaligned(out, no, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    const DnArg *o, *i;
+    if (dn_first_overlap(out, no, in, ni, &o, &i)) return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no output may alias an input", o->name, i->name);
+    for (size_t a = 0; a + 1 < no; ++a)
+        if (dn_first_overlap(&out[a], 1, &out[a + 1], no - a - 1, &o, &i))
+            return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: every output is a tensor of its own", o->name, i->name);
+    return DN_OK;
+}
+
+static void sac_train_args(DnSacTrainArgs &a, const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch, const float *x0,
+                           const float *x1, void *scratch)
+{
+    std::memset(&a, 0, sizeof a);
+    const int E = cfg->n_layers - 1 + cfg->head_parts;
+    for (int c = 0; c < cfg->n_nets; ++c)
+        for (int l = 0; l < E; ++l) a.layer[c][l] = layers[c * E + l];
+    a.x0 = x0; a.x1 = x1;
+    a.scratch = (char *)scratch;
+    a.batch = batch;
+    a.n_nets = cfg->n_nets; a.n_layers = cfg->n_layers; a.head_parts = cfg->head_parts; a.activation = cfg->activation;
+    a.in0 = cfg->in0; a.in1 = cfg->in1; a.flags = cfg->flags;
+}
+
+extern "C" {
+
+int64_t dn_sac_train_scratch_bytes(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch)
+{
+    if (const int32_t rc = sac_train_shape_ok(cfg, layers, batch)) return rc;
+    return dn_sac_train_layout(layers, cfg->n_nets, cfg->n_layers, cfg->head_parts, batch).total;
+}
+
+int32_t dn_sac_train_forward(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, const float *x0, const float *x1,
+                             int64_t batch, float *const *out, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (const int32_t rc = sac_train_shape_ok(cfg, layers, batch)) return rc;
+    if (const int32_t rc = sac_train_pointers_ok(cfg, layers, batch, x0, x1, (const void *const *)out, "out", true, nullptr, nullptr, false, false,
+                                                 scratch, scratch_bytes))
+        return rc;
+    DnSacTrainArgs a;
+    sac_train_args(a, cfg, layers, batch, x0, x1, scratch);
+    for (int c = 0; c < cfg->n_nets; ++c)
+        for (int p = 0; p < cfg->head_parts; ++p) a.out[c][p] = out[c * cfg->head_parts + p];
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_sac_train_forward(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_sac_train_backward(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, const float *x0, const float *x1,
+                              const float *const *d_out, int64_t batch, float *d_x0, float *d_x1, void *scratch, int64_t scratch_bytes,
+                              int32_t device_id, void *stream)
+{
+    if (const int32_t rc = sac_train_shape_ok(cfg, layers, batch)) return rc;
+    const bool grads = !(cfg->flags & DN_MLP_TRAIN_NO_PARAM_GRADS);
+    if (!grads && !d_x0 && !d_x1)
+        return fail(DN_ERR_INVALID_ARGUMENT, "d_x0 or d_x1 is required with DN_MLP_TRAIN_NO_PARAM_GRADS in flags (there is nothing else to do)");
+    if (d_x1 && cfg->in1 == 0) return fail(DN_ERR_INVALID_ARGUMENT, "d_x1 must be NULL when in1 = 0");
+    if (const int32_t rc = sac_train_pointers_ok(cfg, layers, batch, x0, x1, (const void *const *)d_out, "d_out", false, d_x0, d_x1, true, grads,
+                                                 scratch, scratch_bytes))
+        return rc;
+    DnSacTrainArgs a;
+    sac_train_args(a, cfg, layers, batch, x0, x1, scratch);
+    for (int c = 0; c < cfg->n_nets; ++c)
+        for (int p = 0; p < cfg->head_parts; ++p) a.d_out[c][p] = d_out[c * cfg->head_parts + p];
+    a.d_x0 = d_x0; a.d_x1 = d_x1;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_sac_train_backward(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_polyak_update(int32_t n_tensors, const float *const *source, float *const *target, const int64_t *counts, double tau,
+                         int32_t device_id, void *stream)
+{
+    if (n_tensors < 1 || n_tensors > DN_ADAM_MAX_TENSORS)
+        return fail(DN_ERR_INVALID_ARGUMENT, "n_tensors must be in 1..%d (got %d)", DN_ADAM_MAX_TENSORS, n_tensors);
+    if (!source) return fail(DN_ERR_INVALID_ARGUMENT, "source is required");
+    if (!target) return fail(DN_ERR_INVALID_ARGUMENT, "target is required");
+    if (!counts) return fail(DN_ERR_INVALID_ARGUMENT, "counts is required");
+    if (!(tau >= 0.0 && tau <= 1.0)) return fail(DN_ERR_INVALID_ARGUMENT, "tau must be in [0, 1] (got %g)", tau);
+    SacNamed names[2 * DN_ADAM_MAX_TENSORS];
+    DnArg in[DN_ADAM_MAX_TENSORS], out[DN_ADAM_MAX_TENSORS];
+    for (int i = 0; i < n_tensors; ++i) {
+        if (counts[i] < 1 || counts[i] > 0x7fffffffll)
+            return fail(DN_ERR_INVALID_ARGUMENT, "counts[%d] must be in 1..2^31 - 1 (got %lld)", i, (long long)counts[i]);
+        const uintptr_t bytes = (uintptr_t)counts[i] * sizeof(float);
+        in[i] = sac_named(names[2 * i], source[i], bytes, "source[%d]", i);
+        out[i] = sac_named(names[2 * i + 1], target[i], bytes, "target[%d]", i);
+    }
+    const size_t n = (size_t)n_tensors;
+    if (const DnArg *a = dn_first_missing(in, n)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_missing(out, n)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_misaligned(in, n, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    if (const DnArg *a = dn_first_misaligned(out, n, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    const DnArg *o, *i;
+    if (dn_first_overlap(out, n, in, n, &o, &i)) return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no target may alias a source", o->name, i->name);
+    for (size_t a = 0; a + 1 < n; ++a)
+        if (dn_first_overlap(&out[a], 1, &out[a + 1], n - a - 1, &o, &i))
+            return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: every target is a tensor of its own", o->name, i->name);
+    DnPolyakArgs a;
+    std::memset(&a, 0, sizeof a);
+    for (int k = 0; k < n_tensors; ++k) { a.source[k] = source[k]; a.target[k] = target[k]; a.count[k] = counts[k]; }
+    a.tau = tau; a.omt = 1.0 - tau; a.n_tensors = n_tensors;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_polyak(a, (hipStream_t)stream));
     return DN_OK;
 }
 

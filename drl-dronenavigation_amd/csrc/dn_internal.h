@@ -484,6 +484,48 @@ struct DnMlpTrainArgs {
 };
 hipError_t dn_launch_mlp_train_forward(const DnMlpTrainArgs &a, hipStream_t stream);                                           // dn_mlp_train.hip
 hipError_t dn_launch_mlp_train_backward(const DnMlpTrainArgs &a, hipStream_t stream);                                          // dn_mlp_train.hip
+// The training pass of the SAC networks (dn_sac_train_forward / _backward, dn_sac_train.hip): n_nets networks of one shape.  A network's
+// table entries are its hidden layers and then the parts of its head.  The scratch is n_nets consecutive blocks, network c at
+// c * per_net, each block the regions of dn_mlp_train_layout for one network whose layer 0 reads in0 + in1 columns and whose head is its
+// parts taken together: `one` holds a block's offsets.  The dimensions have passed the C ABI's checks.
+constexpr int DN_SAC_TRAIN_MAX_ENTRIES = DN_MLP_TRAIN_MAX_LAYERS - 1 + DN_SAC_TRAIN_MAX_PARTS;
+struct DnSacTrainLayout {
+    DnMlpTrainLayout one;
+    long long per_net, total;
+};
+inline DnSacTrainLayout dn_sac_train_layout(const dn_mlp_train_layer *net0, int n_nets, int n_layers, int head_parts, long long batch)
+{
+    dn_mlp_train_layer whole[DN_MLP_TRAIN_MAX_LAYERS] = {};
+    for (int l = 0; l < n_layers - 1; ++l) { whole[l].in_dim = net0[l].in_dim; whole[l].out_dim = net0[l].out_dim; }
+    whole[n_layers - 1].in_dim = net0[n_layers - 1].in_dim;
+    for (int p = 0; p < head_parts; ++p) whole[n_layers - 1].out_dim += net0[n_layers - 1 + p].out_dim;
+    DnSacTrainLayout lay = {};
+    lay.one = dn_mlp_train_layout(whole, n_layers, batch);
+    lay.per_net = lay.one.total;
+    lay.total = lay.per_net * n_nets;
+    return lay;
+}
+struct DnSacTrainArgs {
+    dn_mlp_train_layer layer[DN_SAC_TRAIN_MAX_NETS][DN_SAC_TRAIN_MAX_ENTRIES];
+    const float *x0, *x1;                              // x1 NULL with in1 = 0
+    const float *d_out[DN_SAC_TRAIN_MAX_NETS][DN_SAC_TRAIN_MAX_PARTS];       // backward only
+    float *out[DN_SAC_TRAIN_MAX_NETS][DN_SAC_TRAIN_MAX_PARTS];               // forward only
+    float *d_x0, *d_x1;                                // backward only, NULL = not wanted
+    char *scratch;
+    long long batch;
+    int n_nets, n_layers, head_parts, activation, in0, in1, flags;
+};
+hipError_t dn_launch_sac_train_forward(const DnSacTrainArgs &a, hipStream_t stream);                                           // dn_sac_train.hip
+hipError_t dn_launch_sac_train_backward(const DnSacTrainArgs &a, hipStream_t stream);                                          // dn_sac_train.hip
+// The Polyak update (dn_polyak_update, dn_sac_train.hip): one launch over a table that travels by value, grid y the tensor.
+struct DnPolyakArgs {
+    const float *source[DN_ADAM_MAX_TENSORS];
+    float *target[DN_ADAM_MAX_TENSORS];
+    long long count[DN_ADAM_MAX_TENSORS];
+    double tau, omt;                                   // omt = 1.0 - tau, formed on the host
+    int n_tensors;
+};
+hipError_t dn_launch_polyak(const DnPolyakArgs &a, hipStream_t stream);                                                        // dn_sac_train.hip
 hipError_t dn_launch_mlp_wide(const dn_mlp_net *nets, int num_nets, const float *obs, const uint8_t *row_mask, long long n, int obs_dim,
                               hipStream_t stream);                                                                             // dn_mlp_wide.hip
 hipError_t dn_launch_mlp_step(const DnParams &p, const DnStepIO &io, const dn_mlp_net *nets, int num_nets, const float *obs, int obs_dim,

@@ -1,6 +1,7 @@
 // dn_sac_math.h -- the per-element arithmetic of the SAC loss heads (dn_sac_policy, dn_sac_policy_backward, dn_sac_critic_loss,
 // dn_sac_actor_loss; include/dronenav.h states it line by line): plain C++ for host and device.  dn_sac_loss.hip runs it a row per lane;
-// tests/tools/check_sac_math.cpp runs the same code on the host.  Everything is IEEE float64 under -ffp-contract=off; exp, tanh and log are
+// tests/tools/check_sac_math.cpp runs the same code on the host.  The last function is the Polyak update's (dn_polyak_update,
+// dn_sac_train.hip; tests/tools/check_sac_train_layout.cpp).  Everything is IEEE float64 under -ffp-contract=off; exp, tanh and log are
 // the float64 library functions (no cancellation follows them), exp(log_ent_coef) is the correctly rounded one of dn_exp_cr.h.  NaN and
 // infinity are not special-cased.
 //
@@ -80,4 +81,13 @@ DN_SAC_FN double dn_sac_alpha(const double log_ent_coef)
 DN_SAC_FN double dn_sac_target(const double reward, const double done, const double gamma, const double nq, const double alpha, const double next_lp)
 {
     return reward + (1.0 - done) * gamma * (nq - alpha * next_lp);
+}
+
+// The Polyak update of one target element (dn_polyak_update): omt = 1.0 - tau is formed once on the host in float64; both float32 values
+// are widened, two float64 products and one float64 add (no contraction), rounded once to float32.
+DN_SAC_FN float dn_polyak(const float target, const float source, const double tau, const double omt)
+{
+    const double keep = omt * (double)target;
+    const double take = tau * (double)source;
+    return (float)(keep + take);
 }

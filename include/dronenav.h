@@ -1199,7 +1199,8 @@ int32_t dn_sac_actor_loss(const dn_sac_config *cfg, int64_t batch, const float *
  *   flags bit 0 (DN_MLP_TRAIN_ACCUMULATE): each finished float32 gradient is added to the tensor (one float32 add) instead of
  *   overwriting it.  Bit 1 (DN_MLP_TRAIN_NO_PARAM_GRADS): the backward forms d_x only; d_weight and d_bias are neither read nor
  *   written and may be NULL.  d_x is always overwritten.  The other bits and `reserved` must be 0; `activation` must be
- *   DN_MLP_ACT_TANH (the field exists so that ReLU can follow without a new layout).
+ *   DN_MLP_ACT_TANH: these three entry points take Tanh only.  ReLU, an input from two tensors, a head of two parts and several
+ *   networks a call are dn_sac_train_forward / dn_sac_train_backward below, on the same product kernel.
  * Arithmetic, float32 grade: every matrix product runs on v_mfma_f32_32x32x16_bf16 with BOTH operands split on the device, as they
  *   are staged, into two bfloat16 words hi = bf16(v), lo = bf16(v - hi), round to nearest even (csrc/dn_bf16_split.h); a product is
  *   the three MFMAs lo hi, hi lo, hi hi, in this order, into one float32 accumulator, K-steps of 16 in ascending order.  Bias add,
@@ -1226,6 +1227,7 @@ int32_t dn_sac_actor_loss(const dn_sac_config *cfg, int64_t batch, const float *
  *   dn_mlp_train_config n_layers at 0, activation at 4, flags at 8, reserved at 12; 16 bytes. */
 #define DN_MLP_TRAIN_MAX_LAYERS 4
 #define DN_MLP_ACT_TANH 0
+#define DN_MLP_ACT_RELU 1
 #define DN_MLP_TRAIN_ACCUMULATE 1
 #define DN_MLP_TRAIN_NO_PARAM_GRADS 2
 #define DN_MLP_TRAIN_CHUNK 1024
@@ -1252,6 +1254,80 @@ int32_t dn_mlp_train_forward(const dn_mlp_train_config *cfg, const dn_mlp_train_
 /* Every d_weight and d_bias, and d_x [batch][layers[0].in_dim] where it is not NULL, from d_out [batch][head out_dim]. */
 int32_t dn_mlp_train_backward(const dn_mlp_train_config *cfg, const dn_mlp_train_layer *layers, const float *x, const float *d_out,
                               int64_t batch, float *d_x, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
+/* The training pass of the SAC networks on the device, and the Polyak update of the target critics: what SB3's SAC.train [from recall]
+ * does between the replay minibatch, the loss heads above and the optimiser -- the actor (latent_pi with the heads mu | log_std), the
+ * critics over cat(obs, actions) and their targets.  The second, wider family on the product kernel of dn_mlp_train_*: everything that
+ * comment says of the arithmetic (v_mfma_f32_32x32x16_bf16, both operands split into bf16 hi + lo as they are staged, lo hi, hi lo,
+ * hi hi into one float32 accumulator, K-steps of 16 ascending), of the chunks of DN_MLP_TRAIN_CHUNK rows, of the float64 bias sums and of
+ * the merge holds here word for word, and a network that both families can express (Tanh, one network, one input tensor, a head of one
+ * part) gets the same bits from both.  What this family adds is addressing, and ReLU:
+ *   activation     DN_MLP_ACT_TANH or DN_MLP_ACT_RELU.  ReLU forward: h = z > 0 ? z : +0.  Backward: dZ = h > 0 ? dH : +0.0, read from
+ *                  the saved activation as torch's threshold_backward does.  A NaN pre-activation is outside the contract (it becomes +0).
+ *   x = (x0 | x1)  layer 0 reads x0 [batch][in0] and x1 [batch][in1] side by side, gathered as they are staged and never materialised:
+ *                  in0 1..64, in1 0..63, in0 + in1 <= 64 = layers[c][0].in_dim; x1 is NULL exactly when in1 = 0.  The input gradient
+ *                  leaves as d_x0 [batch][in0] and d_x1 [batch][in1]; either may be NULL (not wanted: its columns are not stored).
+ *   head parts     the head is head_parts = 1..2 linear layers over the last hidden layer (the actor's mu and log_std), read in place as
+ *                  the row blocks of one head: out_dim 1..32 each, at most 32 together.  Outputs and head gradients are one dense
+ *                  [batch][out_dim of the part] tensor a part.  The forward, the head's weight-gradient partials and dH of the last hidden
+ *                  layer run over the concatenated k / n in the order an undivided head has.
+ *   n_nets         1..4 networks of identical dimensions that share x (the twin critics), advanced by the same launches: a grid
+ *                  dimension is the network (network x chunk for the weight gradient), and the number of launches does not depend on
+ *                  n_nets.  Network c's outputs and gradients have the bits it gets alone.  d_x = sum over the networks of dZ0_c W0_c is
+ *                  ONE product [dZ0_0 | dZ0_1 | ...] against the stacked W0_c, K running over the networks in ascending order: K-steps
+ *                  of 16 over network 0's hidden units, then network 1's, into one accumulator.
+ * `layers` is a HOST array dn_mlp_train_layer[n_nets][n_layers - 1 + head_parts], network-major; a network's last head_parts entries
+ *   are the head's parts, each with in_dim = the last hidden width.  Hidden widths are multiples of 32 in 32..512, batch is 1..2^24.
+ *   `out` and `d_out` are HOST arrays of n_nets * head_parts device pointers, network-major.  flags: DN_MLP_TRAIN_ACCUMULATE and
+ *   DN_MLP_TRAIN_NO_PARAM_GRADS with the meaning above; with the latter at least one of d_x0, d_x1 is required.
+ * Bit-reproducible as above: no atomics, no workgroup waits for another, every output word written exactly once, row b of every
+ *   per-row output independent of the other rows and of batch, and the order of every addition a function of (n_nets, the dimensions,
+ *   batch) alone: within a product k ascends over the concatenated operand; the batch sums are per chunk and merged in ascending chunk
+ *   order in float64.
+ *   scratch        the caller's device memory, 16-byte aligned, at least dn_sac_train_scratch_bytes(cfg, layers, batch): n_nets
+ *                  consecutive blocks, network 0 first.  With r and C as above, in = in0 + in1 for layer 0 and the head taken as one layer
+ *                  of out_L = the sum of its parts, a block's regions are, in this order: h_l, r(4 batch out_l) per hidden layer; dZ_l,
+ *                  the same again per hidden layer; the d_weight partials, r(4 C out_l in_l) per layer; the d_bias partials,
+ *                  r(8 C out_l) per layer.
+ * Launches on `stream`, capturable: the forward one per layer; the backward one weight-gradient and one data-gradient launch per layer
+ *   (none for layer 0's data gradient without d_x0 and d_x1, no weight-gradient launches with DN_MLP_TRAIN_NO_PARAM_GRADS) and the merge.
+ *   No output may overlap an input or another output.
+ * dn_polyak_update: target_i <- (1 - tau) target_i + tau source_i over n_tensors = 1..DN_ADAM_MAX_TENSORS tensors of counts[i] >= 1
+ *   float32 elements, one launch.  source, target and counts are HOST arrays.  omt = 1.0 - tau is formed on the host in float64; an
+ *   element is (float)(omt * (double)t + tau * (double)s): two float64 products and one float64 add, no contraction, rounded once
+ *   (csrc/dn_sac_math.h dn_polyak, which host and device both compile).  That is the float64 statement, not the exact one: beside a
+ *   float32 tie (tau = 0.005 and t / 200 half an ulp of the result) it may be one float32 ulp from (1 - tau) t + tau s evaluated in a
+ *   wider format and rounded once.  tau is a host double in [0, 1]: a captured graph keeps it.
+ *   No target may overlap a source or another target.
+ * Validates before the first device call: DN_ERR_INVALID_ARGUMENT with a dn_last_error text that names the argument, layers[c][l].field
+ *   included.
+ * Layout of dn_sac_train_config: n_nets at 0, n_layers at 4, head_parts at 8, activation at 12, in0 at 16, in1 at 20, flags at 24,
+ *   reserved at 28; 32 bytes. */
+#define DN_SAC_TRAIN_MAX_NETS 4
+#define DN_SAC_TRAIN_MAX_PARTS 2
+typedef struct dn_sac_train_config {
+    int32_t n_nets;         /* 1..4 networks of identical dimensions sharing x */
+    int32_t n_layers;       /* 2..4 linear layers a network, the head counted once */
+    int32_t head_parts;     /* 1..2 */
+    int32_t activation;     /* DN_MLP_ACT_TANH or DN_MLP_ACT_RELU */
+    int32_t in0;            /* 1..64 */
+    int32_t in1;            /* 0..63, in0 + in1 <= 64 */
+    int32_t flags;          /* bit 0 = DN_MLP_TRAIN_ACCUMULATE, bit 1 = DN_MLP_TRAIN_NO_PARAM_GRADS */
+    int32_t reserved;       /* 0 */
+} dn_sac_train_config;
+/* Bytes of scratch (the formula above; only the dimensions of `layers` are read): host only, no HIP call.  A negative dn_status for a
+ * NULL argument, a configuration, dimension or chain the calls refuse, or batch outside 1..2^24. */
+int64_t dn_sac_train_scratch_bytes(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, int64_t batch);
+/* out[c * head_parts + p] [batch][out_dim of part p] from (x0 | x1); the hidden activations stay in scratch for the backward. */
+int32_t dn_sac_train_forward(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, const float *x0, const float *x1,
+                             int64_t batch, float *const *out, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+/* Every d_weight and d_bias, and d_x0, d_x1 where they are not NULL, from d_out[c * head_parts + p]; after a forward with the same
+ * config, layers, batch, x0, x1 and scratch. */
+int32_t dn_sac_train_backward(const dn_sac_train_config *cfg, const dn_mlp_train_layer *layers, const float *x0, const float *x1,
+                              const float *const *d_out, int64_t batch, float *d_x0, float *d_x1, void *scratch, int64_t scratch_bytes,
+                              int32_t device_id, void *stream);
+int32_t dn_polyak_update(int32_t n_tensors, const float *const *source, float *const *target, const int64_t *counts, double tau,
+                         int32_t device_id, void *stream);
 
 #ifdef __cplusplus
 }
