@@ -24,7 +24,7 @@ __all__ = ["DroneVecEnv", "Track", "TrackBank", "tracks", "gae", "DroneNavError"
            "PrivilegedObservation", "PRIV_DIM", "PRIV_GROUPS", "PRIV_SLICES",
            "GoalObservation", "GOAL_DIM", "GOAL_FRAMES", "GOAL_SLICES", "HistoryObservation", "RowNormalizer",
            "ReturnNormalizer", "MinibatchSampler", "PpoLoss", "ClippedAdam", "MlpTrainer", "ReplaySampler", "SacPolicyHead", "SacCriticLoss", "SacActorLoss",
-           "SacCritic", "SacTrainer", "PolyakUpdate"]
+           "SacCritic", "SacTrainer", "PolyakUpdate", "LstmTrainer", "LstmStepper"]
 
 
 def __getattr__(name):
@@ -67,6 +67,9 @@ def __getattr__(name):
     if name in ("sac_train", "SacTrainer", "PolyakUpdate"):
         sac_train = importlib.import_module(__name__ + ".sac_train")
         return sac_train if name == "sac_train" else getattr(sac_train, name)
+    if name in ("lstm_train", "LstmTrainer", "LstmStepper"):
+        lstm_train = importlib.import_module(__name__ + ".lstm_train")
+        return lstm_train if name == "lstm_train" else getattr(lstm_train, name)
     if name == "metrics":
         return importlib.import_module(__name__ + ".metrics")
     if name in ("policy", "MlpActorCritic", "SacActor", "SacCritic", "MlpValue"):

@@ -186,6 +186,19 @@ TRAIN_ACT_RELU = 1
 TRAIN_MAX_NETS, TRAIN_MAX_PARTS = 4, 2
 
 
+class DnLstmConfig(C.Structure):
+    _fields_ = [("in_dim", C.c_int32), ("hidden", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DnLstmParams(C.Structure):
+    _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p), ("d_w_ih", C.c_void_p),
+                ("d_w_hh", C.c_void_p), ("d_b_ih", C.c_void_p), ("d_b_hh", C.c_void_p)]
+
+
+# the bounds of dn_lstm_* as the header's comment states them (tests/test_lstm_cpu.py holds them to the refusals)
+RNN_MAX_IN, RNN_MAX_HIDDEN, RNN_MAX_STEPS, RNN_MAX_ROWS = 64, 512, 1024, 1 << 24
+
+
 class DnTrackBankConfig(C.Structure):
     _fields_ = [("num_tracks", C.c_int32), ("num_waypoints", C.c_int32 * MAX_TRACKS), ("waypoints", C.c_double * (MAX_WAYPOINTS * 3)),
                 ("weight", C.c_float * MAX_TRACKS), ("resample", C.c_int32), ("reserved", C.c_int32)]
@@ -260,6 +273,11 @@ PROTOTYPES = {
     "dn_sac_train_backward": (_I32, [C.POINTER(DnSacTrainConfig), C.POINTER(DnMlpTrainLayer), _VP, _VP, C.POINTER(_VP), _I64, _VP, _VP, _VP, _I64,
                                      _I32, _VP]),
     "dn_polyak_update": (_I32, [_I32, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I64), C.c_double, _I32, _VP]),
+    "dn_lstm_scratch_bytes": (_I64, [C.POINTER(DnLstmConfig), _I64, _I64]),
+    "dn_lstm_forward": (_I32, [C.POINTER(DnLstmConfig), C.POINTER(DnLstmParams), _VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _I32,
+                               _VP]),
+    "dn_lstm_backward": (_I32, [C.POINTER(DnLstmConfig), C.POINTER(DnLstmParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I32,
+                                _VP]),
     "dn_set_launch_events":(_I32, [_VP, _VP, _VP]),
     "dn_state_bytes": (_I64, [_I64, _I32]),
     "dn_enable_dynamics": (_I32, [_VP, C.POINTER(DnDynamicsConfig)]),

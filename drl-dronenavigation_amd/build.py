@@ -15,10 +15,10 @@ LIB_PATH = os.path.join(CSRC, "libdronenav.so")
 # run-time switch it costs the fused kernels ~100 spilled registers); DN_EXACT_NORM=1 makes _capi.load() take this library.
 LIB_PATH_EXACT = os.path.join(CSRC, "libdronenav_exact.so")
 SOURCES = ["dn_kernels.hip", "dn_kernels_mw.hip", "dn_glue.hip", "dn_mlp.hip", "dn_mlp_wide.hip", "dn_fused.hip", "dn_history.hip", "dn_rownorm.hip", "dn_retnorm.hip",
-           "dn_minibatch.hip", "dn_ppo_loss.hip", "dn_adam.hip", "dn_replay.hip", "dn_sac_loss.hip", "dn_mlp_train.hip", "dn_sac_train.hip", "dn_capi.cpp",
+           "dn_minibatch.hip", "dn_ppo_loss.hip", "dn_adam.hip", "dn_replay.hip", "dn_sac_loss.hip", "dn_mlp_train.hip", "dn_sac_train.hip", "dn_lstm.hip", "dn_capi.cpp",
            "dn_capi_envfree.cpp"]
 STEP_SOURCES = ["dn_kernels.hip", "dn_kernels_mw.hip", "dn_fused.hip"]      # the translation units that inline the normaliser
-HEADERS = ["dn_internal.h", "dn_capi_fail.h", "dn_argcheck.h", "dn_shapes.h", "dn_second_moment.h", "dn_role_place.h", "dn_action_sat.h", "dn_action_chain.h", "dn_philox.h", "dn_policy_draw.h", "dn_fleet_rms.h", "dn_row_sums.h", "dn_permute.h", "dn_replay_draw.h", "dn_exp_cr.h", "dn_sac_math.h", "dn_bf16_split.h", "dn_mt_gemm.h", os.path.join("..", "..", "include", "dronenav.h")]
+HEADERS = ["dn_internal.h", "dn_capi_fail.h", "dn_argcheck.h", "dn_shapes.h", "dn_second_moment.h", "dn_role_place.h", "dn_action_sat.h", "dn_action_chain.h", "dn_philox.h", "dn_policy_draw.h", "dn_fleet_rms.h", "dn_row_sums.h", "dn_permute.h", "dn_replay_draw.h", "dn_exp_cr.h", "dn_sac_math.h", "dn_bf16_split.h", "dn_mt_gemm.h", "dn_lstm_cell.h", os.path.join("..", "..", "include", "dronenav.h")]
 # -ffp-contract=off: no multiply-add is fused BY LICENCE -- the float32 action chain rounds every operation as numpy does, and the
 # float64 part writes its fused multiply-adds out explicitly so that every kernel shape produces the same bits.
 # Correctly rounded float32 divide/sqrt is hipcc's default; stated explicitly because parity relies on it.

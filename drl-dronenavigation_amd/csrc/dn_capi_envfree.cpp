@@ -1,6 +1,6 @@
 // dn_capi_envfree.cpp -- the entry points of include/dronenav.h that take a device_id and no dn_env: the rollout glue, the history rows,
 // the two fleet normalisers, the minibatches, the PPO loss, the optimiser step, the replay minibatches, the SAC loss heads, the
-// training passes of the Tanh and of the SAC networks and the Polyak update.
+// training passes of the Tanh and of the SAC networks, the Polyak update and the LSTM layer.
 //
 // Every entry point validates its arguments, turns HIP failures into dn_status codes + the thread-local message of dn_capi.cpp
 // (dn_capi_fail.h), and never falls back to a CPU implementation.
@@ -1096,6 +1096,137 @@ int32_t dn_polyak_update(int32_t n_tensors, const float *const *source, float *c
     a.tau = tau; a.omt = 1.0 - tau; a.n_tensors = n_tensors;
     DN_HIP(hipSetDevice(device_id));
     DN_HIP(dn_launch_polyak(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+}  // extern "C"
+
+// ---- dn_lstm: one LSTM layer, the training pass over a sequence and (T = 1) the rollout step -------------------------------------------------
+/* what the three entry points ask of cfg, T and B */
+static int32_t lstm_shape_ok(const dn_lstm_config *cfg, int64_t T, int64_t B)
+{
+    if (!cfg) return fail(DN_ERR_INVALID_ARGUMENT, "cfg is required");
+    if (cfg->in_dim < 1 || cfg->in_dim > 64) return fail(DN_ERR_INVALID_ARGUMENT, "in_dim must be in 1..64 (got %d)", cfg->in_dim);
+    if (cfg->hidden < 32 || cfg->hidden > 512 || cfg->hidden % 32)
+        return fail(DN_ERR_INVALID_ARGUMENT, "hidden must be a multiple of 32 in 32..512 (got %d)", cfg->hidden);
+    if (cfg->flags & ~(DN_MLP_TRAIN_ACCUMULATE | DN_MLP_TRAIN_NO_PARAM_GRADS))
+        return fail(DN_ERR_INVALID_ARGUMENT, "flags has unknown bits: 0x%x (bit 0 accumulates, bit 1 skips the parameter gradients)", cfg->flags);
+    if (const int32_t rc = reserved_ok(cfg->reserved)) return rc;
+    if (T < 1 || T > DN_LSTM_MAX_STEPS) return fail(DN_ERR_INVALID_ARGUMENT, "T must be in 1..%d (got %lld)", DN_LSTM_MAX_STEPS, (long long)T);
+    if (B < 1 || B > (1ll << 24)) return fail(DN_ERR_INVALID_ARGUMENT, "B must be in 1..2^24 (got %lld)", (long long)B);
+    if (T * B > (1ll << 24)) return fail(DN_ERR_INVALID_ARGUMENT, "T x B must be <= 2^24 rows (got %lld x %lld)", (long long)T, (long long)B);
+    return DN_OK;
+}
+
+/* the pointers of a call: required, aligned, the scratch large enough, no output on an input or on another output.  in[LSTM_IN_STARTS]
+ * is episode_starts in both calls, bytes that need no alignment; the scratch is the last output, its bytes what the call needs.  `same`:
+ * pairs (index into out, index into in) that may be one tensor -- the same address, not a partial overlap. */
+constexpr size_t LSTM_IN_STARTS = 1;
+static int32_t lstm_pointers_ok(const DnArg *in, size_t ni, const DnArg *out, size_t no, int64_t scratch_bytes, const size_t (*same)[2],
+                                size_t n_same)
+{
+    if (const DnArg *a = dn_first_missing(in, ni)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    if (const DnArg *a = dn_first_missing(out, no)) return fail(DN_ERR_INVALID_ARGUMENT, "%s is required", a->name);
+    const DnArg &scratch = out[no - 1];
+    if (dn_scratch_short(scratch_bytes, (int64_t)scratch.bytes)) return scratch_too_small(scratch_bytes, (int64_t)scratch.bytes, "dn_lstm_scratch_bytes");
+    if ((uintptr_t)scratch.p & 15u) return fail(DN_ERR_INVALID_ARGUMENT, "scratch must be 16-byte aligned");
+    for (size_t i = 0; i < ni; ++i)
+        if (i != LSTM_IN_STARTS && ((uintptr_t)in[i].p & 3u))
+            return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", in[i].name);
+    if (const DnArg *a = dn_first_misaligned(out, no, 3u)) return fail(DN_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", a->name);
+    for (size_t o = 0; o < no; ++o)
+        for (size_t i = 0; i < ni; ++i) {
+            if (!dn_ranges_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) continue;
+            bool allowed = false;
+            for (size_t s = 0; s < n_same; ++s)
+                allowed = allowed || (out[o].p == in[i].p && o == same[s][0] && i == same[s][1]);
+            if (!allowed)
+                return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: no output may alias an input (h_T may be h0 itself, c_T c0 itself)", out[o].name,
+                            in[i].name);
+        }
+    const DnArg *o, *i;
+    for (size_t a = 0; a + 1 < no; ++a)
+        if (dn_first_overlap(&out[a], 1, &out[a + 1], no - a - 1, &o, &i))
+            return fail(DN_ERR_INVALID_ARGUMENT, "%s overlaps %s: every output is a tensor of its own", o->name, i->name);
+    return DN_OK;
+}
+
+static void lstm_args(DnLstmArgs &a, const dn_lstm_config *cfg, const dn_lstm_params *p, const float *x, const uint8_t *episode_starts,
+                      int64_t T, int64_t B, void *scratch)
+{
+    std::memset(&a, 0, sizeof a);
+    a.w_ih = p->w_ih; a.w_hh = p->w_hh; a.b_ih = p->b_ih; a.b_hh = p->b_hh;
+    a.d_w_ih = p->d_w_ih; a.d_w_hh = p->d_w_hh; a.d_b_ih = p->d_b_ih; a.d_b_hh = p->d_b_hh;
+    a.x = x; a.episode_starts = episode_starts;
+    a.scratch = (char *)scratch;
+    a.T = T; a.B = B;
+    a.in_dim = cfg->in_dim; a.hidden = cfg->hidden; a.flags = cfg->flags;
+}
+
+extern "C" {
+
+int64_t dn_lstm_scratch_bytes(const dn_lstm_config *cfg, int64_t T, int64_t B)
+{
+    if (const int32_t rc = lstm_shape_ok(cfg, T, B)) return rc;
+    return dn_lstm_layout(cfg->in_dim, cfg->hidden, T, B).total;
+}
+
+int32_t dn_lstm_forward(const dn_lstm_config *cfg, const dn_lstm_params *params, const float *x, const uint8_t *episode_starts,
+                        const float *h0, const float *c0, int64_t T, int64_t B, float *h_seq, float *c_seq, float *h_T, float *c_T,
+                        void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (const int32_t rc = lstm_shape_ok(cfg, T, B)) return rc;
+    if (!params) return fail(DN_ERR_INVALID_ARGUMENT, "params is required");
+    const uintptr_t I = (uintptr_t)cfg->in_dim, H = (uintptr_t)cfg->hidden, f = sizeof(float), rows = (uintptr_t)(T * B);
+    const DnLstmLayout lay = dn_lstm_layout(cfg->in_dim, cfg->hidden, T, B);
+    const DnArg in[] = {{"x", x, rows * I * f, false}, {"episode_starts", episode_starts, rows, true}, {"h0", h0, (uintptr_t)B * H * f, false},
+                        {"c0", c0, (uintptr_t)B * H * f, false}, {"params.w_ih", params->w_ih, 4 * H * I * f, false},
+                        {"params.w_hh", params->w_hh, 4 * H * H * f, false}, {"params.b_ih", params->b_ih, 4 * H * f, false},
+                        {"params.b_hh", params->b_hh, 4 * H * f, false}};
+    // the forward keeps the activated gates and nothing else: the first region of the scratch is all it asks for
+    const DnArg out[] = {{"h_seq", h_seq, rows * H * f, false}, {"c_seq", c_seq, rows * H * f, false}, {"h_T", h_T, (uintptr_t)B * H * f, false},
+                         {"c_T", c_T, (uintptr_t)B * H * f, false}, {"scratch", scratch, (uintptr_t)lay.carry_h, false}};
+    static const size_t same[][2] = {{2, 2}, {3, 3}};   // (h_T, h0) and (c_T, c0), by their places in out and in
+    if (const int32_t rc = lstm_pointers_ok(in, 8, out, 5, scratch_bytes, same, 2)) return rc;
+    DnLstmArgs a;
+    lstm_args(a, cfg, params, x, episode_starts, T, B, scratch);
+    a.h0 = h0; a.c0 = c0; a.h_seq = h_seq; a.c_seq = c_seq; a.h_T = h_T; a.c_T = c_T;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_lstm_forward(a, (hipStream_t)stream));
+    return DN_OK;
+}
+
+int32_t dn_lstm_backward(const dn_lstm_config *cfg, const dn_lstm_params *params, const float *x, const uint8_t *episode_starts,
+                         const float *h0, const float *h_seq, const float *c_seq, const float *c0, const float *d_hseq, int64_t T, int64_t B,
+                         float *d_x, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream)
+{
+    if (const int32_t rc = lstm_shape_ok(cfg, T, B)) return rc;
+    if (!params) return fail(DN_ERR_INVALID_ARGUMENT, "params is required");
+    const bool grads = !(cfg->flags & DN_MLP_TRAIN_NO_PARAM_GRADS);
+    if (!grads && !d_x)
+        return fail(DN_ERR_INVALID_ARGUMENT, "d_x is required with DN_MLP_TRAIN_NO_PARAM_GRADS in flags (there is nothing else to do)");
+    const uintptr_t I = (uintptr_t)cfg->in_dim, H = (uintptr_t)cfg->hidden, f = sizeof(float), rows = (uintptr_t)(T * B);
+    const DnLstmLayout lay = dn_lstm_layout(cfg->in_dim, cfg->hidden, T, B);
+    const DnArg in[] = {{"x", x, rows * I * f, false}, {"episode_starts", episode_starts, rows, true}, {"h0", h0, (uintptr_t)B * H * f, false},
+                        {"h_seq", h_seq, rows * H * f, false}, {"c_seq", c_seq, rows * H * f, false}, {"c0", c0, (uintptr_t)B * H * f, false},
+                        {"d_hseq", d_hseq, rows * H * f, false}, {"params.w_ih", params->w_ih, 4 * H * I * f, false},
+                        {"params.w_hh", params->w_hh, 4 * H * H * f, false}};
+    DnArg outs[6];
+    size_t no = 0;
+    outs[no++] = DnArg{"d_x", d_x, rows * I * f, true};
+    if (grads) {                                       // with DN_MLP_TRAIN_NO_PARAM_GRADS the gradient tensors are neither read nor written
+        outs[no++] = DnArg{"params.d_w_ih", params->d_w_ih, 4 * H * I * f, false};
+        outs[no++] = DnArg{"params.d_w_hh", params->d_w_hh, 4 * H * H * f, false};
+        outs[no++] = DnArg{"params.d_b_ih", params->d_b_ih, 4 * H * f, false};
+        outs[no++] = DnArg{"params.d_b_hh", params->d_b_hh, 4 * H * f, false};
+    }
+    outs[no++] = DnArg{"scratch", scratch, (uintptr_t)lay.total, false};
+    if (const int32_t rc = lstm_pointers_ok(in, 9, outs, no, scratch_bytes, nullptr, 0)) return rc;
+    DnLstmArgs a;
+    lstm_args(a, cfg, params, x, episode_starts, T, B, scratch);
+    a.h0 = h0; a.c0 = c0; a.h_seq = const_cast<float *>(h_seq); a.c_seq = const_cast<float *>(c_seq); a.d_hseq = d_hseq; a.d_x = d_x;
+    DN_HIP(hipSetDevice(device_id));
+    DN_HIP(dn_launch_lstm_backward(a, (hipStream_t)stream));
     return DN_OK;
 }
 

@@ -537,4 +537,61 @@ hipError_t dn_launch_stream_copy(void *dst, const void *src, long long n16, int 
 hipError_t dn_launch_compact(const unsigned long long *mask, long long n, int32_t *indices, int32_t *count,
                              hipStream_t stream);   // dn_glue.hip
 
+// The LSTM layer (dn_lstm_forward / _backward, dn_lstm.hip).  The scratch regions of the header as byte offsets: the activated gates
+// [T][B][4H] (the backward writes dZ over them), the two carries of the backward [B][H], the weight-gradient partials
+// [chunks][4H][I + H] and the float64 bias partials [chunks][4H].  The forward uses the gates alone: the offset carry_h is the bytes it asks for.
+// The dimensions have passed the C ABI's checks: I <= 64, H <= 512, T B <= 2^24, so no product here comes near 2^63.
+#ifdef __HIP__
+#define DN_LSTM_FN __host__ __device__ inline
+#else
+#define DN_LSTM_FN inline
+#endif
+constexpr int DN_LSTM_MAX_STEPS = 1024;
+struct DnLstmLayout {
+    long long gates, carry_h, carry_c, wpart, bpart;
+    long long chunks, total;
+};
+inline DnLstmLayout dn_lstm_layout(int in_dim, int hidden, long long T, long long B)
+{
+    const auto r = [](long long b) { return (b + 255) / 256 * 256; };
+    DnLstmLayout lay = {};
+    lay.chunks = dn_mlp_train_chunks(T * B);
+    long long at = 0;
+    lay.gates = at; at += r(16 * T * B * hidden);
+    lay.carry_h = at; at += r(4 * B * hidden);
+    lay.carry_c = at; at += r(4 * B * hidden);
+    lay.wpart = at; at += r(16 * lay.chunks * hidden * (in_dim + hidden));
+    lay.bpart = at; at += r(32 * lay.chunks * hidden);
+    lay.total = at;
+    return lay;
+}
+// Where row t B + b of hprev, the recurrent input of step t, comes from: nowhere (+0.0) where the row's episode starts at t, else row b
+// of h0 at t = 0 and row (t - 1) B + b of h_seq later.  c_prev follows the same rule with c0 and c_seq.
+enum { DN_LSTM_PREV_NONE = 0, DN_LSTM_PREV_INITIAL = 1, DN_LSTM_PREV_SEQ = 2 };
+struct DnLstmPrev {
+    int source;
+    long long row;
+};
+DN_LSTM_FN DnLstmPrev dn_lstm_prev(long long row, long long B, int episode_start)
+{
+    if (episode_start) return DnLstmPrev{DN_LSTM_PREV_NONE, 0};
+    return row < B ? DnLstmPrev{DN_LSTM_PREV_INITIAL, row} : DnLstmPrev{DN_LSTM_PREV_SEQ, row - B};
+}
+#undef DN_LSTM_FN
+struct DnLstmArgs {
+    const float *w_ih, *w_hh, *b_ih, *b_hh;
+    float *d_w_ih, *d_w_hh, *d_b_ih, *d_b_hh;          // backward only
+    const float *x, *h0, *c0;
+    const uint8_t *episode_starts;                     // [T][B], NULL = no episode starts inside the sequence
+    float *h_seq, *c_seq;                              // written by the forward, read by the backward
+    float *h_T, *c_T;                                  // forward only; may be h0 and c0
+    const float *d_hseq;                               // backward only
+    float *d_x;                                        // backward only, NULL = not wanted
+    char *scratch;
+    long long T, B;
+    int in_dim, hidden, flags;
+};
+hipError_t dn_launch_lstm_forward(const DnLstmArgs &a, hipStream_t stream);                                                    // dn_lstm.hip
+hipError_t dn_launch_lstm_backward(const DnLstmArgs &a, hipStream_t stream);                                                   // dn_lstm.hip
+
 #endif

@@ -1329,6 +1329,83 @@ int32_t dn_sac_train_backward(const dn_sac_train_config *cfg, const dn_mlp_train
 int32_t dn_polyak_update(int32_t n_tensors, const float *const *source, float *const *target, const int64_t *counts, double tau,
                          int32_t device_id, void *stream);
 
+/* One LSTM layer on the device with torch.nn.LSTM semantics -- num_layers = 1, unidirectional, bias = True, proj_size = 0, time-major:
+ * the recurrent policy of the reference's fourth learner (sb3_contrib RecurrentPPO, MlpLstmPolicy [from recall]).  dn_lstm_forward over a
+ * sequence saves what dn_lstm_backward needs; with T = 1 and h_T = h0, c_T = c0 it is the rollout step that updates a resident state in
+ * place.  Env-free; the third family on the product kernel of dn_mlp_train_*: what that comment says of the arithmetic
+ * (v_mfma_f32_32x32x16_bf16, both operands split into bf16 hi + lo as they are staged, lo hi, hi lo, hi hi into one float32 accumulator,
+ * K-steps of 16 ascending), of the chunks of DN_MLP_TRAIN_CHUNK rows, of the float64 bias sums and of the merge holds here word for word.
+ * The layer: in_dim I = 1..64 (any value), hidden H a multiple of 32 in 32..512.  The parameters are torch's tensors, float32, dense, read
+ *   in place: weight_ih_l0 [4H][I], weight_hh_l0 [4H][H], bias_ih_l0 [4H], bias_hh_l0 [4H], the gate rows in torch's order i, f, g, o.
+ *   T = 1..1024 steps, B = 1..2^24 rows a step, T B <= 2^24.  x is [T][B][I]; episode_starts is uint8 [T][B] or NULL (no starts).
+ * Forward, step t = 0..T-1, row b: sb3_contrib's _process_sequence [from recall] multiplies both states by 1 - episode_start.
+ *     keep = episode_starts is NULL or episode_starts[t][b] == 0
+ *     hp = keep ? h_{t-1}[b] : +0.0, cp = keep ? c_{t-1}[b] : +0.0, with h_{-1} = h0, c_{-1} = c0 [B][H]
+ *     z[n] = sum over k of (x_t[b] | hp)[k] (W_ih | W_hh)[n][k] + (b_ih[n] + b_hh[n])     k ascends over the I columns of x, then the H of hp;
+ *                                                  the bias pair is one float32 add, adding it to the accumulator one more
+ *     i = sig(z[j]), f = sig(z[H + j]), g = tanh(z[2H + j]), o = sig(z[3H + j])
+ *                                                  sig(z) = 1 / (1 + 2^(-log2(e) z)), tanh as dn_mlp_train_*: v_exp_f32, v_rcp_f32
+ *     c_t = f cp + i g;  h_t = o tanh(c_t)          float32, no contraction
+ *   Outputs: h_seq, c_seq [T][B][H] (the backward reads both) and h_T, c_T [B][H], the last step's.  h_T may be the tensor h0 and c_T
+ *   the tensor c0 (the same address): step 0 alone reads h0 and c0, step t > 0 reads h_seq[t - 1] and c_seq[t - 1], and h_T, c_T are
+ *   written by the last step after both were read.  The activated gates stay in scratch as float32 [T][B][4H].
+ * Backward, t = T-1..0, from d_hseq [T][B][H]; the two carries start at zero.  It must follow a forward with the same config, params, T,
+ *   B, x, episode_starts, h0, c0, h_seq, c_seq and scratch (the caller's business), and it consumes the saved gates: dZ is written over
+ *   them, so a second backward without a forward in between is the caller's error.  It reads h0 and c0 again (row 0 .. B-1 of hprev
+ *   and of cp), so they must still hold what the forward read: a forward whose h_T was h0 or whose c_T was c0 has overwritten
+ *   them and cannot be followed by a backward.  The in-place pair is for the forward-only rollout step.
+ *     dh = d_hseq[t][b] + carry_h;  tc = tanh(c_seq[t][b]);  dc = carry_c + dh o (1 - tc tc)
+ *     dz_i = dc g i (1 - i), dz_f = dc cp f (1 - f), dz_g = dc i (1 - g g), dz_o = dh tc o (1 - o)     products left to right
+ *     carry_c = keep ? dc f : +0.0;  carry_h = keep ? (dZ_t W_hh)[b] : +0.0     one product a step with K = 4H, the mask in its epilogue
+ *   and after the loop: d_x [T][B][I] = dZ W_ih as one product over all T B rows, where d_x is not NULL; d_w_ih = dZ^T x and
+ *   d_w_hh = dZ^T hprev as one weight-gradient product over the T B rows against the column blocks (x | hprev), row t B + b of hprev
+ *   being keep ? (t ? h_seq[t - 1][b] : h0[b]) : +0.0, addressed as it is staged and never materialised.  The chunks are
+ *   DN_MLP_TRAIN_CHUNK consecutive rows of the T B and may straddle steps.  d_b_ih and d_b_hh both receive the column sums of dZ.
+ *   Gradients with respect to h0, c0, h_T and c_T are not formed.
+ *   flags: DN_MLP_TRAIN_ACCUMULATE and DN_MLP_TRAIN_NO_PARAM_GRADS with the meaning above (with the latter d_x is required and the four
+ *   gradient tensors are neither read nor written and may be NULL); the other bits and `reserved` must be 0.
+ * Bit-reproducible as above: no atomics, no workgroup waits for another, row b of every per-row output independent of the other rows
+ *   and of B, and a sequence of T steps gives the bits of T calls with T = 1 that chain the state.
+ *   scratch        the caller's device memory, 16-byte aligned.  With r(b) = b rounded up to a multiple of 256 and
+ *                  C = ceil(T B / DN_MLP_TRAIN_CHUNK) its regions are, in this order: the gates, r(16 T B H) bytes; carry_h and carry_c,
+ *                  r(4 B H) each; the weight-gradient partials [C][4H][I + H], r(16 C H (I + H)); the float64 bias partials [C][4H],
+ *                  r(32 C H).  dn_lstm_backward asks for all of it, dn_lstm_scratch_bytes(cfg, T, B); dn_lstm_forward for the gates
+ *                  alone, r(16 T B H), so a rollout step holds no gradient scratch.
+ * Launches on `stream`, capturable: the forward two a step (the product, then the cell); the backward two a step (the cell, then the
+ *   product; none for step 0's), one for d_x where it is wanted, and the weight gradient with its merge without bit 1.  Every output
+ *   word is written exactly once by a vector store (read once and written once with bit 0).  No output (h_seq, c_seq, h_T, c_T; d_x and
+ *   the gradient tensors; scratch) may overlap an input or another output, except that h_T may be h0 itself and c_T c0 itself.
+ * Validates before the first device call: DN_ERR_INVALID_ARGUMENT with a dn_last_error text that names the argument.
+ * Layouts: dn_lstm_config in_dim at 0, hidden at 4, flags at 8, reserved at 12; 16 bytes.
+ *   dn_lstm_params w_ih at 0, w_hh at 8, b_ih at 16, b_hh at 24, d_w_ih at 32, d_w_hh at 40, d_b_ih at 48, d_b_hh at 56; 64 bytes. */
+typedef struct dn_lstm_config {
+    int32_t in_dim;         /* I: 1..64 */
+    int32_t hidden;         /* H: a multiple of 32 in 32..512 */
+    int32_t flags;          /* bit 0 = DN_MLP_TRAIN_ACCUMULATE, bit 1 = DN_MLP_TRAIN_NO_PARAM_GRADS */
+    int32_t reserved;       /* 0 */
+} dn_lstm_config;
+typedef struct dn_lstm_params {
+    const float *w_ih;      /* device float32 [4H][I], torch's weight_ih_l0, read in place */
+    const float *w_hh;      /* device float32 [4H][H], weight_hh_l0 */
+    const float *b_ih;      /* device float32 [4H], bias_ih_l0; not read by dn_lstm_backward */
+    const float *b_hh;      /* device float32 [4H], bias_hh_l0; as b_ih */
+    float *d_w_ih;          /* device float32 [4H][I]; may be NULL for dn_lstm_forward and with bit 1 */
+    float *d_w_hh;          /* device float32 [4H][H]; as d_w_ih */
+    float *d_b_ih;          /* device float32 [4H]; as d_w_ih */
+    float *d_b_hh;          /* device float32 [4H]; as d_w_ih; receives the value d_b_ih does */
+} dn_lstm_params;
+/* Bytes of scratch for the backward of T steps of B rows (the formula above): host only, no HIP call.  A negative dn_status for a NULL
+ * cfg, a dimension the calls refuse, or T, B or T B out of range. */
+int64_t dn_lstm_scratch_bytes(const dn_lstm_config *cfg, int64_t T, int64_t B);
+/* h_seq, c_seq [T][B][H] and h_T, c_T [B][H] from x [T][B][I], episode_starts [T][B] or NULL, h0 and c0 [B][H]. */
+int32_t dn_lstm_forward(const dn_lstm_config *cfg, const dn_lstm_params *params, const float *x, const uint8_t *episode_starts,
+                        const float *h0, const float *c0, int64_t T, int64_t B, float *h_seq, float *c_seq, float *h_T, float *c_T,
+                        void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+/* The four gradient tensors, and d_x [T][B][I] where it is not NULL, from d_hseq [T][B][H]; after the forward, once. */
+int32_t dn_lstm_backward(const dn_lstm_config *cfg, const dn_lstm_params *params, const float *x, const uint8_t *episode_starts,
+                         const float *h0, const float *h_seq, const float *c_seq, const float *c0, const float *d_hseq, int64_t T,
+                         int64_t B, float *d_x, void *scratch, int64_t scratch_bytes, int32_t device_id, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
